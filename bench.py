@@ -11,9 +11,12 @@ A "step" is one y = A*x over the whole matrix with the matrix, x and y already r
 
 Headline workload: 'nlpkkt240' (config 5 of BASELINE.json: 28.0 M rows, ~770 M non-zeros, fp64) — the largest
 single-GPU configuration, the one the multi-GPU target is quoted on, and far larger than the 256 MiB Infinity Cache,
-so its algorithmic GB/s is real HBM traffic. At N = 1 the same run also times configs 1-4 (cant, scircuit, pwtk fp32,
-soc-LiveJournal1) with the kernel BASELINE.json NAMES for them and with the engine's best kernel, and reports them
-under "configs" — so the driver-run record carries all five fractions.
+so its algorithmic GB/s is real HBM traffic. A plain run times the headline handle and nothing else. With --full the same
+run also checks sampled rows of y against host dot products, times the floor / jitter legs of the headline and a CPU
+baseline, and at N = 1 times configs 1-4 (cant, scircuit, pwtk fp32, soc-LiveJournal1) with the kernel BASELINE.json NAMES
+for them and with the engine's best kernel, reported under "configs" — so a --full record carries all five fractions.
+--dump-outputs DIR writes y of the last timed step as DIR/y.npy (the whole vector, or a fixed seeded sample of rows when it
+holds more than DUMP_MAX_VALUES values); the inputs depend only on the arguments.
 The matrices are synthetic twins (no SuiteSparse file exists in the reference tree and there is no network; a real
 file under $SPMV_MTX_DIR/<name>.mtx is loaded through the product's own Matrix-Market reader instead).
 
@@ -34,7 +37,7 @@ also moves a matrix array the driver laid across two regions (csrc/placement.hip
 profiles/r02_placement.md, profiles/r03_placement_walk.txt; what the walk found is reported as "placement")
 -> W warm-up launches -> settle (batches until two agree within 0.5 %, >= 500 launches; the reference driver warms GPU kernels
 with 1000 calls) -> EXACTLY K timed launches between HIP events, inside a synchronize bracket (K = 1000 by default: 1.2 s of the
-headline kernel; with K < 200 five such windows are timed and the median one is reported with the spread).
+headline kernel; with --full and K < 200 five such windows are timed and the median one is reported with the spread).
 """
 import argparse
 import hashlib
@@ -74,6 +77,9 @@ ALSO_KERNELS = {"soc-LiveJournal1": [("csr_merge", {"col_blocks": -1})], "scircu
 SMALL_CONFIGS = ("cant", "scircuit", "pwtk", "soc-LiveJournal1")
 # the two banded FEM twins also get a symmetric-storage leg
 SYMMETRIC_CONFIGS = ("cant", "pwtk")
+# --dump-outputs: y is written whole up to this many values (32 MiB of fp64), else as this many seeded rows of it
+DUMP_MAX_VALUES = 4 << 20
+DUMP_SEED = 20
 
 
 def parse(argv=None):
@@ -102,8 +108,13 @@ def parse(argv=None):
     ap.add_argument("--index-modes-off", type=int, default=0,
                     help="SELL delta layout, sensitivity experiment: 1 = no affine slices, 2 = no per-slice lane offsets, 3 = neither "
                          "(every slice stores 8/16-bit deltas per lane); invalid as the headline")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the sampled-row check, the floor / jitter legs, the CPU baseline and configs 1-4 "
+                         "(what --configs, --configs-steps, --no-cpu-baseline, --cpu-baseline-seconds and --headline-only govern)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: write y of the last timed step to DIR/y.npy (a fixed seeded sample of rows when y is large)")
     ap.add_argument("--configs", default="auto", choices=["auto", "on", "off"],
-                    help="time configs 1-4 (named + best kernel) after the headline; auto = on for the default headline at N = 1")
+                    help="--full: time configs 1-4 (named + best kernel) after the headline; auto = on for the default headline at N = 1")
     ap.add_argument("--configs-steps", type=int, default=300)
     ap.add_argument("--overlap", type=int, default=1, help="N>1: overlap the x exchange with the rows/columns that need no remote x")
     ap.add_argument("--exchange", default="auto", choices=["auto", "allgather", "p2p"],
@@ -132,13 +143,16 @@ def parse(argv=None):
                          "walk returned in the background; the settle phase runs through it; profiles/r02_placement.md §6)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--headline-only", action="store_true",
-                    help="only the headline handle: no floor / jitter legs, no configs 1-4 (the profiled command of tools/gpu_profiles.sh: every launch of "
-                         "the headline kernel the profiler then sees is this handle's, so its average can be held against roofline.kernel_ms)")
+                    help="--full: only the headline handle: no floor / jitter legs, no configs 1-4 (every launch of the headline kernel a "
+                         "profiler then sees is this handle's, so its average can be held against roofline.kernel_ms)")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=8.0)
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N>1 (nccl = RCCL)")
     ap.add_argument("--force-multi", action="store_true",
                     help="run the N>1 code path with whatever WORLD_SIZE is, 1 included (tests: the only way to drive the RCCL calls on a one-GPU box)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.configs == "on" and not args.full:
+        ap.error("--configs on needs --full")
+    return args
 
 
 def algorithmic_bytes(m, n, nnz, vbytes):
@@ -297,10 +311,10 @@ def cold_launches(torch, M, xp, yp, sp, count=15, flush_bytes=1 << 30):
 
 
 def time_handle(E, torch, A, fmt, dts, opts, steps, warmup, x_host=None, min_warm_seconds=0.0, idle_after_placement=0.0, windows=1,
-                cold=False):
+                cold=False, check=True, keep_y=False):
     """Build one handle, run warm-up + `windows` x `steps` back-to-back launches, each window timed by HIP events on the launch
-    stream inside a synchronize bracket, check sampled rows. Returns a dict with the measured figures (the MEDIAN window's) and leaves
-    nothing on the device."""
+    stream inside a synchronize bracket, check sampled rows (`check`). Returns a dict with the measured figures (the MEDIAN window's),
+    y of the last launch in its own dtype under "y" when `keep_y`, and leaves nothing on the device."""
     np_dtype = np.float64 if dts == "f64" else np.float32
     t_dtype = torch.float64 if dts == "f64" else torch.float32
     vbytes = 8 if dts == "f64" else 4
@@ -354,19 +368,34 @@ def time_handle(E, torch, A, fmt, dts, opts, steps, warmup, x_host=None, min_war
     wins.sort()
     wall_ms, kernel_ms = wins[len(wins) // 2]
     cold_ms = cold_launches(torch, M, xp, yp, sp) if cold else None
-    yh = M.download_y().astype(np.float64)
-    max_rel, samp = sampled_row_check(yh, A["row_ptr"], A["col_idx"], A["values"], x_host, np_dtype)
-    tol = 1e-12 if dts == "f64" else 1e-5
-    if not (max_rel <= tol) or not np.all(yh == yh):
-        raise SystemExit(f"bench sanity check failed for {M.format_name}: sampled rows differ from the host dot products (max {max_rel})")
     ki = M.kernel_info()
     B = algorithmic_bytes(m, n, nnz, vbytes)
     out = dict(format_name=M.format_name, kernel=ki["name"], kernel_ms=kernel_ms, wall_ms=wall_ms, convert_s=t_conv,
                algorithmic_bytes=B, gbps=B / (kernel_ms * 1e-3) / 1e9, gflops=2.0 * nnz / (kernel_ms * 1e-3) / 1e9,
-               mem_footprint=M.mem_footprint, check=max_rel, yh=yh, samp=samp, x_host=x_host, place_s=t_place,
+               mem_footprint=M.mem_footprint, x_host=x_host, place_s=t_place,
                wall_ms_windows=[round(w[0], 6) for w in wins], cold_ms=cold_ms)
+    if check or keep_y:
+        y = M.download_y()
+    if check:
+        yh = y.astype(np.float64)
+        max_rel, samp = sampled_row_check(yh, A["row_ptr"], A["col_idx"], A["values"], x_host, np_dtype)
+        tol = 1e-12 if dts == "f64" else 1e-5
+        if not (max_rel <= tol) or not np.all(yh == yh):
+            raise SystemExit(f"bench sanity check failed for {M.format_name}: sampled rows differ from the host dot products (max {max_rel})")
+        out.update(check=max_rel, yh=yh, samp=samp)
+    if keep_y:
+        out["y"] = y
     M.close()
     return out
+
+
+def dump_outputs(out_dir, y):
+    """DIR/y.npy: y as the caller of the timed path receives it (float32 or float64), whole when it holds at most DUMP_MAX_VALUES
+    values, else those of DUMP_MAX_VALUES rows drawn with DUMP_SEED (ascending): the same rows for the same arguments."""
+    if len(y) > DUMP_MAX_VALUES:
+        y = y[np.sort(np.random.default_rng(DUMP_SEED).choice(len(y), DUMP_MAX_VALUES, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "y.npy"), np.ascontiguousarray(y))
 
 
 def roofline_record(workload, dts, t, with_traffic=True):
@@ -593,6 +622,8 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU: the engine has no CPU path")
     if world > 1 or args.force_multi:
+        if args.dump_outputs is not None:
+            raise SystemExit("--dump-outputs is implemented for the N = 1 path only")
         import bench_multi
         result = bench_multi.run(args, sys.modules[__name__])
         if rank == 0:
@@ -612,12 +643,16 @@ def main():
     t_gen = time.time() - t0
     m, n, nnz = A["m"], A["n"], A["nnz"]
     small = nnz < 20_000_000
-    # a short sample (the driver's --steps 20 is 25 ms of a kernel whose level moves by a few % over tenths of a second) is timed as
-    # 5 windows of K steps, each in its own synchronize bracket; the line carries the MEDIAN window and the spread
-    windows = 5 if args.steps < 200 else 1
+    # --full: a short sample (the driver's --steps 20 is 25 ms of a kernel whose level moves by a few % over tenths of a second) is timed
+    # as 5 windows of K steps, each in its own synchronize bracket; the line carries the MEDIAN window and the spread. A plain run
+    # times exactly K steps.
+    windows = 5 if args.full and args.steps < 200 else 1
     opts.setdefault("placement", args.placement)
     t = time_handle(E, torch, A, fmt, dts, opts, args.steps, args.warmup, min_warm_seconds=0.25 if small else 0.0,
-                    idle_after_placement=args.idle_after_placement, windows=windows)
+                    idle_after_placement=args.idle_after_placement, windows=windows, check=args.full,
+                    keep_y=args.dump_outputs is not None)
+    if args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, t.pop("y"))
     ms_per_step = t["wall_ms"]                    # synchronize bracket around exactly K launches (the median window of `windows`)
     gflops = 2.0 * nnz / (ms_per_step * 1e-3) / 1e9
     B_alg = t["algorithmic_bytes"]
@@ -638,10 +673,13 @@ def main():
         "hbm_gbps_algorithmic": round(B_alg / (ms_per_step * 1e-3) / 1e9, 2),
         "hbm_pct_of_peak": round(100.0 * B_alg / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBPS, 2),
         "roofline": roofline_record(workload, dts, t, with_traffic=args.scale == 1.0 and not args.jitter and not args.index_modes_off),
-        "check_max_err_over_abs_row": t["check"],
         "setup_s": {"generate": round(t_gen, 2), "convert_upload": round(t["convert_s"], 2), "upload_x_place_vectors": round(t["place_s"], 2)},
         "placement": E.placement_info(torch.cuda.current_device()),
     }
+    if not args.full:
+        print(json.dumps(result), flush=True)
+        return
+    result["check_max_err_over_abs_row"] = t["check"]
     if workload == "nlpkkt240" and fmt == "sell_c_sigma" and not args.index_modes_off and not args.jitter and args.scale == 1.0 and not args.headline_only:
         # the other end of the headline: the same matrix with every index-free mode of the delta layout switched off (8/16-bit deltas per
         # lane and step everywhere) — what a matrix without the twin's translation invariance gets from the format

@@ -5,6 +5,7 @@ import json
 import os
 
 import numpy as np
+import pytest
 
 from conftest import ROOT
 
@@ -129,3 +130,28 @@ def test_filtered_kkt_rows_equal_the_filtered_block():
     some = np.array([5, 17, 900, 901, m - 1], np.int32)
     B = H.gen_kkt_rows_filtered(N, 0, 100, 0, rows=some, values=False)
     assert B["values"] is None and B["m"] == 5 and int(B["row_ptr"][-1]) == B["nnz"] == len(B["col_idx"])
+
+
+def test_dump_outputs_writes_y_whole_or_as_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: y keeps its dtype; a y larger than DUMP_MAX_VALUES is cut to the same ascending seeded rows every time."""
+    b = _bench()
+    y = np.random.default_rng(5).uniform(-1, 1, 1000)
+    b.dump_outputs(str(tmp_path / "whole"), y.astype(np.float32))
+    got = np.load(tmp_path / "whole" / "y.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, y.astype(np.float32))
+    monkeypatch.setattr(b, "DUMP_MAX_VALUES", 100)
+    b.dump_outputs(str(tmp_path / "a"), y)
+    b.dump_outputs(str(tmp_path / "b"), y)
+    a = np.load(tmp_path / "a" / "y.npy")
+    assert a.dtype == np.float64 and len(a) == 100 and np.array_equal(a, np.load(tmp_path / "b" / "y.npy"))
+    rows = np.sort(np.random.default_rng(b.DUMP_SEED).choice(len(y), 100, replace=False))
+    assert np.array_equal(a, y[rows]) and len(np.unique(rows)) == 100
+
+
+def test_extra_legs_need_full():
+    b = _bench()
+    a = b.parse(["--steps", "3"])
+    assert not a.full and a.dump_outputs is None and a.steps == 3
+    assert b.parse(["--full", "--configs", "on"]).full
+    with pytest.raises(SystemExit):
+        b.parse(["--configs", "on"])

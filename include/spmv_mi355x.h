@@ -110,6 +110,10 @@ typedef struct {
 	                           3 = 1 + a search over the handle's matrix arrays (worth 1-5 %, ~500 launches).
 	                           SPMV_MI355X_PLACEMENT in the environment overrides: 0 off, 1 on, 2 on + log on stderr, 3, 4 (diagnostic) */
 	int  placement_budget_gib;  /* transient memory the walk may hold, GiB (0 = 160; it never takes the device's last 8 GiB)             */
+	int  sell_values;       /* SELL delta layout, fp64: slices whose values (in their full groups of 4 steps) are all +-0 / denormal or finite
+	                           normals within 7 binades store each value in 7 bytes (sign, 3-bit exponent code against a per-slice base,
+	                           52-bit mantissa; lossless, bit-identical results; csrc/launch.hpp). 0 = auto (on when the plain value array
+	                           exceeds the 256 MiB Infinity Cache), 1 = on, 2 = off. SPMV_MI355X_SELL_VALUES in the environment overrides */
 } spmv_mi355x_opts;
 
 /* ---- library / device ------------------------------------------------------------------------------------ */

@@ -146,7 +146,7 @@ sell5_exceptions(const int * rp, const int * ci, const int * rows, long maxlen, 
 // SELL-64-sigma-delta build (layout: kernels_sell.hip). Same sigma-window sort and slice widths as build_sell with C = 64,
 // widths padded to a multiple of 4 steps; per slice the narrowest index encoding that holds every (step, lane) delta.
 static int
-build_sell_delta(spmv_mi355x_matrix * A, const int * rp, const int * ci, const double * va)
+build_sell_delta(spmv_mi355x_matrix * A, int sell_values, const int * rp, const int * ci, const double * va)
 {
 	const long m = A->m;
 	constexpr int C = 64;
@@ -155,18 +155,19 @@ build_sell_delta(spmv_mi355x_matrix * A, const int * rp, const int * ci, const d
 	if (A->convert_on_device)
 	{
 		std::vector<int64_t> val_ptr;
-		int64_t nnz_ext = 0, idx_bytes = 0;
+		int64_t nnz_ext = 0, idx_bytes = 0, val_words = 0;
 		void * d_val = nullptr;
-		if (sell_delta_convert_device(A->f32, m, A->n, A->nnz, sigma, rp, ci, va, &A->d_row_of_sorted, &A->d_sell_desc, &A->d_sell_idx,
-				&d_val, val_ptr, A->sell_mode_slices, &nnz_ext, &idx_bytes))
+		if (sell_delta_convert_device(A->f32, m, A->n, A->nnz, sigma, sell_values, rp, ci, va, &A->d_row_of_sorted, &A->d_sell_desc, &A->d_sell_idx,
+				&d_val, val_ptr, A->sell_mode_slices, &nnz_ext, &idx_bytes, &val_words, &A->sell_v7_slices))
 			return 1;
 		A->d_val = d_val;
 		A->sell_slices = num_slices;
 		A->sell_nnz_ext = nnz_ext;
+		A->sell_val_words = val_words;
 		A->sell_idx_bytes = idx_bytes;
 		const long spt = sell_slices_per_tile() / A->sell_split;
 		A->cfg.map = xcd_map_balanced(val_ptr.data(), num_slices, spt, resolve_remap(A->remap, (num_slices + spt - 1) / spt));
-		A->mem_footprint = (double) (num_slices + 1) * 16 + (double) nnz_ext * A->vbytes + (double) idx_bytes + (double) m * 4;
+		A->mem_footprint = (double) (num_slices + 1) * 16 + (double) val_words * A->vbytes + (double) idx_bytes + (double) m * 4;
 		return 0;
 	}
 	std::vector<int> row_of_sorted(std::max<long>(m, 1));
@@ -268,27 +269,65 @@ build_sell_delta(spmv_mi355x_matrix * A, const int * rp, const int * ci, const d
 		idx_ptr[sl + 1] = md == 5 ? (4 * C + 16) + (width / 4) * (16 + (nex + 3) / 4 * 16)
 		                          : (md == 3 ? 4 * C : 0) + (width / 4) * ((md == 0 || md == 3) ? 16 : md == 1 ? 272 : md == 2 ? 528 : 1024);
 	}
+	// 7-byte values (launch.hpp): a slice qualifies on the values of its full groups of 4 steps (padding 0.0 always fits)
+	std::vector<int> v7_e0((size_t) std::max<long>(num_slices, 1), 0);
+	{
+		int64_t plain = 0;
+		for (long sl = 0; sl < num_slices; sl++)
+			plain += val_ptr[sl + 1];
+		if (sell_v7_wanted(A->f32, sell_values, plain))
+		{
+			#pragma omp parallel for num_threads(spmv::host_threads()) schedule(dynamic, 64)
+			for (long sl = 0; sl < num_slices; sl++)
+			{
+				const long maxlen = val_ptr[sl + 1] / C, full = maxlen / 4;
+				SellV7Range r;
+				for (long i = sl * C; i < std::min(m, (sl + 1) * C); i++)
+				{
+					const int o = row_of_sorted[i];
+					for (long k = 0; k < std::min<long>(rp[o + 1] - rp[o], 4 * full); k++)
+					{
+						uint64_t bits;
+						memcpy(&bits, va + rp[o] + k, 8);
+						r.add(bits);
+					}
+				}
+				if (full > 0 && r.ok())
+				{
+					v7_e0[sl] = r.e0();
+					val_ptr[sl + 1] = full * SELL_V7_GROUP_WORDS + (maxlen - 4 * full) * C;
+				}
+			}
+		}
+	}
+	A->sell_v7_slices = 0;
+	A->sell_nnz_ext = 0;
 	for (long sl = 0; sl < num_slices; sl++)
 	{
+		A->sell_nnz_ext += v7_e0[sl] ? sell_v7_width(val_ptr[sl + 1]) * C : val_ptr[sl + 1];
+		A->sell_v7_slices += v7_e0[sl] != 0;
 		val_ptr[sl + 1] += val_ptr[sl];
 		idx_ptr[sl + 1] += idx_ptr[sl];
 		A->sell_mode_slices[((mode[sl] & 7) == 0 || (mode[sl] & 7) == 3 || (mode[sl] & 7) == 5) ? 3 : (mode[sl] & 7) == 1 ? 0 : (mode[sl] & 7) == 2 ? 1 : 2]++;
 	}
-	const int64_t nnz_ext = val_ptr[num_slices];
+	const int64_t val_words = val_ptr[num_slices];
 	const int64_t idx_bytes = idx_ptr[num_slices];
-	std::vector<double> val((size_t) std::max<int64_t>(nnz_ext, 1));
+	std::vector<double> val((size_t) std::max<int64_t>(val_words, 1));
 	std::vector<unsigned char> idx((size_t) std::max<int64_t>(idx_bytes, 16) + 1024, 0);
 	std::vector<int64_t> desc(2 * ((size_t) num_slices + 1), 0);
 	#pragma omp parallel for num_threads(spmv::host_threads()) schedule(dynamic, 64)
 	for (long sl = 0; sl < num_slices; sl++)
 	{
 		const int64_t vb = val_ptr[sl];
-		const long maxlen = (val_ptr[sl + 1] - vb) / C;
+		const int e0 = v7_e0[sl];
+		const long maxlen = e0 ? sell_v7_width(val_ptr[sl + 1] - vb) : (val_ptr[sl + 1] - vb) / C;
 		const long width = (maxlen + 3) / 4 * 4;
+		const long full = e0 ? maxlen / 4 : 0;           // groups stored as 7-byte records
+		unsigned char * vbytes = reinterpret_cast<unsigned char *>(val.data() + vb);
 		const int md = mode[sl] & 7, ref = mode[sl] >> 3;
 		unsigned char * ib = idx.data() + idx_ptr[sl];
 		desc[2 * sl] = vb;
-		desc[2 * sl + 1] = idx_ptr[sl] | md;
+		desc[2 * sl + 1] = idx_ptr[sl] | md | (e0 ? SELL_V7_FLAG | (int64_t) e0 << 48 : 0);
 		const long i_e = std::min(m, (sl + 1) * C);
 		int min_off = 0;
 		unsigned long long exmask = 0;
@@ -357,8 +396,19 @@ build_sell_delta(spmv_mi355x_matrix * A, const int * rp, const int * ci, const d
 						v = va[rp[o] + k];
 					}
 				}
-				if (k < maxlen)
-					val[vb + sell_pair_pos(k, maxlen, r)] = v;   // steps past the longest row exist in the index groups only
+				if (k < 4 * full)
+				{
+					uint64_t bits;
+					memcpy(&bits, &v, 8);
+					const uint32_t lo = (uint32_t) bits;
+					const long hb = sell_v7_hi_bit(k, r);
+					const uint32_t h = sell_v7_encode_hi(bits, e0);
+					memcpy(vbytes + sell_v7_lo_pos(k, r), &lo, 4);
+					for (int b = 0; b < 24; b += 8)
+						vbytes[(hb + b) / 8] = (unsigned char) (h >> b);
+				}
+				else if (k < maxlen)                           // steps past the longest row exist in the index groups only
+					val[vb + full * SELL_V7_GROUP_WORDS + sell_pair_pos(k, maxlen, r) - full * 4 * C] = v;
 				const unsigned d = (unsigned) (c - base);
 				if (md == 5)
 				{
@@ -379,10 +429,10 @@ build_sell_delta(spmv_mi355x_matrix * A, const int * rp, const int * ci, const d
 			}
 		}
 	}
-	desc[2 * num_slices] = nnz_ext;
+	desc[2 * num_slices] = val_words;
 	desc[2 * num_slices + 1] = idx_bytes | 4;
 	A->sell_slices = num_slices;
-	A->sell_nnz_ext = nnz_ext;
+	A->sell_val_words = val_words;
 	A->sell_idx_bytes = idx_bytes;
 	{
 		const long spt = sell_slices_per_tile() / A->sell_split;       // slices per workgroup
@@ -394,11 +444,11 @@ build_sell_delta(spmv_mi355x_matrix * A, const int * rp, const int * ci, const d
 	if (dev_alloc(&A->d_sell_idx, idx.size()))
 		return 1;
 	HIP_TRY(hipMemcpy(A->d_sell_idx, idx.data(), idx.size(), hipMemcpyHostToDevice));
-	if (upload_values(A, val.data(), (size_t) nnz_ext, &A->d_val))
+	if (upload_values(A, val.data(), (size_t) val_words, &A->d_val))
 		return 1;
 	if (upload_ints(row_of_sorted.data(), (size_t) m, &A->d_row_of_sorted))
 		return 1;
-	A->mem_footprint = (double) (num_slices + 1) * 16 + (double) nnz_ext * A->vbytes + (double) idx_bytes + (double) m * 4;
+	A->mem_footprint = (double) (num_slices + 1) * 16 + (double) val_words * A->vbytes + (double) idx_bytes + (double) m * 4;
 	return 0;
 }
 
@@ -678,12 +728,14 @@ build_sell_family(spmv_mi355x_matrix * A, const spmv_mi355x_opts & o, const int 
 			}
 		}
 	}
-	rc = A->sell_delta ? build_sell_delta(A, rp, ci, va) : build_sell(A, rp, ci, va);
+	rc = A->sell_delta ? build_sell_delta(A, sell_values_env(o.sell_values), rp, ci, va) : build_sell(A, rp, ci, va);
 	if (A->sell_delta && A->sell_split > 1)
-		snprintf(A->format_name, sizeof(A->format_name), "MI355X_SELLD_%d_%ld_w%d_%s", C, sigma, A->sell_split, pf);
+		snprintf(A->format_name, sizeof(A->format_name), "MI355X_SELLD_%d_%ld_w%d_%s%s", C, sigma, A->sell_split, pf, A->sell_v7_slices ? "_v7" : "");
 	else
-		snprintf(A->format_name, sizeof(A->format_name), "MI355X_SELL%s_%d_%ld_%s", A->sell_delta ? "D" : "", C, sigma, pf);
+		snprintf(A->format_name, sizeof(A->format_name), "MI355X_SELL%s_%d_%ld_%s%s", A->sell_delta ? "D" : "", C, sigma, pf, A->sell_v7_slices ? "_v7" : "");
 	snprintf(A->kernel_name, sizeof(A->kernel_name), A->sell_delta ? "sell_delta_kernel" : "sell_kernel");
+	if (A->sell_v7_slices && o.nontemporal == 0)
+		A->cfg.nt = A->mem_footprint > 192.0 * 1024 * 1024 ? 1 : 0;      // the auto rule of init_handle on the bytes really stored
 	return rc;
 }
 
@@ -721,23 +773,27 @@ build_sell_delta_resident(spmv_mi355x_matrix * A, const spmv_mi355x_opts & o, co
 	A->convert_on_device = true;
 	A->sell_split = S;
 	std::vector<int64_t> val_ptr;
-	int64_t nnz_ext = 0, idx_bytes = 0;
+	int64_t nnz_ext = 0, idx_bytes = 0, val_words = 0;
 	void * d_val = nullptr;
-	if (sell_delta_convert_resident(A->f32, m, A->n, A->nnz, sigma, d_rp, d_ci, d_va, &A->d_row_of_sorted, &A->d_sell_desc, &A->d_sell_idx, &d_val,
-			val_ptr, A->sell_mode_slices, &nnz_ext, &idx_bytes))
+	if (sell_delta_convert_resident(A->f32, m, A->n, A->nnz, sigma, sell_values_env(o.sell_values), d_rp, d_ci, d_va, &A->d_row_of_sorted, &A->d_sell_desc,
+			&A->d_sell_idx, &d_val, val_ptr, A->sell_mode_slices, &nnz_ext, &idx_bytes, &val_words, &A->sell_v7_slices))
 		return 1;
 	A->d_val = d_val;
 	A->sell_slices = num_slices;
 	A->sell_nnz_ext = nnz_ext;
+	A->sell_val_words = val_words;
 	A->sell_idx_bytes = idx_bytes;
 	const long spt = sell_slices_per_tile() / A->sell_split;
 	A->cfg.map = xcd_map_balanced(val_ptr.data(), num_slices, spt, resolve_remap(A->remap, (num_slices + spt - 1) / spt));
-	A->mem_footprint = (double) (num_slices + 1) * 16 + (double) nnz_ext * A->vbytes + (double) idx_bytes + (double) m * 4;
+	A->mem_footprint = (double) (num_slices + 1) * 16 + (double) val_words * A->vbytes + (double) idx_bytes + (double) m * 4;
+	const char * v7 = A->sell_v7_slices ? "_v7" : "";
 	if (A->sell_split > 1)
-		snprintf(A->format_name, sizeof(A->format_name), "MI355X_SELLD_%d_%ld_w%d_%s", C, sigma, A->sell_split, pf);
+		snprintf(A->format_name, sizeof(A->format_name), "MI355X_SELLD_%d_%ld_w%d_%s%s", C, sigma, A->sell_split, pf, v7);
 	else
-		snprintf(A->format_name, sizeof(A->format_name), "MI355X_SELLD_%d_%ld_%s", C, sigma, pf);
+		snprintf(A->format_name, sizeof(A->format_name), "MI355X_SELLD_%d_%ld_%s%s", C, sigma, pf, v7);
 	snprintf(A->kernel_name, sizeof(A->kernel_name), "sell_delta_kernel");
+	if (A->sell_v7_slices && o.nontemporal == 0)
+		A->cfg.nt = A->mem_footprint > 192.0 * 1024 * 1024 ? 1 : 0;      // the auto rule of init_handle on the bytes really stored
 	return 0;
 }
 

@@ -173,12 +173,51 @@ slice_shape_kernel(const int * __restrict__ rp, const int * __restrict__ ci, con
 	}
 }
 
-// pass 2: one wave per slice fills its values, bases and deltas (layout: kernels_sell.hip)
+// pass 1b (7-byte values, launch.hpp): one wave per slice -> E0 of a slice whose values in its full groups of 4 steps qualify (0 = they do
+// not, or the slice has no full group) and its stored words
+__global__ __launch_bounds__(CV_BLOCK) void
+slice_v7_kernel(const int * __restrict__ rp, const double * __restrict__ va, const int * __restrict__ row_of_sorted, long m, long num_slices,
+		int * __restrict__ v7_e0, int64_t * __restrict__ val_count)
+{
+	const long sl = ((long) blockIdx.x * CV_BLOCK + threadIdx.x) / WAVE;
+	const int lane = threadIdx.x % WAVE;
+	if (sl >= num_slices)
+		return;
+	const long i = sl * WAVE + lane;
+	int start = 0, len = 0;
+	if (i < m)
+	{
+		const int o = row_of_sorted[i];
+		start = rp[o];
+		len = rp[o + 1] - start;
+	}
+	const int maxlen = wave_max_i(len);
+	const int full = maxlen / 4;
+	SellV7Range r;                                      // padding entries are 0.0: exponent 0, always fit
+	for (int k = 0; k < min(len, 4 * full); k++)
+		r.add(__double_as_longlong(va[start + k]));
+	const int lo = wave_min_i(r.lo), hi = wave_max_i(r.hi);
+	const bool bad = __ballot(r.bad) != 0ull;
+	SellV7Range w;
+	w.lo = lo;
+	w.hi = hi;
+	w.bad = bad;
+	if (lane == 0)
+	{
+		const bool take = full > 0 && w.ok();
+		v7_e0[sl] = take ? w.e0() : 0;
+		if (take)
+			val_count[sl] = (int64_t) full * SELL_V7_GROUP_WORDS + (int64_t) (maxlen - 4 * full) * WAVE;
+	}
+}
+
+// pass 2: one wave per slice fills its values, bases and deltas (layout: kernels_sell.hip); v7_e0 (nullptr: none) = E0 of a slice with
+// 7-byte values, 0 for the others
 template <typename T>
 __global__ __launch_bounds__(CV_BLOCK) void
 slice_fill_kernel(const int * __restrict__ rp, const int * __restrict__ ci, const double * __restrict__ va,
 		const int * __restrict__ row_of_sorted, long m, long num_slices, const unsigned char * __restrict__ mode,
-		const int64_t * __restrict__ val_ptr, const int64_t * __restrict__ idx_ptr, T * __restrict__ val,
+		const int64_t * __restrict__ val_ptr, const int64_t * __restrict__ idx_ptr, const int * __restrict__ v7_e0, T * __restrict__ val,
 		unsigned char * __restrict__ idx, int64_t * __restrict__ desc)
 {
 	const long sl = ((long) blockIdx.x * CV_BLOCK + threadIdx.x) / WAVE;
@@ -195,14 +234,16 @@ slice_fill_kernel(const int * __restrict__ rp, const int * __restrict__ ci, cons
 		return;
 	}
 	const int64_t vb = val_ptr[sl];
-	const int maxlen = (int) ((val_ptr[sl + 1] - vb) / WAVE);
+	const int e0 = v7_e0 ? v7_e0[sl] : 0;
+	const int maxlen = e0 ? (int) sell_v7_width(val_ptr[sl + 1] - vb) : (int) ((val_ptr[sl + 1] - vb) / WAVE);
 	const int width = (maxlen + 3) / 4 * 4;
+	const int full = e0 ? maxlen / 4 : 0;              // groups stored as 7-byte records
 	const int md = mode[sl] & 7, ref = mode[sl] >> 3;
 	unsigned char * ib = idx + idx_ptr[sl];
 	if (lane == 0)
 	{
 		desc[2 * sl] = vb;
-		desc[2 * sl + 1] = idx_ptr[sl] | md;
+		desc[2 * sl + 1] = idx_ptr[sl] | md | (e0 ? SELL_V7_FLAG | (int64_t) e0 << 48 : 0);
 	}
 	const long i = sl * WAVE + lane;
 	int start = 0, len = 0;
@@ -250,6 +291,7 @@ slice_fill_kernel(const int * __restrict__ rp, const int * __restrict__ ci, cons
 		unsigned char * gp = ib + g * gbytes;
 		unsigned d[4];
 		int cc[4];
+		unsigned long long vbits[4];
 		#pragma unroll
 		for (int u = 0; u < 4; u++)
 		{
@@ -266,8 +308,10 @@ slice_fill_kernel(const int * __restrict__ rp, const int * __restrict__ ci, cons
 			if (!ok)
 				c = md == 5 ? base + off5 : base;      // padding: value 0 times a column some lane really uses (mode 5: the pattern's, correction 0)
 			cc[u] = md == 5 ? c - (base + off5) : 0;   // mode 5: the correction of this step (0 for a regular lane)
-			if (k < maxlen)                            // steps past the slice's longest row exist in the index groups only
-				val[vb + sell_pair_pos(k, maxlen, lane)] = ok ? (T) va[start + k] : (T) 0;
+			if (g < full)
+				vbits[u] = ok ? (unsigned long long) __double_as_longlong(va[start + k]) : 0ull;
+			else if (k < maxlen)                       // steps past the slice's longest row exist in the index groups only
+				val[vb + (int64_t) full * SELL_V7_GROUP_WORDS + sell_pair_pos(k, maxlen, lane) - (int64_t) full * 4 * WAVE] = ok ? (T) va[start + k] : (T) 0;
 			if (md != 4)
 			{
 				if (lane == 0)
@@ -276,6 +320,22 @@ slice_fill_kernel(const int * __restrict__ rp, const int * __restrict__ ci, cons
 			}
 			else
 				reinterpret_cast<int *>(gp)[u * WAVE + lane] = c;
+		}
+		if (g < full)
+		{
+			// a 7-byte group: the lane's four low dwords, then its four 24-bit high parts packed into three dwords
+			unsigned char * b = reinterpret_cast<unsigned char *>(val + vb) + (size_t) g * (8 * SELL_V7_GROUP_WORDS);
+			unsigned h[4];
+			#pragma unroll
+			for (int u = 0; u < 4; u++)
+			{
+				reinterpret_cast<unsigned *>(b)[lane * 4 + u] = (unsigned) vbits[u];
+				h[u] = sell_v7_encode_hi(vbits[u], e0);
+			}
+			unsigned * hp = reinterpret_cast<unsigned *>(b + 1024) + lane * 3;
+			hp[0] = h[0] | h[1] << 24;
+			hp[1] = h[1] >> 8 | h[2] << 16;
+			hp[2] = h[2] >> 16 | h[3] << 8;
 		}
 		if (md == 5)
 		{
@@ -319,9 +379,10 @@ struct Scratch {
 // Outputs (device, owned by the caller on success): row_of_sorted[m], desc[2*(slices+1)], idx[idx_bytes+1024], val[nnz_ext
 // + STREAM_SLACK] of the handle's precision. Host outputs: val_ptr (slices+1, for the tile map), mode counts, sizes.
 int
-sell_delta_convert_resident(bool f32, long m, long n_cols, long nnz, long sigma, const int * rp, const int * ci,
+sell_delta_convert_resident(bool f32, long m, long n_cols, long nnz, long sigma, int sell_values, const int * rp, const int * ci,
 		const double * va, int ** d_row_of_sorted_out, int64_t ** d_desc_out, unsigned char ** d_idx_out, void ** d_val_out,
-		std::vector<int64_t> & val_ptr_host, long mode_counts[4], int64_t * nnz_ext_out, int64_t * idx_bytes_out)
+		std::vector<int64_t> & val_ptr_host, long mode_counts[4], int64_t * nnz_ext_out, int64_t * idx_bytes_out, int64_t * val_words_out,
+		long * v7_slices_out)
 {
 	(void) nnz;
 	const long num_slices = (m + WAVE - 1) / WAVE;
@@ -379,11 +440,33 @@ sell_delta_convert_resident(bool f32, long m, long n_cols, long nnz, long sigma,
 		HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp, bytes, val_count, val_ptr, (int) (num_slices + 1), (hipStream_t) 0));
 		HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp, bytes, idx_count, idx_ptr, (int) (num_slices + 1), (hipStream_t) 0));
 	}
+	int64_t nnz_ext = 0;
+	HIP_TRY(hipMemcpy(&nnz_ext, val_ptr + num_slices, 8, hipMemcpyDeviceToHost));
+	// 3b. 7-byte values: qualifying slices get their compressed word counts, the value offsets are scanned again
+	int * v7_e0 = nullptr;
+	long v7_slices = 0;
+	if (sell_v7_wanted(f32, sell_values, nnz_ext) && num_slices > 0)
+	{
+		if (tmp.get(&v7_e0, (size_t) num_slices * 4))
+			return 1;
+		hipLaunchKernelGGL(slice_v7_kernel, dim3(slice_grid), dim3(CV_BLOCK), 0, 0, rp, va, row_of_sorted, m, num_slices, v7_e0, val_count);
+		HIP_TRY(hipGetLastError());
+		size_t bytes = 0;
+		HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, val_count, val_ptr, (int) (num_slices + 1), (hipStream_t) 0));
+		void * scan_tmp;
+		if (tmp.get(&scan_tmp, bytes))
+			return 1;
+		HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp, bytes, val_count, val_ptr, (int) (num_slices + 1), (hipStream_t) 0));
+		std::vector<int> e0_host((size_t) num_slices);
+		HIP_TRY(hipMemcpy(e0_host.data(), v7_e0, (size_t) num_slices * 4, hipMemcpyDeviceToHost));
+		for (long sl = 0; sl < num_slices; sl++)
+			v7_slices += e0_host[sl] != 0;
+	}
 	val_ptr_host.assign((size_t) num_slices + 1, 0);
 	HIP_TRY(hipMemcpy(val_ptr_host.data(), val_ptr, (size_t) (num_slices + 1) * 8, hipMemcpyDeviceToHost));
 	int64_t idx_bytes = 0;
 	HIP_TRY(hipMemcpy(&idx_bytes, idx_ptr + num_slices, 8, hipMemcpyDeviceToHost));
-	const int64_t nnz_ext = val_ptr_host[num_slices];
+	const int64_t val_words = val_ptr_host[num_slices];
 	{
 		std::vector<unsigned char> mode_host((size_t) std::max<long>(num_slices, 1));
 		if (num_slices)
@@ -399,22 +482,22 @@ sell_delta_convert_resident(bool f32, long m, long n_cols, long nnz, long sigma,
 	unsigned char * idx = nullptr;
 	int64_t * desc = nullptr;
 	const size_t idx_alloc = (size_t) std::max<int64_t>(idx_bytes, 16) + 1024;
-	HIP_TRY(hipMalloc(&val, ((size_t) nnz_ext + STREAM_SLACK) * vbytes));
+	HIP_TRY(hipMalloc(&val, ((size_t) val_words + STREAM_SLACK) * vbytes));
 	out_guard.ptrs.push_back(val);
 	HIP_TRY(hipMalloc(&idx, idx_alloc));
 	out_guard.ptrs.push_back(idx);
 	HIP_TRY(hipMalloc(&desc, 2 * ((size_t) num_slices + 1) * 8));
 	out_guard.ptrs.push_back(desc);
-	HIP_TRY(hipMemset((char *) val + (size_t) nnz_ext * vbytes, 0, STREAM_SLACK * vbytes));
+	HIP_TRY(hipMemset((char *) val + (size_t) val_words * vbytes, 0, STREAM_SLACK * vbytes));
 	HIP_TRY(hipMemset(idx + (idx_alloc - 1040), 0, 1040));     // the tail the kernels may read past the last group
 	if (idx_bytes < 16)
 		HIP_TRY(hipMemset(idx, 0, idx_alloc));
 	if (f32)
 		hipLaunchKernelGGL((slice_fill_kernel<float>), dim3(slice_grid), dim3(CV_BLOCK), 0, 0, rp, ci, va, row_of_sorted, m, num_slices,
-				mode, val_ptr, idx_ptr, (float *) val, idx, desc);
+				mode, val_ptr, idx_ptr, v7_e0, (float *) val, idx, desc);
 	else
 		hipLaunchKernelGGL((slice_fill_kernel<double>), dim3(slice_grid), dim3(CV_BLOCK), 0, 0, rp, ci, va, row_of_sorted, m, num_slices,
-				mode, val_ptr, idx_ptr, (double *) val, idx, desc);
+				mode, val_ptr, idx_ptr, v7_e0, (double *) val, idx, desc);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipDeviceSynchronize());
 	out_guard.ptrs.clear();                            // success: ownership moves to the caller
@@ -424,14 +507,17 @@ sell_delta_convert_resident(bool f32, long m, long n_cols, long nnz, long sigma,
 	*d_val_out = val;
 	*nnz_ext_out = nnz_ext;
 	*idx_bytes_out = idx_bytes;
+	*val_words_out = val_words;
+	*v7_slices_out = v7_slices;
 	return 0;
 }
 
 // The same from HOST arrays: upload, convert, drop the uploaded copy.
 int
-sell_delta_convert_device(bool f32, long m, long n_cols, long nnz, long sigma, const int * rp_host, const int * ci_host,
+sell_delta_convert_device(bool f32, long m, long n_cols, long nnz, long sigma, int sell_values, const int * rp_host, const int * ci_host,
 		const double * va_host, int ** d_row_of_sorted_out, int64_t ** d_desc_out, unsigned char ** d_idx_out, void ** d_val_out,
-		std::vector<int64_t> & val_ptr_host, long mode_counts[4], int64_t * nnz_ext_out, int64_t * idx_bytes_out)
+		std::vector<int64_t> & val_ptr_host, long mode_counts[4], int64_t * nnz_ext_out, int64_t * idx_bytes_out, int64_t * val_words_out,
+		long * v7_slices_out)
 {
 	Scratch up;
 	int * rp, * ci;
@@ -449,8 +535,8 @@ sell_delta_convert_device(bool f32, long m, long n_cols, long nnz, long sigma, c
 		HIP_TRY(hipMemcpy(ci, ci_host, (size_t) nnz * 4, hipMemcpyHostToDevice));
 		HIP_TRY(hipMemcpy(va, va_host, (size_t) nnz * 8, hipMemcpyHostToDevice));
 	}
-	return sell_delta_convert_resident(f32, m, n_cols, nnz, sigma, rp, ci, va, d_row_of_sorted_out, d_desc_out, d_idx_out, d_val_out, val_ptr_host,
-			mode_counts, nnz_ext_out, idx_bytes_out);
+	return sell_delta_convert_resident(f32, m, n_cols, nnz, sigma, sell_values, rp, ci, va, d_row_of_sorted_out, d_desc_out, d_idx_out, d_val_out,
+			val_ptr_host, mode_counts, nnz_ext_out, idx_bytes_out, val_words_out, v7_slices_out);
 }
 
 // ---------------------------------------------------------------- the LDS-window layout (build_sell.hip: build_sell_window) on the GPU

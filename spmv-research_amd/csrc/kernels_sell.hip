@@ -217,9 +217,52 @@ sell_tail_values(const T * __restrict__ vp, int lane, T (&v)[3])
 	}
 }
 
-template <typename T, int MODE, bool NT, int NSTEPS = 4>
+typedef unsigned sell_uint4 __attribute__((ext_vector_type(4)));
+typedef unsigned sell_uint3 __attribute__((ext_vector_type(3), aligned(4)));     // 12 bytes, one global_load_dwordx3
+
+__device__ __forceinline__ double
+sell_v7_value(unsigned h, unsigned k, unsigned lo)
+{
+	return __builtin_bit_cast(double, (unsigned long long) sell_v7_decode_hi(h, k) << 32 | lo);
+}
+
+// Where a slice's values come from. V7 = false: the pairs above. V7 = true (fp64, sell_values; layout: launch.hpp): a full group is the
+// lane's dwordx4 of low halves and dwordx3 of packed 24-bit high parts — as many load instructions as the pairs, 1792 bytes instead of
+// 2048 — decoded with a few 32-bit VALU operations on the high dwords only; the 1..3-step tail group is stored as pairs, behind the
+// slice's full groups. `vp` = the slice's first value word + 2 * lane either way, `k` = (E0 - 1) << 20.
+template <typename T, bool NT, bool V7>
+struct SellVals {
+	const T * vp;
+	int lane;
+	unsigned k;
+	__device__ __forceinline__ void group(int g, T (&v)[4]) const
+	{
+		if constexpr (!V7)
+			sell_group_values<T, NT>(vp + (size_t) g * 4 * WAVE, v);
+		else
+		{
+			static_assert(sizeof(T) == 8, "7-byte values are fp64 only");
+			const unsigned char * b = reinterpret_cast<const unsigned char *>(vp) + (size_t) g * (8 * SELL_V7_GROUP_WORDS);  // lo plane + 16 * lane
+			const sell_uint4 lo = ld_stream<NT>(reinterpret_cast<const sell_uint4 *>(b));
+			const sell_uint3 * hp = reinterpret_cast<const sell_uint3 *>(b + 1024 - 4 * lane);                   // hi plane + 12 * lane
+			sell_uint3 hi;
+			if constexpr (NT)
+				hi = __builtin_nontemporal_load(hp);
+			else
+				hi = *hp;
+			v[0] = sell_v7_value(hi.x, k, lo.x);
+			v[1] = sell_v7_value(__builtin_amdgcn_alignbit(hi.y, hi.x, 24), k, lo.y);
+			v[2] = sell_v7_value(__builtin_amdgcn_alignbit(hi.z, hi.y, 16), k, lo.z);
+			v[3] = sell_v7_value(hi.z >> 8, k, lo.w);
+		}
+	}
+	// the group `g` (= the number of full groups) that holds the slice's 1..3 last steps: vp-relative as sell_tail_values wants it
+	__device__ __forceinline__ const T * tail(int g) const { return vp + (size_t) g * (V7 ? SELL_V7_GROUP_WORDS : 4 * WAVE); }
+};
+
+template <typename T, int MODE, bool NT, bool V7, int NSTEPS = 4>
 __device__ __forceinline__ void
-sell_delta_group(const unsigned char * __restrict__ gp /* uniform */, const T * __restrict__ vp, int lane, const T * __restrict__ x, T & s,
+sell_delta_group(const unsigned char * __restrict__ gp /* uniform */, const SellVals<T, NT, V7> & vals, int g, int lane, const T * __restrict__ x, T & s,
 		int off = 0)
 {
 	int c0, c1, c2, c3;
@@ -263,7 +306,7 @@ sell_delta_group(const unsigned char * __restrict__ gp /* uniform */, const T * 
 	if (NSTEPS == 4)
 	{
 		T v[4];
-		sell_group_values<T, NT>(vp, v);
+		vals.group(g, v);
 		const T x0 = x[c0], x1 = x[c1], x2 = x[c2], x3 = x[c3];
 		s = fma_t<T>(v[0], x0, s);
 		s = fma_t<T>(v[1], x1, s);
@@ -274,7 +317,7 @@ sell_delta_group(const unsigned char * __restrict__ gp /* uniform */, const T * 
 	{
 		// last group of a slice whose width is not a multiple of 4: the value array holds only the real steps
 		T v[3];
-		sell_tail_values<T, NT, NSTEPS>(vp, lane, v);
+		sell_tail_values<T, NT, NSTEPS>(vals.tail(g), lane, v);
 		const T x0 = x[c0];
 		const T x1 = NSTEPS > 1 ? x[c1] : T(0);
 		const T x2 = NSTEPS > 2 ? x[c2] : T(0);
@@ -346,16 +389,16 @@ sell_delta_cols(const SellDeltaIdx<MODE> & q, int (&c)[4])
 // trip are issued before its first FMA), their index words fetched one trip ahead; what is left (0..3 groups) as a pair and / or a single
 // group on the index words the last trip already fetched. (Two groups per trip: 1 347 us with every index-free mode off; four: see
 // profiles/r03_sell_value_pairs.txt.)
-template <typename T, int MODE, bool NT, int NG>
+template <typename T, int MODE, bool NT, bool V7, int NG>
 __device__ __forceinline__ void
-sell_delta_consume(const SellDeltaIdx<MODE> * q, const T * __restrict__ vp, const int * g, const T * __restrict__ x, T & s)
+sell_delta_consume(const SellDeltaIdx<MODE> * q, const SellVals<T, NT, V7> & vals, const int * g, const T * __restrict__ x, T & s)
 {
 	T v[NG][4];
 	int c[NG][4];
 	T xv[NG][4];
 	#pragma unroll
 	for (int u = 0; u < NG; u++)
-		sell_group_values<T, NT>(vp + (size_t) g[u] * 4 * WAVE, v[u]);
+		vals.group(g[u], v[u]);
 	#pragma unroll
 	for (int u = 0; u < NG; u++)
 		sell_delta_cols<MODE>(q[u], c[u]);
@@ -371,9 +414,9 @@ sell_delta_consume(const SellDeltaIdx<MODE> * q, const T * __restrict__ vp, cons
 			s = fma_t<T>(v[u][t], xv[u][t], s);
 }
 
-template <typename T, int MODE, bool NT>
+template <typename T, int MODE, bool NT, bool V7>
 __device__ __forceinline__ void
-sell_delta_piped(const unsigned char * __restrict__ ip, const T * __restrict__ vp, int lane, const T * __restrict__ x, T & s, int g0, int gs, int n)
+sell_delta_piped(const unsigned char * __restrict__ ip, const SellVals<T, NT, V7> & vals, int lane, const T * __restrict__ x, T & s, int g0, int gs, int n)
 {
 	constexpr int GB = MODE == 1 ? 272 : 528;
 	if (n <= 0)
@@ -390,7 +433,7 @@ sell_delta_piped(const unsigned char * __restrict__ ip, const T * __restrict__ v
 		for (int u = 0; u < 4; u++)
 			sell_delta_load_idx<MODE, NT>(nq[u], ip + (size_t) gidx(k + 4 + u) * GB, lane);
 		const int g[4] = {gidx(k), gidx(k + 1), gidx(k + 2), gidx(k + 3)};
-		sell_delta_consume<T, MODE, NT, 4>(q, vp, g, x, s);
+		sell_delta_consume<T, MODE, NT, V7, 4>(q, vals, g, x, s);
 		#pragma unroll
 		for (int u = 0; u < 4; u++)
 		{
@@ -402,24 +445,24 @@ sell_delta_piped(const unsigned char * __restrict__ ip, const T * __restrict__ v
 	if (r >= 2)
 	{
 		const int g[2] = {gidx(k), gidx(k + 1)};
-		sell_delta_consume<T, MODE, NT, 2>(q, vp, g, x, s);
+		sell_delta_consume<T, MODE, NT, V7, 2>(q, vals, g, x, s);
 	}
 	if (r == 1)                                        // (constant indices into q: a run-time one would send the array to scratch memory)
 	{
 		const int g[1] = {gidx(k)};
-		sell_delta_consume<T, MODE, NT, 1>(q, vp, g, x, s);
+		sell_delta_consume<T, MODE, NT, V7, 1>(q, vals, g, x, s);
 	}
 	if (r == 3)
 	{
 		const int g[1] = {gidx(k + 2)};
-		sell_delta_consume<T, MODE, NT, 1>(q + 2, vp, g, x, s);
+		sell_delta_consume<T, MODE, NT, V7, 1>(q + 2, vals, g, x, s);
 	}
 }
 
 // groups g0, g0+gs, g0+2gs, ... of one slice (gs = 1: the whole slice, in order)
-template <typename T, int MODE, bool NT>
+template <typename T, int MODE, bool NT, bool V7>
 __device__ __forceinline__ T
-sell_delta_slice(const unsigned char * __restrict__ ip, const T * __restrict__ vp, int width, int lane, const T * __restrict__ x,
+sell_delta_slice(const unsigned char * __restrict__ ip, const SellVals<T, NT, V7> & vals, int width, int lane, const T * __restrict__ x,
 		int g0 = 0, int gs = 1)
 {
 	constexpr int GB = (MODE == 0 || MODE == 3) ? 16 : MODE == 1 ? 272 : MODE == 2 ? 528 : 1024;     // bytes of one index group
@@ -438,7 +481,7 @@ sell_delta_slice(const unsigned char * __restrict__ ip, const T * __restrict__ v
 	{
 		const int full = rem == 4 ? groups : last;
 		const int n = full > g0 ? (full - g0 + gs - 1) / gs : 0;
-		sell_delta_piped<T, MODE, NT>(ip, vp, lane, x, s, g0, gs, n);
+		sell_delta_piped<T, MODE, NT, V7>(ip, vals, lane, x, s, g0, gs, n);
 		g = g0 + n * gs;
 	}
 	// 16, then 12, then 8 steps in flight per trip: a slice of 7 full groups (the nlpkkt240 twin's 27-28 entries per row) is 4 + 3. The
@@ -447,32 +490,32 @@ sell_delta_slice(const unsigned char * __restrict__ ip, const T * __restrict__ v
 	const int full_end = rem == 4 ? groups : last;
 	for (; g + 3 * gs < full_end; g += 4 * gs)
 	{
-		sell_delta_group<T, MODE, NT>(ip + (size_t) g * GB, vp + (size_t) g * 4 * WAVE, lane, x, s, off);
-		sell_delta_group<T, MODE, NT>(ip + (size_t) (g + gs) * GB, vp + (size_t) (g + gs) * 4 * WAVE, lane, x, s, off);
-		sell_delta_group<T, MODE, NT>(ip + (size_t) (g + 2 * gs) * GB, vp + (size_t) (g + 2 * gs) * 4 * WAVE, lane, x, s, off);
-		sell_delta_group<T, MODE, NT>(ip + (size_t) (g + 3 * gs) * GB, vp + (size_t) (g + 3 * gs) * 4 * WAVE, lane, x, s, off);
+		sell_delta_group<T, MODE, NT, V7>(ip + (size_t) g * GB, vals, g, lane, x, s, off);
+		sell_delta_group<T, MODE, NT, V7>(ip + (size_t) (g + gs) * GB, vals, g + gs, lane, x, s, off);
+		sell_delta_group<T, MODE, NT, V7>(ip + (size_t) (g + 2 * gs) * GB, vals, g + 2 * gs, lane, x, s, off);
+		sell_delta_group<T, MODE, NT, V7>(ip + (size_t) (g + 3 * gs) * GB, vals, g + 3 * gs, lane, x, s, off);
 	}
 	for (; g + 2 * gs < full_end; g += 3 * gs)
 	{
-		sell_delta_group<T, MODE, NT>(ip + (size_t) g * GB, vp + (size_t) g * 4 * WAVE, lane, x, s, off);
-		sell_delta_group<T, MODE, NT>(ip + (size_t) (g + gs) * GB, vp + (size_t) (g + gs) * 4 * WAVE, lane, x, s, off);
-		sell_delta_group<T, MODE, NT>(ip + (size_t) (g + 2 * gs) * GB, vp + (size_t) (g + 2 * gs) * 4 * WAVE, lane, x, s, off);
+		sell_delta_group<T, MODE, NT, V7>(ip + (size_t) g * GB, vals, g, lane, x, s, off);
+		sell_delta_group<T, MODE, NT, V7>(ip + (size_t) (g + gs) * GB, vals, g + gs, lane, x, s, off);
+		sell_delta_group<T, MODE, NT, V7>(ip + (size_t) (g + 2 * gs) * GB, vals, g + 2 * gs, lane, x, s, off);
 	}
 	for (; g + gs < (rem == 4 ? groups : last); g += 2 * gs)    // 8 steps in flight per trip
 	{
-		sell_delta_group<T, MODE, NT>(ip + (size_t) g * GB, vp + (size_t) g * 4 * WAVE, lane, x, s, off);
-		sell_delta_group<T, MODE, NT>(ip + (size_t) (g + gs) * GB, vp + (size_t) (g + gs) * 4 * WAVE, lane, x, s, off);
+		sell_delta_group<T, MODE, NT, V7>(ip + (size_t) g * GB, vals, g, lane, x, s, off);
+		sell_delta_group<T, MODE, NT, V7>(ip + (size_t) (g + gs) * GB, vals, g + gs, lane, x, s, off);
 	}
 	for (; g < (rem == 4 ? groups : last); g += gs)
-		sell_delta_group<T, MODE, NT>(ip + (size_t) g * GB, vp + (size_t) g * 4 * WAVE, lane, x, s, off);
+		sell_delta_group<T, MODE, NT, V7>(ip + (size_t) g * GB, vals, g, lane, x, s, off);
 	if (rem != 4 && g == last)
 	{
 		if (rem == 1)
-			sell_delta_group<T, MODE, NT, 1>(ip + (size_t) g * GB, vp + (size_t) g * 4 * WAVE, lane, x, s, off);
+			sell_delta_group<T, MODE, NT, V7, 1>(ip + (size_t) g * GB, vals, g, lane, x, s, off);
 		else if (rem == 2)
-			sell_delta_group<T, MODE, NT, 2>(ip + (size_t) g * GB, vp + (size_t) g * 4 * WAVE, lane, x, s, off);
+			sell_delta_group<T, MODE, NT, V7, 2>(ip + (size_t) g * GB, vals, g, lane, x, s, off);
 		else
-			sell_delta_group<T, MODE, NT, 3>(ip + (size_t) g * GB, vp + (size_t) g * 4 * WAVE, lane, x, s, off);
+			sell_delta_group<T, MODE, NT, V7, 3>(ip + (size_t) g * GB, vals, g, lane, x, s, off);
 	}
 	return s;
 }
@@ -552,9 +595,9 @@ sell_pin5(SellDeltaIdx5 & q)
 		sell_pin(q.d);
 }
 
-template <typename T, bool NT, bool SCALAR>
+template <typename T, bool NT, bool V7, bool SCALAR>
 __device__ __forceinline__ T
-sell_delta_slice5_body(const unsigned char * __restrict__ ip, const T * __restrict__ vp, int width, int lane, const T * __restrict__ x,
+sell_delta_slice5_body(const unsigned char * __restrict__ ip, const SellVals<T, NT, V7> & vals, int width, int lane, const T * __restrict__ x,
 		int g0, int gs, unsigned long long mask, int off)
 {
 	const int E = __popcll(mask);
@@ -591,7 +634,7 @@ sell_delta_slice5_body(const unsigned char * __restrict__ ip, const T * __restri
 			T xv[NG][4];
 			#pragma unroll
 			for (int u = 0; u < NG; u++)
-				sell_group_values<T, NT>(vp + (size_t) g[u] * 4 * WAVE, v[u]);
+				vals.group(g[u], v[u]);
 			#pragma unroll
 			for (int u = 0; u < NG; u++)
 				sell_delta_cols5<SCALAR>(q[u], ex, lane, off, xl, c[u]);
@@ -650,7 +693,7 @@ sell_delta_slice5_body(const unsigned char * __restrict__ ip, const T * __restri
 		sell_delta_load_idx5<NT, SCALAR>(q, ip + (size_t) last * GB, rank);
 		int c[4];
 		sell_delta_cols5<SCALAR>(q, ex, lane, off, xl, c);
-		const T * vl = vp + (size_t) last * 4 * WAVE;
+		const T * vl = vals.tail(last);
 		T tv[3];
 		if (rem == 1)
 			sell_tail_values<T, NT, 1>(vl, lane, tv);
@@ -669,22 +712,62 @@ sell_delta_slice5_body(const unsigned char * __restrict__ ip, const T * __restri
 	return s;
 }
 
-template <typename T, bool NT>
+template <typename T, bool NT, bool V7>
 __device__ __forceinline__ T
-sell_delta_slice5(const unsigned char * __restrict__ ip, const T * __restrict__ vp, int width, int lane, const T * __restrict__ x,
+sell_delta_slice5(const unsigned char * __restrict__ ip, const SellVals<T, NT, V7> & vals, int width, int lane, const T * __restrict__ x,
 		int g0 = 0, int gs = 1)
 {
 	const int off = ld_stream<NT>(reinterpret_cast<const int *>(ip) + lane);
 	const unsigned long long mask = *reinterpret_cast<const unsigned long long *>(ip + 4 * WAVE);          // uniform: a scalar load
 	ip += 4 * WAVE + 16;
 	if (__popcll(mask) <= 4)
-		return sell_delta_slice5_body<T, NT, true>(ip, vp, width, lane, x, g0, gs, mask, off);
-	return sell_delta_slice5_body<T, NT, false>(ip, vp, width, lane, x, g0, gs, mask, off);
+		return sell_delta_slice5_body<T, NT, V7, true>(ip, vals, width, lane, x, g0, gs, mask, off);
+	return sell_delta_slice5_body<T, NT, V7, false>(ip, vals, width, lane, x, g0, gs, mask, off);
 }
 
-// desc[2*s] = first value element of slice s, desc[2*s+1] = byte offset of its index block | mode (0 .. 5) in the low bits
-template <typename T, bool NT>
-__global__ __launch_bounds__(SELL_BLOCK) void
+// one slice (groups g0, g0 + gs, ... of it) in its index mode; a wave-uniform branch
+template <typename T, bool NT, bool V7>
+__device__ __forceinline__ T
+sell_delta_modes(int mode, const unsigned char * __restrict__ ip, const SellVals<T, NT, V7> & vals, int width, int lane, const T * __restrict__ x,
+		int g0, int gs)
+{
+	if (mode == 0)
+		return sell_delta_slice<T, 0, NT>(ip, vals, width, lane, x, g0, gs);
+	if (mode == 1)
+		return sell_delta_slice<T, 1, NT>(ip, vals, width, lane, x, g0, gs);
+	if (mode == 2)
+		return sell_delta_slice<T, 2, NT>(ip, vals, width, lane, x, g0, gs);
+	if (mode == 3)
+		return sell_delta_slice<T, 3, NT>(ip, vals, width, lane, x, g0, gs);
+	if (mode == 5)
+		return sell_delta_slice5<T, NT>(ip, vals, width, lane, x, g0, gs);
+	return sell_delta_slice<T, 4, NT>(ip, vals, width, lane, x, g0, gs);
+}
+
+// one slice from its two descriptor words: V7 = the handle holds slices with 7-byte values (launch.hpp), each one flagged in desc[2s+1];
+// without it the code is that of the plain pairs alone
+template <typename T, bool NT, bool V7>
+__device__ __forceinline__ T
+sell_delta_one(const int64_t * __restrict__ desc, int slice, const unsigned char * __restrict__ idx, const T * __restrict__ val, int lane,
+		const T * __restrict__ x, int g0, int gs)
+{
+	const int64_t v_off = desc[2 * slice];
+	const int64_t i_word = desc[2 * slice + 1];
+	const int64_t v_next = desc[2 * slice + 2];
+	const int mode = (int) (i_word & 7);
+	const unsigned char * ip = idx + (i_word & SELL_IDX_MASK);
+	const T * vp = val + v_off + 2 * lane;
+	if (V7 && (i_word & SELL_V7_FLAG))
+		return sell_delta_modes<T, NT, V7>(mode, ip, SellVals<T, NT, V7>{vp, lane, (unsigned) (sell_v7_e0(i_word) - 1) << 20},
+				(int) sell_v7_width(v_next - v_off), lane, x, g0, gs);
+	return sell_delta_modes<T, NT, false>(mode, ip, SellVals<T, NT, false>{vp, lane, 0u}, (int) ((v_next - v_off) / WAVE), lane, x, g0, gs);
+}
+
+// desc[2*s] = first value word of slice s, desc[2*s+1] = byte offset of its index block | 7-byte values flag (bit 3) | mode (0 .. 5) in the
+// low bits, E0 of the 7-byte values in bits 48..58
+// (V7: the compiler's own choice of 109 VGPRs would cost a wave per SIMD against the plain kernel's 96; held to 5 waves it takes 92, no scratch)
+template <typename T, bool NT, bool V7>
+__global__ __launch_bounds__(SELL_BLOCK) __attribute__((amdgpu_waves_per_eu(V7 ? 5 : 1))) void
 sell_delta_kernel(const int64_t * __restrict__ desc, const unsigned char * __restrict__ idx, const T * __restrict__ val,
 		const int * __restrict__ row_of_sorted, const T * __restrict__ x, T * __restrict__ y,
 		int m, int num_slices, int beta, XcdMap map)
@@ -696,26 +779,7 @@ sell_delta_kernel(const int64_t * __restrict__ desc, const unsigned char * __res
 	const int slice = __builtin_amdgcn_readfirstlane((int) (tile * SELL_WAVES + threadIdx.x / WAVE));
 	if (slice >= num_slices)
 		return;
-	const int64_t v_off = desc[2 * slice];
-	const int64_t i_word = desc[2 * slice + 1];
-	const int64_t v_next = desc[2 * slice + 2];
-	const int mode = (int) (i_word & 7);
-	const unsigned char * ip = idx + (i_word & ~(int64_t) 15);
-	const T * vp = val + v_off + 2 * lane;
-	const int groups = (int) ((v_next - v_off) / WAVE);       // = the slice's width in steps (name kept: passed as `width`)
-	T s;
-	if (mode == 0)
-		s = sell_delta_slice<T, 0, NT>(ip, vp, groups, lane, x);
-	else if (mode == 1)
-		s = sell_delta_slice<T, 1, NT>(ip, vp, groups, lane, x);
-	else if (mode == 2)
-		s = sell_delta_slice<T, 2, NT>(ip, vp, groups, lane, x);
-	else if (mode == 3)
-		s = sell_delta_slice<T, 3, NT>(ip, vp, groups, lane, x);
-	else if (mode == 5)
-		s = sell_delta_slice5<T, NT>(ip, vp, groups, lane, x);
-	else
-		s = sell_delta_slice<T, 4, NT>(ip, vp, groups, lane, x);
+	const T s = sell_delta_one<T, NT, V7>(desc, slice, idx, val, lane, x, 0, 1);
 	const long sorted_row = (long) slice * WAVE + lane;
 	if (sorted_row < m)
 	{
@@ -727,7 +791,7 @@ sell_delta_kernel(const int64_t * __restrict__ desc, const unsigned char * __res
 // Small matrices (a few thousand slices) cannot fill 256 CUs with one wave per slice: S waves share a slice, wave w takes
 // the index groups w, w+S, ..., the S partial sums of a row meet in LDS and are added in wave order (deterministic;
 // no longer the sequential order, so parity is to tolerance). One workgroup = 4/S slices.
-template <typename T, int S, bool NT>
+template <typename T, int S, bool NT, bool V7>
 __global__ __launch_bounds__(SELL_BLOCK) void
 sell_delta_split_kernel(const int64_t * __restrict__ desc, const unsigned char * __restrict__ idx, const T * __restrict__ val,
 		const int * __restrict__ row_of_sorted, const T * __restrict__ x, T * __restrict__ y,
@@ -744,27 +808,7 @@ sell_delta_split_kernel(const int64_t * __restrict__ desc, const unsigned char *
 	const int slice = __builtin_amdgcn_readfirstlane((int) (tile * SPB + wave / S));
 	T s = 0;
 	if (slice < num_slices)
-	{
-		const int64_t v_off = desc[2 * slice];
-		const int64_t i_word = desc[2 * slice + 1];
-		const int64_t v_next = desc[2 * slice + 2];
-		const int mode = (int) (i_word & 7);
-		const unsigned char * ip = idx + (i_word & ~(int64_t) 15);
-		const T * vp = val + v_off + 2 * lane;
-		const int groups = (int) ((v_next - v_off) / WAVE);       // = the slice's width in steps (name kept: passed as `width`)
-		if (mode == 0)
-			s = sell_delta_slice<T, 0, NT>(ip, vp, groups, lane, x, w, S);
-		else if (mode == 1)
-			s = sell_delta_slice<T, 1, NT>(ip, vp, groups, lane, x, w, S);
-		else if (mode == 2)
-			s = sell_delta_slice<T, 2, NT>(ip, vp, groups, lane, x, w, S);
-		else if (mode == 3)
-			s = sell_delta_slice<T, 3, NT>(ip, vp, groups, lane, x, w, S);
-		else if (mode == 5)
-			s = sell_delta_slice5<T, NT>(ip, vp, groups, lane, x, w, S);
-		else
-			s = sell_delta_slice<T, 4, NT>(ip, vp, groups, lane, x, w, S);
-	}
+		s = sell_delta_one<T, NT, V7>(desc, slice, idx, val, lane, x, w, S);
 	s_part[wave][lane] = s;
 	__syncthreads();
 	if (w == 0 && slice < num_slices)
@@ -782,7 +826,7 @@ sell_delta_split_kernel(const int64_t * __restrict__ desc, const unsigned char *
 	}
 }
 
-template <typename T>
+template <typename T, bool V7>
 static int
 sell_delta_launch(int S, const int64_t * desc, const unsigned char * idx, const void * val, const int * row_of_sorted, const void * x, void * y,
 		int m, int num_slices, const LaunchCfg & cfg, hipStream_t stream, long * grid_out)
@@ -796,18 +840,18 @@ sell_delta_launch(int S, const int64_t * desc, const unsigned char * idx, const 
 			row_of_sorted, (const T *) x, (T *) y, m, num_slices, cfg.beta, cfg.map)
 	if (S == 1)
 	{
-		if (cfg.nt) SELLD_LAUNCH((sell_delta_kernel<T, true>));
-		else        SELLD_LAUNCH((sell_delta_kernel<T, false>));
+		if (cfg.nt) SELLD_LAUNCH((sell_delta_kernel<T, true, V7>));
+		else        SELLD_LAUNCH((sell_delta_kernel<T, false, V7>));
 	}
 	else if (S == 2)
 	{
-		if (cfg.nt) SELLD_LAUNCH((sell_delta_split_kernel<T, 2, true>));
-		else        SELLD_LAUNCH((sell_delta_split_kernel<T, 2, false>));
+		if (cfg.nt) SELLD_LAUNCH((sell_delta_split_kernel<T, 2, true, V7>));
+		else        SELLD_LAUNCH((sell_delta_split_kernel<T, 2, false, V7>));
 	}
 	else if (S == 4)
 	{
-		if (cfg.nt) SELLD_LAUNCH((sell_delta_split_kernel<T, 4, true>));
-		else        SELLD_LAUNCH((sell_delta_split_kernel<T, 4, false>));
+		if (cfg.nt) SELLD_LAUNCH((sell_delta_split_kernel<T, 4, true, V7>));
+		else        SELLD_LAUNCH((sell_delta_split_kernel<T, 4, false, V7>));
 	}
 	else
 	{
@@ -820,11 +864,17 @@ sell_delta_launch(int S, const int64_t * desc, const unsigned char * idx, const 
 }
 
 int
-launch_sell_delta(bool f32, int waves_per_slice, const int64_t * desc, const unsigned char * idx, const void * val, const int * row_of_sorted,
+launch_sell_delta(bool f32, int waves_per_slice, bool v7, const int64_t * desc, const unsigned char * idx, const void * val, const int * row_of_sorted,
 		const void * x, void * y, int m, int num_slices, const LaunchCfg & cfg, hipStream_t stream, long * grid_out)
 {
-	return f32 ? sell_delta_launch<float>(waves_per_slice, desc, idx, val, row_of_sorted, x, y, m, num_slices, cfg, stream, grid_out)
-	           : sell_delta_launch<double>(waves_per_slice, desc, idx, val, row_of_sorted, x, y, m, num_slices, cfg, stream, grid_out);
+	if (f32 && v7)
+	{
+		set_error("sell_delta: 7-byte values are fp64 only");
+		return 1;
+	}
+	return f32 ? sell_delta_launch<float, false>(waves_per_slice, desc, idx, val, row_of_sorted, x, y, m, num_slices, cfg, stream, grid_out)
+	     : v7  ? sell_delta_launch<double, true>(waves_per_slice, desc, idx, val, row_of_sorted, x, y, m, num_slices, cfg, stream, grid_out)
+	           : sell_delta_launch<double, false>(waves_per_slice, desc, idx, val, row_of_sorted, x, y, m, num_slices, cfg, stream, grid_out);
 }
 
 template <typename T, int C>

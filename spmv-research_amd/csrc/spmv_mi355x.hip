@@ -301,7 +301,7 @@ spmv_mi355x_spmv_device_async(spmv_mi355x_matrix * A, const void * x, void * y, 
 			     ? launch_sell_window(A->f32, A->sell_split, A->sellw_ns, A->d_sellw_grp, A->d_sell_desc, (const unsigned short *) A->d_sell_idx, A->d_val,
 					A->d_row_of_sorted, x, y, (int) A->m, A->sellw_lds, cfg, st, &grid)
 			     : A->sell_delta
-			     ? launch_sell_delta(A->f32, A->sell_split, A->d_sell_desc, A->d_sell_idx, A->d_val, A->d_row_of_sorted, x, y, (int) A->m,
+			     ? launch_sell_delta(A->f32, A->sell_split, A->sell_v7_slices > 0, A->d_sell_desc, A->d_sell_idx, A->d_val, A->d_row_of_sorted, x, y, (int) A->m,
 					(int) A->sell_slices, cfg, st, &grid)
 			     : launch_sell(A->f32, A->sell_c, A->d_slice_ptr, A->d_col, A->d_val, A->d_row_of_sorted, x, y, (int) A->m,
 					(int) A->sell_slices, cfg, st, &grid);
@@ -451,7 +451,7 @@ spmv_mi355x_spmv(spmv_mi355x_matrix * A, const void * x_host, void * y_host)
 }
 
 // One of the handle's stored arrays as it lies in device memory, copied to a malloc'ed host buffer (free with spmv_mi355x_free): the
-// LDS-window SELL layout and the column-blocked layout, whose host and GPU builders must give the same bytes (tests/test_gpu_parity.py).
+// SELL layouts and the column-blocked layout, whose host and GPU builders must give the same bytes (tests/test_gpu_parity.py).
 int
 spmv_mi355x_stored_array(const spmv_mi355x_matrix * A, const char * name, void ** out, size_t * bytes_out)
 {
@@ -468,7 +468,10 @@ spmv_mi355x_stored_array(const spmv_mi355x_matrix * A, const char * name, void *
 		arrs = {{"val", A->d_val, (size_t) A->sell_nnz_ext * A->vbytes}, {"idx", A->d_sell_idx, (size_t) A->sell_idx_bytes},
 		        {"desc", A->d_sell_desc, 2 * ((size_t) A->sell_slices + 1) * 8}, {"row_of_sorted", A->d_row_of_sorted, (size_t) A->m * 4},
 		        {"groups", A->d_sellw_grp, (size_t) A->sellw_groups * 16}};
-	else if (A->format == SPMV_MI355X_SELL_C_SIGMA && !A->sell_delta)
+	else if (A->format == SPMV_MI355X_SELL_C_SIGMA && A->sell_delta)
+		arrs = {{"val", A->d_val, (size_t) A->sell_val_words * A->vbytes}, {"idx", A->d_sell_idx, (size_t) A->sell_idx_bytes},
+		        {"desc", A->d_sell_desc, 2 * ((size_t) A->sell_slices + 1) * 8}, {"row_of_sorted", A->d_row_of_sorted, (size_t) A->m * 4}};
+	else if (A->format == SPMV_MI355X_SELL_C_SIGMA)
 		arrs = {{"val", A->d_val, (size_t) A->sell_nnz_ext * A->vbytes}, {"col", A->d_col, (size_t) A->sell_nnz_ext * 4},
 		        {"slice_ptr", A->d_slice_ptr, ((size_t) A->sell_slices + 1) * 8}, {"row_of_sorted", A->d_row_of_sorted, (size_t) A->m * 4}};
 	else if (A->d_coob_ent)
@@ -483,7 +486,7 @@ spmv_mi355x_stored_array(const spmv_mi355x_matrix * A, const char * name, void *
 	}
 	else
 	{
-		set_error("stored_array: only for the plain and the LDS-window SELL layouts and the column-blocked layout (this handle: %s)", A->format_name);
+		set_error("stored_array: only for the SELL layouts and the column-blocked layout (this handle: %s)", A->format_name);
 		return 1;
 	}
 	for (const Arr & a : arrs)
@@ -529,7 +532,7 @@ spmv_mi355x_sell_layout(const spmv_mi355x_matrix * A, long * C_out, long * sigma
 	if (sigma_out) *sigma_out = A->sell_sigma;
 	if (num_slices_out) *num_slices_out = A->sell_slices;
 	if (nnz_ext_out) *nnz_ext_out = A->sell_nnz_ext;
-	std::vector<int64_t> h_desc;
+	std::vector<int64_t> h_desc, plain_ptr;              // delta layout: descriptors, and where each slice starts in the plain layout
 	std::vector<unsigned char> h_idx;
 	if (A->sell_delta)
 	{
@@ -537,13 +540,18 @@ spmv_mi355x_sell_layout(const spmv_mi355x_matrix * A, long * C_out, long * sigma
 		HIP_TRY(hipMemcpy(h_desc.data(), A->d_sell_desc, h_desc.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
 		h_idx.resize((size_t) std::max<long>(A->sell_idx_bytes, 1));
 		HIP_TRY(hipMemcpy(h_idx.data(), A->d_sell_idx, (size_t) A->sell_idx_bytes, hipMemcpyDeviceToHost));
+		plain_ptr.assign((size_t) A->sell_slices + 1, 0);
+		for (long sl = 0; sl < A->sell_slices; sl++)
+		{
+			const int64_t words = h_desc[2 * sl + 2] - h_desc[2 * sl];
+			plain_ptr[sl + 1] = plain_ptr[sl] + ((h_desc[2 * sl + 1] & spmv::SELL_V7_FLAG) ? spmv::sell_v7_width(words) * 64 : words);
+		}
 	}
 	if (slice_ptr_out)
 	{
 		*slice_ptr_out = (int64_t *) malloc(((size_t) A->sell_slices + 1) * sizeof(int64_t));
 		if (A->sell_delta)
-			for (long sl = 0; sl <= A->sell_slices; sl++)
-				(*slice_ptr_out)[sl] = h_desc[2 * sl];
+			memcpy(*slice_ptr_out, plain_ptr.data(), ((size_t) A->sell_slices + 1) * sizeof(int64_t));
 		else
 			HIP_TRY(hipMemcpy(*slice_ptr_out, A->d_slice_ptr, ((size_t) A->sell_slices + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
 	}
@@ -556,10 +564,10 @@ spmv_mi355x_sell_layout(const spmv_mi355x_matrix * A, long * C_out, long * sigma
 			// decode the compressed indices back to the plain column-major layout
 			for (long sl = 0; sl < A->sell_slices; sl++)
 			{
-				const int64_t vb = h_desc[2 * sl];
-				const long width = (h_desc[2 * sl + 2] - vb) / 64;
+				const int64_t vb = plain_ptr[sl];
+				const long width = (plain_ptr[sl + 1] - vb) / 64;
 				const int md = (int) (h_desc[2 * sl + 1] & 7);
-				const unsigned char * ib = h_idx.data() + (h_desc[2 * sl + 1] & ~(int64_t) 15);
+				const unsigned char * ib = h_idx.data() + (h_desc[2 * sl + 1] & spmv::SELL_IDX_MASK);
 				const int * offs = reinterpret_cast<const int *>(ib);
 				unsigned long long exmask = 0;
 				if (md == 3)
@@ -601,27 +609,48 @@ spmv_mi355x_sell_layout(const spmv_mi355x_matrix * A, long * C_out, long * sigma
 	if (val_out)
 	{
 		*val_out = (double *) malloc(ne * sizeof(double));
+		const size_t nw = A->sell_delta ? (size_t) A->sell_val_words : (size_t) A->sell_nnz_ext;        // elements stored
+		std::vector<double> raw(std::max<size_t>(nw, 1));
 		if (!A->f32)
-			HIP_TRY(hipMemcpy(*val_out, A->d_val, (size_t) A->sell_nnz_ext * sizeof(double), hipMemcpyDeviceToHost));
+			HIP_TRY(hipMemcpy(raw.data(), A->d_val, nw * sizeof(double), hipMemcpyDeviceToHost));
 		else
 		{
-			std::vector<float> tmp(ne);
-			HIP_TRY(hipMemcpy(tmp.data(), A->d_val, (size_t) A->sell_nnz_ext * sizeof(float), hipMemcpyDeviceToHost));
-			for (size_t i = 0; i < (size_t) A->sell_nnz_ext; i++)
-				(*val_out)[i] = tmp[i];
+			std::vector<float> tmp(std::max<size_t>(nw, 1));
+			HIP_TRY(hipMemcpy(tmp.data(), A->d_val, nw * sizeof(float), hipMemcpyDeviceToHost));
+			for (size_t i = 0; i < nw; i++)
+				raw[i] = tmp[i];
 		}
-		if (A->sell_delta)
+		if (!A->sell_delta)
+			memcpy(*val_out, raw.data(), nw * sizeof(double));
+		else
 		{
-			// the delta layout keeps a lane's steps in pairs (launch.hpp: sell_pair_pos): back to plain column-major
-			std::vector<double> slice;
+			// the delta layout keeps a lane's steps in pairs (launch.hpp: sell_pair_pos), the full groups of a slice with 7-byte values as
+			// lo / hi planes (launch.hpp: sell_v7_lo_pos, sell_v7_hi_bit): back to plain column-major fp64
 			for (long sl = 0; sl < A->sell_slices; sl++)
 			{
-				const int64_t vb = h_desc[2 * sl];
-				const long width = (h_desc[2 * sl + 2] - vb) / 64;
-				slice.assign(*val_out + vb, *val_out + vb + width * 64);
+				const int64_t vb = h_desc[2 * sl], pb = plain_ptr[sl];
+				const long width = (plain_ptr[sl + 1] - pb) / 64;
+				const bool v7 = h_desc[2 * sl + 1] & spmv::SELL_V7_FLAG;
+				const long full = v7 ? width / 4 : 0;
+				const unsigned k0 = (unsigned) (spmv::sell_v7_e0(h_desc[2 * sl + 1]) - 1) << 20;
+				const unsigned char * b = reinterpret_cast<const unsigned char *>(raw.data() + vb);
 				for (long k = 0; k < width; k++)
 					for (long r = 0; r < 64; r++)
-						(*val_out)[vb + k * 64 + r] = slice[(size_t) spmv::sell_pair_pos(k, width, r)];
+					{
+						double v;
+						if (k < 4 * full)
+						{
+							uint32_t lo;
+							memcpy(&lo, b + spmv::sell_v7_lo_pos(k, r), 4);
+							const long hb = spmv::sell_v7_hi_bit(k, r);
+							const unsigned h = (unsigned) b[hb / 8] | (unsigned) b[hb / 8 + 1] << 8 | (unsigned) b[hb / 8 + 2] << 16;
+							const uint64_t bits = (uint64_t) spmv::sell_v7_decode_hi(h, k0) << 32 | lo;
+							memcpy(&v, &bits, 8);
+						}
+						else
+							v = raw[(size_t) (vb + full * spmv::SELL_V7_GROUP_WORDS + spmv::sell_pair_pos(k, width, r) - full * 256)];
+						(*val_out)[pb + k * 64 + r] = v;
+					}
 			}
 		}
 	}

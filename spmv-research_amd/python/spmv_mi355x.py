@@ -28,7 +28,7 @@ class Opts(C.Structure):
                 ("col_filter_mode", C.c_int), ("sell_delta", C.c_int), ("convert_on", C.c_int),
                 ("symmetric_input", C.c_int), ("rows_per_group", C.c_int), ("col_blocks", C.c_int),
                 ("sell_window", C.c_int), ("kahan", C.c_int), ("sell_group", C.c_int), ("placement", C.c_int),
-                ("placement_budget_gib", C.c_int)]
+                ("placement_budget_gib", C.c_int), ("sell_values", C.c_int)]
 
 
 # every symbol declared in include/spmv_mi355x.h (checked by tests/test_abi.py)

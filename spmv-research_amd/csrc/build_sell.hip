@@ -6,6 +6,30 @@
 namespace spmv {
 
 // ---------------------------------------------------------------------------------------------------- SELL build
+// row_of_sorted[m]: the rows of every window of sigma rows sorted by length, descending and stable (a counting sort per window)
+static std::vector<int>
+sigma_sort(const int * rp, long m, long sigma)
+{
+	std::vector<int> row_of_sorted(std::max<long>(m, 1));
+	const long num_windows = (m + sigma - 1) / sigma;
+	#pragma omp parallel for num_threads(spmv::host_threads()) schedule(dynamic, 4)
+	for (long w = 0; w < num_windows; w++)
+	{
+		long s = w * sigma, e = std::min(m, s + sigma);
+		int maxlen = 0;
+		for (long i = s; i < e; i++)
+			maxlen = std::max(maxlen, rp[i + 1] - rp[i]);
+		std::vector<long> cnt((size_t) maxlen + 2, 0);
+		for (long i = s; i < e; i++)
+			cnt[maxlen - (rp[i + 1] - rp[i]) + 1]++;
+		for (int b = 0; b <= maxlen; b++)
+			cnt[b + 1] += cnt[b];
+		for (long i = s; i < e; i++)
+			row_of_sorted[s + cnt[maxlen - (rp[i + 1] - rp[i])]++] = (int) i;
+	}
+	return row_of_sorted;
+}
+
 // Host-side CSR -> SELL-C-sigma (the reference converts on the host too: sell_sorted.cpp:112-298, sellcs_format.c:137-200).
 // Window sort: stable, DESCENDING row length inside each window of sigma rows (radix_sort.c:103-122 semantics).
 static int
@@ -30,24 +54,7 @@ build_sell(spmv_mi355x_matrix * A, const int * rp, const int * ci, const double 
 		A->mem_footprint = (double) (num_slices + 1) * sizeof(int64_t) + (double) nnz_ext * (A->vbytes + 4) + (double) m * 4;
 		return 0;
 	}
-	std::vector<int> row_of_sorted(std::max<long>(m, 1));
-	const long num_windows = (m + sigma - 1) / sigma;
-	#pragma omp parallel for num_threads(spmv::host_threads()) schedule(dynamic, 4)
-	for (long w = 0; w < num_windows; w++)
-	{
-		long s = w * sigma, e = std::min(m, s + sigma);
-		// counting sort by length, descending, stable
-		int maxlen = 0;
-		for (long i = s; i < e; i++)
-			maxlen = std::max(maxlen, rp[i + 1] - rp[i]);
-		std::vector<long> cnt((size_t) maxlen + 2, 0);
-		for (long i = s; i < e; i++)
-			cnt[maxlen - (rp[i + 1] - rp[i]) + 1]++;
-		for (int b = 0; b <= maxlen; b++)
-			cnt[b + 1] += cnt[b];
-		for (long i = s; i < e; i++)
-			row_of_sorted[s + cnt[maxlen - (rp[i + 1] - rp[i])]++] = (int) i;
-	}
+	const std::vector<int> row_of_sorted = sigma_sort(rp, m, sigma);
 	std::vector<int64_t> slice_ptr((size_t) num_slices + 1, 0);
 	#pragma omp parallel for num_threads(spmv::host_threads())
 	for (long sl = 0; sl < num_slices; sl++)
@@ -143,50 +150,66 @@ sell5_exceptions(const int * rp, const int * ci, const int * rows, long maxlen, 
 	return mask;
 }
 
-// SELL-64-sigma-delta build (layout: kernels_sell.hip). Same sigma-window sort and slice widths as build_sell with C = 64,
+// the XCD tile map and the memory footprint of a delta handle whose slices, stored value words and index bytes are set
+static void
+sell_delta_map(spmv_mi355x_matrix * A, const int64_t * val_ptr)
+{
+	const long num_slices = A->sell_slices;
+	const long spt = sell_slices_per_tile() / A->sell_split;       // slices per workgroup
+	A->cfg.map = xcd_map_balanced(val_ptr, num_slices, spt, resolve_remap(A->remap, (num_slices + spt - 1) / spt));
+	A->mem_footprint = (double) (num_slices + 1) * 16 + (double) A->sell_val_words * A->vbytes + (double) A->sell_idx_bytes + (double) A->m * 4;
+}
+
+// the GPU builder's arrays into the handle
+static void
+sell_delta_install(spmv_mi355x_matrix * A, const SellDeltaArrays & r)
+{
+	A->d_row_of_sorted = r.row_of_sorted;
+	A->d_sell_desc = r.desc;
+	A->d_sell_idx = r.idx;
+	A->d_val = r.val;
+	std::copy(r.mode_counts, r.mode_counts + 4, A->sell_mode_slices);
+	A->sell_v7_slices = r.v7_slices;
+	A->sell_slices = (long) r.val_ptr.size() - 1;
+	A->sell_nnz_ext = r.nnz_ext;
+	A->sell_val_words = r.val_words;
+	A->sell_idx_bytes = r.idx_bytes;
+	sell_delta_map(A, r.val_ptr.data());
+}
+
+// format name, kernel name and nontemporal rule of a delta handle
+static void
+sell_delta_names(spmv_mi355x_matrix * A, const spmv_mi355x_opts & o)
+{
+	const char * pf = A->f32 ? "f" : "d";
+	const char * v7 = A->sell_v7_slices ? "_v7" : "";
+	if (A->sell_split > 1)
+		snprintf(A->format_name, sizeof(A->format_name), "MI355X_SELLD_%d_%ld_w%d_%s%s", A->sell_c, A->sell_sigma, A->sell_split, pf, v7);
+	else
+		snprintf(A->format_name, sizeof(A->format_name), "MI355X_SELLD_%d_%ld_%s%s", A->sell_c, A->sell_sigma, pf, v7);
+	snprintf(A->kernel_name, sizeof(A->kernel_name), "sell_delta_kernel");
+	if (A->sell_v7_slices && o.nontemporal == 0)
+		A->cfg.nt = A->mem_footprint > 192.0 * 1024 * 1024 ? 1 : 0;      // the auto rule of init_handle on the bytes really stored
+}
+
+// SELL-64-sigma-delta build (layout: sell_delta_layout.hpp). Same sigma-window sort and slice widths as build_sell with C = 64,
 // widths padded to a multiple of 4 steps; per slice the narrowest index encoding that holds every (step, lane) delta.
 static int
 build_sell_delta(spmv_mi355x_matrix * A, int sell_values, const int * rp, const int * ci, const double * va)
 {
 	const long m = A->m;
-	constexpr int C = 64;
+	constexpr int C = SELL_DELTA_C;
 	const long sigma = A->sell_sigma;
 	const long num_slices = (m + C - 1) / C;
 	if (A->convert_on_device)
 	{
-		std::vector<int64_t> val_ptr;
-		int64_t nnz_ext = 0, idx_bytes = 0, val_words = 0;
-		void * d_val = nullptr;
-		if (sell_delta_convert_device(A->f32, m, A->n, A->nnz, sigma, sell_values, rp, ci, va, &A->d_row_of_sorted, &A->d_sell_desc, &A->d_sell_idx,
-				&d_val, val_ptr, A->sell_mode_slices, &nnz_ext, &idx_bytes, &val_words, &A->sell_v7_slices))
+		SellDeltaArrays r;
+		if (sell_delta_convert_device(A->f32, m, A->n, A->nnz, sigma, sell_values, rp, ci, va, r))
 			return 1;
-		A->d_val = d_val;
-		A->sell_slices = num_slices;
-		A->sell_nnz_ext = nnz_ext;
-		A->sell_val_words = val_words;
-		A->sell_idx_bytes = idx_bytes;
-		const long spt = sell_slices_per_tile() / A->sell_split;
-		A->cfg.map = xcd_map_balanced(val_ptr.data(), num_slices, spt, resolve_remap(A->remap, (num_slices + spt - 1) / spt));
-		A->mem_footprint = (double) (num_slices + 1) * 16 + (double) val_words * A->vbytes + (double) idx_bytes + (double) m * 4;
+		sell_delta_install(A, r);
 		return 0;
 	}
-	std::vector<int> row_of_sorted(std::max<long>(m, 1));
-	const long num_windows = (m + sigma - 1) / sigma;
-	#pragma omp parallel for num_threads(spmv::host_threads()) schedule(dynamic, 4)
-	for (long w = 0; w < num_windows; w++)
-	{
-		long s = w * sigma, e = std::min(m, s + sigma);
-		int maxlen = 0;
-		for (long i = s; i < e; i++)
-			maxlen = std::max(maxlen, rp[i + 1] - rp[i]);
-		std::vector<long> cnt((size_t) maxlen + 2, 0);
-		for (long i = s; i < e; i++)
-			cnt[maxlen - (rp[i + 1] - rp[i]) + 1]++;
-		for (int b = 0; b <= maxlen; b++)
-			cnt[b + 1] += cnt[b];
-		for (long i = s; i < e; i++)
-			row_of_sorted[s + cnt[maxlen - (rp[i + 1] - rp[i])]++] = (int) i;
-	}
+	const std::vector<int> row_of_sorted = sigma_sort(rp, m, sigma);
 	// pass 1: width and mode of every slice
 	std::vector<int64_t> val_ptr((size_t) num_slices + 1, 0), idx_ptr((size_t) num_slices + 1, 0);
 	std::vector<unsigned char> mode((size_t) std::max<long>(num_slices, 1), 4);
@@ -201,16 +224,14 @@ build_sell_delta(spmv_mi355x_matrix * A, int sell_values, const int * rp, const 
 			width = std::max<long>(width, rp[o + 1] - rp[o]);
 		}
 		const long maxlen = width;
-		width = (width + 3) / 4 * 4;
+		width = (width + 3) / 4 * 4;                     // index groups cover the width rounded up to 4 steps
 		long maxdelta = 0;
 		// step-invariant lane offsets: a full slice of equally long rows whose step-k columns are c_k[lane 0] + off[lane] with the
 		// SAME off for every step (rows of one kind of a stencil: column = row + const_k). off = lane is the affine case.
-		bool rowoff = (sl + 1) * C <= m && A->n >= C && maxlen > 0;
-		for (long i = sl * C; i < i_e && rowoff; i++)
-		{
-			int o = row_of_sorted[i];
-			rowoff = (rp[o + 1] - rp[o]) == maxlen;
-		}
+		bool equal_len = (sl + 1) * C <= m && A->n >= C && maxlen > 0;
+		for (long i = sl * C; i < i_e && equal_len; i++)
+			equal_len = (rp[row_of_sorted[i] + 1] - rp[row_of_sorted[i]]) == maxlen;
+		bool rowoff = equal_len;
 		bool affine = (sl + 1) * C <= m && A->n >= C && maxlen == 0;      // an all-empty slice stores nothing either
 		if (rowoff)
 		{
@@ -244,32 +265,25 @@ build_sell_delta(spmv_mi355x_matrix * A, int sell_values, const int * rp, const 
 			if (hi >= 0)
 				maxdelta = std::max<long>(maxdelta, (long) hi - lo);
 		}
-		// lane offsets with exceptions (mode 5, kernels_sell.hip): equally long rows, not all of one pattern, but at least 48 of the
-		// 64 agree with one of the first four lanes taken as the reference (the same rule as convert_sell.hip: same bytes)
+		// lane offsets with exceptions (mode 5): equally long rows, not all of one pattern, but most of them agree with one of the
+		// first four lanes taken as the reference (the same rule as convert_sell.hip: same bytes)
 		int ref = -1, nex = 0;
-		{
-			bool equal_len = (sl + 1) * C <= m && A->n >= C && maxlen > 0;
-			for (long i = sl * C; i < i_e && equal_len; i++)
-				equal_len = (rp[row_of_sorted[i] + 1] - rp[row_of_sorted[i]]) == maxlen;
-			if (equal_len && !rowoff && !(sell_modes_off() & 4))
-				for (int r = 0; r < 4 && ref < 0; r++)
+		if (equal_len && !rowoff && !(sell_modes_off() & 4))
+			for (int r = 0; r < 4 && ref < 0; r++)
+			{
+				bool hard;
+				const int e = __builtin_popcountll(sell5_exceptions(rp, ci, row_of_sorted.data() + sl * C, maxlen, r, hard));
+				if (sell5_accepts(e, hard))
 				{
-					bool hard;
-					const int e = __builtin_popcountll(sell5_exceptions(rp, ci, row_of_sorted.data() + sl * C, maxlen, r, hard));
-					if (C - e >= 48 && e > 0 && !hard)
-					{
-						ref = r;
-						nex = e;
-					}
+					ref = r;
+					nex = e;
 				}
-		}
-		const int md = (affine && !(sell_modes_off() & 1)) ? 0 : (rowoff && !(sell_modes_off() & 2)) ? 3 : ref >= 0 ? 5 : maxdelta < 256 ? 1 : maxdelta < 65536 ? 2 : 4;
-		mode[sl] = (unsigned char) (md == 5 ? (5 | ref << 3) : md);
-		val_ptr[sl + 1] = maxlen * C;                    // values: exact width; index groups: rounded up to 4 steps
-		idx_ptr[sl + 1] = md == 5 ? (4 * C + 16) + (width / 4) * (16 + (nex + 3) / 4 * 16)
-		                          : (md == 3 ? 4 * C : 0) + (width / 4) * ((md == 0 || md == 3) ? 16 : md == 1 ? 272 : md == 2 ? 528 : 1024);
+			}
+		mode[sl] = (unsigned char) sell_mode_byte(affine, rowoff, ref, maxdelta, sell_modes_off());
+		val_ptr[sl + 1] = sell_slice_val_words(maxlen, 0);
+		idx_ptr[sl + 1] = sell_slice_idx_bytes(mode[sl] & 7, nex, maxlen);
 	}
-	// 7-byte values (launch.hpp): a slice qualifies on the values of its full groups of 4 steps (padding 0.0 always fits)
+	// 7-byte values: a slice qualifies on the values of its full groups of 4 steps (padding 0.0 always fits)
 	std::vector<int> v7_e0((size_t) std::max<long>(num_slices, 1), 0);
 	{
 		int64_t plain = 0;
@@ -295,7 +309,7 @@ build_sell_delta(spmv_mi355x_matrix * A, int sell_values, const int * rp, const 
 				if (full > 0 && r.ok())
 				{
 					v7_e0[sl] = r.e0();
-					val_ptr[sl + 1] = full * SELL_V7_GROUP_WORDS + (maxlen - 4 * full) * C;
+					val_ptr[sl + 1] = sell_slice_val_words(maxlen, full);
 				}
 			}
 		}
@@ -304,11 +318,11 @@ build_sell_delta(spmv_mi355x_matrix * A, int sell_values, const int * rp, const 
 	A->sell_nnz_ext = 0;
 	for (long sl = 0; sl < num_slices; sl++)
 	{
-		A->sell_nnz_ext += v7_e0[sl] ? sell_v7_width(val_ptr[sl + 1]) * C : val_ptr[sl + 1];
+		A->sell_nnz_ext += sell_slice_width(val_ptr[sl + 1], v7_e0[sl] != 0) * C;
 		A->sell_v7_slices += v7_e0[sl] != 0;
 		val_ptr[sl + 1] += val_ptr[sl];
 		idx_ptr[sl + 1] += idx_ptr[sl];
-		A->sell_mode_slices[((mode[sl] & 7) == 0 || (mode[sl] & 7) == 3 || (mode[sl] & 7) == 5) ? 3 : (mode[sl] & 7) == 1 ? 0 : (mode[sl] & 7) == 2 ? 1 : 2]++;
+		A->sell_mode_slices[sell_mode_bucket(mode[sl])]++;
 	}
 	const int64_t val_words = val_ptr[num_slices];
 	const int64_t idx_bytes = idx_ptr[num_slices];
@@ -320,14 +334,14 @@ build_sell_delta(spmv_mi355x_matrix * A, int sell_values, const int * rp, const 
 	{
 		const int64_t vb = val_ptr[sl];
 		const int e0 = v7_e0[sl];
-		const long maxlen = e0 ? sell_v7_width(val_ptr[sl + 1] - vb) : (val_ptr[sl + 1] - vb) / C;
+		const long maxlen = sell_slice_width(val_ptr[sl + 1] - vb, e0 != 0);
 		const long width = (maxlen + 3) / 4 * 4;
 		const long full = e0 ? maxlen / 4 : 0;           // groups stored as 7-byte records
 		unsigned char * vbytes = reinterpret_cast<unsigned char *>(val.data() + vb);
 		const int md = mode[sl] & 7, ref = mode[sl] >> 3;
 		unsigned char * ib = idx.data() + idx_ptr[sl];
 		desc[2 * sl] = vb;
-		desc[2 * sl + 1] = idx_ptr[sl] | md | (e0 ? SELL_V7_FLAG | (int64_t) e0 << 48 : 0);
+		desc[2 * sl + 1] = sell_desc_word(idx_ptr[sl], md, e0);
 		const long i_e = std::min(m, (sl + 1) * C);
 		int min_off = 0;
 		unsigned long long exmask = 0;
@@ -348,7 +362,7 @@ build_sell_delta(spmv_mi355x_matrix * A, int sell_values, const int * rp, const 
 			}
 			reinterpret_cast<unsigned long long *>(ib + 4 * C)[0] = exmask;
 			reinterpret_cast<unsigned long long *>(ib + 4 * C)[1] = 0ull;
-			ib += 4 * C + 16;
+			ib += sell_header_bytes(5);
 		}
 		if (md == 3)
 		{
@@ -360,7 +374,7 @@ build_sell_delta(spmv_mi355x_matrix * A, int sell_values, const int * rp, const 
 				reinterpret_cast<int *>(ib)[r] = off;
 				min_off = std::min(min_off, off);
 			}
-			ib += 4 * C;
+			ib += sell_header_bytes(3);
 		}
 		for (long k = 0; k < width; k++)
 		{
@@ -378,8 +392,7 @@ build_sell_delta(spmv_mi355x_matrix * A, int sell_values, const int * rp, const 
 			if (md == 5)                               // ... the reference lane's
 				base = k < maxlen ? ci[rp[row_of_sorted[sl * C + ref]] + k] : -min_off;
 			const long g = k / 4, u = k % 4;
-			const long gbytes = md == 5 ? 16 + (nex + 3) / 4 * 16 : (md == 0 || md == 3) ? 16 : md == 1 ? 272 : md == 2 ? 528 : 1024;
-			unsigned char * gp = ib + g * gbytes;
+			unsigned char * gp = ib + g * sell_group_bytes(md, nex);
 			if (md != 4)
 				reinterpret_cast<int *>(gp)[u] = base;
 			for (int r = 0; r < C; r++)
@@ -408,14 +421,14 @@ build_sell_delta(spmv_mi355x_matrix * A, int sell_values, const int * rp, const 
 						vbytes[(hb + b) / 8] = (unsigned char) (h >> b);
 				}
 				else if (k < maxlen)                           // steps past the longest row exist in the index groups only
-					val[vb + full * SELL_V7_GROUP_WORDS + sell_pair_pos(k, maxlen, r) - full * 4 * C] = v;
+					val[vb + sell_pair_slot(k, maxlen, r, full)] = v;
 				const unsigned d = (unsigned) (c - base);
 				if (md == 5)
 				{
-					// an exception lane's correction of this step: one signed byte at 4 * (its rank among the exception lanes) + u
-					// (the idx array starts out zeroed: padding steps and the tail of the 16-byte-padded group stay 0)
+					// an exception lane's correction of this step (the idx array starts out zeroed: padding steps and the tail of the
+					// 16-byte-padded group stay 0)
 					if (((exmask >> r) & 1ull) && k < maxlen)
-						reinterpret_cast<signed char *>(gp + 16)[4 * __builtin_popcountll(exmask & ((1ull << r) - 1ull)) + u] = (signed char) (c - (base + off5[r]));
+						reinterpret_cast<signed char *>(gp)[sell5_corr_pos(__builtin_popcountll(exmask & ((1ull << r) - 1ull)), (int) u)] = (signed char) (c - (base + off5[r]));
 					continue;
 				}
 				if (md == 0 || md == 3)
@@ -430,14 +443,11 @@ build_sell_delta(spmv_mi355x_matrix * A, int sell_values, const int * rp, const 
 		}
 	}
 	desc[2 * num_slices] = val_words;
-	desc[2 * num_slices + 1] = idx_bytes | 4;
+	desc[2 * num_slices + 1] = sell_desc_word(idx_bytes, 4, 0);
 	A->sell_slices = num_slices;
 	A->sell_val_words = val_words;
 	A->sell_idx_bytes = idx_bytes;
-	{
-		const long spt = sell_slices_per_tile() / A->sell_split;       // slices per workgroup
-		A->cfg.map = xcd_map_balanced(val_ptr.data(), num_slices, spt, resolve_remap(A->remap, (num_slices + spt - 1) / spt));
-	}
+	sell_delta_map(A, val_ptr.data());
 	if (dev_alloc(&A->d_sell_desc, desc.size()))
 		return 1;
 	HIP_TRY(hipMemcpy(A->d_sell_desc, desc.data(), desc.size() * sizeof(int64_t), hipMemcpyHostToDevice));
@@ -448,7 +458,6 @@ build_sell_delta(spmv_mi355x_matrix * A, int sell_values, const int * rp, const 
 		return 1;
 	if (upload_ints(row_of_sorted.data(), (size_t) m, &A->d_row_of_sorted))
 		return 1;
-	A->mem_footprint = (double) (num_slices + 1) * 16 + (double) val_words * A->vbytes + (double) idx_bytes + (double) m * 4;
 	return 0;
 }
 
@@ -728,15 +737,15 @@ build_sell_family(spmv_mi355x_matrix * A, const spmv_mi355x_opts & o, const int 
 			}
 		}
 	}
-	rc = A->sell_delta ? build_sell_delta(A, sell_values_env(o.sell_values), rp, ci, va) : build_sell(A, rp, ci, va);
-	if (A->sell_delta && A->sell_split > 1)
-		snprintf(A->format_name, sizeof(A->format_name), "MI355X_SELLD_%d_%ld_w%d_%s%s", C, sigma, A->sell_split, pf, A->sell_v7_slices ? "_v7" : "");
-	else
-		snprintf(A->format_name, sizeof(A->format_name), "MI355X_SELL%s_%d_%ld_%s%s", A->sell_delta ? "D" : "", C, sigma, pf, A->sell_v7_slices ? "_v7" : "");
-	snprintf(A->kernel_name, sizeof(A->kernel_name), A->sell_delta ? "sell_delta_kernel" : "sell_kernel");
-	if (A->sell_v7_slices && o.nontemporal == 0)
-		A->cfg.nt = A->mem_footprint > 192.0 * 1024 * 1024 ? 1 : 0;      // the auto rule of init_handle on the bytes really stored
-	return rc;
+	if (A->sell_delta)
+	{
+		rc = build_sell_delta(A, sell_values_env(o.sell_values), rp, ci, va);
+		sell_delta_names(A, o);
+		return rc;
+	}
+	snprintf(A->format_name, sizeof(A->format_name), "MI355X_SELL_%d_%ld_%s", C, sigma, pf);
+	snprintf(A->kernel_name, sizeof(A->kernel_name), "sell_kernel");
+	return build_sell(A, rp, ci, va);
 }
 
 
@@ -746,9 +755,8 @@ build_sell_family(spmv_mi355x_matrix * A, const spmv_mi355x_opts & o, const int 
 int
 build_sell_delta_resident(spmv_mi355x_matrix * A, const spmv_mi355x_opts & o, const int * d_rp, const int * d_ci, const double * d_va)
 {
-	constexpr int C = 64;
+	constexpr int C = SELL_DELTA_C;
 	const long m = A->m;
-	const char * pf = A->f32 ? "f" : "d";
 	if ((o.sell_c && o.sell_c != C) || o.sell_delta == 2 || o.convert_on == 2 || o.sell_window == 1)
 	{
 		set_error("create_from_stream: only the SELL-64 delta layout converted on the device is built from a device-resident CSR");
@@ -772,28 +780,11 @@ build_sell_delta_resident(spmv_mi355x_matrix * A, const spmv_mi355x_opts & o, co
 	A->sell_delta = true;
 	A->convert_on_device = true;
 	A->sell_split = S;
-	std::vector<int64_t> val_ptr;
-	int64_t nnz_ext = 0, idx_bytes = 0, val_words = 0;
-	void * d_val = nullptr;
-	if (sell_delta_convert_resident(A->f32, m, A->n, A->nnz, sigma, sell_values_env(o.sell_values), d_rp, d_ci, d_va, &A->d_row_of_sorted, &A->d_sell_desc,
-			&A->d_sell_idx, &d_val, val_ptr, A->sell_mode_slices, &nnz_ext, &idx_bytes, &val_words, &A->sell_v7_slices))
+	SellDeltaArrays r;
+	if (sell_delta_convert_resident(A->f32, m, A->n, A->nnz, sigma, sell_values_env(o.sell_values), d_rp, d_ci, d_va, r))
 		return 1;
-	A->d_val = d_val;
-	A->sell_slices = num_slices;
-	A->sell_nnz_ext = nnz_ext;
-	A->sell_val_words = val_words;
-	A->sell_idx_bytes = idx_bytes;
-	const long spt = sell_slices_per_tile() / A->sell_split;
-	A->cfg.map = xcd_map_balanced(val_ptr.data(), num_slices, spt, resolve_remap(A->remap, (num_slices + spt - 1) / spt));
-	A->mem_footprint = (double) (num_slices + 1) * 16 + (double) val_words * A->vbytes + (double) idx_bytes + (double) m * 4;
-	const char * v7 = A->sell_v7_slices ? "_v7" : "";
-	if (A->sell_split > 1)
-		snprintf(A->format_name, sizeof(A->format_name), "MI355X_SELLD_%d_%ld_w%d_%s%s", C, sigma, A->sell_split, pf, v7);
-	else
-		snprintf(A->format_name, sizeof(A->format_name), "MI355X_SELLD_%d_%ld_%s%s", C, sigma, pf, v7);
-	snprintf(A->kernel_name, sizeof(A->kernel_name), "sell_delta_kernel");
-	if (A->sell_v7_slices && o.nontemporal == 0)
-		A->cfg.nt = A->mem_footprint > 192.0 * 1024 * 1024 ? 1 : 0;      // the auto rule of init_handle on the bytes really stored
+	sell_delta_install(A, r);
+	sell_delta_names(A, o);
 	return 0;
 }
 

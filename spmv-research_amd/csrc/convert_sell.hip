@@ -1,7 +1,7 @@
 // CSR -> SELL-64-sigma-delta ON THE GPU.
 //
 // The reference converts on the host (sell_sorted.cpp:112-298, sellcs_format.c:137-200; the driver reports it as
-// "time convert to format", bench.cpp:600-603) and so did build_sell_delta() in spmv_mi355x.hip, which stays as the
+// "time convert to format", bench.cpp:600-603) and so did build_sell_delta() in build_sell.hip, which stays as the
 // checker: this path must produce the SAME bytes (tests/test_gpu_parity.py compares the two layouts).
 //   1. row lengths; stable sort of the rows of every sigma-window by length, descending (radix_sort.c:103-122 semantics):
 //      one segmented radix sort (hipCUB; radix sort is stable, so equal lengths keep their row order);
@@ -57,18 +57,10 @@ wave_max_i(int v)
 	return v;
 }
 
-__device__ __forceinline__ long
-group_bytes(int md)
-{
-	return (md == 0 || md == 3) ? 16 : md == 1 ? 272 : md == 2 ? 528 : 1024;
-}
-
-// Mode 5 (kernels_sell.hip): every lane of a slice of equally long rows gets the offset off = its first column - the reference lane's
+// Mode 5 (sell_delta_layout.hpp): every lane of a slice of equally long rows gets the offset off = its first column - the reference lane's
 // first column; a lane is REGULAR when column_k = column_k[reference] + off at every step, an EXCEPTION when the difference fits a
-// signed byte at every step, HARD otherwise. The reference lanes 0..3 are tried in turn; the first one with at least 48 regular lanes,
-// at least one exception and no hard lane is taken. Returns the 64-bit mask of the exception lanes (every lane the same value) and,
-// through `hard`, whether some lane needs more than 8 bits.
-constexpr int SELL5_MIN_REGULAR = 48;
+// signed byte at every step, HARD otherwise. The reference lanes 0..3 are tried in turn; the first one sell5_accepts is taken. Returns
+// the 64-bit mask of the exception lanes (every lane the same value) and, through `hard`, whether some lane needs more than 8 bits.
 
 __device__ __forceinline__ unsigned long long
 sell5_exceptions(const int * __restrict__ ci, int start, int maxlen, int r, bool & hard)
@@ -100,7 +92,7 @@ sell5_reference(const int * __restrict__ ci, int start, int maxlen, int lane, in
 	{
 		bool hard;
 		const int e = __popcll(sell5_exceptions(ci, start, maxlen, r, hard));
-		if (WAVE - e >= SELL5_MIN_REGULAR && e > 0 && !hard)
+		if (sell5_accepts(e, hard))
 		{
 			ref = r;
 			nex = e;
@@ -126,7 +118,7 @@ slice_shape_kernel(const int * __restrict__ rp, const int * __restrict__ ci, con
 		len = rp[o + 1] - start;
 	}
 	const int maxlen = wave_max_i(len);
-	const int width = (maxlen + 3) / 4 * 4;
+	const int width = (maxlen + 3) / 4 * 4;            // index groups cover the width rounded up to 4 steps
 	int maxdelta = 0;
 	// step-invariant lane offsets (modes 0 and 3): a full slice of equally long rows whose step-k columns are
 	// c_k[lane 0] + off[lane] with the same off at every step; off = lane is the affine case (mode 0)
@@ -156,24 +148,21 @@ slice_shape_kernel(const int * __restrict__ rp, const int * __restrict__ ci, con
 	}
 	if (!rowoff)
 		affine = (uniform && maxlen == 0) ? 1 : 0;
-	// lane offsets with exceptions (mode 5): the slice is not of one pattern, but at least 48 of its 64 rows are — against one of the
-	// first four lanes as the reference (a reference that is itself out of line agrees with nobody)
+	// lane offsets with exceptions (mode 5): the slice is not of one pattern, but most of its rows are — against one of the first four
+	// lanes as the reference (a reference that is itself out of line agrees with nobody)
 	int ref = -1, nex = 0;
 	if (uniform && maxlen > 0 && !rowoff && !(modes_off & 4))
 		sell5_reference(ci, start, maxlen, lane, ref, nex);
 	if (lane == 0)
 	{
-		// modes_off (sensitivity experiments, sell_modes_off()): bit 0 forbids the affine mode, bit 1 the per-slice lane offsets,
-		// bit 2 the lane offsets with exceptions
-		const int md = (affine && !(modes_off & 1)) ? 0 : (rowoff && !(modes_off & 2)) ? 3 : ref >= 0 ? 5 : maxdelta < 256 ? 1 : maxdelta < 65536 ? 2 : 4;
-		mode[sl] = (unsigned char) (md == 5 ? (5 | ref << 3) : md);
-		val_count[sl] = (int64_t) maxlen * WAVE;             // values: exact width; index groups: rounded up to 4 steps
-		idx_count[sl] = md == 5 ? (int64_t) (4 * WAVE + 16) + (int64_t) (width / 4) * (16 + (nex + 3) / 4 * 16)
-		                        : (int64_t) (md == 3 ? 4 * WAVE : 0) + (int64_t) (width / 4) * group_bytes(md);
+		const int mb = sell_mode_byte(affine, rowoff, ref, maxdelta, modes_off);
+		mode[sl] = (unsigned char) mb;
+		val_count[sl] = sell_slice_val_words(maxlen, 0);
+		idx_count[sl] = sell_slice_idx_bytes(mb & 7, nex, maxlen);
 	}
 }
 
-// pass 1b (7-byte values, launch.hpp): one wave per slice -> E0 of a slice whose values in its full groups of 4 steps qualify (0 = they do
+// pass 1b (7-byte values, sell_delta_layout.hpp): one wave per slice -> E0 of a slice whose values in its full groups of 4 steps qualify (0 = they do
 // not, or the slice has no full group) and its stored words
 __global__ __launch_bounds__(CV_BLOCK) void
 slice_v7_kernel(const int * __restrict__ rp, const double * __restrict__ va, const int * __restrict__ row_of_sorted, long m, long num_slices,
@@ -207,11 +196,11 @@ slice_v7_kernel(const int * __restrict__ rp, const double * __restrict__ va, con
 		const bool take = full > 0 && w.ok();
 		v7_e0[sl] = take ? w.e0() : 0;
 		if (take)
-			val_count[sl] = (int64_t) full * SELL_V7_GROUP_WORDS + (int64_t) (maxlen - 4 * full) * WAVE;
+			val_count[sl] = sell_slice_val_words(maxlen, full);
 	}
 }
 
-// pass 2: one wave per slice fills its values, bases and deltas (layout: kernels_sell.hip); v7_e0 (nullptr: none) = E0 of a slice with
+// pass 2: one wave per slice fills its values, bases and deltas (layout: sell_delta_layout.hpp); v7_e0 (nullptr: none) = E0 of a slice with
 // 7-byte values, 0 for the others
 template <typename T>
 __global__ __launch_bounds__(CV_BLOCK) void
@@ -229,13 +218,13 @@ slice_fill_kernel(const int * __restrict__ rp, const int * __restrict__ ci, cons
 		if (lane == 0)
 		{
 			desc[2 * sl] = val_ptr[sl];
-			desc[2 * sl + 1] = idx_ptr[sl] | 4;
+			desc[2 * sl + 1] = sell_desc_word(idx_ptr[sl], 4, 0);
 		}
 		return;
 	}
 	const int64_t vb = val_ptr[sl];
 	const int e0 = v7_e0 ? v7_e0[sl] : 0;
-	const int maxlen = e0 ? (int) sell_v7_width(val_ptr[sl + 1] - vb) : (int) ((val_ptr[sl + 1] - vb) / WAVE);
+	const int maxlen = (int) sell_slice_width(val_ptr[sl + 1] - vb, e0 != 0);
 	const int width = (maxlen + 3) / 4 * 4;
 	const int full = e0 ? maxlen / 4 : 0;              // groups stored as 7-byte records
 	const int md = mode[sl] & 7, ref = mode[sl] >> 3;
@@ -243,7 +232,7 @@ slice_fill_kernel(const int * __restrict__ rp, const int * __restrict__ ci, cons
 	if (lane == 0)
 	{
 		desc[2 * sl] = vb;
-		desc[2 * sl + 1] = idx_ptr[sl] | md | (e0 ? SELL_V7_FLAG | (int64_t) e0 << 48 : 0);
+		desc[2 * sl + 1] = sell_desc_word(idx_ptr[sl], md, e0);
 	}
 	const long i = sl * WAVE + lane;
 	int start = 0, len = 0;
@@ -253,7 +242,7 @@ slice_fill_kernel(const int * __restrict__ rp, const int * __restrict__ ci, cons
 		start = rp[o];
 		len = rp[o + 1] - start;
 	}
-	long gbytes = group_bytes(md);
+	long gbytes = sell_group_bytes(md);
 	int pad_base = 0;
 	bool ex = false;
 	int ex_rank = 0, off5 = 0, nex5 = 0;
@@ -273,9 +262,9 @@ slice_fill_kernel(const int * __restrict__ rp, const int * __restrict__ ci, cons
 			reinterpret_cast<unsigned long long *>(ib + 4 * WAVE)[0] = mask;
 			reinterpret_cast<unsigned long long *>(ib + 4 * WAVE)[1] = 0ull;
 		}
-		ib += 4 * WAVE + 16;
+		ib += sell_header_bytes(5);
 		nex5 = __popcll(mask);
-		gbytes = 16 + (nex5 + 3) / 4 * 16;
+		gbytes = sell_group_bytes(5, nex5);
 	}
 	if (md == 3)
 	{
@@ -284,7 +273,7 @@ slice_fill_kernel(const int * __restrict__ rp, const int * __restrict__ ci, cons
 		const int off = c_first - __shfl(c_first, 0, WAVE);
 		reinterpret_cast<int *>(ib)[lane] = off;
 		pad_base = -wave_min_i(off);                       // all-padding steps: base + off must stay a valid column
-		ib += 4 * WAVE;
+		ib += sell_header_bytes(3);
 	}
 	for (int g = 0; g < width / 4; g++)
 	{
@@ -311,7 +300,7 @@ slice_fill_kernel(const int * __restrict__ rp, const int * __restrict__ ci, cons
 			if (g < full)
 				vbits[u] = ok ? (unsigned long long) __double_as_longlong(va[start + k]) : 0ull;
 			else if (k < maxlen)                       // steps past the slice's longest row exist in the index groups only
-				val[vb + (int64_t) full * SELL_V7_GROUP_WORDS + sell_pair_pos(k, maxlen, lane) - (int64_t) full * 4 * WAVE] = ok ? (T) va[start + k] : (T) 0;
+				val[vb + sell_pair_slot(k, maxlen, lane, full)] = ok ? (T) va[start + k] : (T) 0;
 			if (md != 4)
 			{
 				if (lane == 0)
@@ -325,23 +314,24 @@ slice_fill_kernel(const int * __restrict__ rp, const int * __restrict__ ci, cons
 		{
 			// a 7-byte group: the lane's four low dwords, then its four 24-bit high parts packed into three dwords
 			unsigned char * b = reinterpret_cast<unsigned char *>(val + vb) + (size_t) g * (8 * SELL_V7_GROUP_WORDS);
-			unsigned h[4];
+			unsigned h[4], w[3];
 			#pragma unroll
 			for (int u = 0; u < 4; u++)
 			{
-				reinterpret_cast<unsigned *>(b)[lane * 4 + u] = (unsigned) vbits[u];
+				reinterpret_cast<unsigned *>(b + sell_v7_lo_pos(u, lane))[0] = (unsigned) vbits[u];
 				h[u] = sell_v7_encode_hi(vbits[u], e0);
 			}
-			unsigned * hp = reinterpret_cast<unsigned *>(b + 1024) + lane * 3;
-			hp[0] = h[0] | h[1] << 24;
-			hp[1] = h[1] >> 8 | h[2] << 16;
-			hp[2] = h[2] >> 16 | h[3] << 8;
+			sell_v7_pack_hi(h, w);
+			unsigned * hp = reinterpret_cast<unsigned *>(b + sell_v7_hi_bit(0, lane) / 8);
+			hp[0] = w[0];
+			hp[1] = w[1];
+			hp[2] = w[2];
 		}
 		if (md == 5)
 		{
 			// the exception lanes' four corrections of the group, one signed byte each; the tail of the 16-byte-padded group is zeroed
 			if (ex)
-				reinterpret_cast<unsigned *>(gp + 16)[ex_rank] = ((unsigned) cc[0] & 255u) | ((unsigned) cc[1] & 255u) << 8 | ((unsigned) cc[2] & 255u) << 16 | ((unsigned) cc[3] & 255u) << 24;
+				*reinterpret_cast<unsigned *>(gp + sell5_corr_pos(ex_rank, 0)) = ((unsigned) cc[0] & 255u) | ((unsigned) cc[1] & 255u) << 8 | ((unsigned) cc[2] & 255u) << 16 | ((unsigned) cc[3] & 255u) << 24;
 			if (lane >= nex5 && lane < (int) ((gbytes - 16) / 4))             // dword slots of the group behind the last exception's
 				reinterpret_cast<unsigned *>(gp + 16)[lane] = 0u;
 		}
@@ -376,13 +366,10 @@ struct Scratch {
 };
 
 // The conversion proper, on a CSR that already lives in device memory (rp[m+1] from 0, ci[nnz], va[nnz] as fp64).
-// Outputs (device, owned by the caller on success): row_of_sorted[m], desc[2*(slices+1)], idx[idx_bytes+1024], val[nnz_ext
-// + STREAM_SLACK] of the handle's precision. Host outputs: val_ptr (slices+1, for the tile map), mode counts, sizes.
+// Device outputs: row_of_sorted[m], desc[2*(slices+1)], idx[idx_bytes+1024], val[val_words + STREAM_SLACK] of the handle's precision.
 int
 sell_delta_convert_resident(bool f32, long m, long n_cols, long nnz, long sigma, int sell_values, const int * rp, const int * ci,
-		const double * va, int ** d_row_of_sorted_out, int64_t ** d_desc_out, unsigned char ** d_idx_out, void ** d_val_out,
-		std::vector<int64_t> & val_ptr_host, long mode_counts[4], int64_t * nnz_ext_out, int64_t * idx_bytes_out, int64_t * val_words_out,
-		long * v7_slices_out)
+		const double * va, SellDeltaArrays & out)
 {
 	(void) nnz;
 	const long num_slices = (m + WAVE - 1) / WAVE;
@@ -462,18 +449,17 @@ sell_delta_convert_resident(bool f32, long m, long n_cols, long nnz, long sigma,
 		for (long sl = 0; sl < num_slices; sl++)
 			v7_slices += e0_host[sl] != 0;
 	}
-	val_ptr_host.assign((size_t) num_slices + 1, 0);
-	HIP_TRY(hipMemcpy(val_ptr_host.data(), val_ptr, (size_t) (num_slices + 1) * 8, hipMemcpyDeviceToHost));
+	out.val_ptr.assign((size_t) num_slices + 1, 0);
+	HIP_TRY(hipMemcpy(out.val_ptr.data(), val_ptr, (size_t) (num_slices + 1) * 8, hipMemcpyDeviceToHost));
 	int64_t idx_bytes = 0;
 	HIP_TRY(hipMemcpy(&idx_bytes, idx_ptr + num_slices, 8, hipMemcpyDeviceToHost));
-	const int64_t val_words = val_ptr_host[num_slices];
+	const int64_t val_words = out.val_ptr[num_slices];
 	{
 		std::vector<unsigned char> mode_host((size_t) std::max<long>(num_slices, 1));
 		if (num_slices)
 			HIP_TRY(hipMemcpy(mode_host.data(), mode, (size_t) num_slices, hipMemcpyDeviceToHost));
-		mode_counts[0] = mode_counts[1] = mode_counts[2] = mode_counts[3] = 0;
 		for (long sl = 0; sl < num_slices; sl++)
-			mode_counts[((mode_host[sl] & 7) == 0 || (mode_host[sl] & 7) == 3 || (mode_host[sl] & 7) == 5) ? 3 : (mode_host[sl] & 7) == 1 ? 0 : (mode_host[sl] & 7) == 2 ? 1 : 2]++;
+			out.mode_counts[sell_mode_bucket(mode_host[sl])]++;
 	}
 
 	// 4. fill
@@ -501,23 +487,21 @@ sell_delta_convert_resident(bool f32, long m, long n_cols, long nnz, long sigma,
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipDeviceSynchronize());
 	out_guard.ptrs.clear();                            // success: ownership moves to the caller
-	*d_row_of_sorted_out = row_of_sorted;
-	*d_desc_out = desc;
-	*d_idx_out = idx;
-	*d_val_out = val;
-	*nnz_ext_out = nnz_ext;
-	*idx_bytes_out = idx_bytes;
-	*val_words_out = val_words;
-	*v7_slices_out = v7_slices;
+	out.row_of_sorted = row_of_sorted;
+	out.desc = desc;
+	out.idx = idx;
+	out.val = val;
+	out.nnz_ext = nnz_ext;
+	out.idx_bytes = idx_bytes;
+	out.val_words = val_words;
+	out.v7_slices = v7_slices;
 	return 0;
 }
 
 // The same from HOST arrays: upload, convert, drop the uploaded copy.
 int
 sell_delta_convert_device(bool f32, long m, long n_cols, long nnz, long sigma, int sell_values, const int * rp_host, const int * ci_host,
-		const double * va_host, int ** d_row_of_sorted_out, int64_t ** d_desc_out, unsigned char ** d_idx_out, void ** d_val_out,
-		std::vector<int64_t> & val_ptr_host, long mode_counts[4], int64_t * nnz_ext_out, int64_t * idx_bytes_out, int64_t * val_words_out,
-		long * v7_slices_out)
+		const double * va_host, SellDeltaArrays & out)
 {
 	Scratch up;
 	int * rp, * ci;
@@ -535,8 +519,7 @@ sell_delta_convert_device(bool f32, long m, long n_cols, long nnz, long sigma, i
 		HIP_TRY(hipMemcpy(ci, ci_host, (size_t) nnz * 4, hipMemcpyHostToDevice));
 		HIP_TRY(hipMemcpy(va, va_host, (size_t) nnz * 8, hipMemcpyHostToDevice));
 	}
-	return sell_delta_convert_resident(f32, m, n_cols, nnz, sigma, sell_values, rp, ci, va, d_row_of_sorted_out, d_desc_out, d_idx_out, d_val_out,
-			val_ptr_host, mode_counts, nnz_ext_out, idx_bytes_out, val_words_out, v7_slices_out);
+	return sell_delta_convert_resident(f32, m, n_cols, nnz, sigma, sell_values, rp, ci, va, out);
 }
 
 // ---------------------------------------------------------------- the LDS-window layout (build_sell.hip: build_sell_window) on the GPU

@@ -4,7 +4,7 @@
 // width, hardware gather, y scattered through rev_permutation — and the BSC library driven by sell_c_s.cpp:124-131,
 // sell-C-s/RISC-V/sellcs_mv_kernels_epi.c:178-257 — C = 256, sigma = 16384, descending radix sort per window).
 //
-// Layout (built in spmv_mi355x.cpp): rows are sorted by length (descending, stable) inside windows of sigma rows; a slice
+// Layout (built in build_sell.hip, on the GPU in convert_sell.hip): rows are sorted by length (descending, stable) inside windows of sigma rows; a slice
 // is C consecutive sorted rows, stored column-major and padded to the slice's longest row, so that the 64 lanes of ONE
 // wavefront read 64 consecutive values / column indices per step:
 //       element (row r of the slice, column k)  ->  slice_ptr[s] + k*C + r
@@ -169,22 +169,18 @@ sell_wide_kernel(const int64_t * __restrict__ slice_ptr, const int * __restrict_
 // Column indices are the only compressible stream of SpMV (values are data, x and y are compulsory). In a 64-row slice
 // the 64 lanes of step k hold neighbouring rows, and on banded / stencil / FEM matrices their columns sit within a few
 // hundred entries of each other. Per slice the indices are therefore stored as one int32 base per step plus one
-// unsigned delta per lane: 8 bits (max delta < 256), 16 bits, or plain int32 when neither fits (mode per slice).
-// Steps come in groups of 4 so that a lane's four deltas are ONE dword (8-bit) / ONE dwordx2 (16-bit) load:
-//     group of 4 steps, mode 1:  [4 x int32 base][64 lanes x 4 x u8 ]  = 16 + 256 bytes   ( 9.06 B per fp64 non-zero)
-//                      mode 2:  [4 x int32 base][64 lanes x 4 x u16]  = 16 + 512 bytes   (10.06 B)
-//                      mode 4:  [4 steps][64 lanes] int32               = 1024 bytes       (12 B, as plain SELL)
+// unsigned delta per lane: 8 bits (9.06 B per fp64 non-zero), 16 bits (10.06 B), or plain int32 when neither fits (12 B, as
+// plain SELL), or as lane offsets with no bytes per lane and step at all (layout: sell_delta_layout.hpp).
 // The bases are wave-uniform (scalar loads). Arithmetic and its order are exactly those of sell_kernel<C = 64>: one lane
 // per row, one FMA per element, left to right -> bit-identical to the sequential CSR loop; lossless by construction.
 // HBM bytes per non-zero drop by up to 24 % (fp64) / 37 % (fp32) below the CSR-normalised "algorithmic" 12 / 8 bytes.
 typedef int sell_int4 __attribute__((ext_vector_type(4)));
 typedef unsigned sell_uint2 __attribute__((ext_vector_type(2)));
 
-// VALUES of a slice are stored in PAIRS of steps: a lane's steps 2p and 2p+1 lie side by side — [pair][lane][2] — so that a group of 4
-// steps is TWO 16-byte loads per lane (fp64; global_load_dwordx4) instead of four 8-byte ones. The kernel sits at the issue rate of
-// its vector-memory instructions (4 value loads + 4 gathers per group: with the value loads at half the count the nlpkkt240 twin runs
-// 9 % faster on the same bytes, profiles/r03_sell_value_pairs.txt). The last step of an odd width stands alone, one element per lane
-// (launch.hpp: sell_pair_pos). `vp` = the group's first element + 2 * lane.
+// VALUES of a slice are stored in PAIRS of steps (sell_pair_pos), so that a group of 4 steps is TWO 16-byte loads per lane (fp64;
+// global_load_dwordx4) instead of four 8-byte ones. The kernel sits at the issue rate of its vector-memory instructions (4 value loads
+// + 4 gathers per group: with the value loads at half the count the nlpkkt240 twin runs 9 % faster on the same bytes,
+// profiles/r03_sell_value_pairs.txt). `vp` = the group's first element + 2 * lane.
 template <typename T, bool NT>
 __device__ __forceinline__ void
 sell_group_values(const T * __restrict__ vp, T (&v)[4])
@@ -226,7 +222,7 @@ sell_v7_value(unsigned h, unsigned k, unsigned lo)
 	return __builtin_bit_cast(double, (unsigned long long) sell_v7_decode_hi(h, k) << 32 | lo);
 }
 
-// Where a slice's values come from. V7 = false: the pairs above. V7 = true (fp64, sell_values; layout: launch.hpp): a full group is the
+// Where a slice's values come from. V7 = false: the pairs above. V7 = true (fp64, sell_values; layout: sell_delta_layout.hpp): a full group is the
 // lane's dwordx4 of low halves and dwordx3 of packed 24-bit high parts — as many load instructions as the pairs, 1792 bytes instead of
 // 2048 — decoded with a few 32-bit VALU operations on the high dwords only; the 1..3-step tail group is stored as pairs, behind the
 // slice's full groups. `vp` = the slice's first value word + 2 * lane either way, `k` = (E0 - 1) << 20.
@@ -250,7 +246,7 @@ struct SellVals {
 				hi = __builtin_nontemporal_load(hp);
 			else
 				hi = *hp;
-			v[0] = sell_v7_value(hi.x, k, lo.x);
+			v[0] = sell_v7_value(hi.x, k, lo.x);                                           // sell_v7_unpack_hi, as alignbit
 			v[1] = sell_v7_value(__builtin_amdgcn_alignbit(hi.y, hi.x, 24), k, lo.y);
 			v[2] = sell_v7_value(__builtin_amdgcn_alignbit(hi.z, hi.y, 16), k, lo.z);
 			v[3] = sell_v7_value(hi.z >> 8, k, lo.w);
@@ -418,7 +414,7 @@ template <typename T, int MODE, bool NT, bool V7>
 __device__ __forceinline__ void
 sell_delta_piped(const unsigned char * __restrict__ ip, const SellVals<T, NT, V7> & vals, int lane, const T * __restrict__ x, T & s, int g0, int gs, int n)
 {
-	constexpr int GB = MODE == 1 ? 272 : 528;
+	constexpr long GB = sell_group_bytes(MODE);
 	if (n <= 0)
 		return;
 	auto gidx = [&](int k) { return g0 + (k < n ? k : n - 1) * gs; };       // past the end: the last group again (loaded, not used)
@@ -465,14 +461,14 @@ __device__ __forceinline__ T
 sell_delta_slice(const unsigned char * __restrict__ ip, const SellVals<T, NT, V7> & vals, int width, int lane, const T * __restrict__ x,
 		int g0 = 0, int gs = 1)
 {
-	constexpr int GB = (MODE == 0 || MODE == 3) ? 16 : MODE == 1 ? 272 : MODE == 2 ? 528 : 1024;     // bytes of one index group
+	constexpr long GB = sell_group_bytes(MODE);
 	const int groups = (width + 3) / 4;     // index groups cover the width rounded up to 4 steps, values only the real steps
 	const int rem = width - 4 * (groups - 1);
 	int off = lane;
 	if constexpr (MODE == 3)
 	{
 		off = ld_stream<NT>(reinterpret_cast<const int *>(ip) + lane);          // the slice's 64 lane offsets, then the groups
-		ip += 4 * WAVE;
+		ip += sell_header_bytes(3);
 	}
 	T s = 0;
 	int g = g0;
@@ -520,18 +516,14 @@ sell_delta_slice(const unsigned char * __restrict__ ip, const SellVals<T, NT, V7
 	return s;
 }
 
-// MODE 5: lane offsets WITH EXCEPTIONS. Modes 0 and 3 need all 64 rows of a slice to follow one pattern; one row out of line (a
-// boundary row of a stencil, a perturbed row) used to send the whole slice back to 8/16-bit deltas per lane and step. Here EVERY lane
-// has an offset (its first column minus the reference lane's), the rows that fit (at least 48 of 64) have column = base_k + off_lane
-// at every step, and the E <= 16 others add a signed 8-bit correction per step:
-//     slice header: [64 x int32 lane offsets][u64 exception mask][8 bytes of padding]                       = 272 bytes
-//     group of 4 steps: [4 x int32 base][E x (4 x int8 corrections of exception lane number j)], padded to 16 = 32 .. 80 bytes
-// An exception lane loads its four corrections as ONE dword at gp + 16 + 4 * (its rank among the exception lanes); the other lanes
-// load the first exception's (one address for all of them) and drop it. (A first version stored the exception lanes' columns as
+// MODE 5: lane offsets WITH EXCEPTIONS (layout: sell_delta_layout.hpp). Modes 0 and 3 need all 64 rows of a slice to follow one
+// pattern; one row out of line (a boundary row of a stencil, a perturbed row) used to send the whole slice back to 8/16-bit deltas per
+// lane and step. Here the rows out of line add a signed 8-bit correction per step. An exception lane loads its four corrections as ONE
+// dword (sell5_corr_pos); the other lanes load the first exception's (one address for all of them) and drop it. (A first version stored the exception lanes' columns as
 // 4 x int32 and loaded them with a dwordx4 per lane: 1 447 us on the 5 %-jittered nlpkkt240 twin against 1 425 us for plain 8/16-bit
 // deltas although it moves 7 % fewer bytes — the wide load of all 64 lanes cost more than the bytes saved.) That load sits in front
 // of the lane's gathers, so it is fetched one pair of groups ahead like the delta words of modes 1 / 2. Same FMAs in the same order
-// as every other mode: bit-identical results. A slice with a row that needs more than 8 bits falls back to modes 1 / 2 / 4.
+// as every other mode: bit-identical results.
 // Slices with at most FOUR exception rows (the common case: 5 % of the rows out of line puts 3.2 into a slice on average) take the
 // corrections through the SCALAR cache instead: the 16 bytes behind the bases hold all of them, one s_load brings bases and corrections,
 // and a compare-and-select per exception puts its dword into its lane — no vector-memory instruction at all for the indices, as in modes 0 / 3.
@@ -615,7 +607,7 @@ sell_delta_slice5_body(const unsigned char * __restrict__ ip, const SellVals<T, 
 			mm &= mm - 1ull;
 		}
 	}
-	const size_t GB = 16 + ((size_t) E + 3) / 4 * 16;
+	const size_t GB = sell_group_bytes(5, E);
 	const int groups = (width + 3) / 4;
 	const int rem = width - 4 * (groups - 1);
 	const int last = groups - 1;
@@ -719,7 +711,7 @@ sell_delta_slice5(const unsigned char * __restrict__ ip, const SellVals<T, NT, V
 {
 	const int off = ld_stream<NT>(reinterpret_cast<const int *>(ip) + lane);
 	const unsigned long long mask = *reinterpret_cast<const unsigned long long *>(ip + 4 * WAVE);          // uniform: a scalar load
-	ip += 4 * WAVE + 16;
+	ip += sell_header_bytes(5);
 	if (__popcll(mask) <= 4)
 		return sell_delta_slice5_body<T, NT, V7, true>(ip, vals, width, lane, x, g0, gs, mask, off);
 	return sell_delta_slice5_body<T, NT, V7, false>(ip, vals, width, lane, x, g0, gs, mask, off);
@@ -744,8 +736,8 @@ sell_delta_modes(int mode, const unsigned char * __restrict__ ip, const SellVals
 	return sell_delta_slice<T, 4, NT>(ip, vals, width, lane, x, g0, gs);
 }
 
-// one slice from its two descriptor words: V7 = the handle holds slices with 7-byte values (launch.hpp), each one flagged in desc[2s+1];
-// without it the code is that of the plain pairs alone
+// one slice from its two descriptor words (sell_delta_layout.hpp): V7 = the handle holds slices with 7-byte values, each one flagged in
+// desc[2s+1]; without it the code is that of the plain pairs alone
 template <typename T, bool NT, bool V7>
 __device__ __forceinline__ T
 sell_delta_one(const int64_t * __restrict__ desc, int slice, const unsigned char * __restrict__ idx, const T * __restrict__ val, int lane,
@@ -754,18 +746,17 @@ sell_delta_one(const int64_t * __restrict__ desc, int slice, const unsigned char
 	const int64_t v_off = desc[2 * slice];
 	const int64_t i_word = desc[2 * slice + 1];
 	const int64_t v_next = desc[2 * slice + 2];
-	const int mode = (int) (i_word & 7);
-	const unsigned char * ip = idx + (i_word & SELL_IDX_MASK);
+	const int mode = sell_desc_mode(i_word);
+	const unsigned char * ip = idx + sell_desc_idx(i_word);
 	const T * vp = val + v_off + 2 * lane;
-	if (V7 && (i_word & SELL_V7_FLAG))
+	if (V7 && sell_desc_v7(i_word))
 		return sell_delta_modes<T, NT, V7>(mode, ip, SellVals<T, NT, V7>{vp, lane, (unsigned) (sell_v7_e0(i_word) - 1) << 20},
-				(int) sell_v7_width(v_next - v_off), lane, x, g0, gs);
-	return sell_delta_modes<T, NT, false>(mode, ip, SellVals<T, NT, false>{vp, lane, 0u}, (int) ((v_next - v_off) / WAVE), lane, x, g0, gs);
+				(int) sell_slice_width(v_next - v_off, true), lane, x, g0, gs);
+	return sell_delta_modes<T, NT, false>(mode, ip, SellVals<T, NT, false>{vp, lane, 0u}, (int) sell_slice_width(v_next - v_off, false), lane, x,
+			g0, gs);
 }
 
-// desc[2*s] = first value word of slice s, desc[2*s+1] = byte offset of its index block | 7-byte values flag (bit 3) | mode (0 .. 5) in the
-// low bits, E0 of the 7-byte values in bits 48..58
-// (V7: the compiler's own choice of 109 VGPRs would cost a wave per SIMD against the plain kernel's 96; held to 5 waves it takes 92, no scratch)
+// one wave per slice (V7: the compiler's own choice of 109 VGPRs would cost a wave per SIMD against the plain kernel's 96; held to 5 waves it takes 92, no scratch)
 template <typename T, bool NT, bool V7>
 __global__ __launch_bounds__(SELL_BLOCK) __attribute__((amdgpu_waves_per_eu(V7 ? 5 : 1))) void
 sell_delta_kernel(const int64_t * __restrict__ desc, const unsigned char * __restrict__ idx, const T * __restrict__ val,

@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "sell_delta_layout.hpp"
 
 namespace spmv {
 
@@ -63,8 +64,8 @@ int launch_merge(bool f32, int items_per_thread, const int * row_ptr, const int 
 int launch_sell(bool f32, int C, const int64_t * slice_ptr, const int * col, const void * val, const int * row_of_sorted,
 		const void * x, void * y, int m, int num_slices, const LaunchCfg & cfg, hipStream_t stream, long * grid_out);
 
-// SELL-64-sigma with delta-compressed column indices (desc: 2 int64 per slice + terminator, idx: byte stream)
-// v7: the handle holds slices with 7-byte values (SELL_V7_FLAG below); launches the kernel variant that looks at the flag
+// SELL-64-sigma with delta-compressed column indices (layout: sell_delta_layout.hpp)
+// v7: the handle holds slices with 7-byte values (SELL_V7_FLAG); launches the kernel variant that looks at the flag
 int launch_sell_delta(bool f32, int waves_per_slice, bool v7, const int64_t * desc, const unsigned char * idx, const void * val, const int * row_of_sorted,
 		const void * x, void * y, int m, int num_slices, const LaunchCfg & cfg, hipStream_t stream, long * grid_out);
 
@@ -89,90 +90,6 @@ sell_modes_off()
 	return e ? atoi(e) & 7 : 0;
 }
 
-// Where value (step k, lane r) of a 64-row slice of the delta layout lies behind the slice's first element: steps in pairs, a lane's steps
-// 2p and 2p+1 side by side (kernels_sell.hip: sell_group_values); the last step of an odd width stands alone, one element per lane.
-__host__ __device__ inline long
-sell_pair_pos(long k, long width, long r)
-{
-	return (k | 1) < width ? (k / 2) * 128 + r * 2 + (k & 1) : (k / 2) * 128 + r;
-}
-
-// 7-byte fp64 values of the delta layout (sell_values). A slice whose stored values in its FULL groups of 4 steps (padding included) are
-// all either exponent-0 values (+-0, denormals) or finite normals with biased exponent in [E0, E0 + 6] keeps each of them as a 56-bit
-// record: sign (1 bit), exponent code c (3 bits: 0 = exponent field 0, 1..7 = E0 + c - 1), the 52 mantissa bits verbatim. Decoding gives
-// back the same bits. A compressed group of 4 steps is 1792 bytes instead of 2048:
-//     lo plane [64 lanes][4 dwords]   the low 32 bits of the lane's four values, as they are      (one dwordx4 per lane)
-//     hi plane [64 lanes][3 dwords]   the four 24-bit high parts sign|c|mantissa[51:32], packed  (one dwordx3 per lane)
-// The 1..3-step tail group stays in today's pairs (sell_pair_pos, relative to the tail's first word). Every slice starts on a multiple of
-// 32 words (plain: 64 words per step; compressed: 224 per group, 64 per tail step), so desc[2s] stays an offset in 8-byte words and the
-// slice's width follows from the difference of two offsets (sell_v7_width). desc[2s+1] carries the flag (bit 3, free: index blocks are
-// 16-byte aligned) and E0 (bits 48..58) beside the index byte offset and the mode.
-constexpr int SELL_V7_GROUP_WORDS = 224;                 // 8-byte words of one compressed group (1792 bytes)
-constexpr int64_t SELL_V7_FLAG = 8;
-constexpr int64_t SELL_IDX_MASK = 0x0000fffffffffff0LL;  // index byte offset of desc[2s+1]
-
-__host__ __device__ inline int
-sell_v7_e0(int64_t i_word)
-{
-	return (int) ((i_word >> 48) & 2047);
-}
-
-// width in steps of a compressed slice of `words` 8-byte words: 224 per full group, 64 per tail step (at most 3, 192 < 224)
-__host__ __device__ inline long
-sell_v7_width(int64_t words)
-{
-	return 4 * (words / SELL_V7_GROUP_WORDS) + (words % SELL_V7_GROUP_WORDS) / 64;
-}
-
-// the exponent range of a set of fp64 values: does it qualify, and with which E0
-struct SellV7Range {
-	int lo = 2047, hi = 0;                               // lowest / highest biased exponent of the normal values seen
-	bool bad = false;                                    // an Inf or NaN
-	__host__ __device__ void add(uint64_t bits)
-	{
-		const int e = (int) ((bits >> 52) & 2047);
-		if (e == 2047)
-			bad = true;
-		else if (e)
-		{
-			lo = e < lo ? e : lo;
-			hi = e > hi ? e : hi;
-		}
-	}
-	__host__ __device__ bool ok() const { return !bad && (lo == 2047 || hi - lo <= 6); }
-	__host__ __device__ int e0() const { return lo == 2047 ? 1 : lo; }    // no normal value at all: any E0 does
-};
-
-// the 24-bit high part of a value that qualifies for E0
-__host__ __device__ inline unsigned
-sell_v7_encode_hi(uint64_t bits, int e0)
-{
-	const unsigned e = (unsigned) (bits >> 52) & 2047u;
-	const unsigned c = e ? e - (unsigned) e0 + 1u : 0u;
-	return (unsigned) (bits >> 63) << 23 | c << 20 | ((unsigned) (bits >> 32) & 0xfffffu);
-}
-
-// ... and back to the value's high dword; bits 24..31 of `h` are ignored, k = (E0 - 1) << 20. Four 32-bit VALU operations.
-__host__ __device__ inline unsigned
-sell_v7_decode_hi(unsigned h, unsigned k)
-{
-	const unsigned a = h & 0x7fffffu;                    // c | mantissa[51:32]
-	return (a < 0x100000u ? a : a + k) | ((h << 8) & 0x80000000u);
-}
-
-// byte position of the low / high part of value (step k < 4 * full groups, lane r) behind a compressed slice's first byte, and the word
-// of its hi plane that holds bits [shift, shift + 24) of the packed high parts (shift 24 and 16 run into the next word)
-__host__ __device__ inline long
-sell_v7_lo_pos(long k, long r)
-{
-	return (k / 4) * 1792 + r * 16 + (k & 3) * 4;
-}
-__host__ __device__ inline long
-sell_v7_hi_bit(long k, long r)
-{
-	return ((k / 4) * 1792 + 1024 + r * 12) * 8 + (k & 3) * 24;
-}
-
 // 7-byte values: SPMV_MI355X_SELL_VALUES = 0 (auto) | 1 (on) | 2 (off) overrides opts.sell_values; read at every create()
 inline int
 sell_values_env(int opt)
@@ -181,35 +98,37 @@ sell_values_env(int opt)
 	return e ? atoi(e) : opt;
 }
 
-// whether a delta-layout handle looks for slices to store in 7 bytes: fp64, and on (1) or auto (0) with a plain value array of `nnz_ext`
-// entries larger than the 256 MiB Infinity Cache (below that the values stay cache-resident from launch to launch: nothing to save)
-inline bool
-sell_v7_wanted(bool f32, int sell_values, int64_t nnz_ext)
-{
-	return !f32 && (sell_values == 1 || (sell_values == 0 && (double) nnz_ext * 8 > 256.0 * 1024 * 1024));
-}
-
-// ... and of the LDS-window layout, whose slices are padded to whole groups of 4 steps: 16 bytes per lane and load — fp64 as above,
-// fp32 a lane's 4 steps of a group side by side (kernels_sell_window.hip: sellw_values)
+// Where value (step k, lane r) of a slice of the LDS-window layout lies behind the slice's first element; its slices are padded to
+// whole groups of 4 steps: 16 bytes per lane and load — fp64 in pairs of steps as the delta layout (sell_pair_pos), fp32 a lane's 4
+// steps of a group side by side (kernels_sell_window.hip: sellw_values)
 __host__ __device__ inline long
 sellw_val_pos(long k, long r, bool f32)
 {
 	return f32 ? (k / 4) * 256 + r * 4 + (k & 3) : (k / 2) * 128 + r * 2 + (k & 1);
 }
 
-// CSR -> SELL-64-sigma-delta on the GPU (convert_sell.hip); outputs are device arrays owned by the caller
-// (sell_values: 0 = auto, 1 = on, 2 = off, sell_v7_wanted; nnz_ext_out = padded entries, val_words_out = stored value elements,
-// v7_slices_out = slices with 7-byte values)
+// CSR -> SELL-64-sigma-delta on the GPU (convert_sell.hip): the device arrays (owned by the caller on success) and what the handle
+// needs to know of them
+struct SellDeltaArrays {
+	int * row_of_sorted = nullptr;
+	int64_t * desc = nullptr;
+	unsigned char * idx = nullptr;
+	void * val = nullptr;
+	std::vector<int64_t> val_ptr;          // host copy of the value offsets (slices + 1): they feed the XCD tile map
+	long mode_counts[4] = {0, 0, 0, 0};    // slices per sell_mode_bucket
+	int64_t nnz_ext = 0;                   // padded entries of the plain layout
+	int64_t idx_bytes = 0;
+	int64_t val_words = 0;                 // stored value elements
+	long v7_slices = 0;                    // slices with 7-byte values
+};
+
+// (sell_values: 0 = auto, 1 = on, 2 = off, sell_v7_wanted)
 int sell_delta_convert_device(bool f32, long m, long n_cols, long nnz, long sigma, int sell_values, const int * rp_host, const int * ci_host,
-		const double * va_host, int ** d_row_of_sorted_out, int64_t ** d_desc_out, unsigned char ** d_idx_out, void ** d_val_out,
-		std::vector<int64_t> & val_ptr_host, long mode_counts[4], int64_t * nnz_ext_out, int64_t * idx_bytes_out, int64_t * val_words_out,
-		long * v7_slices_out);
+		const double * va_host, SellDeltaArrays & out);
 
 // the same on a CSR already resident in device memory (rp, ci, va are device pointers; va fp64)
 int sell_delta_convert_resident(bool f32, long m, long n_cols, long nnz, long sigma, int sell_values, const int * rp, const int * ci,
-		const double * va, int ** d_row_of_sorted_out, int64_t ** d_desc_out, unsigned char ** d_idx_out, void ** d_val_out,
-		std::vector<int64_t> & val_ptr_host, long mode_counts[4], int64_t * nnz_ext_out, int64_t * idx_bytes_out, int64_t * val_words_out,
-		long * v7_slices_out);
+		const double * va, SellDeltaArrays & out);
 // the entry arrays of the column-blocked layout on the GPU (convert_coo.hip)
 int blocked_entries_convert_device(bool f32, bool uniform, long m, long nnz, const int * rp_host, const int * ci_host, const double * va_host, long NR, int WGS, long CH,
 		const std::vector<int> & range_row, const std::vector<int> & range_long, const std::vector<int> & long_row, const std::vector<int> & chunk_ptr,

@@ -543,8 +543,8 @@ spmv_mi355x_sell_layout(const spmv_mi355x_matrix * A, long * C_out, long * sigma
 		plain_ptr.assign((size_t) A->sell_slices + 1, 0);
 		for (long sl = 0; sl < A->sell_slices; sl++)
 		{
-			const int64_t words = h_desc[2 * sl + 2] - h_desc[2 * sl];
-			plain_ptr[sl + 1] = plain_ptr[sl] + ((h_desc[2 * sl + 1] & spmv::SELL_V7_FLAG) ? spmv::sell_v7_width(words) * 64 : words);
+			const long width = spmv::sell_slice_width(h_desc[2 * sl + 2] - h_desc[2 * sl], spmv::sell_desc_v7(h_desc[2 * sl + 1]));
+			plain_ptr[sl + 1] = plain_ptr[sl] + width * 64;
 		}
 	}
 	if (slice_ptr_out)
@@ -566,18 +566,12 @@ spmv_mi355x_sell_layout(const spmv_mi355x_matrix * A, long * C_out, long * sigma
 			{
 				const int64_t vb = plain_ptr[sl];
 				const long width = (plain_ptr[sl + 1] - vb) / 64;
-				const int md = (int) (h_desc[2 * sl + 1] & 7);
-				const unsigned char * ib = h_idx.data() + (h_desc[2 * sl + 1] & spmv::SELL_IDX_MASK);
+				const int md = spmv::sell_desc_mode(h_desc[2 * sl + 1]);
+				const unsigned char * ib = h_idx.data() + spmv::sell_desc_idx(h_desc[2 * sl + 1]);
 				const int * offs = reinterpret_cast<const int *>(ib);
-				unsigned long long exmask = 0;
-				if (md == 3)
-					ib += 4 * 64;
-				if (md == 5)
-				{
-					exmask = *reinterpret_cast<const unsigned long long *>(ib + 4 * 64);
-					ib += 4 * 64 + 16;
-				}
-				const long gbytes = md == 5 ? 16 + (__builtin_popcountll(exmask) + 3) / 4 * 16 : (md == 0 || md == 3) ? 16 : md == 1 ? 272 : md == 2 ? 528 : 1024;
+				const unsigned long long exmask = md == 5 ? *reinterpret_cast<const unsigned long long *>(ib + 4 * 64) : 0;
+				const long gbytes = spmv::sell_group_bytes(md, __builtin_popcountll(exmask));
+				ib += spmv::sell_header_bytes(md);
 				for (long k = 0; k < width; k++)
 				{
 					const unsigned char * gp = ib + (k / 4) * gbytes;
@@ -591,7 +585,7 @@ spmv_mi355x_sell_layout(const spmv_mi355x_matrix * A, long * C_out, long * sigma
 							c = reinterpret_cast<const int *>(gp)[u] + offs[r];
 						else if (md == 5)
 							c = reinterpret_cast<const int *>(gp)[u] + offs[r] +
-							    (((exmask >> r) & 1ull) ? (int) reinterpret_cast<const signed char *>(gp + 16)[4 * __builtin_popcountll(exmask & ((1ull << r) - 1ull)) + u] : 0);
+							    (((exmask >> r) & 1ull) ? (int) reinterpret_cast<const signed char *>(gp)[spmv::sell5_corr_pos(__builtin_popcountll(exmask & ((1ull << r) - 1ull)), (int) u)] : 0);
 						else if (md == 1)
 							c = reinterpret_cast<const int *>(gp)[u] + gp[16 + r * 4 + u];
 						else if (md == 2)
@@ -624,13 +618,13 @@ spmv_mi355x_sell_layout(const spmv_mi355x_matrix * A, long * C_out, long * sigma
 			memcpy(*val_out, raw.data(), nw * sizeof(double));
 		else
 		{
-			// the delta layout keeps a lane's steps in pairs (launch.hpp: sell_pair_pos), the full groups of a slice with 7-byte values as
-			// lo / hi planes (launch.hpp: sell_v7_lo_pos, sell_v7_hi_bit): back to plain column-major fp64
+			// the delta layout keeps a lane's steps in pairs (sell_pair_pos), the full groups of a slice with 7-byte values as lo / hi planes
+			// (sell_v7_lo_pos, sell_v7_hi_bit; sell_delta_layout.hpp): back to plain column-major fp64
 			for (long sl = 0; sl < A->sell_slices; sl++)
 			{
 				const int64_t vb = h_desc[2 * sl], pb = plain_ptr[sl];
 				const long width = (plain_ptr[sl + 1] - pb) / 64;
-				const bool v7 = h_desc[2 * sl + 1] & spmv::SELL_V7_FLAG;
+				const bool v7 = spmv::sell_desc_v7(h_desc[2 * sl + 1]);
 				const long full = v7 ? width / 4 : 0;
 				const unsigned k0 = (unsigned) (spmv::sell_v7_e0(h_desc[2 * sl + 1]) - 1) << 20;
 				const unsigned char * b = reinterpret_cast<const unsigned char *>(raw.data() + vb);
@@ -648,7 +642,7 @@ spmv_mi355x_sell_layout(const spmv_mi355x_matrix * A, long * C_out, long * sigma
 							memcpy(&v, &bits, 8);
 						}
 						else
-							v = raw[(size_t) (vb + full * spmv::SELL_V7_GROUP_WORDS + spmv::sell_pair_pos(k, width, r) - full * 256)];
+							v = raw[(size_t) (vb + spmv::sell_pair_slot(k, width, r, full))];
 						(*val_out)[pb + k * 64 + r] = v;
 					}
 			}

@@ -1,10 +1,10 @@
-// decode(encode(v)) of the 7-byte fp64 values of the SELL delta layout (csrc/launch.hpp) and their qualification rule, on the host:
-// compiled and run by tests/test_sell_values_codec.py
+// decode(encode(v)) of the 7-byte fp64 values of the SELL delta layout (csrc/sell_delta_layout.hpp) and their qualification rule, and
+// the layout's size, descriptor and packing helpers, on the host: compiled and run by tests/test_sell_values_codec.py
 #include <cstdio>
 #include <cstring>
 #include <random>
 
-#include "launch.hpp"
+#include "sell_delta_layout.hpp"
 
 using spmv::SellV7Range;
 
@@ -30,6 +30,75 @@ static int check_group(const uint64_t (&v)[4], int e0)
 		if (((uint64_t) spmv::sell_v7_decode_hi(got[u], k) << 32 | (uint32_t) v[u]) != v[u])
 			return 1;
 	return 0;
+}
+
+// the size, descriptor and packing helpers of the layout against the numbers its description gives
+static long check_layout_helpers(std::mt19937_64 & g)
+{
+	long bad = 0;
+	const long want[5] = {16, 272, 528, 16, 1024};
+	for (int md = 0; md < 5; md++)
+		if (spmv::sell_group_bytes(md) != want[md])
+		{
+			printf("group bytes of mode %d: %ld\n", md, spmv::sell_group_bytes(md));
+			bad++;
+		}
+	for (unsigned e = 1; e <= 16; e++)
+		if (spmv::sell_group_bytes(5, e) != 16 + 16 * (long) ((e + 3) / 4) || spmv::sell_group_bytes(5, e) < 32 || spmv::sell_group_bytes(5, e) > 80)
+		{
+			printf("group bytes of mode 5 with %u exceptions: %ld\n", e, spmv::sell_group_bytes(5, e));
+			bad++;
+		}
+	bad += spmv::sell_group_bytes(5, 1) != 32 || spmv::sell_group_bytes(5, 16) != 80;
+	bad += spmv::sell_header_bytes(0) != 0 || spmv::sell_header_bytes(3) != 256 || spmv::sell_header_bytes(5) != 272;
+	// desc[2s+1]: index offset (16-byte aligned, up to 48 bits), mode, 7-byte flag, E0
+	const int e0s[] = {0, 1, 2, 1023, 2045, 2046};
+	for (int t = 0; t < 100000; t++)
+	{
+		const int64_t off = t < 2 ? (t ? 0x0000fffffffffff0LL : 0) : (int64_t) (g() & 0x0000fffffffffff0ULL);
+		const int md = (int) (g() % 6);
+		const int e0 = t < 6 * 6 ? e0s[t % 6] : (g() & 1) ? 0 : 1 + (int) (g() % 2046);
+		const int64_t w = spmv::sell_desc_word(off, md, e0);
+		if (spmv::sell_desc_idx(w) != off || spmv::sell_desc_mode(w) != md || spmv::sell_desc_v7(w) != (e0 != 0) ||
+		    (e0 && spmv::sell_v7_e0(w) != e0))
+		{
+			if (bad < 20)
+				printf("desc word: off %lld mode %d E0 %d\n", (long long) off, md, e0);
+			bad++;
+		}
+	}
+	// a slice's width from its value words, plain and 7-byte
+	for (long w = 0; w <= 40; w++)
+	{
+		bad += spmv::sell_slice_width(spmv::sell_slice_val_words(w, 0), false) != w;
+		bad += spmv::sell_slice_width(spmv::sell_slice_val_words(w, w / 4), true) != w;
+	}
+	// the three packed hi dwords of a lane hold each high part at the bits sell_v7_hi_bit names; unpacking gives them back
+	for (int t = 0; t < 100000; t++)
+	{
+		const long r = (long) (g() % 64);
+		unsigned h[4], w[3], back[4];
+		for (int u = 0; u < 4; u++)
+			h[u] = (unsigned) g() & 0xffffffu;
+		spmv::sell_v7_pack_hi(h, w);
+		unsigned char plane[1792] = {};
+		memcpy(plane + spmv::sell_v7_hi_bit(0, r) / 8, w, 12);
+		unsigned char bytes[1792] = {};
+		for (int u = 0; u < 4; u++)
+			for (int b = 0; b < 24; b += 8)
+				bytes[(spmv::sell_v7_hi_bit(u, r) + b) / 8] = (unsigned char) (h[u] >> b);
+		spmv::sell_v7_unpack_hi(w[0], w[1], w[2], back);
+		bool ok = memcmp(plane, bytes, sizeof(plane)) == 0;
+		for (int u = 0; u < 4; u++)
+			ok = ok && (back[u] & 0xffffffu) == h[u];
+		if (!ok)
+		{
+			if (bad < 20)
+				printf("hi plane: lane %ld packs differently\n", r);
+			bad++;
+		}
+	}
+	return bad;
 }
 
 int main()
@@ -110,6 +179,7 @@ int main()
 	for (long w = 0; w < 4000; w++)
 		if (spmv::sell_v7_width((w / 4) * spmv::SELL_V7_GROUP_WORDS + (w % 4) * 64) != w)
 			bad++;
+	bad += check_layout_helpers(g);
 	printf("groups %ld, sets refused %ld, failures %ld\n", groups, said_no, bad);
 	return bad != 0;
 }

@@ -171,6 +171,25 @@ int  spmv_mi355x_spmv_device_async(spmv_mi355x_matrix * A, const void * x_dev, v
 /* Time `iters` back-to-back launches with HIP events recorded on the stream the kernels run on; ms per iteration. */
 int  spmv_mi355x_time_device(spmv_mi355x_matrix * A, const void * x_dev, void * y_dev, int iters,
 		void * hip_stream, double * ms_per_iter_out);
+/* ---- Y = A X for k vectors at once ------------------------------------------------------------------------------------ */
+/* Y = A X (beta == 0) or Y += A X (beta == 1) for k >= 1 vectors at once, enqueued on hip_stream.
+ * X: cols() rows of k values, row i at X_dev + i*ldx (ldx >= k, counted in values of the handle's precision);
+ * Y: rows() rows, row i at Y_dev + i*ldy (ldy >= k). Only Y[i*ldy + j], i < rows(), j < k is written.
+ * Column j of Y is bit-identical to spmv_mi355x_spmv_device_async(A, x_j, y_j, beta, ...) on the contiguous column x_j
+ * whenever that product is deterministic (every layout without LDS / global atomics).
+ * The SELL-C-sigma delta layout (not the LDS-window or symmetric ones) reads the matrix once per PASS of up to 8 columns: k runs as
+ * passes of 8 columns, then the binary remainder (k = 7: 4 + 2 + 1, k = 16: 8 + 8); k == 1 with ldx == ldy == 1 is the single-vector
+ * kernel itself. Every other layout runs the single-vector product once per column, through a column of scratch the handle owns
+ * (allocated at its first such call), so one handle serves one spmm at a time.
+ * rc 1 without touching memory for k < 1, ldx < k, ldy < k, a NULL handle, or a NULL X / Y where columns / rows exist. */
+int  spmv_mi355x_spmm_device_async(spmv_mi355x_matrix * A, int k, const void * X_dev, long ldx, void * Y_dev, long ldy,
+		int beta, void * hip_stream);
+/* HIP-event timing of `iters` back-to-back spmm launches (beta 0), like spmv_mi355x_time_device */
+int  spmv_mi355x_time_spmm_device(spmv_mi355x_matrix * A, int k, const void * X_dev, long ldx, void * Y_dev, long ldy,
+		int iters, void * hip_stream, double * ms_per_iter_out);
+/* blocking host-buffer form: X is cols() x k, Y is rows() x k, both dense row-major (ld = k) */
+int  spmv_mi355x_spmm(spmv_mi355x_matrix * A, int k, const void * X_host, void * Y_host);
+
 /* Name and launch shape of the dominant kernel (for matching rocprofv3 kernel-trace rows). */
 int  spmv_mi355x_kernel_info(const spmv_mi355x_matrix * A, char * name_out, long name_n, long * grid_out, int * block_out);
 

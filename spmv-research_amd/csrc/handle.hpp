@@ -75,6 +75,11 @@ struct spmv_mi355x_matrix {
 	int coo_k = 0, coo_num_waves = 0;
 	int * d_rowind = nullptr;
 
+	// spmm of the layouts served column by column (spmv_mi355x_spmm_device_async): one column of X (cols() + 64 values) and of Y
+	// (rows() + 64), allocated at the first such call
+	void * d_spmm_x = nullptr;
+	void * d_spmm_y = nullptr;
+
 	// host-buffer path
 	void * d_x = nullptr;
 	void * d_y = nullptr;

@@ -18,7 +18,7 @@
 
 #include <type_traits>
 
-#include "launch.hpp"
+#include "sell_delta_read.hpp"
 
 namespace spmv {
 
@@ -174,131 +174,16 @@ sell_wide_kernel(const int64_t * __restrict__ slice_ptr, const int * __restrict_
 // The bases are wave-uniform (scalar loads). Arithmetic and its order are exactly those of sell_kernel<C = 64>: one lane
 // per row, one FMA per element, left to right -> bit-identical to the sequential CSR loop; lossless by construction.
 // HBM bytes per non-zero drop by up to 24 % (fp64) / 37 % (fp32) below the CSR-normalised "algorithmic" 12 / 8 bytes.
-typedef int sell_int4 __attribute__((ext_vector_type(4)));
-typedef unsigned sell_uint2 __attribute__((ext_vector_type(2)));
-
-// VALUES of a slice are stored in PAIRS of steps (sell_pair_pos), so that a group of 4 steps is TWO 16-byte loads per lane (fp64;
-// global_load_dwordx4) instead of four 8-byte ones. The kernel sits at the issue rate of its vector-memory instructions (4 value loads
-// + 4 gathers per group: with the value loads at half the count the nlpkkt240 twin runs 9 % faster on the same bytes,
-// profiles/r03_sell_value_pairs.txt). `vp` = the group's first element + 2 * lane.
-template <typename T, bool NT>
-__device__ __forceinline__ void
-sell_group_values(const T * __restrict__ vp, T (&v)[4])
-{
-	typedef T T2 __attribute__((ext_vector_type(2)));
-	const T2 w0 = ld_stream<NT>(reinterpret_cast<const T2 *>(vp));
-	const T2 w1 = ld_stream<NT>(reinterpret_cast<const T2 *>(vp + 2 * WAVE));
-	v[0] = w0.x;
-	v[1] = w0.y;
-	v[2] = w1.x;
-	v[3] = w1.y;
-}
-
-// the 1..3 real steps of a slice's last group
-template <typename T, bool NT, int NSTEPS>
-__device__ __forceinline__ void
-sell_tail_values(const T * __restrict__ vp, int lane, T (&v)[3])
-{
-	typedef T T2 __attribute__((ext_vector_type(2)));
-	v[1] = v[2] = T(0);
-	if (NSTEPS == 1)
-		v[0] = ld_stream<NT>(vp - lane);
-	else
-	{
-		const T2 w0 = ld_stream<NT>(reinterpret_cast<const T2 *>(vp));
-		v[0] = w0.x;
-		v[1] = w0.y;
-		if (NSTEPS == 3)
-			v[2] = ld_stream<NT>(vp + 2 * WAVE - lane);
-	}
-}
-
-typedef unsigned sell_uint4 __attribute__((ext_vector_type(4)));
-typedef unsigned sell_uint3 __attribute__((ext_vector_type(3), aligned(4)));     // 12 bytes, one global_load_dwordx3
-
-__device__ __forceinline__ double
-sell_v7_value(unsigned h, unsigned k, unsigned lo)
-{
-	return __builtin_bit_cast(double, (unsigned long long) sell_v7_decode_hi(h, k) << 32 | lo);
-}
-
-// Where a slice's values come from. V7 = false: the pairs above. V7 = true (fp64, sell_values; layout: sell_delta_layout.hpp): a full group is the
-// lane's dwordx4 of low halves and dwordx3 of packed 24-bit high parts — as many load instructions as the pairs, 1792 bytes instead of
-// 2048 — decoded with a few 32-bit VALU operations on the high dwords only; the 1..3-step tail group is stored as pairs, behind the
-// slice's full groups. `vp` = the slice's first value word + 2 * lane either way, `k` = (E0 - 1) << 20.
-template <typename T, bool NT, bool V7>
-struct SellVals {
-	const T * vp;
-	int lane;
-	unsigned k;
-	__device__ __forceinline__ void group(int g, T (&v)[4]) const
-	{
-		if constexpr (!V7)
-			sell_group_values<T, NT>(vp + (size_t) g * 4 * WAVE, v);
-		else
-		{
-			static_assert(sizeof(T) == 8, "7-byte values are fp64 only");
-			const unsigned char * b = reinterpret_cast<const unsigned char *>(vp) + (size_t) g * (8 * SELL_V7_GROUP_WORDS);  // lo plane + 16 * lane
-			const sell_uint4 lo = ld_stream<NT>(reinterpret_cast<const sell_uint4 *>(b));
-			const sell_uint3 * hp = reinterpret_cast<const sell_uint3 *>(b + 1024 - 4 * lane);                   // hi plane + 12 * lane
-			sell_uint3 hi;
-			if constexpr (NT)
-				hi = __builtin_nontemporal_load(hp);
-			else
-				hi = *hp;
-			v[0] = sell_v7_value(hi.x, k, lo.x);                                           // sell_v7_unpack_hi, as alignbit
-			v[1] = sell_v7_value(__builtin_amdgcn_alignbit(hi.y, hi.x, 24), k, lo.y);
-			v[2] = sell_v7_value(__builtin_amdgcn_alignbit(hi.z, hi.y, 16), k, lo.z);
-			v[3] = sell_v7_value(hi.z >> 8, k, lo.w);
-		}
-	}
-	// the group `g` (= the number of full groups) that holds the slice's 1..3 last steps: vp-relative as sell_tail_values wants it
-	__device__ __forceinline__ const T * tail(int g) const { return vp + (size_t) g * (V7 ? SELL_V7_GROUP_WORDS : 4 * WAVE); }
-};
+// The value readers and index decoders live in sell_delta_read.hpp, shared with the multi-vector kernel (kernels_sell_spmm.hip).
 
 template <typename T, int MODE, bool NT, bool V7, int NSTEPS = 4>
 __device__ __forceinline__ void
 sell_delta_group(const unsigned char * __restrict__ gp /* uniform */, const SellVals<T, NT, V7> & vals, int g, int lane, const T * __restrict__ x, T & s,
 		int off = 0)
 {
-	int c0, c1, c2, c3;
-	if constexpr (MODE == 0 || MODE == 3)
-	{
-		// step-invariant lane offsets: column of lane l at step k = base_k + off_l. MODE 0 (affine slice: 64 consecutive rows of
-		// a stencil diagonal) has off_l = l; MODE 3 stores the 64 offsets once per slice (rows of one kind that are not
-		// consecutive). Either way no per-step index bytes per lane, one scalar base per step.
-		const sell_int4 base = *reinterpret_cast<const sell_int4 *>(gp);
-		c0 = base.x + off;
-		c1 = base.y + off;
-		c2 = base.z + off;
-		c3 = base.w + off;
-	}
-	else if constexpr (MODE == 1)
-	{
-		const sell_int4 base = *reinterpret_cast<const sell_int4 *>(gp);
-		const unsigned d = ld_stream<NT>(reinterpret_cast<const unsigned *>(gp + 16) + lane);
-		c0 = base.x + (int) (d & 255u);
-		c1 = base.y + (int) ((d >> 8) & 255u);
-		c2 = base.z + (int) ((d >> 16) & 255u);
-		c3 = base.w + (int) (d >> 24);
-	}
-	else if constexpr (MODE == 2)
-	{
-		const sell_int4 base = *reinterpret_cast<const sell_int4 *>(gp);
-		const sell_uint2 d = ld_stream<NT>(reinterpret_cast<const sell_uint2 *>(gp + 16) + lane);
-		c0 = base.x + (int) (d.x & 0xffffu);
-		c1 = base.y + (int) (d.x >> 16);
-		c2 = base.z + (int) (d.y & 0xffffu);
-		c3 = base.w + (int) (d.y >> 16);
-	}
-	else
-	{
-		const int * cp = reinterpret_cast<const int *>(gp) + lane;
-		c0 = ld_stream<NT>(cp);
-		c1 = ld_stream<NT>(cp + WAVE);
-		c2 = ld_stream<NT>(cp + 2 * WAVE);
-		c3 = ld_stream<NT>(cp + 3 * WAVE);
-	}
+	int c[4];
+	sell_group_cols<MODE, NT>(gp, lane, off, c);
+	const int c0 = c[0], c1 = c[1], c2 = c[2], c3 = c[3];
 	if (NSTEPS == 4)
 	{
 		T v[4];
@@ -342,44 +227,6 @@ sell_pin(sell_uint2 & v, bool both)
 		v.y = b;
 }
 
-// Modes 1 and 2 put a dependent load in front of every gather (deltas -> column -> x): their index words are fetched one pair of
-// groups AHEAD, so that a trip costs one exposed round trip (the gathers) like the index-free modes, not two.
-template <int MODE>
-struct SellDeltaIdx {
-	sell_int4 base;
-	sell_uint2 d;                                  // MODE 1 uses d.x only
-};
-
-template <int MODE, bool NT>
-__device__ __forceinline__ void
-sell_delta_load_idx(SellDeltaIdx<MODE> & q, const unsigned char * __restrict__ gp /* uniform */, int lane)
-{
-	q.base = *reinterpret_cast<const sell_int4 *>(gp);
-	if constexpr (MODE == 1)
-		q.d.x = ld_stream<NT>(reinterpret_cast<const unsigned *>(gp + 16) + lane);
-	else
-		q.d = ld_stream<NT>(reinterpret_cast<const sell_uint2 *>(gp + 16) + lane);
-}
-
-template <int MODE>
-__device__ __forceinline__ void
-sell_delta_cols(const SellDeltaIdx<MODE> & q, int (&c)[4])
-{
-	if constexpr (MODE == 1)
-	{
-		c[0] = q.base.x + (int) (q.d.x & 255u);
-		c[1] = q.base.y + (int) ((q.d.x >> 8) & 255u);
-		c[2] = q.base.z + (int) ((q.d.x >> 16) & 255u);
-		c[3] = q.base.w + (int) (q.d.x >> 24);
-	}
-	else
-	{
-		c[0] = q.base.x + (int) (q.d.x & 0xffffu);
-		c[1] = q.base.y + (int) (q.d.x >> 16);
-		c[2] = q.base.z + (int) (q.d.y & 0xffffu);
-		c[3] = q.base.w + (int) (q.d.y >> 16);
-	}
-}
 
 // the full 4-step groups number g0, g0+gs, ... (n of them) of a slice in mode 1 / 2: FOUR groups per trip (16 steps in flight: all loads of a
 // trip are issued before its first FMA), their index words fetched one trip ahead; what is left (0..3 groups) as a pair and / or a single
@@ -516,58 +363,6 @@ sell_delta_slice(const unsigned char * __restrict__ ip, const SellVals<T, NT, V7
 	return s;
 }
 
-// MODE 5: lane offsets WITH EXCEPTIONS (layout: sell_delta_layout.hpp). Modes 0 and 3 need all 64 rows of a slice to follow one
-// pattern; one row out of line (a boundary row of a stencil, a perturbed row) used to send the whole slice back to 8/16-bit deltas per
-// lane and step. Here the rows out of line add a signed 8-bit correction per step. An exception lane loads its four corrections as ONE
-// dword (sell5_corr_pos); the other lanes load the first exception's (one address for all of them) and drop it. (A first version stored the exception lanes' columns as
-// 4 x int32 and loaded them with a dwordx4 per lane: 1 447 us on the 5 %-jittered nlpkkt240 twin against 1 425 us for plain 8/16-bit
-// deltas although it moves 7 % fewer bytes — the wide load of all 64 lanes cost more than the bytes saved.) That load sits in front
-// of the lane's gathers, so it is fetched one pair of groups ahead like the delta words of modes 1 / 2. Same FMAs in the same order
-// as every other mode: bit-identical results.
-// Slices with at most FOUR exception rows (the common case: 5 % of the rows out of line puts 3.2 into a slice on average) take the
-// corrections through the SCALAR cache instead: the 16 bytes behind the bases hold all of them, one s_load brings bases and corrections,
-// and a compare-and-select per exception puts its dword into its lane — no vector-memory instruction at all for the indices, as in modes 0 / 3.
-// (The kernel runs at the issue rate of its vector-memory instructions: the per-lane dword load of the general path is a ninth
-// instruction per group of 4 steps beside 2 value loads and 4 gathers.)
-struct SellDeltaIdx5 {
-	sell_int4 base;                                // wave-uniform
-	unsigned d;                                    // 4 x int8, exception lanes only            (general path)
-	sell_int4 corr;                                // corrections of exceptions 0..3, uniform   (scalar path)
-};
-
-// `rank` is 0 for the lanes that are no exception: they load the first exception's corrections (one address for all of them) and drop
-// them. No branch around the load: with one the compiler cannot count what is outstanding and waits for everything at every trip.
-template <bool NT, bool SCALAR>
-__device__ __forceinline__ void
-sell_delta_load_idx5(SellDeltaIdx5 & q, const unsigned char * __restrict__ gp /* uniform */, int rank)
-{
-	q.base = *reinterpret_cast<const sell_int4 *>(gp);
-	if constexpr (SCALAR)
-		q.corr = *reinterpret_cast<const sell_int4 *>(gp + 16);
-	else
-		q.d = ld_stream<NT>(reinterpret_cast<const unsigned *>(gp + 16) + rank);
-}
-
-template <bool SCALAR>
-__device__ __forceinline__ void
-sell_delta_cols5(const SellDeltaIdx5 & q, bool ex, int lane, int off, const int (&xl)[4], int (&c)[4])
-{
-	int d;
-	if constexpr (SCALAR)
-	{
-		// exception j's dword into its lane; slots past the slice's last exception name a lane that is none and hold zeros (a spare lane keeps 0)
-		d = lane == xl[0] ? q.corr.x : 0;
-		d = lane == xl[1] ? q.corr.y : d;
-		d = lane == xl[2] ? q.corr.z : d;
-		d = lane == xl[3] ? q.corr.w : d;
-	}
-	else
-		d = ex ? (int) q.d : 0;
-	c[0] = q.base.x + off + ((d << 24) >> 24);
-	c[1] = q.base.y + off + ((d << 16) >> 24);
-	c[2] = q.base.z + off + ((d << 8) >> 24);
-	c[3] = q.base.w + off + (d >> 24);
-}
 
 // keeps what was fetched a trip ahead in the trip it was fetched in (sell_pin above)
 template <bool SCALAR>

@@ -69,6 +69,17 @@ int launch_sell(bool f32, int C, const int64_t * slice_ptr, const int * col, con
 int launch_sell_delta(bool f32, int waves_per_slice, bool v7, const int64_t * desc, const unsigned char * idx, const void * val, const int * row_of_sorted,
 		const void * x, void * y, int m, int num_slices, const LaunchCfg & cfg, hipStream_t stream, long * grid_out);
 
+// Y = A X (beta 0) / Y += A X (beta 1) for k vectors on the same layout (kernels_sell_spmm.hip): X holds the cols() rows of k values at
+// X + c * ldx, Y the rows at Y + r * ldy. One launch per pass of 8, 4, 2 or 1 columns (8 per pass, then the binary remainder of k);
+// k == 1 with ldx == ldy == 1 is launch_sell_delta itself. Column j is bit-identical to launch_sell_delta on column j.
+int launch_sell_delta_spmm(bool f32, int waves_per_slice, bool v7, const int64_t * desc, const unsigned char * idx, const void * val,
+		const int * row_of_sorted, int k, const void * X, long ldx, void * Y, long ldy, int m, int num_slices, const LaunchCfg & cfg,
+		hipStream_t stream, long * grid_out);
+// what every other layout's spmm runs per column j (kernels_sell_spmm.hip): x[i] = X[i * ldx] for i < n, and Y[i * ldy] = y[i]
+// (beta 0) / Y[i * ldy] + y[i] (beta 1) for i < m; X and Y point at column j
+int launch_spmm_column_gather(bool f32, const void * X, long ldx, void * x, long n, hipStream_t stream);
+int launch_spmm_column_scatter(bool f32, const void * y, void * Y, long ldy, long m, int beta, hipStream_t stream);
+
 // SELL-64 with the slice group's x window in LDS and 16-bit window-relative indices (kernels_sell_window.hip)
 int sell_window_lds_budget();
 int launch_sell_window(bool f32, int waves_per_slice, int slices_per_group, const int * grp, const int64_t * sdesc, const unsigned short * idx,

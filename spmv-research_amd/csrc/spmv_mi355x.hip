@@ -358,6 +358,138 @@ spmv_mi355x_time_device(spmv_mi355x_matrix * A, const void * x, void * y, int it
 	return 0;
 }
 
+// ---- Y = A X for k vectors (include/spmv_mi355x.h)
+
+// the argument checks every spmm entry point makes before it touches a device or any memory
+static int
+spmm_args_ok(const char * what, const spmv_mi355x_matrix * A, int k, const void * X, long ldx, const void * Y, long ldy)
+{
+	if (k < 1)
+		set_error("%s: k must be >= 1 (got %d)", what, k);
+	else if (ldx < k)
+		set_error("%s: ldx (%ld) must be >= k (%d)", what, ldx, k);
+	else if (ldy < k)
+		set_error("%s: ldy (%ld) must be >= k (%d)", what, ldy, k);
+	else if (!A)
+		set_error("%s: NULL handle", what);
+	else if ((!X && A->n > 0) || (!Y && A->m > 0))
+		set_error("%s: NULL %s", what, !X && A->n > 0 ? "X" : "Y");
+	else
+		return 1;
+	return 0;
+}
+
+static int
+spmm_enqueue(spmv_mi355x_matrix * A, int k, const void * X, long ldx, void * Y, long ldy, int beta, hipStream_t st)
+{
+	int cur = -1;
+	HIP_TRY(hipGetDevice(&cur));
+	if (cur != A->device)
+		HIP_TRY(hipSetDevice(A->device));
+	if (A->nnz == 0)
+	{
+		// as spmv_mi355x_spmv_device_async: Y = 0 is a fill of the k columns, Y += 0 nothing
+		if (!beta && A->m > 0)
+			HIP_TRY(hipMemset2DAsync(Y, (size_t) ldy * A->vbytes, 0, (size_t) k * A->vbytes, (size_t) A->m, st));
+		A->last_grid = 0;
+		return 0;
+	}
+	if (A->format == SPMV_MI355X_SELL_C_SIGMA && A->sell_delta && !A->sell_window && !A->sell_sym)
+	{
+		LaunchCfg cfg = A->cfg;
+		cfg.beta = beta ? 1 : 0;
+		long grid = 0;
+		const int rc = launch_sell_delta_spmm(A->f32, A->sell_split, A->sell_v7_slices > 0, A->d_sell_desc, A->d_sell_idx, A->d_val, A->d_row_of_sorted,
+				k, X, ldx, Y, ldy, (int) A->m, (int) A->sell_slices, cfg, st, &grid);
+		A->last_grid = grid;
+		return rc;
+	}
+	// every other layout, column by column: X[:, j] into contiguous scratch, the layout's own SpMV, the result into Y[:, j]
+	if (k == 1 && ldx == 1 && ldy == 1)
+		return spmv_mi355x_spmv_device_async(A, X, Y, beta, st);
+	if (!A->d_spmm_x)
+	{
+		const size_t xb = (size_t) (A->n + 64) * A->vbytes, yb = (size_t) (A->m + 64) * A->vbytes;
+		if (dev_alloc_bytes(&A->d_spmm_x, xb) || dev_alloc_bytes(&A->d_spmm_y, yb))
+			return 1;
+		HIP_TRY(hipMemset(A->d_spmm_x, 0, xb));
+		HIP_TRY(hipMemset(A->d_spmm_y, 0, yb));
+		HIP_TRY(hipDeviceSynchronize());
+	}
+	for (int j = 0; j < k; j++)
+	{
+		if (launch_spmm_column_gather(A->f32, (const char *) X + (size_t) j * A->vbytes, ldx, A->d_spmm_x, A->n, st)
+		    || spmv_mi355x_spmv_device_async(A, A->d_spmm_x, A->d_spmm_y, 0, st)
+		    || launch_spmm_column_scatter(A->f32, A->d_spmm_y, (char *) Y + (size_t) j * A->vbytes, ldy, A->m, beta ? 1 : 0, st))
+			return 1;
+	}
+	return 0;
+}
+
+int
+spmv_mi355x_spmm_device_async(spmv_mi355x_matrix * A, int k, const void * X, long ldx, void * Y, long ldy, int beta, void * hip_stream)
+{
+	if (!spmm_args_ok("spmm_device_async", A, k, X, ldx, Y, ldy))
+		return 1;
+	return spmm_enqueue(A, k, X, ldx, Y, ldy, beta, (hipStream_t) hip_stream);
+}
+
+int
+spmv_mi355x_time_spmm_device(spmv_mi355x_matrix * A, int k, const void * X, long ldx, void * Y, long ldy, int iters, void * hip_stream,
+		double * ms_out)
+{
+	if (!spmm_args_ok("time_spmm_device", A, k, X, ldx, Y, ldy))
+		return 1;
+	if (!ms_out)
+	{
+		set_error("time_spmm_device: NULL ms_per_iter_out");
+		return 1;
+	}
+	hipStream_t st = (hipStream_t) hip_stream;
+	HIP_TRY(hipSetDevice(A->device));
+	hipEvent_t e0, e1;
+	HIP_TRY(hipEventCreate(&e0));
+	HIP_TRY(hipEventCreate(&e1));
+	HIP_TRY(hipEventRecord(e0, st));
+	for (int i = 0; i < iters; i++)
+		if (spmm_enqueue(A, k, X, ldx, Y, ldy, 0, st))
+			return 1;
+	HIP_TRY(hipEventRecord(e1, st));
+	HIP_TRY(hipEventSynchronize(e1));
+	float ms = 0;
+	HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+	(void) hipEventDestroy(e0);
+	(void) hipEventDestroy(e1);
+	*ms_out = iters > 0 ? (double) ms / iters : 0;
+	return 0;
+}
+
+int
+spmv_mi355x_spmm(spmv_mi355x_matrix * A, int k, const void * X_host, void * Y_host)
+{
+	if (!spmm_args_ok("spmm", A, k, X_host, k, Y_host, k))
+		return 1;
+	HIP_TRY(hipSetDevice(A->device));
+	const size_t xb = (size_t) std::max<long>(A->n, 1) * k * A->vbytes, yb = (size_t) std::max<long>(A->m, 1) * k * A->vbytes;
+	void * dX = nullptr, * dY = nullptr;
+	hipStream_t st = nullptr;
+	auto hip_ok = [](hipError_t e, const char * call) {
+		if (e != hipSuccess)
+			set_error("spmm: %s: %s", call, hipGetErrorString(e));
+		return e == hipSuccess;
+	};
+	bool ok = !dev_alloc_bytes(&dX, xb) && !dev_alloc_bytes(&dY, yb) && hip_ok(hipStreamCreate(&st), "hipStreamCreate");
+	ok = ok && (A->n == 0 || hip_ok(hipMemcpyAsync(dX, X_host, (size_t) A->n * k * A->vbytes, hipMemcpyHostToDevice, st), "upload of X"));
+	ok = ok && !spmm_enqueue(A, k, dX, k, dY, k, 0, st);
+	ok = ok && (A->m == 0 || hip_ok(hipMemcpyAsync(Y_host, dY, (size_t) A->m * k * A->vbytes, hipMemcpyDeviceToHost, st), "download of Y"));
+	ok = ok && hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize");
+	if (st)
+		(void) hipStreamDestroy(st);
+	(void) hipFree(dX);
+	(void) hipFree(dY);
+	return ok ? 0 : 1;
+}
+
 int
 spmv_mi355x_kernel_info(const spmv_mi355x_matrix * A, char * name_out, long name_n, long * grid_out, int * block_out)
 {

@@ -47,6 +47,7 @@ SYMBOLS = [
     "spmv_mi355x_partitioned_mem_footprint",
     "spmv_mi355x_upload_y", "spmv_mi355x_output_alloc", "spmv_mi355x_input_alloc", "spmv_mi355x_output_free", "spmv_mi355x_placement_release", "spmv_mi355x_placement_info", "spmv_mi355x_place_arrays",
     "spmv_mi355x_csr_stream_begin", "spmv_mi355x_csr_stream_append", "spmv_mi355x_create_from_stream", "spmv_mi355x_csr_stream_discard",
+    "spmv_mi355x_spmm_device_async", "spmv_mi355x_time_spmm_device", "spmv_mi355x_spmm",
 ]
 
 _lib = None
@@ -356,6 +357,30 @@ class Matrix:
         ms = C.c_double()
         _check(lib().spmv_mi355x_time_device(self.h, C.c_void_p(x_ptr), C.c_void_p(y_ptr), C.c_int(iters),
                                              C.c_void_p(stream), C.byref(ms)))
+        return ms.value
+
+    def spmm(self, X):
+        """Y = A X for a host array X of shape (cols, k): returns Y of shape (rows, k) (spmv_mi355x_spmm, one pass over the matrix per
+        8 columns on the SELL delta layout)."""
+        X = np.ascontiguousarray(X, self.dtype)
+        if X.ndim != 2 or X.shape[0] != self.n:
+            raise ValueError(f"X must have shape ({self.n}, k), got {X.shape}")
+        k = X.shape[1]
+        Y = np.zeros((self.m, k), self.dtype)
+        _check(lib().spmv_mi355x_spmm(self.h, C.c_int(k), _p(X), _p(Y)))
+        return Y
+
+    def spmm_device(self, k, x_ptr, ldx, y_ptr, ldy, beta=0, stream=0):
+        """Y = A X (beta 0) / Y += A X (beta 1) on device pointers: X has cols rows of k values ldx apart, Y rows rows ldy apart (in
+        values); enqueued on `stream` (spmv_mi355x_spmm_device_async)."""
+        _check(lib().spmv_mi355x_spmm_device_async(self.h, C.c_int(k), C.c_void_p(x_ptr), C.c_long(ldx), C.c_void_p(y_ptr), C.c_long(ldy),
+                                                   C.c_int(beta), C.c_void_p(stream)))
+
+    def time_spmm_device(self, k, x_ptr, ldx, y_ptr, ldy, iters, stream=0):
+        """ms per spmm of `iters` back-to-back launches, timed with HIP events on `stream` (spmv_mi355x_time_spmm_device)."""
+        ms = C.c_double()
+        _check(lib().spmv_mi355x_time_spmm_device(self.h, C.c_int(k), C.c_void_p(x_ptr), C.c_long(ldx), C.c_void_p(y_ptr), C.c_long(ldy),
+                                                  C.c_int(iters), C.c_void_p(stream), C.byref(ms)))
         return ms.value
 
     def kernel_info(self):

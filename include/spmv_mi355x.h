@@ -257,6 +257,23 @@ int  spmv_mi355x_pcg(spmv_mi355x_matrix * A, const int32_t * row_ptr, const int3
 int  spmv_mi355x_pbicgstab(spmv_mi355x_matrix * A, const int32_t * row_ptr, const int32_t * col_idx, const double * values_fp64,
 		const void * b_host, void * x_res_out_host, long max_iterations, double * history_out, spmv_mi355x_solver_info * info);
 
+/* Multi-RHS form of the same two solvers: k independent systems A x_j = b_j on one handle. Column j returns exactly (bit for
+ * bit) what spmv_mi355x_pcg / _pbicgstab return for b_j on the same handle whenever the handle's SpMV is deterministic; the
+ * k recurrences stay independent (no shared Krylov subspace). What is shared: one spmv_mi355x_spmm_device_async pass over
+ * the matrix per SpMV of the single solver, every kernel launch, the Jacobi diagonal.
+ * B_host is rows() x k, row-major (ld = k), in the handle's precision; X_res_out_host has the same shape and receives each
+ * column's x_best. history_out (may be NULL): k * 3 * max_iterations doubles, column j's block at
+ * history_out + j * 3 * max_iterations, laid out as the single solver's. info (may be NULL): an array of k elements whose
+ * stride is the caller's info[0].struct_size; every element is written with that size. iterations, error, error_best, eps,
+ * eps_counter and restarts are per column; spmv_calls counts the SpMM launches of the call and seconds is its wall time
+ * (both the same in every element). The host stops enqueueing once every column has reached its `err < eps` break (with
+ * the single solver's polling lag); until then a broken column stays frozen. Errors as the single solvers, plus k < 1;
+ * argument errors return before any device is touched. */
+int  spmv_mi355x_pcg_multi(spmv_mi355x_matrix * A, int k, const int32_t * row_ptr, const int32_t * col_idx, const double * values_fp64,
+		const void * B_host, void * X_res_out_host, long max_iterations, double * history_out, spmv_mi355x_solver_info * info);
+int  spmv_mi355x_pbicgstab_multi(spmv_mi355x_matrix * A, int k, const int32_t * row_ptr, const int32_t * col_idx, const double * values_fp64,
+		const void * B_host, void * X_res_out_host, long max_iterations, double * history_out, spmv_mi355x_solver_info * info);
+
 /* Row-partitioned (multi-GPU) form of the same two solvers: one process per GPU owns the row block [row_offset,
  * row_offset + m_local) of A, b and x. The solver keeps every vector device-resident and local; the two things that cross
  * ranks are handed to the caller, who has the communicator (torch.distributed / RCCL in bench-level code):

@@ -1,0 +1,1025 @@
+// Multi-RHS forms of the device-resident Krylov solvers of solvers.hip: k independent systems A x_j = b_j solved together.
+//
+// Column j of spmv_mi355x_pcg_multi / spmv_mi355x_pbicgstab_multi returns exactly what spmv_mi355x_pcg / _pbicgstab
+// return for b_j on the same handle. The k recurrences stay independent (this is not block CG with a shared subspace);
+// what they share is the matrix pass, the launches and the Jacobi diagonal:
+//   * every solver vector is a row-major m x k block (ld = k), K is one vector of m; each SpMV of the single solver is
+//     one spmv_mi355x_spmm_device_async over the k columns, bit-identical per column to the single SpMV;
+//   * each vector kernel of solvers.hip has a batched twin here that serves a chunk of KC in {8, 4, 2, 1} columns
+//     (k = 8s, then the binary remainder, as the SpMM does); a thread owns row i of its chunk, so it reads KC
+//     contiguous values per vector (vector loads when ld and the chunk start are multiples of KC);
+//   * bit-identity: every per-column dot product goes through the same additions in the same order as the single
+//     solver's (same nb and grid-stride rows per (block, thread), same wave shuffle tree, same in-order sum of the 4
+//     wave partials, same sum_partials order), and every element update is the same T expression, so FMA contraction
+//     matches; the KC columns only share the LDS barriers of one block reduction;
+//   * state is SolverState[2][k], partials are [k][NUM_SLOTS][MAX_PART]; each column has its own `done` flag, which
+//     freezes that column only (its values are stored back unchanged; the SpMM keeps computing it);
+//   * block 0 of the last chunk of an iteration's last kernel posts (iterations finished, loop count at which the last
+//     still-running column broke, or -1) to the host-mapped progress word; the host applies the single solver's stop
+//     rule to it.
+
+#include <chrono>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <type_traits>
+#include <vector>
+
+#include "common.hpp"
+#include "solvers_common.hpp"
+#include "../../include/spmv_mi355x.h"
+
+namespace spmv {
+
+constexpr int MAX_KC = 8;          // columns per chunk
+
+// block_sum() for N values at once: each value goes through the same shuffle tree and the same in-order sum of the
+// VB / WAVE wave partials, behind one set of barriers.
+template <int N>
+__device__ __forceinline__ void
+block_sum_n(double * v)
+{
+	__shared__ double sh[N][VB / WAVE];
+	__shared__ double total[N];
+	#pragma unroll
+	for (int c = 0; c < N; c++)
+		for (int o = WAVE / 2; o > 0; o >>= 1)
+			v[c] += __shfl_down(v[c], o, WAVE);
+	__syncthreads();                       // protects sh/total against the previous call
+	if (threadIdx.x % WAVE == 0)
+	{
+		#pragma unroll
+		for (int c = 0; c < N; c++)
+			sh[c][threadIdx.x / WAVE] = v[c];
+	}
+	__syncthreads();
+	if (threadIdx.x < N)
+	{
+		double s = 0;
+		for (int w = 0; w < VB / WAVE; w++)
+			s += sh[threadIdx.x][w];
+		total[threadIdx.x] = s;
+	}
+	__syncthreads();
+	#pragma unroll
+	for (int c = 0; c < N; c++)
+		v[c] = total[c];
+}
+
+__host__ __device__ __forceinline__ long
+part_at(int col, int slot)
+{
+	return ((long) col * NUM_SLOTS + slot) * MAX_PART;
+}
+
+// sum_partials() of S slots for the KC columns c0.. : out[s * KC + c]
+template <int KC, int S>
+__device__ __forceinline__ void
+sum_partials_n(const double * __restrict__ part, int c0, const int (&slot)[S], int nb, double * out)
+{
+	#pragma unroll
+	for (int s = 0; s < S; s++)
+	{
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+		{
+			const double * p = part + part_at(c0 + c, slot[s]);
+			double v = 0;
+			for (int i = threadIdx.x; i < nb; i += VB)
+				v += p[i];
+			out[s * KC + c] = v;
+		}
+	}
+	block_sum_n<S * KC>(out);
+}
+
+// store_partial() of S slots for the KC columns c0.. from v[s * KC + c]; only the columns in `keep` are written
+template <int KC, int S>
+__device__ __forceinline__ void
+store_partials_n(double * __restrict__ part, int c0, const int (&slot)[S], double * v, unsigned keep)
+{
+	block_sum_n<S * KC>(v);
+	if (threadIdx.x == 0)
+	{
+		#pragma unroll
+		for (int s = 0; s < S; s++)
+		{
+			#pragma unroll
+			for (int c = 0; c < KC; c++)
+				if (keep >> c & 1)
+					part[part_at(c0 + c, slot[s]) + blockIdx.x] = v[s * KC + c];
+		}
+	}
+}
+
+// KC contiguous values of one row; `vec` (uniform) when the row start is KC-aligned
+template <typename T, int KC>
+__device__ __forceinline__ void
+load_row(T (&o)[KC], const T * p, bool vec)
+{
+	if constexpr (KC > 1)
+	{
+		if (vec)
+		{
+			typedef T V __attribute__((ext_vector_type(KC)));
+			const V t = *(const V *) p;
+			#pragma unroll
+			for (int c = 0; c < KC; c++)
+				o[c] = t[c];
+			return;
+		}
+	}
+	#pragma unroll
+	for (int c = 0; c < KC; c++)
+		o[c] = p[c];
+}
+
+template <typename T, int KC>
+__device__ __forceinline__ void
+store_row(T * p, const T (&o)[KC], bool vec)
+{
+	if constexpr (KC > 1)
+	{
+		if (vec)
+		{
+			typedef T V __attribute__((ext_vector_type(KC)));
+			V t;
+			#pragma unroll
+			for (int c = 0; c < KC; c++)
+				t[c] = o[c];
+			*(V *) p = t;
+			return;
+		}
+	}
+	#pragma unroll
+	for (int c = 0; c < KC; c++)
+		p[c] = o[c];
+}
+
+// the columns of the chunk that have not reached the `err < eps` break
+template <int KC>
+__device__ __forceinline__ unsigned
+live_mask(const SolverState * __restrict__ st_p, int c0)
+{
+	unsigned live = 0;
+	#pragma unroll
+	for (int c = 0; c < KC; c++)
+		if (!st_p[c0 + c].done)
+			live |= 1u << c;
+	return live;
+}
+
+// ------------------------------------------------------------------------------------------------ shared kernels
+
+// residual_kernel per column: r = b - Ax ; partials A = r.r, B = b.b
+template <typename T, int KC>
+__global__ __launch_bounds__(VB) void
+residual_multi_kernel(const T * __restrict__ b, const T * __restrict__ Ax, T * __restrict__ r, long m, long ld, int c0,
+		double * __restrict__ part)
+{
+	const bool vec = ld % KC == 0 && c0 % KC == 0;
+	double acc[2 * KC] = {};
+	GRID_STRIDE(i, m)
+	{
+		const long o = i * ld + c0;
+		T bv[KC], av[KC], rv[KC];
+		load_row(bv, b + o, vec);
+		load_row(av, Ax + o, vec);
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+		{
+			const T bi = bv[c];
+			const T ri = bi + (T) -1 * av[c];
+			rv[c] = ri;
+			acc[c] += (double) ri * (double) ri;
+			acc[KC + c] += (double) bi * (double) bi;
+		}
+		store_row(r + o, rv, vec);
+	}
+	store_partials_n<KC, 2>(part, c0, {P_A, P_B}, acc, ~0u);
+}
+
+// explicit_kernel per column
+template <typename T, int KC>
+__global__ __launch_bounds__(VB) void
+explicit_multi_kernel(const SolverState * __restrict__ st_p, const T * __restrict__ x, T * __restrict__ x_best,
+		const T * __restrict__ r_explicit, T * __restrict__ r, T * __restrict__ p, const T * __restrict__ K, long m, long ld,
+		int c0, int nb, int allow_restart, int ignore_done, double * __restrict__ part)
+{
+	const unsigned act = ignore_done ? (1u << KC) - 1 : live_mask<KC>(st_p, c0);
+	if (!act)
+		return;
+	double ee[KC];
+	sum_partials_n<KC, 1>(part, c0, {P_A}, nb, ee);
+	unsigned promote = 0, restart = 0;
+	#pragma unroll
+	for (int c = 0; c < KC; c++)
+	{
+		bool pr, rs;
+		explicit_decide(st_p[c0 + c], sqrt(ee[c]), allow_restart, pr, rs);
+		if (act >> c & 1)
+		{
+			promote |= (unsigned) pr << c;
+			restart |= (unsigned) rs << c;
+		}
+	}
+	double zr[KC] = {};
+	if (promote | restart)
+	{
+		GRID_STRIDE(i, m)
+		{
+			const long o = i * ld + c0;
+			#pragma unroll
+			for (int c = 0; c < KC; c++)
+			{
+				if (promote >> c & 1)
+					x_best[o + c] = x[o + c];
+				if (restart >> c & 1)
+				{
+					const T ri = r_explicit[o + c];
+					const T zi = ri / K[i];
+					r[o + c] = ri;
+					p[o + c] = zi;
+					zr[c] += (double) zi * (double) ri;
+				}
+			}
+		}
+	}
+	if (restart)
+		store_partials_n<KC, 1>(part, c0, {P_C}, zr, restart);
+}
+
+// explicit_fin_kernel with one block per column
+__global__ __launch_bounds__(VB) void
+explicit_fin_multi_kernel(SolverState * __restrict__ st_base, int nb, int allow_restart, int ignore_done, const double * __restrict__ part_base)
+{
+	SolverState * st_p = st_base + blockIdx.x;
+	const double * part = part_base + part_at(blockIdx.x, 0);
+	SolverState st = *st_p;
+	if (st.done && !ignore_done)
+		return;
+	const double err_explicit = sqrt(sum_partials(part, P_A, nb));
+	bool promote, restart;
+	explicit_decide(st, err_explicit, allow_restart, promote, restart);
+	double zr = 0;
+	if (restart)
+		zr = sum_partials(part, P_C, nb);
+	if (threadIdx.x == 0)
+	{
+		st.err_explicit = err_explicit;
+		if (promote)
+			st.err_best = err_explicit;
+		if (restart)
+		{
+			st.zr = zr;
+			st.restarts++;
+		}
+		*st_p = st;
+	}
+}
+
+// init_state_kernel with one block per column
+__global__ __launch_bounds__(VB) void
+init_state_multi_kernel(SolverState * __restrict__ st_base, int k, int nb, int mode, const double * __restrict__ part_base)
+{
+	const double * part = part_base + part_at(blockIdx.x, 0);
+	const double rr = sum_partials(part, P_A, nb);
+	const double bb = sum_partials(part, P_B, nb);
+	const double zr = mode == 0 ? sum_partials(part, P_C, nb) : rr;
+	if (threadIdx.x == 0)
+	{
+		SolverState st;
+		const double b_norm = sqrt(bb);
+		st.err = sqrt(rr);
+		st.eps = 1.0e-15 * b_norm;
+		st.eps_counter = 1.0e-7 * b_norm;
+		st.err_explicit = st.err;
+		st.err_best = st.err;
+		st.zr = zr;
+		st.k = 0;
+		st.restarts = 0;
+		st.done = mode == 0 && st.err < st.eps;
+		st.pad = 0;
+		st_base[blockIdx.x] = st;
+		st_base[k + blockIdx.x] = st;
+	}
+}
+
+// history rows of the chunk's columns at iteration it (block 0, thread 0)
+template <int KC>
+__device__ __forceinline__ void
+record_history(const SolverState * __restrict__ st_p, int c0, unsigned cols, double * __restrict__ history, long hist_ld, long it)
+{
+	if (history && blockIdx.x == 0 && threadIdx.x == 0)
+	{
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+			if (cols >> c & 1)
+			{
+				const SolverState & st = st_p[c0 + c];
+				double * h = history + (c0 + c) * hist_ld + 3 * it;
+				h[0] = st.err;
+				h[1] = st.err_explicit;
+				h[2] = st.err_best;
+			}
+	}
+}
+
+// (iterations finished, loop count at which the last still-running column broke, or -1) from the next states of all
+// k columns: the earlier chunks wrote theirs in earlier launches, this thread wrote its own chunk's
+__device__ __forceinline__ void
+post_progress_multi(const SolverState * st_next, int k, long it, volatile long * host_progress)
+{
+	long broke_at = 0;
+	for (int c = 0; c < k; c++)
+	{
+		if (!st_next[c].done)
+		{
+			broke_at = -1;
+			break;
+		}
+		broke_at = st_next[c].k > broke_at ? st_next[c].k : broke_at;
+	}
+	post_progress(host_progress, it + 1, broke_at);
+}
+
+// ------------------------------------------------------------------------------------------------ CG
+
+// cg_init_kernel per column: p = z = r/K; partial C = z.r
+template <typename T, int KC>
+__global__ __launch_bounds__(VB) void
+cg_init_multi_kernel(const T * __restrict__ r, const T * __restrict__ K, T * __restrict__ p, long m, long ld, int c0,
+		double * __restrict__ part)
+{
+	const bool vec = ld % KC == 0 && c0 % KC == 0;
+	double zr[KC] = {};
+	GRID_STRIDE(i, m)
+	{
+		const long o = i * ld + c0;
+		T rv[KC], pv[KC];
+		load_row(rv, r + o, vec);
+		const T ki = K[i];
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+		{
+			const T ri = rv[c];
+			const T zi = ri / ki;
+			pv[c] = zi;
+			zr[c] += (double) zi * (double) ri;
+		}
+		store_row(p + o, pv, vec);
+	}
+	store_partials_n<KC, 1>(part, c0, {P_C}, zr, ~0u);
+}
+
+// cg_dot_kernel per column: partial A = p.Ap, history row
+template <typename T, int KC>
+__global__ __launch_bounds__(VB) void
+cg_dot_multi_kernel(const SolverState * __restrict__ st_p, const T * __restrict__ p, const T * __restrict__ Ap, long m, long ld,
+		int c0, double * __restrict__ history, long hist_ld, long it, double * __restrict__ part)
+{
+	const unsigned live = live_mask<KC>(st_p, c0);
+	if (!live)
+		return;
+	record_history<KC>(st_p, c0, live, history, hist_ld, it);
+	const bool vec = ld % KC == 0 && c0 % KC == 0;
+	double s[KC] = {};
+	GRID_STRIDE(i, m)
+	{
+		const long o = i * ld + c0;
+		T pv[KC], av[KC];
+		load_row(pv, p + o, vec);
+		load_row(av, Ap + o, vec);
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+			s[c] += (double) pv[c] * (double) av[c];
+	}
+	store_partials_n<KC, 1>(part, c0, {P_A}, s, live);
+}
+
+// cg_update_kernel per column: x += ak p; r -= ak Ap; partials D = z.r, E = r.r
+template <typename T, int KC>
+__global__ __launch_bounds__(VB) void
+cg_update_multi_kernel(const SolverState * __restrict__ st_p, T * __restrict__ x, T * __restrict__ r, const T * __restrict__ p,
+		const T * __restrict__ Ap, const T * __restrict__ K, long m, long ld, int c0, int nb, double * __restrict__ part)
+{
+	const unsigned live = live_mask<KC>(st_p, c0);
+	if (!live)
+		return;
+	const bool vec = ld % KC == 0 && c0 % KC == 0;
+	double pap[KC];
+	sum_partials_n<KC, 1>(part, c0, {P_A}, nb, pap);
+	T ak[KC];
+	#pragma unroll
+	for (int c = 0; c < KC; c++)
+		ak[c] = (T) (st_p[c0 + c].zr / pap[c]);
+	double acc[2 * KC] = {};
+	GRID_STRIDE(i, m)
+	{
+		const long o = i * ld + c0;
+		T xv[KC], rv[KC], pv[KC], av[KC];
+		load_row(xv, x + o, vec);
+		load_row(rv, r + o, vec);
+		load_row(pv, p + o, vec);
+		load_row(av, Ap + o, vec);
+		const T ki = K[i];
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+		{
+			const T xi = xv[c] + ak[c] * pv[c];
+			const T ri = rv[c] + (-ak[c]) * av[c];
+			const T zi = ri / ki;
+			acc[c] += (double) zi * (double) ri;
+			acc[KC + c] += (double) ri * (double) ri;
+			if (live >> c & 1)
+			{
+				xv[c] = xi;
+				rv[c] = ri;
+			}
+		}
+		store_row(x + o, xv, vec);
+		store_row(r + o, rv, vec);
+	}
+	store_partials_n<KC, 2>(part, c0, {P_D, P_E}, acc, live);
+}
+
+// cg_direction_kernel per column: p = z + bk p; block 0 writes the next states; the last chunk posts progress
+template <typename T, int KC>
+__global__ __launch_bounds__(VB) void
+cg_direction_multi_kernel(const SolverState * __restrict__ st_p, SolverState * __restrict__ st_next, const T * __restrict__ r,
+		T * __restrict__ p, const T * __restrict__ K, long m, long ld, int c0, int k, int nb, const double * __restrict__ part,
+		long it, volatile long * host_progress)
+{
+	const unsigned live = live_mask<KC>(st_p, c0);
+	double zr_new[KC] = {}, rr[KC] = {};
+	if (live)
+	{
+		const bool vec = ld % KC == 0 && c0 % KC == 0;
+		sum_partials_n<KC, 1>(part, c0, {P_D}, nb, zr_new);
+		T bk[KC];
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+			bk[c] = (T) (zr_new[c] / st_p[c0 + c].zr);
+		GRID_STRIDE(i, m)
+		{
+			const long o = i * ld + c0;
+			T rv[KC], pv[KC];
+			load_row(rv, r + o, vec);
+			load_row(pv, p + o, vec);
+			const T ki = K[i];
+			#pragma unroll
+			for (int c = 0; c < KC; c++)
+			{
+				const T pi = rv[c] / ki + bk[c] * pv[c];
+				if (live >> c & 1)
+					pv[c] = pi;
+			}
+			store_row(p + o, pv, vec);
+		}
+	}
+	if (blockIdx.x == 0)
+	{
+		if (live)
+			sum_partials_n<KC, 1>(part, c0, {P_E}, nb, rr);
+		if (threadIdx.x == 0)
+		{
+			#pragma unroll
+			for (int c = 0; c < KC; c++)
+			{
+				SolverState nx = st_p[c0 + c];
+				if (live >> c & 1)
+				{
+					nx.zr = zr_new[c];
+					nx.err = sqrt(rr[c]);
+					nx.k = nx.k + 1;
+					nx.done = nx.err < nx.eps;
+				}
+				st_next[c0 + c] = nx;
+			}
+			if (c0 + KC == k)
+				post_progress_multi(st_next, k, it, host_progress);
+		}
+	}
+}
+
+// ------------------------------------------------------------------------------------------------ BiCGSTAB
+
+// bicg_init_kernel per column: r0_ = r, p = r, y = p/K
+template <typename T, int KC>
+__global__ __launch_bounds__(VB) void
+bicg_init_multi_kernel(const T * __restrict__ r, const T * __restrict__ K, T * __restrict__ r0, T * __restrict__ p, T * __restrict__ y,
+		long m, long ld, int c0)
+{
+	const bool vec = ld % KC == 0 && c0 % KC == 0;
+	GRID_STRIDE(i, m)
+	{
+		const long o = i * ld + c0;
+		T rv[KC], yv[KC];
+		load_row(rv, r + o, vec);
+		const T ki = K[i];
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+			yv[c] = rv[c] / ki;
+		store_row(r0 + o, rv, vec);
+		store_row(p + o, rv, vec);
+		store_row(y + o, yv, vec);
+	}
+}
+
+// bicg_dot_kernel per column: partial A = r0_.v, history row
+template <typename T, int KC>
+__global__ __launch_bounds__(VB) void
+bicg_dot_multi_kernel(const SolverState * __restrict__ st_p, const T * __restrict__ r0, const T * __restrict__ v, long m, long ld,
+		int c0, double * __restrict__ history, long hist_ld, long it, double * __restrict__ part)
+{
+	record_history<KC>(st_p, c0, ~0u, history, hist_ld, it);
+	const bool vec = ld % KC == 0 && c0 % KC == 0;
+	double s[KC] = {};
+	GRID_STRIDE(i, m)
+	{
+		const long o = i * ld + c0;
+		T r0v[KC], vv[KC];
+		load_row(r0v, r0 + o, vec);
+		load_row(vv, v + o, vec);
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+			s[c] += (double) r0v[c] * (double) vv[c];
+	}
+	store_partials_n<KC, 1>(part, c0, {P_A}, s, ~0u);
+}
+
+// bicg_s_kernel per column: s = r - s_a v; z = s/K
+template <typename T, int KC>
+__global__ __launch_bounds__(VB) void
+bicg_s_multi_kernel(const SolverState * __restrict__ st_p, const T * __restrict__ r, const T * __restrict__ v, const T * __restrict__ K,
+		T * __restrict__ s, T * __restrict__ z, long m, long ld, int c0, int nb, const double * __restrict__ part)
+{
+	const bool vec = ld % KC == 0 && c0 % KC == 0;
+	double pa[KC];
+	sum_partials_n<KC, 1>(part, c0, {P_A}, nb, pa);
+	T s_a[KC];
+	#pragma unroll
+	for (int c = 0; c < KC; c++)
+		s_a[c] = (T) ((T) st_p[c0 + c].zr / (T) pa[c]);
+	GRID_STRIDE(i, m)
+	{
+		const long o = i * ld + c0;
+		T rv[KC], vv[KC], sv[KC], zv[KC];
+		load_row(rv, r + o, vec);
+		load_row(vv, v + o, vec);
+		const T ki = K[i];
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+		{
+			const T si = rv[c] + (-s_a[c]) * vv[c];
+			sv[c] = si;
+			zv[c] = si / ki;
+		}
+		store_row(s + o, sv, vec);
+		store_row(z + o, zv, vec);
+	}
+}
+
+// bicg_omega_kernel per column: partials B = sum (t/K)(s/K), C = sum (t/K)^2
+template <typename T, int KC>
+__global__ __launch_bounds__(VB) void
+bicg_omega_multi_kernel(const T * __restrict__ t, const T * __restrict__ s, const T * __restrict__ K, long m, long ld, int c0,
+		double * __restrict__ part)
+{
+	const bool vec = ld % KC == 0 && c0 % KC == 0;
+	double acc[2 * KC] = {};
+	GRID_STRIDE(i, m)
+	{
+		const long o = i * ld + c0;
+		T tv[KC], sv[KC];
+		load_row(tv, t + o, vec);
+		load_row(sv, s + o, vec);
+		const T ki = K[i];
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+		{
+			const T v1 = tv[c] / ki;
+			const T v2 = sv[c] / ki;
+			acc[c] += (double) v1 * (double) v2;
+			acc[KC + c] += (double) v1 * (double) v1;
+		}
+	}
+	store_partials_n<KC, 2>(part, c0, {P_B, P_C}, acc, ~0u);
+}
+
+// bicg_update_kernel per column: r = s - s_w t; x = (x + s_a y) + s_w z; partials D = r0_.r, E = r.r
+template <typename T, int KC>
+__global__ __launch_bounds__(VB) void
+bicg_update_multi_kernel(const SolverState * __restrict__ st_p, const T * __restrict__ s, const T * __restrict__ t, const T * __restrict__ y,
+		const T * __restrict__ z, const T * __restrict__ r0, T * __restrict__ r, T * __restrict__ x, long m, long ld, int c0, int nb,
+		double * __restrict__ part)
+{
+	const bool vec = ld % KC == 0 && c0 % KC == 0;
+	double q[3 * KC];
+	sum_partials_n<KC, 3>(part, c0, {P_A, P_B, P_C}, nb, q);
+	T s_a[KC], s_w[KC];
+	#pragma unroll
+	for (int c = 0; c < KC; c++)
+	{
+		s_a[c] = (T) ((T) st_p[c0 + c].zr / (T) q[c]);
+		s_w[c] = (T) ((T) q[KC + c] / (T) q[2 * KC + c]);
+	}
+	double acc[2 * KC] = {};
+	GRID_STRIDE(i, m)
+	{
+		const long o = i * ld + c0;
+		T sv[KC], tv[KC], yv[KC], zv[KC], r0v[KC], rv[KC], xv[KC];
+		load_row(sv, s + o, vec);
+		load_row(tv, t + o, vec);
+		load_row(yv, y + o, vec);
+		load_row(zv, z + o, vec);
+		load_row(r0v, r0 + o, vec);
+		load_row(xv, x + o, vec);
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+		{
+			const T ri = sv[c] + (-s_w[c]) * tv[c];
+			rv[c] = ri;
+			const T hi = xv[c] + s_a[c] * yv[c];
+			xv[c] = hi + s_w[c] * zv[c];
+			acc[c] += (double) r0v[c] * (double) ri;
+			acc[KC + c] += (double) ri * (double) ri;
+		}
+		store_row(r + o, rv, vec);
+		store_row(x + o, xv, vec);
+	}
+	store_partials_n<KC, 2>(part, c0, {P_D, P_E}, acc, ~0u);
+}
+
+// bicg_direction_kernel per column: p = r + s_b (p - s_w v); y = p/K; block 0 writes the next states; the last chunk posts
+template <typename T, int KC>
+__global__ __launch_bounds__(VB) void
+bicg_direction_multi_kernel(const SolverState * __restrict__ st_p, SolverState * __restrict__ st_next, const T * __restrict__ r,
+		const T * __restrict__ v, const T * __restrict__ K, T * __restrict__ p, T * __restrict__ y, long m, long ld, int c0, int k,
+		int nb, const double * __restrict__ part, long it, volatile long * host_progress)
+{
+	const bool vec = ld % KC == 0 && c0 % KC == 0;
+	double q[4 * KC];
+	sum_partials_n<KC, 4>(part, c0, {P_A, P_B, P_C, P_D}, nb, q);
+	T s_w[KC], s_b[KC], s_pk[KC];
+	#pragma unroll
+	for (int c = 0; c < KC; c++)
+	{
+		const T s_pk_p = (T) st_p[c0 + c].zr;
+		const T s_a = (T) (s_pk_p / (T) q[c]);
+		s_w[c] = (T) ((T) q[KC + c] / (T) q[2 * KC + c]);
+		const double s_pk_d = q[3 * KC + c];
+		s_pk[c] = (T) s_pk_d;
+		s_b[c] = (s_pk[c] / s_pk_p) * (s_a / s_w[c]);
+	}
+	GRID_STRIDE(i, m)
+	{
+		const long o = i * ld + c0;
+		T rv[KC], vv[KC], pv[KC], yv[KC];
+		load_row(rv, r + o, vec);
+		load_row(vv, v + o, vec);
+		load_row(pv, p + o, vec);
+		const T ki = K[i];
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+		{
+			const T pi = rv[c] + s_b[c] * (pv[c] - s_w[c] * vv[c]);
+			pv[c] = pi;
+			yv[c] = pi / ki;
+		}
+		store_row(p + o, pv, vec);
+		store_row(y + o, yv, vec);
+	}
+	if (blockIdx.x == 0)
+	{
+		double rr[KC];
+		sum_partials_n<KC, 1>(part, c0, {P_E}, nb, rr);
+		if (threadIdx.x == 0)
+		{
+			#pragma unroll
+			for (int c = 0; c < KC; c++)
+			{
+				SolverState nx = st_p[c0 + c];
+				nx.zr = (double) s_pk[c];
+				nx.err = sqrt(rr[c]);
+				nx.k = nx.k + 1;
+				st_next[c0 + c] = nx;
+			}
+			if (c0 + KC == k)
+				post_progress(host_progress, it + 1, -1);
+		}
+	}
+}
+
+// ------------------------------------------------------------------------------------------------ host side
+
+struct Chunk {
+	int c0, kc;
+};
+
+// k = 8s, then the binary remainder (the SpMM's column passes)
+static std::vector<Chunk>
+column_chunks(int k)
+{
+	std::vector<Chunk> out;
+	int c0 = 0;
+	for (; k - c0 >= MAX_KC; c0 += MAX_KC)
+		out.push_back({c0, MAX_KC});
+	for (int w = MAX_KC / 2; w >= 1; w /= 2)
+		if (k - c0 >= w)
+		{
+			out.push_back({c0, w});
+			c0 += w;
+		}
+	return out;
+}
+
+// f(c0, std::integral_constant<int, KC>) for every chunk, in column order
+template <typename F>
+static void
+for_chunks(const std::vector<Chunk> & chunks, F && f)
+{
+	for (const Chunk & ch : chunks)
+		switch (ch.kc)
+		{
+		case 8: f(ch.c0, std::integral_constant<int, 8>()); break;
+		case 4: f(ch.c0, std::integral_constant<int, 4>()); break;
+		case 2: f(ch.c0, std::integral_constant<int, 2>()); break;
+		default: f(ch.c0, std::integral_constant<int, 1>()); break;
+		}
+}
+
+template <typename T>
+static int
+solve_multi(const char * what, int method, spmv_mi355x_matrix * A, int k, const int32_t * row_ptr, const int32_t * col,
+		const double * val, const void * b_host, void * x_host, long max_iterations, double * history_host,
+		spmv_mi355x_solver_info * info)
+{
+	const auto t_start = std::chrono::steady_clock::now();
+	const long m = spmv_mi355x_rows(A);
+	const long ld = k;
+	hipStream_t stream = nullptr;
+	DeviceBuffers buf;
+	const size_t vb = (size_t) m * k * sizeof(T);
+
+	std::vector<T> K_host((size_t) std::max<long>(m, 1));
+	const long bad = jacobi_diagonal<T>(row_ptr, col, val, m, 0, K_host.data());
+	if (bad >= 0)
+	{
+		set_error("%s: bad K, zero in diagonal (row %ld)", what, bad);
+		return 1;
+	}
+
+	T * b, * K, * x, * x_best, * r, * r_explicit, * p, * Ap;
+	T * r0 = nullptr, * y = nullptr, * z = nullptr, * s = nullptr, * v = nullptr;
+	for (T ** q : {&b, &x, &x_best, &r, &r_explicit, &p, &Ap})
+		ABI_TRY(buf.alloc(q, vb));
+	ABI_TRY(buf.alloc(&K, (size_t) m * sizeof(T)));
+	if (method == 1)
+		for (T ** q : {&r0, &y, &z, &s, &v})
+			ABI_TRY(buf.alloc(q, vb));
+	double * part, * history = nullptr;
+	SolverState * st;
+	const size_t part_bytes = sizeof(double) * (size_t) k * NUM_SLOTS * MAX_PART;
+	ABI_TRY(buf.alloc(&part, part_bytes));
+	ABI_TRY(buf.alloc(&st, 2 * (size_t) k * sizeof(SolverState)));
+	const long hist_ld = 3 * max_iterations;
+	if (history_host && max_iterations > 0)
+	{
+		ABI_TRY(buf.alloc(&history, sizeof(double) * (size_t) k * hist_ld));
+		HIP_TRY(hipMemsetAsync(history, 0, sizeof(double) * (size_t) k * hist_ld, stream));
+	}
+	HIP_TRY(hipHostMalloc(&buf.pinned, 2 * sizeof(long), hipHostMallocMapped | hipHostMallocCoherent));
+	volatile long * progress = (volatile long *) buf.pinned;          // [0] iterations finished, [1] break flag
+	progress[0] = 0;
+	progress[1] = -1;
+	long * progress_dev = nullptr;
+	HIP_TRY(hipHostGetDevicePointer((void **) &progress_dev, buf.pinned, 0));
+
+	HIP_TRY(hipMemcpyAsync(b, b_host, vb, hipMemcpyHostToDevice, stream));
+	HIP_TRY(hipMemcpyAsync(K, K_host.data(), (size_t) m * sizeof(T), hipMemcpyHostToDevice, stream));
+	HIP_TRY(hipMemsetAsync(x, 0, vb, stream));
+	HIP_TRY(hipMemsetAsync(x_best, 0, vb, stream));
+	HIP_TRY(hipMemsetAsync(part, 0, part_bytes, stream));
+
+	// the single solver's launch shape: the same rows per (block, thread), hence the same additions per column
+	const int nb = (int) std::min<long>(MAX_PART, std::max<long>(1, (m + 4 * VB - 1) / (4 * VB)));
+	const dim3 grid(nb), block(VB), per_col(k);
+	const std::vector<Chunk> chunks = column_chunks(k);
+	long spmv_calls = 0;
+	auto spmm = [&](const T * in, T * out) {
+		spmv_calls++;
+		return spmv_mi355x_spmm_device_async(A, k, in, ld, out, ld, 0, stream);
+	};
+	// |b - A x|^2 into partial A of every column, r_explicit = b - A x
+	auto explicit_residual = [&](const T * xx) {
+		if (spmm(xx, Ap))
+			return 1;
+		for_chunks(chunks, [&](int c0, auto kc) {
+			hipLaunchKernelGGL((residual_multi_kernel<T, decltype(kc)::value>), grid, block, 0, stream, b, Ap, r_explicit, m, ld, c0, part);
+		});
+		return 0;
+	};
+	auto explicit_step = [&](SolverState * cur, int allow_restart, int ignore_done) {
+		for_chunks(chunks, [&](int c0, auto kc) {
+			hipLaunchKernelGGL((explicit_multi_kernel<T, decltype(kc)::value>), grid, block, 0, stream, cur, x, x_best, r_explicit, r, p, K, m,
+					ld, c0, nb, allow_restart, ignore_done, part);
+		});
+		hipLaunchKernelGGL(explicit_fin_multi_kernel, per_col, block, 0, stream, cur, nb, allow_restart, ignore_done, part);
+	};
+
+	// r0 = b - A x0
+	ABI_TRY(spmm(x, Ap));
+	for_chunks(chunks, [&](int c0, auto kc) {
+		constexpr int KC = decltype(kc)::value;
+		hipLaunchKernelGGL((residual_multi_kernel<T, KC>), grid, block, 0, stream, b, Ap, r, m, ld, c0, part);
+		if (method == 0)
+			hipLaunchKernelGGL((cg_init_multi_kernel<T, KC>), grid, block, 0, stream, r, K, p, m, ld, c0, part);
+		else
+			hipLaunchKernelGGL((bicg_init_multi_kernel<T, KC>), grid, block, 0, stream, r, K, r0, p, y, m, ld, c0);
+	});
+	hipLaunchKernelGGL(init_state_multi_kernel, per_col, block, 0, stream, st, k, nb, method, part);
+	HIP_TRY(hipGetLastError());
+
+	const auto t_loop = std::chrono::steady_clock::now();
+	long it = 0;
+	for (; it < max_iterations; it++)
+	{
+		if (it % POLL == 0 && it >= 2 * POLL)
+		{
+			// the single solver's rule: stay at most 2*POLL iterations ahead, stop once what the device had posted by
+			// iteration it - POLL says that every column has broken
+			const auto t_wait = std::chrono::steady_clock::now();
+			long spins = 0;
+			while (progress[0] < it - POLL)
+			{
+				if ((++spins & 0xfff) == 0)
+				{
+					HIP_TRY(hipGetLastError());
+					if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t_wait).count() > 120.0)
+					{
+						set_error("%s: the device made no progress for 120 s at iteration %ld", what, it);
+						(void) hipStreamSynchronize(stream);
+						return 1;
+					}
+				}
+				__builtin_ia32_pause();
+			}
+			const long broke_at = progress[1];
+			if (broke_at >= 0 && broke_at <= it - POLL)
+				break;
+		}
+		SolverState * cur = st + (it & 1) * k, * nxt = st + ((it + 1) & 1) * k;
+		if (it > 0 && it % RESTART_K == 0)
+		{
+			ABI_TRY(explicit_residual(x));
+			explicit_step(cur, method == 0, 0);
+		}
+		if (method == 0)
+		{
+			ABI_TRY(spmm(p, Ap));
+			for_chunks(chunks, [&](int c0, auto kc) {
+				hipLaunchKernelGGL((cg_dot_multi_kernel<T, decltype(kc)::value>), grid, block, 0, stream, cur, p, Ap, m, ld, c0, history,
+						hist_ld, it, part);
+			});
+			for_chunks(chunks, [&](int c0, auto kc) {
+				hipLaunchKernelGGL((cg_update_multi_kernel<T, decltype(kc)::value>), grid, block, 0, stream, cur, x, r, p, Ap, K, m, ld, c0,
+						nb, part);
+			});
+			for_chunks(chunks, [&](int c0, auto kc) {
+				hipLaunchKernelGGL((cg_direction_multi_kernel<T, decltype(kc)::value>), grid, block, 0, stream, cur, nxt, r, p, K, m, ld, c0,
+						k, nb, part, it, progress_dev);
+			});
+		}
+		else
+		{
+			ABI_TRY(spmm(y, v));
+			for_chunks(chunks, [&](int c0, auto kc) {
+				constexpr int KC = decltype(kc)::value;
+				hipLaunchKernelGGL((bicg_dot_multi_kernel<T, KC>), grid, block, 0, stream, cur, r0, v, m, ld, c0, history, hist_ld, it, part);
+				hipLaunchKernelGGL((bicg_s_multi_kernel<T, KC>), grid, block, 0, stream, cur, r, v, K, s, z, m, ld, c0, nb, part);
+			});
+			ABI_TRY(spmm(z, Ap));                                // t = A z
+			for_chunks(chunks, [&](int c0, auto kc) {
+				constexpr int KC = decltype(kc)::value;
+				hipLaunchKernelGGL((bicg_omega_multi_kernel<T, KC>), grid, block, 0, stream, Ap, s, K, m, ld, c0, part);
+				hipLaunchKernelGGL((bicg_update_multi_kernel<T, KC>), grid, block, 0, stream, cur, s, Ap, y, z, r0, r, x, m, ld, c0, nb, part);
+			});
+			for_chunks(chunks, [&](int c0, auto kc) {
+				hipLaunchKernelGGL((bicg_direction_multi_kernel<T, decltype(kc)::value>), grid, block, 0, stream, cur, nxt, r, v, K, p, y, m,
+						ld, c0, k, nb, part, it, progress_dev);
+			});
+		}
+	}
+	HIP_TRY(hipGetLastError());
+	const auto t_loop_end = std::chrono::steady_clock::now();
+	if (getenv("SPMV_MI355X_SOLVER_DEBUG"))
+		fprintf(stderr, "[solver multi] k %d, setup %.3f ms, enqueue loop %.3f ms, %ld iterations launched\n", k,
+				std::chrono::duration<double>(t_loop - t_start).count() * 1e3,
+				std::chrono::duration<double>(t_loop_end - t_loop).count() * 1e3, it);
+
+	// final explicit residual of x and promotion of x_best, then error = |b - A x_best| (as the single solver)
+	SolverState * fin = st + (it & 1) * k;
+	ABI_TRY(explicit_residual(x));
+	explicit_step(fin, 0, 1);
+	ABI_TRY(explicit_residual(x_best));
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(x_host, x_best, vb, hipMemcpyDeviceToHost, stream));
+	std::vector<SolverState> st_host((size_t) k);
+	std::vector<double> part_host((size_t) k * NUM_SLOTS * MAX_PART);
+	HIP_TRY(hipMemcpyAsync(st_host.data(), fin, sizeof(SolverState) * k, hipMemcpyDeviceToHost, stream));
+	HIP_TRY(hipMemcpyAsync(part_host.data(), part, part_bytes, hipMemcpyDeviceToHost, stream));
+	if (history)
+		HIP_TRY(hipMemcpyAsync(history_host, history, sizeof(double) * (size_t) k * hist_ld, hipMemcpyDeviceToHost, stream));
+	HIP_TRY(hipStreamSynchronize(stream));
+	if (info)
+	{
+		// info[0].struct_size is the caller's stride; every element is written with that size
+		const unsigned want = info->struct_size;
+		const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
+		for (int c = 0; c < k; c++)
+		{
+			spmv_mi355x_solver_info out;
+			memset(&out, 0, sizeof(out));
+			double ee = 0;
+			for (int i = 0; i < nb; i++)
+				ee += part_host[part_at(c, P_A) + i];
+			const SolverState & sc = st_host[c];
+			out.iterations = sc.k;
+			out.error = std::sqrt(ee);
+			out.error_best = sc.err_best;
+			out.eps = sc.eps;
+			out.eps_counter = sc.eps_counter;
+			out.restarts = sc.restarts;
+			out.spmv_calls = spmv_calls - 1;                      // the last one is the final check, not the solver's
+			out.seconds = seconds;
+			out.struct_size = (unsigned) std::min<size_t>(want, sizeof(out));
+			memcpy((char *) info + (size_t) c * want, &out, std::min<size_t>(want, sizeof(out)));
+		}
+	}
+	return 0;
+}
+
+static int
+solve_multi_entry(const char * what, int method, spmv_mi355x_matrix * A, int k, const int32_t * row_ptr, const int32_t * col,
+		const double * val, const void * b_host, void * x_host, long max_iterations, double * history_host,
+		spmv_mi355x_solver_info * info)
+{
+	// every argument check comes before the device is touched
+	if (k < 1)
+	{
+		set_error("%s: k must be >= 1 (got %d)", what, k);
+		return 1;
+	}
+	if (info && info->struct_size < 8)
+	{
+		set_error("%s: info->struct_size not set", what);
+		return 1;
+	}
+	if (!A || !row_ptr || !b_host || !x_host)
+	{
+		set_error("%s: NULL argument", what);
+		return 1;
+	}
+	if (spmv_mi355x_rows(A) != spmv_mi355x_cols(A))
+	{
+		set_error("%s: the matrix must be square", what);
+		return 1;
+	}
+	if (max_iterations < 0)
+	{
+		set_error("%s: max_iterations < 0", what);
+		return 1;
+	}
+	if (spmv_mi355x_nnz(A) > 0 && (!col || !val))
+	{
+		set_error("%s: NULL CSR arrays", what);
+		return 1;
+	}
+	HIP_TRY(hipSetDevice(spmv_mi355x_device(A)));
+	if (spmv_mi355x_precision(A) == SPMV_MI355X_F32)
+		return solve_multi<float>(what, method, A, k, row_ptr, col, val, b_host, x_host, max_iterations, history_host, info);
+	return solve_multi<double>(what, method, A, k, row_ptr, col, val, b_host, x_host, max_iterations, history_host, info);
+}
+
+}  // namespace spmv
+
+extern "C" {
+
+int
+spmv_mi355x_pcg_multi(spmv_mi355x_matrix * A, int k, const int32_t * row_ptr, const int32_t * col_idx, const double * values_fp64,
+		const void * B_host, void * X_res_out_host, long max_iterations, double * history_out, spmv_mi355x_solver_info * info)
+{
+	return spmv::solve_multi_entry("pcg_multi", 0, A, k, row_ptr, col_idx, values_fp64, B_host, X_res_out_host, max_iterations,
+			history_out, info);
+}
+
+int
+spmv_mi355x_pbicgstab_multi(spmv_mi355x_matrix * A, int k, const int32_t * row_ptr, const int32_t * col_idx, const double * values_fp64,
+		const void * B_host, void * X_res_out_host, long max_iterations, double * history_out, spmv_mi355x_solver_info * info)
+{
+	return spmv::solve_multi_entry("pbicgstab_multi", 1, A, k, row_ptr, col_idx, values_fp64, B_host, X_res_out_host, max_iterations,
+			history_out, info);
+}
+
+}

@@ -40,6 +40,7 @@ SYMBOLS = [
     "spmv_mi355x_kernel_info", "spmv_mi355x_x_device", "spmv_mi355x_y_device", "spmv_mi355x_sell_layout", "spmv_mi355x_stored_array",
     "spmv_mi355x_merge_tiles", "spmv_mi355x_free", "spmv_mi355x_precision", "spmv_mi355x_device",
     "spmv_mi355x_pcg", "spmv_mi355x_pbicgstab", "spmv_mi355x_pcg_dist", "spmv_mi355x_pbicgstab_dist",
+    "spmv_mi355x_pcg_multi", "spmv_mi355x_pbicgstab_multi",
     "spmv_mi355x_copy_device_async",
     "spmv_mi355x_create_partitioned", "spmv_mi355x_destroy_partitioned", "spmv_mi355x_spmv_partitioned",
     "spmv_mi355x_partitioned_set_always_copy", "spmv_mi355x_time_partitioned", "spmv_mi355x_partitioned_parts",
@@ -480,6 +481,39 @@ class Matrix:
     def pbicgstab(self, row_ptr, col_idx, values, b, max_iterations, history=True):
         """preconditioned_bicgstab() of bench_bicg.cpp:149-459 with every vector resident in HBM."""
         return self._solve(lib().spmv_mi355x_pbicgstab, row_ptr, col_idx, values, b, max_iterations, history)
+
+    def _solve_multi(self, fn, row_ptr, col_idx, values, B, max_iterations, history):
+        row_ptr = np.ascontiguousarray(row_ptr, np.int32)
+        col_idx = np.ascontiguousarray(col_idx, np.int32)
+        values = np.ascontiguousarray(values, np.float64)
+        B = np.ascontiguousarray(B, self.dtype)
+        if B.ndim != 2 or B.shape[0] != self.m or B.shape[1] < 1:
+            raise ValueError(f"B must have shape ({self.m}, k) with k >= 1, got {B.shape}")
+        assert len(row_ptr) == self.m + 1
+        k = B.shape[1]
+        X = np.zeros((max(self.m, 1), k), self.dtype)
+        hist = np.zeros(k * max(max_iterations, 1) * 3, np.float64) if history else None
+        info = (SolverInfo * k)()
+        info[0].struct_size = C.sizeof(SolverInfo)
+        _check(fn(self.h, C.c_int(k), _p(row_ptr), _p(col_idx), _p(values), _p(B), _p(X), C.c_long(max_iterations),
+                  _p(hist) if history else None, info))
+        out = []
+        for j in range(k):
+            d = {f: getattr(info[j], f) for f, _ in SolverInfo._fields_ if f != "struct_size"}
+            d["x"] = X[:self.n, j].copy()
+            d["history"] = hist[j * 3 * max_iterations:(j + 1) * 3 * max_iterations].reshape(max_iterations, 3)[:d["iterations"]].copy() \
+                if history else None
+            out.append(d)
+        return out
+
+    def pcg_multi(self, row_ptr, col_idx, values, B, max_iterations, history=True):
+        """Matrix.pcg for the k columns of B (shape (rows, k)) in one solve with one SpMM per iteration
+        (spmv_mi355x_pcg_multi): a list of k dicts, element j bit-identical to pcg(B[:, j]) on a deterministic handle."""
+        return self._solve_multi(lib().spmv_mi355x_pcg_multi, row_ptr, col_idx, values, B, max_iterations, history)
+
+    def pbicgstab_multi(self, row_ptr, col_idx, values, B, max_iterations, history=True):
+        """Matrix.pbicgstab for the k columns of B (spmv_mi355x_pbicgstab_multi), as pcg_multi."""
+        return self._solve_multi(lib().spmv_mi355x_pbicgstab_multi, row_ptr, col_idx, values, B, max_iterations, history)
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h:

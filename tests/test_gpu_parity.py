@@ -6,7 +6,10 @@ Bars (BASELINE.json north_star):
   * csr_scalar and SELL with C = 64 walk a row left to right with one FMA per element -> BIT-EXACT vs the reference
     CPU kernel (csr.cpp:334-350) in fp64 and fp32;
   * the reordering kernels (csr_vector, csr_merge, coo, SELL C<64): |y - y_ref| <= tol * sum_j |a_ij x_j| with
-    tol = 1e-12 (fp64) / 1e-5 (fp32), and <= tol relative to |y_ref| on rows without cancellation.
+    tol = 1e-12 (fp64) / 1e-5 (fp32), and <= tol relative to |y_ref| on rows without cancellation;
+  * the device call (check_device_call: every variant, both precisions): y = A x as above and bit-identical to the host-buffer path;
+    y += A x is y0 + y_ref bit for bit for the row-sequential kernels, <= tol * (sum_j |a_ij x_j| + |y0|) otherwise, rows without
+    entries keep y0 exactly; nothing outside y[0 .. rows()) is written, whatever the element offsets of x and y.
 """
 import numpy as np
 import pytest
@@ -102,6 +105,107 @@ def check(y, y_ref, absrow, dtype, exact, what):
         assert rel.max() <= tol, f"{what}: max relative error {rel.max()}"
 
 
+# ---- the device call (spmv_mi355x_spmv_device_async) as the solvers and the multi-GPU paths use it: y = A x and y += A x into exactly
+# rows() values of a y that sits at any element offset of a buffer, with neighbours right in front of and behind it --------------------
+
+SENTINEL = -7.25                                 # what the guards around y (and the slack in front of x) hold
+OFFSETS = (0, 1, 3)                              # element offsets: 1 and 3 leave a pointer aligned to its element size only
+ATOMIC_LAYOUTS = ("COOB", "MERGEB", "SELLWS")    # LDS / global atomics: the order of a row's additions changes from run to run
+
+
+def device_layout(variant_index):
+    """(ox, g0, g1, side_beta): x starts ox elements into its buffer, y has g0 guard values in front and g1 >= 1 behind, and the call
+    with beta == side_beta runs on a stream of its own. Nine consecutive indices hold every (ox, g0) pair."""
+    i = int(variant_index)
+    return OFFSETS[i % 3], OFFSETS[(i // 3) % 3], 1 + (i // 9) % 3, i % 2
+
+
+def compare_device_result(y_buffer, y0, y_ref, absrow, g0, m, dtype, exact, what=""):
+    """The comparison half of check_device_call, a plain function of host arrays. y_buffer = [g0 guards | m values | guards] as the
+    device left it; y0 = None for y = A x, else what y held before y += A x; y_ref = the oracle's product in the handle's precision;
+    absrow = sum_j |a_ij x_j| in fp64.
+      * the guards still hold SENTINEL;
+      * beta = 0: what check() asks;
+      * beta = 1, exact: y == y0 + y_ref evaluated in the handle's precision (the row sum is the oracle's, the addition rounds once);
+        otherwise |y - (y0 + y_ref)| <= tol * (absrow + |y0|), additions in fp64 — the extra rounding of y0 + s is at most
+        eps/2 * (|y0| + absrow), and eps/2 << tol in both precisions;
+      * beta = 1, rows whose products are all zero (absrow == 0: empty rows among them) keep y0 exactly: y0 + 0 is exact."""
+    y_buffer = np.asarray(y_buffer)
+    assert y_buffer.dtype == np.dtype(dtype) and y_buffer.ndim == 1 and y_buffer.shape[0] > g0 + m, what
+    front, y, back = y_buffer[:g0], y_buffer[g0:g0 + m], y_buffer[g0 + m:]
+    for name, guard, first in (("in front of y", front, -g0), ("behind y", back, m)):
+        bad = np.nonzero(guard != dtype(SENTINEL))[0]
+        assert bad.size == 0, f"{what}: guard {name} overwritten at row {first + bad[0]} (y starts at row 0, rows() = {m}): {guard[bad[0]]!r}"
+    if y0 is None:
+        check(y, y_ref, absrow, dtype, exact, what)
+        return
+    y0 = np.asarray(y0)
+    assert y0.dtype == np.dtype(dtype) and y0.shape == y.shape == y_ref.shape == absrow.shape, what
+    bad = np.nonzero(~np.isfinite(y))[0]
+    assert bad.size == 0, f"{what}: row {bad[:5]} not finite"
+    still = absrow == 0
+    bad = np.nonzero(still & (y != y0))[0]
+    assert bad.size == 0, f"{what}: {bad.size} rows without entries do not keep y0; row {bad[:5]}: y {y[bad[:5]]!r} y0 {y0[bad[:5]]!r}"
+    if exact:
+        want = y0 + y_ref.astype(dtype)                           # one rounding, in the handle's precision
+        bad = np.nonzero(y != want)[0]
+        assert bad.size == 0, f"{what}: {bad.size} rows differ from y0 + y_ref; row {bad[:5]}: y {y[bad[:5]]!r} want {want[bad[:5]]!r}"
+        return
+    tol = TOL[dtype]
+    want = y0.astype(np.float64) + y_ref.astype(np.float64)
+    err = np.abs(y.astype(np.float64) - want)
+    bound = tol * (absrow + np.abs(y0.astype(np.float64)))
+    bad = np.nonzero(err > bound)[0]
+    assert bad.size == 0, (f"{what}: {bad.size} rows beyond {tol}*(sum|a x| + |y0|); row {bad[:5]} err {err[bad[:5]]} "
+                           f"y {y[bad[:5]]!r} y0 {y0[bad[:5]]!r} y_ref {y_ref[bad[:5]]!r}")
+
+
+def check_device_call(A, x, y_ref, absrow, dtype, exact, what, variant_index, y_host=None):
+    """spmv_device on a built handle with x and y placed as device_layout(variant_index) says: beta = 0 twice (the second launch tells
+    whether the handle is deterministic), beta = 1 on a y0 that dominates most rows, beta = 1 on y0 = 0. Every expectation comes
+    from the oracle (y_ref, absrow); the engine is compared with itself only where bit-identity is the contract: the host path
+    (y_host = A.spmv(x)) and 0 + A x against the beta = 0 launch, on deterministic handles."""
+    import torch
+    m, n = A.m, A.n
+    assert y_ref.shape == (m,) and absrow.shape == (m,), what
+    ox, g0, g1, side_beta = device_layout(variant_index)
+    tdt = torch.float64 if np.dtype(dtype) == np.float64 else torch.float32
+    item = np.dtype(dtype).itemsize
+    xbuf = torch.full((ox + n,), SENTINEL, dtype=tdt, device="cuda")
+    xbuf[ox:] = torch.from_numpy(np.ascontiguousarray(x, dtype)).cuda()
+    xkeep = xbuf.clone()
+    side = torch.cuda.Stream()
+    y0 = (np.random.default_rng(1000 + variant_index).uniform(-1, 1, m) * 8).astype(dtype)
+
+    def launch(beta, y_init, tag):
+        ybuf = torch.full((g0 + m + g1,), SENTINEL, dtype=tdt, device="cuda")
+        if y_init is not None:
+            ybuf[g0:g0 + m] = torch.from_numpy(y_init).cuda()
+        torch.cuda.synchronize()                                  # the buffers were filled on the current stream
+        stream = side if beta == side_beta else torch.cuda.current_stream()
+        A.spmv_device(xbuf.data_ptr() + ox * item, ybuf.data_ptr() + g0 * item, beta, stream.cuda_stream)
+        stream.synchronize()
+        assert torch.equal(xbuf, xkeep), f"{what} {tag}: x changed"
+        out = ybuf.cpu().numpy()
+        compare_device_result(out, y_init if beta else None, y_ref, absrow, g0, m, dtype, exact,
+                              f"{what} device call {tag} ox={ox} g0={g0} g1={g1} side={beta == side_beta}")
+        return out[g0:g0 + m]
+
+    yb0 = launch(0, None, "beta=0")
+    again = launch(0, None, "beta=0 again")
+    det = np.array_equal(yb0, again)
+    if any(t in A.format_name for t in ATOMIC_LAYOUTS):
+        det = False                                               # two launches may agree by chance
+    else:
+        assert det, f"{what}: two launches of {A.format_name} differ, and the layout uses no atomics"
+    if det and y_host is not None:
+        np.testing.assert_array_equal(yb0, y_host, err_msg=f"{what}: device path vs host path")
+    launch(1, y0, "beta=1")
+    yz = launch(1, np.zeros(m, dtype), "beta=1 y0=0")
+    if det:
+        np.testing.assert_array_equal(yz, yb0, err_msg=f"{what}: 0 + A x vs A x")
+
+
 @pytest.mark.parametrize("variant", VARIANTS, ids=IDS)
 @pytest.mark.parametrize("case", CASES)
 def test_golden_cases(eng, oracle, case, variant):
@@ -119,6 +223,9 @@ def test_golden_cases(eng, oracle, case, variant):
             # golden vector from the genuine reference CPU kernel, and the oracle's restatement of it
             check(y, g[f"y_csr_{pk}_{xn}"], ar, dtype, exact, f"{case}/{fmt}{opts}/{pk}/{xn} vs golden")
             check(y, oracle.csr_spmv(rp, ci, a, x, dtype), ar, dtype, exact, f"{case}/{fmt}{opts}/{pk}/{xn} vs oracle")
+        # x_rand through the device call (y is the host path's result for it); the placement of x and y moves on from case to case
+        check_device_call(A, x, oracle.csr_spmv(rp, ci, a, x, dtype), absrow, dtype, exact, f"{case}/{fmt}{opts}/{pk}",
+                          VARIANTS.index(variant) + CASES.index(case), y_host=y)
         A.close()
 
 
@@ -169,7 +276,7 @@ def test_synthetic_all_formats(eng, oracle, kind, m, n):
     for dtype in (np.float64, np.float32):
         y_ref = oracle.csr_spmv(rp, ci, a, x, dtype, num_threads=4)
         absrow = oracle.csr_spmv(rp, ci, np.abs(a), np.abs(x))
-        for fmt, opts, exact in VARIANTS:
+        for vi, (fmt, opts, exact) in enumerate(VARIANTS):
             try:
                 A = eng.Matrix(rp, ci, a, m, n, fmt, dtype, **opts)
             except eng.SpmvError as e:
@@ -181,6 +288,9 @@ def test_synthetic_all_formats(eng, oracle, kind, m, n):
             # x changes between calls (CG/BiCG callers): always_copy path must pick the new vector up
             y2 = A.spmv(2 * x)
             check(y2, (2 * y_ref).astype(dtype), 2 * absrow, dtype, exact, f"{kind}/{fmt}{opts} second x")
+            # the device call, both betas, guarded y; fp32 and the later shapes shift the placement of x and y
+            check_device_call(A, x, y_ref, absrow, dtype, exact, f"{kind}/{fmt}{opts}/{np.dtype(dtype).name}",
+                              vi + SYNTH.index((kind, m, n)) + (0 if dtype == np.float64 else 4), y_host=y)
             A.close()
 
 
@@ -240,6 +350,7 @@ def test_blocked_layout_with_several_passes_and_split_rows(eng, oracle, fmt, mon
     cases = [(g["row_ptr"], g["col_idx"], g["values"], len(g["row_ptr"]) - 1, len(g["x_rand"])) for g in cases]
     rp, ci, a = synth(rng, 70000, 70000, "powerlaw")
     cases.append((rp, ci, a, 70000, 70000))
+    handles = 0
     for rp, ci, a, m, n in cases:
         x = rng.uniform(-1, 1, n)
         absrow = oracle.csr_spmv(rp, ci, np.abs(a), np.abs(x))
@@ -251,6 +362,9 @@ def test_blocked_layout_with_several_passes_and_split_rows(eng, oracle, fmt, mon
                 if m >= 70000:
                     assert "_split" in A.format_name and int(A.format_name.split("_r")[1].split("_")[0]) > 8
                 check(A.spmv(x), y_ref, absrow, dtype, False, f"{A.format_name} m={m}")
+                # y += A x with rows recombined by the carry fix-up and rows spread over several passes
+                check_device_call(A, x, y_ref, absrow, dtype, False, f"{A.format_name} m={m}", handles)
+                handles += 1
                 A.close()
 
 
@@ -348,6 +462,84 @@ def test_beta_accumulate_and_row_blocks(eng, oracle):
             rem.close()
         y = np.concatenate(y_all)
         check(y, y_ref, absrow, np.float64, False, f"rowblocks/{fmt}")
+
+
+def test_device_call_on_handles_outside_the_variant_list(eng, oracle):
+    """check_device_call (both betas, guarded y, odd offsets) for what VARIANTS does not hold: the Kahan kernel, csr_stream's LDS-DMA
+    mode, the delta layout with 7-byte values, a handle converted from a CSR streamed in pieces — and the multi-GPU pair of a row
+    block (col_filter_mode 1 and 2) run as that code runs it: `loc` with beta 0, then `rem` with beta 1 into the same y, which lies
+    between guards at an odd offset; against the oracle's product of the undivided matrix, six formats, fp64 and fp32, with empty
+    rows (`short`) and rows of 40 000 entries (`powerlaw`)."""
+    import torch
+    import spmv_host as H
+    rng = np.random.default_rng(31)
+    m = n = 20000
+    rp, ci, a = synth(rng, m, n, "short")
+    x = rng.uniform(-1, 1, n)
+    absrow = oracle.csr_spmv(rp, ci, np.abs(a), np.abs(x))
+    A = eng.Matrix(rp, ci, a, m, n, "csr_scalar", np.float64, kahan=1)
+    assert A.format_name == "MI355X_CSR_SCALAR_KAHAN_d"
+    check_device_call(A, x, oracle.csr_kahan_spmv(rp, ci, a, x), absrow, np.float64, True, A.format_name, 4, y_host=A.spmv(x))
+    A.close()
+    for i, dtype in enumerate((np.float64, np.float32)):
+        A = eng.Matrix(rp, ci, a, m, n, "csr_stream", dtype, stream_mode=3)
+        assert A.format_name.startswith("MI355X_CSR_STREAMD_") and A.kernel_info()["name"] == "csr_stream_d_kernel", A.format_name
+        check_device_call(A, x, oracle.csr_spmv(rp, ci, a, x, dtype), absrow, dtype, False, f"{A.format_name} stream_mode=3", 7 + i,
+                          y_host=A.spmv(x))
+        A.close()
+    # the delta layout, one wave per slice (bit-exact): 7-byte values on a matrix whose values qualify, and the streamed CSR
+    K = H.gen_kkt(12)
+    krp, kci, ka, km, kn = K["row_ptr"], K["col_idx"], K["values"], K["m"], K["n"]
+    kx = rng.uniform(-1, 1, kn)
+    kabs = oracle.csr_spmv(krp, kci, np.abs(ka), np.abs(kx))
+    V = eng.Matrix(krp, kci, ka, km, kn, "sell_c_sigma", np.float64, sell_c=64, sell_split=1, sell_values=1, sell_window=2)
+    assert V.format_name.endswith("_v7") and "SELLD" in V.format_name and "_w" not in V.format_name, V.format_name
+    check_device_call(V, kx, oracle.csr_spmv(krp, kci, ka, kx), kabs, np.float64, True, V.format_name, 2, y_host=V.spmv(kx))
+    V.close()
+    for i, dtype in enumerate((np.float64, np.float32)):
+        st = eng.CsrStream(km, kn, int(krp[km]))
+        for r0, r1 in ((0, km // 3), (km // 3, km // 3 + 1), (km // 3 + 1, km)):
+            st.append(krp[r0:r1 + 1] - krp[r0], kci[krp[r0]:krp[r1]], ka[krp[r0]:krp[r1]])
+        S = st.finish("sell_c_sigma", dtype, sell_split=1)
+        assert "SELLD" in S.format_name
+        exact = "_w" not in S.format_name                         # one wave per slice walks a row left to right
+        check_device_call(S, kx, oracle.csr_spmv(krp, kci, ka, kx, dtype), kabs, dtype, exact, f"{S.format_name} from a stream", 5 + 3 * i,
+                          y_host=S.spmv(kx))
+        S.close()
+    # ---- loc (beta 0) then rem (beta 1) of a row block into one guarded y
+    pair = 0
+    side = torch.cuda.Stream()
+    for kind in ("short", "powerlaw"):
+        rp, ci, a = synth(rng, m, n, kind)
+        x = rng.uniform(-1, 1, n)
+        absrow = oracle.csr_spmv(rp, ci, np.abs(a), np.abs(x))
+        for dtype in (np.float64, np.float32):
+            tdt = torch.float64 if dtype == np.float64 else torch.float32
+            item = np.dtype(dtype).itemsize
+            y_ref = oracle.csr_spmv(rp, ci, a, x, dtype)
+            for fmt in ("csr_scalar", "csr_vector", "csr_stream", "csr_merge", "sell_c_sigma", "coo"):
+                parts = 3
+                for p in range(parts):
+                    r0, r1 = oracle.partition_prefix_sums(parts, p, rp, m, int(rp[m]))
+                    ox, g0, g1, on_side = device_layout(pair)
+                    pair += 1
+                    loc = eng.Matrix(rp, ci, a, m, n, fmt, dtype, row_begin=r0, row_end=r1, col_begin=r0, col_end=r1, col_filter_mode=1)
+                    rem = eng.Matrix(rp, ci, a, m, n, fmt, dtype, row_begin=r0, row_end=r1, col_begin=r0, col_end=r1, col_filter_mode=2)
+                    assert loc.m == rem.m == r1 - r0 and loc.nnz + rem.nnz == int(rp[r1] - rp[r0])
+                    xbuf = torch.full((ox + n,), SENTINEL, dtype=tdt, device="cuda")
+                    xbuf[ox:] = torch.from_numpy(x.astype(dtype)).cuda()
+                    xkeep = xbuf.clone()
+                    ybuf = torch.full((g0 + r1 - r0 + g1,), SENTINEL, dtype=tdt, device="cuda")
+                    torch.cuda.synchronize()
+                    stream = side if on_side else torch.cuda.current_stream()
+                    loc.spmv_device(xbuf.data_ptr() + ox * item, ybuf.data_ptr() + g0 * item, 0, stream.cuda_stream)
+                    rem.spmv_device(xbuf.data_ptr() + ox * item, ybuf.data_ptr() + g0 * item, 1, stream.cuda_stream)
+                    stream.synchronize()
+                    what = f"{kind}/{fmt}/{np.dtype(dtype).name} rows [{r0}, {r1}) loc {loc.format_name} + rem {rem.format_name} ox={ox} g0={g0} g1={g1}"
+                    assert torch.equal(xbuf, xkeep), f"{what}: x changed"
+                    compare_device_result(ybuf.cpu().numpy(), None, y_ref[r0:r1], absrow[r0:r1], g0, r1 - r0, dtype, False, what)
+                    loc.close()
+                    rem.close()
 
 
 def test_formats_report_footprint(eng):

@@ -10,12 +10,12 @@ import pytest
 import oracle
 import spmv_host as H
 from conftest import load_case
+from test_gpu_parity import SENTINEL, compare_device_result
 
 pytestmark = pytest.mark.gpu
 
 KS = (1, 2, 3, 4, 5, 7, 8, 9, 16)
 KMAX = max(KS)
-SENTINEL = -7.25
 
 
 @pytest.fixture(scope="module")
@@ -82,36 +82,46 @@ def _values(rng, m, w):
 
 class Columns:
     """X (n x KMAX) and Y0 (m x KMAX) on the device, and the single-vector products of every column: ref0[:, j] = A x_j,
-    ref1[:, j] = y0_j + A x_j as spmv_device(beta = 1) computes it."""
+    ref1[:, j] = y0_j + A x_j as spmv_device(beta = 1) computes it. The bit-identity contract of spmm is stated against these, so they
+    come from the handle under test — and are themselves held to the oracle's product of `csr` = (row_ptr, col_idx, values), with
+    the bound of test_gpu_parity.compare_device_result, before anything is compared with them."""
 
-    def __init__(self, torch, M, X, Y0):
+    def __init__(self, torch, M, X, Y0, csr):
         self.X, self.Y0 = X, Y0
         self.ref0 = torch.empty_like(Y0)
         self.ref1 = torch.empty_like(Y0)
         self.det = True
+        rp, ci, a = csr
+        dtype = M.dtype.type
         for j in range(X.shape[1]):
             x = X[:, j].contiguous()
-            y = torch.empty(M.m + 64, dtype=X.dtype, device="cuda")
+            y = torch.full((M.m + 64,), SENTINEL, dtype=X.dtype, device="cuda")
             M.spmv_device(x.data_ptr(), y.data_ptr(), 0)
             y2 = torch.empty_like(y)
             M.spmv_device(x.data_ptr(), y2.data_ptr(), 0)
             torch.cuda.synchronize()
             self.det = self.det and bool(torch.equal(y[:M.m], y2[:M.m]))
             self.ref0[:, j] = y[:M.m]
-            y1 = torch.empty_like(y)
+            y1 = torch.full_like(y, SENTINEL)
             y1[:M.m] = Y0[:, j]
             M.spmv_device(x.data_ptr(), y1.data_ptr(), 1)
             torch.cuda.synchronize()
             self.ref1[:, j] = y1[:M.m]
+            xj = x.cpu().numpy()
+            y_ref = oracle.csr_spmv(rp, ci, a, xj, dtype)
+            absrow = oracle.csr_spmv(rp, ci, np.abs(a), np.abs(xj).astype(np.float64))
+            what = f"{M.format_name} single-vector product of column {j}"
+            compare_device_result(y.cpu().numpy(), None, y_ref, absrow, 0, M.m, dtype, False, what + ", beta = 0")
+            compare_device_result(y1.cpu().numpy(), Y0[:, j].cpu().numpy(), y_ref, absrow, 0, M.m, dtype, False, what + ", beta = 1")
 
 
-def _make_columns(torch, M, seed):
+def _make_columns(torch, M, seed, csr):
     g = torch.Generator(device="cuda")
     g.manual_seed(seed)
     dt = _tdtype(torch, M.dtype)
     X = (torch.rand((M.n, KMAX), generator=g, device="cuda", dtype=torch.float64) * 2 - 1).to(dt)
     Y0 = (torch.rand((M.m, KMAX), generator=g, device="cuda", dtype=torch.float64) * 2 - 1).to(dt)
-    return Columns(torch, M, X, Y0)
+    return Columns(torch, M, X, Y0, csr)
 
 
 def _spmm(torch, M, cols, k, beta):
@@ -128,8 +138,8 @@ def _assert_exact(torch, got, want, what):
         raise AssertionError(f"{what}: not bit-identical, {int((got != want).sum())} entries differ, max |d| {float(d.max())}")
 
 
-def _check_delta_handle(torch, M, seed, what, ks=KS):
-    cols = _make_columns(torch, M, seed)
+def _check_delta_handle(torch, M, seed, what, csr, ks=KS):
+    cols = _make_columns(torch, M, seed, csr)
     assert cols.det, what
     for k in ks:
         for beta in (0, 1):
@@ -158,7 +168,7 @@ def test_sell_delta_bit_identical_per_column(eng, torch, modes_off, store, split
                                sell_window=2, sell_values=sell_values, convert_on=conv)
                 if name == "f64_v7" and w >= 4:
                     assert M.format_name.endswith("_v7"), M.format_name
-                _check_delta_handle(torch, M, w * 10 + off, f"{name} split={split} w={w} modes_off={off} convert_on={conv}")
+                _check_delta_handle(torch, M, w * 10 + off, f"{name} split={split} w={w} modes_off={off} convert_on={conv}", (rp, ci, a))
                 M.close()
 
 
@@ -171,7 +181,7 @@ def test_sell_delta_from_stream(eng, torch):
         for r0, r1 in ((0, m // 3), (m // 3, m // 3 + 1), (m // 3 + 1, m)):
             st.append(rp[r0:r1 + 1] - rp[r0], ci[rp[r0]:rp[r1]], va[rp[r0]:rp[r1]])
         S = st.finish("sell_c_sigma", dtype)
-        _check_delta_handle(torch, S, 3, f"create_from_stream {np.dtype(dtype).name}", ks=(1, 2, 4, 7, 8, 16))
+        _check_delta_handle(torch, S, 3, f"create_from_stream {np.dtype(dtype).name}", (rp, ci, va), ks=(1, 2, 4, 7, 8, 16))
         S.close()
 
 
@@ -184,7 +194,7 @@ def test_strides_and_sentinels(eng, torch, dtype, fmt, opts, beta1_exact):
     A = H.gen_named("cant", 0.1)
     rp, ci, va, m, n = A["row_ptr"], A["col_idx"], A["values"], A["m"], A["n"]
     M = eng.Matrix(rp, ci, va, m, n, fmt, dtype, **opts)
-    cols = _make_columns(torch, M, 5)
+    cols = _make_columns(torch, M, 5, (rp, ci, va))
     dt = cols.X.dtype
     tol = 1e-10 if dt == torch.float64 else 1e-4
     sent = torch.full((1,), SENTINEL, dtype=dt, device="cuda")
@@ -241,7 +251,7 @@ def test_every_other_layout_per_column(eng, torch, dtype, fmt, opts, beta1_exact
     A = H.gen_named("cant", 0.1)
     rp, ci, va, m, n = A["row_ptr"], A["col_idx"], A["values"], A["m"], A["n"]
     M = eng.Matrix(rp, ci, va, m, n, fmt, dtype, **opts)
-    cols = _make_columns(torch, M, 9)
+    cols = _make_columns(torch, M, 9, (rp, ci, va))
     tol = 1e-10 if np.dtype(dtype) == np.float64 else 1e-4
     for k in (1, 3, 8):
         for beta in (0, 1):
@@ -263,7 +273,12 @@ def test_symmetric_window_layout_per_column(eng, torch):
     lens = np.array([np.count_nonzero(ci[rp[i]:rp[i + 1]] <= i) for i in range(m)])
     trp = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
     M = eng.Matrix(trp, ci[keep], va[keep], m, m, "sell_c_sigma", np.float64, symmetric_input=1, sell_window=1)
-    cols = _make_columns(torch, M, 2)
+    # what the handle multiplies by: the expansion T + T^t - diag T of the stored triangle
+    import scipy.sparse as sp
+    T = sp.csr_matrix((va[keep], ci[keep], trp), shape=(m, m))
+    E = (T + sp.tril(T, -1).T).tocsr()
+    E.sort_indices()
+    cols = _make_columns(torch, M, 2, (E.indptr.astype(np.int32), E.indices.astype(np.int32), E.data.astype(np.float64)))
     for k in (1, 4, 5):
         for beta in (0, 1):
             Y = _spmm(torch, M, cols, k, beta)

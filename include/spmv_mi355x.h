@@ -177,13 +177,21 @@ int  spmv_mi355x_time_device(spmv_mi355x_matrix * A, const void * x_dev, void * 
  * Y: rows() rows, row i at Y_dev + i*ldy (ldy >= k). Only Y[i*ldy + j], i < rows(), j < k is written.
  * Column j of Y is bit-identical to spmv_mi355x_spmv_device_async(A, x_j, y_j, beta, ...) on the contiguous column x_j
  * whenever that product is deterministic (every layout without LDS / global atomics).
- * The SELL-C-sigma delta layout (not the LDS-window or symmetric ones) reads the matrix once per PASS of up to 8 columns: k runs as
- * passes of 8 columns, then the binary remainder (k = 7: 4 + 2 + 1, k = 16: 8 + 8); k == 1 with ldx == ldy == 1 is the single-vector
- * kernel itself. Every other layout runs the single-vector product once per column, through a column of scratch the handle owns
- * (allocated at its first such call), so one handle serves one spmm at a time.
+ * The SELL-C-sigma delta layout reads the matrix once per PASS of up to 8 columns: k runs as passes of the largest power of two
+ * <= min(8, columns left) (k = 7: 4 + 2 + 1, k = 16: 8 + 8). The SELL-C-sigma LDS-window layout (MI355X_SELLW_*, not its
+ * symmetric-storage form) does the same with Kmax in place of 8: a pass of K columns keeps the slice group's window of X in LDS,
+ *     need(K) = align16((wmax + 1) * K * sizeof(value)) + (waves per slice > 1 ? threads per workgroup * K * sizeof(value) : 0)
+ * bytes (wmax = the widest window of the handle's groups), and Kmax is the largest K in {8, 4, 2, 1} with need(K) <= 163 840, the
+ * LDS one workgroup may declare (Kmax = 2: k = 5 runs as 2 + 2 + 1). Its kernel reads strided X and writes strided Y itself, also
+ * when Kmax = 1. On both layouts k == 1 with ldx == ldy == 1 is the single-vector kernel itself. Every other layout runs the
+ * single-vector product once per column, through a column of scratch the handle owns (allocated at its first such call), so one
+ * handle serves one spmm at a time. spmv_mi355x_spmm_plan tells which of these a handle does.
  * rc 1 without touching memory for k < 1, ldx < k, ldy < k, a NULL handle, or a NULL X / Y where columns / rows exist. */
 int  spmv_mi355x_spmm_device_async(spmv_mi355x_matrix * A, int k, const void * X_dev, long ldx, void * Y_dev, long ldy,
 		int beta, void * hip_stream);
+/* How spmm_device_async serves k columns on this handle: times the matrix arrays are streamed, and the most columns one pass serves
+ * (1 = one column per pass). Host-only: touches no device. rc 1 for a NULL handle, k < 1 or a NULL out pointer. */
+int  spmv_mi355x_spmm_plan(const spmv_mi355x_matrix * A, int k, int * matrix_passes_out, int * max_cols_per_pass_out);
 /* HIP-event timing of `iters` back-to-back spmm launches (beta 0), like spmv_mi355x_time_device */
 int  spmv_mi355x_time_spmm_device(spmv_mi355x_matrix * A, int k, const void * X_dev, long ldx, void * Y_dev, long ldy,
 		int iters, void * hip_stream, double * ms_per_iter_out);

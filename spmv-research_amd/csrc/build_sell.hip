@@ -490,6 +490,7 @@ build_sell_window(spmv_mi355x_matrix * A, const int * rp, const int * ci, const 
 		A->sellw_ns = NS;
 		A->sell_split = S;
 		A->sellw_lds = (int) (((long) (max_w + 1) * A->vbytes + 15) / 16 * 16);
+		A->sellw_wmax = max_w;
 		std::vector<int64_t> gp((size_t) num_groups + 1, 0);
 		for (long g = 0; g < num_groups; g++)
 			gp[(size_t) g + 1] = sdesc[2 * (size_t) std::min<long>(num_slices, (g + 1) * NS)];
@@ -593,6 +594,7 @@ build_sell_window(spmv_mi355x_matrix * A, const int * rp, const int * ci, const 
 	A->sellw_ns = NS;
 	A->sell_split = S;
 	A->sellw_lds = (int) (((long) (max_w + 1) * A->vbytes + 15) / 16 * 16);
+	A->sellw_wmax = max_w;
 	{
 		// XCD map over the groups, balanced by their stored entries
 		std::vector<int64_t> gp((size_t) num_groups + 1, 0);

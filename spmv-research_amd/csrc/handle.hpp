@@ -68,6 +68,7 @@ struct spmv_mi355x_matrix {
 	bool sell_sym = false;                 // the window layout holds ONE TRIANGLE of a symmetric matrix (sell_window_sym_kernel)
 	int * d_sellw_grp = nullptr;           // [groups][4]: window start, width, first slice, slices
 	int sellw_groups = 0, sellw_ns = 0, sellw_lds = 0;
+	int sellw_wmax = 0;                    // the widest window of a group, in columns (spmm: LDS of a pass of K columns)
 	long sell_mode_slices[4] = {0, 0, 0, 0};  // slices stored with 8-bit / 16-bit / 32-bit indices / lane offsets (modes 0, 3, 5; sell_mode_bucket)
 	long sell_v7_slices = 0;               // slices whose values are stored in 7 bytes (sell_values; sell_delta_layout.hpp)
 	int64_t sell_val_words = 0;            // stored value array in elements of the handle's precision (= sell_nnz_ext without 7-byte slices)

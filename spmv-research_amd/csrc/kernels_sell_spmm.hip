@@ -336,7 +336,7 @@ spmm_passes(int S, const SpmmArgs & a, int k, const void * X, long ldx, void * Y
 {
 	for (int j0 = 0; j0 < k;)
 	{
-		const int K = k - j0 >= 8 ? 8 : k - j0 >= 4 ? 4 : k - j0 >= 2 ? 2 : 1;
+		const int K = spmm_pass_cols(SELL_DELTA_SPMM_COLS, k - j0);
 		const void * Xp = (const T *) X + j0;
 		void * Yp = (T *) Y + j0;
 		const int rc = K == 8 ? spmm_pass<T, 8, V7>(S, a, Xp, ldx, Yp, ldy, cfg, grid, stream)

@@ -19,11 +19,9 @@
 //     element: bit-identical to the sequential CSR loop (csr.cpp:334-350), like sell_kernel<64>.
 // Reference counterparts: sell_sorted.cpp:338-419 (gather + y scatter through the permutation), sell_c_s.cpp:58-60.
 
-#include "launch.hpp"
+#include "sell_window_read.hpp"
 
 namespace spmv {
-
-typedef unsigned sellw_uint2 __attribute__((ext_vector_type(2)));
 
 // One or two index groups (4 steps each) of one lane: an 8-byte index load + 4 value loads per group, all issued before the
 // first LDS read. Values and indices are both padded to whole groups (<= 3 zero steps per slice), so every group is full.
@@ -34,32 +32,6 @@ struct SellwPair {
 	sellw_uint2 d0, d1;
 	T a[4], b[4];
 };
-
-// the 4 values of one lane in one group; vp = the group's first element + (16 / sizeof(T)) * lane
-template <typename T, bool NT>
-__device__ __forceinline__ void
-sellw_values(const T * __restrict__ vp, T (&v)[4])
-{
-	if constexpr (sizeof(T) == 8)
-	{
-		typedef T T2 __attribute__((ext_vector_type(2)));
-		const T2 w0 = ld_stream<NT>(reinterpret_cast<const T2 *>(vp));
-		const T2 w1 = ld_stream<NT>(reinterpret_cast<const T2 *>(vp + 2 * WAVE));
-		v[0] = w0.x;
-		v[1] = w0.y;
-		v[2] = w1.x;
-		v[3] = w1.y;
-	}
-	else
-	{
-		typedef T T4 __attribute__((ext_vector_type(4)));
-		const T4 w = ld_stream<NT>(reinterpret_cast<const T4 *>(vp));
-		v[0] = w.x;
-		v[1] = w.y;
-		v[2] = w.z;
-		v[3] = w.w;
-	}
-}
 
 template <typename T, bool NT>
 __device__ __forceinline__ void

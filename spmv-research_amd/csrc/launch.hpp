@@ -75,6 +75,17 @@ int launch_sell_delta(bool f32, int waves_per_slice, bool v7, const int64_t * de
 int launch_sell_delta_spmm(bool f32, int waves_per_slice, bool v7, const int64_t * desc, const unsigned char * idx, const void * val,
 		const int * row_of_sorted, int k, const void * X, long ldx, void * Y, long ldy, int m, int num_slices, const LaunchCfg & cfg,
 		hipStream_t stream, long * grid_out);
+// columns of the next pass of a multi-vector product with `remaining` columns left on a layout whose pass serves at most `cap`
+// (8, 4, 2 or 1): the largest power of two <= min(cap, remaining). Every layout's launcher and spmv_mi355x_spmm_plan walk k with it.
+inline int
+spmm_pass_cols(int cap, int remaining)
+{
+	int K = 1;
+	while (2 * K <= cap && 2 * K <= remaining)
+		K *= 2;
+	return K;
+}
+constexpr int SELL_DELTA_SPMM_COLS = 8;                                // columns one pass of launch_sell_delta_spmm serves at most
 // what every other layout's spmm runs per column j (kernels_sell_spmm.hip): x[i] = X[i * ldx] for i < n, and Y[i * ldy] = y[i]
 // (beta 0) / Y[i * ldy] + y[i] (beta 1) for i < m; X and Y point at column j
 int launch_spmm_column_gather(bool f32, const void * X, long ldx, void * x, long n, hipStream_t stream);
@@ -84,6 +95,15 @@ int launch_spmm_column_scatter(bool f32, const void * y, void * Y, long ldy, lon
 int sell_window_lds_budget();
 int launch_sell_window(bool f32, int waves_per_slice, int slices_per_group, const int * grp, const int64_t * sdesc, const unsigned short * idx,
 		const void * val, const int * row_of_sorted, const void * x, void * y, int m, int lds_window_bytes, const LaunchCfg & cfg,
+		hipStream_t stream, long * grid_out);
+
+// Y = A X (beta 0) / Y += A X (beta 1) for k vectors on the same layout (kernels_sell_window_spmm.hip), X and Y as for
+// launch_sell_delta_spmm, wmax = the widest window of the handle's groups. One launch per pass of K = 8, 4, 2 or 1 columns whose window
+// of X, (wmax + 1) * K values, and partial sums fit the 160 KiB of LDS a workgroup may declare: sell_window_spmm_max_cols is the largest
+// such K, and k runs as passes of spmm_pass_cols(that, columns left). Column j is bit-identical to launch_sell_window on column j.
+int sell_window_spmm_max_cols(bool f32, int waves_per_slice, int slices_per_group, int wmax);
+int launch_sell_window_spmm(bool f32, int waves_per_slice, int slices_per_group, const int * grp, const int64_t * sdesc, const unsigned short * idx,
+		const void * val, const int * row_of_sorted, int k, const void * X, long ldx, void * Y, long ldy, int m, int wmax, const LaunchCfg & cfg,
 		hipStream_t stream, long * grid_out);
 
 // the same layout holding ONE TRIANGLE of a symmetric matrix: y window in LDS beside the x window, mirrored entries as LDS atomics

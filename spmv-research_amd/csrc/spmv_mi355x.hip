@@ -379,6 +379,41 @@ spmm_args_ok(const char * what, const spmv_mi355x_matrix * A, int k, const void 
 	return 0;
 }
 
+// the most columns one pass over the matrix arrays serves on this handle (0: a handle without entries streams nothing)
+static int
+spmm_cols_per_pass(const spmv_mi355x_matrix * A)
+{
+	if (A->nnz == 0)
+		return 0;
+	if (A->format == SPMV_MI355X_SELL_C_SIGMA && A->sell_window && !A->sell_sym)
+		return spmv::sell_window_spmm_max_cols(A->f32, A->sell_split, A->sellw_ns, A->sellw_wmax);
+	if (A->format == SPMV_MI355X_SELL_C_SIGMA && A->sell_delta && !A->sell_window && !A->sell_sym)
+		return spmv::SELL_DELTA_SPMM_COLS;
+	return 1;
+}
+
+int
+spmv_mi355x_spmm_plan(const spmv_mi355x_matrix * A, int k, int * matrix_passes_out, int * max_cols_per_pass_out)
+{
+	if (!A || k < 1 || !matrix_passes_out || !max_cols_per_pass_out)
+	{
+		set_error("spmm_plan: %s", !A ? "NULL handle" : k < 1 ? "k must be >= 1" : "NULL out pointer");
+		return 1;
+	}
+	// the walk over k of the launchers (spmm_pass_cols), with the handle's cap
+	const int cap = spmm_cols_per_pass(A);
+	int passes = 0, widest = 0;
+	for (int j0 = 0; cap > 0 && j0 < k; passes++)
+	{
+		const int K = spmv::spmm_pass_cols(cap, k - j0);
+		widest = std::max(widest, K);
+		j0 += K;
+	}
+	*matrix_passes_out = passes;
+	*max_cols_per_pass_out = widest;
+	return 0;
+}
+
 static int
 spmm_enqueue(spmv_mi355x_matrix * A, int k, const void * X, long ldx, void * Y, long ldy, int beta, hipStream_t st)
 {
@@ -404,9 +439,20 @@ spmm_enqueue(spmv_mi355x_matrix * A, int k, const void * X, long ldx, void * Y, 
 		A->last_grid = grid;
 		return rc;
 	}
-	// every other layout, column by column: X[:, j] into contiguous scratch, the layout's own SpMV, the result into Y[:, j]
 	if (k == 1 && ldx == 1 && ldy == 1)
 		return spmv_mi355x_spmv_device_async(A, X, Y, beta, st);
+	if (A->format == SPMV_MI355X_SELL_C_SIGMA && A->sell_window && !A->sell_sym)
+	{
+		// the LDS-window layout: passes of up to Kmax columns, strided X and Y read and written by the kernel itself (also when Kmax = 1)
+		LaunchCfg cfg = A->cfg;
+		cfg.beta = beta ? 1 : 0;
+		long grid = 0;
+		const int rc = launch_sell_window_spmm(A->f32, A->sell_split, A->sellw_ns, A->d_sellw_grp, A->d_sell_desc, (const unsigned short *) A->d_sell_idx,
+				A->d_val, A->d_row_of_sorted, k, X, ldx, Y, ldy, (int) A->m, A->sellw_wmax, cfg, st, &grid);
+		A->last_grid = grid;
+		return rc;
+	}
+	// every other layout, column by column: X[:, j] into contiguous scratch, the layout's own SpMV, the result into Y[:, j]
 	if (!A->d_spmm_x)
 	{
 		const size_t xb = (size_t) (A->n + 64) * A->vbytes, yb = (size_t) (A->m + 64) * A->vbytes;

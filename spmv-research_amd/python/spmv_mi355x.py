@@ -48,7 +48,7 @@ SYMBOLS = [
     "spmv_mi355x_partitioned_mem_footprint",
     "spmv_mi355x_upload_y", "spmv_mi355x_output_alloc", "spmv_mi355x_input_alloc", "spmv_mi355x_output_free", "spmv_mi355x_placement_release", "spmv_mi355x_placement_info", "spmv_mi355x_place_arrays",
     "spmv_mi355x_csr_stream_begin", "spmv_mi355x_csr_stream_append", "spmv_mi355x_create_from_stream", "spmv_mi355x_csr_stream_discard",
-    "spmv_mi355x_spmm_device_async", "spmv_mi355x_time_spmm_device", "spmv_mi355x_spmm",
+    "spmv_mi355x_spmm_device_async", "spmv_mi355x_time_spmm_device", "spmv_mi355x_spmm", "spmv_mi355x_spmm_plan",
 ]
 
 _lib = None
@@ -361,8 +361,8 @@ class Matrix:
         return ms.value
 
     def spmm(self, X):
-        """Y = A X for a host array X of shape (cols, k): returns Y of shape (rows, k) (spmv_mi355x_spmm, one pass over the matrix per
-        8 columns on the SELL delta layout)."""
+        """Y = A X for a host array X of shape (cols, k): returns Y of shape (rows, k) (spmv_mi355x_spmm; one pass over the matrix per
+        8 columns on the SELL delta layout, per spmm_plan(k)[1] columns on the LDS-window layout)."""
         X = np.ascontiguousarray(X, self.dtype)
         if X.ndim != 2 or X.shape[0] != self.n:
             raise ValueError(f"X must have shape ({self.n}, k), got {X.shape}")
@@ -376,6 +376,13 @@ class Matrix:
         values); enqueued on `stream` (spmv_mi355x_spmm_device_async)."""
         _check(lib().spmv_mi355x_spmm_device_async(self.h, C.c_int(k), C.c_void_p(x_ptr), C.c_long(ldx), C.c_void_p(y_ptr), C.c_long(ldy),
                                                    C.c_int(beta), C.c_void_p(stream)))
+
+    def spmm_plan(self, k):
+        """(passes over the matrix arrays, most columns one pass serves) of an spmm with k columns on this handle
+        (spmv_mi355x_spmm_plan): (k, 1) = served column by column, (0, 0) = a handle without entries."""
+        passes, cols = C.c_int(), C.c_int()
+        _check(lib().spmv_mi355x_spmm_plan(self.h, C.c_int(k), C.byref(passes), C.byref(cols)))
+        return passes.value, cols.value
 
     def time_spmm_device(self, k, x_ptr, ldx, y_ptr, ldy, iters, stream=0):
         """ms per spmm of `iters` back-to-back launches, timed with HIP events on `stream` (spmv_mi355x_time_spmm_device)."""

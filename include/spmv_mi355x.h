@@ -114,7 +114,32 @@ typedef struct {
 	                           normals within 7 binades store each value in 7 bytes (sign, 3-bit exponent code against a per-slice base,
 	                           52-bit mantissa; lossless, bit-identical results; csrc/launch.hpp). 0 = auto (on when the plain value array
 	                           exceeds the 256 MiB Infinity Cache), 1 = on, 2 = off. SPMV_MI355X_SELL_VALUES in the environment overrides */
+	int  value_storage;     /* how the matrix VALUES are stored, independent of the precision of x and y:
+	                           0 = in the handle's precision (default), 1 = fp32. See "mixed precision" below.                  */
 } spmv_mi355x_opts;
+
+/* ---- mixed precision: fp64 vectors over fp32-stored values (opts.value_storage = 1) ------------------------------------- */
+/* With precision SPMV_MI355X_F64 and value_storage = 1 the values are narrowed to fp32 on upload, exactly as an F32 handle narrows
+ * them, while x, y, every product and every row sum stay fp64: the kernel widens each stored value (exactly) and runs the fp64
+ * kernel's FMAs in the fp64 kernel's order. The value stream is half as long: about 4.3 instead of 8.3 bytes per non-zero in the
+ * delta layout's index-free modes.
+ *   - LOSSY, and therefore never chosen automatically: the product is that of the ROUNDED matrix, bit-identical to what an fp64
+ *     handle (sell_values = 2) built from (double) (float) values gives, on every variant of the layout and for spmm of any k.
+ *     Each stored value is off by at most half an fp32 ulp (2^-24 relative); a value outside fp32's range becomes +-inf or is
+ *     flushed, as in an F32 handle.
+ *   - served by SPMV_MI355X_SELL_C_SIGMA in the delta layout only (spmv_mi355x_create and spmv_mi355x_create_from_stream). The
+ *     stored arrays are byte for byte those of the F32 handle of the same matrix and options. With the field set the automatic
+ *     choices go to that layout: sell_window auto = off, sell_values auto = off (7-byte records are fp64 only), and
+ *     symmetric_input = 1 always expands the triangle at create(). Row blocks and column filters work as always.
+ *   - rc 1, with a last_error that names value_storage and before any device is touched, for: another format, sell_window = 1,
+ *     sell_delta = 2, sell_c other than 0 or 64, sell_values = 1; and for any value_storage other than 0 or 1.
+ *   - with precision SPMV_MI355X_F32 value_storage = 1 is accepted and changes nothing (whatever the format and layout).
+ *   - format_name() of a mixed handle ends in "_v4" (4-byte values under fp64 vectors: MI355X_SELLD_64_16384_d_v4);
+ *     spmv_mi355x_precision() keeps meaning the precision of x and y, spmv_mi355x_value_storage() tells that of the stored values;
+ *     mem_footprint() counts the stored bytes, csr_mem_footprint() keeps normalising by the vector precision (the fp64 problem);
+ *     spmv_mi355x_sell_layout() returns the stored values widened to fp64.
+ *   - the solvers (pcg, pbicgstab, their _multi forms) run on a mixed handle unchanged, with fp64 vectors.
+ * A caller whose struct_size ends before the field gets value_storage = 0. */
 
 /* ---- library / device ------------------------------------------------------------------------------------ */
 const char * spmv_mi355x_last_error(void);
@@ -135,7 +160,8 @@ double spmv_mi355x_csr_mem_footprint(const spmv_mi355x_matrix * A);  /* nnz*(siz
 long   spmv_mi355x_rows(const spmv_mi355x_matrix * A);               /* local rows (row block)                      */
 long   spmv_mi355x_cols(const spmv_mi355x_matrix * A);
 long   spmv_mi355x_nnz(const spmv_mi355x_matrix * A);                /* local non-zeros after row/column filtering  */
-int    spmv_mi355x_precision(const spmv_mi355x_matrix * A);          /* SPMV_MI355X_F64 / SPMV_MI355X_F32           */
+int    spmv_mi355x_precision(const spmv_mi355x_matrix * A);          /* SPMV_MI355X_F64 / SPMV_MI355X_F32 of x and y */
+int    spmv_mi355x_value_storage(const spmv_mi355x_matrix * A);      /* ... of the stored values (opts.value_storage); NULL: -1 */
 int    spmv_mi355x_device(const spmv_mi355x_matrix * A);             /* HIP device ordinal the handle lives on      */
 
 /* ---- a handle from a CSR that arrives in pieces ---------------------------------------------------------------------- */

@@ -157,7 +157,7 @@ sell_delta_map(spmv_mi355x_matrix * A, const int64_t * val_ptr)
 	const long num_slices = A->sell_slices;
 	const long spt = sell_slices_per_tile() / A->sell_split;       // slices per workgroup
 	A->cfg.map = xcd_map_balanced(val_ptr, num_slices, spt, resolve_remap(A->remap, (num_slices + spt - 1) / spt));
-	A->mem_footprint = (double) (num_slices + 1) * 16 + (double) A->sell_val_words * A->vbytes + (double) A->sell_idx_bytes + (double) A->m * 4;
+	A->mem_footprint = (double) (num_slices + 1) * 16 + (double) A->sell_val_words * A->val_bytes + (double) A->sell_idx_bytes + (double) A->m * 4;
 }
 
 // the GPU builder's arrays into the handle
@@ -182,12 +182,12 @@ static void
 sell_delta_names(spmv_mi355x_matrix * A, const spmv_mi355x_opts & o)
 {
 	const char * pf = A->f32 ? "f" : "d";
-	const char * v7 = A->sell_v7_slices ? "_v7" : "";
+	const char * v7 = A->sell_v7_slices ? "_v7" : A->mixed() ? "_v4" : "";      // _v4: fp32 values under fp64 vectors (opts.value_storage)
 	if (A->sell_split > 1)
 		snprintf(A->format_name, sizeof(A->format_name), "MI355X_SELLD_%d_%ld_w%d_%s%s", A->sell_c, A->sell_sigma, A->sell_split, pf, v7);
 	else
 		snprintf(A->format_name, sizeof(A->format_name), "MI355X_SELLD_%d_%ld_%s%s", A->sell_c, A->sell_sigma, pf, v7);
-	snprintf(A->kernel_name, sizeof(A->kernel_name), "sell_delta_kernel");
+	snprintf(A->kernel_name, sizeof(A->kernel_name), A->mixed() ? "sell_delta_mixed_kernel" : "sell_delta_kernel");
 	if (A->sell_v7_slices && o.nontemporal == 0)
 		A->cfg.nt = A->mem_footprint > 192.0 * 1024 * 1024 ? 1 : 0;      // the auto rule of init_handle on the bytes really stored
 }
@@ -204,7 +204,7 @@ build_sell_delta(spmv_mi355x_matrix * A, int sell_values, const int * rp, const 
 	if (A->convert_on_device)
 	{
 		SellDeltaArrays r;
-		if (sell_delta_convert_device(A->f32, m, A->n, A->nnz, sigma, sell_values, rp, ci, va, r))
+		if (sell_delta_convert_device(A->val_f32, m, A->n, A->nnz, sigma, sell_values, rp, ci, va, r))
 			return 1;
 		sell_delta_install(A, r);
 		return 0;
@@ -289,7 +289,7 @@ build_sell_delta(spmv_mi355x_matrix * A, int sell_values, const int * rp, const 
 		int64_t plain = 0;
 		for (long sl = 0; sl < num_slices; sl++)
 			plain += val_ptr[sl + 1];
-		if (sell_v7_wanted(A->f32, sell_values, plain))
+		if (sell_v7_wanted(A->val_f32, sell_values, plain))
 		{
 			#pragma omp parallel for num_threads(spmv::host_threads()) schedule(dynamic, 64)
 			for (long sl = 0; sl < num_slices; sl++)
@@ -689,7 +689,8 @@ build_sell_family(spmv_mi355x_matrix * A, const spmv_mi355x_opts & o, const int 
 	// ---- x window in LDS + 16-bit indices (banded / FEM matrices): sell_window 0 = auto, 1 = on (error when not applicable), 2 = off
 	// (auto only when sell_sigma, sell_delta and convert_on are all at their defaults: the window layout sorts inside a slice group, i.e. with
 	// its own sigma = 64 * slices per group — a caller who names a sigma, e.g. for the a6'/a7 layout parity entry point, gets that sigma)
-	if (C == 64 && o.sell_window != 2 && (o.sell_window == 1 || (o.sell_delta == 0 && o.convert_on == 0 && o.sell_sigma == 0)))
+	// (fp32 values under fp64 vectors live in the delta layout alone: no window layout on its own)
+	if (C == 64 && !A->mixed() && o.sell_window != 2 && (o.sell_window == 1 || (o.sell_delta == 0 && o.convert_on == 0 && o.sell_sigma == 0)))
 	{
 		const long slices = (lm + 63) / 64;
 		const double mean = lm > 0 ? (double) A->nnz / lm : 0;
@@ -783,7 +784,7 @@ build_sell_delta_resident(spmv_mi355x_matrix * A, const spmv_mi355x_opts & o, co
 	A->convert_on_device = true;
 	A->sell_split = S;
 	SellDeltaArrays r;
-	if (sell_delta_convert_resident(A->f32, m, A->n, A->nnz, sigma, sell_values_env(o.sell_values), d_rp, d_ci, d_va, r))
+	if (sell_delta_convert_resident(A->val_f32, m, A->n, A->nnz, sigma, sell_values_env(o.sell_values), d_rp, d_ci, d_va, r))
 		return 1;
 	sell_delta_install(A, r);
 	sell_delta_names(A, o);

@@ -177,6 +177,8 @@ spmv_mi355x_create_from_stream(spmv_mi355x_matrix ** out, spmv_mi355x_csr_stream
 		set_error("unknown precision %d", precision);
 		rc = 1;
 	}
+	else if (value_storage_check("create_from_stream", o, format, precision))
+		rc = 1;
 	else if (s->rows_done != s->m)
 	{
 		set_error("create_from_stream: %ld of %ld rows were appended", s->rows_done, s->m);

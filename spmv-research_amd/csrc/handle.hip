@@ -29,17 +29,17 @@ free_all(spmv_mi355x_matrix * A)
 		(void) hipStreamDestroy(A->stream);
 }
 
-// narrow fp64 reference values to the handle's precision (csr.cpp:72 `a[i] = values[i]`) and upload
+// narrow fp64 reference values to the handle's value storage (csr.cpp:72 `a[i] = values[i]`) and upload
 int
 upload_values(spmv_mi355x_matrix * A, const double * v, size_t count, void ** d_out)
 {
 	// STREAM_SLACK spare entries: the LDS-DMA row-block copy reads whole 1 KiB chunks (kernels_csr_stream.hip)
-	if (dev_alloc_bytes(d_out, (count + STREAM_SLACK) * A->vbytes))
+	if (dev_alloc_bytes(d_out, (count + STREAM_SLACK) * A->val_bytes))
 		return 1;
-	HIP_TRY(hipMemset((char *) *d_out + count * A->vbytes, 0, STREAM_SLACK * A->vbytes));
+	HIP_TRY(hipMemset((char *) *d_out + count * A->val_bytes, 0, STREAM_SLACK * A->val_bytes));
 	if (count == 0)
 		return 0;
-	if (!A->f32)
+	if (!A->val_f32)
 	{
 		HIP_TRY(hipMemcpy(*d_out, v, count * sizeof(double), hipMemcpyHostToDevice));
 		return 0;
@@ -109,7 +109,7 @@ values_uniform(const spmv_mi355x_matrix * A, const double * va, long nnz, double
 {
 	if (nnz <= 0)
 		return false;
-	const bool f32 = A->f32;
+	const bool f32 = A->val_f32;
 	const double v0 = f32 ? (double) (float) va[0] : va[0];
 	long differs = 0;
 	#pragma omp parallel for num_threads(spmv::host_threads()) reduction(+ : differs)

@@ -18,8 +18,14 @@ struct spmv_mi355x_matrix {
 	int format = 0, precision = 0;
 	long m = 0, n = 0, nnz = 0;            // local rows, columns, local non-zeros
 	int device = 0;
-	bool f32 = false;
-	size_t vbytes = 8;
+	// Two precisions (opts.value_storage): that of the VECTORS — x, y, scratch columns, solver state, host transfers, the type the
+	// kernels compute in — and that of the stored VALUE array. Only the SELL delta layout may hold fp32 values under fp64 vectors
+	// (mixed()); every other layout keeps both equal.
+	bool f32 = false;                      // vectors are fp32 (= precision)
+	size_t vbytes = 8;                     // bytes of a vector element
+	bool val_f32 = false;                  // values are stored as fp32
+	size_t val_bytes = 8;                  // bytes of a stored value
+	bool mixed() const { return val_f32 && !f32; }
 	spmv::LaunchCfg cfg{};
 	int remap = 1;
 
@@ -104,6 +110,8 @@ namespace spmv {
 int dev_alloc_bytes(void ** p, size_t bytes);
 int build_sell_delta_resident(spmv_mi355x_matrix * A, const spmv_mi355x_opts & o, const int * d_rp, const int * d_ci, const double * d_va);   // build_sell.hip
 void init_handle(spmv_mi355x_matrix * A, int format, int precision, int device, const spmv_mi355x_opts & o, long m, long n, long nnz);   // spmv_mi355x.hip
+// opts.value_storage against format, precision and the layout options: 0 = fine, 1 = error set (spmv_mi355x.hip; touches no device)
+int value_storage_check(const char * what, const spmv_mi355x_opts & o, int format, int precision);
 int ensure_x(spmv_mi355x_matrix * A);                                    // spmv_mi355x.hip: stream + the handle's own (zeroed) x
 int tune_placement(spmv_mi355x_matrix * A);                              // placement.hip: allocates the handle's y (and re-homes its x) in the device's vector pools
 int place_vector(spmv_mi355x_matrix * A, void ** out, size_t bytes, bool is_output);   // placement.hip: a zero-filled vector A's SpMV writes / reads
@@ -115,13 +123,13 @@ dev_alloc(T ** p, size_t count)
 	return dev_alloc_bytes((void **) p, (count ? count : 1) * sizeof(T));
 }
 void free_all(spmv_mi355x_matrix * A);
-// narrow fp64 reference values to the handle's precision (csr.cpp:72 `a[i] = values[i]`) and upload, with STREAM_SLACK spare entries
+// narrow fp64 reference values to the handle's value storage (csr.cpp:72 `a[i] = values[i]`) and upload, with STREAM_SLACK spare entries
 int upload_values(spmv_mi355x_matrix * A, const double * v, size_t count, void ** d_out);
 int upload_ints(const int * src, size_t count, int ** d_out);
 int upload_bytes(const void * src, size_t bytes, size_t slack_bytes, void ** d_out);
 int pick_lanes_per_row(double mean);
 int resolve_remap(int requested, long ntiles);
-// every stored value (narrowed to the handle's precision) equals *v0_out: Matrix-Market `pattern` matrices carry the dummy 1.0
+// every stored value (narrowed to the handle's value storage) equals *v0_out: Matrix-Market `pattern` matrices carry the dummy 1.0
 bool values_uniform(const spmv_mi355x_matrix * A, const double * va, long nnz, double * v0_out);
 
 // ---- input stage of create() (build_input.hip): what csr_to_format() receives -> the local CSR a format is built from

@@ -176,9 +176,9 @@ sell_wide_kernel(const int64_t * __restrict__ slice_ptr, const int * __restrict_
 // HBM bytes per non-zero drop by up to 24 % (fp64) / 37 % (fp32) below the CSR-normalised "algorithmic" 12 / 8 bytes.
 // The value readers and index decoders live in sell_delta_read.hpp, shared with the multi-vector kernel (kernels_sell_spmm.hip).
 
-template <typename T, int MODE, bool NT, bool V7, int NSTEPS = 4>
+template <typename T, int MODE, bool NT, bool V7, int NSTEPS = 4, typename S = T>
 __device__ __forceinline__ void
-sell_delta_group(const unsigned char * __restrict__ gp /* uniform */, const SellVals<T, NT, V7> & vals, int g, int lane, const T * __restrict__ x, T & s,
+sell_delta_group(const unsigned char * __restrict__ gp /* uniform */, const SellVals<T, NT, V7, S> & vals, int g, int lane, const T * __restrict__ x, T & s,
 		int off = 0)
 {
 	int c[4];
@@ -232,9 +232,9 @@ sell_pin(sell_uint2 & v, bool both)
 // trip are issued before its first FMA), their index words fetched one trip ahead; what is left (0..3 groups) as a pair and / or a single
 // group on the index words the last trip already fetched. (Two groups per trip: 1 347 us with every index-free mode off; four: see
 // profiles/r03_sell_value_pairs.txt.)
-template <typename T, int MODE, bool NT, bool V7, int NG>
+template <typename T, int MODE, bool NT, bool V7, int NG, typename S = T>
 __device__ __forceinline__ void
-sell_delta_consume(const SellDeltaIdx<MODE> * q, const SellVals<T, NT, V7> & vals, const int * g, const T * __restrict__ x, T & s)
+sell_delta_consume(const SellDeltaIdx<MODE> * q, const SellVals<T, NT, V7, S> & vals, const int * g, const T * __restrict__ x, T & s)
 {
 	T v[NG][4];
 	int c[NG][4];
@@ -257,9 +257,9 @@ sell_delta_consume(const SellDeltaIdx<MODE> * q, const SellVals<T, NT, V7> & val
 			s = fma_t<T>(v[u][t], xv[u][t], s);
 }
 
-template <typename T, int MODE, bool NT, bool V7>
+template <typename T, int MODE, bool NT, bool V7, typename S = T>
 __device__ __forceinline__ void
-sell_delta_piped(const unsigned char * __restrict__ ip, const SellVals<T, NT, V7> & vals, int lane, const T * __restrict__ x, T & s, int g0, int gs, int n)
+sell_delta_piped(const unsigned char * __restrict__ ip, const SellVals<T, NT, V7, S> & vals, int lane, const T * __restrict__ x, T & s, int g0, int gs, int n)
 {
 	constexpr long GB = sell_group_bytes(MODE);
 	if (n <= 0)
@@ -303,9 +303,9 @@ sell_delta_piped(const unsigned char * __restrict__ ip, const SellVals<T, NT, V7
 }
 
 // groups g0, g0+gs, g0+2gs, ... of one slice (gs = 1: the whole slice, in order)
-template <typename T, int MODE, bool NT, bool V7>
+template <typename T, int MODE, bool NT, bool V7, typename S = T>
 __device__ __forceinline__ T
-sell_delta_slice(const unsigned char * __restrict__ ip, const SellVals<T, NT, V7> & vals, int width, int lane, const T * __restrict__ x,
+sell_delta_slice(const unsigned char * __restrict__ ip, const SellVals<T, NT, V7, S> & vals, int width, int lane, const T * __restrict__ x,
 		int g0 = 0, int gs = 1)
 {
 	constexpr long GB = sell_group_bytes(MODE);
@@ -382,9 +382,9 @@ sell_pin5(SellDeltaIdx5 & q)
 		sell_pin(q.d);
 }
 
-template <typename T, bool NT, bool V7, bool SCALAR>
+template <typename T, bool NT, bool V7, bool SCALAR, typename S = T>
 __device__ __forceinline__ T
-sell_delta_slice5_body(const unsigned char * __restrict__ ip, const SellVals<T, NT, V7> & vals, int width, int lane, const T * __restrict__ x,
+sell_delta_slice5_body(const unsigned char * __restrict__ ip, const SellVals<T, NT, V7, S> & vals, int width, int lane, const T * __restrict__ x,
 		int g0, int gs, unsigned long long mask, int off)
 {
 	const int E = __popcll(mask);
@@ -480,7 +480,7 @@ sell_delta_slice5_body(const unsigned char * __restrict__ ip, const SellVals<T, 
 		sell_delta_load_idx5<NT, SCALAR>(q, ip + (size_t) last * GB, rank);
 		int c[4];
 		sell_delta_cols5<SCALAR>(q, ex, lane, off, xl, c);
-		const T * vl = vals.tail(last);
+		const S * vl = vals.tail(last);
 		T tv[3];
 		if (rem == 1)
 			sell_tail_values<T, NT, 1>(vl, lane, tv);
@@ -499,9 +499,9 @@ sell_delta_slice5_body(const unsigned char * __restrict__ ip, const SellVals<T, 
 	return s;
 }
 
-template <typename T, bool NT, bool V7>
+template <typename T, bool NT, bool V7, typename S = T>
 __device__ __forceinline__ T
-sell_delta_slice5(const unsigned char * __restrict__ ip, const SellVals<T, NT, V7> & vals, int width, int lane, const T * __restrict__ x,
+sell_delta_slice5(const unsigned char * __restrict__ ip, const SellVals<T, NT, V7, S> & vals, int width, int lane, const T * __restrict__ x,
 		int g0 = 0, int gs = 1)
 {
 	const int off = ld_stream<NT>(reinterpret_cast<const int *>(ip) + lane);
@@ -513,9 +513,9 @@ sell_delta_slice5(const unsigned char * __restrict__ ip, const SellVals<T, NT, V
 }
 
 // one slice (groups g0, g0 + gs, ... of it) in its index mode; a wave-uniform branch
-template <typename T, bool NT, bool V7>
+template <typename T, bool NT, bool V7, typename S = T>
 __device__ __forceinline__ T
-sell_delta_modes(int mode, const unsigned char * __restrict__ ip, const SellVals<T, NT, V7> & vals, int width, int lane, const T * __restrict__ x,
+sell_delta_modes(int mode, const unsigned char * __restrict__ ip, const SellVals<T, NT, V7, S> & vals, int width, int lane, const T * __restrict__ x,
 		int g0, int gs)
 {
 	if (mode == 0)
@@ -532,10 +532,10 @@ sell_delta_modes(int mode, const unsigned char * __restrict__ ip, const SellVals
 }
 
 // one slice from its two descriptor words (sell_delta_layout.hpp): V7 = the handle holds slices with 7-byte values, each one flagged in
-// desc[2s+1]; without it the code is that of the plain pairs alone
-template <typename T, bool NT, bool V7>
+// desc[2s+1]; without it the code is that of the plain pairs alone. S: the type the values are stored in (sell_delta_read.hpp)
+template <typename T, bool NT, bool V7, typename S = T>
 __device__ __forceinline__ T
-sell_delta_one(const int64_t * __restrict__ desc, int slice, const unsigned char * __restrict__ idx, const T * __restrict__ val, int lane,
+sell_delta_one(const int64_t * __restrict__ desc, int slice, const unsigned char * __restrict__ idx, const S * __restrict__ val, int lane,
 		const T * __restrict__ x, int g0, int gs)
 {
 	const int64_t v_off = desc[2 * slice];
@@ -543,11 +543,11 @@ sell_delta_one(const int64_t * __restrict__ desc, int slice, const unsigned char
 	const int64_t v_next = desc[2 * slice + 2];
 	const int mode = sell_desc_mode(i_word);
 	const unsigned char * ip = idx + sell_desc_idx(i_word);
-	const T * vp = val + v_off + 2 * lane;
+	const S * vp = val + v_off + 2 * lane;
 	if (V7 && sell_desc_v7(i_word))
-		return sell_delta_modes<T, NT, V7>(mode, ip, SellVals<T, NT, V7>{vp, lane, (unsigned) (sell_v7_e0(i_word) - 1) << 20},
+		return sell_delta_modes<T, NT, V7>(mode, ip, SellVals<T, NT, V7, S>{vp, lane, (unsigned) (sell_v7_e0(i_word) - 1) << 20},
 				(int) sell_slice_width(v_next - v_off, true), lane, x, g0, gs);
-	return sell_delta_modes<T, NT, false>(mode, ip, SellVals<T, NT, false>{vp, lane, 0u}, (int) sell_slice_width(v_next - v_off, false), lane, x,
+	return sell_delta_modes<T, NT, false>(mode, ip, SellVals<T, NT, false, S>{vp, lane, 0u}, (int) sell_slice_width(v_next - v_off, false), lane, x,
 			g0, gs);
 }
 
@@ -612,7 +612,70 @@ sell_delta_split_kernel(const int64_t * __restrict__ desc, const unsigned char *
 	}
 }
 
-template <typename T, bool V7>
+// fp32 values under fp64 vectors (opts.value_storage = 1): sell_delta_kernel<double> on the fp32 handle's arrays — the values are read
+// from the fp32 pair layout and widened (sell_delta_read.hpp), the gathers and FMAs are the fp64 kernel's in its order -> bit-identical
+// to the fp64 kernel on the values rounded to fp32. Kernels of their own names, so that every instantiation above keeps its symbol
+// and its code. (VGPRs and occupancy beside the fp64 kernels': profiles/r08_value_storage.txt)
+template <bool NT>
+__global__ __launch_bounds__(SELL_BLOCK) void
+sell_delta_mixed_kernel(const int64_t * __restrict__ desc, const unsigned char * __restrict__ idx, const float * __restrict__ val,
+		const int * __restrict__ row_of_sorted, const double * __restrict__ x, double * __restrict__ y,
+		int m, int num_slices, int beta, XcdMap map)
+{
+	unsigned tile = xcd_tile(blockIdx.x, map);
+	if (tile == NO_TILE)
+		return;
+	const int lane = threadIdx.x % WAVE;
+	const int slice = __builtin_amdgcn_readfirstlane((int) (tile * SELL_WAVES + threadIdx.x / WAVE));
+	if (slice >= num_slices)
+		return;
+	const double s = sell_delta_one<double, NT, false>(desc, slice, idx, val, lane, x, 0, 1);
+	const long sorted_row = (long) slice * WAVE + lane;
+	if (sorted_row < m)
+	{
+		double * yp = y + row_of_sorted[sorted_row];
+		*yp = beta ? *yp + s : s;
+	}
+}
+
+// ... S waves per slice (sell_delta_split_kernel)
+template <int S, bool NT>
+__global__ __launch_bounds__(SELL_BLOCK) void
+sell_delta_mixed_split_kernel(const int64_t * __restrict__ desc, const unsigned char * __restrict__ idx, const float * __restrict__ val,
+		const int * __restrict__ row_of_sorted, const double * __restrict__ x, double * __restrict__ y,
+		int m, int num_slices, int beta, XcdMap map)
+{
+	constexpr int SPB = SELL_WAVES / S;
+	__shared__ double s_part[SELL_WAVES][WAVE];
+	unsigned tile = xcd_tile(blockIdx.x, map);
+	if (tile == NO_TILE)
+		return;
+	const int lane = threadIdx.x % WAVE;
+	const int wave = threadIdx.x / WAVE;
+	const int w = __builtin_amdgcn_readfirstlane(wave % S);
+	const int slice = __builtin_amdgcn_readfirstlane((int) (tile * SPB + wave / S));
+	double s = 0;
+	if (slice < num_slices)
+		s = sell_delta_one<double, NT, false>(desc, slice, idx, val, lane, x, w, S);
+	s_part[wave][lane] = s;
+	__syncthreads();
+	if (w == 0 && slice < num_slices)
+	{
+		double t = s_part[wave][lane];
+		#pragma unroll
+		for (int u = 1; u < S; u++)
+			t += s_part[wave + u][lane];
+		const long sorted_row = (long) slice * WAVE + lane;
+		if (sorted_row < m)
+		{
+			double * yp = y + row_of_sorted[sorted_row];
+			*yp = beta ? *yp + t : t;
+		}
+	}
+}
+
+// MIXED: T = double over values stored as float (sell_delta_mixed_kernel); V7 is then false
+template <typename T, bool V7, bool MIXED = false>
 static int
 sell_delta_launch(int S, const int64_t * desc, const unsigned char * idx, const void * val, const int * row_of_sorted, const void * x, void * y,
 		int m, int num_slices, const LaunchCfg & cfg, hipStream_t stream, long * grid_out)
@@ -622,9 +685,34 @@ sell_delta_launch(int S, const int64_t * desc, const unsigned char * idx, const 
 		*grid_out = grid;
 	if (grid == 0)
 		return 0;
-	#define SELLD_LAUNCH(K) hipLaunchKernelGGL(K, dim3(grid), dim3(SELL_BLOCK), 0, stream, desc, idx, (const T *) val, \
+	typedef std::conditional_t<MIXED, float, T> SV;
+	#define SELLD_LAUNCH(K) hipLaunchKernelGGL(K, dim3(grid), dim3(SELL_BLOCK), 0, stream, desc, idx, (const SV *) val, \
 			row_of_sorted, (const T *) x, (T *) y, m, num_slices, cfg.beta, cfg.map)
-	if (S == 1)
+	if (S != 1 && S != 2 && S != 4)
+	{
+		set_error("sell_delta: waves per slice must be 1, 2 or 4 (got %d)", S);
+		return 1;
+	}
+	if constexpr (MIXED)
+	{
+		static_assert(std::is_same<T, double>::value && !V7, "fp32 values under fp64 vectors, plain pairs");
+		if (S == 1)
+		{
+			if (cfg.nt) SELLD_LAUNCH((sell_delta_mixed_kernel<true>));
+			else        SELLD_LAUNCH((sell_delta_mixed_kernel<false>));
+		}
+		else if (S == 2)
+		{
+			if (cfg.nt) SELLD_LAUNCH((sell_delta_mixed_split_kernel<2, true>));
+			else        SELLD_LAUNCH((sell_delta_mixed_split_kernel<2, false>));
+		}
+		else
+		{
+			if (cfg.nt) SELLD_LAUNCH((sell_delta_mixed_split_kernel<4, true>));
+			else        SELLD_LAUNCH((sell_delta_mixed_split_kernel<4, false>));
+		}
+	}
+	else if (S == 1)
 	{
 		if (cfg.nt) SELLD_LAUNCH((sell_delta_kernel<T, true, V7>));
 		else        SELLD_LAUNCH((sell_delta_kernel<T, false, V7>));
@@ -634,15 +722,10 @@ sell_delta_launch(int S, const int64_t * desc, const unsigned char * idx, const 
 		if (cfg.nt) SELLD_LAUNCH((sell_delta_split_kernel<T, 2, true, V7>));
 		else        SELLD_LAUNCH((sell_delta_split_kernel<T, 2, false, V7>));
 	}
-	else if (S == 4)
+	else
 	{
 		if (cfg.nt) SELLD_LAUNCH((sell_delta_split_kernel<T, 4, true, V7>));
 		else        SELLD_LAUNCH((sell_delta_split_kernel<T, 4, false, V7>));
-	}
-	else
-	{
-		set_error("sell_delta: waves per slice must be 1, 2 or 4 (got %d)", S);
-		return 1;
 	}
 	#undef SELLD_LAUNCH
 	HIP_TRY(hipGetLastError());
@@ -650,14 +733,21 @@ sell_delta_launch(int S, const int64_t * desc, const unsigned char * idx, const 
 }
 
 int
-launch_sell_delta(bool f32, int waves_per_slice, bool v7, const int64_t * desc, const unsigned char * idx, const void * val, const int * row_of_sorted,
+launch_sell_delta(bool f32, bool val_f32, int waves_per_slice, bool v7, const int64_t * desc, const unsigned char * idx, const void * val, const int * row_of_sorted,
 		const void * x, void * y, int m, int num_slices, const LaunchCfg & cfg, hipStream_t stream, long * grid_out)
 {
-	if (f32 && v7)
+	if (val_f32 && v7)
 	{
 		set_error("sell_delta: 7-byte values are fp64 only");
 		return 1;
 	}
+	if (f32 && !val_f32)
+	{
+		set_error("sell_delta: fp32 vectors over fp64 values are not served");
+		return 1;
+	}
+	if (val_f32 && !f32)
+		return sell_delta_launch<double, false, true>(waves_per_slice, desc, idx, val, row_of_sorted, x, y, m, num_slices, cfg, stream, grid_out);
 	return f32 ? sell_delta_launch<float, false>(waves_per_slice, desc, idx, val, row_of_sorted, x, y, m, num_slices, cfg, stream, grid_out)
 	     : v7  ? sell_delta_launch<double, true>(waves_per_slice, desc, idx, val, row_of_sorted, x, y, m, num_slices, cfg, stream, grid_out)
 	           : sell_delta_launch<double, false>(waves_per_slice, desc, idx, val, row_of_sorted, x, y, m, num_slices, cfg, stream, grid_out);

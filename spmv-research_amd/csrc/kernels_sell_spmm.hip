@@ -81,9 +81,9 @@ struct SpmmCols5 {
 };
 
 // NG full groups g[0..NG) of a slice: all loads of the trip first (indices, values, then the gathers), then the FMAs step by step
-template <typename T, int K, int VW, int NG, bool NT, bool V7, typename Cols>
+template <typename T, int K, int VW, int NG, bool NT, bool V7, typename Cols, typename SV = T>
 __device__ __forceinline__ void
-spmm_trip(const Cols & cols, const SellVals<T, NT, V7> & vals, const int (&g)[NG], const T * __restrict__ X, long ldx, T (&acc)[K])
+spmm_trip(const Cols & cols, const SellVals<T, NT, V7, SV> & vals, const int (&g)[NG], const T * __restrict__ X, long ldx, T (&acc)[K])
 {
 	int c[NG][4];
 	T v[NG][4];
@@ -109,9 +109,9 @@ spmm_trip(const Cols & cols, const SellVals<T, NT, V7> & vals, const int (&g)[NG
 }
 
 // the last group of a slice whose width is not a multiple of 4: NSTEPS (1..3) real steps
-template <typename T, int K, int VW, int NSTEPS, bool NT, bool V7, typename Cols>
+template <typename T, int K, int VW, int NSTEPS, bool NT, bool V7, typename Cols, typename SV = T>
 __device__ __forceinline__ void
-spmm_tail(const Cols & cols, const SellVals<T, NT, V7> & vals, int g, int lane, const T * __restrict__ X, long ldx, T (&acc)[K])
+spmm_tail(const Cols & cols, const SellVals<T, NT, V7, SV> & vals, int g, int lane, const T * __restrict__ X, long ldx, T (&acc)[K])
 {
 	int c[4];
 	cols(g, c);
@@ -129,9 +129,9 @@ spmm_tail(const Cols & cols, const SellVals<T, NT, V7> & vals, int g, int lane, 
 }
 
 // groups g0, g0 + gs, ... of one slice in order (gs = 1: the whole slice), then its tail group if this wave's sequence reaches it
-template <typename T, int K, int VW, bool NT, bool V7, typename Cols>
+template <typename T, int K, int VW, bool NT, bool V7, typename Cols, typename SV = T>
 __device__ __forceinline__ void
-spmm_walk(const Cols & cols, const SellVals<T, NT, V7> & vals, int width, int lane, const T * __restrict__ X, long ldx, T (&acc)[K], int g0,
+spmm_walk(const Cols & cols, const SellVals<T, NT, V7, SV> & vals, int width, int lane, const T * __restrict__ X, long ldx, T (&acc)[K], int g0,
 		int gs)
 {
 	constexpr int NG = spmm_trip_groups<T, K>();
@@ -174,9 +174,9 @@ spmm_walk(const Cols & cols, const SellVals<T, NT, V7> & vals, int width, int la
 }
 
 // one slice in its index mode (a wave-uniform branch); ip = the slice's index block
-template <typename T, int K, int VW, bool NT, bool V7>
+template <typename T, int K, int VW, bool NT, bool V7, typename SV = T>
 __device__ __forceinline__ void
-spmm_modes(int mode, const unsigned char * __restrict__ ip, const SellVals<T, NT, V7> & vals, int width, int lane, const T * __restrict__ X,
+spmm_modes(int mode, const unsigned char * __restrict__ ip, const SellVals<T, NT, V7, SV> & vals, int width, int lane, const T * __restrict__ X,
 		long ldx, T (&acc)[K], int g0, int gs)
 {
 	if (mode == 0)
@@ -278,6 +278,69 @@ sell_delta_spmm_kernel(const int64_t * __restrict__ desc, const unsigned char * 
 	}
 }
 
+// fp32 values under fp64 vectors (opts.value_storage = 1; kernels_sell.hip: sell_delta_mixed_kernel): sell_delta_spmm_kernel<double> on
+// values read from the fp32 pair layout and widened, under a name of its own so that every instantiation above keeps its symbol and code
+template <int K, int VW, int S, bool NT>
+__global__ __launch_bounds__(SPMM_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) void
+sell_delta_mixed_spmm_kernel(const int64_t * __restrict__ desc, const unsigned char * __restrict__ idx, const float * __restrict__ val,
+		const int * __restrict__ row_of_sorted, const double * __restrict__ X, long ldx, double * __restrict__ Y, long ldy, int m,
+		int num_slices, int beta, XcdMap map)
+{
+	typedef double T;
+	constexpr int SPB = SPMM_WAVES / S;            // slices per workgroup
+	const unsigned tile = xcd_tile(blockIdx.x, map);
+	if (tile == NO_TILE)
+		return;
+	const int lane = threadIdx.x % WAVE;
+	const int wave = threadIdx.x / WAVE;
+	const int w = __builtin_amdgcn_readfirstlane(wave % S);
+	const int slice = __builtin_amdgcn_readfirstlane((int) (tile * SPB + wave / S));
+	if (S == 1 && slice >= num_slices)
+		return;
+	T acc[K];
+	#pragma unroll
+	for (int j = 0; j < K; j++)
+		acc[j] = T(0);
+	if (slice < num_slices)
+	{
+		const int64_t v_off = desc[2 * slice];
+		const int64_t i_word = desc[2 * slice + 1];
+		const int64_t v_next = desc[2 * slice + 2];
+		const int mode = sell_desc_mode(i_word);
+		const unsigned char * ip = idx + sell_desc_idx(i_word);
+		const float * vp = val + v_off + 2 * lane;
+		spmm_modes<T, K, VW, NT, false>(mode, ip, SellVals<T, NT, false, float>{vp, lane, 0u}, (int) sell_slice_width(v_next - v_off, false), lane, X,
+				ldx, acc, w, S);
+	}
+	if constexpr (S > 1)
+	{
+		__shared__ T s_part[SPMM_WAVES][K][WAVE];
+		#pragma unroll
+		for (int j = 0; j < K; j++)
+			s_part[wave][j][lane] = acc[j];
+		__syncthreads();
+		if (w != 0 || slice >= num_slices)
+			return;
+		#pragma unroll
+		for (int j = 0; j < K; j++)
+		{
+			T t = s_part[wave][j][lane];
+			#pragma unroll
+			for (int u = 1; u < S; u++)
+				t += s_part[wave + u][j][lane];
+			acc[j] = t;
+		}
+	}
+	const long sorted_row = (long) slice * WAVE + lane;
+	if (sorted_row < m)
+	{
+		T * yp = Y + (long) row_of_sorted[sorted_row] * ldy;
+		#pragma unroll
+		for (int j = 0; j < K; j++)
+			yp[j] = beta ? yp[j] + acc[j] : acc[j];
+	}
+}
+
 struct SpmmArgs {
 	const int64_t * desc;
 	const unsigned char * idx;
@@ -286,12 +349,19 @@ struct SpmmArgs {
 	int m, num_slices;
 };
 
-template <typename T, int K, int VW, bool V7>
+// MIXED: T = double over values stored as float (sell_delta_mixed_spmm_kernel); V7 is then false
+template <typename T, int K, int VW, bool V7, bool MIXED>
 static int
 spmm_launch(int S, const SpmmArgs & a, const void * X, long ldx, void * Y, long ldy, const LaunchCfg & cfg, unsigned grid, hipStream_t stream)
 {
-	#define SPMM_LAUNCH(S_, NT_) hipLaunchKernelGGL((sell_delta_spmm_kernel<T, K, VW, S_, NT_, V7>), dim3(grid), dim3(SPMM_BLOCK), 0, stream, \
-			a.desc, a.idx, (const T *) a.val, a.row_of_sorted, (const T *) X, ldx, (T *) Y, ldy, a.m, a.num_slices, cfg.beta, cfg.map)
+	#define SPMM_LAUNCH(S_, NT_) do { \
+			if constexpr (MIXED) \
+				hipLaunchKernelGGL((sell_delta_mixed_spmm_kernel<K, VW, S_, NT_>), dim3(grid), dim3(SPMM_BLOCK), 0, stream, a.desc, a.idx, \
+						(const float *) a.val, a.row_of_sorted, (const double *) X, ldx, (double *) Y, ldy, a.m, a.num_slices, cfg.beta, cfg.map); \
+			else \
+				hipLaunchKernelGGL((sell_delta_spmm_kernel<T, K, VW, S_, NT_, V7>), dim3(grid), dim3(SPMM_BLOCK), 0, stream, a.desc, a.idx, \
+						(const T *) a.val, a.row_of_sorted, (const T *) X, ldx, (T *) Y, ldy, a.m, a.num_slices, cfg.beta, cfg.map); \
+		} while (0)
 	if (S == 1)
 	{
 		if (cfg.nt) SPMM_LAUNCH(1, true);
@@ -318,18 +388,18 @@ spmm_launch(int S, const SpmmArgs & a, const void * X, long ldx, void * Y, long 
 }
 
 // one pass of K columns: vector gathers of VMAX values (16 bytes at most) when X and ldx keep every row's run of K aligned to them
-template <typename T, int K, bool V7>
+template <typename T, int K, bool V7, bool MIXED>
 static int
 spmm_pass(int S, const SpmmArgs & a, const void * X, long ldx, void * Y, long ldy, const LaunchCfg & cfg, unsigned grid, hipStream_t stream)
 {
 	constexpr int VMAX = K < (int) (16 / sizeof(T)) ? K : (int) (16 / sizeof(T));
 	if constexpr (VMAX > 1)
 		if ((uintptr_t) X % (VMAX * sizeof(T)) == 0 && ldx % VMAX == 0)
-			return spmm_launch<T, K, VMAX, V7>(S, a, X, ldx, Y, ldy, cfg, grid, stream);
-	return spmm_launch<T, K, 1, V7>(S, a, X, ldx, Y, ldy, cfg, grid, stream);
+			return spmm_launch<T, K, VMAX, V7, MIXED>(S, a, X, ldx, Y, ldy, cfg, grid, stream);
+	return spmm_launch<T, K, 1, V7, MIXED>(S, a, X, ldx, Y, ldy, cfg, grid, stream);
 }
 
-template <typename T, bool V7>
+template <typename T, bool V7, bool MIXED = false>
 static int
 spmm_passes(int S, const SpmmArgs & a, int k, const void * X, long ldx, void * Y, long ldy, const LaunchCfg & cfg, unsigned grid,
 		hipStream_t stream)
@@ -339,10 +409,10 @@ spmm_passes(int S, const SpmmArgs & a, int k, const void * X, long ldx, void * Y
 		const int K = spmm_pass_cols(SELL_DELTA_SPMM_COLS, k - j0);
 		const void * Xp = (const T *) X + j0;
 		void * Yp = (T *) Y + j0;
-		const int rc = K == 8 ? spmm_pass<T, 8, V7>(S, a, Xp, ldx, Yp, ldy, cfg, grid, stream)
-		             : K == 4 ? spmm_pass<T, 4, V7>(S, a, Xp, ldx, Yp, ldy, cfg, grid, stream)
-		             : K == 2 ? spmm_pass<T, 2, V7>(S, a, Xp, ldx, Yp, ldy, cfg, grid, stream)
-		                      : spmm_pass<T, 1, V7>(S, a, Xp, ldx, Yp, ldy, cfg, grid, stream);
+		const int rc = K == 8 ? spmm_pass<T, 8, V7, MIXED>(S, a, Xp, ldx, Yp, ldy, cfg, grid, stream)
+		             : K == 4 ? spmm_pass<T, 4, V7, MIXED>(S, a, Xp, ldx, Yp, ldy, cfg, grid, stream)
+		             : K == 2 ? spmm_pass<T, 2, V7, MIXED>(S, a, Xp, ldx, Yp, ldy, cfg, grid, stream)
+		                      : spmm_pass<T, 1, V7, MIXED>(S, a, Xp, ldx, Yp, ldy, cfg, grid, stream);
 		if (rc)
 			return rc;
 		j0 += K;
@@ -351,15 +421,20 @@ spmm_passes(int S, const SpmmArgs & a, int k, const void * X, long ldx, void * Y
 }
 
 int
-launch_sell_delta_spmm(bool f32, int waves_per_slice, bool v7, const int64_t * desc, const unsigned char * idx, const void * val,
+launch_sell_delta_spmm(bool f32, bool val_f32, int waves_per_slice, bool v7, const int64_t * desc, const unsigned char * idx, const void * val,
 		const int * row_of_sorted, int k, const void * X, long ldx, void * Y, long ldy, int m, int num_slices, const LaunchCfg & cfg,
 		hipStream_t stream, long * grid_out)
 {
 	if (k == 1 && ldx == 1 && ldy == 1)            // one contiguous vector: the single-vector kernel itself
-		return launch_sell_delta(f32, waves_per_slice, v7, desc, idx, val, row_of_sorted, X, Y, m, num_slices, cfg, stream, grid_out);
-	if (f32 && v7)
+		return launch_sell_delta(f32, val_f32, waves_per_slice, v7, desc, idx, val, row_of_sorted, X, Y, m, num_slices, cfg, stream, grid_out);
+	if (val_f32 && v7)
 	{
 		set_error("sell_delta_spmm: 7-byte values are fp64 only");
+		return 1;
+	}
+	if (f32 && !val_f32)
+	{
+		set_error("sell_delta_spmm: fp32 vectors over fp64 values are not served");
 		return 1;
 	}
 	const unsigned grid = xcd_grid(cfg.map);
@@ -368,6 +443,8 @@ launch_sell_delta_spmm(bool f32, int waves_per_slice, bool v7, const int64_t * d
 	if (grid == 0)
 		return 0;
 	const SpmmArgs a{desc, idx, val, row_of_sorted, m, num_slices};
+	if (val_f32 && !f32)
+		return spmm_passes<double, false, true>(waves_per_slice, a, k, X, ldx, Y, ldy, cfg, grid, stream);
 	return f32 ? spmm_passes<float, false>(waves_per_slice, a, k, X, ldx, Y, ldy, cfg, grid, stream)
 	     : v7  ? spmm_passes<double, true>(waves_per_slice, a, k, X, ldx, Y, ldy, cfg, grid, stream)
 	           : spmm_passes<double, false>(waves_per_slice, a, k, X, ldx, Y, ldy, cfg, grid, stream);

@@ -66,13 +66,15 @@ int launch_sell(bool f32, int C, const int64_t * slice_ptr, const int * col, con
 
 // SELL-64-sigma with delta-compressed column indices (layout: sell_delta_layout.hpp)
 // v7: the handle holds slices with 7-byte values (SELL_V7_FLAG); launches the kernel variant that looks at the flag
-int launch_sell_delta(bool f32, int waves_per_slice, bool v7, const int64_t * desc, const unsigned char * idx, const void * val, const int * row_of_sorted,
+// f32: x and y are float; val_f32: the value array is float. val_f32 without f32 = fp32 values under fp64 vectors (opts.value_storage):
+// the fp32 handle's arrays, the fp64 kernel's arithmetic (sell_delta_mixed_kernel)
+int launch_sell_delta(bool f32, bool val_f32, int waves_per_slice, bool v7, const int64_t * desc, const unsigned char * idx, const void * val, const int * row_of_sorted,
 		const void * x, void * y, int m, int num_slices, const LaunchCfg & cfg, hipStream_t stream, long * grid_out);
 
 // Y = A X (beta 0) / Y += A X (beta 1) for k vectors on the same layout (kernels_sell_spmm.hip): X holds the cols() rows of k values at
 // X + c * ldx, Y the rows at Y + r * ldy. One launch per pass of 8, 4, 2 or 1 columns (8 per pass, then the binary remainder of k);
 // k == 1 with ldx == ldy == 1 is launch_sell_delta itself. Column j is bit-identical to launch_sell_delta on column j.
-int launch_sell_delta_spmm(bool f32, int waves_per_slice, bool v7, const int64_t * desc, const unsigned char * idx, const void * val,
+int launch_sell_delta_spmm(bool f32, bool val_f32, int waves_per_slice, bool v7, const int64_t * desc, const unsigned char * idx, const void * val,
 		const int * row_of_sorted, int k, const void * X, long ldx, void * Y, long ldy, int m, int num_slices, const LaunchCfg & cfg,
 		hipStream_t stream, long * grid_out);
 // columns of the next pass of a multi-vector product with `remaining` columns left on a layout whose pass serves at most `cap`
@@ -153,7 +155,7 @@ struct SellDeltaArrays {
 	long v7_slices = 0;                    // slices with 7-byte values
 };
 
-// (sell_values: 0 = auto, 1 = on, 2 = off, sell_v7_wanted)
+// (sell_values: 0 = auto, 1 = on, 2 = off, sell_v7_wanted; f32: the values are STORED as float — the handle's val_f32)
 int sell_delta_convert_device(bool f32, long m, long n_cols, long nnz, long sigma, int sell_values, const int * rp_host, const int * ci_host,
 		const double * va_host, SellDeltaArrays & out);
 

@@ -15,13 +15,16 @@ typedef unsigned sell_uint2 __attribute__((ext_vector_type(2)));
 // global_load_dwordx4) instead of four 8-byte ones. The kernel sits at the issue rate of its vector-memory instructions (4 value loads
 // + 4 gathers per group: with the value loads at half the count the nlpkkt240 twin runs 9 % faster on the same bytes,
 // profiles/r03_sell_value_pairs.txt). `vp` = the group's first element + 2 * lane.
-template <typename T, bool NT>
+// S is the type the values are STORED in, T the type the kernel computes in. S = float under T = double (opts.value_storage: fp32
+// values under fp64 vectors) reads the fp32 pair layout, two 8-byte loads per group, and widens the four values (v_cvt_f64_f32,
+// exact); everything behind the reader is the fp64 kernel's.
+template <typename T, bool NT, typename S = T>
 __device__ __forceinline__ void
-sell_group_values(const T * __restrict__ vp, T (&v)[4])
+sell_group_values(const S * __restrict__ vp, T (&v)[4])
 {
-	typedef T T2 __attribute__((ext_vector_type(2)));
-	const T2 w0 = ld_stream<NT>(reinterpret_cast<const T2 *>(vp));
-	const T2 w1 = ld_stream<NT>(reinterpret_cast<const T2 *>(vp + 2 * WAVE));
+	typedef S S2 __attribute__((ext_vector_type(2)));
+	const S2 w0 = ld_stream<NT>(reinterpret_cast<const S2 *>(vp));
+	const S2 w1 = ld_stream<NT>(reinterpret_cast<const S2 *>(vp + 2 * WAVE));
 	v[0] = w0.x;
 	v[1] = w0.y;
 	v[2] = w1.x;
@@ -29,17 +32,17 @@ sell_group_values(const T * __restrict__ vp, T (&v)[4])
 }
 
 // the 1..3 real steps of a slice's last group
-template <typename T, bool NT, int NSTEPS>
+template <typename T, bool NT, int NSTEPS, typename S = T>
 __device__ __forceinline__ void
-sell_tail_values(const T * __restrict__ vp, int lane, T (&v)[3])
+sell_tail_values(const S * __restrict__ vp, int lane, T (&v)[3])
 {
-	typedef T T2 __attribute__((ext_vector_type(2)));
+	typedef S S2 __attribute__((ext_vector_type(2)));
 	v[1] = v[2] = T(0);
 	if (NSTEPS == 1)
 		v[0] = ld_stream<NT>(vp - lane);
 	else
 	{
-		const T2 w0 = ld_stream<NT>(reinterpret_cast<const T2 *>(vp));
+		const S2 w0 = ld_stream<NT>(reinterpret_cast<const S2 *>(vp));
 		v[0] = w0.x;
 		v[1] = w0.y;
 		if (NSTEPS == 3)
@@ -59,19 +62,19 @@ sell_v7_value(unsigned h, unsigned k, unsigned lo)
 // Where a slice's values come from. V7 = false: the pairs above. V7 = true (fp64, sell_values; layout: sell_delta_layout.hpp): a full group is the
 // lane's dwordx4 of low halves and dwordx3 of packed 24-bit high parts — as many load instructions as the pairs, 1792 bytes instead of
 // 2048 — decoded with a few 32-bit VALU operations on the high dwords only; the 1..3-step tail group is stored as pairs, behind the
-// slice's full groups. `vp` = the slice's first value word + 2 * lane either way, `k` = (E0 - 1) << 20.
-template <typename T, bool NT, bool V7>
+// slice's full groups. `vp` = the slice's first value word + 2 * lane either way, `k` = (E0 - 1) << 20. S: the stored type (above).
+template <typename T, bool NT, bool V7, typename S = T>
 struct SellVals {
-	const T * vp;
+	const S * vp;
 	int lane;
 	unsigned k;
 	__device__ __forceinline__ void group(int g, T (&v)[4]) const
 	{
 		if constexpr (!V7)
-			sell_group_values<T, NT>(vp + (size_t) g * 4 * WAVE, v);
+			sell_group_values<T, NT, S>(vp + (size_t) g * 4 * WAVE, v);
 		else
 		{
-			static_assert(sizeof(T) == 8, "7-byte values are fp64 only");
+			static_assert(sizeof(T) == 8 && sizeof(S) == 8, "7-byte values are fp64 only");
 			const unsigned char * b = reinterpret_cast<const unsigned char *>(vp) + (size_t) g * (8 * SELL_V7_GROUP_WORDS);  // lo plane + 16 * lane
 			const sell_uint4 lo = ld_stream<NT>(reinterpret_cast<const sell_uint4 *>(b));
 			const sell_uint3 * hp = reinterpret_cast<const sell_uint3 *>(b + 1024 - 4 * lane);                   // hi plane + 12 * lane
@@ -87,7 +90,7 @@ struct SellVals {
 		}
 	}
 	// the group `g` (= the number of full groups) that holds the slice's 1..3 last steps: vp-relative as sell_tail_values wants it
-	__device__ __forceinline__ const T * tail(int g) const { return vp + (size_t) g * (V7 ? SELL_V7_GROUP_WORDS : 4 * WAVE); }
+	__device__ __forceinline__ const S * tail(int g) const { return vp + (size_t) g * (V7 ? SELL_V7_GROUP_WORDS : 4 * WAVE); }
 };
 
 // Modes 1 and 2 put a dependent load in front of every gather (deltas -> column -> x): their index words are fetched one pair of

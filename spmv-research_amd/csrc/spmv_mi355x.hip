@@ -25,6 +25,8 @@ init_handle(spmv_mi355x_matrix * A, int format, int precision, int device, const
 	A->precision = precision;
 	A->f32 = (precision == SPMV_MI355X_F32);
 	A->vbytes = A->f32 ? 4 : 8;
+	A->val_f32 = A->f32 || o.value_storage == 1;         // fp32 values under fp64 vectors: the SELL delta layout only (value_storage_check)
+	A->val_bytes = A->val_f32 ? 4 : 8;
 	A->device = device;
 	A->placement_level = (o.placement == 1 || o.placement == 3 || o.placement == 4) ? o.placement : 0;      // 0 and 2: off
 	A->placement_budget_gib = o.placement_budget_gib > 0 ? o.placement_budget_gib : 0;
@@ -34,9 +36,33 @@ init_handle(spmv_mi355x_matrix * A, int format, int precision, int device, const
 	A->nnz = nnz;
 	A->csr_mem_footprint = (double) nnz * (A->vbytes + 4) + (double) (m + 1) * 4;
 	A->remap = (o.xcd_remap == 2) ? 0 : (o.xcd_remap == 3) ? 2 : (o.xcd_remap == 1) ? 1 : -1;   // -1 = auto, resolved per kernel
-	const double stream_bytes = (double) nnz * (A->vbytes + 4);
+	const double stream_bytes = (double) nnz * (A->val_bytes + 4);       // what a launch streams: the stored values
 	A->cfg.nt = (o.nontemporal == 1) ? 1 : (o.nontemporal == 2) ? 0 : (stream_bytes > 192.0 * 1024 * 1024 ? 1 : 0);
 	A->cfg.beta = 0;
+}
+
+// opts.value_storage = 1 under fp64 vectors is served by the SELL delta layout alone (include/spmv_mi355x.h "mixed precision"); under
+// fp32 vectors it asks for what the handle stores anyway
+int
+value_storage_check(const char * what, const spmv_mi355x_opts & o, int format, int precision)
+{
+	if (o.value_storage != 0 && o.value_storage != 1)
+	{
+		set_error("%s: value_storage must be 0 (the handle's precision) or 1 (fp32) (got %d)", what, o.value_storage);
+		return 1;
+	}
+	if (o.value_storage == 0 || precision == SPMV_MI355X_F32)
+		return 0;
+	const char * why = format != SPMV_MI355X_SELL_C_SIGMA ? "the format is not SPMV_MI355X_SELL_C_SIGMA"
+	                 : o.sell_window == 1                 ? "sell_window = 1 asks for the LDS-window layout"
+	                 : o.sell_delta == 2                  ? "sell_delta = 2 turns the delta layout off"
+	                 : (o.sell_c != 0 && o.sell_c != 64)  ? "sell_c must be 0 or 64"
+	                 : o.sell_values == 1                 ? "sell_values = 1 asks for 7-byte records, which are fp64 only"
+	                                                      : nullptr;
+	if (!why)
+		return 0;
+	set_error("%s: value_storage = 1 (fp32 values under fp64 vectors) is served by the SELL-C-sigma delta layout only: %s", what, why);
+	return 1;
 }
 
 // the handle's own (zeroed) input vector. No stream of its own here: callers of the device-pointer entry points bring theirs, and with
@@ -125,6 +151,8 @@ spmv_mi355x_create(spmv_mi355x_matrix ** out, int format, int precision, long m,
 		set_error("unknown precision %d", precision);
 		return 1;
 	}
+	if (value_storage_check("create", o, format, precision))
+		return 1;
 	if (m < 0 || n < 0 || nnz < 0 || m >= 0x7fffffffL || n >= 0x7fffffffL || nnz >= 0x7fffffffL || m + nnz >= 0x7fffffffL)
 	{
 		set_error("sizes out of the int32 index range (m=%ld n=%ld nnz=%ld)", m, n, nnz);
@@ -154,7 +182,8 @@ spmv_mi355x_create(spmv_mi355x_matrix ** out, int format, int precision, long m,
 	// ---- symmetric storage in + SELL-C-sigma: the stored triangle itself in the LDS-window layout, when the matrix is banded enough for
 	// a slice group's window of rows and columns to fit LDS (half the matrix stream; kernels_sell_window.hip). Anything else — and every
 	// malformed input, for its error message — goes through the expansion below.
-	if (o.symmetric_input && format == SPMV_MI355X_SELL_C_SIGMA && o.sell_window != 2 && o.sell_delta != 1 && (o.sell_c == 0 || o.sell_c == 64) &&
+	const bool mixed = o.value_storage == 1 && precision == SPMV_MI355X_F64;       // always expands the triangle: the delta layout
+	if (o.symmetric_input && !mixed && format == SPMV_MI355X_SELL_C_SIGMA && o.sell_window != 2 && o.sell_delta != 1 && (o.sell_c == 0 || o.sell_c == 64) &&
 	    o.sell_sigma == 0 && m == n && !o.row_begin && !o.row_end && !o.col_filter_mode && row_ptr[0] == 0 && row_ptr[m] == nnz && nnz >= (1L << 16))
 	{
 		bool ok = true;
@@ -239,6 +268,7 @@ long spmv_mi355x_rows(const spmv_mi355x_matrix * A) { return A->m; }
 long spmv_mi355x_cols(const spmv_mi355x_matrix * A) { return A->n; }
 long spmv_mi355x_nnz(const spmv_mi355x_matrix * A) { return A->nnz; }
 int spmv_mi355x_precision(const spmv_mi355x_matrix * A) { return A->precision; }
+int spmv_mi355x_value_storage(const spmv_mi355x_matrix * A) { return !A ? -1 : A->val_f32 ? SPMV_MI355X_F32 : SPMV_MI355X_F64; }
 int spmv_mi355x_device(const spmv_mi355x_matrix * A) { return A->device; }
 
 int
@@ -301,7 +331,7 @@ spmv_mi355x_spmv_device_async(spmv_mi355x_matrix * A, const void * x, void * y, 
 			     ? launch_sell_window(A->f32, A->sell_split, A->sellw_ns, A->d_sellw_grp, A->d_sell_desc, (const unsigned short *) A->d_sell_idx, A->d_val,
 					A->d_row_of_sorted, x, y, (int) A->m, A->sellw_lds, cfg, st, &grid)
 			     : A->sell_delta
-			     ? launch_sell_delta(A->f32, A->sell_split, A->sell_v7_slices > 0, A->d_sell_desc, A->d_sell_idx, A->d_val, A->d_row_of_sorted, x, y, (int) A->m,
+			     ? launch_sell_delta(A->f32, A->val_f32, A->sell_split, A->sell_v7_slices > 0, A->d_sell_desc, A->d_sell_idx, A->d_val, A->d_row_of_sorted, x, y, (int) A->m,
 					(int) A->sell_slices, cfg, st, &grid)
 			     : launch_sell(A->f32, A->sell_c, A->d_slice_ptr, A->d_col, A->d_val, A->d_row_of_sorted, x, y, (int) A->m,
 					(int) A->sell_slices, cfg, st, &grid);
@@ -434,7 +464,7 @@ spmm_enqueue(spmv_mi355x_matrix * A, int k, const void * X, long ldx, void * Y, 
 		LaunchCfg cfg = A->cfg;
 		cfg.beta = beta ? 1 : 0;
 		long grid = 0;
-		const int rc = launch_sell_delta_spmm(A->f32, A->sell_split, A->sell_v7_slices > 0, A->d_sell_desc, A->d_sell_idx, A->d_val, A->d_row_of_sorted,
+		const int rc = launch_sell_delta_spmm(A->f32, A->val_f32, A->sell_split, A->sell_v7_slices > 0, A->d_sell_desc, A->d_sell_idx, A->d_val, A->d_row_of_sorted,
 				k, X, ldx, Y, ldy, (int) A->m, (int) A->sell_slices, cfg, st, &grid);
 		A->last_grid = grid;
 		return rc;
@@ -647,7 +677,7 @@ spmv_mi355x_stored_array(const spmv_mi355x_matrix * A, const char * name, void *
 		        {"desc", A->d_sell_desc, 2 * ((size_t) A->sell_slices + 1) * 8}, {"row_of_sorted", A->d_row_of_sorted, (size_t) A->m * 4},
 		        {"groups", A->d_sellw_grp, (size_t) A->sellw_groups * 16}};
 	else if (A->format == SPMV_MI355X_SELL_C_SIGMA && A->sell_delta)
-		arrs = {{"val", A->d_val, (size_t) A->sell_val_words * A->vbytes}, {"idx", A->d_sell_idx, (size_t) A->sell_idx_bytes},
+		arrs = {{"val", A->d_val, (size_t) A->sell_val_words * A->val_bytes}, {"idx", A->d_sell_idx, (size_t) A->sell_idx_bytes},
 		        {"desc", A->d_sell_desc, 2 * ((size_t) A->sell_slices + 1) * 8}, {"row_of_sorted", A->d_row_of_sorted, (size_t) A->m * 4}};
 	else if (A->format == SPMV_MI355X_SELL_C_SIGMA)
 		arrs = {{"val", A->d_val, (size_t) A->sell_nnz_ext * A->vbytes}, {"col", A->d_col, (size_t) A->sell_nnz_ext * 4},
@@ -783,7 +813,7 @@ spmv_mi355x_sell_layout(const spmv_mi355x_matrix * A, long * C_out, long * sigma
 		*val_out = (double *) malloc(ne * sizeof(double));
 		const size_t nw = A->sell_delta ? (size_t) A->sell_val_words : (size_t) A->sell_nnz_ext;        // elements stored
 		std::vector<double> raw(std::max<size_t>(nw, 1));
-		if (!A->f32)
+		if (!A->val_f32)
 			HIP_TRY(hipMemcpy(raw.data(), A->d_val, nw * sizeof(double), hipMemcpyDeviceToHost));
 		else
 		{

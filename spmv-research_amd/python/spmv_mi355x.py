@@ -28,7 +28,7 @@ class Opts(C.Structure):
                 ("col_filter_mode", C.c_int), ("sell_delta", C.c_int), ("convert_on", C.c_int),
                 ("symmetric_input", C.c_int), ("rows_per_group", C.c_int), ("col_blocks", C.c_int),
                 ("sell_window", C.c_int), ("kahan", C.c_int), ("sell_group", C.c_int), ("placement", C.c_int),
-                ("placement_budget_gib", C.c_int), ("sell_values", C.c_int)]
+                ("placement_budget_gib", C.c_int), ("sell_values", C.c_int), ("value_storage", C.c_int)]
 
 
 # every symbol declared in include/spmv_mi355x.h (checked by tests/test_abi.py)
@@ -38,7 +38,7 @@ SYMBOLS = [
     "spmv_mi355x_rows", "spmv_mi355x_cols", "spmv_mi355x_nnz", "spmv_mi355x_spmv", "spmv_mi355x_set_always_copy",
     "spmv_mi355x_upload_x", "spmv_mi355x_download_y", "spmv_mi355x_spmv_device_async", "spmv_mi355x_time_device",
     "spmv_mi355x_kernel_info", "spmv_mi355x_x_device", "spmv_mi355x_y_device", "spmv_mi355x_sell_layout", "spmv_mi355x_stored_array",
-    "spmv_mi355x_merge_tiles", "spmv_mi355x_free", "spmv_mi355x_precision", "spmv_mi355x_device",
+    "spmv_mi355x_merge_tiles", "spmv_mi355x_free", "spmv_mi355x_precision", "spmv_mi355x_value_storage", "spmv_mi355x_device",
     "spmv_mi355x_pcg", "spmv_mi355x_pbicgstab", "spmv_mi355x_pcg_dist", "spmv_mi355x_pbicgstab_dist",
     "spmv_mi355x_pcg_multi", "spmv_mi355x_pbicgstab_multi",
     "spmv_mi355x_copy_device_async",
@@ -333,6 +333,8 @@ class Matrix:
         self.format_name = L.spmv_mi355x_format_name(self.h).decode()
         self.mem_footprint = L.spmv_mi355x_mem_footprint(self.h)
         self.csr_mem_footprint = L.spmv_mi355x_csr_mem_footprint(self.h)
+        # what the matrix values are stored as (opts.value_storage); self.dtype stays the precision of x and y
+        self.value_dtype = np.dtype(np.float32 if L.spmv_mi355x_value_storage(self.h) == F32 else np.float64)
 
     # Matrix_Format::spmv(x, y) on host buffers; y gets the driver's +64 slack and 1.0 canary (bench_spmv.cpp:606-609)
     def spmv(self, x, always_copy=True):

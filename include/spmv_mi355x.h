@@ -181,6 +181,46 @@ int  spmv_mi355x_create_from_stream(spmv_mi355x_matrix ** out, spmv_mi355x_csr_s
 		const spmv_mi355x_opts * opts);
 int  spmv_mi355x_csr_stream_discard(spmv_mi355x_csr_stream * s);
 
+/* ---- new values for an existing handle --------------------------------------------------------------------------------- */
+/* Same pattern, new numbers: a Newton / interior-point / time-stepping caller changes the values of its matrix between solves and
+ * never its pattern. update_values rewrites the stored value array in place and keeps everything create() derived from the pattern
+ * (row sort, index encodings, LDS-window groups, tile maps, the uploaded column indices, the placement of the arrays).
+ * THE CONTRACT: a handle created from (pattern, V1, opts) and updated with V2 is indistinguishable from one freshly created from
+ * (pattern, V2, opts): every array spmv_mi355x_stored_array exposes is byte-identical, format_name / mem_footprint / sell_layout /
+ * kernel_info / spmm_plan answer the same, and spmv, spmm and the solvers give the same bits on every deterministic layout.
+ *   - values: nnz() fp64 values, values[e] belonging to entry e of the handle's LOCAL CSR (for a row block created with
+ *     opts.row_begin / row_end: that contiguous stretch of the caller's array), narrowed to the handle's value storage as create()
+ *     narrows them (fp32 for an F32 handle and for value_storage = 1). NaN and Inf pass through, as in create().
+ *   - prepare, once per handle before the first update: row_ptr = the local row pointer the handle was built from (host, rows() + 1
+ *     entries from 0). It is checked (starts at 0, monotone, ends at nnz(); SELL layouts: every slice's stored width against the
+ *     longest of its rows — a mismatch is "row_ptr does not match the pattern this handle was built from") and a device copy is kept
+ *     (4 * (rows() + 1) bytes, not counted in mem_footprint(), freed at destroy). THE COLUMNS CANNOT BE VERIFIED: values passed in the
+ *     order of another pattern with the same row lengths are stored as given. CSR-ordered layouts need no map, but prepare is required
+ *     all the same (one protocol). Calling it again replaces the copy.
+ *   - update_values_device orders its work on hip_stream behind what is enqueued there and WAITS for it (blocking, as every entry
+ *     without _async): with 7-byte values the host-side counts of the handle change. update_values is the same through a transient
+ *     device copy of the host array.
+ *   - what create() chooses from the values is chosen again: the slices of a delta handle that store 7-byte values (sell_values on, or
+ *     auto on a large matrix), with the value offsets, descriptors, tile map, footprint, nontemporal rule and the _v7 suffix that follow
+ *     (the value array is reallocated when the new selection needs more room); and the merge path's dropping of a uniform value
+ *     stream: a merge handle updated with uniform values becomes the _unit handle create() would build — and, like it, takes no
+ *     further update.
+ *   - kept: the handle's x / y device buffers and its cached-x state, its spmm scratch, arrays moved by placement level 3 (they are
+ *     written where they live). The next host-buffer spmv downloads y again.
+ *   - rc 1, a last_error naming update_values, the handle untouched: a NULL handle or pointer; update before prepare; a handle created
+ *     with a column filter (col_filter_mode != 0: its entries are a subset of the caller's) or with symmetric_input = 1 (expanded or
+ *     kept as a triangle: its entries are not the caller's); the column-blocked layout (col_blocks != 0: entries sorted by column); a
+ *     handle without a value stream (the _unit layouts of uniform values). spmv_mi355x_partitioned handles have no such entry (their
+ *     parts carry column filters).
+ *   - update_values_state, host-only: 0 = this handle cannot be updated (last_error says why), 1 = it can, prepare is still missing,
+ *     2 = ready. NULL: 0.
+ * SPMV_MI355X_UPDATE_STAGE = 0 makes the SELL kernels read every row straight from global memory instead of staging a slice's
+ * contiguous stretch of the CSR array through LDS. */
+int  spmv_mi355x_update_values_prepare(spmv_mi355x_matrix * A, const int32_t * row_ptr);
+int  spmv_mi355x_update_values(spmv_mi355x_matrix * A, const double * values_fp64_host);
+int  spmv_mi355x_update_values_device(spmv_mi355x_matrix * A, const double * values_fp64_dev, void * hip_stream);
+int  spmv_mi355x_update_values_state(const spmv_mi355x_matrix * A);
+
 /* ---- Matrix_Format::spmv(x, y) with HOST buffers --------------------------------------------------------- */
 /* Reference GPU-backend semantics (GPU_clean/csr_rocm_vector.cpp:224-257): x is uploaded when the host
  * pointer is new (or always_copy is set), one launch + device sync, y is downloaded on the first call (or when

@@ -179,7 +179,7 @@ sell_delta_install(spmv_mi355x_matrix * A, const SellDeltaArrays & r)
 
 // format name, kernel name and nontemporal rule of a delta handle
 static void
-sell_delta_names(spmv_mi355x_matrix * A, const spmv_mi355x_opts & o)
+sell_delta_names(spmv_mi355x_matrix * A)
 {
 	const char * pf = A->f32 ? "f" : "d";
 	const char * v7 = A->sell_v7_slices ? "_v7" : A->mixed() ? "_v4" : "";      // _v4: fp32 values under fp64 vectors (opts.value_storage)
@@ -188,8 +188,19 @@ sell_delta_names(spmv_mi355x_matrix * A, const spmv_mi355x_opts & o)
 	else
 		snprintf(A->format_name, sizeof(A->format_name), "MI355X_SELLD_%d_%ld_%s%s", A->sell_c, A->sell_sigma, pf, v7);
 	snprintf(A->kernel_name, sizeof(A->kernel_name), A->mixed() ? "sell_delta_mixed_kernel" : "sell_delta_kernel");
-	if (A->sell_v7_slices && o.nontemporal == 0)
-		A->cfg.nt = A->mem_footprint > 192.0 * 1024 * 1024 ? 1 : 0;      // the auto rule of init_handle on the bytes really stored
+	// the auto rule of init_handle on the bytes really stored; without 7-byte slices init_handle's own answer (an update of the values
+	// can take the last 7-byte slice away)
+	A->cfg.nt = (A->sell_v7_slices && A->opt_nontemporal == 0) ? (A->mem_footprint > 192.0 * 1024 * 1024 ? 1 : 0) : A->nt_init;
+}
+
+// spmv_mi355x_update_values re-made the 7-byte selection: everything create() derives from the value offsets
+void
+sell_delta_values_changed(spmv_mi355x_matrix * A, const int64_t * val_ptr, long v7_slices)
+{
+	A->sell_v7_slices = v7_slices;
+	A->sell_val_words = val_ptr[A->sell_slices];
+	sell_delta_map(A, val_ptr);
+	sell_delta_names(A);
 }
 
 // SELL-64-sigma-delta build (layout: sell_delta_layout.hpp). Same sigma-window sort and slice widths as build_sell with C = 64,
@@ -743,7 +754,8 @@ build_sell_family(spmv_mi355x_matrix * A, const spmv_mi355x_opts & o, const int 
 	if (A->sell_delta)
 	{
 		rc = build_sell_delta(A, sell_values_env(o.sell_values), rp, ci, va);
-		sell_delta_names(A, o);
+		A->sell_v7_active = !rc && sell_v7_wanted(A->val_f32, sell_values_env(o.sell_values), A->sell_nnz_ext);
+		sell_delta_names(A);
 		return rc;
 	}
 	snprintf(A->format_name, sizeof(A->format_name), "MI355X_SELL_%d_%ld_%s", C, sigma, pf);
@@ -787,7 +799,8 @@ build_sell_delta_resident(spmv_mi355x_matrix * A, const spmv_mi355x_opts & o, co
 	if (sell_delta_convert_resident(A->val_f32, m, A->n, A->nnz, sigma, sell_values_env(o.sell_values), d_rp, d_ci, d_va, r))
 		return 1;
 	sell_delta_install(A, r);
-	sell_delta_names(A, o);
+	A->sell_v7_active = sell_v7_wanted(A->val_f32, sell_values_env(o.sell_values), A->sell_nnz_ext);
+	sell_delta_names(A);
 	return 0;
 }
 

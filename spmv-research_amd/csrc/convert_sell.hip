@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "launch.hpp"
+#include "sell_values_device.hpp"
 
 namespace spmv {
 
@@ -39,22 +40,6 @@ window_offsets_kernel(long m, long sigma, long num_windows, int * __restrict__ o
 	const long w = (long) blockIdx.x * CV_BLOCK + threadIdx.x;
 	if (w <= num_windows)
 		off[w] = (int) (w * sigma < m ? w * sigma : m);
-}
-
-__device__ __forceinline__ int
-wave_min_i(int v)
-{
-	for (int o = WAVE / 2; o > 0; o >>= 1)
-		v = min(v, __shfl_xor(v, o, WAVE));
-	return v;
-}
-
-__device__ __forceinline__ int
-wave_max_i(int v)
-{
-	for (int o = WAVE / 2; o > 0; o >>= 1)
-		v = max(v, __shfl_xor(v, o, WAVE));
-	return v;
 }
 
 // Mode 5 (sell_delta_layout.hpp): every lane of a slice of equally long rows gets the offset off = its first column - the reference lane's
@@ -172,31 +157,15 @@ slice_v7_kernel(const int * __restrict__ rp, const double * __restrict__ va, con
 	const int lane = threadIdx.x % WAVE;
 	if (sl >= num_slices)
 		return;
-	const long i = sl * WAVE + lane;
-	int start = 0, len = 0;
-	if (i < m)
-	{
-		const int o = row_of_sorted[i];
-		start = rp[o];
-		len = rp[o + 1] - start;
-	}
+	int start, len;
+	sell_lane_row(rp, row_of_sorted, m, sl, lane, start, len);
 	const int maxlen = wave_max_i(len);
-	const int full = maxlen / 4;
-	SellV7Range r;                                      // padding entries are 0.0: exponent 0, always fit
-	for (int k = 0; k < min(len, 4 * full); k++)
-		r.add(__double_as_longlong(va[start + k]));
-	const int lo = wave_min_i(r.lo), hi = wave_max_i(r.hi);
-	const bool bad = __ballot(r.bad) != 0ull;
-	SellV7Range w;
-	w.lo = lo;
-	w.hi = hi;
-	w.bad = bad;
+	const int e0 = sell_v7_select(va, start, len, maxlen);
 	if (lane == 0)
 	{
-		const bool take = full > 0 && w.ok();
-		v7_e0[sl] = take ? w.e0() : 0;
-		if (take)
-			val_count[sl] = sell_slice_val_words(maxlen, full);
+		v7_e0[sl] = e0;
+		if (e0)
+			val_count[sl] = sell_slice_val_words(maxlen, maxlen / 4);
 	}
 }
 
@@ -312,20 +281,8 @@ slice_fill_kernel(const int * __restrict__ rp, const int * __restrict__ ci, cons
 		}
 		if (g < full)
 		{
-			// a 7-byte group: the lane's four low dwords, then its four 24-bit high parts packed into three dwords
-			unsigned char * b = reinterpret_cast<unsigned char *>(val + vb) + (size_t) g * (8 * SELL_V7_GROUP_WORDS);
-			unsigned h[4], w[3];
-			#pragma unroll
-			for (int u = 0; u < 4; u++)
-			{
-				reinterpret_cast<unsigned *>(b + sell_v7_lo_pos(u, lane))[0] = (unsigned) vbits[u];
-				h[u] = sell_v7_encode_hi(vbits[u], e0);
-			}
-			sell_v7_pack_hi(h, w);
-			unsigned * hp = reinterpret_cast<unsigned *>(b + sell_v7_hi_bit(0, lane) / 8);
-			hp[0] = w[0];
-			hp[1] = w[1];
-			hp[2] = w[2];
+			// a 7-byte group (sell_values_device.hpp)
+			sell_v7_store_group(reinterpret_cast<unsigned char *>(val + vb) + (size_t) g * (8 * SELL_V7_GROUP_WORDS), lane, vbits, e0);
 		}
 		if (md == 5)
 		{

@@ -97,6 +97,16 @@ struct spmv_mi355x_matrix {
 	bool always_copy = false;
 	hipStream_t stream = nullptr;
 
+	// new values for an existing handle (update_values.hip). Facts of create() that decide whether the stored value array is the local
+	// CSR's values at positions the pattern alone fixes, and what prepare() keeps.
+	int upd_col_filter = 0;                // opts.col_filter_mode: the caller's entries are not the handle's
+	int upd_symmetric = 0;                 // opts.symmetric_input: expanded (entries doubled and re-sorted) or kept as a triangle
+	int opt_nontemporal = 0;               // opts.nontemporal and what init_handle made of it: the delta layout's nt rule looks at the
+	int nt_init = 0;                       //   bytes really stored once 7-byte slices exist (sell_delta_names)
+	bool sell_v7_active = false;           // the delta handle re-selects its 7-byte slices from the values (sell_v7_wanted at create)
+	int * d_upd_row_ptr = nullptr;         // prepare(): device copy of the local row pointer (m + 1); not in mem_footprint
+	size_t val_capacity = 0;               // bytes of the allocation behind d_val, as of prepare() / the last reallocation
+
 	double mem_footprint = 0, csr_mem_footprint = 0;
 	char format_name[96] = "";
 	char kernel_name[64] = "";
@@ -108,6 +118,8 @@ namespace spmv {
 
 // ---- device memory helpers (handle.hip)
 int dev_alloc_bytes(void ** p, size_t bytes);
+// update_values.hip -> build_sell.hip: the host-side counts of a delta handle whose 7-byte selection was re-made (slices + 1 value offsets)
+void sell_delta_values_changed(spmv_mi355x_matrix * A, const int64_t * val_ptr, long v7_slices);
 int build_sell_delta_resident(spmv_mi355x_matrix * A, const spmv_mi355x_opts & o, const int * d_rp, const int * d_ci, const double * d_va);   // build_sell.hip
 void init_handle(spmv_mi355x_matrix * A, int format, int precision, int device, const spmv_mi355x_opts & o, long m, long n, long nnz);   // spmv_mi355x.hip
 // opts.value_storage against format, precision and the layout options: 0 = fine, 1 = error set (spmv_mi355x.hip; touches no device)

@@ -39,6 +39,10 @@ init_handle(spmv_mi355x_matrix * A, int format, int precision, int device, const
 	const double stream_bytes = (double) nnz * (A->val_bytes + 4);       // what a launch streams: the stored values
 	A->cfg.nt = (o.nontemporal == 1) ? 1 : (o.nontemporal == 2) ? 0 : (stream_bytes > 192.0 * 1024 * 1024 ? 1 : 0);
 	A->cfg.beta = 0;
+	A->nt_init = A->cfg.nt;                // what spmv_mi355x_update_values needs to know of this create()
+	A->opt_nontemporal = o.nontemporal;
+	A->upd_col_filter = (o.col_filter_mode == 1 || o.col_filter_mode == 2) ? o.col_filter_mode : 0;
+	A->upd_symmetric = o.symmetric_input ? 1 : 0;
 }
 
 // opts.value_storage = 1 under fp64 vectors is served by the SELL delta layout alone (include/spmv_mi355x.h "mixed precision"); under

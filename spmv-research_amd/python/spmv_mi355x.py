@@ -49,6 +49,7 @@ SYMBOLS = [
     "spmv_mi355x_upload_y", "spmv_mi355x_output_alloc", "spmv_mi355x_input_alloc", "spmv_mi355x_output_free", "spmv_mi355x_placement_release", "spmv_mi355x_placement_info", "spmv_mi355x_place_arrays",
     "spmv_mi355x_csr_stream_begin", "spmv_mi355x_csr_stream_append", "spmv_mi355x_create_from_stream", "spmv_mi355x_csr_stream_discard",
     "spmv_mi355x_spmm_device_async", "spmv_mi355x_time_spmm_device", "spmv_mi355x_spmm", "spmv_mi355x_spmm_plan",
+    "spmv_mi355x_update_values_prepare", "spmv_mi355x_update_values", "spmv_mi355x_update_values_device", "spmv_mi355x_update_values_state",
 ]
 
 _lib = None
@@ -392,6 +393,32 @@ class Matrix:
         _check(lib().spmv_mi355x_time_spmm_device(self.h, C.c_int(k), C.c_void_p(x_ptr), C.c_long(ldx), C.c_void_p(y_ptr), C.c_long(ldy),
                                                   C.c_int(iters), C.c_void_p(stream), C.byref(ms)))
         return ms.value
+
+    # ---- new values for an existing handle (include/spmv_mi355x.h): same pattern, new numbers
+    def update_values_prepare(self, row_ptr):
+        """Once per handle before the first update: the LOCAL row pointer the handle was built from (rows + 1 entries from 0)."""
+        row_ptr = np.ascontiguousarray(row_ptr, np.int32)
+        if row_ptr.shape != (self.m + 1,):
+            raise ValueError(f"row_ptr must have {self.m + 1} entries, got {row_ptr.shape}")
+        _check(lib().spmv_mi355x_update_values_prepare(self.h, _p(row_ptr)))
+
+    def update_values(self, values):
+        """Replace the stored values by nnz fp64 values in the order of the handle's local CSR (spmv_mi355x_update_values); what
+        create() derives from the values (format_name, mem_footprint) is refreshed."""
+        values = np.ascontiguousarray(values, np.float64)
+        if values.shape != (self.nnz,):
+            raise ValueError(f"values must have {self.nnz} entries, got {values.shape}")
+        _check(lib().spmv_mi355x_update_values(self.h, _p(values)))
+        self._describe()
+
+    def update_values_device(self, ptr, stream=0):
+        """The same from nnz fp64 values resident on the handle's device, ordered on `stream`; blocking."""
+        _check(lib().spmv_mi355x_update_values_device(self.h, C.c_void_p(ptr), C.c_void_p(stream)))
+        self._describe()
+
+    def update_values_state(self):
+        """0 = this handle cannot be updated (spmv_mi355x_last_error says why), 1 = prepare is still missing, 2 = ready."""
+        return lib().spmv_mi355x_update_values_state(self.h)
 
     def kernel_info(self):
         name = C.create_string_buffer(128)

@@ -116,6 +116,9 @@ typedef struct {
 	                           exceeds the 256 MiB Infinity Cache), 1 = on, 2 = off. SPMV_MI355X_SELL_VALUES in the environment overrides */
 	int  value_storage;     /* how the matrix VALUES are stored, independent of the precision of x and y:
 	                           0 = in the handle's precision (default), 1 = fp32. See "mixed precision" below.                  */
+	int  transpose;         /* 0 = a handle of A (default), 1 = a handle of A^t, transposed on the GPU from the CSR of A. See "transposed
+	                           handles" below. (The field took the struct's tail padding: sizeof did not change, and a caller that
+	                           zero-initialises as asked above has 0 here.)                                                       */
 } spmv_mi355x_opts;
 
 /* ---- mixed precision: fp64 vectors over fp32-stored values (opts.value_storage = 1) ------------------------------------- */
@@ -141,6 +144,36 @@ typedef struct {
  *   - the solvers (pcg, pbicgstab, their _multi forms) run on a mixed handle unchanged, with fp64 vectors.
  * A caller whose struct_size ends before the field gets value_storage = 0. */
 
+/* ---- transposed handles: y = A^t x from the CSR of A (opts.transpose = 1) ------------------------------------------------------- */
+/* Callers that need both products (A D A^t of interior-point steps, CGLS / LSQR, BiCG / QMR, restriction with R = P^t) create a second
+ * handle with transpose = 1 from the same arrays: spmv_mi355x_create(m, n, nnz, row_ptr, col_idx, values) and
+ * spmv_mi355x_create_from_stream then build a handle of A^t: rows() is n, cols() is m, x has m values and y has n. The CSR is
+ * transposed in device memory (csrc/transpose_csr.hip) and the handle is built in A^t's own best layout, so every kernel, spmm, the
+ * solvers, the 7-byte and fp32 value stores and placement serve it unchanged and deterministically. There is no y = A^t x over the
+ * layout of A: that would be one scattered fp64 atomic per entry (profiles/r01_atomic_bench.txt) and not reproducible.
+ * THE CONTRACT: a handle built from (A, opts with transpose = 1) is indistinguishable from the handle create() builds from the CSR of
+ * A^t with transpose = 0 and otherwise equal opts, where that CSR has the rows of A^t in order, inside a row its entries in ascending
+ * row of A, and entries of equal (row, column) in their input order (a stable counting sort by column). Indistinguishable: every array
+ * of spmv_mi355x_stored_array is byte-identical, format_name (no suffix) / mem_footprint / csr_mem_footprint / nnz / sell_layout /
+ * kernel_info / spmm_plan answer the same, and spmv, spmm and the solvers give the same bits on every deterministic layout.
+ * spmv_mi355x_transposed() tells the two apart.
+ *   - order of the input stage: the caller's arrays are validated as they are (row_ptr monotone, columns in [0, n), the int32 limits
+ *     — same messages — plus n + nnz < 2^31 for the transposed shape), then transposed; EVERY other option sees the n x m matrix A^t:
+ *     row_begin / row_end are rows of A^t, the column filter bounds are columns of A^t, and the automatic layout choices (LDS window,
+ *     7-byte values, nontemporal) are made on A^t. convert_on = 2 transposes on the host (the checker of the GPU routine; same bytes).
+ *   - create() uploads the CSR, transposes it on the device and downloads the result (12 bytes per non-zero each way) so that the row
+ *     block, the column filter and every format's builder run from one local CSR; create_from_stream transposes the resident arrays
+ *     and nothing passes through the host. Transient device memory: 16 bytes per non-zero + the sort's scratch, next to the CSR of
+ *     A^t (12 bytes per non-zero); all of it is freed before the format is built (the stream's own arrays too).
+ *   - rc 1 with a last_error that names transpose, before any device is touched: a value other than 0 or 1; transpose = 1 with
+ *     symmetric_input = 1 (the transpose of a symmetric matrix is the matrix itself); spmv_mi355x_create_partitioned with
+ *     transpose = 1 (its parts would each transpose the whole matrix).
+ *   - update_values_prepare / update_values / update_values_device refuse a transposed handle (rc 1, update_values_state 0): its
+ *     entries are not in the caller's order. Carrying the entry permutation is left to a later change.
+ *   - the solvers read the Jacobi diagonal from the host CSR they are given: on a transposed handle pass the CSR create() was given
+ *     (that of A) — the diagonal of A^t is that of A.
+ * A caller whose struct_size ends before the field gets transpose = 0. */
+
 /* ---- library / device ------------------------------------------------------------------------------------ */
 const char * spmv_mi355x_last_error(void);
 int  spmv_mi355x_device_count(int * count_out);
@@ -163,6 +196,7 @@ long   spmv_mi355x_nnz(const spmv_mi355x_matrix * A);                /* local no
 int    spmv_mi355x_precision(const spmv_mi355x_matrix * A);          /* SPMV_MI355X_F64 / SPMV_MI355X_F32 of x and y */
 int    spmv_mi355x_value_storage(const spmv_mi355x_matrix * A);      /* ... of the stored values (opts.value_storage); NULL: -1 */
 int    spmv_mi355x_device(const spmv_mi355x_matrix * A);             /* HIP device ordinal the handle lives on      */
+int    spmv_mi355x_transposed(const spmv_mi355x_matrix * A);         /* 1 = built with opts.transpose = 1, else 0; NULL: -1 */
 
 /* ---- a handle from a CSR that arrives in pieces ---------------------------------------------------------------------- */
 /* spmv_mi355x_create() needs the whole CSR in host memory at once. A caller that generates or reads its rows piece by piece (a rank
@@ -208,7 +242,8 @@ int  spmv_mi355x_csr_stream_discard(spmv_mi355x_csr_stream * s);
  *   - kept: the handle's x / y device buffers and its cached-x state, its spmm scratch, arrays moved by placement level 3 (they are
  *     written where they live). The next host-buffer spmv downloads y again.
  *   - rc 1, a last_error naming update_values, the handle untouched: a NULL handle or pointer; update before prepare; a handle created
- *     with a column filter (col_filter_mode != 0: its entries are a subset of the caller's) or with symmetric_input = 1 (expanded or
+ *     with opts.transpose = 1 (its entries are not in the caller's order), with a column filter (col_filter_mode != 0: its entries
+ *     are a subset of the caller's) or with symmetric_input = 1 (expanded or
  *     kept as a triangle: its entries are not the caller's); the column-blocked layout (col_blocks != 0: entries sorted by column); a
  *     handle without a value stream (the _unit layouts of uniform values). spmv_mi355x_partitioned handles have no such entry (their
  *     parts carry column filters).

@@ -34,6 +34,42 @@ prepare_local_csr(const spmv_mi355x_opts & o, long m, long n, long nnz, const in
 		set_error("row_ptr[m]-row_ptr[0] = %ld does not match nnz = %ld", (long) row_ptr[m] - row_ptr[0], nnz);
 		return 1;
 	}
+	out.n = n;
+	// ---- transposition (opts.transpose) comes first: the caller's arrays are checked as they are, then every later stage — row block,
+	// column filter, the builders with all their automatic choices — sees the n x m matrix A^t. On the device (transpose_csr.hip), or on
+	// the host where the host builders are asked for (convert_on = 2: the checker; same bytes).
+	if (o.transpose == 1)
+	{
+		long bad = -1;
+		const int32_t * ci0 = col_idx + row_ptr[0];
+		#pragma omp parallel for num_threads(spmv::host_threads()) reduction(max : bad)
+		for (long j = 0; j < nnz; j++)
+			if (ci0[j] < 0 || ci0[j] >= n)
+				bad = std::max(bad, j);
+		if (bad >= 0)
+		{
+			set_error("column index %d out of range [0,%ld) at entry %ld", ci0[bad], n, bad);
+			return 1;
+		}
+		std::vector<int> rp0;
+		if (row_ptr[0] != 0)
+		{
+			rp0.resize((size_t) m + 1);
+			for (long i = 0; i <= m; i++)
+				rp0[(size_t) i] = row_ptr[i] - row_ptr[0];
+		}
+		const int32_t * rp_in = rp0.empty() ? row_ptr : rp0.data();
+		const double * va0 = values + row_ptr[0];
+		if (o.convert_on == 2 || getenv("SPMV_MI355X_HOST_CONVERT"))
+			transpose_csr_host(m, n, nnz, rp_in, ci0, va0, out.t_rp, out.t_ci, out.t_va);
+		else if (transpose_csr_upload(m, n, nnz, rp_in, ci0, va0, out.t_rp, out.t_ci, out.t_va))
+			return 1;
+		row_ptr = out.t_rp.data();
+		col_idx = out.t_ci.data();
+		values = out.t_va.data();
+		std::swap(m, n);
+		out.n = n;
+	}
 	// ---- symmetric storage in (KEEP_SYMMETRY builds of the harness; csr_sym.cpp:118-123 accepts exactly this): the arrays
 	// hold ONE triangle; the product is y = (T + T^t - diag(T)) x, every stored off-diagonal (i, j, a) also acting as
 	// (j, i, +a) — csr_sym.cpp:204-232, bench_spmv.cpp:135-148. The engine expands it and runs its general kernels:

@@ -179,6 +179,8 @@ spmv_mi355x_create_from_stream(spmv_mi355x_matrix ** out, spmv_mi355x_csr_stream
 	}
 	else if (value_storage_check("create_from_stream", o, format, precision))
 		rc = 1;
+	else if (transpose_check("create_from_stream", o, s->n, s->nnz_done))
+		rc = 1;
 	else if (s->rows_done != s->m)
 	{
 		set_error("create_from_stream: %ld of %ld rows were appended", s->rows_done, s->m);
@@ -195,9 +197,31 @@ spmv_mi355x_create_from_stream(spmv_mi355x_matrix ** out, spmv_mi355x_csr_stream
 		return 1;
 	}
 	spmv_mi355x_matrix * A = new spmv_mi355x_matrix();
-	init_handle(A, format, precision, s->device, o, s->m, s->n, s->nnz_done);
-	rc = build_sell_delta_resident(A, o, s->d_rp, s->d_ci, s->d_va);
-	stream_free(s);
+	if (o.transpose == 1)
+	{
+		// the resident arrays transposed where they are (transpose_csr.hip); the stream's own arrays go before the builder allocates its,
+		// and the handle is that of the n x m matrix A^t. Nothing passes through the host.
+		int * d_rp_t = nullptr, * d_ci_t = nullptr;
+		double * d_va_t = nullptr;
+		const int device = s->device;
+		const long m = s->m, n = s->n, nnz = s->nnz_done;
+		rc = transpose_csr_device(m, n, nnz, s->d_rp, s->d_ci, s->d_va, &d_rp_t, &d_ci_t, &d_va_t);
+		stream_free(s);
+		if (!rc)
+		{
+			init_handle(A, format, precision, device, o, n, m, nnz);
+			rc = build_sell_delta_resident(A, o, d_rp_t, d_ci_t, d_va_t);
+		}
+		for (void * p : {(void *) d_rp_t, (void *) d_ci_t, (void *) d_va_t})
+			if (p)
+				(void) hipFree(p);
+	}
+	else
+	{
+		init_handle(A, format, precision, s->device, o, s->m, s->n, s->nnz_done);
+		rc = build_sell_delta_resident(A, o, s->d_rp, s->d_ci, s->d_va);
+		stream_free(s);
+	}
 	if (rc)
 	{
 		free_all(A);

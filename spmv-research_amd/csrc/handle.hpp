@@ -18,6 +18,7 @@ struct spmv_mi355x_matrix {
 	int format = 0, precision = 0;
 	long m = 0, n = 0, nnz = 0;            // local rows, columns, local non-zeros
 	int device = 0;
+	int transposed = 0;                    // opts.transpose: the handle holds A^t of the CSR create() was given (m, n are those of A^t)
 	// Two precisions (opts.value_storage): that of the VECTORS — x, y, scratch columns, solver state, host transfers, the type the
 	// kernels compute in — and that of the stored VALUE array. Only the SELL delta layout may hold fp32 values under fp64 vectors
 	// (mixed()); every other layout keeps both equal.
@@ -124,6 +125,17 @@ int build_sell_delta_resident(spmv_mi355x_matrix * A, const spmv_mi355x_opts & o
 void init_handle(spmv_mi355x_matrix * A, int format, int precision, int device, const spmv_mi355x_opts & o, long m, long n, long nnz);   // spmv_mi355x.hip
 // opts.value_storage against format, precision and the layout options: 0 = fine, 1 = error set (spmv_mi355x.hip; touches no device)
 int value_storage_check(const char * what, const spmv_mi355x_opts & o, int format, int precision);
+// opts.transpose against its range, symmetric_input and the sizes of the transposed shape: 0 = fine, 1 = error set (touches no device)
+int transpose_check(const char * what, const spmv_mi355x_opts & o, long n, long nnz);
+// CSR of A (m x n) -> CSR of A^t, rows in order, entries of a row in ascending row of A, duplicates in input order (transpose_csr.hip):
+// on a device-resident CSR (outputs are device allocations the caller frees), through an upload and a download for create(), and on
+// the host as the checker of both (opts.convert_on = 2; same bytes)
+int transpose_csr_device(long m, long n, long nnz, const int * d_rp, const int * d_ci, const double * d_va, int ** d_rp_t_out, int ** d_ci_t_out,
+		double ** d_va_t_out);
+int transpose_csr_upload(long m, long n, long nnz, const int * rp, const int * ci, const double * va, std::vector<int> & rp_t, std::vector<int> & ci_t,
+		std::vector<double> & va_t);
+void transpose_csr_host(long m, long n, long nnz, const int * rp, const int * ci, const double * va, std::vector<int> & rp_t, std::vector<int> & ci_t,
+		std::vector<double> & va_t);
 int ensure_x(spmv_mi355x_matrix * A);                                    // spmv_mi355x.hip: stream + the handle's own (zeroed) x
 int tune_placement(spmv_mi355x_matrix * A);                              // placement.hip: allocates the handle's y (and re-homes its x) in the device's vector pools
 int place_vector(spmv_mi355x_matrix * A, void ** out, size_t bytes, bool is_output);   // placement.hip: a zero-filled vector A's SpMV writes / reads
@@ -146,6 +158,8 @@ bool values_uniform(const spmv_mi355x_matrix * A, const double * va, long nnz, d
 
 // ---- input stage of create() (build_input.hip): what csr_to_format() receives -> the local CSR a format is built from
 struct LocalCsr {
+	std::vector<int> t_rp, t_ci;          // transposition (opts.transpose): the CSR of A^t, which every later stage sees
+	std::vector<double> t_va;
 	std::vector<int> e_rp, e_ci;          // symmetric expansion (opts.symmetric_input)
 	std::vector<double> e_va;
 	std::vector<int> l_rp, l_ci;          // row block / column filter copy
@@ -154,6 +168,7 @@ struct LocalCsr {
 	const int * ci = nullptr;
 	const double * va = nullptr;
 	long m = 0, nnz = 0;
+	long n = 0;                           // columns: n of create(), or m with opts.transpose
 };
 int prepare_local_csr(const spmv_mi355x_opts & o, long m, long n, long nnz, const int32_t * row_ptr, const int32_t * col_idx,
 		const double * values, LocalCsr & out);

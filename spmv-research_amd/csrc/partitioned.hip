@@ -273,6 +273,12 @@ spmv_mi355x_create_partitioned(spmv_mi355x_partitioned ** out, int nparts, const
 		set_error("create_partitioned: symmetric_input / row blocks / column filters are set by the partition itself");
 		return 1;
 	}
+	if (o.transpose != 0)
+	{
+		set_error("create_partitioned: transpose = %d: a partitioned handle is not built transposed (every part would transpose the whole matrix); "
+		          "transpose the CSR and partition that", o.transpose);
+		return 1;
+	}
 	int ndev = 0;
 	spmv_mi355x_device_count(&ndev);
 	if (ndev < 1)

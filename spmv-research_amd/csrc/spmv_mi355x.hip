@@ -28,6 +28,7 @@ init_handle(spmv_mi355x_matrix * A, int format, int precision, int device, const
 	A->val_f32 = A->f32 || o.value_storage == 1;         // fp32 values under fp64 vectors: the SELL delta layout only (value_storage_check)
 	A->val_bytes = A->val_f32 ? 4 : 8;
 	A->device = device;
+	A->transposed = o.transpose == 1 ? 1 : 0;            // the callers pass the sizes of A^t
 	A->placement_level = (o.placement == 1 || o.placement == 3 || o.placement == 4) ? o.placement : 0;      // 0 and 2: off
 	A->placement_budget_gib = o.placement_budget_gib > 0 ? o.placement_budget_gib : 0;
 	A->convert_on_device = o.convert_on != 2 && !getenv("SPMV_MI355X_HOST_CONVERT");      // layouts with a GPU builder: SELL delta, SELL window, column-blocked
@@ -67,6 +68,30 @@ value_storage_check(const char * what, const spmv_mi355x_opts & o, int format, i
 		return 0;
 	set_error("%s: value_storage = 1 (fp32 values under fp64 vectors) is served by the SELL-C-sigma delta layout only: %s", what, why);
 	return 1;
+}
+
+// opts.transpose (include/spmv_mi355x.h "transposed handles"): what can be refused from the arguments alone
+int
+transpose_check(const char * what, const spmv_mi355x_opts & o, long n, long nnz)
+{
+	if (o.transpose != 0 && o.transpose != 1)
+	{
+		set_error("%s: transpose must be 0 (a handle of A) or 1 (a handle of A^t) (got %d)", what, o.transpose);
+		return 1;
+	}
+	if (o.transpose == 0)
+		return 0;
+	if (o.symmetric_input)
+	{
+		set_error("%s: transpose = 1 with symmetric_input = 1: the transpose of a symmetric matrix is the matrix itself, create it with transpose = 0", what);
+		return 1;
+	}
+	if (n + nnz >= 0x7fffffffL)
+	{
+		set_error("%s: transpose = 1: sizes of the transposed matrix out of the int32 index range (n=%ld nnz=%ld)", what, n, nnz);
+		return 1;
+	}
+	return 0;
 }
 
 // the handle's own (zeroed) input vector. No stream of its own here: callers of the device-pointer entry points bring theirs, and with
@@ -167,6 +192,8 @@ spmv_mi355x_create(spmv_mi355x_matrix ** out, int format, int precision, long m,
 		set_error("NULL input array");
 		return 1;
 	}
+	if (transpose_check("create", o, n, nnz))
+		return 1;
 	int ndev = 0;
 	spmv_mi355x_device_count(&ndev);
 	if (ndev < 1)
@@ -229,7 +256,7 @@ spmv_mi355x_create(spmv_mi355x_matrix ** out, int format, int precision, long m,
 		return 1;
 
 	spmv_mi355x_matrix * A = new spmv_mi355x_matrix();
-	init_handle(A, format, precision, device, o, in.m, n, in.nnz);
+	init_handle(A, format, precision, device, o, in.m, in.n, in.nnz);
 
 	// ---- the format's constructor (= csr_to_format of the reference's backends)
 	int rc;
@@ -274,6 +301,7 @@ long spmv_mi355x_nnz(const spmv_mi355x_matrix * A) { return A->nnz; }
 int spmv_mi355x_precision(const spmv_mi355x_matrix * A) { return A->precision; }
 int spmv_mi355x_value_storage(const spmv_mi355x_matrix * A) { return !A ? -1 : A->val_f32 ? SPMV_MI355X_F32 : SPMV_MI355X_F64; }
 int spmv_mi355x_device(const spmv_mi355x_matrix * A) { return A->device; }
+int spmv_mi355x_transposed(const spmv_mi355x_matrix * A) { return !A ? -1 : A->transposed; }
 
 int
 spmv_mi355x_spmv_device_async(spmv_mi355x_matrix * A, const void * x, void * y, int beta, void * hip_stream)

@@ -1,0 +1,273 @@
+// CSR of A (m x n) -> CSR of A^t (n x m), where the matrix already is: in device memory (include/spmv_mi355x.h "transposed handles",
+// opts.transpose). The engine then builds a handle of A^t in A^t's own best layout, and every kernel, spmm, the solvers and the value
+// stores serve the transposed product unchanged. There is deliberately no y = A^t x over A's layout: that is one scattered fp64 atomic
+// per entry (24 G updates/s scattered, 178 G/s at best: profiles/r01_atomic_bench.txt) and a result that changes from run to run.
+//
+// THE ORDER (the contract): the rows of A^t in order; inside a row the entries in ascending row of A; entries of equal (row, column)
+// in their input order = a stable counting sort of the entries by column. Nothing here depends on the order in which atomics land:
+//   1. one lane per entry: its row, by binary search of the entry number in row_ptr (neighbouring lanes walk the same cache lines);
+//   2. one stable radix sort of (column, entry number) over the ceil(log2 n) bits a column takes (hipcub);
+//   3. row_ptr of A^t = the first sorted position of every column: a lower-bound search in the sorted keys, one lane per column;
+//   4. one gather: col_t[e] = row[id[e]], val_t[e] = val[id[e]] — a bandwidth kernel with two scattered reads per entry (4 + 8 bytes;
+//      inside one column of A the ids ascend, so a column that many consecutive rows own reads whole lines), four entries per lane
+//      and step, the sorted ids read once as 16 bytes with the nt policy, both results stored as 16 bytes, a grid sized from the CUs.
+// Transient: the row marks, the ids and the sort's second pair of buffers (16 bytes per entry + the sort's own scratch), freed before
+// this returns; the three output arrays are the caller's to free (before the format builder allocates its own, csr_stream.hip).
+// transpose_csr_host is the same order on the host (OpenMP) and stays as the checker (opts.convert_on = 2): same bytes.
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <vector>
+
+#include "handle.hpp"
+
+namespace spmv {
+
+namespace {
+
+constexpr int TB = 256;
+
+struct Scratch {
+	std::vector<void *> ptrs;
+	~Scratch() { release(); }
+	void release()
+	{
+		for (void * p : ptrs)
+			(void) hipFree(p);
+		ptrs.clear();
+	}
+	template <typename P>
+	int get(P ** out, size_t bytes)
+	{
+		void * p = nullptr;
+		HIP_TRY(hipMalloc(&p, bytes ? bytes : 16));
+		ptrs.push_back(p);
+		*out = (P *) p;
+		return 0;
+	}
+};
+
+// row[e] = the row of entry e (the last i with rp[i] <= e: empty rows never own an entry), ids[e] = e
+__global__ __launch_bounds__(TB) void
+transpose_mark_kernel(const int * __restrict__ rp, long m, long nnz, int * __restrict__ row, unsigned * __restrict__ ids)
+{
+	for (long e = (long) blockIdx.x * TB + threadIdx.x; e < nnz; e += (long) gridDim.x * TB)
+	{
+		long lo = 0, hi = m - 1;
+		while (lo < hi)
+		{
+			const long mid = (lo + hi + 1) / 2;
+			if (rp[mid] <= e)
+				lo = mid;
+			else
+				hi = mid - 1;
+		}
+		row[e] = (int) lo;
+		ids[e] = (unsigned) e;
+	}
+}
+
+// rp_t[c] = the first sorted entry whose column is >= c, c = 0 .. n (rp_t[n] = nnz)
+__global__ __launch_bounds__(TB) void
+transpose_start_kernel(const unsigned * __restrict__ key, long nnz, long n, int * __restrict__ rp_t)
+{
+	const long c = (long) blockIdx.x * TB + threadIdx.x;
+	if (c > n)
+		return;
+	long lo = 0, hi = nnz;
+	while (lo < hi)
+	{
+		const long mid = (lo + hi) / 2;
+		if ((long) key[mid] < c)
+			lo = mid + 1;
+		else
+			hi = mid;
+	}
+	rp_t[c] = (int) lo;
+}
+
+// ci_t[e] = row[ids[e]], va_t[e] = va[ids[e]]; ids, ci_t and va_t are allocations of this file (16-byte aligned)
+__global__ __launch_bounds__(TB) void
+transpose_gather_kernel(const unsigned * __restrict__ ids, const int * __restrict__ row, const double * __restrict__ va, long nnz,
+		int * __restrict__ ci_t, double * __restrict__ va_t)
+{
+	typedef unsigned U4 __attribute__((ext_vector_type(4)));
+	typedef int I4 __attribute__((ext_vector_type(4)));
+	typedef double D2 __attribute__((ext_vector_type(2)));
+	const long quads = nnz / 4;
+	for (long q = (long) blockIdx.x * TB + threadIdx.x; q < quads; q += (long) gridDim.x * TB)
+	{
+		const U4 id = __builtin_nontemporal_load(reinterpret_cast<const U4 *>(ids) + q);
+		I4 r;
+		D2 a, b;
+		r.x = row[id.x];
+		r.y = row[id.y];
+		r.z = row[id.z];
+		r.w = row[id.w];
+		a.x = va[id.x];
+		a.y = va[id.y];
+		b.x = va[id.z];
+		b.y = va[id.w];
+		reinterpret_cast<I4 *>(ci_t)[q] = r;
+		reinterpret_cast<D2 *>(va_t)[2 * q] = a;
+		reinterpret_cast<D2 *>(va_t)[2 * q + 1] = b;
+	}
+	// the last nnz % 4 entries
+	if (blockIdx.x == 0 && threadIdx.x < nnz - 4 * quads)
+	{
+		const long e = 4 * quads + threadIdx.x;
+		const unsigned id = ids[e];
+		ci_t[e] = row[id];
+		va_t[e] = va[id];
+	}
+}
+
+static unsigned
+bandwidth_grid(long items)
+{
+	int dev = 0, cus = 256;
+	if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
+	{
+		(void) hipGetLastError();
+		cus = 256;
+	}
+	const long want = (items + TB - 1) / TB, cap = (long) cus * 8;
+	return (unsigned) std::max<long>(1, std::min(want, cap));
+}
+
+}  // namespace
+
+// rp, ci, va: device pointers of an m x n CSR with row_ptr[0] = 0, row_ptr[m] = nnz and columns in [0, n) (the caller has checked).
+// Outputs: device allocations of n + 1, max(nnz, 1) and max(nnz, 1) elements, the caller's to hipFree. 0 = done, 1 = error set.
+int
+transpose_csr_device(long m, long n, long nnz, const int * rp, const int * ci, const double * va, int ** rp_t_out, int ** ci_t_out, double ** va_t_out)
+{
+	*rp_t_out = nullptr;
+	*ci_t_out = nullptr;
+	*va_t_out = nullptr;
+	if (m < 0 || n < 0 || nnz < 0 || n + nnz >= 0x7fffffffL || (nnz > 0 && (m < 1 || n < 1)))
+	{
+		set_error("transpose: sizes out of range (m=%ld n=%ld nnz=%ld)", m, n, nnz);
+		return 1;
+	}
+	Scratch out, tmp;
+	int * rp_t, * ci_t;
+	double * va_t;
+	if (out.get(&rp_t, (size_t) (n + 1) * 4) || out.get(&ci_t, (size_t) nnz * 4) || out.get(&va_t, (size_t) nnz * 8))
+		return 1;
+	if (nnz == 0)
+		HIP_TRY(hipMemset(rp_t, 0, (size_t) (n + 1) * 4));
+	else
+	{
+		int * row;
+		unsigned * ids, * ids_sorted, * key_sorted;
+		if (tmp.get(&row, (size_t) nnz * 4) || tmp.get(&ids, (size_t) nnz * 4) || tmp.get(&ids_sorted, (size_t) nnz * 4) || tmp.get(&key_sorted, (size_t) nnz * 4))
+			return 1;
+		hipLaunchKernelGGL(transpose_mark_kernel, dim3(bandwidth_grid(nnz)), dim3(TB), 0, 0, rp, m, nnz, row, ids);
+		HIP_TRY(hipGetLastError());
+		int bits = 1;
+		while ((1L << bits) < n)
+			bits++;
+		const unsigned * key = reinterpret_cast<const unsigned *>(ci);        // columns are in [0, n): non-negative
+		size_t bytes = 0;
+		HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, key, key_sorted, ids, ids_sorted, (int) nnz, 0, bits, (hipStream_t) 0));
+		void * sort_tmp;
+		if (tmp.get(&sort_tmp, bytes))
+			return 1;
+		HIP_TRY(hipcub::DeviceRadixSort::SortPairs(sort_tmp, bytes, key, key_sorted, ids, ids_sorted, (int) nnz, 0, bits, (hipStream_t) 0));
+		hipLaunchKernelGGL(transpose_start_kernel, dim3((unsigned) ((n + 1 + TB - 1) / TB)), dim3(TB), 0, 0, key_sorted, nnz, n, rp_t);
+		HIP_TRY(hipGetLastError());
+		hipLaunchKernelGGL(transpose_gather_kernel, dim3(bandwidth_grid((nnz + 3) / 4)), dim3(TB), 0, 0, ids_sorted, row, va, nnz, ci_t, va_t);
+		HIP_TRY(hipGetLastError());
+	}
+	HIP_TRY(hipDeviceSynchronize());
+	tmp.release();
+	out.ptrs.clear();
+	*rp_t_out = rp_t;
+	*ci_t_out = ci_t;
+	*va_t_out = va_t;
+	return 0;
+}
+
+// create(): the caller's (validated) host CSR, row_ptr from 0 -> the host CSR of A^t, transposed on the device. One upload and one
+// download of 12 bytes per non-zero around it: accepted, so that the row block, the column filter and every builder family keep
+// working from one local CSR.
+int
+transpose_csr_upload(long m, long n, long nnz, const int * rp, const int * ci, const double * va, std::vector<int> & rp_t, std::vector<int> & ci_t,
+		std::vector<double> & va_t)
+{
+	Scratch in, out;
+	int * d_rp, * d_ci, * d_rp_t = nullptr, * d_ci_t = nullptr;
+	double * d_va, * d_va_t = nullptr;
+	if (in.get(&d_rp, (size_t) (m + 1) * 4) || in.get(&d_ci, (size_t) nnz * 4) || in.get(&d_va, (size_t) nnz * 8))
+		return 1;
+	HIP_TRY(hipMemcpy(d_rp, rp, (size_t) (m + 1) * 4, hipMemcpyHostToDevice));
+	if (nnz)
+	{
+		HIP_TRY(hipMemcpy(d_ci, ci, (size_t) nnz * 4, hipMemcpyHostToDevice));
+		HIP_TRY(hipMemcpy(d_va, va, (size_t) nnz * 8, hipMemcpyHostToDevice));
+	}
+	if (transpose_csr_device(m, n, nnz, d_rp, d_ci, d_va, &d_rp_t, &d_ci_t, &d_va_t))
+		return 1;
+	out.ptrs = {d_rp_t, d_ci_t, d_va_t};
+	in.release();
+	rp_t.resize((size_t) n + 1);
+	ci_t.resize((size_t) std::max<long>(nnz, 1));
+	va_t.resize((size_t) std::max<long>(nnz, 1));
+	HIP_TRY(hipMemcpy(rp_t.data(), d_rp_t, (size_t) (n + 1) * 4, hipMemcpyDeviceToHost));
+	if (nnz)
+	{
+		HIP_TRY(hipMemcpy(ci_t.data(), d_ci_t, (size_t) nnz * 4, hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(va_t.data(), d_va_t, (size_t) nnz * 8, hipMemcpyDeviceToHost));
+	}
+	return 0;
+}
+
+// The checker of the above (opts.convert_on = 2): the same stable counting sort by column on the host. Counts through atomics (integer
+// sums do not depend on their order); for the fill every thread owns a range of columns of about equal non-zeros and walks the whole
+// matrix in entry order, so a column's entries land in ascending entry number whatever the thread count.
+void
+transpose_csr_host(long m, long n, long nnz, const int * rp, const int * ci, const double * va, std::vector<int> & rp_t, std::vector<int> & ci_t,
+		std::vector<double> & va_t)
+{
+	rp_t.assign((size_t) n + 1, 0);
+	ci_t.assign((size_t) std::max<long>(nnz, 1), 0);
+	va_t.assign((size_t) std::max<long>(nnz, 1), 0.0);
+	if (nnz == 0)
+		return;
+	#pragma omp parallel for num_threads(spmv::host_threads()) schedule(static, 4096)
+	for (long e = 0; e < nnz; e++)
+	{
+		#pragma omp atomic
+		rp_t[(size_t) ci[e] + 1]++;
+	}
+	for (long c = 0; c < n; c++)
+		rp_t[(size_t) c + 1] += rp_t[(size_t) c];
+	const int T = std::max(1, spmv::host_threads());
+	std::vector<long> cut((size_t) T + 1, n);
+	cut[0] = 0;
+	for (int t = 1; t < T; t++)
+		cut[(size_t) t] = std::lower_bound(rp_t.begin(), rp_t.end(), (int) (nnz * t / T)) - rp_t.begin();
+	for (int t = 1; t <= T; t++)
+		cut[(size_t) t] = std::min<long>(n, std::max(cut[(size_t) t], cut[(size_t) t - 1]));
+	std::vector<int> pos(rp_t.begin(), rp_t.end() - 1);
+	#pragma omp parallel for num_threads(T) schedule(static, 1)
+	for (int t = 0; t < T; t++)
+	{
+		const long c0 = cut[(size_t) t], c1 = cut[(size_t) t + 1];
+		if (c0 >= c1)
+			continue;
+		for (long i = 0; i < m; i++)
+			for (long e = rp[i]; e < rp[i + 1]; e++)
+			{
+				const long c = ci[e];
+				if (c < c0 || c >= c1)
+					continue;
+				const int k = pos[(size_t) c]++;
+				ci_t[(size_t) k] = (int) i;
+				va_t[(size_t) k] = va[e];
+			}
+	}
+}
+
+}  // namespace spmv

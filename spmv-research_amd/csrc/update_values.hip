@@ -391,6 +391,8 @@ is_sell(const spmv_mi355x_matrix * A)
 static const char *
 update_refusal(const spmv_mi355x_matrix * A)
 {
+	if (A->transposed)
+		return "the handle was created with transpose = 1: its entries are not in the caller's order";
 	if (A->upd_col_filter)
 		return "the handle was created with a column filter (col_filter_mode): its entries are a subset of the caller's";
 	if (A->upd_symmetric)

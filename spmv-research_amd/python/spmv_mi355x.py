@@ -31,6 +31,16 @@ class Opts(C.Structure):
                 ("placement_budget_gib", C.c_int), ("sell_values", C.c_int), ("value_storage", C.c_int)]
 
 
+# opts.transpose, the last field of spmv_mi355x_opts (include/spmv_mi355x.h "transposed handles"). In C it took the struct's tail
+# padding: sizeof did not change, and the field sits right behind value_storage, inside what ctypes counts as padding of the
+# _fields_ above. That list is pinned by the ABI tests of the options before it, so the mirror of this field is a property over the
+# same bytes: Opts().transpose reads and writes the int at OPTS_TRANSPOSE_OFFSET.
+OPTS_TRANSPOSE_OFFSET = Opts.value_storage.offset + C.sizeof(C.c_int)
+assert OPTS_TRANSPOSE_OFFSET + C.sizeof(C.c_int) <= C.sizeof(Opts), "spmv_mi355x_opts has no room behind value_storage"
+Opts.transpose = property(lambda self: C.c_int.from_buffer(self, OPTS_TRANSPOSE_OFFSET).value,
+                          lambda self, v: setattr(C.c_int.from_buffer(self, OPTS_TRANSPOSE_OFFSET), "value", v))
+
+
 # every symbol declared in include/spmv_mi355x.h (checked by tests/test_abi.py)
 SYMBOLS = [
     "spmv_mi355x_last_error", "spmv_mi355x_device_count", "spmv_mi355x_device_info", "spmv_mi355x_create",
@@ -39,6 +49,7 @@ SYMBOLS = [
     "spmv_mi355x_upload_x", "spmv_mi355x_download_y", "spmv_mi355x_spmv_device_async", "spmv_mi355x_time_device",
     "spmv_mi355x_kernel_info", "spmv_mi355x_x_device", "spmv_mi355x_y_device", "spmv_mi355x_sell_layout", "spmv_mi355x_stored_array",
     "spmv_mi355x_merge_tiles", "spmv_mi355x_free", "spmv_mi355x_precision", "spmv_mi355x_value_storage", "spmv_mi355x_device",
+    "spmv_mi355x_transposed",
     "spmv_mi355x_pcg", "spmv_mi355x_pbicgstab", "spmv_mi355x_pcg_dist", "spmv_mi355x_pbicgstab_dist",
     "spmv_mi355x_pcg_multi", "spmv_mi355x_pbicgstab_multi",
     "spmv_mi355x_copy_device_async",
@@ -174,7 +185,8 @@ def _make_opts(opts):
 class CsrStream:
     """A CSR assembled in device memory from pieces of consecutive rows (include/spmv_mi355x.h "a handle from a CSR that arrives in
     pieces"): append(row_ptr, col_idx, values) per piece, finish(fmt, dtype, **opts) -> Matrix. The host never holds more than a
-    piece. SELL-C-sigma (64-row slices, delta layout) only."""
+    piece. SELL-C-sigma (64-row slices, delta layout) only. finish(..., transpose=1) gives the handle of the transposed matrix,
+    transposed on the GPU from the resident arrays."""
 
     def __init__(self, m, n, nnz_capacity, device=-1):
         self.s = C.c_void_p()
@@ -300,7 +312,9 @@ class PartitionedMatrix:
 
 
 class Matrix:
-    """One converted matrix on one GPU = the reference's `struct Matrix_Format` instance."""
+    """One converted matrix on one GPU = the reference's `struct Matrix_Format` instance. Matrix(..., transpose=1) holds the
+    transpose of the CSR it is given (include/spmv_mi355x.h "transposed handles"): m and n are then those of the transpose, and
+    `transposed` is 1."""
 
     def __init__(self, row_ptr, col_idx, values, m, n, fmt="csr_vector", dtype=np.float64, _handle=None, **opts):
         if _handle is not None:                        # CsrStream.finish(): the handle exists already
@@ -336,6 +350,7 @@ class Matrix:
         self.csr_mem_footprint = L.spmv_mi355x_csr_mem_footprint(self.h)
         # what the matrix values are stored as (opts.value_storage); self.dtype stays the precision of x and y
         self.value_dtype = np.dtype(np.float32 if L.spmv_mi355x_value_storage(self.h) == F32 else np.float64)
+        self.transposed = L.spmv_mi355x_transposed(self.h)
 
     # Matrix_Format::spmv(x, y) on host buffers; y gets the driver's +64 slack and 1.0 canary (bench_spmv.cpp:606-609)
     def spmv(self, x, always_copy=True):

@@ -383,6 +383,45 @@ int  spmv_mi355x_pcg_multi(spmv_mi355x_matrix * A, int k, const int32_t * row_pt
 int  spmv_mi355x_pbicgstab_multi(spmv_mi355x_matrix * A, int k, const int32_t * row_ptr, const int32_t * col_idx, const double * values_fp64,
 		const void * B_host, void * X_res_out_host, long max_iterations, double * history_out, spmv_mi355x_solver_info * info);
 
+/* ---- CGLS: least squares over a handle of A and a handle of A^t ------------------------------------------------------------ */
+/* min |A x - b|^2 + damp * |x|^2 (damp >= 0, Tikhonov) for ANY m x n matrix — tall, wide, rank-deficient — from x0 = 0, so that an
+ * underdetermined system with damp = 0 returns its minimum-norm solution. The CGLS recurrences, A^t A never formed, every vector
+ * resident in device memory (csrc/solver_cgls.hip; 2 SpMV + 4 vector launches per iteration):
+ *     r = b; s = A^t r; p = s; gamma = s.s; gamma0 = gamma
+ *     loop k: q = A p;  delta = q.q + damp * p.p;  alpha = gamma / delta;  x += alpha p;  r -= alpha q;
+ *             s = A^t r - damp * x;  gamma' = s.s;  beta = gamma' / gamma;  p = s + beta p;  gamma = gamma'
+ *             stop when sqrt(gamma') <= tol * sqrt(gamma0)
+ *   - A is m x n; At is a handle of its transpose (n x m), built with opts.transpose = 1 or from the caller's own CSR of A^t;
+ *     spmv_mi355x_transposed() is not consulted. CHECKED: rows(At) == cols(A), cols(At) == rows(A), the same precision, the same
+ *     device. NOT CHECKABLE: that At really holds A^t — with another n x m matrix the recurrences run on and mean nothing.
+ *   - b_host: m values, x_out_host: n values, both of the handles' precision. Scalars and dot products are fp64 in both precisions.
+ *   - any format and layout serves (the solver only calls spmv_mi355x_spmv_device_async), value_storage = 1, 7-byte values and row
+ *     blocks of At's own rules included; on handles whose SpMV is deterministic the whole solve is, bit for bit. The solver's vectors
+ *     are plain allocations (placement is not used, as in pcg).
+ *   - tol == 0 is legal and means "never stop on the tolerance". max_iterations == 0 returns x = 0, stop 2 and the norms of x = 0.
+ *   - history_out (may be NULL): 2 * max_iterations doubles; row k = (|r_{k+1}|, |s_{k+1}|) after loop body k, both the RECURSIVE
+ *     quantities; rows >= info->iterations stay 0.
+ *   - after a stop the iteration is frozen on the device: x, iterations and the history are those of the iteration at which the
+ *     rule fired, however far the host had run ahead (at most 64 iterations).
+ *   - rc 1, a last_error that names cgls, before any device is touched and with every caller buffer untouched: a NULL A, At, b or
+ *     x_out; info->struct_size < 8; damp or tol negative or not finite; max_iterations < 0; a shape (the message gives both),
+ *     precision or device mismatch between the two handles. */
+typedef struct {
+	unsigned struct_size;   /* in: sizeof(spmv_mi355x_lsq_info) */
+	long   iterations;      /* completed loop bodies */
+	int    stop;            /* 1 = |s_k| <= tol*|s_0|, 2 = max_iterations reached, 3 = A^t b == 0 (x = 0 returned, 0 iterations),
+	                           4 = breakdown: delta = |q|^2 + damp*|p|^2 was 0 or not finite (x of the last good iteration returned) */
+	double rnorm;           /* |b - A x_out|, EXPLICIT (one SpMV with A after the loop) */
+	double arnorm;          /* |A^t (b - A x_out) - damp * x_out|, EXPLICIT (one SpMV with At after the loop) */
+	double arnorm0;         /* |A^t b| */
+	double xnorm;           /* |x_out| */
+	long   spmv_calls;      /* SpMV launches of the whole call, both handles, setup and the two explicit ones included */
+	double seconds;         /* wall time of the call */
+} spmv_mi355x_lsq_info;
+int  spmv_mi355x_cgls(spmv_mi355x_matrix * A, spmv_mi355x_matrix * At,
+		const void * b_host, void * x_out_host, double damp, double tol, long max_iterations,
+		double * history_out /* may be NULL: 2*max_iterations doubles */, spmv_mi355x_lsq_info * info /* may be NULL */);
+
 /* Row-partitioned (multi-GPU) form of the same two solvers: one process per GPU owns the row block [row_offset,
  * row_offset + m_local) of A, b and x. The solver keeps every vector device-resident and local; the two things that cross
  * ranks are handed to the caller, who has the communicator (torch.distributed / RCCL in bench-level code):

@@ -51,7 +51,7 @@ SYMBOLS = [
     "spmv_mi355x_merge_tiles", "spmv_mi355x_free", "spmv_mi355x_precision", "spmv_mi355x_value_storage", "spmv_mi355x_device",
     "spmv_mi355x_transposed",
     "spmv_mi355x_pcg", "spmv_mi355x_pbicgstab", "spmv_mi355x_pcg_dist", "spmv_mi355x_pbicgstab_dist",
-    "spmv_mi355x_pcg_multi", "spmv_mi355x_pbicgstab_multi",
+    "spmv_mi355x_pcg_multi", "spmv_mi355x_pbicgstab_multi", "spmv_mi355x_cgls",
     "spmv_mi355x_copy_device_async",
     "spmv_mi355x_create_partitioned", "spmv_mi355x_destroy_partitioned", "spmv_mi355x_spmv_partitioned",
     "spmv_mi355x_partitioned_set_always_copy", "spmv_mi355x_time_partitioned", "spmv_mi355x_partitioned_parts",
@@ -90,6 +90,9 @@ def lib():
         L.spmv_mi355x_partitioned_mem_footprint.restype = C.c_double
         L.spmv_mi355x_x_device.restype = C.c_void_p
         L.spmv_mi355x_y_device.restype = C.c_void_p
+        L.spmv_mi355x_cgls.restype = C.c_int
+        L.spmv_mi355x_cgls.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_long,
+                                       C.c_void_p, C.POINTER(LsqInfo)]
         _lib = L
     return _lib
 
@@ -223,6 +226,12 @@ class SolverInfo(C.Structure):
     _fields_ = [("struct_size", C.c_uint), ("iterations", C.c_long), ("error", C.c_double), ("error_best", C.c_double),
                 ("eps", C.c_double), ("eps_counter", C.c_double), ("restarts", C.c_long), ("spmv_calls", C.c_long),
                 ("seconds", C.c_double)]
+
+
+class LsqInfo(C.Structure):
+    """spmv_mi355x_lsq_info (include/spmv_mi355x.h)"""
+    _fields_ = [("struct_size", C.c_uint), ("iterations", C.c_long), ("stop", C.c_int), ("rnorm", C.c_double), ("arnorm", C.c_double),
+                ("arnorm0", C.c_double), ("xnorm", C.c_double), ("spmv_calls", C.c_long), ("seconds", C.c_double)]
 
 
 SPMV_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p)
@@ -565,6 +574,24 @@ class Matrix:
     def pbicgstab_multi(self, row_ptr, col_idx, values, B, max_iterations, history=True):
         """Matrix.pbicgstab for the k columns of B (spmv_mi355x_pbicgstab_multi), as pcg_multi."""
         return self._solve_multi(lib().spmv_mi355x_pbicgstab_multi, row_ptr, col_idx, values, B, max_iterations, history)
+
+    def cgls(self, At, b, damp=0.0, tol=1e-12, max_iterations=1000, history=True):
+        """min |A x - b|^2 + damp |x|^2 by CGLS over this handle (A) and `At`, a handle of its transpose (spmv_mi355x_cgls): a dict of
+        the spmv_mi355x_lsq_info fields plus x (cols values) and history (rows (|r_{k+1}|, |s_{k+1}|), shape (iterations, 2), or None).
+        The shape, precision and device of At are checked by the library."""
+        b = np.ascontiguousarray(b, self.dtype)
+        if b.shape != (self.m,):
+            raise ValueError(f"b must have {self.m} values, got {b.shape}")
+        x = np.zeros(max(self.n, 1), self.dtype)
+        hist = np.zeros((max(max_iterations, 1), 2), np.float64) if history else None
+        info = LsqInfo()
+        info.struct_size = C.sizeof(LsqInfo)
+        _check(lib().spmv_mi355x_cgls(self.h, At.h, _p(b), _p(x), damp, tol, max_iterations, _p(hist) if history else None,
+                                      C.byref(info)))
+        out = {k: getattr(info, k) for k, _ in LsqInfo._fields_ if k != "struct_size"}
+        out["x"] = x[:self.n]
+        out["history"] = hist[:info.iterations] if history else None
+        return out
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h:

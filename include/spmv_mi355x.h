@@ -168,8 +168,10 @@ typedef struct {
  *   - rc 1 with a last_error that names transpose, before any device is touched: a value other than 0 or 1; transpose = 1 with
  *     symmetric_input = 1 (the transpose of a symmetric matrix is the matrix itself); spmv_mi355x_create_partitioned with
  *     transpose = 1 (its parts would each transpose the whole matrix).
- *   - update_values_prepare / update_values / update_values_device refuse a transposed handle (rc 1, update_values_state 0): its
- *     entries are not in the caller's order. Carrying the entry permutation is left to a later change.
+ *   - update_values / update_values_device refuse a transposed handle (rc 1, update_values_state 0: its entries are not in the
+ *     caller's order) until spmv_mi355x_update_values_prepare_transposed has derived the entry map from the pattern of A; from then
+ *     on they take new values in A's entry order ("new values for an existing handle"). The map is not made at create(): it is 4 bytes
+ *     per entry that only a caller who updates needs, and a transposed handle's footprint is that of the handle of A^t.
  *   - the solvers read the Jacobi diagonal from the host CSR they are given: on a transposed handle pass the CSR create() was given
  *     (that of A) — the diagonal of A^t is that of A.
  * A caller whose struct_size ends before the field gets transpose = 0. */
@@ -242,19 +244,53 @@ int  spmv_mi355x_csr_stream_discard(spmv_mi355x_csr_stream * s);
  *   - kept: the handle's x / y device buffers and its cached-x state, its spmm scratch, arrays moved by placement level 3 (they are
  *     written where they live). The next host-buffer spmv downloads y again.
  *   - rc 1, a last_error naming update_values, the handle untouched: a NULL handle or pointer; update before prepare; a handle created
- *     with opts.transpose = 1 (its entries are not in the caller's order), with a column filter (col_filter_mode != 0: its entries
+ *     with opts.transpose = 1 that has no entry map yet (see below), with a column filter (col_filter_mode != 0: its entries
  *     are a subset of the caller's) or with symmetric_input = 1 (expanded or
  *     kept as a triangle: its entries are not the caller's); the column-blocked layout (col_blocks != 0: entries sorted by column); a
  *     handle without a value stream (the _unit layouts of uniform values). spmv_mi355x_partitioned handles have no such entry (their
  *     parts carry column filters).
  *   - update_values_state, host-only: 0 = this handle cannot be updated (last_error says why), 1 = it can, prepare is still missing,
  *     2 = ready. NULL: 0.
+ * TRANSPOSED HANDLES (opts.transpose = 1): the caller holds the CSR of A, the handle the entries of A^t in the order of the
+ * transposition. update_values_prepare_transposed, once per handle before its first update, takes the PATTERN of A as create() or the
+ * stream was given it (m, n, row_ptr of m + 1 and col_idx of row_ptr[m] entries, host arrays, row_ptr from 0; no values) and derives
+ * the ENTRY MAP src: entry e of the handle's local CSR is entry src[e] of the CSR of A. From then on update_values and
+ * update_values_device read update_values_count() = nnz(A) fp64 values, values[e] belonging to entry e of the CSR of A — all of A's
+ * values, also when the handle holds a row block of A^t — so ONE array of new values refreshes the handle of A and the handle of A^t.
+ * THE CONTRACT: a handle created from (pattern of A, V1, opts with transpose = 1), prepared and updated with V2, is indistinguishable
+ * (as above) from the handle create() builds from (pattern of A, V2, the same opts), and so from the handle of the CSR of A^t with V2.
+ *   - the pattern is checked as create() checks it (row_ptr from 0 and monotone, columns in [0, n): same messages) and against what
+ *     the handle recorded at create: m == cols(At), n == the rows of the whole A^t, row_ptr[m] == nnz(A) (a mismatch names both
+ *     numbers). It is uploaded and ordered on the GPU by the transposition's own stable sort by column (csrc/transpose_csr.hip:
+ *     one definition of the order); the sorted entry numbers are the map, for a row block [row_begin, row_end) of A^t that stretch of
+ *     them with the row pointer rebased to 0. A handle created with convert_on = 2 (or SPMV_MI355X_HOST_CONVERT) derives the map on the
+ *     host with the order's host form instead: the checker, same bytes. The derived local row pointer then passes the checks of
+ *     update_values_prepare: it ends at nnz(), and on SELL layouts every slice's stored width equals the longest of its rows — else
+ *     "the pattern does not match the pattern this handle was built from". NOT CHECKABLE: a pattern with the same number of entries
+ *     per column (row of A^t) within every slice but other row positions: its values are stored as the map orders them.
+ *   - kept with the handle until destroy or the next prepare_transposed, neither counted in mem_footprint(): the local row pointer
+ *     (4 * (rows() + 1) bytes) and the map (4 * nnz() bytes). Transient device memory during the call: the pattern of A (4 bytes per
+ *     row and per non-zero), the row pointer of A^t, and what the transposition takes without its value arrays: 16 bytes per non-zero
+ *     + the sort's scratch.
+ *   - an update gathers va_t[e] = values[src[e]] into a transient device array of nnz() doubles (one launch, 12 bytes read and 8
+ *     written per entry) and then runs the update above unchanged, 7-byte re-selection, reallocation and the merge path's _unit rule
+ *     included. Everything is ordered on hip_stream and the call blocks; the host form uploads update_values_count() doubles first.
+ *   - state: 0 before prepare_transposed (last_error names transpose), 2 after. update_values_prepare keeps refusing a transposed
+ *     handle, prepared or not (a prepared one stays prepared). prepare_transposed returns rc 1 with a last_error naming
+ *     update_values_prepare_transposed, the handle untouched, for a NULL handle or array, a handle created with transpose = 0, a
+ *     handle no map can serve (column filter, col_blocks, a _unit layout), a shape or nnz mismatch, a bad pattern; the NULL and argument
+ *     errors come before any device is touched.
+ *   - update_values_count, host-only: the values an update of this handle reads: nnz(), and nnz(A) once prepare_transposed has run.
+ *     NULL: -1.
  * SPMV_MI355X_UPDATE_STAGE = 0 makes the SELL kernels read every row straight from global memory instead of staging a slice's
  * contiguous stretch of the CSR array through LDS. */
 int  spmv_mi355x_update_values_prepare(spmv_mi355x_matrix * A, const int32_t * row_ptr);
 int  spmv_mi355x_update_values(spmv_mi355x_matrix * A, const double * values_fp64_host);
 int  spmv_mi355x_update_values_device(spmv_mi355x_matrix * A, const double * values_fp64_dev, void * hip_stream);
 int  spmv_mi355x_update_values_state(const spmv_mi355x_matrix * A);
+int  spmv_mi355x_update_values_prepare_transposed(spmv_mi355x_matrix * At, long m, long n,
+		const int32_t * row_ptr, const int32_t * col_idx);
+long spmv_mi355x_update_values_count(const spmv_mi355x_matrix * A);
 
 /* ---- Matrix_Format::spmv(x, y) with HOST buffers --------------------------------------------------------- */
 /* Reference GPU-backend semantics (GPU_clean/csr_rocm_vector.cpp:224-257): x is uploaded when the host

@@ -210,6 +210,10 @@ spmv_mi355x_create_from_stream(spmv_mi355x_matrix ** out, spmv_mi355x_csr_stream
 		if (!rc)
 		{
 			init_handle(A, format, precision, device, o, n, m, nnz);
+			A->t_nnz = nnz;
+			A->t_rows = n;
+			A->t_row_begin = 0;
+			A->t_row_end = n;
 			rc = build_sell_delta_resident(A, o, d_rp_t, d_ci_t, d_va_t);
 		}
 		for (void * p : {(void *) d_rp_t, (void *) d_ci_t, (void *) d_va_t})

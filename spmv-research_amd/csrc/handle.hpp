@@ -107,6 +107,13 @@ struct spmv_mi355x_matrix {
 	bool sell_v7_active = false;           // the delta handle re-selects its 7-byte slices from the values (sell_v7_wanted at create)
 	int * d_upd_row_ptr = nullptr;         // prepare(): device copy of the local row pointer (m + 1); not in mem_footprint
 	size_t val_capacity = 0;               // bytes of the allocation behind d_val, as of prepare() / the last reallocation
+	// a transposed handle: what create() saw of A (host integers only), and what update_values_prepare_transposed keeps
+	long t_nnz = 0;                        // the non-zeros of A (nnz may be those of a row block of A^t)
+	long t_rows = 0;                       // the rows of the whole A^t (= the columns of A)
+	long t_row_begin = 0, t_row_end = 0;   // the rows of A^t this handle holds: opts.row_begin / row_end, resolved
+	unsigned * d_upd_src = nullptr;        // local entry e -> the caller's entry (nnz entries); with it d_upd_row_ptr is the derived local
+	                                       //   row pointer. Not in mem_footprint
+	long upd_count = 0;                    // the values an update through d_upd_src reads (= t_nnz)
 
 	double mem_footprint = 0, csr_mem_footprint = 0;
 	char format_name[96] = "";
@@ -136,6 +143,11 @@ int transpose_csr_upload(long m, long n, long nnz, const int * rp, const int * c
 		std::vector<double> & va_t);
 void transpose_csr_host(long m, long n, long nnz, const int * rp, const int * ci, const double * va, std::vector<int> & rp_t, std::vector<int> & ci_t,
 		std::vector<double> & va_t);
+// the entry map of the same order for the rows [r0, r1) of A^t, from the host pattern of A: the block's row pointer from 0 and, per
+// entry of the block, its number in the CSR of A (device allocations, the caller's to hipFree); and the gather through such a map
+int transpose_entry_map(bool on_device, long m, long n, long nnz, const int * rp, const int * ci, long r0, long r1, int ** d_lrp_out,
+		unsigned ** d_src_out, long * lnnz_out);
+int transpose_gather_values(const unsigned * d_src, const double * d_va, long nnz, double * d_va_t, hipStream_t st);
 int ensure_x(spmv_mi355x_matrix * A);                                    // spmv_mi355x.hip: stream + the handle's own (zeroed) x
 int tune_placement(spmv_mi355x_matrix * A);                              // placement.hip: allocates the handle's y (and re-homes its x) in the device's vector pools
 int place_vector(spmv_mi355x_matrix * A, void ** out, size_t bytes, bool is_output);   // placement.hip: a zero-filled vector A's SpMV writes / reads

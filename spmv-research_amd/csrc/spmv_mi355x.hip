@@ -257,6 +257,14 @@ spmv_mi355x_create(spmv_mi355x_matrix ** out, int format, int precision, long m,
 
 	spmv_mi355x_matrix * A = new spmv_mi355x_matrix();
 	init_handle(A, format, precision, device, o, in.m, in.n, in.nnz);
+	if (A->transposed)
+	{
+		// what spmv_mi355x_update_values_prepare_transposed checks its pattern of A against
+		A->t_nnz = nnz;
+		A->t_rows = n;
+		A->t_row_begin = o.row_begin;
+		A->t_row_end = (o.row_begin == 0 && o.row_end == 0) ? n : o.row_end;
+	}
 
 	// ---- the format's constructor (= csr_to_format of the reference's backends)
 	int rc;

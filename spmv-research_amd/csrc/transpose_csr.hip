@@ -14,6 +14,11 @@
 // Transient: the row marks, the ids and the sort's second pair of buffers (16 bytes per entry + the sort's own scratch), freed before
 // this returns; the three output arrays are the caller's to free (before the format builder allocates its own, csr_stream.hip).
 // transpose_csr_host is the same order on the host (OpenMP) and stays as the checker (opts.convert_on = 2): same bytes.
+//
+// Steps 1 to 3 are transpose_order(): THE ORDER has this one definition. Its sorted ids are also the ENTRY MAP of the transposition —
+// entry e of the CSR of A^t is entry ids[e] of the CSR of A — which transpose_entry_map() keeps (for a row block of A^t: that stretch,
+// with the row pointer rebased to 0) so that update_values can refresh a transposed handle from values in A's entry order
+// (update_values.hip, spmv_mi355x_update_values_prepare_transposed): one launch of values_gather_kernel, step 4 without the rows.
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
@@ -122,6 +127,42 @@ transpose_gather_kernel(const unsigned * __restrict__ ids, const int * __restric
 	}
 }
 
+// va_t[e] = va[src[e]]: step 4 for new values alone (12 bytes read, 8 written per entry). src and va_t are allocations of the library
+// (16-byte aligned); va is the caller's, 8-byte aligned, and is read one value at a time
+__global__ __launch_bounds__(TB) void
+values_gather_kernel(const unsigned * __restrict__ src, const double * __restrict__ va, long nnz, double * __restrict__ va_t)
+{
+	typedef unsigned U4 __attribute__((ext_vector_type(4)));
+	typedef double D2 __attribute__((ext_vector_type(2)));
+	const long quads = nnz / 4;
+	for (long q = (long) blockIdx.x * TB + threadIdx.x; q < quads; q += (long) gridDim.x * TB)
+	{
+		const U4 id = __builtin_nontemporal_load(reinterpret_cast<const U4 *>(src) + q);
+		D2 a, b;
+		a.x = va[id.x];
+		a.y = va[id.y];
+		b.x = va[id.z];
+		b.y = va[id.w];
+		reinterpret_cast<D2 *>(va_t)[2 * q] = a;
+		reinterpret_cast<D2 *>(va_t)[2 * q + 1] = b;
+	}
+	// the last nnz % 4 entries
+	if (blockIdx.x == 0 && threadIdx.x < nnz - 4 * quads)
+	{
+		const long e = 4 * quads + threadIdx.x;
+		va_t[e] = va[src[e]];
+	}
+}
+
+// lrp[i] = rp_t[r0 + i] - rp_t[r0], i = 0 .. rows: the row pointer of the row block [r0, r0 + rows) of A^t, from 0
+__global__ __launch_bounds__(TB) void
+transpose_block_kernel(const int * __restrict__ rp_t, long r0, long rows, int * __restrict__ lrp)
+{
+	const long i = (long) blockIdx.x * TB + threadIdx.x;
+	if (i <= rows)
+		lrp[i] = rp_t[r0 + i] - rp_t[r0];
+}
+
 static unsigned
 bandwidth_grid(long items)
 {
@@ -135,6 +176,45 @@ bandwidth_grid(long items)
 	return (unsigned) std::max<long>(1, std::min(want, cap));
 }
 
+static bool
+transpose_sizes_bad(long m, long n, long nnz)
+{
+	if (m < 0 || n < 0 || nnz < 0 || n + nnz >= 0x7fffffffL || (nnz > 0 && (m < 1 || n < 1)))
+	{
+		set_error("transpose: sizes out of range (m=%ld n=%ld nnz=%ld)", m, n, nnz);
+		return true;
+	}
+	return false;
+}
+
+// Steps 1 to 3 of THE ORDER for nnz > 0, enqueued on the null stream: rp_t (n + 1 entries, the caller's allocation) is written;
+// *row_out (the row of every entry of A) and *ids_out (the sorted entry numbers) are allocations of `tmp`, like the sort's buffers.
+static int
+transpose_order(long m, long n, long nnz, const int * rp, const int * ci, Scratch & tmp, int * rp_t, int ** row_out, unsigned ** ids_out)
+{
+	int * row;
+	unsigned * ids, * ids_sorted, * key_sorted;
+	if (tmp.get(&row, (size_t) nnz * 4) || tmp.get(&ids, (size_t) nnz * 4) || tmp.get(&ids_sorted, (size_t) nnz * 4) || tmp.get(&key_sorted, (size_t) nnz * 4))
+		return 1;
+	hipLaunchKernelGGL(transpose_mark_kernel, dim3(bandwidth_grid(nnz)), dim3(TB), 0, 0, rp, m, nnz, row, ids);
+	HIP_TRY(hipGetLastError());
+	int bits = 1;
+	while ((1L << bits) < n)
+		bits++;
+	const unsigned * key = reinterpret_cast<const unsigned *>(ci);        // columns are in [0, n): non-negative
+	size_t bytes = 0;
+	HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, key, key_sorted, ids, ids_sorted, (int) nnz, 0, bits, (hipStream_t) 0));
+	void * sort_tmp;
+	if (tmp.get(&sort_tmp, bytes))
+		return 1;
+	HIP_TRY(hipcub::DeviceRadixSort::SortPairs(sort_tmp, bytes, key, key_sorted, ids, ids_sorted, (int) nnz, 0, bits, (hipStream_t) 0));
+	hipLaunchKernelGGL(transpose_start_kernel, dim3((unsigned) ((n + 1 + TB - 1) / TB)), dim3(TB), 0, 0, key_sorted, nnz, n, rp_t);
+	HIP_TRY(hipGetLastError());
+	*row_out = row;
+	*ids_out = ids_sorted;
+	return 0;
+}
+
 }  // namespace
 
 // rp, ci, va: device pointers of an m x n CSR with row_ptr[0] = 0, row_ptr[m] = nnz and columns in [0, n) (the caller has checked).
@@ -145,11 +225,8 @@ transpose_csr_device(long m, long n, long nnz, const int * rp, const int * ci, c
 	*rp_t_out = nullptr;
 	*ci_t_out = nullptr;
 	*va_t_out = nullptr;
-	if (m < 0 || n < 0 || nnz < 0 || n + nnz >= 0x7fffffffL || (nnz > 0 && (m < 1 || n < 1)))
-	{
-		set_error("transpose: sizes out of range (m=%ld n=%ld nnz=%ld)", m, n, nnz);
+	if (transpose_sizes_bad(m, n, nnz))
 		return 1;
-	}
 	Scratch out, tmp;
 	int * rp_t, * ci_t;
 	double * va_t;
@@ -160,23 +237,9 @@ transpose_csr_device(long m, long n, long nnz, const int * rp, const int * ci, c
 	else
 	{
 		int * row;
-		unsigned * ids, * ids_sorted, * key_sorted;
-		if (tmp.get(&row, (size_t) nnz * 4) || tmp.get(&ids, (size_t) nnz * 4) || tmp.get(&ids_sorted, (size_t) nnz * 4) || tmp.get(&key_sorted, (size_t) nnz * 4))
+		unsigned * ids_sorted;
+		if (transpose_order(m, n, nnz, rp, ci, tmp, rp_t, &row, &ids_sorted))
 			return 1;
-		hipLaunchKernelGGL(transpose_mark_kernel, dim3(bandwidth_grid(nnz)), dim3(TB), 0, 0, rp, m, nnz, row, ids);
-		HIP_TRY(hipGetLastError());
-		int bits = 1;
-		while ((1L << bits) < n)
-			bits++;
-		const unsigned * key = reinterpret_cast<const unsigned *>(ci);        // columns are in [0, n): non-negative
-		size_t bytes = 0;
-		HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, key, key_sorted, ids, ids_sorted, (int) nnz, 0, bits, (hipStream_t) 0));
-		void * sort_tmp;
-		if (tmp.get(&sort_tmp, bytes))
-			return 1;
-		HIP_TRY(hipcub::DeviceRadixSort::SortPairs(sort_tmp, bytes, key, key_sorted, ids, ids_sorted, (int) nnz, 0, bits, (hipStream_t) 0));
-		hipLaunchKernelGGL(transpose_start_kernel, dim3((unsigned) ((n + 1 + TB - 1) / TB)), dim3(TB), 0, 0, key_sorted, nnz, n, rp_t);
-		HIP_TRY(hipGetLastError());
 		hipLaunchKernelGGL(transpose_gather_kernel, dim3(bandwidth_grid((nnz + 3) / 4)), dim3(TB), 0, 0, ids_sorted, row, va, nnz, ci_t, va_t);
 		HIP_TRY(hipGetLastError());
 	}
@@ -186,6 +249,96 @@ transpose_csr_device(long m, long n, long nnz, const int * rp, const int * ci, c
 	*rp_t_out = rp_t;
 	*ci_t_out = ci_t;
 	*va_t_out = va_t;
+	return 0;
+}
+
+// The entry map of the transposition for the rows [r0, r1) of A^t, from the (validated) host pattern of A: *d_lrp_out = the block's row
+// pointer from 0 (r1 - r0 + 1 entries), *d_src_out = for every entry of the block the number of that entry in the CSR of A
+// (*lnnz_out entries, 16-byte aligned), both device allocations the caller frees. on_device: transpose_order() on the uploaded pattern;
+// otherwise transpose_csr_host() carries the entry numbers in place of the values (the checker: the same bytes).
+// Transient device memory: the pattern of A, the row pointer of A^t, and on the device what the transposition takes without its value
+// arrays (16 bytes per non-zero + the sort's scratch).
+int
+transpose_entry_map(bool on_device, long m, long n, long nnz, const int * rp, const int * ci, long r0, long r1, int ** d_lrp_out, unsigned ** d_src_out,
+		long * lnnz_out)
+{
+	*d_lrp_out = nullptr;
+	*d_src_out = nullptr;
+	*lnnz_out = 0;
+	if (transpose_sizes_bad(m, n, nnz))
+		return 1;
+	if (r0 < 0 || r1 > n || r0 > r1)
+	{
+		set_error("transpose: bad row block [%ld,%ld) for %ld rows", r0, r1, n);
+		return 1;
+	}
+	Scratch out, tmp;
+	int * d_rp_t, * d_lrp;
+	unsigned * d_src = nullptr, * d_ids = nullptr;
+	if (tmp.get(&d_rp_t, (size_t) (n + 1) * 4) || out.get(&d_lrp, (size_t) (r1 - r0 + 1) * 4))
+		return 1;
+	if (nnz == 0)
+		HIP_TRY(hipMemset(d_rp_t, 0, (size_t) (n + 1) * 4));
+	else if (on_device)
+	{
+		int * d_rp, * d_ci, * row;
+		if (tmp.get(&d_rp, (size_t) (m + 1) * 4) || tmp.get(&d_ci, (size_t) nnz * 4))
+			return 1;
+		HIP_TRY(hipMemcpy(d_rp, rp, (size_t) (m + 1) * 4, hipMemcpyHostToDevice));
+		HIP_TRY(hipMemcpy(d_ci, ci, (size_t) nnz * 4, hipMemcpyHostToDevice));
+		if (transpose_order(m, n, nnz, d_rp, d_ci, tmp, d_rp_t, &row, &d_ids))
+			return 1;
+	}
+	else
+	{
+		std::vector<double> number((size_t) nnz), number_t;
+		#pragma omp parallel for num_threads(spmv::host_threads())
+		for (long e = 0; e < nnz; e++)
+			number[(size_t) e] = (double) e;                    // exact: nnz < 2^31
+		std::vector<int> rp_t, ci_t;
+		transpose_csr_host(m, n, nnz, rp, ci, number.data(), rp_t, ci_t, number_t);
+		std::vector<unsigned> ids((size_t) nnz);
+		#pragma omp parallel for num_threads(spmv::host_threads())
+		for (long e = 0; e < nnz; e++)
+			ids[(size_t) e] = (unsigned) number_t[(size_t) e];
+		if (tmp.get(&d_ids, (size_t) nnz * 4))
+			return 1;
+		HIP_TRY(hipMemcpy(d_rp_t, rp_t.data(), (size_t) (n + 1) * 4, hipMemcpyHostToDevice));
+		HIP_TRY(hipMemcpy(d_ids, ids.data(), (size_t) nnz * 4, hipMemcpyHostToDevice));
+	}
+	int ends[2] = {0, 0};
+	HIP_TRY(hipMemcpy(&ends[0], d_rp_t + r0, 4, hipMemcpyDeviceToHost));         // null stream: behind the kernels above
+	HIP_TRY(hipMemcpy(&ends[1], d_rp_t + r1, 4, hipMemcpyDeviceToHost));
+	const long lnnz = (long) ends[1] - ends[0];
+	if (ends[0] < 0 || lnnz < 0 || ends[1] > nnz)
+	{
+		set_error("transpose: row pointer of the transposed matrix out of range (%d, %d of %ld)", ends[0], ends[1], nnz);
+		return 1;
+	}
+	if (out.get(&d_src, (size_t) lnnz * 4))
+		return 1;
+	hipLaunchKernelGGL(transpose_block_kernel, dim3((unsigned) ((r1 - r0 + 1 + TB - 1) / TB)), dim3(TB), 0, 0, d_rp_t, r0, r1 - r0, d_lrp);
+	HIP_TRY(hipGetLastError());
+	if (lnnz)
+		HIP_TRY(hipMemcpy(d_src, d_ids + ends[0], (size_t) lnnz * 4, hipMemcpyDeviceToDevice));
+	HIP_TRY(hipDeviceSynchronize());
+	tmp.release();
+	out.ptrs.clear();
+	*d_lrp_out = d_lrp;
+	*d_src_out = d_src;
+	*lnnz_out = lnnz;
+	return 0;
+}
+
+// va_t[e] = va[src[e]] for the nnz entries of a map transpose_entry_map() made, enqueued on st. src and va_t are 16-byte aligned
+// device allocations; every src[e] indexes va.
+int
+transpose_gather_values(const unsigned * src, const double * va, long nnz, double * va_t, hipStream_t st)
+{
+	if (nnz <= 0)
+		return 0;
+	hipLaunchKernelGGL(values_gather_kernel, dim3(bandwidth_grid((nnz + 3) / 4)), dim3(TB), 0, st, src, va, nnz, va_t);
+	HIP_TRY(hipGetLastError());
 	return 0;
 }
 

@@ -387,12 +387,10 @@ is_sell(const spmv_mi355x_matrix * A)
 	return A->format == SPMV_MI355X_SELL_C_SIGMA;
 }
 
-// why this handle's values cannot be replaced in place (nullptr: they can)
+// why this handle's values cannot be replaced in place whatever map it is given (nullptr: they can)
 static const char *
-update_refusal(const spmv_mi355x_matrix * A)
+update_refusal_of_layout(const spmv_mi355x_matrix * A)
 {
-	if (A->transposed)
-		return "the handle was created with transpose = 1: its entries are not in the caller's order";
 	if (A->upd_col_filter)
 		return "the handle was created with a column filter (col_filter_mode): its entries are a subset of the caller's";
 	if (A->upd_symmetric)
@@ -402,6 +400,64 @@ update_refusal(const spmv_mi355x_matrix * A)
 	if (A->cfg.unit)
 		return "the handle dropped its value stream because its values were uniform (a _unit layout)";
 	return nullptr;
+}
+
+static const char * const TRANSPOSED_UNMAPPED = "the handle was created with transpose = 1: its entries are not in the caller's order "
+                                                "(call spmv_mi355x_update_values_prepare_transposed with the pattern of A)";
+
+// why this handle takes no update as it is: a transposed handle needs its entry map first (update_values_prepare_transposed)
+static const char *
+update_refusal(const spmv_mi355x_matrix * A)
+{
+	if (A->transposed && !A->d_upd_src)
+		return TRANSPOSED_UNMAPPED;
+	return update_refusal_of_layout(A);
+}
+
+// What prepare keeps. d_rp: a device row pointer of rows() + 1 entries from 0 to nnz(), checked against the layout (SELL: every slice's
+// stored width against the longest of its rows). d_src: the entry map that goes with it (transposed handles), or nullptr.
+// 0 = both are the handle's now, what it kept before is freed; 1 = error set (`what: subject does not match ...`), both still the caller's.
+static int
+keep_row_ptr(spmv_mi355x_matrix * A, int * d_rp, unsigned * d_src, long count, const char * what, const char * subject)
+{
+	const long m = A->m;
+	if (is_sell(A) && A->sell_slices > 0)
+	{
+		DevScratch guard;
+		int * flag;
+		if (guard.get(&flag, 4))
+			return 1;
+		HIP_TRY(hipMemset(flag, 0, 4));
+		const int C = A->sell_c;
+		const int layout = A->sell_window ? 1 : A->sell_delta ? 2 : 0;
+		const int round = layout == 1 ? 4 : layout == 2 ? 1 : (C >= WAVE ? 1 : WAVE / C);
+		const int64_t * ptr = layout == 0 ? A->d_slice_ptr : A->d_sell_desc;
+		hipLaunchKernelGGL(check_widths_kernel, dim3((unsigned) ((A->sell_slices + UPD_BLOCK - 1) / UPD_BLOCK)), dim3(UPD_BLOCK), 0, 0, d_rp, A->d_row_of_sorted, m,
+				A->sell_slices, C, round, layout, ptr, flag);
+		HIP_TRY(hipGetLastError());
+		int flag_host = 0;
+		HIP_TRY(hipMemcpy(&flag_host, flag, 4, hipMemcpyDeviceToHost));
+		if (flag_host)
+		{
+			set_error("%s: %s does not match the pattern this handle was built from", what, subject);
+			return 1;
+		}
+	}
+	size_t cap = 0;
+	if (A->d_val && hipMemPtrGetInfo(A->d_val, &cap) != hipSuccess)
+	{
+		(void) hipGetLastError();
+		cap = 0;                                           // unknown: the first update that needs room allocates
+	}
+	if (A->d_upd_row_ptr)
+		(void) hipFree(A->d_upd_row_ptr);
+	if (A->d_upd_src)
+		(void) hipFree(A->d_upd_src);
+	A->d_upd_row_ptr = d_rp;
+	A->d_upd_src = d_src;
+	A->upd_count = d_src ? count : 0;
+	A->val_capacity = cap;
+	return 0;
 }
 
 static unsigned
@@ -589,7 +645,7 @@ spmv_mi355x_update_values_prepare(spmv_mi355x_matrix * A, const int32_t * row_pt
 		set_error("update_values_prepare: NULL %s", !A ? "handle" : "row_ptr");
 		return 1;
 	}
-	if (const char * why = update_refusal(A))
+	if (const char * why = A->transposed ? TRANSPOSED_UNMAPPED : update_refusal(A))
 	{
 		set_error("update_values_prepare: %s", why);
 		return 1;
@@ -617,45 +673,97 @@ spmv_mi355x_update_values_prepare(spmv_mi355x_matrix * A, const int32_t * row_pt
 	DevScratch guard;
 	guard.ptrs.push_back(d_rp);
 	HIP_TRY(hipMemcpy(d_rp, row_ptr, ((size_t) m + 1) * 4, hipMemcpyHostToDevice));
-	if (is_sell(A) && A->sell_slices > 0)
-	{
-		int * flag;
-		if (guard.get(&flag, 4))
-			return 1;
-		HIP_TRY(hipMemset(flag, 0, 4));
-		const int C = A->sell_c;
-		const int layout = A->sell_window ? 1 : A->sell_delta ? 2 : 0;
-		const int round = layout == 1 ? 4 : layout == 2 ? 1 : (C >= WAVE ? 1 : WAVE / C);
-		const int64_t * ptr = layout == 0 ? A->d_slice_ptr : A->d_sell_desc;
-		hipLaunchKernelGGL(check_widths_kernel, dim3((unsigned) ((A->sell_slices + UPD_BLOCK - 1) / UPD_BLOCK)), dim3(UPD_BLOCK), 0, 0, d_rp, A->d_row_of_sorted, m,
-				A->sell_slices, C, round, layout, ptr, flag);
-		HIP_TRY(hipGetLastError());
-		int flag_host = 0;
-		HIP_TRY(hipMemcpy(&flag_host, flag, 4, hipMemcpyDeviceToHost));
-		if (flag_host)
-		{
-			set_error("update_values_prepare: row_ptr does not match the pattern this handle was built from");
-			return 1;
-		}
-	}
-	size_t cap = 0;
-	if (A->d_val && hipMemPtrGetInfo(A->d_val, &cap) != hipSuccess)
-	{
-		(void) hipGetLastError();
-		cap = 0;                                           // unknown: the first update that needs room allocates
-	}
-	guard.ptrs.erase(guard.ptrs.begin());                  // the copy stays with the handle
-	if (A->d_upd_row_ptr)
-		(void) hipFree(A->d_upd_row_ptr);
-	A->d_upd_row_ptr = d_rp;
-	A->val_capacity = cap;
+	if (keep_row_ptr(A, d_rp, nullptr, 0, "update_values_prepare", "row_ptr"))
+		return 1;
+	guard.ptrs.clear();                                    // the copy stays with the handle
 	return 0;
+}
+
+// A handle built with transpose = 1, from values in A's entry order: the pattern of A once more -> the entry map (transpose_csr.hip)
+int
+spmv_mi355x_update_values_prepare_transposed(spmv_mi355x_matrix * At, long m, long n, const int32_t * row_ptr, const int32_t * col_idx)
+{
+	const char * const what = "update_values_prepare_transposed";
+	if (!At || !row_ptr || (!col_idx && At->t_nnz > 0))
+	{
+		set_error("%s: NULL %s", what, !At ? "handle" : !row_ptr ? "row_ptr" : "col_idx");
+		return 1;
+	}
+	if (!At->transposed)
+	{
+		set_error("%s: the handle was not created with transpose = 1 (its entries are the caller's: spmv_mi355x_update_values_prepare)", what);
+		return 1;
+	}
+	if (const char * why = update_refusal_of_layout(At))
+	{
+		set_error("%s: %s", what, why);
+		return 1;
+	}
+	if (m != At->n || n != At->t_rows)
+	{
+		set_error("%s: the pattern is %ld x %ld, the handle was created from a matrix of %ld x %ld", what, m, n, At->n, At->t_rows);
+		return 1;
+	}
+	if (row_ptr[0] != 0)
+	{
+		set_error("%s: row_ptr must start at 0 (got %d)", what, row_ptr[0]);
+		return 1;
+	}
+	long bad = -1;
+	#pragma omp parallel for num_threads(spmv::host_threads()) reduction(max : bad)
+	for (long i = 0; i < m; i++)
+		if (row_ptr[i + 1] < row_ptr[i])
+			bad = std::max(bad, i);
+	if (bad >= 0)
+	{
+		set_error("%s: row_ptr is not monotone at row %ld", what, bad);
+		return 1;
+	}
+	const long nnz = row_ptr[m];
+	if (nnz != At->t_nnz)
+	{
+		set_error("%s: row_ptr[m] = %ld does not match the nnz = %ld of the matrix the handle was created from", what, nnz, At->t_nnz);
+		return 1;
+	}
+	#pragma omp parallel for num_threads(spmv::host_threads()) reduction(max : bad)
+	for (long j = 0; j < nnz; j++)
+		if (col_idx[j] < 0 || col_idx[j] >= n)
+			bad = std::max(bad, j);
+	if (bad >= 0)
+	{
+		set_error("%s: column index %d out of range [0,%ld) at entry %ld", what, col_idx[bad], n, bad);
+		return 1;
+	}
+	HIP_TRY(hipSetDevice(At->device));
+	int * d_lrp = nullptr;
+	unsigned * d_src = nullptr;
+	long lnnz = 0;
+	if (transpose_entry_map(At->convert_on_device, m, n, nnz, row_ptr, col_idx, At->t_row_begin, At->t_row_end, &d_lrp, &d_src, &lnnz))
+		return 1;
+	DevScratch guard;
+	guard.ptrs = {d_lrp, d_src};
+	if (lnnz != At->nnz)
+	{
+		set_error("%s: the rows [%ld,%ld) of the transposed pattern hold %ld entries, the handle's nnz = %ld: the pattern does not match the pattern "
+		          "this handle was built from", what, At->t_row_begin, At->t_row_end, lnnz, At->nnz);
+		return 1;
+	}
+	if (keep_row_ptr(At, d_lrp, d_src, nnz, what, "the pattern"))
+		return 1;
+	guard.ptrs.clear();                                    // both stay with the handle
+	return 0;
+}
+
+long
+spmv_mi355x_update_values_count(const spmv_mi355x_matrix * A)
+{
+	return !A ? -1 : A->d_upd_src ? A->upd_count : A->nnz;
 }
 
 int
 spmv_mi355x_update_values_device(spmv_mi355x_matrix * A, const double * values_dev, void * hip_stream)
 {
-	if (!A || (!values_dev && A->nnz > 0))
+	if (!A || (!values_dev && spmv_mi355x_update_values_count(A) > 0))
 	{
 		set_error("update_values_device: NULL %s", !A ? "handle" : "values");
 		return 1;
@@ -680,6 +788,16 @@ spmv_mi355x_update_values_device(spmv_mi355x_matrix * A, const double * values_d
 	HIP_TRY(hipGetDevice(&cur));
 	if (cur != A->device)
 		HIP_TRY(hipSetDevice(A->device));
+	// a transposed handle: the values arrive in A's entry order; one gather through the entry map puts them in the handle's local CSR
+	// order, and everything below runs on that transient array as on a caller's
+	DevScratch mapped;
+	if (A->d_upd_src && A->nnz > 0)
+	{
+		double * va_t = nullptr;
+		if (mapped.get(&va_t, (size_t) A->nnz * 8) || transpose_gather_values(A->d_upd_src, values_dev, A->nnz, va_t, st))
+			return 1;
+		values_dev = va_t;
+	}
 	int rc = 0;
 	if (A->nnz == 0)
 		HIP_TRY(hipStreamSynchronize(st));
@@ -700,7 +818,8 @@ spmv_mi355x_update_values_device(spmv_mi355x_matrix * A, const double * values_d
 int
 spmv_mi355x_update_values(spmv_mi355x_matrix * A, const double * values_host)
 {
-	if (!A || (!values_host && A->nnz > 0))
+	const long count = spmv_mi355x_update_values_count(A);
+	if (!A || (!values_host && count > 0))
 	{
 		set_error("update_values: NULL %s", !A ? "handle" : "values");
 		return 1;
@@ -718,10 +837,10 @@ spmv_mi355x_update_values(spmv_mi355x_matrix * A, const double * values_host)
 	HIP_TRY(hipSetDevice(A->device));
 	DevScratch tmp;
 	double * d_va = nullptr;
-	if (tmp.get(&d_va, (size_t) A->nnz * 8))
+	if (tmp.get(&d_va, (size_t) count * 8))
 		return 1;
-	if (A->nnz)
-		HIP_TRY(hipMemcpy(d_va, values_host, (size_t) A->nnz * 8, hipMemcpyHostToDevice));
+	if (count)
+		HIP_TRY(hipMemcpy(d_va, values_host, (size_t) count * 8, hipMemcpyHostToDevice));
 	return spmv_mi355x_update_values_device(A, d_va, nullptr);
 }
 

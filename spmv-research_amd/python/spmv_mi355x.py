@@ -61,6 +61,7 @@ SYMBOLS = [
     "spmv_mi355x_csr_stream_begin", "spmv_mi355x_csr_stream_append", "spmv_mi355x_create_from_stream", "spmv_mi355x_csr_stream_discard",
     "spmv_mi355x_spmm_device_async", "spmv_mi355x_time_spmm_device", "spmv_mi355x_spmm", "spmv_mi355x_spmm_plan",
     "spmv_mi355x_update_values_prepare", "spmv_mi355x_update_values", "spmv_mi355x_update_values_device", "spmv_mi355x_update_values_state",
+    "spmv_mi355x_update_values_prepare_transposed", "spmv_mi355x_update_values_count",
 ]
 
 _lib = None
@@ -83,7 +84,7 @@ def lib():
         L.spmv_mi355x_format_name.restype = C.c_char_p
         L.spmv_mi355x_mem_footprint.restype = C.c_double
         L.spmv_mi355x_csr_mem_footprint.restype = C.c_double
-        for f in ("spmv_mi355x_rows", "spmv_mi355x_cols", "spmv_mi355x_nnz"):
+        for f in ("spmv_mi355x_rows", "spmv_mi355x_cols", "spmv_mi355x_nnz", "spmv_mi355x_update_values_count"):
             getattr(L, f).restype = C.c_long
         L.spmv_mi355x_partitioned_format_name.restype = C.c_char_p
         L.spmv_mi355x_partitioned_exchange.restype = C.c_char_p
@@ -426,17 +427,32 @@ class Matrix:
             raise ValueError(f"row_ptr must have {self.m + 1} entries, got {row_ptr.shape}")
         _check(lib().spmv_mi355x_update_values_prepare(self.h, _p(row_ptr)))
 
+    def update_values_prepare_transposed(self, row_ptr, col_idx, m, n):
+        """Once per handle created with transpose=1, before its first update: the pattern of A (m x n) as the handle was created from.
+        From then on update_values takes update_values_count() values in A's entry order (spmv_mi355x_update_values_prepare_transposed)."""
+        row_ptr = np.ascontiguousarray(row_ptr, np.int32)
+        col_idx = np.ascontiguousarray(col_idx, np.int32)
+        if row_ptr.shape != (m + 1,) or col_idx.shape != (int(row_ptr[-1]),):
+            raise ValueError(f"row_ptr must have {m + 1} entries and col_idx row_ptr[m], got {row_ptr.shape} and {col_idx.shape}")
+        _check(lib().spmv_mi355x_update_values_prepare_transposed(self.h, C.c_long(m), C.c_long(n), _p(row_ptr), _p(col_idx)))
+
+    def update_values_count(self):
+        """The values an update of this handle reads: nnz, and the nnz of A once update_values_prepare_transposed has run."""
+        return lib().spmv_mi355x_update_values_count(self.h)
+
     def update_values(self, values):
-        """Replace the stored values by nnz fp64 values in the order of the handle's local CSR (spmv_mi355x_update_values); what
-        create() derives from the values (format_name, mem_footprint) is refreshed."""
+        """Replace the stored values by update_values_count() fp64 values in the order of the handle's local CSR — of the CSR of A
+        for a prepared transposed handle (spmv_mi355x_update_values); what create() derives from the values (format_name,
+        mem_footprint) is refreshed."""
         values = np.ascontiguousarray(values, np.float64)
-        if values.shape != (self.nnz,):
-            raise ValueError(f"values must have {self.nnz} entries, got {values.shape}")
+        count = self.update_values_count()
+        if values.shape != (count,):
+            raise ValueError(f"values must have {count} entries, got {values.shape}")
         _check(lib().spmv_mi355x_update_values(self.h, _p(values)))
         self._describe()
 
     def update_values_device(self, ptr, stream=0):
-        """The same from nnz fp64 values resident on the handle's device, ordered on `stream`; blocking."""
+        """The same from update_values_count() fp64 values resident on the handle's device, ordered on `stream`; blocking."""
         _check(lib().spmv_mi355x_update_values_device(self.h, C.c_void_p(ptr), C.c_void_p(stream)))
         self._describe()
 

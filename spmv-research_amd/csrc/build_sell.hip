@@ -188,6 +188,7 @@ sell_delta_names(spmv_mi355x_matrix * A)
 	else
 		snprintf(A->format_name, sizeof(A->format_name), "MI355X_SELLD_%d_%ld_%s%s", A->sell_c, A->sell_sigma, pf, v7);
 	snprintf(A->kernel_name, sizeof(A->kernel_name), A->mixed() ? "sell_delta_mixed_kernel" : "sell_delta_kernel");
+	A->kernel_block = (A->sell_split == 1 && !A->f32 && !A->mixed()) ? WAVE * SELL_DELTA_WAVES : 256;
 	// the auto rule of init_handle on the bytes really stored; without 7-byte slices init_handle's own answer (an update of the values
 	// can take the last 7-byte slice away)
 	A->cfg.nt = (A->sell_v7_slices && A->opt_nontemporal == 0) ? (A->mem_footprint > 192.0 * 1024 * 1024 ? 1 : 0) : A->nt_init;

@@ -551,9 +551,36 @@ sell_delta_one(const int64_t * __restrict__ desc, int slice, const unsigned char
 			g0, gs);
 }
 
-// one wave per slice (V7: the compiler's own choice of 109 VGPRs would cost a wave per SIMD against the plain kernel's 96; held to 5 waves it takes 92, no scratch)
-template <typename T, bool NT, bool V7>
-__global__ __launch_bounds__(SELL_BLOCK) __attribute__((amdgpu_waves_per_eu(V7 ? 5 : 1))) void
+// sell_delta_kernel has a workgroup size of its own (launch.hpp: SELL_DELTA_WAVES), apart from the SELL_WAVES that
+// sell_delta_split_kernel needs for its LDS sums: ONE slice = one wave per workgroup for fp64 (the nlpkkt240 twin: 1.05 ms against
+// 1.09 - 1.10 at four, 1.07 - 1.08 at two; the 8-byte kernel 1.13 against 1.18; profiles/r13_sell_v7_bound.txt). A wave that finishes
+// its slice early no longer holds its workgroup's slot until the other three are through. fp32 keeps four (not measured).
+static_assert(SELL_WAVES % SELL_DELTA_WAVES == 0, "the handle's tiles are whole numbers of sell_delta_kernel's");
+template <typename T> constexpr int sell_delta_waves() { return sizeof(T) == 8 ? SELL_DELTA_WAVES : SELL_WAVES; }
+
+// The handle's tile map counts tiles of SELL_WAVES slices (launch.hpp: sell_slices_per_tile). The same map for tiles of W slices:
+// F = SELL_WAVES / W times as many tiles, chunks of F times as many tiles (the same 16 384 rows per chunk), the work-balanced ranges
+// cut at the same slices. Every tile, and so every slice, is still dealt exactly once: xcd_tile maps the grid one-to-one onto the tile
+// numbers below the grid size for any chunk, and the ranges [start[k], start[k+1]) still partition [0, ntiles).
+template <int W>
+static XcdMap
+sell_delta_tile_map(const XcdMap & mp, int num_slices)
+{
+	constexpr unsigned F = SELL_WAVES / W;
+	XcdMap o = mp;
+	o.ntiles = ((unsigned) num_slices + W - 1) / W;
+	o.chunk = mp.chunk * F;
+	for (int k = 0; k < NUM_XCD; k++)
+		o.start[k] = mp.start[k] * F < o.ntiles ? mp.start[k] * F : o.ntiles;
+	o.start[NUM_XCD] = o.ntiles;
+	return o;
+}
+
+// one wave per slice, W of them per workgroup. No occupancy attribute: left alone the compiler gives the V7 kernel 107 VGPRs = 4 waves
+// per SIMD, which measured no slower than the 5 waves at 92 VGPRs it was held to before and faster at W = 1 (1.049 - 1.050 against
+// 1.051 - 1.090 ms, no scratch either way; profiles/r13_sell_v7_bound.txt).
+template <typename T, bool NT, bool V7, int W = sell_delta_waves<T>()>
+__global__ __launch_bounds__(W * WAVE) void
 sell_delta_kernel(const int64_t * __restrict__ desc, const unsigned char * __restrict__ idx, const T * __restrict__ val,
 		const int * __restrict__ row_of_sorted, const T * __restrict__ x, T * __restrict__ y,
 		int m, int num_slices, int beta, XcdMap map)
@@ -562,7 +589,7 @@ sell_delta_kernel(const int64_t * __restrict__ desc, const unsigned char * __res
 	if (tile == NO_TILE)
 		return;
 	const int lane = threadIdx.x % WAVE;
-	const int slice = __builtin_amdgcn_readfirstlane((int) (tile * SELL_WAVES + threadIdx.x / WAVE));
+	const int slice = __builtin_amdgcn_readfirstlane((int) (tile * W + threadIdx.x / WAVE));
 	if (slice >= num_slices)
 		return;
 	const T s = sell_delta_one<T, NT, V7>(desc, slice, idx, val, lane, x, 0, 1);
@@ -714,8 +741,16 @@ sell_delta_launch(int S, const int64_t * desc, const unsigned char * idx, const 
 	}
 	else if (S == 1)
 	{
-		if (cfg.nt) SELLD_LAUNCH((sell_delta_kernel<T, true, V7>));
-		else        SELLD_LAUNCH((sell_delta_kernel<T, false, V7>));
+		constexpr int W = sell_delta_waves<T>();
+		const XcdMap map1 = sell_delta_tile_map<W>(cfg.map, num_slices);
+		grid = xcd_grid(map1);
+		if (grid_out)
+			*grid_out = grid;
+		#define SELLD_LAUNCH1(K) hipLaunchKernelGGL(K, dim3(grid), dim3(W * WAVE), 0, stream, desc, idx, (const T *) val, \
+				row_of_sorted, (const T *) x, (T *) y, m, num_slices, cfg.beta, map1)
+		if (cfg.nt) SELLD_LAUNCH1((sell_delta_kernel<T, true, V7>));
+		else        SELLD_LAUNCH1((sell_delta_kernel<T, false, V7>));
+		#undef SELLD_LAUNCH1
 	}
 	else if (S == 2)
 	{

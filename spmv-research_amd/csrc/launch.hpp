@@ -23,6 +23,10 @@ inline long csr_scalar_rows_per_tile() { return 256; }
 inline long csr_vector_rows_per_tile(int lanes_per_row, int rows_per_group = 1) { return 256L / lanes_per_row * rows_per_group; }
 inline long csr_stream_rows_per_tile(int rows_per_wave) { return 4L * rows_per_wave; }
 inline long sell_slices_per_tile() { return 4; }
+// sell_delta_kernel (one wave per slice, fp64 vectors over fp64 values) has a workgroup size of its own: this many slices = waves per
+// workgroup. Its tile map is derived from the handle's at launch (kernels_sell.hip: sell_delta_tile_map), which keeps counting tiles of
+// sell_slices_per_tile() slices for every other kernel of the layout.
+constexpr int SELL_DELTA_WAVES = 1;
 inline long coo_waves_per_tile() { return 4; }
 
 // ---- CSR (kernels_csr.hip)

@@ -458,6 +458,67 @@ int  spmv_mi355x_cgls(spmv_mi355x_matrix * A, spmv_mi355x_matrix * At,
 		const void * b_host, void * x_out_host, double damp, double tol, long max_iterations,
 		double * history_out /* may be NULL: 2*max_iterations doubles */, spmv_mi355x_lsq_info * info /* may be NULL */);
 
+/* ---- MINRES: symmetric indefinite systems over one handle ------------------------------------------------------------------- */
+/* (A - shift * I) x = b from x0 = 0 for a square SYMMETRIC matrix: indefinite, singular-but-consistent, saddle-point (KKT) matrices
+ * with a zero diagonal block included — what pcg / pbicgstab refuse ("zero in diagonal") and what CG is not defined for. Paige and
+ * Saunders' MINRES with an optional DIAGONAL preconditioner given as its inverse, M^-1 = diag(minv): one SpMV per iteration, short
+ * recurrences, the residual (in the M^-1 norm) never increases, the diagonal of A is never needed. Every vector is resident in
+ * device memory (csrc/solver_minres.hip; 1 SpMV + 3 vector launches per iteration). The recurrences are scipy's
+ * minres without its norm-estimate stopping tests, every scalar fp64:
+ *     r1 = b; y = M^-1 b; beta1 = sqrt(b.y)                                        (b.y == 0: stop 3; < 0 or not finite: stop 4)
+ *     oldb = 0; beta = beta1; dbar = 0; epsln = 0; phibar = beta1; cs = -1; sn = 0; w = w2 = 0; r2 = r1
+ *     loop itn = 1, 2, ...:
+ *         v = y / beta;  y = A v - shift v;  if itn >= 2: y -= (beta/oldb) r1
+ *         alfa = v.y;    y -= (alfa/beta) r2;  r1 = r2;  r2 = y;  y = M^-1 r2
+ *         oldb = beta;   beta^2 = r2.y                        (negative or not finite: stop 4, x untouched by this iteration)
+ *         beta = sqrt(beta^2)
+ *         oldeps = epsln; delta = cs dbar + sn alfa; gbar = sn dbar - cs alfa; epsln = sn beta; dbar = -cs beta
+ *         gamma = max(hypot(gbar, beta), DBL_EPSILON); cs = gbar/gamma; sn = beta/gamma; phi = cs phibar; phibar = sn phibar
+ *         w1 = w2; w2 = w; w = (v - oldeps w1 - delta w2) / gamma;  x += phi w
+ *         history[itn-1] = phibar
+ *         if tol > 0 and phibar <= tol beta1: stop 1;  else if beta == 0: stop 5
+ *   - b_host, x_out_host and minv_host: rows() values of the handle's precision. Scalars and dot products are fp64 in both precisions.
+ *   - minv_host (may be NULL): every entry finite and > 0. NULL = no preconditioner: no extra vector is stored and no multiply is
+ *     issued. The library derives no preconditioner itself: the caller knows whether 1/|a_ii|, a row norm or nothing suits its zero
+ *     block.
+ *   - any format and layout serves (the solver only calls spmv_mi355x_spmv_device_async): value_storage = 1, 7-byte values and
+ *     symmetric_input = 1 handles included; on handles whose SpMV is deterministic the whole solve is, bit for bit. The solver's
+ *     vectors are plain allocations (placement is not used, as in pcg and cgls).
+ *   - tol == 0 is legal and means "never stop on the tolerance". max_iterations == 0 returns x = 0, stop 2 and rnorm = rnorm0.
+ *     On stop 3 x = 0 and every norm is 0.
+ *   - history_out (may be NULL): max_iterations doubles; entry k = phibar after loop body k + 1, the RECURSIVE residual in the M^-1
+ *     norm; entries >= info->iterations stay 0.
+ *   - after a stop the iteration is frozen on the device: x, iterations and the history are those of the iteration at which the
+ *     rule fired, however far the host had run ahead (at most 64 iterations).
+ *   - rc 1, a last_error that names minres, every caller buffer and info untouched. First the scalars, before any device is touched
+ *     and before the NULL checks: info->struct_size < 8; shift not finite; tol negative or not finite; max_iterations < 0. Then a
+ *     NULL A, b or x_out. Then rows() != cols() (the message gives both; this also refuses row-block handles). Then a minv entry
+ *     that is not finite or is <= 0 (the message names the first such index): a host pass over the n values before any launch.
+ *   - NOT CHECKABLE: that A is symmetric — on an unsymmetric matrix the recurrences run on and mean nothing; that a
+ *     symmetric_input = 1 handle holds what the caller thinks it holds.
+ *   - NOT BUILT: multi-RHS and row-partitioned forms, device-pointer b / x, scipy's Anorm / Acond estimates and the stopping tests
+ *     built on them. */
+typedef struct {
+	unsigned struct_size;   /* in: sizeof(spmv_mi355x_minres_info) */
+	long   iterations;      /* completed loop bodies */
+	int    stop;            /* 1 = phibar_k <= tol * beta1 (tol > 0)
+	                           2 = max_iterations reached
+	                           3 = b == 0 (beta1 == 0): x = 0, 0 iterations
+	                           4 = breakdown: r.(M^-1 r) negative or any scalar not finite;
+	                               x of the last good iteration is returned
+	                           5 = the Lanczos process ended (beta_{k+1} == 0) */
+	double rnorm;           /* |b - (A - shift I) x_out|, EXPLICIT (one SpMV after the loop) */
+	double rnorm0;          /* |b| */
+	double prnorm;          /* phibar at the stop: recursive residual in the M^-1 norm */
+	double prnorm0;         /* beta1 = sqrt(b . M^-1 b) */
+	double xnorm;           /* |x_out| */
+	long   spmv_calls;      /* the one explicit SpMV included */
+	double seconds;
+} spmv_mi355x_minres_info;
+int  spmv_mi355x_minres(spmv_mi355x_matrix * A, const void * b_host, void * x_out_host,
+		double shift, const void * minv_host /* may be NULL */, double tol, long max_iterations,
+		double * history_out /* may be NULL: max_iterations doubles */, spmv_mi355x_minres_info * info /* may be NULL */);
+
 /* Row-partitioned (multi-GPU) form of the same two solvers: one process per GPU owns the row block [row_offset,
  * row_offset + m_local) of A, b and x. The solver keeps every vector device-resident and local; the two things that cross
  * ranks are handed to the caller, who has the communicator (torch.distributed / RCCL in bench-level code):

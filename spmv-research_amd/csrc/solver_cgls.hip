@@ -6,7 +6,7 @@
 //           s = A^t r - damp x;  gamma' = s.s;  beta = gamma' / gamma;  p = s + beta p;  gamma = gamma'
 //           stop when sqrt(gamma') <= tol sqrt(gamma0)
 // Built like solvers.hip (state ping-pong, two-stage deterministic dots re-reduced by every block of the consumer, a device
-// `done` flag that predicates every later vector kernel off, the host-mapped progress word), on what solvers_common.hpp holds.
+// `done` flag that predicates every later vector kernel off) and driven by the same host loop: ProgressGate of solvers_common.hpp.
 // Per iteration: 2 SpMV + 4 vector launches
 //   q = A p | cgls_delta (q.q, p.p) | cgls_update (x, r, r.r) | s = A^t r | cgls_normal (s -= damp x, s.s) | cgls_direction (p, state).
 // Stored vectors: b, r, q (m values) and x, p, s (n values), nothing else.
@@ -263,6 +263,7 @@ cgls_solve(spmv_mi355x_matrix * A, spmv_mi355x_matrix * At, const void * b_host,
 	const auto t_start = std::chrono::steady_clock::now();
 	const long m = spmv_mi355x_rows(A), n = spmv_mi355x_cols(A);
 	hipStream_t stream = nullptr;
+	ProgressGate gate;                // outlives buf, whose hipFree waits for the kernels that post to it
 	DeviceBuffers buf;
 	const size_t mb = (size_t) m * sizeof(T), nbytes = (size_t) n * sizeof(T);
 
@@ -284,12 +285,7 @@ cgls_solve(spmv_mi355x_matrix * A, spmv_mi355x_matrix * At, const void * b_host,
 		ABI_TRY(buf.alloc(&history, hist_bytes));
 		HIP_TRY(hipMemsetAsync(history, 0, hist_bytes, stream));
 	}
-	HIP_TRY(hipHostMalloc(&buf.pinned, 2 * sizeof(long), hipHostMallocMapped | hipHostMallocCoherent));
-	volatile long * progress = (volatile long *) buf.pinned;          // [0] iterations finished, [1] break flag
-	progress[0] = 0;
-	progress[1] = -1;
-	long * progress_dev = nullptr;
-	HIP_TRY(hipHostGetDevicePointer((void **) &progress_dev, buf.pinned, 0));
+	ABI_TRY(gate.init());
 
 	HIP_TRY(hipMemcpyAsync(b, b_host, mb, hipMemcpyHostToDevice, stream));
 	HIP_TRY(hipMemsetAsync(x, 0, nbytes, stream));                   // x0 = 0
@@ -297,8 +293,7 @@ cgls_solve(spmv_mi355x_matrix * A, spmv_mi355x_matrix * At, const void * b_host,
 	HIP_TRY(hipMemsetAsync(part, 0, sizeof(double) * CGLS_SLOTS * MAX_PART, stream));
 	HIP_TRY(hipMemsetAsync(bad, 0, sizeof(int), stream));
 
-	auto blocks_for = [](long len) { return (int) std::min<long>(MAX_PART, std::max<long>(1, (len + 4 * VB - 1) / (4 * VB))); };
-	const int nb = std::max(blocks_for(m), blocks_for(n));           // ONE grid for both lengths (head of this file)
+	const int nb = std::max(solver_blocks(m), solver_blocks(n));     // ONE grid for both lengths (head of this file)
 	const dim3 grid(nb), block(VB), one(1);
 	long spmv_calls = 0;
 	auto spmv = [&](spmv_mi355x_matrix * M, const T * in, T * out) {
@@ -315,30 +310,10 @@ cgls_solve(spmv_mi355x_matrix * A, spmv_mi355x_matrix * At, const void * b_host,
 	long it = 0;
 	for (; it < max_iterations; it++)
 	{
-		if (it % POLL == 0 && it >= 2 * POLL)
-		{
-			// stay at most 2*POLL iterations ahead; plain reads of the mapped word, no HIP call
-			const auto t_wait = std::chrono::steady_clock::now();
-			long spins = 0;
-			while (progress[0] < it - POLL)
-			{
-				if ((++spins & 0xfff) == 0)
-				{
-					HIP_TRY(hipGetLastError());
-					if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t_wait).count() > 120.0)
-					{
-						set_error("cgls: the device made no progress for 120 s at iteration %ld", it);
-						(void) hipStreamSynchronize(stream);
-						return 1;
-					}
-				}
-				__builtin_ia32_pause();
-			}
-			// only what the device had posted by iteration it - POLL counts, never "whatever is visible now"
-			const long broke_at = progress[1];
-			if (broke_at >= 0 && broke_at <= it - POLL)
-				break;
-		}
+		bool stop;
+		ABI_TRY(gate.wait(it, "cgls", stream, &stop));
+		if (stop)
+			break;
 		CglsState * cur = st + (it & 1), * nxt = st + ((it + 1) & 1);
 		ABI_TRY(spmv(A, p, q));
 		hipLaunchKernelGGL((cgls_delta_kernel<T>), grid, block, 0, stream, cur, q, p, m, n, damp, part);
@@ -346,7 +321,7 @@ cgls_solve(spmv_mi355x_matrix * A, spmv_mi355x_matrix * At, const void * b_host,
 		ABI_TRY(spmv(At, r, s));
 		hipLaunchKernelGGL((cgls_normal_kernel<T>), grid, block, 0, stream, cur, s, x, n, damp, part, bad);
 		hipLaunchKernelGGL((cgls_direction_kernel<T>), grid, block, 0, stream, cur, nxt, s, p, n, nb, tol, part, history, it,
-				progress_dev, bad);
+				gate.dev, bad);
 	}
 	HIP_TRY(hipGetLastError());
 
@@ -367,12 +342,7 @@ cgls_solve(spmv_mi355x_matrix * A, spmv_mi355x_matrix * At, const void * b_host,
 	HIP_TRY(hipStreamSynchronize(stream));
 	if (info)
 	{
-		auto norm_of = [&](int slot) {
-			double v = 0;
-			for (int i = 0; i < nb; i++)
-				v += part_host[(size_t) slot * MAX_PART + i];
-			return std::sqrt(v);
-		};
+		auto norm_of = [&](int slot) { return std::sqrt(host_sum(part_host.data(), (size_t) slot * MAX_PART, nb)); };
 		spmv_mi355x_lsq_info out;
 		memset(&out, 0, sizeof(out));
 		out.iterations = st_host.k;
@@ -383,10 +353,7 @@ cgls_solve(spmv_mi355x_matrix * A, spmv_mi355x_matrix * At, const void * b_host,
 		out.xnorm = norm_of(C_XX);
 		out.spmv_calls = spmv_calls;
 		out.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
-		const unsigned want = info->struct_size;
-		out.struct_size = sizeof(out);
-		memcpy(info, &out, std::min<size_t>(want, sizeof(out)));
-		info->struct_size = (unsigned) std::min<size_t>(want, sizeof(out));
+		put_info(info, info->struct_size, out);
 	}
 	return 0;
 }
@@ -399,11 +366,8 @@ spmv_mi355x_cgls(spmv_mi355x_matrix * A, spmv_mi355x_matrix * At, const void * b
 {
 	using namespace spmv;
 	// the checks that need no handle come first, so each can be met (and tested) on its own
-	if (info && info->struct_size < 8)
-	{
-		set_error("cgls: info->struct_size not set");
+	if (!info_size_ok("cgls", info))
 		return 1;
-	}
 	if (!(damp >= 0) || !std::isfinite(damp))
 	{
 		set_error("cgls: damp must be finite and >= 0 (got %g)", damp);

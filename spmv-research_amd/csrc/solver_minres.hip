@@ -13,7 +13,7 @@
 //       w1 = w2; w2 = w; w = (v - oldeps w1 - delta w2) / gamma;  x += phi w
 //       stop when phibar <= tol beta1 (1), else when beta == 0 (5)
 // Built like solver_cgls.hip (state ping-pong, two-stage deterministic dots re-reduced by every block of the consumer, a device
-// `done` flag that predicates every later vector kernel off, the host-mapped progress word), on what solvers_common.hpp holds.
+// `done` flag that predicates every later vector kernel off) and driven by the same host loop: ProgressGate of solvers_common.hpp.
 // Per iteration: 1 SpMV + 3 vector launches
 //   y = A v | minres_lanczos (y -= shift v + (beta/oldb) r1, v.y) | minres_orth (y -= (alfa/beta) r2, y.(minv y)) |
 //   minres_update (rotation, w, x, next v, state).
@@ -278,6 +278,7 @@ minres_solve(spmv_mi355x_matrix * A, const void * b_host, void * x_host, double 
 	const auto t_start = std::chrono::steady_clock::now();
 	const long n = spmv_mi355x_rows(A);
 	hipStream_t stream = nullptr;
+	ProgressGate gate;                // outlives buf, whose hipFree waits for the kernels that post to it
 	DeviceBuffers buf;
 	const size_t nbytes = (size_t) n * sizeof(T);
 
@@ -297,19 +298,14 @@ minres_solve(spmv_mi355x_matrix * A, const void * b_host, void * x_host, double 
 		ABI_TRY(buf.alloc(&history, hist_bytes));
 		HIP_TRY(hipMemsetAsync(history, 0, hist_bytes, stream));
 	}
-	HIP_TRY(hipHostMalloc(&buf.pinned, 2 * sizeof(long), hipHostMallocMapped | hipHostMallocCoherent));
-	volatile long * progress = (volatile long *) buf.pinned;          // [0] iterations finished, [1] break flag
-	progress[0] = 0;
-	progress[1] = -1;
-	long * progress_dev = nullptr;
-	HIP_TRY(hipHostGetDevicePointer((void **) &progress_dev, buf.pinned, 0));
+	ABI_TRY(gate.init());
 
 	HIP_TRY(hipMemcpyAsync(b, b_host, nbytes, hipMemcpyHostToDevice, stream));
 	if (PRE)
 		HIP_TRY(hipMemcpyAsync(minv, minv_host, nbytes, hipMemcpyHostToDevice, stream));
 	HIP_TRY(hipMemsetAsync(part, 0, sizeof(double) * MINRES_SLOTS * MAX_PART, stream));
 
-	const int nb = (int) std::min<long>(MAX_PART, std::max<long>(1, (n + 4 * VB - 1) / (4 * VB)));
+	const int nb = solver_blocks(n);
 	const dim3 grid(nb), block(VB), one(1);
 	long spmv_calls = 0;
 	auto spmv = [&](const T * in, T * out) {
@@ -327,37 +323,17 @@ minres_solve(spmv_mi355x_matrix * A, const void * b_host, void * x_host, double 
 	long it = 0;
 	for (; it < max_iterations; it++)
 	{
-		if (it % POLL == 0 && it >= 2 * POLL)
-		{
-			// stay at most 2*POLL iterations ahead; plain reads of the mapped word, no HIP call
-			const auto t_wait = std::chrono::steady_clock::now();
-			long spins = 0;
-			while (progress[0] < it - POLL)
-			{
-				if ((++spins & 0xfff) == 0)
-				{
-					HIP_TRY(hipGetLastError());
-					if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t_wait).count() > 120.0)
-					{
-						set_error("minres: the device made no progress for 120 s at iteration %ld", it);
-						(void) hipStreamSynchronize(stream);
-						return 1;
-					}
-				}
-				__builtin_ia32_pause();
-			}
-			// only what the device had posted by iteration it - POLL counts, never "whatever is visible now"
-			const long broke_at = progress[1];
-			if (broke_at >= 0 && broke_at <= it - POLL)
-				break;
-		}
+		bool stop;
+		ABI_TRY(gate.wait(it, "minres", stream, &stop));
+		if (stop)
+			break;
 		MinresState * cur = st + (it & 1), * nxt = st + ((it + 1) & 1);
 		T * r1 = R[it % 3], * r2 = R[(it + 1) % 3], * y = R[(it + 2) % 3];
 		ABI_TRY(spmv(v, y));
 		hipLaunchKernelGGL((minres_lanczos_kernel<T>), grid, block, 0, stream, cur, y, v, r1, n, shift, part);
 		hipLaunchKernelGGL((minres_orth_kernel<T, PRE>), grid, block, 0, stream, cur, y, r2, minv, n, nb, part);
 		hipLaunchKernelGGL((minres_update_kernel<T, PRE>), grid, block, 0, stream, cur, nxt, x, v, W[it & 1], W[(it + 1) & 1], y,
-				minv, n, nb, tol, part, history, it, progress_dev);
+				minv, n, nb, tol, part, history, it, gate.dev);
 	}
 	HIP_TRY(hipGetLastError());
 
@@ -377,12 +353,7 @@ minres_solve(spmv_mi355x_matrix * A, const void * b_host, void * x_host, double 
 	HIP_TRY(hipStreamSynchronize(stream));
 	if (info)
 	{
-		auto norm_of = [&](int slot) {
-			double s = 0;
-			for (int i = 0; i < nb; i++)
-				s += part_host[(size_t) slot * MAX_PART + i];
-			return std::sqrt(s);
-		};
+		auto norm_of = [&](int slot) { return std::sqrt(host_sum(part_host.data(), (size_t) slot * MAX_PART, nb)); };
 		spmv_mi355x_minres_info out;
 		memset(&out, 0, sizeof(out));
 		out.iterations = st_host.k;
@@ -394,10 +365,7 @@ minres_solve(spmv_mi355x_matrix * A, const void * b_host, void * x_host, double 
 		out.xnorm = norm_of(M_XX);
 		out.spmv_calls = spmv_calls;
 		out.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
-		const unsigned want = info->struct_size;
-		out.struct_size = sizeof(out);
-		memcpy(info, &out, std::min<size_t>(want, sizeof(out)));
-		info->struct_size = (unsigned) std::min<size_t>(want, sizeof(out));
+		put_info(info, info->struct_size, out);
 	}
 	return 0;
 }
@@ -422,11 +390,8 @@ spmv_mi355x_minres(spmv_mi355x_matrix * A, const void * b_host, void * x_out_hos
 {
 	using namespace spmv;
 	// the checks that need no handle come first, so each can be met (and tested) on its own
-	if (info && info->struct_size < 8)
-	{
-		set_error("minres: info->struct_size not set");
+	if (!info_size_ok("minres", info))
 		return 1;
-	}
 	if (!std::isfinite(shift))
 	{
 		set_error("minres: shift must be finite (got %g)", shift);

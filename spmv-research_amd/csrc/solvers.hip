@@ -12,9 +12,8 @@
 //     the <= 1024 partials in a fixed order — deterministic, and no separate "finish the reduction" launch;
 //   * the `err < eps` break (bench_cg.cpp:238) becomes a device flag that predicates every later vector kernel off, so
 //     x, x_best, the counter and the history are frozen exactly where the reference breaks; the last kernel of every
-//     iteration also posts (iterations finished, done) into host-mapped pinned memory, which the host READS (no HIP call:
-//     hipEventSynchronize in this loop was measured to stall the queue for up to 100 ms at a time) to stop enqueueing
-//     after a break and to stay at most 2*POLL iterations ahead of the device;
+//     iteration also posts (iterations finished, loop count at the break) into the host-mapped progress word, which lets
+//     the host stop enqueueing after a break and stay at most 2*POLL iterations ahead (ProgressGate, solvers_common.hpp);
 //   * the vector updates around the SpMV are fused: CG = SpMV + 3 passes (p.Ap | x,r update + z.r, r.r | p update),
 //     BiCGSTAB = 2 SpMV + 5 passes. z = r/K and h = x + s_a*y are never materialised.
 // Same iteration semantics as the reference: Jacobi K = first stored diagonal entry (error on a zero), x0 = 0,
@@ -404,6 +403,7 @@ solve(int method, spmv_mi355x_matrix * A, const spmv_mi355x_dist_ops * dist, lon
 	const auto t_start = std::chrono::steady_clock::now();
 	const long m = dist ? m_arg : spmv_mi355x_rows(A);
 	hipStream_t stream = nullptr;
+	ProgressGate gate;                // outlives buf, whose hipFree waits for the kernels that post to it
 	DeviceBuffers buf;
 	const size_t vb = (size_t) m * sizeof(T);
 
@@ -435,12 +435,7 @@ solve(int method, spmv_mi355x_matrix * A, const spmv_mi355x_dist_ops * dist, lon
 		ABI_TRY(buf.alloc(&history, sizeof(double) * 3 * (size_t) max_iterations));
 		HIP_TRY(hipMemsetAsync(history, 0, sizeof(double) * 3 * (size_t) max_iterations, stream));
 	}
-	HIP_TRY(hipHostMalloc(&buf.pinned, 2 * sizeof(long), hipHostMallocMapped | hipHostMallocCoherent));
-	volatile long * progress = (volatile long *) buf.pinned;          // [0] iterations finished, [1] break flag
-	progress[0] = 0;
-	progress[1] = -1;
-	long * progress_dev = nullptr;
-	HIP_TRY(hipHostGetDevicePointer((void **) &progress_dev, buf.pinned, 0));
+	ABI_TRY(gate.init());
 
 	HIP_TRY(hipMemcpyAsync(b, b_host, vb, hipMemcpyHostToDevice, stream));
 	HIP_TRY(hipMemcpyAsync(K, K_host.data(), vb, hipMemcpyHostToDevice, stream));
@@ -448,7 +443,7 @@ solve(int method, spmv_mi355x_matrix * A, const spmv_mi355x_dist_ops * dist, lon
 	HIP_TRY(hipMemsetAsync(x_best, 0, vb, stream));
 	HIP_TRY(hipMemsetAsync(part, 0, sizeof(double) * NUM_SLOTS * MAX_PART, stream));
 
-	const int nb = (int) std::min<long>(MAX_PART, std::max<long>(1, (m + 4 * VB - 1) / (4 * VB)));
+	const int nb = solver_blocks(m);
 	const dim3 grid(nb), block(VB), one(1);
 	long spmv_calls = 0;
 	auto spmv = [&](const T * in, T * out) {
@@ -499,37 +494,14 @@ solve(int method, spmv_mi355x_matrix * A, const spmv_mi355x_dist_ops * dist, lon
 	HIP_TRY(hipGetLastError());
 
 	const bool debug = getenv("SPMV_MI355X_SOLVER_DEBUG") != nullptr;
-	double t_spin = 0;
 	const auto t_loop = std::chrono::steady_clock::now();
 	long it = 0;
 	for (; it < max_iterations; it++)
 	{
-		if (it % POLL == 0 && it >= 2 * POLL)
-		{
-			// stay at most 2*POLL iterations ahead; plain reads of the mapped word, no HIP call
-			const auto t_wait = std::chrono::steady_clock::now();
-			long spins = 0;
-			while (progress[0] < it - POLL)
-			{
-				if ((++spins & 0xfff) == 0)
-				{
-					HIP_TRY(hipGetLastError());
-					if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t_wait).count() > 120.0)
-					{
-						set_error("solver: the device made no progress for 120 s at iteration %ld", it);
-						(void) hipStreamSynchronize(stream);
-						return 1;
-					}
-				}
-				__builtin_ia32_pause();
-			}
-			t_spin += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_wait).count();
-			// stop rule that every rank of a distributed solve evaluates identically: only what the device had posted by
-			// iteration it - POLL counts (the wait above guarantees it is visible), never "whatever is visible now"
-			const long broke_at = progress[1];
-			if (broke_at >= 0 && broke_at <= it - POLL)
-				break;
-		}
+		bool stop;
+		ABI_TRY(gate.wait(it, "solver", stream, &stop));
+		if (stop)
+			break;
 		SolverState * cur = st + (it & 1), * nxt = st + ((it + 1) & 1);
 		if (it > 0 && it % RESTART_K == 0)
 		{
@@ -547,7 +519,7 @@ solve(int method, spmv_mi355x_matrix * A, const spmv_mi355x_dist_ops * dist, lon
 			ABI_TRY(global_reduce({1, {P_A, 0, 0}}));
 			hipLaunchKernelGGL((cg_update_kernel<T>), grid, block, 0, stream, cur, x, r, p, Ap, K, m, nbc, part);
 			ABI_TRY(global_reduce({2, {P_D, P_E, 0}}));
-			hipLaunchKernelGGL((cg_direction_kernel<T>), grid, block, 0, stream, cur, nxt, r, p, K, m, nbc, part, it, progress_dev);
+			hipLaunchKernelGGL((cg_direction_kernel<T>), grid, block, 0, stream, cur, nxt, r, p, K, m, nbc, part, it, gate.dev);
 		}
 		else
 		{
@@ -561,7 +533,7 @@ solve(int method, spmv_mi355x_matrix * A, const spmv_mi355x_dist_ops * dist, lon
 			hipLaunchKernelGGL((bicg_update_kernel<T>), grid, block, 0, stream, cur, s, Ap, y, z, r0, r, x, m, nbc, part);
 			ABI_TRY(global_reduce({2, {P_D, P_E, 0}}));
 			hipLaunchKernelGGL((bicg_direction_kernel<T>), grid, block, 0, stream, cur, nxt, r, v, K, p, y, m, nbc, part, it,
-					progress_dev);
+					gate.dev);
 		}
 	}
 	HIP_TRY(hipGetLastError());
@@ -572,7 +544,7 @@ solve(int method, spmv_mi355x_matrix * A, const spmv_mi355x_dist_ops * dist, lon
 		const auto t_sync = std::chrono::steady_clock::now();
 		fprintf(stderr, "[solver] setup %.3f ms, enqueue loop %.3f ms (spin %.3f ms), drain %.3f ms, %ld iterations launched\n",
 				std::chrono::duration<double>(t_loop - t_start).count() * 1e3,
-				std::chrono::duration<double>(t_loop_end - t_loop).count() * 1e3, t_spin * 1e3,
+				std::chrono::duration<double>(t_loop_end - t_loop).count() * 1e3, gate.spin_seconds * 1e3,
 				std::chrono::duration<double>(t_sync - t_loop_end).count() * 1e3, it);
 	}
 
@@ -596,11 +568,8 @@ solve(int method, spmv_mi355x_matrix * A, const spmv_mi355x_dist_ops * dist, lon
 	{
 		spmv_mi355x_solver_info out;
 		memset(&out, 0, sizeof(out));
-		double ee = 0;
-		for (double v : part_host)
-			ee += v;
 		out.iterations = st_host.k;
-		out.error = std::sqrt(ee);
+		out.error = std::sqrt(host_sum(part_host.data(), 0, nbc));
 		out.error_best = st_host.err_best;
 		out.eps = st_host.eps;
 		out.eps_counter = st_host.eps_counter;
@@ -610,10 +579,7 @@ solve(int method, spmv_mi355x_matrix * A, const spmv_mi355x_dist_ops * dist, lon
 		if (debug)
 			fprintf(stderr, "[solver] tail (final residuals, downloads) %.3f ms, total %.3f ms\n",
 					std::chrono::duration<double>(std::chrono::steady_clock::now() - t_loop_end).count() * 1e3, out.seconds * 1e3);
-		const unsigned want = info->struct_size;
-		out.struct_size = sizeof(out);
-		memcpy(info, &out, std::min<size_t>(want, sizeof(out)));
-		info->struct_size = (unsigned) std::min<size_t>(want, sizeof(out));
+		put_info(info, info->struct_size, out);
 	}
 	return 0;
 }
@@ -627,11 +593,8 @@ solve_entry(int method, spmv_mi355x_matrix * A, const int32_t * row_ptr, const i
 		set_error("solver: NULL argument");
 		return 1;
 	}
-	if (info && info->struct_size < 8)
-	{
-		set_error("solver: info->struct_size not set");
+	if (!info_size_ok("solver", info))
 		return 1;
-	}
 	if (spmv_mi355x_rows(A) != spmv_mi355x_cols(A))
 	{
 		set_error("the matrix must be square");                  // bench_cg.cpp:487-488
@@ -668,11 +631,8 @@ solve_dist_entry(int method, const spmv_mi355x_dist_ops * ops, int precision, lo
 		set_error("distributed solver: bad argument");
 		return 1;
 	}
-	if (info && info->struct_size < 8)
-	{
-		set_error("solver: info->struct_size not set");
+	if (!info_size_ok("solver", info))
 		return 1;
-	}
 	if (precision == SPMV_MI355X_F32)
 		return solve<float>(method, nullptr, ops, m_local, row_ptr, col, val, b_host, x_host, max_iterations, history_host, info);
 	if (precision == SPMV_MI355X_F64)

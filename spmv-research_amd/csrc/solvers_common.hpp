@@ -1,8 +1,12 @@
-// What the single- and multi-RHS Krylov solvers (solvers.hip, solvers_multi.hip) share: the launch shape of the vector
-// kernels, the device state, the deterministic two-stage dot products, the host progress word, the explicit-residual
-// decision, the device buffer owner and the Jacobi diagonal.
+// What the Krylov solvers (solvers.hip, solvers_multi.hip, solver_cgls.hip, solver_minres.hip) share. Device side: the launch
+// shape of the vector kernels, the device state, the deterministic two-stage dot products, the post to the host progress word, the
+// explicit-residual decision. Host side: the device buffer owner, the Jacobi diagonal, and the run-ahead driver of every solve loop
+// (solver_blocks, ProgressGate, info_size_ok / put_info, host_sum).
 #pragma once
 
+#include <algorithm>
+#include <chrono>
+#include <cstring>
 #include <vector>
 
 #include "common.hpp"
@@ -66,7 +70,7 @@ store_partial(double * __restrict__ part, int slot, double v)
 		part[(long) slot * MAX_PART + blockIdx.x] = v;
 }
 
-// (iterations the device has finished, loop count at the break or -1) for the host, in host-mapped pinned memory
+// (iterations the device has finished, loop count at the break or -1) for the host (ProgressGate below), in host-mapped pinned memory
 __device__ __forceinline__ void
 post_progress(volatile long * host_progress, long finished, long broke_at)
 {
@@ -91,13 +95,10 @@ explicit_decide(const SolverState & st, double err_explicit, int allow_restart, 
 
 struct DeviceBuffers {
 	std::vector<void *> ptrs;
-	void * pinned = nullptr;
 	~DeviceBuffers()
 	{
 		for (void * p : ptrs)
 			(void) hipFree(p);
-		if (pinned)
-			(void) hipHostFree(pinned);
 	}
 	template <typename P>
 	int alloc(P ** out, size_t bytes)
@@ -142,5 +143,108 @@ jacobi_diagonal(const int32_t * row_ptr, const int32_t * col, const double * val
 		if ((expr))         \
 			return 1;       \
 	} while (0)
+
+// ------------------------------------------------------------------------------------------------ the host's half of a solve
+
+// Blocks of every vector kernel of a solve over len elements = partials per slot.
+inline int
+solver_blocks(long len)
+{
+	return (int) std::min<long>(MAX_PART, std::max<long>(1, (len + 4 * VB - 1) / (4 * VB)));
+}
+
+// The progress word that post_progress() writes, and the gate that keeps the enqueueing host at most 2*POLL iterations ahead of
+// the device and stops it after a break. Each solve loop starts with
+//   bool stop; ABI_TRY(gate.wait(it, "<solver>", stream, &stop)); if (stop) break;
+struct ProgressGate {
+	volatile long * host = nullptr;   // [0] iterations finished, [1] loop count at the break or -1
+	long * dev = nullptr;             // the same two words as the kernels see them
+	double spin_seconds = 0;          // spent waiting for the device, for SPMV_MI355X_SOLVER_DEBUG
+
+	ProgressGate() = default;
+	ProgressGate(const ProgressGate &) = delete;
+	ProgressGate & operator=(const ProgressGate &) = delete;
+	~ProgressGate()
+	{
+		if (host)
+			(void) hipHostFree((void *) host);
+	}
+
+	int init()
+	{
+		void * p = nullptr;
+		HIP_TRY(hipHostMalloc(&p, 2 * sizeof(long), hipHostMallocMapped | hipHostMallocCoherent));
+		host = (volatile long *) p;
+		host[0] = 0;
+		host[1] = -1;
+		HIP_TRY(hipHostGetDevicePointer((void **) &dev, p, 0));
+		return 0;
+	}
+
+	// Acts every POLL iterations from 2*POLL on. The wait is plain reads of the mapped word with no HIP call in the loop:
+	// hipEventSynchronize there was measured to stall the queue for up to 100 ms at a time. rc 1 on a HIP error or when the
+	// device posts nothing for 120 s.
+	int wait(long it, const char * what, hipStream_t stream, bool * stop)
+	{
+		*stop = false;
+		if (it % POLL != 0 || it < 2 * POLL)
+			return 0;
+		const auto t_wait = std::chrono::steady_clock::now();
+		long spins = 0;
+		while (host[0] < it - POLL)
+		{
+			if ((++spins & 0xfff) == 0)
+			{
+				HIP_TRY(hipGetLastError());
+				if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t_wait).count() > 120.0)
+				{
+					set_error("%s: the device made no progress for 120 s at iteration %ld", what, it);
+					(void) hipStreamSynchronize(stream);
+					return 1;
+				}
+			}
+			__builtin_ia32_pause();
+		}
+		spin_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_wait).count();
+		// The stop rule that every rank of a distributed solve evaluates identically, so that all stop enqueueing at the same
+		// iteration: only what the device had posted by iteration it - POLL counts (the wait above guarantees it is visible),
+		// never "whatever is visible now".
+		const long broke_at = host[1];
+		*stop = broke_at >= 0 && broke_at <= it - POLL;
+		return 0;
+	}
+};
+
+// The first check of a caller's info struct: its struct_size must at least cover the field itself.
+template <typename Info>
+inline bool
+info_size_ok(const char * what, const Info * info)
+{
+	if (info && info->struct_size < 8)
+	{
+		set_error("%s: info->struct_size not set", what);
+		return false;
+	}
+	return true;
+}
+
+// Writes the first min(want, sizeof(out)) bytes of out to dst, struct_size set to that count (want = the caller's struct_size).
+template <typename Info>
+inline void
+put_info(void * dst, unsigned want, Info & out)
+{
+	out.struct_size = (unsigned) std::min<size_t>(want, sizeof(out));
+	memcpy(dst, &out, out.struct_size);
+}
+
+// The sum of nb downloaded partials from part_host[slot_offset] on, left to right.
+inline double
+host_sum(const double * part_host, size_t slot_offset, int nb)
+{
+	double v = 0;
+	for (int i = 0; i < nb; i++)
+		v += part_host[slot_offset + i];
+	return v;
+}
 
 }  // namespace spmv

@@ -15,8 +15,8 @@
 //   * state is SolverState[2][k], partials are [k][NUM_SLOTS][MAX_PART]; each column has its own `done` flag, which
 //     freezes that column only (its values are stored back unchanged; the SpMM keeps computing it);
 //   * block 0 of the last chunk of an iteration's last kernel posts (iterations finished, loop count at which the last
-//     still-running column broke, or -1) to the host-mapped progress word; the host applies the single solver's stop
-//     rule to it.
+//     still-running column broke, or -1) to the host-mapped progress word, so the one stop rule (ProgressGate,
+//     solvers_common.hpp) fires once every column has broken.
 
 #include <chrono>
 #include <cmath>
@@ -759,6 +759,7 @@ solve_multi(const char * what, int method, spmv_mi355x_matrix * A, int k, const 
 	const long m = spmv_mi355x_rows(A);
 	const long ld = k;
 	hipStream_t stream = nullptr;
+	ProgressGate gate;                // outlives buf, whose hipFree waits for the kernels that post to it
 	DeviceBuffers buf;
 	const size_t vb = (size_t) m * k * sizeof(T);
 
@@ -789,12 +790,7 @@ solve_multi(const char * what, int method, spmv_mi355x_matrix * A, int k, const 
 		ABI_TRY(buf.alloc(&history, sizeof(double) * (size_t) k * hist_ld));
 		HIP_TRY(hipMemsetAsync(history, 0, sizeof(double) * (size_t) k * hist_ld, stream));
 	}
-	HIP_TRY(hipHostMalloc(&buf.pinned, 2 * sizeof(long), hipHostMallocMapped | hipHostMallocCoherent));
-	volatile long * progress = (volatile long *) buf.pinned;          // [0] iterations finished, [1] break flag
-	progress[0] = 0;
-	progress[1] = -1;
-	long * progress_dev = nullptr;
-	HIP_TRY(hipHostGetDevicePointer((void **) &progress_dev, buf.pinned, 0));
+	ABI_TRY(gate.init());
 
 	HIP_TRY(hipMemcpyAsync(b, b_host, vb, hipMemcpyHostToDevice, stream));
 	HIP_TRY(hipMemcpyAsync(K, K_host.data(), (size_t) m * sizeof(T), hipMemcpyHostToDevice, stream));
@@ -803,7 +799,7 @@ solve_multi(const char * what, int method, spmv_mi355x_matrix * A, int k, const 
 	HIP_TRY(hipMemsetAsync(part, 0, part_bytes, stream));
 
 	// the single solver's launch shape: the same rows per (block, thread), hence the same additions per column
-	const int nb = (int) std::min<long>(MAX_PART, std::max<long>(1, (m + 4 * VB - 1) / (4 * VB)));
+	const int nb = solver_blocks(m);
 	const dim3 grid(nb), block(VB), per_col(k);
 	const std::vector<Chunk> chunks = column_chunks(k);
 	long spmv_calls = 0;
@@ -845,30 +841,10 @@ solve_multi(const char * what, int method, spmv_mi355x_matrix * A, int k, const 
 	long it = 0;
 	for (; it < max_iterations; it++)
 	{
-		if (it % POLL == 0 && it >= 2 * POLL)
-		{
-			// the single solver's rule: stay at most 2*POLL iterations ahead, stop once what the device had posted by
-			// iteration it - POLL says that every column has broken
-			const auto t_wait = std::chrono::steady_clock::now();
-			long spins = 0;
-			while (progress[0] < it - POLL)
-			{
-				if ((++spins & 0xfff) == 0)
-				{
-					HIP_TRY(hipGetLastError());
-					if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t_wait).count() > 120.0)
-					{
-						set_error("%s: the device made no progress for 120 s at iteration %ld", what, it);
-						(void) hipStreamSynchronize(stream);
-						return 1;
-					}
-				}
-				__builtin_ia32_pause();
-			}
-			const long broke_at = progress[1];
-			if (broke_at >= 0 && broke_at <= it - POLL)
-				break;
-		}
+		bool stop;
+		ABI_TRY(gate.wait(it, what, stream, &stop));
+		if (stop)
+			break;
 		SolverState * cur = st + (it & 1) * k, * nxt = st + ((it + 1) & 1) * k;
 		if (it > 0 && it % RESTART_K == 0)
 		{
@@ -888,7 +864,7 @@ solve_multi(const char * what, int method, spmv_mi355x_matrix * A, int k, const 
 			});
 			for_chunks(chunks, [&](int c0, auto kc) {
 				hipLaunchKernelGGL((cg_direction_multi_kernel<T, decltype(kc)::value>), grid, block, 0, stream, cur, nxt, r, p, K, m, ld, c0,
-						k, nb, part, it, progress_dev);
+						k, nb, part, it, gate.dev);
 			});
 		}
 		else
@@ -907,7 +883,7 @@ solve_multi(const char * what, int method, spmv_mi355x_matrix * A, int k, const 
 			});
 			for_chunks(chunks, [&](int c0, auto kc) {
 				hipLaunchKernelGGL((bicg_direction_multi_kernel<T, decltype(kc)::value>), grid, block, 0, stream, cur, nxt, r, v, K, p, y, m,
-						ld, c0, k, nb, part, it, progress_dev);
+						ld, c0, k, nb, part, it, gate.dev);
 			});
 		}
 	}
@@ -941,20 +917,16 @@ solve_multi(const char * what, int method, spmv_mi355x_matrix * A, int k, const 
 		{
 			spmv_mi355x_solver_info out;
 			memset(&out, 0, sizeof(out));
-			double ee = 0;
-			for (int i = 0; i < nb; i++)
-				ee += part_host[part_at(c, P_A) + i];
 			const SolverState & sc = st_host[c];
 			out.iterations = sc.k;
-			out.error = std::sqrt(ee);
+			out.error = std::sqrt(host_sum(part_host.data(), part_at(c, P_A), nb));
 			out.error_best = sc.err_best;
 			out.eps = sc.eps;
 			out.eps_counter = sc.eps_counter;
 			out.restarts = sc.restarts;
 			out.spmv_calls = spmv_calls - 1;                      // the last one is the final check, not the solver's
 			out.seconds = seconds;
-			out.struct_size = (unsigned) std::min<size_t>(want, sizeof(out));
-			memcpy((char *) info + (size_t) c * want, &out, std::min<size_t>(want, sizeof(out)));
+			put_info((char *) info + (size_t) c * want, want, out);
 		}
 	}
 	return 0;
@@ -971,11 +943,8 @@ solve_multi_entry(const char * what, int method, spmv_mi355x_matrix * A, int k, 
 		set_error("%s: k must be >= 1 (got %d)", what, k);
 		return 1;
 	}
-	if (info && info->struct_size < 8)
-	{
-		set_error("%s: info->struct_size not set", what);
+	if (!info_size_ok(what, info))
 		return 1;
-	}
 	if (!A || !row_ptr || !b_host || !x_host)
 	{
 		set_error("%s: NULL argument", what);

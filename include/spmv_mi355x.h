@@ -519,6 +519,68 @@ int  spmv_mi355x_minres(spmv_mi355x_matrix * A, const void * b_host, void * x_ou
 		double shift, const void * minv_host /* may be NULL */, double tol, long max_iterations,
 		double * history_out /* may be NULL: max_iterations doubles */, spmv_mi355x_minres_info * info /* may be NULL */);
 
+/* ---- GMRES(m): general square systems over one handle ----------------------------------------------------------------------- */
+/* A x = b from x0 = 0 for ANY square matrix, symmetric or not, a zero on the diagonal included: restarted GMRES with restart length
+ * m = `restart`, classical Gram-Schmidt applied twice (CGS2: the dots of a pass are independent, so they are one launch, and two
+ * passes keep the basis orthogonal to working precision), Givens rotations on the Hessenberg column, and an optional DIAGONAL RIGHT
+ * preconditioner given as its inverse: the solver runs GMRES on A diag(minv) and returns x = diag(minv) u, so the residual it
+ * minimises, reports and stops on is the true 2-norm |b - A x|, which never increases within a cycle. Every vector is resident in
+ * device memory (csrc/solver_gmres.hip; 1 SpMV + 6 launches per inner step). The recurrences, every scalar and every
+ * dot fp64, vectors in the handle's precision, M v = minv v (or v):
+ *     x = 0; beta0 = |b|                                                        (beta0 == 0: stop 3; not finite: stop 4)
+ *     r = b; beta = beta0; it = 0
+ *     cycle:  v_0 = r / beta;  g = (beta, 0, ..., 0);  j = 0
+ *       inner step, while j < m and it < max_iterations:
+ *         w = A M v_j;  h = 0
+ *         twice:  c_i = v_i.w for i <= j, all from the same w;  w -= c_0 v_0, ..., w -= c_j v_j in that order;  h_i += c_i
+ *         hn = h_{j+1} = |w|
+ *         for i < j:  (h_i, h_{i+1}) = (cs_i h_i + sn_i h_{i+1}, -sn_i h_i + cs_i h_{i+1})
+ *         rho = hypot(h_j, h_{j+1})                  (not finite or 0: stop 4; this column is dropped: j, it and x as before it)
+ *         cs_j = h_j / rho;  sn_j = h_{j+1} / rho;  h_j = rho;  R[0..j, j] = h[0..j]
+ *         g_{j+1} = -sn_j g_j;  g_j = cs_j g_j;  it += 1;  j += 1;  history[it-1] = |g_j|
+ *         if tol > 0 and |g_j| <= tol beta0: stop 1;  else if hn == 0: stop 5;  else v_j = w / hn
+ *       cycle end:  R[0..j, 0..j] y = g[0..j] by back substitution;  u = y_0 v_0 + ... + y_{j-1} v_{j-1} in that order;  x += M u
+ *       if stopped or it >= max_iterations: return
+ *       r = b - A x;  beta = |r|;  restarts += 1                                 (beta not finite: stop 4; beta == 0: stop 5)
+ *   - b_host, x_out_host and minv_host: rows() values of the handle's precision.
+ *   - restart: 1 .. 128. The cap covers three things: the basis of (restart + 1) * rows() values in device memory, the serial
+ *     rotation chain that one thread walks in every inner step, and the restart + 4 slots of partial sums.
+ *   - minv_host (may be NULL): every entry finite and > 0. NULL = no preconditioner: no extra vector is stored and no multiply is
+ *     issued. The library derives no preconditioner itself.
+ *   - any format and layout serves (the solver only calls spmv_mi355x_spmv_device_async): value_storage = 1 and 7-byte values
+ *     included; on handles whose SpMV is deterministic the whole solve is, bit for bit. The solver's vectors are plain allocations.
+ *   - tol == 0 is legal and means "never stop on the tolerance". max_iterations == 0 returns x = 0, stop 2 and rnorm = rnorm0.
+ *     On stop 3 x = 0 and every norm is 0.
+ *   - history_out (may be NULL): max_iterations doubles; entry k = |g| after inner step k + 1, the RECURSIVE residual; entries >=
+ *     info->iterations stay 0.
+ *   - after a stop the solve is frozen on the device: x, iterations and the history are those of the step at which the rule fired
+ *     (the columns of its unfinished cycle applied once), however far the host had run ahead (at most 64 inner steps).
+ *   - rc 1, a last_error that names gmres, every caller buffer and info untouched. First the scalars, before any device is touched
+ *     and before the NULL checks: info->struct_size < 8; restart < 1 or > 128; tol negative or not finite; max_iterations < 0. Then a
+ *     NULL A, b or x_out. Then rows() != cols() (the message gives both; this also refuses row-block handles). Then a minv entry
+ *     that is not finite or is <= 0 (the message names the first such index): a host pass over the n values before any launch.
+ *   - NOT BUILT: multi-RHS and row-partitioned forms, device-pointer b / x, left preconditioning, flexible GMRES (a preconditioner
+ *     that changes from step to step), a non-zero x0. */
+typedef struct {
+	unsigned struct_size;   /* in: sizeof(spmv_mi355x_gmres_info) */
+	long   iterations;      /* completed inner steps (one SpMV each), over all cycles */
+	int    stop;            /* 1 = |g_{j+1}| <= tol * |b| (tol > 0)
+	                           2 = max_iterations reached
+	                           3 = b == 0: x = 0, 0 iterations
+	                           4 = breakdown: a scalar not finite, or rho == 0; x of the last good step's columns is returned
+	                           5 = the Krylov space ended: h_{j+1,j} == 0 with rho != 0, or an explicit restart residual == 0 */
+	long   restarts;        /* restarts taken = cycles begun after the first */
+	double rnorm;           /* |b - A x_out|, EXPLICIT (one SpMV after the loop) */
+	double rnorm0;          /* |b| */
+	double prnorm;          /* |g_{j+1}| at the stop: the recursive residual (right preconditioning: the true 2-norm one) */
+	double xnorm;           /* |x_out| */
+	long   spmv_calls;      /* every launch: inner steps incl. the host's run-ahead, one per restart, the explicit one */
+	double seconds;
+} spmv_mi355x_gmres_info;
+int  spmv_mi355x_gmres(spmv_mi355x_matrix * A, const void * b_host, void * x_out_host, int restart,
+		const void * minv_host /* may be NULL */, double tol, long max_iterations,
+		double * history_out /* may be NULL: max_iterations doubles */, spmv_mi355x_gmres_info * info /* may be NULL */);
+
 /* Row-partitioned (multi-GPU) form of the same two solvers: one process per GPU owns the row block [row_offset,
  * row_offset + m_local) of A, b and x. The solver keeps every vector device-resident and local; the two things that cross
  * ranks are handed to the caller, who has the communicator (torch.distributed / RCCL in bench-level code):

@@ -51,7 +51,7 @@ SYMBOLS = [
     "spmv_mi355x_merge_tiles", "spmv_mi355x_free", "spmv_mi355x_precision", "spmv_mi355x_value_storage", "spmv_mi355x_device",
     "spmv_mi355x_transposed",
     "spmv_mi355x_pcg", "spmv_mi355x_pbicgstab", "spmv_mi355x_pcg_dist", "spmv_mi355x_pbicgstab_dist",
-    "spmv_mi355x_pcg_multi", "spmv_mi355x_pbicgstab_multi", "spmv_mi355x_cgls", "spmv_mi355x_minres",
+    "spmv_mi355x_pcg_multi", "spmv_mi355x_pbicgstab_multi", "spmv_mi355x_cgls", "spmv_mi355x_minres", "spmv_mi355x_gmres",
     "spmv_mi355x_copy_device_async",
     "spmv_mi355x_create_partitioned", "spmv_mi355x_destroy_partitioned", "spmv_mi355x_spmv_partitioned",
     "spmv_mi355x_partitioned_set_always_copy", "spmv_mi355x_time_partitioned", "spmv_mi355x_partitioned_parts",
@@ -97,6 +97,9 @@ def lib():
         L.spmv_mi355x_minres.restype = C.c_int
         L.spmv_mi355x_minres.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_double, C.c_long,
                                          C.c_void_p, C.POINTER(MinresInfo)]
+        L.spmv_mi355x_gmres.restype = C.c_int
+        L.spmv_mi355x_gmres.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_long,
+                                        C.c_void_p, C.POINTER(GmresInfo)]
         _lib = L
     return _lib
 
@@ -242,6 +245,13 @@ class MinresInfo(C.Structure):
     """spmv_mi355x_minres_info (include/spmv_mi355x.h)"""
     _fields_ = [("struct_size", C.c_uint), ("iterations", C.c_long), ("stop", C.c_int), ("rnorm", C.c_double), ("rnorm0", C.c_double),
                 ("prnorm", C.c_double), ("prnorm0", C.c_double), ("xnorm", C.c_double), ("spmv_calls", C.c_long),
+                ("seconds", C.c_double)]
+
+
+class GmresInfo(C.Structure):
+    """spmv_mi355x_gmres_info (include/spmv_mi355x.h)"""
+    _fields_ = [("struct_size", C.c_uint), ("iterations", C.c_long), ("stop", C.c_int), ("restarts", C.c_long), ("rnorm", C.c_double),
+                ("rnorm0", C.c_double), ("prnorm", C.c_double), ("xnorm", C.c_double), ("spmv_calls", C.c_long),
                 ("seconds", C.c_double)]
 
 
@@ -638,6 +648,29 @@ class Matrix:
         _check(lib().spmv_mi355x_minres(self.h, _p(b), _p(x), shift, None if minv is None else _p(minv), tol, max_iterations,
                                         _p(hist) if history else None, C.byref(info)))
         out = {k: getattr(info, k) for k, _ in MinresInfo._fields_ if k != "struct_size"}
+        out["x"] = x[:self.m]
+        out["history"] = hist[:info.iterations] if history else None
+        return out
+
+    def gmres(self, b, restart=30, minv=None, tol=1e-12, max_iterations=1000, history=True):
+        """A x = b by restarted GMRES(restart) for any square matrix (spmv_mi355x_gmres): a dict of the spmv_mi355x_gmres_info fields
+        plus x (rows values) and history (|g| after each inner step, shape (iterations,), or None). `minv`, when given, is the inverse
+        of a diagonal right preconditioner: rows values, every one finite and > 0 (checked by the library, like `restart` and the
+        shape of the handle)."""
+        b = np.ascontiguousarray(b, self.dtype)
+        if b.shape != (self.m,):
+            raise ValueError(f"b must have {self.m} values, got {b.shape}")
+        if minv is not None:
+            minv = np.ascontiguousarray(minv, self.dtype)
+            if minv.shape != (self.m,):
+                raise ValueError(f"minv must have {self.m} values, got {minv.shape}")
+        x = np.zeros(max(self.m, 1), self.dtype)
+        hist = np.zeros(max(max_iterations, 1), np.float64) if history else None
+        info = GmresInfo()
+        info.struct_size = C.sizeof(GmresInfo)
+        _check(lib().spmv_mi355x_gmres(self.h, _p(b), _p(x), restart, None if minv is None else _p(minv), tol, max_iterations,
+                                       _p(hist) if history else None, C.byref(info)))
+        out = {k: getattr(info, k) for k, _ in GmresInfo._fields_ if k != "struct_size"}
         out["x"] = x[:self.m]
         out["history"] = hist[:info.iterations] if history else None
         return out

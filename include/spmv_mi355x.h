@@ -581,6 +581,71 @@ int  spmv_mi355x_gmres(spmv_mi355x_matrix * A, const void * b_host, void * x_out
 		const void * minv_host /* may be NULL */, double tol, long max_iterations,
 		double * history_out /* may be NULL: max_iterations doubles */, spmv_mi355x_gmres_info * info /* may be NULL */);
 
+/* ---- sparse triangular solve: level-scheduled L x = b and U x = b handles --------------------------------------------------------- */
+/* What applies Gauss-Seidel / SSOR (A's own triangles) and ILU(0) / IC(0) (the caller's factors): T x = b for one triangle T of a
+ * square n x n matrix given as CSR (csrc/trsv.hip, csrc/kernels_trsv.hip). The primitive only: no solver calls it yet.
+ * WHICH TRIANGLE. uplo = SPMV_MI355X_LOWER keeps the entries with column <= row, SPMV_MI355X_UPPER those with column >= row; entries
+ * on the other side are ignored, so one CSR array holding both ILU factors (unit L below, U on and above the diagonal) serves two
+ * handles, and the CSR of A serves both halves of a Gauss-Seidel sweep. diag = SPMV_MI355X_DIAG_STORED reads d_i from row i;
+ * SPMV_MI355X_DIAG_UNIT takes d_i = 1 and ignores every stored entry with column i, a zero or a missing one included.
+ * THE SOLVE, PINNED TO THE BIT. For every row i
+ *     s = b[i]
+ *     for each kept off-diagonal entry (i, j, a) of row i, in STORED order:   s = fma(-a, x[j], s)
+ *     x[i] = s / d_i     (STORED: an IEEE division, never a multiplication by a reciprocal)     |     x[i] = s     (UNIT)
+ * with every operation, every value and both vectors in the handle's precision (fma and / on double, fmaf and / on float); values are
+ * narrowed on upload exactly as spmv_mi355x_create narrows them. Duplicate off-diagonal entries are separate fmas, stored explicit
+ * zeros count as dependencies, padding of the stored layout never contributes an operation. A row's result does not depend on the
+ * order in which rows are processed, so every level schedule and launch plan gives the bits of the sequential CPU loop
+ * (tests/trsv_reference.c), run after run.
+ * THE ANALYSIS (host, O(nnz)). level[i] = 0 when row i has no kept off-diagonal entry, else 1 + the largest level[j] over those
+ * entries; LOWER walks the rows in ascending order, UPPER in descending order. A level with at most chain_rows rows is THIN. A
+ * maximal run of consecutive thin levels is ONE launch of ONE workgroup, which walks the run with a workgroup barrier between levels;
+ * every other level is one launch with one lane per row. launches = (levels that are not thin) + (maximal thin runs); n = 0 gives 0
+ * levels and 0 launches. chain_rows: 1 .. 65536, 0 = the default (256, from the sweep in
+ * profiles/r16_trsv.txt). The order of the launches on the stream is the only ordering
+ * between workgroups: nothing spins on a flag, there is no grid barrier and no cooperative or persistent kernel.
+ * spmv_mi355x_trsv_analyze returns what create() derives from the pattern without touching a device (create() runs the same
+ * routine; trsv_info agrees with it): level_of_row_out receives a malloc'ed array of n levels (at least one element; free with
+ * spmv_mi355x_free), any out pointer may be NULL.
+ *   - create() deep-copies its inputs. Stored: the rows permuted by (level, row) in column-major slices of up to 64 rows that never
+ *     straddle a level, each with its own width and a per-row length (a long row pads its own slice only), the permutation, and the
+ *     diagonal itself. trsv_mem_footprint() is the bytes of these device arrays. nnz_kept of trsv_info counts the entries a solve
+ *     reads: the kept off-diagonal ones, plus n diagonal ones under DIAG_STORED.
+ *   - solve_device_async: b_dev and x_dev hold n values of the handle's precision on the handle's device; the launches are enqueued
+ *     on hip_stream (NULL = the default stream) and the call returns. b_dev == x_dev (in place) is legal; any other overlap is not.
+ *     Only x[0 .. n) is written. trsv_solve is the blocking host-buffer form (its two device vectors are allocated at the first
+ *     call and kept). n = 0: rc 0, nothing read or written. One solve at a time per handle and vector pair.
+ *   - time_trsv_device: HIP-event timing of `iters` back-to-back solves, like spmv_mi355x_time_device.
+ *   - rc 1 with a last_error that names trsv, checked in this order, everything but the last on the host before any device is touched:
+ *     1. scalars: uplo, diag, precision, n < 0 (or beyond the int32 range), chain_rows < 0 or > 65536;
+ *     2. NULL pointers: out, row_ptr; col_idx / values when row_ptr[n] > 0;
+ *     3. the pattern, as spmv_mi355x_create checks it and with its messages: row_ptr from 0 and monotone, columns in [0, n);
+ *     4. with DIAG_STORED the diagonal of every row, the message naming the first bad row: the diagonal is the first stored entry
+ *        with column i (the rule the solvers' Jacobi diagonal uses); it must exist, be finite and be non-zero AFTER narrowing to the
+ *        handle's precision; a second entry with column i in the same row is refused;
+ *     5. the device: without a usable one the library's "no HIP device available" message; `device` out of range.
+ *     trsv_analyze makes the checks 1 to 3 that apply to its arguments. The solve entries refuse a NULL handle and, for n > 0, a NULL
+ *     vector; trsv_info a NULL handle; trsv_mem_footprint(NULL) is 0; trsv_destroy(NULL) is rc 0.
+ *   - NOT CHECKABLE: that b_dev / x_dev hold n values on the right device.
+ *   - NOT BUILT: wiring into the solvers (SGS / ILU preconditioning of pcg / gmres); the ILU(0) / IC(0) factorization itself; a solve
+ *     with T^t over T's layout; multi-RHS; update_values for a trsv handle; GPU-side analysis; graph capture; a row-partitioned form;
+ *     a "sync-free" variant in which workgroups wait for each other inside one launch. */
+typedef struct spmv_mi355x_trsv spmv_mi355x_trsv;   /* opaque */
+enum { SPMV_MI355X_LOWER = 0, SPMV_MI355X_UPPER = 1 };
+enum { SPMV_MI355X_DIAG_STORED = 0, SPMV_MI355X_DIAG_UNIT = 1 };
+int  spmv_mi355x_trsv_analyze(int uplo, long n, const int32_t * row_ptr, const int32_t * col_idx, int chain_rows /* 0 = default */,
+		int32_t ** level_of_row_out /* malloc'ed, spmv_mi355x_free; may be NULL */, long * levels_out, long * launches_out,
+		long * max_level_rows_out, int * chain_rows_used_out);
+int  spmv_mi355x_trsv_create(spmv_mi355x_trsv ** out, int uplo, int diag, int precision, long n,
+		const int32_t * row_ptr, const int32_t * col_idx, const double * values_fp64, int chain_rows, int device /* -1 = current */);
+int  spmv_mi355x_trsv_destroy(spmv_mi355x_trsv * T);
+int  spmv_mi355x_trsv_solve_device_async(spmv_mi355x_trsv * T, const void * b_dev, void * x_dev, void * hip_stream);
+int  spmv_mi355x_trsv_solve(spmv_mi355x_trsv * T, const void * b_host, void * x_host);          /* blocking */
+int  spmv_mi355x_trsv_info(const spmv_mi355x_trsv * T, long * n_out, long * nnz_kept_out, long * levels_out, long * launches_out,
+		long * max_level_rows_out, int * chain_rows_out);                                      /* any pointer may be NULL */
+double spmv_mi355x_trsv_mem_footprint(const spmv_mi355x_trsv * T);
+int  spmv_mi355x_time_trsv_device(spmv_mi355x_trsv * T, const void * b_dev, void * x_dev, int iters, void * hip_stream, double * ms_per_iter_out);
+
 /* Row-partitioned (multi-GPU) form of the same two solvers: one process per GPU owns the row block [row_offset,
  * row_offset + m_local) of A, b and x. The solver keeps every vector device-resident and local; the two things that cross
  * ranks are handed to the caller, who has the communicator (torch.distributed / RCCL in bench-level code):

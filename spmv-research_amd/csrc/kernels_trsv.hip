@@ -1,0 +1,218 @@
+// The two kernels of the sparse triangular solve T x = b over the level-sliced layout of trsv.hpp. One lane owns one row:
+//   s = b[i];  for each kept off-diagonal entry (i, j, a) in stored order: s = fma(-a, x[j], s);  x[i] = s / d_i  (or s under UNIT)
+// in the handle's precision, with an IEEE division. A row's result depends on its own entry order only, never on which lane,
+// workgroup or launch computes it, so every plan gives the bits of the sequential loop (tests/trsv_reference.c).
+//
+// trsv_level_kernel: one level, one lane per row, any number of workgroups. Every x[j] it reads belongs to an earlier level and was
+// written by an earlier launch on the same stream: the launch boundary is the only ordering between workgroups anywhere in this file.
+// trsv_chain_kernel: a run of consecutive thin levels in ONE workgroup, which walks them with a barrier in between.
+//
+// x is read and written inside one launch by both kernels (in the chain kernel the reads DEPEND on the writes), and b may be x:
+// neither pointer is const, __restrict__ or loaded through a non-temporal / read-only path.
+
+#include "trsv.hpp"
+
+namespace spmv {
+
+template <typename T>
+struct TrsvTyped {
+	const T * val;
+	const int * col;
+	const int64_t * slice_ptr;
+	const int * len;
+	const int * perm;
+	const T * diag;
+	const int * level_ptr;
+	const int * level_slice;
+};
+
+template <typename T>
+static TrsvTyped<T>
+typed(const TrsvArrays & a)
+{
+	return TrsvTyped<T>{(const T *) a.val, a.col, a.slice_ptr, a.len, a.perm, (const T *) a.diag, a.level_ptr, a.level_slice};
+}
+
+// What a row needs that does not depend on x: where it is, b[i], the diagonal and its first TRSV_UNROLL entries. The chain kernel
+// loads it for the NEXT level before the barrier that ends the current one, so that behind the barrier only the gathers of x remain.
+constexpr int TRSV_UNROLL = 4;
+
+template <typename T>
+struct TrsvHead {
+	int cnt, i, lanes;
+	int64_t base;
+	T s, d;
+	T a[TRSV_UNROLL];
+	int c[TRSV_UNROLL];
+};
+
+// TRSV_UNROLL entries of a row from entry k on, k < cnt. Slots at or beyond cnt repeat entry k (a valid address: padding is never
+// read) and are never used.
+template <typename T>
+__device__ __forceinline__ void
+trsv_entries(const TrsvTyped<T> & a, int64_t base, int lanes, int cnt, int k, T (&av)[TRSV_UNROLL], int (&cv)[TRSV_UNROLL])
+{
+	#pragma unroll
+	for (int j = 0; j < TRSV_UNROLL; j++)
+	{
+		const int64_t e = base + (int64_t) (k + j < cnt ? k + j : k) * lanes;
+		av[j] = a.val[e];
+		cv[j] = a.col[e];
+	}
+}
+
+// the gathers and the fmas of those entries, in stored order
+template <typename T>
+__device__ __forceinline__ T
+trsv_apply(const T * x, int cnt, int k, const T (&av)[TRSV_UNROLL], const int (&cv)[TRSV_UNROLL], T s)
+{
+	T xv[TRSV_UNROLL];
+	#pragma unroll
+	for (int j = 0; j < TRSV_UNROLL; j++)
+		xv[j] = x[cv[j]];
+	#pragma unroll
+	for (int j = 0; j < TRSV_UNROLL; j++)
+		if (k + j < cnt)
+			s = fma_t<T>(-av[j], xv[j], s);
+	return s;
+}
+
+// row number q of a level that starts at position pos0 with `rows` rows and slice slice0
+template <typename T, bool UNIT>
+__device__ __forceinline__ void
+trsv_head(const TrsvTyped<T> & a, int pos0, int rows, int slice0, int q, const T * b, TrsvHead<T> & h)
+{
+	const int p = pos0 + q;
+	const int first = q & ~(TRSV_SLICE - 1);                                  // first row of this lane's slice within the level
+	h.lanes = rows - first < TRSV_SLICE ? rows - first : TRSV_SLICE;          // only a level's last slice is short
+	h.base = a.slice_ptr[slice0 + q / TRSV_SLICE] + (q - first);
+	h.cnt = a.len[p];
+	h.i = a.perm[p];
+	h.s = b[h.i];
+	h.d = UNIT ? (T) 1 : a.diag[p];
+	if (h.cnt > 0)
+		trsv_entries<T>(a, h.base, h.lanes, h.cnt, 0, h.a, h.c);
+	else
+	{
+		#pragma unroll
+		for (int j = 0; j < TRSV_UNROLL; j++)
+		{
+			h.a[j] = 0;
+			h.c[j] = h.i;
+		}
+	}
+}
+
+template <typename T, bool UNIT>
+__device__ __forceinline__ void
+trsv_finish(const TrsvTyped<T> & a, const TrsvHead<T> & h, T * x)
+{
+	T s = h.s;
+	if (h.cnt > 0)
+		s = trsv_apply<T>(x, h.cnt, 0, h.a, h.c, s);
+	for (int k = TRSV_UNROLL; k < h.cnt; k += TRSV_UNROLL)
+	{
+		T av[TRSV_UNROLL];
+		int cv[TRSV_UNROLL];
+		trsv_entries<T>(a, h.base, h.lanes, h.cnt, k, av, cv);
+		s = trsv_apply<T>(x, h.cnt, k, av, cv, s);
+	}
+	x[h.i] = UNIT ? s : s / h.d;
+}
+
+template <typename T, bool UNIT>
+__device__ __forceinline__ void
+trsv_row(const TrsvTyped<T> & a, int pos0, int rows, int slice0, int q, const T * b, T * x)
+{
+	TrsvHead<T> h;
+	trsv_head<T, UNIT>(a, pos0, rows, slice0, q, b, h);
+	trsv_finish<T, UNIT>(a, h, x);
+}
+
+template <typename T, bool UNIT>
+__global__ __launch_bounds__(TRSV_LEVEL_BLOCK) void
+trsv_level_kernel(TrsvTyped<T> a, int pos0, int rows, int slice0, const T * b, T * x)
+{
+	const int q = blockIdx.x * TRSV_LEVEL_BLOCK + threadIdx.x;
+	if (q < rows)
+		trsv_row<T, UNIT>(a, pos0, rows, slice0, q, b, x);
+}
+
+// ONE workgroup. The loop over the levels and the barrier in it are uniform: every thread executes every barrier, whether or not
+// a level has a row for it.
+// What orders level l's stores of x before level l + 1's loads: all waves of a workgroup run on one CU and go through that CU's
+// vector L1, which is write-through and sees its own CU's stores, so workgroup scope is all this hand-off needs; no agent-scope
+// fence, which exists for readers on OTHER CUs. But s_barrier itself waits for no memory counter: beside the barrier every storing
+// wave must have drained its stores (s_waitcnt vmcnt(0)) BEFORE it arrives, and the compiler must not move a load of x across the
+// barrier. The explicit wait gives the first on every path, __syncthreads() (a workgroup-scope release / acquire pair around
+// s_barrier) the second.
+// A thread's first row of the next level is begun (trsv_head: nothing of it reads x; b[i], which may be x[i], is written by this
+// thread alone) before that wait, so its loads fly while the stores drain and only the gathers of x follow the barrier.
+template <typename T, bool UNIT>
+__global__ __launch_bounds__(TRSV_CHAIN_BLOCK_MAX) void
+trsv_chain_kernel(TrsvTyped<T> a, int l0, int l1, const T * b, T * x)
+{
+	const int t = threadIdx.x;
+	int pos0 = a.level_ptr[l0], end = a.level_ptr[l0 + 1], slice0 = a.level_slice[l0];
+	TrsvHead<T> h;
+	bool have = t < end - pos0;
+	if (have)
+		trsv_head<T, UNIT>(a, pos0, end - pos0, slice0, t, b, h);
+	for (int l = l0; l < l1; l++)
+	{
+		const int rows = end - pos0;
+		if (have)
+			trsv_finish<T, UNIT>(a, h, x);
+		for (int q = t + blockDim.x; q < rows; q += blockDim.x)
+			trsv_row<T, UNIT>(a, pos0, rows, slice0, q, b, x);
+		if (l + 1 < l1)
+		{
+			pos0 = end;
+			end = a.level_ptr[l + 2];
+			slice0 = a.level_slice[l + 1];
+			have = t < end - pos0;
+			if (have)
+				trsv_head<T, UNIT>(a, pos0, end - pos0, slice0, t, b, h);
+		}
+		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+		__syncthreads();
+	}
+}
+
+template <typename T, bool UNIT>
+static void
+level_launch(const TrsvArrays & a, const TrsvStep & s, const void * b, void * x, hipStream_t st)
+{
+	const unsigned grid = (unsigned) ((s.rows + TRSV_LEVEL_BLOCK - 1) / TRSV_LEVEL_BLOCK);
+	hipLaunchKernelGGL((trsv_level_kernel<T, UNIT>), dim3(grid), dim3(TRSV_LEVEL_BLOCK), 0, st, typed<T>(a), s.pos0, s.rows, s.slice0,
+			(const T *) b, (T *) x);
+}
+
+template <typename T, bool UNIT>
+static void
+chain_launch(const TrsvArrays & a, const TrsvStep & s, const void * b, void * x, hipStream_t st)
+{
+	hipLaunchKernelGGL((trsv_chain_kernel<T, UNIT>), dim3(1), dim3(s.block), 0, st, typed<T>(a), s.l0, s.l1, (const T *) b, (T *) x);
+}
+
+int
+launch_trsv_level(bool f32, bool unit, const TrsvArrays & a, const TrsvStep & s, const void * b, void * x, hipStream_t st)
+{
+	if (f32)
+		unit ? level_launch<float, true>(a, s, b, x, st) : level_launch<float, false>(a, s, b, x, st);
+	else
+		unit ? level_launch<double, true>(a, s, b, x, st) : level_launch<double, false>(a, s, b, x, st);
+	return 0;
+}
+
+int
+launch_trsv_chain(bool f32, bool unit, const TrsvArrays & a, const TrsvStep & s, const void * b, void * x, hipStream_t st)
+{
+	if (f32)
+		unit ? chain_launch<float, true>(a, s, b, x, st) : chain_launch<float, false>(a, s, b, x, st);
+	else
+		unit ? chain_launch<double, true>(a, s, b, x, st) : chain_launch<double, false>(a, s, b, x, st);
+	return 0;
+}
+
+}  // namespace spmv

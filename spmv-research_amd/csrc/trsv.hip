@@ -1,0 +1,539 @@
+// Sparse triangular solve handles (include/spmv_mi355x.h "sparse triangular solve"): the host analysis (levels and launch plan), the
+// level-sliced layout of trsv.hpp, and the C ABI. Host code only; the kernels are in kernels_trsv.hip.
+//
+// THE PLAN. level[i] = 0 when row i has no kept off-diagonal entry, else 1 + the largest level among the rows those entries name;
+// LOWER walks the rows upwards, UPPER downwards. A level of at most chain_rows rows is THIN. A maximal run of consecutive thin
+// levels is one launch of one workgroup (trsv_chain_kernel), every other level is one launch with one lane per row
+// (trsv_level_kernel). The launches of a solve go to one stream in level order and that order is the only thing that orders
+// workgroups: no flag is spun on, there is no grid barrier, no cooperative or persistent kernel and no captured graph. A workgroup
+// never waits for another one, so a solve cannot hang whatever else runs on the device.
+
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "handle.hpp"
+#include "trsv.hpp"
+
+namespace spmv {
+
+struct TrsvAnalysis {
+	std::vector<int32_t> level_of_row;     // n
+	std::vector<int32_t> level_ptr;        // levels + 1: positions of each level in the (level, row) order
+	std::vector<int32_t> level_slice;      // levels + 1: slices of up to TRSV_SLICE rows, none straddling a level
+	std::vector<TrsvStep> plan;
+	long levels = 0, max_level_rows = 0;
+	int chain_rows = 0;
+};
+
+static bool
+trsv_scalars_ok(const char * what, int uplo, const int * diag, const int * precision, long n, int chain_rows)
+{
+	if (uplo != SPMV_MI355X_LOWER && uplo != SPMV_MI355X_UPPER)
+		set_error("%s: uplo must be SPMV_MI355X_LOWER (0) or SPMV_MI355X_UPPER (1) (got %d)", what, uplo);
+	else if (diag && *diag != SPMV_MI355X_DIAG_STORED && *diag != SPMV_MI355X_DIAG_UNIT)
+		set_error("%s: diag must be SPMV_MI355X_DIAG_STORED (0) or SPMV_MI355X_DIAG_UNIT (1) (got %d)", what, *diag);
+	else if (precision && *precision != SPMV_MI355X_F64 && *precision != SPMV_MI355X_F32)
+		set_error("%s: unknown precision %d", what, *precision);
+	else if (n < 0 || n >= 0x7fffffffL)
+		set_error("%s: n = %ld out of range [0, 2^31 - 1)", what, n);
+	else if (chain_rows < 0 || chain_rows > TRSV_CHAIN_ROWS_MAX)
+		set_error("%s: chain_rows must be 0 (the default) or 1 .. %d (got %d)", what, TRSV_CHAIN_ROWS_MAX, chain_rows);
+	else
+		return true;
+	return false;
+}
+
+// row_ptr from 0 and monotone, columns in [0, n): the checks and the messages of spmv_mi355x_create
+static int
+trsv_check_pattern(const char * what, long n, const int32_t * rp, const int32_t * ci)
+{
+	if (rp[0] != 0)
+	{
+		set_error("%s: row_ptr must start at 0 (got %d)", what, rp[0]);
+		return 1;
+	}
+	long bad = -1;
+	#pragma omp parallel for num_threads(spmv::host_threads()) reduction(max : bad)
+	for (long i = 0; i < n; i++)
+		if (rp[i + 1] < rp[i])
+			bad = std::max(bad, i);
+	if (bad >= 0)
+	{
+		set_error("%s: row_ptr is not monotone at row %ld", what, bad);
+		return 1;
+	}
+	const long nnz = rp[n];
+	#pragma omp parallel for num_threads(spmv::host_threads()) reduction(max : bad)
+	for (long j = 0; j < nnz; j++)
+		if (ci[j] < 0 || ci[j] >= n)
+			bad = std::max(bad, j);
+	if (bad >= 0)
+	{
+		set_error("%s: column index %d out of range [0,%ld) at entry %ld", what, ci[bad], n, bad);
+		return 1;
+	}
+	return 0;
+}
+
+// is entry (i, c) a kept off-diagonal entry, i.e. a dependency of row i?
+static inline bool
+trsv_dep(int uplo, long i, long c)
+{
+	return uplo == SPMV_MI355X_LOWER ? c < i : c > i;
+}
+
+// O(nnz). The pattern has been checked.
+static void
+trsv_analysis(int uplo, long n, const int32_t * rp, const int32_t * ci, int chain_rows, TrsvAnalysis & an)
+{
+	an.chain_rows = chain_rows ? chain_rows : TRSV_CHAIN_ROWS_DEFAULT;
+	an.level_of_row.assign((size_t) n, 0);
+	int32_t * level = an.level_of_row.data();
+	int32_t top = -1;
+	const bool lower = uplo == SPMV_MI355X_LOWER;
+	for (long t = 0; t < n; t++)
+	{
+		const long i = lower ? t : n - 1 - t;
+		int32_t lv = 0;
+		for (long j = rp[i]; j < rp[i + 1]; j++)
+			if (trsv_dep(uplo, i, ci[j]))
+				lv = std::max(lv, level[ci[j]] + 1);
+		level[i] = lv;
+		top = std::max(top, lv);
+	}
+	an.levels = (long) top + 1;
+	an.level_ptr.assign((size_t) an.levels + 1, 0);
+	an.level_slice.assign((size_t) an.levels + 1, 0);
+	for (long i = 0; i < n; i++)
+		an.level_ptr[level[i] + 1]++;
+	an.max_level_rows = 0;
+	for (long l = 0; l < an.levels; l++)
+	{
+		const int32_t rows = an.level_ptr[l + 1];
+		an.max_level_rows = std::max<long>(an.max_level_rows, rows);
+		an.level_ptr[l + 1] = an.level_ptr[l] + rows;
+		an.level_slice[l + 1] = an.level_slice[l] + (rows + TRSV_SLICE - 1) / TRSV_SLICE;
+	}
+	an.plan.clear();
+	for (long l = 0; l < an.levels;)
+	{
+		const int rows = an.level_ptr[l + 1] - an.level_ptr[l];
+		TrsvStep s;
+		memset(&s, 0, sizeof(s));
+		s.l0 = (int) l;
+		if (rows > an.chain_rows)
+		{
+			s.l1 = (int) l + 1;
+			s.pos0 = an.level_ptr[l];
+			s.rows = rows;
+			s.slice0 = an.level_slice[l];
+			l++;
+		}
+		else
+		{
+			// the maximal run of thin levels from l on; its workgroup is as wide as the widest of them, in whole waves
+			int widest = 0;
+			long e = l;
+			for (; e < an.levels && an.level_ptr[e + 1] - an.level_ptr[e] <= an.chain_rows; e++)
+				widest = std::max(widest, an.level_ptr[e + 1] - an.level_ptr[e]);
+			s.chain = 1;
+			s.l1 = (int) e;
+			s.block = std::min(TRSV_CHAIN_BLOCK_MAX, (widest + WAVE - 1) / WAVE * WAVE);
+			l = e;
+		}
+		an.plan.push_back(s);
+	}
+}
+
+}  // namespace spmv
+
+using namespace spmv;
+
+struct spmv_mi355x_trsv {
+	int uplo = 0, diag = 0, precision = 0, device = 0;
+	bool f32 = false;
+	long n = 0, nnz_kept = 0, levels = 0, max_level_rows = 0;
+	int chain_rows = 0;
+	std::vector<TrsvStep> plan;
+	TrsvArrays arr = {};
+	void * owned[8] = {};                 // the device arrays behind arr
+	void * d_b = nullptr, * d_x = nullptr;     // the vectors of the host-buffer solve, allocated at its first call
+	double mem_footprint = 0;
+};
+
+namespace spmv {
+
+// STORED: the diagonal of row i is the first stored entry with column i (the rule of jacobi_diagonal); it must exist, be finite and
+// non-zero after narrowing to the handle's precision, and be the only entry with column i. The first bad row is reported.
+template <typename T>
+static int
+trsv_check_diagonal(long n, const int32_t * rp, const int32_t * ci, const double * va)
+{
+	long bad = n;
+	#pragma omp parallel for num_threads(spmv::host_threads()) reduction(min : bad) schedule(static, 4096)
+	for (long i = 0; i < n; i++)
+	{
+		long at = -1;
+		bool twice = false;
+		for (long j = rp[i]; j < rp[i + 1]; j++)
+			if (ci[j] == i)
+			{
+				twice = twice || at >= 0;
+				if (at < 0)
+					at = j;
+			}
+		const T d = at >= 0 ? (T) va[at] : (T) 0;
+		if (at < 0 || twice || !std::isfinite(d) || d == 0)
+			bad = std::min(bad, i);
+	}
+	if (bad == n)
+		return 0;
+	long at = -1, count = 0;
+	for (long j = rp[bad]; j < rp[bad + 1]; j++)
+		if (ci[j] == bad)
+		{
+			if (at < 0)
+				at = j;
+			count++;
+		}
+	if (at < 0)
+		set_error("trsv_create: row %ld has no diagonal entry (SPMV_MI355X_DIAG_STORED needs one in every row)", bad);
+	else if (count > 1)
+		set_error("trsv_create: row %ld stores %ld entries with column %ld: the diagonal must be stored once", bad, count, bad);
+	else
+		set_error("trsv_create: the diagonal of row %ld is %g in the handle's precision (from %g): it must be finite and non-zero", bad,
+				(double) (T) va[at], va[at]);
+	return 1;
+}
+
+template <typename T>
+static int
+trsv_build(spmv_mi355x_trsv * H, const TrsvAnalysis & an, const int32_t * rp, const int32_t * ci, const double * va)
+{
+	const long n = H->n, levels = an.levels;
+	const long slices = levels ? an.level_slice[levels] : 0;
+	const bool stored = H->diag == SPMV_MI355X_DIAG_STORED;
+	std::vector<int32_t> perm((size_t) n), len((size_t) n);
+	std::vector<T> diag(stored ? (size_t) n : 0);
+	{
+		std::vector<int32_t> next(an.level_ptr.begin(), an.level_ptr.end());
+		for (long i = 0; i < n; i++)                 // ascending rows: (level, row) order
+			perm[next[an.level_of_row[i]]++] = (int32_t) i;
+	}
+	long kept = 0;
+	#pragma omp parallel for num_threads(spmv::host_threads()) reduction(+ : kept) schedule(static, 4096)
+	for (long p = 0; p < n; p++)
+	{
+		const long i = perm[p];
+		int32_t c = 0;
+		bool have = false;
+		for (long j = rp[i]; j < rp[i + 1]; j++)
+		{
+			c += trsv_dep(H->uplo, i, ci[j]);
+			if (stored && !have && ci[j] == i)
+			{
+				diag[p] = (T) va[j];
+				have = true;
+			}
+		}
+		len[p] = c;
+		kept += c;
+	}
+	H->nnz_kept = kept + (stored ? n : 0);
+	// slice s holds the positions [slice_pos[s], slice_pos[s + 1])
+	std::vector<int32_t> slice_pos((size_t) slices + 1, 0);
+	for (long l = 0; l < levels; l++)
+		for (long s = an.level_slice[l]; s < an.level_slice[l + 1]; s++)
+			slice_pos[s] = an.level_ptr[l] + (int32_t) (s - an.level_slice[l]) * TRSV_SLICE;
+	slice_pos[slices] = (int32_t) n;
+	// the last slice of a level ends where the level ends
+	std::vector<int64_t> slice_ptr((size_t) slices + 1, 0);
+	auto slice_end = [&](long s, long l) { return std::min<long>(slice_pos[s] + TRSV_SLICE, an.level_ptr[l + 1]); };
+	for (long l = 0; l < levels; l++)
+		for (long s = an.level_slice[l]; s < an.level_slice[l + 1]; s++)
+		{
+			int32_t w = 0;
+			for (long p = slice_pos[s]; p < slice_end(s, l); p++)
+				w = std::max(w, len[p]);
+			slice_ptr[s + 1] = (int64_t) w * (slice_end(s, l) - slice_pos[s]);     // prefix-summed below
+		}
+	for (long s = 0; s < slices; s++)
+		slice_ptr[s + 1] += slice_ptr[s];
+	const size_t stored_entries = (size_t) slice_ptr[slices];
+	std::vector<T> val(stored_entries, (T) 0);
+	std::vector<int32_t> col(stored_entries, 0);
+	std::vector<int32_t> level_of_slice((size_t) slices);
+	for (long l = 0; l < levels; l++)
+		for (long s = an.level_slice[l]; s < an.level_slice[l + 1]; s++)
+			level_of_slice[s] = (int32_t) l;
+	#pragma omp parallel for num_threads(spmv::host_threads()) schedule(dynamic, 64)
+	for (long s = 0; s < slices; s++)
+	{
+		const long p0 = slice_pos[s], lanes = slice_end(s, level_of_slice[s]) - p0;
+		for (long r = 0; r < lanes; r++)
+		{
+			const long i = perm[p0 + r];
+			int64_t e = slice_ptr[s] + r;
+			for (long j = rp[i]; j < rp[i + 1]; j++)
+				if (trsv_dep(H->uplo, i, ci[j]))
+				{
+					val[e] = (T) va[j];              // narrowed as spmv_mi355x_create narrows
+					col[e] = ci[j];
+					e += lanes;
+				}
+		}
+	}
+	struct Up { const void * src; size_t bytes; } ups[8] = {
+		{val.data(), stored_entries * sizeof(T)}, {col.data(), stored_entries * sizeof(int32_t)},
+		{slice_ptr.data(), slice_ptr.size() * sizeof(int64_t)}, {len.data(), (size_t) n * sizeof(int32_t)},
+		{perm.data(), (size_t) n * sizeof(int32_t)}, {diag.data(), diag.size() * sizeof(T)},
+		{an.level_ptr.data(), an.level_ptr.size() * sizeof(int32_t)}, {an.level_slice.data(), an.level_slice.size() * sizeof(int32_t)}};
+	H->mem_footprint = 0;
+	for (int k = 0; k < 8; k++)
+	{
+		if (k == 5 && !stored)
+			continue;
+		if (upload_bytes(ups[k].src, ups[k].bytes, 0, &H->owned[k]))
+			return 1;
+		H->mem_footprint += (double) ups[k].bytes;
+	}
+	H->arr.val = H->owned[0];
+	H->arr.col = (const int *) H->owned[1];
+	H->arr.slice_ptr = (const int64_t *) H->owned[2];
+	H->arr.len = (const int *) H->owned[3];
+	H->arr.perm = (const int *) H->owned[4];
+	H->arr.diag = H->owned[5];
+	H->arr.level_ptr = (const int *) H->owned[6];
+	H->arr.level_slice = (const int *) H->owned[7];
+	return 0;
+}
+
+static void
+trsv_free(spmv_mi355x_trsv * H)
+{
+	for (void * p : H->owned)
+		if (p)
+			(void) hipFree(p);
+	if (H->d_b)
+		(void) hipFree(H->d_b);
+	if (H->d_x)
+		(void) hipFree(H->d_x);
+	delete H;
+}
+
+}  // namespace spmv
+
+extern "C" {
+
+int
+spmv_mi355x_trsv_analyze(int uplo, long n, const int32_t * row_ptr, const int32_t * col_idx, int chain_rows,
+		int32_t ** level_of_row_out, long * levels_out, long * launches_out, long * max_level_rows_out, int * chain_rows_used_out)
+{
+	if (level_of_row_out)
+		*level_of_row_out = nullptr;
+	if (!trsv_scalars_ok("trsv_analyze", uplo, nullptr, nullptr, n, chain_rows))
+		return 1;
+	if (!row_ptr || (!col_idx && row_ptr[n] > 0))
+	{
+		set_error("trsv_analyze: NULL argument (%s%s )", !row_ptr ? " row_ptr" : "", !col_idx ? " col_idx" : "");
+		return 1;
+	}
+	if (trsv_check_pattern("trsv_analyze", n, row_ptr, col_idx))
+		return 1;
+	TrsvAnalysis an;
+	trsv_analysis(uplo, n, row_ptr, col_idx, chain_rows, an);
+	if (level_of_row_out)
+	{
+		int32_t * lv = (int32_t *) malloc(std::max<size_t>((size_t) n, 1) * sizeof(int32_t));
+		if (!lv)
+		{
+			set_error("trsv_analyze: out of host memory (%ld levels of rows)", n);
+			return 1;
+		}
+		if (n)
+			memcpy(lv, an.level_of_row.data(), (size_t) n * sizeof(int32_t));
+		*level_of_row_out = lv;
+	}
+	if (levels_out)
+		*levels_out = an.levels;
+	if (launches_out)
+		*launches_out = (long) an.plan.size();
+	if (max_level_rows_out)
+		*max_level_rows_out = an.max_level_rows;
+	if (chain_rows_used_out)
+		*chain_rows_used_out = an.chain_rows;
+	return 0;
+}
+
+int
+spmv_mi355x_trsv_create(spmv_mi355x_trsv ** out, int uplo, int diag, int precision, long n, const int32_t * row_ptr,
+		const int32_t * col_idx, const double * values, int chain_rows, int device)
+{
+	if (out)
+		*out = nullptr;
+	// 1. scalars, 2. NULL pointers, 3. the pattern, 4. the diagonal: all on the host; 5. the device
+	if (!trsv_scalars_ok("trsv_create", uplo, &diag, &precision, n, chain_rows))
+		return 1;
+	const bool entries = row_ptr && row_ptr[n] > 0;
+	if (!out || !row_ptr || (entries && (!col_idx || !values)))
+	{
+		set_error("trsv_create: NULL argument (%s%s%s%s )", !out ? " out" : "", !row_ptr ? " row_ptr" : "",
+				entries && !col_idx ? " col_idx" : "", entries && !values ? " values" : "");
+		return 1;
+	}
+	if (trsv_check_pattern("trsv_create", n, row_ptr, col_idx))
+		return 1;
+	const bool f32 = precision == SPMV_MI355X_F32;
+	if (diag == SPMV_MI355X_DIAG_STORED &&
+	    (f32 ? trsv_check_diagonal<float>(n, row_ptr, col_idx, values) : trsv_check_diagonal<double>(n, row_ptr, col_idx, values)))
+		return 1;
+	int ndev = 0;
+	spmv_mi355x_device_count(&ndev);
+	if (ndev < 1)
+	{
+		set_error("trsv_create: no HIP device available: this engine has no CPU fallback");
+		return 1;
+	}
+	if (device < 0)
+		HIP_TRY(hipGetDevice(&device));
+	if (device >= ndev)
+	{
+		set_error("trsv_create: device %d out of range (%d devices)", device, ndev);
+		return 1;
+	}
+	HIP_TRY(hipSetDevice(device));
+	TrsvAnalysis an;
+	trsv_analysis(uplo, n, row_ptr, col_idx, chain_rows, an);
+	spmv_mi355x_trsv * H = new spmv_mi355x_trsv();
+	H->uplo = uplo;
+	H->diag = diag;
+	H->precision = precision;
+	H->f32 = f32;
+	H->device = device;
+	H->n = n;
+	H->levels = an.levels;
+	H->max_level_rows = an.max_level_rows;
+	H->chain_rows = an.chain_rows;
+	H->plan = an.plan;
+	if (f32 ? trsv_build<float>(H, an, row_ptr, col_idx, values) : trsv_build<double>(H, an, row_ptr, col_idx, values))
+	{
+		trsv_free(H);
+		return 1;
+	}
+	*out = H;
+	return 0;
+}
+
+int
+spmv_mi355x_trsv_destroy(spmv_mi355x_trsv * T)
+{
+	if (!T)
+		return 0;
+	(void) hipSetDevice(T->device);
+	trsv_free(T);
+	return 0;
+}
+
+int
+spmv_mi355x_trsv_solve_device_async(spmv_mi355x_trsv * T, const void * b_dev, void * x_dev, void * hip_stream)
+{
+	if (!T || (T->n > 0 && (!b_dev || !x_dev)))
+	{
+		set_error("trsv_solve: NULL argument (%s%s%s )", !T ? " T" : "", T && !b_dev ? " b" : "", T && !x_dev ? " x" : "");
+		return 1;
+	}
+	if (T->plan.empty())
+		return 0;
+	int cur = -1;
+	HIP_TRY(hipGetDevice(&cur));
+	if (cur != T->device)
+		HIP_TRY(hipSetDevice(T->device));
+	hipStream_t st = (hipStream_t) hip_stream;
+	const bool unit = T->diag == SPMV_MI355X_DIAG_UNIT;
+	for (const TrsvStep & s : T->plan)
+		s.chain ? launch_trsv_chain(T->f32, unit, T->arr, s, b_dev, x_dev, st) : launch_trsv_level(T->f32, unit, T->arr, s, b_dev, x_dev, st);
+	HIP_TRY(hipGetLastError());
+	return 0;
+}
+
+int
+spmv_mi355x_trsv_solve(spmv_mi355x_trsv * T, const void * b_host, void * x_host)
+{
+	if (!T || (T->n > 0 && (!b_host || !x_host)))
+	{
+		set_error("trsv_solve: NULL argument (%s%s%s )", !T ? " T" : "", T && !b_host ? " b" : "", T && !x_host ? " x" : "");
+		return 1;
+	}
+	if (T->n == 0)
+		return 0;
+	HIP_TRY(hipSetDevice(T->device));
+	const size_t bytes = (size_t) T->n * (T->f32 ? 4 : 8);
+	if (!T->d_b && (dev_alloc_bytes(&T->d_b, bytes) || dev_alloc_bytes(&T->d_x, bytes)))
+		return 1;
+	HIP_TRY(hipMemcpyAsync(T->d_b, b_host, bytes, hipMemcpyHostToDevice, nullptr));
+	if (spmv_mi355x_trsv_solve_device_async(T, T->d_b, T->d_x, nullptr))
+		return 1;
+	HIP_TRY(hipMemcpyAsync(x_host, T->d_x, bytes, hipMemcpyDeviceToHost, nullptr));
+	HIP_TRY(hipStreamSynchronize(nullptr));
+	return 0;
+}
+
+int
+spmv_mi355x_trsv_info(const spmv_mi355x_trsv * T, long * n_out, long * nnz_kept_out, long * levels_out, long * launches_out,
+		long * max_level_rows_out, int * chain_rows_out)
+{
+	if (!T)
+	{
+		set_error("trsv_info: NULL handle");
+		return 1;
+	}
+	if (n_out)
+		*n_out = T->n;
+	if (nnz_kept_out)
+		*nnz_kept_out = T->nnz_kept;
+	if (levels_out)
+		*levels_out = T->levels;
+	if (launches_out)
+		*launches_out = (long) T->plan.size();
+	if (max_level_rows_out)
+		*max_level_rows_out = T->max_level_rows;
+	if (chain_rows_out)
+		*chain_rows_out = T->chain_rows;
+	return 0;
+}
+
+double
+spmv_mi355x_trsv_mem_footprint(const spmv_mi355x_trsv * T)
+{
+	return T ? T->mem_footprint : 0;
+}
+
+int
+spmv_mi355x_time_trsv_device(spmv_mi355x_trsv * T, const void * b_dev, void * x_dev, int iters, void * hip_stream, double * ms_out)
+{
+	if (!T || !ms_out)
+	{
+		set_error("time_trsv_device: NULL %s", !T ? "handle" : "ms_per_iter_out");
+		return 1;
+	}
+	HIP_TRY(hipSetDevice(T->device));
+	hipStream_t st = (hipStream_t) hip_stream;
+	hipEvent_t e0, e1;
+	HIP_TRY(hipEventCreate(&e0));
+	HIP_TRY(hipEventCreate(&e1));
+	HIP_TRY(hipEventRecord(e0, st));
+	for (int i = 0; i < iters; i++)
+		if (spmv_mi355x_trsv_solve_device_async(T, b_dev, x_dev, hip_stream))
+			return 1;
+	HIP_TRY(hipEventRecord(e1, st));
+	HIP_TRY(hipEventSynchronize(e1));
+	float ms = 0;
+	HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+	(void) hipEventDestroy(e0);
+	(void) hipEventDestroy(e1);
+	*ms_out = iters > 0 ? (double) ms / iters : 0;
+	return 0;
+}
+
+}  // extern "C"

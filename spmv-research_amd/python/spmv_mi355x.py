@@ -62,6 +62,8 @@ SYMBOLS = [
     "spmv_mi355x_spmm_device_async", "spmv_mi355x_time_spmm_device", "spmv_mi355x_spmm", "spmv_mi355x_spmm_plan",
     "spmv_mi355x_update_values_prepare", "spmv_mi355x_update_values", "spmv_mi355x_update_values_device", "spmv_mi355x_update_values_state",
     "spmv_mi355x_update_values_prepare_transposed", "spmv_mi355x_update_values_count",
+    "spmv_mi355x_trsv_analyze", "spmv_mi355x_trsv_create", "spmv_mi355x_trsv_destroy", "spmv_mi355x_trsv_solve_device_async",
+    "spmv_mi355x_trsv_solve", "spmv_mi355x_trsv_info", "spmv_mi355x_trsv_mem_footprint", "spmv_mi355x_time_trsv_device",
 ]
 
 _lib = None
@@ -89,6 +91,7 @@ def lib():
         L.spmv_mi355x_partitioned_format_name.restype = C.c_char_p
         L.spmv_mi355x_partitioned_exchange.restype = C.c_char_p
         L.spmv_mi355x_partitioned_mem_footprint.restype = C.c_double
+        L.spmv_mi355x_trsv_mem_footprint.restype = C.c_double
         L.spmv_mi355x_x_device.restype = C.c_void_p
         L.spmv_mi355x_y_device.restype = C.c_void_p
         L.spmv_mi355x_cgls.restype = C.c_int
@@ -224,6 +227,85 @@ class CsrStream:
     def __del__(self):
         try:
             self.discard()
+        except Exception:
+            pass
+
+
+LOWER, UPPER = 0, 1
+DIAG_STORED, DIAG_UNIT = 0, 1
+_UPLO = {"lower": LOWER, "upper": UPPER, LOWER: LOWER, UPPER: UPPER}
+_DIAG = {"stored": DIAG_STORED, "unit": DIAG_UNIT, DIAG_STORED: DIAG_STORED, DIAG_UNIT: DIAG_UNIT}
+
+
+def trsv_analyze(row_ptr, col_idx, n, uplo, chain_rows=0):
+    """What TriangularSolve derives from the pattern, on the host (spmv_mi355x_trsv_analyze): dict(level_of_row, levels, launches,
+    max_level_rows, chain_rows), chain_rows being the threshold used (the default when 0 was passed)."""
+    row_ptr = np.ascontiguousarray(row_ptr, np.int32)
+    col_idx = np.ascontiguousarray(col_idx, np.int32)
+    lv = C.POINTER(C.c_int32)()
+    levels, launches, widest, used = C.c_long(), C.c_long(), C.c_long(), C.c_int()
+    _check(lib().spmv_mi355x_trsv_analyze(C.c_int(_UPLO[uplo]), C.c_long(n), _p(row_ptr), _p(col_idx), C.c_int(chain_rows), C.byref(lv),
+                                          C.byref(levels), C.byref(launches), C.byref(widest), C.byref(used)))
+    level_of_row = np.ctypeslib.as_array(lv, shape=(max(n, 1),))[:n].copy()
+    lib().spmv_mi355x_free(lv)
+    return dict(level_of_row=level_of_row, levels=levels.value, launches=launches.value, max_level_rows=widest.value,
+                chain_rows=used.value)
+
+
+class TriangularSolve:
+    """T x = b for one triangle of a square CSR matrix (include/spmv_mi355x.h "sparse triangular solve"): uplo "lower" keeps the
+    entries with column <= row, "upper" those with column >= row; diag "stored" divides by the stored diagonal, "unit" takes 1 and
+    ignores what is stored there. Bit-identical to the sequential loop whatever the plan."""
+
+    def __init__(self, row_ptr, col_idx, values, n, uplo="lower", diag="stored", dtype=np.float64, chain_rows=0, device=-1):
+        row_ptr = np.ascontiguousarray(row_ptr, np.int32)
+        col_idx = np.ascontiguousarray(col_idx, np.int32)
+        values = np.ascontiguousarray(values, np.float64)
+        self.dtype = np.dtype(dtype)
+        self.n = int(n)
+        self.h = C.c_void_p()
+        _check(lib().spmv_mi355x_trsv_create(C.byref(self.h), C.c_int(_UPLO[uplo]), C.c_int(_DIAG[diag]),
+                                             F64 if self.dtype == np.float64 else F32, C.c_long(n), _p(row_ptr), _p(col_idx), _p(values),
+                                             C.c_int(chain_rows), C.c_int(device)))
+        self.mem_footprint = lib().spmv_mi355x_trsv_mem_footprint(self.h)
+
+    @property
+    def info(self):
+        """dict(n, nnz_kept, levels, launches, max_level_rows, chain_rows) of spmv_mi355x_trsv_info"""
+        n, kept, levels, launches, widest, chain = C.c_long(), C.c_long(), C.c_long(), C.c_long(), C.c_long(), C.c_int()
+        _check(lib().spmv_mi355x_trsv_info(self.h, C.byref(n), C.byref(kept), C.byref(levels), C.byref(launches), C.byref(widest),
+                                           C.byref(chain)))
+        return dict(n=n.value, nnz_kept=kept.value, levels=levels.value, launches=launches.value, max_level_rows=widest.value,
+                    chain_rows=chain.value)
+
+    def solve(self, b):
+        """x of T x = b for a host vector b of n values (spmv_mi355x_trsv_solve; blocking)"""
+        b = np.ascontiguousarray(b, self.dtype)
+        if b.shape != (self.n,):
+            raise ValueError(f"b must have {self.n} values, got {b.shape}")
+        x = np.full(max(self.n, 1), np.nan, self.dtype)
+        _check(lib().spmv_mi355x_trsv_solve(self.h, _p(b), _p(x)))
+        return x[:self.n]
+
+    def solve_device(self, b_ptr, x_ptr, stream=None):
+        """The same on device pointers (b_ptr == x_ptr: in place), enqueued on `stream` (spmv_mi355x_trsv_solve_device_async)"""
+        _check(lib().spmv_mi355x_trsv_solve_device_async(self.h, C.c_void_p(b_ptr), C.c_void_p(x_ptr), C.c_void_p(stream or 0)))
+
+    def time_device(self, b_ptr, x_ptr, iters, stream=None):
+        """ms per solve of `iters` back-to-back solves, timed with HIP events on `stream` (spmv_mi355x_time_trsv_device)"""
+        ms = C.c_double()
+        _check(lib().spmv_mi355x_time_trsv_device(self.h, C.c_void_p(b_ptr), C.c_void_p(x_ptr), C.c_int(iters), C.c_void_p(stream or 0),
+                                                  C.byref(ms)))
+        return ms.value
+
+    def close(self):
+        if getattr(self, "h", None) is not None and self.h:
+            lib().spmv_mi355x_trsv_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
         except Exception:
             pass
 

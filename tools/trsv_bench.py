@@ -1,0 +1,158 @@
+"""A sparse triangular solve (spmv_mi355x_trsv_*; include/spmv_mi355x.h "sparse triangular solve") against its floor, and the
+chain_rows sweep behind the default.
+
+For the LOWER triangle (diagonal included) of each workload twin of bench.py and of the 27-point stencil of tools/solver_bench.py the
+tool prints n, the kept entries, the levels and the widest level, and per chain_rows value the launches of the plan. In one process,
+alternating window by window, it times
+  floor:  time_device of an E.Matrix (sell_c_sigma, its own best layout) built from the same triangle: one SpMV reads the same
+          entries with no dependency between rows, so no triangular solve of this matrix can be faster;
+  trsv:   time_device of one TriangularSolve handle per chain_rows value, `reps` back-to-back solves under HIP events, reps
+          calibrated so that a leg lasts about --leg-ms.
+The medians over the windows are reported with their spreads, and the ratio solve / floor.
+
+    python tools/trsv_bench.py                                       # cant, nlpkkt240, stencil160, fp64
+    python tools/trsv_bench.py --runs cant:f64,cant:f32,stencil40:f64 --windows 7 --chain-rows 64,256,1024,4096
+    python tools/trsv_bench.py --runs nlpkkt240:f64 --scale 0.25
+One JSON line per run and a table at the end.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "spmv-research_amd", "python"), os.path.join(ROOT, "tools")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+
+def lower_triangle(rp, ci, va, n):
+    """the entries with column <= row, stored order kept; row by row in blocks so that no index array of the full size is held twice"""
+    rp = np.asarray(rp, np.int64)
+    keep = np.empty(len(ci), bool)
+    counts = np.zeros(n, np.int64)
+    step = 1 << 20
+    for r0 in range(0, n, step):
+        r1 = min(n, r0 + step)
+        rows = np.repeat(np.arange(r0, r1, dtype=np.int32), np.diff(rp[r0:r1 + 1]))
+        k = ci[rp[r0]:rp[r1]] <= rows
+        keep[rp[r0]:rp[r1]] = k
+        counts[r0:r1] = np.bincount(rows[k] - r0, minlength=r1 - r0)
+    rp2 = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+    return rp2, np.ascontiguousarray(ci[keep]), np.ascontiguousarray(va[keep])
+
+
+def safe_diagonal(rp, ci, va, n):
+    """the twins were made for SpMV: where a row's diagonal is missing from the pattern the tool cannot add one (the pattern is the
+    workload), so such a workload is solved under DIAG_UNIT; a stored zero or tiny diagonal is replaced by 1 (timing does not care)"""
+    rows = np.repeat(np.arange(n, dtype=np.int32), np.diff(rp))
+    on = ci == rows
+    has = np.zeros(n, bool)
+    has[rows[on]] = True
+    va = va.copy()
+    d = va[on]
+    d[~np.isfinite(d) | (np.abs(d) < 1e-30)] = 1.0
+    va[on] = d
+    return va, bool(has.all()) and int(on.sum()) == n
+
+
+def run(E, torch, name, rp, ci, va, n, dts, data, args):
+    np_dtype = np.float32 if dts == "f32" else np.float64
+    tdt = torch.float32 if dts == "f32" else torch.float64
+    t0 = time.perf_counter()
+    rp, ci, va = lower_triangle(rp, ci, va, n)
+    va, stored = safe_diagonal(rp, ci, va, n)
+    t_tri = time.perf_counter() - t0
+    M = E.Matrix(rp, ci, va, n, n, "sell_c_sigma", np_dtype)
+    x = (torch.rand(n, device="cuda", dtype=torch.float64) * 2 - 1).to(tdt)
+    y = torch.empty(n + 64, dtype=tdt, device="cuda")
+    b = (torch.rand(n, device="cuda", dtype=torch.float64) * 2 - 1).to(tdt)
+    out = torch.empty(n, dtype=tdt, device="cuda")
+    stream = torch.cuda.current_stream().cuda_stream
+    handles, create_s = {}, {}
+    for c in args.chain_rows:
+        t0 = time.perf_counter()
+        handles[c] = E.TriangularSolve(rp, ci, va, n, "lower", "stored" if stored else "unit", np_dtype, chain_rows=c)
+        create_s[c] = time.perf_counter() - t0
+    infos = {c: T.info for c, T in handles.items()}
+    reps = {}
+    for c, T in handles.items():                          # the first solve warms up, the second calibrates
+        T.time_device(b.data_ptr(), out.data_ptr(), 1, stream)
+        one = T.time_device(b.data_ptr(), out.data_ptr(), 2, stream)
+        reps[c] = int(min(200, max(3, np.ceil(args.leg_ms / max(one, 1e-3)))))
+    legs = {"spmv": []}
+    legs.update({c: [] for c in handles})
+    for w in range(args.windows + 1):                     # window 0 warms every leg up and is dropped
+        t = {"spmv": M.time_device(x.data_ptr(), y.data_ptr(), args.reps, stream)}
+        for c, T in handles.items():
+            t[c] = T.time_device(b.data_ptr(), out.data_ptr(), reps[c], stream)
+        torch.cuda.synchronize()
+        if w:
+            for k, v in t.items():
+                legs[k].append(v)
+    first = infos[args.chain_rows[0]]
+    rec = dict(workload=name, dtype=dts, data=data, n=int(n), nnz_kept=int(first["nnz_kept"]), diag="stored" if stored else "unit",
+               levels=int(first["levels"]), max_level_rows=int(first["max_level_rows"]), floor_format=M.format_name,
+               spmv_ms=round(float(np.median(legs["spmv"])), 5), spmv_spread=[round(min(legs["spmv"]), 5), round(max(legs["spmv"]), 5)],
+               windows=args.windows, triangle_seconds=round(t_tri, 2), sweep=[])
+    for c, T in handles.items():
+        ts = legs[c]
+        rec["sweep"].append(dict(chain_rows=int(infos[c]["chain_rows"]), launches=int(infos[c]["launches"]), reps=reps[c],
+                                 ms=round(float(np.median(ts)), 5), spread=[round(min(ts), 5), round(max(ts), 5)],
+                                 over_floor=round(float(np.median(ts)) / rec["spmv_ms"], 2), create_seconds=round(create_s[c], 2),
+                                 mem_footprint=int(T.mem_footprint)))
+        T.close()
+    M.close()
+    print(json.dumps(rec), flush=True)
+    return rec
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--runs", default="cant:f64,nlpkkt240:f64,stencil160:f64", help="workload|stencil<N>:f64|f32,...")
+    ap.add_argument("--windows", type=int, default=7)
+    ap.add_argument("--chain-rows", default="64,256,1024,4096", help="the thresholds to sweep, first = the one the header line reports")
+    ap.add_argument("--reps", type=int, default=20, help="SpMV launches per timed floor leg")
+    ap.add_argument("--leg-ms", type=float, default=40.0, help="solves per timed leg: as many as last about this long (3 .. 200)")
+    ap.add_argument("--scale", type=float, default=1.0, help="shrink the workload twins")
+    args = ap.parse_args()
+    if args.windows < 5:
+        ap.error("--windows: at least 5")
+    args.chain_rows = [int(c) for c in args.chain_rows.split(",")]
+    os.environ.setdefault("OMP_NUM_THREADS", "16")
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("trsv_bench.py needs a GPU: the engine has no CPU path")
+    import bench
+    import spmv_host as H
+    import spmv_mi355x as E
+    from solver_bench import stencil27
+    rows = []
+    for item in args.runs.split(","):
+        w, dts = item.split(":")
+        if w.startswith("stencil"):
+            rp, ci, va, n = stencil27(int(w[len("stencil"):]))
+            data = "generated"
+        else:
+            A, data = bench.load_workload(H, w, args.scale)
+            if A["m"] != A["n"]:
+                raise SystemExit(f"{w}: {A['m']} x {A['n']} is not square")
+            rp, ci, va, n = A["row_ptr"], A["col_idx"], np.ascontiguousarray(A["values"], np.float64), A["n"]
+            del A
+        rows.append(run(E, torch, w, rp, ci, va, n, dts, data, args))
+        del rp, ci, va
+    print(f"{'workload':11s} {'dtype':5s} {'n':>9s} {'kept nnz':>10s} {'levels':>7s} {'widest':>8s} {'spmv ms':>9s} | "
+          f"{'chain_rows':>10s} {'launches':>8s} {'trsv ms':>9s} {'spread':>19s} {'/ floor':>8s}")
+    for r in rows:
+        for k, s in enumerate(r["sweep"]):
+            head = (f"{r['workload']:11s} {r['dtype']:5s} {r['n']:9d} {r['nnz_kept']:10d} {r['levels']:7d} {r['max_level_rows']:8d} "
+                    f"{r['spmv_ms']:9.4f}") if k == 0 else " " * 65
+            print(f"{head} | {s['chain_rows']:10d} {s['launches']:8d} {s['ms']:9.4f} {s['spread'][0]:9.4f} ..{s['spread'][1]:8.4f} "
+                  f"{s['over_floor']:8.2f}")
+
+
+if __name__ == "__main__":
+    main()

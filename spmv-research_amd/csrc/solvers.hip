@@ -20,11 +20,31 @@
 // eps = 1e-15*|b|, explicit residual every 100 iterations with x_best tracking and (CG only) the restart rule.
 // Dot products accumulate in double for both precisions (the reference accumulates in ValueType with an OpenMP
 // thread-count-dependent order, so its last bits are not reproducible either).
+//
+// One set of kernels and one host solve<T> serve all six entry points: k independent systems A x_j = b_j are solved
+// together, and the single-RHS and row-partitioned (_dist) entries are its k = 1 case. Column j of spmv_mi355x_pcg_multi /
+// spmv_mi355x_pbicgstab_multi returns exactly what spmv_mi355x_pcg / _pbicgstab return for b_j on the same handle. The
+// k recurrences stay independent (this is not block CG with a shared subspace); what they share is the matrix pass, the
+// launches and the Jacobi diagonal:
+//   * every solver vector is a row-major m x k block (ld = k), K is one vector of m; the _multi entries' matrix product is
+//     one spmv_mi355x_spmm_device_async over the k columns, bit-identical per column to the SpMV of the single entries;
+//   * each vector kernel serves a chunk of KC in {8, 4, 2, 1} columns (k = 8s, then the binary remainder, as the SpMM
+//     does); a thread owns row i of its chunk, so it reads KC contiguous values per vector (vector loads when ld and the
+//     chunk start are multiples of KC);
+//   * bit-identity: every per-column dot product goes through the same additions in the same order whatever chunk the
+//     column sits in (same nb and grid-stride rows per (block, thread), same wave shuffle tree, same in-order sum of the
+//     4 wave partials, same order over the partials), and every element update is the same T expression, so FMA
+//     contraction matches; the KC columns only share the LDS barriers of one block reduction;
+//   * state is SolverState[2][k], partials are [k][NUM_SLOTS][MAX_PART]; each column has its own `done` flag, which
+//     freezes that column only (its values are stored back unchanged; the SpMM keeps computing it);
+//   * block 0 of the last chunk of an iteration's last kernel posts (iterations finished, loop count at which the last
+//     still-running column broke, or -1) to the progress word, so the one stop rule fires once every column has broken.
 
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "common.hpp"
@@ -33,85 +53,232 @@
 
 namespace spmv {
 
-// Distributed solves: the per-block partials of up to 3 slots are summed into red[], all-reduced over the ranks by the
-// caller's collective, and written back as the single partial of their slot (consumers then run with nb = 1).
-struct SlotList {
-	int n;
-	int s[3];
-};
+constexpr int MAX_KC = 8;          // columns per chunk
 
-__global__ __launch_bounds__(VB) void
-reduce_slots_kernel(const double * __restrict__ part, int nb, SlotList sl, double * __restrict__ red)
+// block_sum() for N values at once: each value goes through the same shuffle tree and the same in-order sum of the
+// VB / WAVE wave partials, behind one set of barriers.
+template <int N>
+__device__ __forceinline__ void
+block_sum_n(double * v)
 {
-	const double v = sum_partials(part, sl.s[blockIdx.x], nb);
+	__shared__ double sh[N][VB / WAVE];
+	__shared__ double total[N];
+	#pragma unroll
+	for (int c = 0; c < N; c++)
+		for (int o = WAVE / 2; o > 0; o >>= 1)
+			v[c] += __shfl_down(v[c], o, WAVE);
+	__syncthreads();                       // protects sh/total against the previous call
+	if (threadIdx.x % WAVE == 0)
+	{
+		#pragma unroll
+		for (int c = 0; c < N; c++)
+			sh[c][threadIdx.x / WAVE] = v[c];
+	}
+	__syncthreads();
+	if (threadIdx.x < N)
+	{
+		double s = 0;
+		for (int w = 0; w < VB / WAVE; w++)
+			s += sh[threadIdx.x][w];
+		total[threadIdx.x] = s;
+	}
+	__syncthreads();
+	#pragma unroll
+	for (int c = 0; c < N; c++)
+		v[c] = total[c];
+}
+
+__host__ __device__ __forceinline__ long
+part_at(int col, int slot)
+{
+	return ((long) col * NUM_SLOTS + slot) * MAX_PART;
+}
+
+// sum_partials() of S slots for the KC columns c0.. : out[s * KC + c]
+template <int KC, int S>
+__device__ __forceinline__ void
+sum_partials_n(const double * __restrict__ part, int c0, const int (&slot)[S], int nb, double * out)
+{
+	#pragma unroll
+	for (int s = 0; s < S; s++)
+	{
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+		{
+			const double * p = part + part_at(c0 + c, slot[s]);
+			double v = 0;
+			for (int i = threadIdx.x; i < nb; i += VB)
+				v += p[i];
+			out[s * KC + c] = v;
+		}
+	}
+	block_sum_n<S * KC>(out);
+}
+
+// store_partial() of S slots for the KC columns c0.. from v[s * KC + c]; only the columns in `keep` are written
+template <int KC, int S>
+__device__ __forceinline__ void
+store_partials_n(double * __restrict__ part, int c0, const int (&slot)[S], double * v, unsigned keep)
+{
+	block_sum_n<S * KC>(v);
 	if (threadIdx.x == 0)
-		red[blockIdx.x] = v;
+	{
+		#pragma unroll
+		for (int s = 0; s < S; s++)
+		{
+			#pragma unroll
+			for (int c = 0; c < KC; c++)
+				if (keep >> c & 1)
+					part[part_at(c0 + c, slot[s]) + blockIdx.x] = v[s * KC + c];
+		}
+	}
 }
 
-__global__ void
-scatter_slots_kernel(double * __restrict__ part, SlotList sl, const double * __restrict__ red)
+// KC contiguous values of one row; `vec` (uniform) when the row start is KC-aligned
+template <typename T, int KC>
+__device__ __forceinline__ void
+load_row(T (&o)[KC], const T * p, bool vec)
 {
-	if ((int) threadIdx.x < sl.n)
-		part[(long) sl.s[threadIdx.x] * MAX_PART] = red[threadIdx.x];
+	if constexpr (KC > 1)
+	{
+		if (vec)
+		{
+			typedef T V __attribute__((ext_vector_type(KC)));
+			const V t = *(const V *) p;
+			#pragma unroll
+			for (int c = 0; c < KC; c++)
+				o[c] = t[c];
+			return;
+		}
+	}
+	#pragma unroll
+	for (int c = 0; c < KC; c++)
+		o[c] = p[c];
 }
 
+template <typename T, int KC>
+__device__ __forceinline__ void
+store_row(T * p, const T (&o)[KC], bool vec)
+{
+	if constexpr (KC > 1)
+	{
+		if (vec)
+		{
+			typedef T V __attribute__((ext_vector_type(KC)));
+			V t;
+			#pragma unroll
+			for (int c = 0; c < KC; c++)
+				t[c] = o[c];
+			*(V *) p = t;
+			return;
+		}
+	}
+	#pragma unroll
+	for (int c = 0; c < KC; c++)
+		p[c] = o[c];
+}
+
+// the columns of the chunk that have not reached the `err < eps` break
+template <int KC>
+__device__ __forceinline__ unsigned
+live_mask(const SolverState * __restrict__ st_p, int c0)
+{
+	unsigned live = 0;
+	#pragma unroll
+	for (int c = 0; c < KC; c++)
+		if (!st_p[c0 + c].done)
+			live |= 1u << c;
+	return live;
+}
 
 // ------------------------------------------------------------------------------------------------ shared kernels
+// Every vector kernel below serves the KC columns c0.. of the m x k blocks (row stride ld), each column on its own.
 
 // r = b - Ax ; partials: A = r.r, B = b.b     (bench_cg.cpp:146-150,163-166)
-template <typename T>
+template <typename T, int KC>
 __global__ __launch_bounds__(VB) void
-residual_kernel(const T * __restrict__ b, const T * __restrict__ Ax, T * __restrict__ r, long m, double * __restrict__ part)
+residual_kernel(const T * __restrict__ b, const T * __restrict__ Ax, T * __restrict__ r, long m, long ld, int c0,
+		double * __restrict__ part)
 {
-	double rr = 0, bb = 0;
+	const bool vec = ld % KC == 0 && c0 % KC == 0;
+	double acc[2 * KC] = {};
 	GRID_STRIDE(i, m)
 	{
-		const T bi = b[i];
-		const T ri = bi + (T) -1 * Ax[i];
-		r[i] = ri;
-		rr += (double) ri * (double) ri;
-		bb += (double) bi * (double) bi;
+		const long o = i * ld + c0;
+		T bv[KC], av[KC], rv[KC];
+		load_row(bv, b + o, vec);
+		load_row(av, Ax + o, vec);
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+		{
+			const T bi = bv[c];
+			const T ri = bi + (T) -1 * av[c];
+			rv[c] = ri;
+			acc[c] += (double) ri * (double) ri;
+			acc[KC + c] += (double) bi * (double) bi;
+		}
+		store_row(r + o, rv, vec);
 	}
-	store_partial(part, P_A, rr);
-	store_partial(part, P_B, bb);
+	store_partials_n<KC, 2>(part, c0, {P_A, P_B}, acc, ~0u);
 }
 
-template <typename T>
+// the explicit-residual step of the chunk's columns (explicit_decide, solvers_common.hpp): x_best = x on a promotion;
+// r = r_explicit, p = z = r/K and partial C = z.r on a restart
+template <typename T, int KC>
 __global__ __launch_bounds__(VB) void
 explicit_kernel(const SolverState * __restrict__ st_p, const T * __restrict__ x, T * __restrict__ x_best,
-		const T * __restrict__ r_explicit, T * __restrict__ r, T * __restrict__ p, const T * __restrict__ K, long m,
-		int nb, int allow_restart, int ignore_done, double * __restrict__ part)
+		const T * __restrict__ r_explicit, T * __restrict__ r, T * __restrict__ p, const T * __restrict__ K, long m, long ld,
+		int c0, int nb, int allow_restart, int ignore_done, double * __restrict__ part)
 {
-	const SolverState st = *st_p;
-	if (st.done && !ignore_done)
+	const unsigned act = ignore_done ? (1u << KC) - 1 : live_mask<KC>(st_p, c0);
+	if (!act)
 		return;
-	const double err_explicit = sqrt(sum_partials(part, P_A, nb));
-	bool promote, restart;
-	explicit_decide(st, err_explicit, allow_restart, promote, restart);
-	double zr = 0;
-	if (promote || restart)
+	double ee[KC];
+	sum_partials_n<KC, 1>(part, c0, {P_A}, nb, ee);
+	unsigned promote = 0, restart = 0;
+	#pragma unroll
+	for (int c = 0; c < KC; c++)
+	{
+		bool pr, rs;
+		explicit_decide(st_p[c0 + c], sqrt(ee[c]), allow_restart, pr, rs);
+		if (act >> c & 1)
+		{
+			promote |= (unsigned) pr << c;
+			restart |= (unsigned) rs << c;
+		}
+	}
+	double zr[KC] = {};
+	if (promote | restart)
 	{
 		GRID_STRIDE(i, m)
 		{
-			if (promote)
-				x_best[i] = x[i];
-			if (restart)
+			const long o = i * ld + c0;
+			#pragma unroll
+			for (int c = 0; c < KC; c++)
 			{
-				const T ri = r_explicit[i];
-				const T zi = ri / K[i];
-				r[i] = ri;
-				p[i] = zi;
-				zr += (double) zi * (double) ri;
+				if (promote >> c & 1)
+					x_best[o + c] = x[o + c];
+				if (restart >> c & 1)
+				{
+					const T ri = r_explicit[o + c];
+					const T zi = ri / K[i];
+					r[o + c] = ri;
+					p[o + c] = zi;
+					zr[c] += (double) zi * (double) ri;
+				}
 			}
 		}
 	}
 	if (restart)
-		store_partial(part, P_C, zr);
+		store_partials_n<KC, 1>(part, c0, {P_C}, zr, restart);
 }
 
+// the same decisions again, then the state of column blockIdx.x updated in place; one block per column
 __global__ __launch_bounds__(VB) void
-explicit_fin_kernel(SolverState * __restrict__ st_p, int nb, int allow_restart, int ignore_done, const double * __restrict__ part)
+explicit_fin_kernel(SolverState * __restrict__ st_base, int nb, int allow_restart, int ignore_done, const double * __restrict__ part_base)
 {
+	SolverState * st_p = st_base + blockIdx.x;
+	const double * part = part_base + part_at(blockIdx.x, 0);
 	SolverState st = *st_p;
 	if (st.done && !ignore_done)
 		return;
@@ -135,29 +302,12 @@ explicit_fin_kernel(SolverState * __restrict__ st_p, int nb, int allow_restart, 
 	}
 }
 
-// ------------------------------------------------------------------------------------------------ CG
-
-// z0 = r0/K, p0 = z0 (bench_cg.cpp:153-157); partial C = z.r
-template <typename T>
-__global__ __launch_bounds__(VB) void
-cg_init_kernel(const T * __restrict__ r, const T * __restrict__ K, T * __restrict__ p, long m, double * __restrict__ part)
-{
-	double zr = 0;
-	GRID_STRIDE(i, m)
-	{
-		const T ri = r[i];
-		const T zi = ri / K[i];
-		p[i] = zi;
-		zr += (double) zi * (double) ri;
-	}
-	store_partial(part, P_C, zr);
-}
-
-// eps / eps_counter / first error (bench_cg.cpp:159-182); 1 block. mode 0 = CG (zr = z.r from partial C),
+// eps / eps_counter / first error (bench_cg.cpp:159-182); one block per column. mode 0 = CG (zr = z.r from partial C),
 // mode 1 = BiCGSTAB (zr = s_pk_p = (r0_, rk) = r.r since r0_ = rk, bench_bicg.cpp:232-241).
 __global__ __launch_bounds__(VB) void
-init_state_kernel(SolverState * __restrict__ st_p, int nb, int mode, const double * __restrict__ part)
+init_state_kernel(SolverState * __restrict__ st_base, int k, int nb, int mode, const double * __restrict__ part_base)
 {
+	const double * part = part_base + part_at(blockIdx.x, 0);
 	const double rr = sum_partials(part, P_A, nb);
 	const double bb = sum_partials(part, P_B, nb);
 	const double zr = mode == 0 ? sum_partials(part, P_C, nb) : rr;
@@ -175,90 +325,205 @@ init_state_kernel(SolverState * __restrict__ st_p, int nb, int mode, const doubl
 		st.restarts = 0;
 		st.done = mode == 0 && st.err < st.eps;      // the first `if (err < eps) break` (k = 0); BiCGSTAB never breaks
 		st.pad = 0;
-		st_p[0] = st;
-		st_p[1] = st;
+		st_base[blockIdx.x] = st;
+		st_base[k + blockIdx.x] = st;
 	}
+}
+
+// history rows of the chunk's columns at iteration it (block 0, thread 0)
+template <int KC>
+__device__ __forceinline__ void
+record_history(const SolverState * __restrict__ st_p, int c0, unsigned cols, double * __restrict__ history, long hist_ld, long it)
+{
+	if (history && blockIdx.x == 0 && threadIdx.x == 0)
+	{
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+			if (cols >> c & 1)
+			{
+				const SolverState & st = st_p[c0 + c];
+				double * h = history + (c0 + c) * hist_ld + 3 * it;
+				h[0] = st.err;
+				h[1] = st.err_explicit;
+				h[2] = st.err_best;
+			}
+	}
+}
+
+// (iterations finished, loop count at which the last still-running column broke, or -1) from the next states of all
+// k columns: the earlier chunks wrote theirs in earlier launches, this thread wrote its own chunk's
+__device__ __forceinline__ void
+post_columns_progress(const SolverState * st_next, int k, long it, volatile long * host_progress)
+{
+	long broke_at = 0;
+	for (int c = 0; c < k; c++)
+	{
+		if (!st_next[c].done)
+		{
+			broke_at = -1;
+			break;
+		}
+		broke_at = st_next[c].k > broke_at ? st_next[c].k : broke_at;
+	}
+	post_progress(host_progress, it + 1, broke_at);
+}
+
+// ------------------------------------------------------------------------------------------------ CG
+
+// z0 = r0/K, p0 = z0 (bench_cg.cpp:153-157); partial C = z.r
+template <typename T, int KC>
+__global__ __launch_bounds__(VB) void
+cg_init_kernel(const T * __restrict__ r, const T * __restrict__ K, T * __restrict__ p, long m, long ld, int c0,
+		double * __restrict__ part)
+{
+	const bool vec = ld % KC == 0 && c0 % KC == 0;
+	double zr[KC] = {};
+	GRID_STRIDE(i, m)
+	{
+		const long o = i * ld + c0;
+		T rv[KC], pv[KC];
+		load_row(rv, r + o, vec);
+		const T ki = K[i];
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+		{
+			const T ri = rv[c];
+			const T zi = ri / ki;
+			pv[c] = zi;
+			zr[c] += (double) zi * (double) ri;
+		}
+		store_row(p + o, pv, vec);
+	}
+	store_partials_n<KC, 1>(part, c0, {P_C}, zr, ~0u);
 }
 
 // partial A = p.Ap ; block 0 records the per-iteration report line (bench_cg.cpp:249)
-template <typename T>
+template <typename T, int KC>
 __global__ __launch_bounds__(VB) void
-cg_dot_kernel(const SolverState * __restrict__ st_p, const T * __restrict__ p, const T * __restrict__ Ap, long m,
-		double * __restrict__ history, long it, double * __restrict__ part)
+cg_dot_kernel(const SolverState * __restrict__ st_p, const T * __restrict__ p, const T * __restrict__ Ap, long m, long ld,
+		int c0, double * __restrict__ history, long hist_ld, long it, double * __restrict__ part)
 {
-	const SolverState st = *st_p;
-	if (st.done)
+	const unsigned live = live_mask<KC>(st_p, c0);
+	if (!live)
 		return;
-	if (history && blockIdx.x == 0 && threadIdx.x == 0)
-	{
-		history[3 * it + 0] = st.err;
-		history[3 * it + 1] = st.err_explicit;
-		history[3 * it + 2] = st.err_best;
-	}
-	double s = 0;
+	record_history<KC>(st_p, c0, live, history, hist_ld, it);
+	const bool vec = ld % KC == 0 && c0 % KC == 0;
+	double s[KC] = {};
 	GRID_STRIDE(i, m)
-		s += (double) p[i] * (double) Ap[i];
-	store_partial(part, P_A, s);
+	{
+		const long o = i * ld + c0;
+		T pv[KC], av[KC];
+		load_row(pv, p + o, vec);
+		load_row(av, Ap + o, vec);
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+			s[c] += (double) pv[c] * (double) av[c];
+	}
+	store_partials_n<KC, 1>(part, c0, {P_A}, s, live);
 }
 
 // ak = (z.r)/(p.Ap); x += ak p; r -= ak Ap; z = r/K (not stored); partials D = z.r, E = r.r   (bench_cg.cpp:259-274)
-template <typename T>
+template <typename T, int KC>
 __global__ __launch_bounds__(VB) void
 cg_update_kernel(const SolverState * __restrict__ st_p, T * __restrict__ x, T * __restrict__ r, const T * __restrict__ p,
-		const T * __restrict__ Ap, const T * __restrict__ K, long m, int nb, double * __restrict__ part)
+		const T * __restrict__ Ap, const T * __restrict__ K, long m, long ld, int c0, int nb, double * __restrict__ part)
 {
-	const SolverState st = *st_p;
-	if (st.done)
+	const unsigned live = live_mask<KC>(st_p, c0);
+	if (!live)
 		return;
-	const T ak = (T) (st.zr / sum_partials(part, P_A, nb));
-	double zr = 0, rr = 0;
+	const bool vec = ld % KC == 0 && c0 % KC == 0;
+	double pap[KC];
+	sum_partials_n<KC, 1>(part, c0, {P_A}, nb, pap);
+	T ak[KC];
+	#pragma unroll
+	for (int c = 0; c < KC; c++)
+		ak[c] = (T) (st_p[c0 + c].zr / pap[c]);
+	double acc[2 * KC] = {};
 	GRID_STRIDE(i, m)
 	{
-		x[i] = x[i] + ak * p[i];
-		const T ri = r[i] + (-ak) * Ap[i];
-		r[i] = ri;
-		const T zi = ri / K[i];
-		zr += (double) zi * (double) ri;
-		rr += (double) ri * (double) ri;
+		const long o = i * ld + c0;
+		T xv[KC], rv[KC], pv[KC], av[KC];
+		load_row(xv, x + o, vec);
+		load_row(rv, r + o, vec);
+		load_row(pv, p + o, vec);
+		load_row(av, Ap + o, vec);
+		const T ki = K[i];
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+		{
+			const T xi = xv[c] + ak[c] * pv[c];
+			const T ri = rv[c] + (-ak[c]) * av[c];
+			const T zi = ri / ki;
+			acc[c] += (double) zi * (double) ri;
+			acc[KC + c] += (double) ri * (double) ri;
+			if (live >> c & 1)
+			{
+				xv[c] = xi;
+				rv[c] = ri;
+			}
+		}
+		store_row(x + o, xv, vec);
+		store_row(r + o, rv, vec);
 	}
-	store_partial(part, P_D, zr);
-	store_partial(part, P_E, rr);
+	store_partials_n<KC, 2>(part, c0, {P_D, P_E}, acc, live);
 }
 
-// bk = (z.r)_new / (z.r)_old ; p = z + bk p (bench_cg.cpp:278-283); block 0 writes the next state: k+1, err = |r|
-// and the `err < eps` break of the next loop top (bench_cg.cpp:209-214,238-239).
-template <typename T>
+// bk = (z.r)_new / (z.r)_old ; p = z + bk p (bench_cg.cpp:278-283); block 0 writes the next states: k+1, err = |r| and the
+// `err < eps` break of the next loop top (bench_cg.cpp:209-214,238-239); the last chunk posts progress
+template <typename T, int KC>
 __global__ __launch_bounds__(VB) void
 cg_direction_kernel(const SolverState * __restrict__ st_p, SolverState * __restrict__ st_next, const T * __restrict__ r,
-		T * __restrict__ p, const T * __restrict__ K, long m, int nb, const double * __restrict__ part, long it,
-		volatile long * host_progress)
+		T * __restrict__ p, const T * __restrict__ K, long m, long ld, int c0, int k, int nb, const double * __restrict__ part,
+		long it, volatile long * host_progress)
 {
-	const SolverState st = *st_p;
-	if (st.done)
+	const unsigned live = live_mask<KC>(st_p, c0);
+	double zr_new[KC] = {}, rr[KC] = {};
+	if (live)
 	{
-		if (blockIdx.x == 0 && threadIdx.x == 0)
+		const bool vec = ld % KC == 0 && c0 % KC == 0;
+		sum_partials_n<KC, 1>(part, c0, {P_D}, nb, zr_new);
+		T bk[KC];
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+			bk[c] = (T) (zr_new[c] / st_p[c0 + c].zr);
+		GRID_STRIDE(i, m)
 		{
-			*st_next = st;
-			post_progress(host_progress, it + 1, st.k);
+			const long o = i * ld + c0;
+			T rv[KC], pv[KC];
+			load_row(rv, r + o, vec);
+			load_row(pv, p + o, vec);
+			const T ki = K[i];
+			#pragma unroll
+			for (int c = 0; c < KC; c++)
+			{
+				const T pi = rv[c] / ki + bk[c] * pv[c];
+				if (live >> c & 1)
+					pv[c] = pi;
+			}
+			store_row(p + o, pv, vec);
 		}
-		return;
 	}
-	const double zr_new = sum_partials(part, P_D, nb);
-	const T bk = (T) (zr_new / st.zr);
-	GRID_STRIDE(i, m)
-		p[i] = r[i] / K[i] + bk * p[i];
 	if (blockIdx.x == 0)
 	{
-		const double rr = sum_partials(part, P_E, nb);
+		if (live)
+			sum_partials_n<KC, 1>(part, c0, {P_E}, nb, rr);
 		if (threadIdx.x == 0)
 		{
-			SolverState nx = st;
-			nx.zr = zr_new;
-			nx.err = sqrt(rr);
-			nx.k = st.k + 1;
-			nx.done = nx.err < nx.eps;
-			*st_next = nx;
-			post_progress(host_progress, it + 1, nx.done ? nx.k : -1);
+			#pragma unroll
+			for (int c = 0; c < KC; c++)
+			{
+				SolverState nx = st_p[c0 + c];
+				if (live >> c & 1)
+				{
+					nx.zr = zr_new[c];
+					nx.err = sqrt(rr[c]);
+					nx.k = nx.k + 1;
+					nx.done = nx.err < nx.eps;
+				}
+				st_next[c0 + c] = nx;
+			}
+			if (c0 + KC == k)
+				post_columns_progress(st_next, k, it, host_progress);
 		}
 	}
 }
@@ -266,152 +531,304 @@ cg_direction_kernel(const SolverState * __restrict__ st_p, SolverState * __restr
 // ------------------------------------------------------------------------------------------------ BiCGSTAB
 
 // r0_ = r, p = r, y = p/K (bench_bicg.cpp:232-246,328-332)
-template <typename T>
+template <typename T, int KC>
 __global__ __launch_bounds__(VB) void
-bicg_init_kernel(const T * __restrict__ r, const T * __restrict__ K, T * __restrict__ r0, T * __restrict__ p, T * __restrict__ y, long m)
+bicg_init_kernel(const T * __restrict__ r, const T * __restrict__ K, T * __restrict__ r0, T * __restrict__ p, T * __restrict__ y,
+		long m, long ld, int c0)
 {
+	const bool vec = ld % KC == 0 && c0 % KC == 0;
 	GRID_STRIDE(i, m)
 	{
-		const T ri = r[i];
-		r0[i] = ri;
-		p[i] = ri;
-		y[i] = ri / K[i];
+		const long o = i * ld + c0;
+		T rv[KC], yv[KC];
+		load_row(rv, r + o, vec);
+		const T ki = K[i];
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+			yv[c] = rv[c] / ki;
+		store_row(r0 + o, rv, vec);
+		store_row(p + o, rv, vec);
+		store_row(y + o, yv, vec);
 	}
 }
 
 // partial A = r0_.v ; block 0 records the report line (bench_bicg.cpp:323)
-template <typename T>
+template <typename T, int KC>
 __global__ __launch_bounds__(VB) void
-bicg_dot_kernel(const SolverState * __restrict__ st_p, const T * __restrict__ r0, const T * __restrict__ v, long m,
-		double * __restrict__ history, long it, double * __restrict__ part)
+bicg_dot_kernel(const SolverState * __restrict__ st_p, const T * __restrict__ r0, const T * __restrict__ v, long m, long ld,
+		int c0, double * __restrict__ history, long hist_ld, long it, double * __restrict__ part)
 {
-	const SolverState st = *st_p;
-	if (history && blockIdx.x == 0 && threadIdx.x == 0)
-	{
-		history[3 * it + 0] = st.err;
-		history[3 * it + 1] = st.err_explicit;
-		history[3 * it + 2] = st.err_best;
-	}
-	double s = 0;
+	record_history<KC>(st_p, c0, ~0u, history, hist_ld, it);
+	const bool vec = ld % KC == 0 && c0 % KC == 0;
+	double s[KC] = {};
 	GRID_STRIDE(i, m)
-		s += (double) r0[i] * (double) v[i];
-	store_partial(part, P_A, s);
+	{
+		const long o = i * ld + c0;
+		T r0v[KC], vv[KC];
+		load_row(r0v, r0 + o, vec);
+		load_row(vv, v + o, vec);
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+			s[c] += (double) r0v[c] * (double) vv[c];
+	}
+	store_partials_n<KC, 1>(part, c0, {P_A}, s, ~0u);
 }
 
 // s_a = s_pk_p / (r0_.v); s = r - s_a v; z = s/K (bench_bicg.cpp:343-360)
-template <typename T>
+template <typename T, int KC>
 __global__ __launch_bounds__(VB) void
 bicg_s_kernel(const SolverState * __restrict__ st_p, const T * __restrict__ r, const T * __restrict__ v, const T * __restrict__ K,
-		T * __restrict__ s, T * __restrict__ z, long m, int nb, const double * __restrict__ part)
+		T * __restrict__ s, T * __restrict__ z, long m, long ld, int c0, int nb, const double * __restrict__ part)
 {
-	const SolverState st = *st_p;
-	const T s_a = (T) ((T) st.zr / (T) sum_partials(part, P_A, nb));
+	const bool vec = ld % KC == 0 && c0 % KC == 0;
+	double pa[KC];
+	sum_partials_n<KC, 1>(part, c0, {P_A}, nb, pa);
+	T s_a[KC];
+	#pragma unroll
+	for (int c = 0; c < KC; c++)
+		s_a[c] = (T) ((T) st_p[c0 + c].zr / (T) pa[c]);
 	GRID_STRIDE(i, m)
 	{
-		const T si = r[i] + (-s_a) * v[i];
-		s[i] = si;
-		z[i] = si / K[i];
+		const long o = i * ld + c0;
+		T rv[KC], vv[KC], sv[KC], zv[KC];
+		load_row(rv, r + o, vec);
+		load_row(vv, v + o, vec);
+		const T ki = K[i];
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+		{
+			const T si = rv[c] + (-s_a[c]) * vv[c];
+			sv[c] = si;
+			zv[c] = si / ki;
+		}
+		store_row(s + o, sv, vec);
+		store_row(z + o, zv, vec);
 	}
 }
 
 // partials B = sum (t/K)(s/K), C = sum (t/K)^2 (bench_bicg.cpp:374-391)
-template <typename T>
+template <typename T, int KC>
 __global__ __launch_bounds__(VB) void
-bicg_omega_kernel(const T * __restrict__ t, const T * __restrict__ s, const T * __restrict__ K, long m, double * __restrict__ part)
+bicg_omega_kernel(const T * __restrict__ t, const T * __restrict__ s, const T * __restrict__ K, long m, long ld, int c0,
+		double * __restrict__ part)
 {
-	double ts = 0, tt = 0;
+	const bool vec = ld % KC == 0 && c0 % KC == 0;
+	double acc[2 * KC] = {};
 	GRID_STRIDE(i, m)
 	{
+		const long o = i * ld + c0;
+		T tv[KC], sv[KC];
+		load_row(tv, t + o, vec);
+		load_row(sv, s + o, vec);
 		const T ki = K[i];
-		const T v1 = t[i] / ki;
-		const T v2 = s[i] / ki;
-		ts += (double) v1 * (double) v2;
-		tt += (double) v1 * (double) v1;
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+		{
+			const T v1 = tv[c] / ki;
+			const T v2 = sv[c] / ki;
+			acc[c] += (double) v1 * (double) v2;
+			acc[KC + c] += (double) v1 * (double) v1;
+		}
 	}
-	store_partial(part, P_B, ts);
-	store_partial(part, P_C, tt);
+	store_partials_n<KC, 2>(part, c0, {P_B, P_C}, acc, ~0u);
 }
 
 // s_w; r = s - s_w t; x = (x + s_a y) + s_w z; partials D = r0_.r, E = r.r (bench_bicg.cpp:350,394-402)
-template <typename T>
+template <typename T, int KC>
 __global__ __launch_bounds__(VB) void
 bicg_update_kernel(const SolverState * __restrict__ st_p, const T * __restrict__ s, const T * __restrict__ t, const T * __restrict__ y,
-		const T * __restrict__ z, const T * __restrict__ r0, T * __restrict__ r, T * __restrict__ x, long m, int nb,
+		const T * __restrict__ z, const T * __restrict__ r0, T * __restrict__ r, T * __restrict__ x, long m, long ld, int c0, int nb,
 		double * __restrict__ part)
 {
-	const SolverState st = *st_p;
-	const T s_a = (T) ((T) st.zr / (T) sum_partials(part, P_A, nb));
-	const T s_w = (T) ((T) sum_partials(part, P_B, nb) / (T) sum_partials(part, P_C, nb));
-	double r0r = 0, rr = 0;
+	const bool vec = ld % KC == 0 && c0 % KC == 0;
+	double q[3 * KC];
+	sum_partials_n<KC, 3>(part, c0, {P_A, P_B, P_C}, nb, q);
+	T s_a[KC], s_w[KC];
+	#pragma unroll
+	for (int c = 0; c < KC; c++)
+	{
+		s_a[c] = (T) ((T) st_p[c0 + c].zr / (T) q[c]);
+		s_w[c] = (T) ((T) q[KC + c] / (T) q[2 * KC + c]);
+	}
+	double acc[2 * KC] = {};
 	GRID_STRIDE(i, m)
 	{
-		const T ri = s[i] + (-s_w) * t[i];
-		r[i] = ri;
-		const T hi = x[i] + s_a * y[i];
-		x[i] = hi + s_w * z[i];
-		r0r += (double) r0[i] * (double) ri;
-		rr += (double) ri * (double) ri;
+		const long o = i * ld + c0;
+		T sv[KC], tv[KC], yv[KC], zv[KC], r0v[KC], rv[KC], xv[KC];
+		load_row(sv, s + o, vec);
+		load_row(tv, t + o, vec);
+		load_row(yv, y + o, vec);
+		load_row(zv, z + o, vec);
+		load_row(r0v, r0 + o, vec);
+		load_row(xv, x + o, vec);
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+		{
+			const T ri = sv[c] + (-s_w[c]) * tv[c];
+			rv[c] = ri;
+			const T hi = xv[c] + s_a[c] * yv[c];
+			xv[c] = hi + s_w[c] * zv[c];
+			acc[c] += (double) r0v[c] * (double) ri;
+			acc[KC + c] += (double) ri * (double) ri;
+		}
+		store_row(r + o, rv, vec);
+		store_row(x + o, xv, vec);
 	}
-	store_partial(part, P_D, r0r);
-	store_partial(part, P_E, rr);
+	store_partials_n<KC, 2>(part, c0, {P_D, P_E}, acc, ~0u);
 }
 
-// s_b = (s_pk/s_pk_p)(s_a/s_w); p = r + s_b (p - s_w v); y = p/K for the next iteration; block 0 writes the next state
-// (bench_bicg.cpp:402-419, 304-311, 328-332)
-template <typename T>
+// s_b = (s_pk/s_pk_p)(s_a/s_w); p = r + s_b (p - s_w v); y = p/K for the next iteration; block 0 writes the next states;
+// the last chunk posts progress (bench_bicg.cpp:402-419, 304-311, 328-332)
+template <typename T, int KC>
 __global__ __launch_bounds__(VB) void
 bicg_direction_kernel(const SolverState * __restrict__ st_p, SolverState * __restrict__ st_next, const T * __restrict__ r,
-		const T * __restrict__ v, const T * __restrict__ K, T * __restrict__ p, T * __restrict__ y, long m, int nb,
-		const double * __restrict__ part, long it, volatile long * host_progress)
+		const T * __restrict__ v, const T * __restrict__ K, T * __restrict__ p, T * __restrict__ y, long m, long ld, int c0, int k,
+		int nb, const double * __restrict__ part, long it, volatile long * host_progress)
 {
-	const SolverState st = *st_p;
-	const T s_pk_p = (T) st.zr;
-	const T s_a = (T) (s_pk_p / (T) sum_partials(part, P_A, nb));
-	const T s_w = (T) ((T) sum_partials(part, P_B, nb) / (T) sum_partials(part, P_C, nb));
-	const double s_pk_d = sum_partials(part, P_D, nb);
-	const T s_pk = (T) s_pk_d;
-	const T s_b = (s_pk / s_pk_p) * (s_a / s_w);
+	const bool vec = ld % KC == 0 && c0 % KC == 0;
+	double q[4 * KC];
+	sum_partials_n<KC, 4>(part, c0, {P_A, P_B, P_C, P_D}, nb, q);
+	T s_w[KC], s_b[KC], s_pk[KC];
+	#pragma unroll
+	for (int c = 0; c < KC; c++)
+	{
+		const T s_pk_p = (T) st_p[c0 + c].zr;
+		const T s_a = (T) (s_pk_p / (T) q[c]);
+		s_w[c] = (T) ((T) q[KC + c] / (T) q[2 * KC + c]);
+		const double s_pk_d = q[3 * KC + c];
+		s_pk[c] = (T) s_pk_d;
+		s_b[c] = (s_pk[c] / s_pk_p) * (s_a / s_w[c]);
+	}
 	GRID_STRIDE(i, m)
 	{
-		const T pi = r[i] + s_b * (p[i] - s_w * v[i]);
-		p[i] = pi;
-		y[i] = pi / K[i];
+		const long o = i * ld + c0;
+		T rv[KC], vv[KC], pv[KC], yv[KC];
+		load_row(rv, r + o, vec);
+		load_row(vv, v + o, vec);
+		load_row(pv, p + o, vec);
+		const T ki = K[i];
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+		{
+			const T pi = rv[c] + s_b[c] * (pv[c] - s_w[c] * vv[c]);
+			pv[c] = pi;
+			yv[c] = pi / ki;
+		}
+		store_row(p + o, pv, vec);
+		store_row(y + o, yv, vec);
 	}
 	if (blockIdx.x == 0)
 	{
-		const double rr = sum_partials(part, P_E, nb);
+		double rr[KC];
+		sum_partials_n<KC, 1>(part, c0, {P_E}, nb, rr);
 		if (threadIdx.x == 0)
 		{
-			SolverState nx = st;
-			nx.zr = (double) s_pk;
-			nx.err = sqrt(rr);
-			nx.k = st.k + 1;
-			*st_next = nx;
-			post_progress(host_progress, it + 1, -1);
+			#pragma unroll
+			for (int c = 0; c < KC; c++)
+			{
+				SolverState nx = st_p[c0 + c];
+				nx.zr = (double) s_pk[c];
+				nx.err = sqrt(rr[c]);
+				nx.k = nx.k + 1;
+				st_next[c0 + c] = nx;
+			}
+			if (c0 + KC == k)
+				post_progress(host_progress, it + 1, -1);
 		}
 	}
 }
 
+// Distributed solves (k = 1): the per-block partials of up to 3 slots are summed into red[], all-reduced over the ranks by the
+// caller's collective, and written back as the single partial of their slot (consumers then run with nb = 1).
+struct SlotList {
+	int n;
+	int s[3];
+};
+
+__global__ __launch_bounds__(VB) void
+reduce_slots_kernel(const double * __restrict__ part, int nb, SlotList sl, double * __restrict__ red)
+{
+	const double v = sum_partials(part, sl.s[blockIdx.x], nb);
+	if (threadIdx.x == 0)
+		red[blockIdx.x] = v;
+}
+
+__global__ void
+scatter_slots_kernel(double * __restrict__ part, SlotList sl, const double * __restrict__ red)
+{
+	if ((int) threadIdx.x < sl.n)
+		part[(long) sl.s[threadIdx.x] * MAX_PART] = red[threadIdx.x];
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 
+struct Chunk {
+	int c0, kc;
+};
+
+// k = 8s, then the binary remainder (the SpMM's column passes)
+static std::vector<Chunk>
+column_chunks(int k)
+{
+	std::vector<Chunk> out;
+	int c0 = 0;
+	for (; k - c0 >= MAX_KC; c0 += MAX_KC)
+		out.push_back({c0, MAX_KC});
+	for (int w = MAX_KC / 2; w >= 1; w /= 2)
+		if (k - c0 >= w)
+		{
+			out.push_back({c0, w});
+			c0 += w;
+		}
+	return out;
+}
+
+// f(c0, std::integral_constant<int, KC>) for every chunk, in column order; stops at the first f that returns nonzero
+template <typename F>
+static int
+for_chunks(const std::vector<Chunk> & chunks, F && f)
+{
+	for (const Chunk & ch : chunks)
+	{
+		int rc;
+		switch (ch.kc)
+		{
+		case 8: rc = f(ch.c0, std::integral_constant<int, 8>()); break;
+		case 4: rc = f(ch.c0, std::integral_constant<int, 4>()); break;
+		case 2: rc = f(ch.c0, std::integral_constant<int, 2>()); break;
+		default: rc = f(ch.c0, std::integral_constant<int, 1>()); break;
+		}
+		if (rc)
+			return rc;
+	}
+	return 0;
+}
+
+// The one solve behind all six entry points. `multi`: the _multi entries, whose matrix product is the SpMM for every k
+// (1 included) and whose messages carry `what`; the single entries (k = 1) use the SpMV and, with `dist` (row-partitioned,
+// k = 1 only), the caller's callbacks.
 template <typename T>
 static int
-solve(int method, spmv_mi355x_matrix * A, const spmv_mi355x_dist_ops * dist, long m_arg, const int32_t * row_ptr, const int32_t * col,
-		const double * val, const void * b_host, void * x_host, long max_iterations, double * history_host,
-		spmv_mi355x_solver_info * info)
+solve(const char * what, bool multi, int method, spmv_mi355x_matrix * A, const spmv_mi355x_dist_ops * dist, int k, long m_arg,
+		const int32_t * row_ptr, const int32_t * col, const double * val, const void * b_host, void * x_host, long max_iterations,
+		double * history_host, spmv_mi355x_solver_info * info)
 {
 	const auto t_start = std::chrono::steady_clock::now();
 	const long m = dist ? m_arg : spmv_mi355x_rows(A);
+	const long ld = k;
 	hipStream_t stream = nullptr;
 	ProgressGate gate;                // outlives buf, whose hipFree waits for the kernels that post to it
 	DeviceBuffers buf;
-	const size_t vb = (size_t) m * sizeof(T);
+	const size_t vb = (size_t) m * k * sizeof(T);
 
 	std::vector<T> K_host((size_t) std::max<long>(m, 1));
 	const long bad = jacobi_diagonal<T>(row_ptr, col, val, m, dist ? dist->row_offset : 0, K_host.data());
 	if (bad >= 0)
 	{
-		set_error("bad K, zero in diagonal (row %ld)", bad);
+		if (multi)
+			set_error("%s: bad K, zero in diagonal (row %ld)", what, bad);
+		else
+			set_error("bad K, zero in diagonal (row %ld)", bad);
 		return 1;
 	}
 
@@ -421,32 +838,37 @@ solve(int method, spmv_mi355x_matrix * A, const spmv_mi355x_dist_ops * dist, lon
 	// driver clearing 160 GiB for seconds afterwards — more than a solve of a few hundred iterations takes (measured: 0.27 instead of
 	// 0.24 ms per CG iteration on the 160^3 stencil right after it). A caller who solves many systems with one handle can hand in
 	// vectors from spmv_mi355x_output_alloc through the device-pointer entry points instead.
-	for (T ** q : {&b, &K, &x, &x_best, &r, &r_explicit, &p, &Ap})
+	for (T ** q : {&b, &x, &x_best, &r, &r_explicit, &p, &Ap})
 		ABI_TRY(buf.alloc(q, vb));
+	ABI_TRY(buf.alloc(&K, (size_t) m * sizeof(T)));
 	if (method == 1)
 		for (T ** q : {&r0, &y, &z, &s, &v})
 			ABI_TRY(buf.alloc(q, vb));
 	double * part, * history = nullptr;
 	SolverState * st;
-	ABI_TRY(buf.alloc(&part, sizeof(double) * NUM_SLOTS * MAX_PART));
-	ABI_TRY(buf.alloc(&st, 2 * sizeof(SolverState)));
+	const size_t part_bytes = sizeof(double) * (size_t) k * NUM_SLOTS * MAX_PART;
+	ABI_TRY(buf.alloc(&part, part_bytes));
+	ABI_TRY(buf.alloc(&st, 2 * (size_t) k * sizeof(SolverState)));
+	const long hist_ld = 3 * max_iterations;
 	if (history_host && max_iterations > 0)
 	{
-		ABI_TRY(buf.alloc(&history, sizeof(double) * 3 * (size_t) max_iterations));
-		HIP_TRY(hipMemsetAsync(history, 0, sizeof(double) * 3 * (size_t) max_iterations, stream));
+		ABI_TRY(buf.alloc(&history, sizeof(double) * (size_t) k * hist_ld));
+		HIP_TRY(hipMemsetAsync(history, 0, sizeof(double) * (size_t) k * hist_ld, stream));
 	}
 	ABI_TRY(gate.init());
 
 	HIP_TRY(hipMemcpyAsync(b, b_host, vb, hipMemcpyHostToDevice, stream));
-	HIP_TRY(hipMemcpyAsync(K, K_host.data(), vb, hipMemcpyHostToDevice, stream));
+	HIP_TRY(hipMemcpyAsync(K, K_host.data(), (size_t) m * sizeof(T), hipMemcpyHostToDevice, stream));
 	HIP_TRY(hipMemsetAsync(x, 0, vb, stream));                    // x0 = 0 (bench_cg.cpp:139-145)
 	HIP_TRY(hipMemsetAsync(x_best, 0, vb, stream));
-	HIP_TRY(hipMemsetAsync(part, 0, sizeof(double) * NUM_SLOTS * MAX_PART, stream));
+	HIP_TRY(hipMemsetAsync(part, 0, part_bytes, stream));
 
+	// one launch shape for every k: the same rows per (block, thread), hence the same additions per column
 	const int nb = solver_blocks(m);
-	const dim3 grid(nb), block(VB), one(1);
+	const dim3 grid(nb), block(VB), per_col(k);
+	const std::vector<Chunk> chunks = column_chunks(k);
 	long spmv_calls = 0;
-	auto spmv = [&](const T * in, T * out) {
+	auto product = [&](const T * in, T * out) {
 		spmv_calls++;
 		if (dist)
 		{
@@ -457,10 +879,13 @@ solve(int method, spmv_mi355x_matrix * A, const spmv_mi355x_dist_ops * dist, lon
 			}
 			return 0;
 		}
+		if (multi)
+			return spmv_mi355x_spmm_device_async(A, k, in, ld, out, ld, 0, stream);
 		return spmv_mi355x_spmv_device_async(A, in, out, 0, stream);
 	};
-	// single GPU: consumers re-reduce the nb per-block partials themselves. Distributed: the listed slots are reduced,
-	// summed over the ranks by the caller's collective and put back as ONE partial; consumers then read nbc = 1 partial.
+	// single GPU: consumers re-reduce the nb per-block partials themselves. Distributed (k = 1, so column 0's slot s starts at
+	// s * MAX_PART): the listed slots are reduced, summed over the ranks by the caller's collective and put back as ONE partial;
+	// consumers then read nbc = 1 partial.
 	const int nbc = dist ? 1 : nb;
 	auto global_reduce = [&](SlotList sl) {
 		if (!dist)
@@ -471,26 +896,44 @@ solve(int method, spmv_mi355x_matrix * A, const spmv_mi355x_dist_ops * dist, lon
 			set_error("solver: the caller's all-reduce callback failed");
 			return 1;
 		}
-		hipLaunchKernelGGL(scatter_slots_kernel, one, dim3(WAVE), 0, stream, part, sl, dist->reduce_buf_dev);
+		hipLaunchKernelGGL(scatter_slots_kernel, dim3(1), dim3(WAVE), 0, stream, part, sl, dist->reduce_buf_dev);
 		return 0;
 	};
-	// |b - A x|^2 into partial A, r_explicit = b - A x
+	// |b - A x|^2 into partial A of every column, r_explicit = b - A x
 	auto explicit_residual = [&](const T * xx) {
-		if (spmv(xx, Ap))
+		if (product(xx, Ap))
 			return 1;
-		hipLaunchKernelGGL((residual_kernel<T>), grid, block, 0, stream, b, Ap, r_explicit, m, part);
+		for_chunks(chunks, [&](int c0, auto kc) {
+			hipLaunchKernelGGL((residual_kernel<T, decltype(kc)::value>), grid, block, 0, stream, b, Ap, r_explicit, m, ld, c0, part);
+			return 0;
+		});
 		return global_reduce({1, {P_A, 0, 0}});
+	};
+	auto explicit_step = [&](SolverState * cur, int allow_restart, int ignore_done) {
+		for_chunks(chunks, [&](int c0, auto kc) {
+			hipLaunchKernelGGL((explicit_kernel<T, decltype(kc)::value>), grid, block, 0, stream, cur, x, x_best, r_explicit, r, p, K, m, ld,
+					c0, nbc, allow_restart, ignore_done, part);
+			return 0;
+		});
+		if (allow_restart && global_reduce({1, {P_C, 0, 0}}))         // z.r of a restart (stale and unread otherwise)
+			return 1;
+		hipLaunchKernelGGL(explicit_fin_kernel, per_col, block, 0, stream, cur, nbc, allow_restart, ignore_done, part);
+		return 0;
 	};
 
 	// r0 = b - A x0
-	ABI_TRY(spmv(x, Ap));
-	hipLaunchKernelGGL((residual_kernel<T>), grid, block, 0, stream, b, Ap, r, m, part);
-	if (method == 0)
-		hipLaunchKernelGGL((cg_init_kernel<T>), grid, block, 0, stream, r, K, p, m, part);
-	else
-		hipLaunchKernelGGL((bicg_init_kernel<T>), grid, block, 0, stream, r, K, r0, p, y, m);
+	ABI_TRY(product(x, Ap));
+	for_chunks(chunks, [&](int c0, auto kc) {
+		constexpr int KC = decltype(kc)::value;
+		hipLaunchKernelGGL((residual_kernel<T, KC>), grid, block, 0, stream, b, Ap, r, m, ld, c0, part);
+		if (method == 0)
+			hipLaunchKernelGGL((cg_init_kernel<T, KC>), grid, block, 0, stream, r, K, p, m, ld, c0, part);
+		else
+			hipLaunchKernelGGL((bicg_init_kernel<T, KC>), grid, block, 0, stream, r, K, r0, p, y, m, ld, c0);
+		return 0;
+	});
 	ABI_TRY(global_reduce({3, {P_A, P_B, P_C}}));
-	hipLaunchKernelGGL(init_state_kernel, one, block, 0, stream, st, nbc, method, part);
+	hipLaunchKernelGGL(init_state_kernel, per_col, block, 0, stream, st, k, nbc, method, part);
 	HIP_TRY(hipGetLastError());
 
 	const bool debug = getenv("SPMV_MI355X_SOLVER_DEBUG") != nullptr;
@@ -499,41 +942,64 @@ solve(int method, spmv_mi355x_matrix * A, const spmv_mi355x_dist_ops * dist, lon
 	for (; it < max_iterations; it++)
 	{
 		bool stop;
-		ABI_TRY(gate.wait(it, "solver", stream, &stop));
+		ABI_TRY(gate.wait(it, what, stream, &stop));
 		if (stop)
 			break;
-		SolverState * cur = st + (it & 1), * nxt = st + ((it + 1) & 1);
+		SolverState * cur = st + (it & 1) * k, * nxt = st + ((it + 1) & 1) * k;
 		if (it > 0 && it % RESTART_K == 0)
 		{
 			ABI_TRY(explicit_residual(x));
-			hipLaunchKernelGGL((explicit_kernel<T>), grid, block, 0, stream, cur, x, x_best, r_explicit, r, p, K, m, nbc,
-					method == 0, 0, part);
-			if (method == 0)
-				ABI_TRY(global_reduce({1, {P_C, 0, 0}}));             // z.r of a restart (stale and unread otherwise)
-			hipLaunchKernelGGL(explicit_fin_kernel, one, block, 0, stream, cur, nbc, method == 0, 0, part);
+			ABI_TRY(explicit_step(cur, method == 0, 0));
 		}
 		if (method == 0)
 		{
-			ABI_TRY(spmv(p, Ap));
-			hipLaunchKernelGGL((cg_dot_kernel<T>), grid, block, 0, stream, cur, p, Ap, m, history, it, part);
+			ABI_TRY(product(p, Ap));
+			for_chunks(chunks, [&](int c0, auto kc) {
+				hipLaunchKernelGGL((cg_dot_kernel<T, decltype(kc)::value>), grid, block, 0, stream, cur, p, Ap, m, ld, c0, history, hist_ld,
+						it, part);
+				return 0;
+			});
 			ABI_TRY(global_reduce({1, {P_A, 0, 0}}));
-			hipLaunchKernelGGL((cg_update_kernel<T>), grid, block, 0, stream, cur, x, r, p, Ap, K, m, nbc, part);
+			for_chunks(chunks, [&](int c0, auto kc) {
+				hipLaunchKernelGGL((cg_update_kernel<T, decltype(kc)::value>), grid, block, 0, stream, cur, x, r, p, Ap, K, m, ld, c0, nbc,
+						part);
+				return 0;
+			});
 			ABI_TRY(global_reduce({2, {P_D, P_E, 0}}));
-			hipLaunchKernelGGL((cg_direction_kernel<T>), grid, block, 0, stream, cur, nxt, r, p, K, m, nbc, part, it, gate.dev);
+			for_chunks(chunks, [&](int c0, auto kc) {
+				hipLaunchKernelGGL((cg_direction_kernel<T, decltype(kc)::value>), grid, block, 0, stream, cur, nxt, r, p, K, m, ld, c0, k,
+						nbc, part, it, gate.dev);
+				return 0;
+			});
 		}
 		else
 		{
-			ABI_TRY(spmv(y, v));
-			hipLaunchKernelGGL((bicg_dot_kernel<T>), grid, block, 0, stream, cur, r0, v, m, history, it, part);
-			ABI_TRY(global_reduce({1, {P_A, 0, 0}}));
-			hipLaunchKernelGGL((bicg_s_kernel<T>), grid, block, 0, stream, cur, r, v, K, s, z, m, nbc, part);
-			ABI_TRY(spmv(z, Ap));                                // t = A z
-			hipLaunchKernelGGL((bicg_omega_kernel<T>), grid, block, 0, stream, Ap, s, K, m, part);
-			ABI_TRY(global_reduce({2, {P_B, P_C, 0}}));
-			hipLaunchKernelGGL((bicg_update_kernel<T>), grid, block, 0, stream, cur, s, Ap, y, z, r0, r, x, m, nbc, part);
+			// dot and s, omega and update stay paired per chunk; a distributed solve has one chunk (k = 1), so the global_reduce
+			// between them still follows the whole kernel
+			ABI_TRY(product(y, v));
+			ABI_TRY(for_chunks(chunks, [&](int c0, auto kc) {
+				constexpr int KC = decltype(kc)::value;
+				hipLaunchKernelGGL((bicg_dot_kernel<T, KC>), grid, block, 0, stream, cur, r0, v, m, ld, c0, history, hist_ld, it, part);
+				if (global_reduce({1, {P_A, 0, 0}}))
+					return 1;
+				hipLaunchKernelGGL((bicg_s_kernel<T, KC>), grid, block, 0, stream, cur, r, v, K, s, z, m, ld, c0, nbc, part);
+				return 0;
+			}));
+			ABI_TRY(product(z, Ap));                             // t = A z
+			ABI_TRY(for_chunks(chunks, [&](int c0, auto kc) {
+				constexpr int KC = decltype(kc)::value;
+				hipLaunchKernelGGL((bicg_omega_kernel<T, KC>), grid, block, 0, stream, Ap, s, K, m, ld, c0, part);
+				if (global_reduce({2, {P_B, P_C, 0}}))
+					return 1;
+				hipLaunchKernelGGL((bicg_update_kernel<T, KC>), grid, block, 0, stream, cur, s, Ap, y, z, r0, r, x, m, ld, c0, nbc, part);
+				return 0;
+			}));
 			ABI_TRY(global_reduce({2, {P_D, P_E, 0}}));
-			hipLaunchKernelGGL((bicg_direction_kernel<T>), grid, block, 0, stream, cur, nxt, r, v, K, p, y, m, nbc, part, it,
-					gate.dev);
+			for_chunks(chunks, [&](int c0, auto kc) {
+				hipLaunchKernelGGL((bicg_direction_kernel<T, decltype(kc)::value>), grid, block, 0, stream, cur, nxt, r, v, K, p, y, m, ld,
+						c0, k, nbc, part, it, gate.dev);
+				return 0;
+			});
 		}
 	}
 	HIP_TRY(hipGetLastError());
@@ -542,44 +1008,50 @@ solve(int method, spmv_mi355x_matrix * A, const spmv_mi355x_dist_ops * dist, lon
 	{
 		HIP_TRY(hipStreamSynchronize(stream));
 		const auto t_sync = std::chrono::steady_clock::now();
-		fprintf(stderr, "[solver] setup %.3f ms, enqueue loop %.3f ms (spin %.3f ms), drain %.3f ms, %ld iterations launched\n",
+		fprintf(stderr, "[%s k %d] setup %.3f ms, enqueue loop %.3f ms (spin %.3f ms), drain %.3f ms, %ld iterations launched\n", what, k,
 				std::chrono::duration<double>(t_loop - t_start).count() * 1e3,
 				std::chrono::duration<double>(t_loop_end - t_loop).count() * 1e3, gate.spin_seconds * 1e3,
 				std::chrono::duration<double>(t_sync - t_loop_end).count() * 1e3, it);
 	}
 
 	// final explicit residual of x, promotion of x_best (bench_cg.cpp:288-306); runs after a break too
-	SolverState * fin = st + (it & 1);
+	SolverState * fin = st + (it & 1) * k;
 	ABI_TRY(explicit_residual(x));
-	hipLaunchKernelGGL((explicit_kernel<T>), grid, block, 0, stream, fin, x, x_best, r_explicit, r, p, K, m, nbc, 0, 1, part);
-	hipLaunchKernelGGL(explicit_fin_kernel, one, block, 0, stream, fin, nbc, 0, 1, part);
+	ABI_TRY(explicit_step(fin, 0, 1));
 	// the harness's own check of the returned vector: error = |b - A x_best| (bench_cg.cpp:412-418)
 	ABI_TRY(explicit_residual(x_best));
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipMemcpyAsync(x_host, x_best, vb, hipMemcpyDeviceToHost, stream));
-	SolverState st_host;
-	std::vector<double> part_host((size_t) nbc);
-	HIP_TRY(hipMemcpyAsync(&st_host, fin, sizeof(SolverState), hipMemcpyDeviceToHost, stream));
-	HIP_TRY(hipMemcpyAsync(part_host.data(), part + (long) P_A * MAX_PART, sizeof(double) * nbc, hipMemcpyDeviceToHost, stream));
+	std::vector<SolverState> st_host((size_t) k);
+	std::vector<double> part_host((size_t) k * NUM_SLOTS * MAX_PART);
+	HIP_TRY(hipMemcpyAsync(st_host.data(), fin, sizeof(SolverState) * k, hipMemcpyDeviceToHost, stream));
+	HIP_TRY(hipMemcpyAsync(part_host.data(), part, part_bytes, hipMemcpyDeviceToHost, stream));
 	if (history)
-		HIP_TRY(hipMemcpyAsync(history_host, history, sizeof(double) * 3 * (size_t) max_iterations, hipMemcpyDeviceToHost, stream));
+		HIP_TRY(hipMemcpyAsync(history_host, history, sizeof(double) * (size_t) k * hist_ld, hipMemcpyDeviceToHost, stream));
 	HIP_TRY(hipStreamSynchronize(stream));
 	if (info)
 	{
-		spmv_mi355x_solver_info out;
-		memset(&out, 0, sizeof(out));
-		out.iterations = st_host.k;
-		out.error = std::sqrt(host_sum(part_host.data(), 0, nbc));
-		out.error_best = st_host.err_best;
-		out.eps = st_host.eps;
-		out.eps_counter = st_host.eps_counter;
-		out.restarts = st_host.restarts;
-		out.spmv_calls = spmv_calls - 1;                          // the last one is the harness's check, not the solver's
-		out.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
+		// info[0].struct_size is the caller's stride; every element is written with that size
+		const unsigned want = info->struct_size;
+		const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
 		if (debug)
-			fprintf(stderr, "[solver] tail (final residuals, downloads) %.3f ms, total %.3f ms\n",
-					std::chrono::duration<double>(std::chrono::steady_clock::now() - t_loop_end).count() * 1e3, out.seconds * 1e3);
-		put_info(info, info->struct_size, out);
+			fprintf(stderr, "[%s k %d] tail (final residuals, downloads) %.3f ms, total %.3f ms\n", what, k,
+					std::chrono::duration<double>(std::chrono::steady_clock::now() - t_loop_end).count() * 1e3, seconds * 1e3);
+		for (int c = 0; c < k; c++)
+		{
+			spmv_mi355x_solver_info out;
+			memset(&out, 0, sizeof(out));
+			const SolverState & sc = st_host[c];
+			out.iterations = sc.k;
+			out.error = std::sqrt(host_sum(part_host.data(), part_at(c, P_A), nbc));
+			out.error_best = sc.err_best;
+			out.eps = sc.eps;
+			out.eps_counter = sc.eps_counter;
+			out.restarts = sc.restarts;
+			out.spmv_calls = spmv_calls - 1;                      // the last one is the harness's check, not the solver's
+			out.seconds = seconds;
+			put_info((char *) info + (size_t) c * want, want, out);
+		}
 	}
 	return 0;
 }
@@ -612,8 +1084,8 @@ solve_entry(int method, spmv_mi355x_matrix * A, const int32_t * row_ptr, const i
 	}
 	HIP_TRY(hipSetDevice(spmv_mi355x_device(A)));
 	if (spmv_mi355x_precision(A) == SPMV_MI355X_F32)
-		return solve<float>(method, A, nullptr, 0, row_ptr, col, val, b_host, x_host, max_iterations, history_host, info);
-	return solve<double>(method, A, nullptr, 0, row_ptr, col, val, b_host, x_host, max_iterations, history_host, info);
+		return solve<float>("solver", false, method, A, nullptr, 1, 0, row_ptr, col, val, b_host, x_host, max_iterations, history_host, info);
+	return solve<double>("solver", false, method, A, nullptr, 1, 0, row_ptr, col, val, b_host, x_host, max_iterations, history_host, info);
 }
 
 static int
@@ -634,11 +1106,52 @@ solve_dist_entry(int method, const spmv_mi355x_dist_ops * ops, int precision, lo
 	if (!info_size_ok("solver", info))
 		return 1;
 	if (precision == SPMV_MI355X_F32)
-		return solve<float>(method, nullptr, ops, m_local, row_ptr, col, val, b_host, x_host, max_iterations, history_host, info);
+		return solve<float>("solver", false, method, nullptr, ops, 1, m_local, row_ptr, col, val, b_host, x_host, max_iterations,
+				history_host, info);
 	if (precision == SPMV_MI355X_F64)
-		return solve<double>(method, nullptr, ops, m_local, row_ptr, col, val, b_host, x_host, max_iterations, history_host, info);
+		return solve<double>("solver", false, method, nullptr, ops, 1, m_local, row_ptr, col, val, b_host, x_host, max_iterations,
+				history_host, info);
 	set_error("unknown precision %d", precision);
 	return 1;
+}
+
+static int
+solve_multi_entry(const char * what, int method, spmv_mi355x_matrix * A, int k, const int32_t * row_ptr, const int32_t * col,
+		const double * val, const void * b_host, void * x_host, long max_iterations, double * history_host,
+		spmv_mi355x_solver_info * info)
+{
+	// every argument check comes before the device is touched
+	if (k < 1)
+	{
+		set_error("%s: k must be >= 1 (got %d)", what, k);
+		return 1;
+	}
+	if (!info_size_ok(what, info))
+		return 1;
+	if (!A || !row_ptr || !b_host || !x_host)
+	{
+		set_error("%s: NULL argument", what);
+		return 1;
+	}
+	if (spmv_mi355x_rows(A) != spmv_mi355x_cols(A))
+	{
+		set_error("%s: the matrix must be square", what);
+		return 1;
+	}
+	if (max_iterations < 0)
+	{
+		set_error("%s: max_iterations < 0", what);
+		return 1;
+	}
+	if (spmv_mi355x_nnz(A) > 0 && (!col || !val))
+	{
+		set_error("%s: NULL CSR arrays", what);
+		return 1;
+	}
+	HIP_TRY(hipSetDevice(spmv_mi355x_device(A)));
+	if (spmv_mi355x_precision(A) == SPMV_MI355X_F32)
+		return solve<float>(what, true, method, A, nullptr, k, 0, row_ptr, col, val, b_host, x_host, max_iterations, history_host, info);
+	return solve<double>(what, true, method, A, nullptr, k, 0, row_ptr, col, val, b_host, x_host, max_iterations, history_host, info);
 }
 
 }  // namespace spmv
@@ -675,6 +1188,22 @@ spmv_mi355x_pbicgstab(spmv_mi355x_matrix * A, const int32_t * row_ptr, const int
 		const void * b_host, void * x_host, long max_iterations, double * history_out, spmv_mi355x_solver_info * info)
 {
 	return spmv::solve_entry(1, A, row_ptr, col_idx, values_fp64, b_host, x_host, max_iterations, history_out, info);
+}
+
+int
+spmv_mi355x_pcg_multi(spmv_mi355x_matrix * A, int k, const int32_t * row_ptr, const int32_t * col_idx, const double * values_fp64,
+		const void * B_host, void * X_res_out_host, long max_iterations, double * history_out, spmv_mi355x_solver_info * info)
+{
+	return spmv::solve_multi_entry("pcg_multi", 0, A, k, row_ptr, col_idx, values_fp64, B_host, X_res_out_host, max_iterations,
+			history_out, info);
+}
+
+int
+spmv_mi355x_pbicgstab_multi(spmv_mi355x_matrix * A, int k, const int32_t * row_ptr, const int32_t * col_idx, const double * values_fp64,
+		const void * B_host, void * X_res_out_host, long max_iterations, double * history_out, spmv_mi355x_solver_info * info)
+{
+	return spmv::solve_multi_entry("pbicgstab_multi", 1, A, k, row_ptr, col_idx, values_fp64, B_host, X_res_out_host, max_iterations,
+			history_out, info);
 }
 
 }

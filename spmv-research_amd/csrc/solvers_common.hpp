@@ -1,4 +1,4 @@
-// What the Krylov solvers (solvers.hip, solvers_multi.hip, solver_cgls.hip, solver_minres.hip) share. Device side: the launch
+// What the Krylov solvers (solvers.hip, solver_cgls.hip, solver_minres.hip, solver_gmres.hip) share. Device side: the launch
 // shape of the vector kernels, the device state, the deterministic two-stage dot products, the post to the host progress word, the
 // explicit-residual decision. Host side: the device buffer owner, the Jacobi diagonal, and the run-ahead driver of every solve loop
 // (solver_blocks, ProgressGate, info_size_ok / put_info, host_sum).

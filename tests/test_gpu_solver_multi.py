@@ -2,8 +2,10 @@
 
 The contract is exact: on a handle whose SpMV is deterministic, column j of a multi-RHS solve returns bit for bit what the
 single-RHS solver returns for b_j on the same handle (x, history, iterations, error, error_best, eps, eps_counter,
-restarts). Other layouts are compared with the oracle to the tolerances of test_solvers.py. The systems are those of
-test_solvers.py.
+restarts). Both run the same kernels (csrc/solvers.hip), so what the comparison checks is a column inside a chunk of
+KC in {8, 4, 2} columns against the same column alone in the KC = 1 instantiation, and the SpMM against the SpMV. The
+independent reference is the oracle: test_solvers.py compares the single solvers with it, and here the other layouts are
+compared with it to the tolerances of test_solvers.py. The systems are those of test_solvers.py.
 """
 import numpy as np
 import pytest

@@ -583,7 +583,8 @@ int  spmv_mi355x_gmres(spmv_mi355x_matrix * A, const void * b_host, void * x_out
 
 /* ---- sparse triangular solve: level-scheduled L x = b and U x = b handles --------------------------------------------------------- */
 /* What applies Gauss-Seidel / SSOR (A's own triangles) and ILU(0) / IC(0) (the caller's factors): T x = b for one triangle T of a
- * square n x n matrix given as CSR (csrc/trsv.hip, csrc/kernels_trsv.hip). The primitive only: no solver calls it yet.
+ * square n x n matrix given as CSR (csrc/trsv.hip, csrc/kernels_trsv.hip). spmv_mi355x_gmres_tri (below) is the one
+ * solver that calls it.
  * WHICH TRIANGLE. uplo = SPMV_MI355X_LOWER keeps the entries with column <= row, SPMV_MI355X_UPPER those with column >= row; entries
  * on the other side are ignored, so one CSR array holding both ILU factors (unit L below, U on and above the diagonal) serves two
  * handles, and the CSR of A serves both halves of a Gauss-Seidel sweep. diag = SPMV_MI355X_DIAG_STORED reads d_i from row i;
@@ -627,7 +628,7 @@ int  spmv_mi355x_gmres(spmv_mi355x_matrix * A, const void * b_host, void * x_out
  *     trsv_analyze makes the checks 1 to 3 that apply to its arguments. The solve entries refuse a NULL handle and, for n > 0, a NULL
  *     vector; trsv_info a NULL handle; trsv_mem_footprint(NULL) is 0; trsv_destroy(NULL) is rc 0.
  *   - NOT CHECKABLE: that b_dev / x_dev hold n values on the right device.
- *   - NOT BUILT: wiring into the solvers (SGS / ILU preconditioning of pcg / gmres); the ILU(0) / IC(0) factorization itself; a solve
+ *   - NOT BUILT: wiring into pcg / pbicgstab / minres (gmres has it: spmv_mi355x_gmres_tri); the ILU(0) / IC(0) factorization itself; a solve
  *     with T^t over T's layout; multi-RHS; update_values for a trsv handle; GPU-side analysis; graph capture; a row-partitioned form;
  *     a "sync-free" variant in which workgroups wait for each other inside one launch. */
 typedef struct spmv_mi355x_trsv spmv_mi355x_trsv;   /* opaque */
@@ -645,6 +646,67 @@ int  spmv_mi355x_trsv_info(const spmv_mi355x_trsv * T, long * n_out, long * nnz_
 		long * max_level_rows_out, int * chain_rows_out);                                      /* any pointer may be NULL */
 double spmv_mi355x_trsv_mem_footprint(const spmv_mi355x_trsv * T);
 int  spmv_mi355x_time_trsv_device(spmv_mi355x_trsv * T, const void * b_dev, void * x_dev, int iters, void * hip_stream, double * ms_per_iter_out);
+
+/* THE BLOCKED FORM: the block-Jacobi variant of the same solve, ONE launch per solve. The global plan above is
+ * launch-bound (hundreds to thousands of launches, or one workgroup walking thousands of levels through global memory). Here the
+ * rows are cut into contiguous blocks of B = block_rows rows, block b owning the rows [b B, min(n, (b + 1) B)) whatever uplo is, and
+ * an entry (i, j, a) is kept when the rule above keeps it (LOWER: j < i, UPPER: j > i) AND floor(j / B) == floor(i / B). Every other
+ * off-diagonal entry is ignored, exactly as the other triangle is. The diagonal rule (STORED / UNIT, the first stored entry with
+ * column i, its checks and messages), the narrowing of the values and the per-row arithmetic are those of the global handle, so x is
+ * bit for bit what tests/trsv_reference.c returns for the CSR with the dropped entries removed, and with B >= n, where nothing is
+ * dropped, bit for bit what the global handle returns. What is lost is the dropped couplings: as a preconditioner the blocked
+ * handle is weaker than the global one and far cheaper to apply.
+ * No row depends on a row of another block, so one workgroup solves each block with the block's own level schedule (the level rule
+ * above over the kept entries) and all blocks run in one launch; the block's part of x lives in LDS, which is why B is capped. No
+ * workgroup reads what another one writes: nothing waits for anything, nothing can hang.
+ *   - block_rows: 1 .. 16384 (16384 fp64 values = 128 KiB of the 160 KiB of LDS a workgroup may declare; the same cap for fp32),
+ *     0 = the default (4096, NOT yet from a sweep: profiles/r18_trsv_blocked.txt).
+ *   - trsv_analyze_blocked: level_of_row_out receives the level of each row WITHIN its block; blocks = ceil(n / B);
+ *     max_block_levels = the most levels of any block; max_level_rows = the widest level of any block; nnz_dropped = the off-diagonal
+ *     entries of the chosen triangle that cross a block boundary; block_rows_used = B. Any out pointer may be NULL.
+ *   - trsv_solve_device_async, trsv_solve, time_trsv_device, trsv_mem_footprint and trsv_destroy serve a blocked handle unchanged.
+ *     trsv_info returns n, nnz_kept = the kept in-block entries (+ n under STORED), levels = max_block_levels, launches = 1 (0 when
+ *     n == 0), max_level_rows as above, chain_rows = 0. trsv_block_info on a global handle gives block_rows 0, blocks 0, levels 0,
+ *     dropped 0.
+ *   - Stored: the layout of the global handle with the positions ordered by (block, level within the block, row), the first level
+ *     of every block, and the columns block-local in 32 bits: 12 (fp64) / 8 (fp32) bytes per kept entry plus the slices' padding.
+ *   - rc 1 in trsv_create's order and with its messages, the prefixes being trsv_create_blocked / trsv_analyze_blocked; block_rows
+ *     takes the place of chain_rows in step 1: "block_rows must be 0 (the default) or 1 .. 16384 (got N)".
+ *   - NOT BUILT: overlapping blocks, a reordering that would shrink what is dropped, 16-bit columns. */
+int  spmv_mi355x_trsv_analyze_blocked(int uplo, long n, const int32_t * row_ptr, const int32_t * col_idx, long block_rows /* 0 = default */,
+		int32_t ** level_of_row_out /* level WITHIN the row's block; malloc'ed, spmv_mi355x_free; may be NULL */,
+		long * blocks_out, long * max_block_levels_out, long * max_level_rows_out, long * nnz_dropped_out, long * block_rows_used_out);
+int  spmv_mi355x_trsv_create_blocked(spmv_mi355x_trsv ** out, int uplo, int diag, int precision, long n,
+		const int32_t * row_ptr, const int32_t * col_idx, const double * values_fp64, long block_rows, int device /* -1 = current */);
+int  spmv_mi355x_trsv_block_info(const spmv_mi355x_trsv * T, long * block_rows_out, long * blocks_out, long * max_block_levels_out,
+		long * nnz_dropped_out);                                                               /* any out pointer may be NULL */
+
+/* ---- GMRES(m) right-preconditioned by triangular solves ------------------------------------------------------------------------ */
+/* spmv_mi355x_gmres with M^-1 v = second^-1 ( scale o ( first^-1 v ) ) for "M v" (csrc/solver_gmres.hip): each of
+ * the three parts may be NULL, the two solves are spmv_mi355x_trsv handles of any kind, blocked or global, and scale is a vector.
+ * The recurrences, the stop codes, the freeze, history and info are exactly those of spmv_mi355x_gmres. Two ways to fill it:
+ *     SGS of A:               first = LOWER / STORED handle of A's CSR, scale = diag(A), second = UPPER / STORED handle of A's CSR
+ *     the caller's ILU(0):    first = LOWER / UNIT, second = UPPER / STORED, no scale
+ *   - per inner step: the launches of the two solves and one scale kernel on top of spmv_mi355x_gmres's; one scratch vector.
+ *   - scale_host: rows() values of the handle's precision. M = (NULL, s, NULL) with s > 0 returns bit for bit what
+ *     spmv_mi355x_gmres returns with minv = s.
+ *   - the handles are used, not owned: they must outlive the call, and one handle serves one solve at a time.
+ *   - rc 1 with a last_error that names gmres_tri, caller buffers and info untouched: first the checks of spmv_mi355x_gmres in its
+ *     order (info->struct_size, restart, tol, max_iterations; NULL A, b or x_out; rows() != cols()), then
+ *     1. M is NULL or M->struct_size < sizeof(spmv_mi355x_tri_precond);
+ *     2. first, scale_host and second are all NULL (the message points to spmv_mi355x_gmres);
+ *     3. a handle's n differs from rows(), or its precision or its device from A's (first before second);
+ *     4. a scale entry that is not finite or is zero (the message names the first such index).
+ *   - NOT BUILT: the same for pcg / pbicgstab / minres, left preconditioning, a preconditioner that changes between steps. */
+typedef struct {
+	unsigned struct_size;         /* in: sizeof(spmv_mi355x_tri_precond) */
+	spmv_mi355x_trsv * first;     /* may be NULL */
+	const void * scale_host;      /* may be NULL: rows() values of the handle's precision, finite and non-zero */
+	spmv_mi355x_trsv * second;    /* may be NULL */
+} spmv_mi355x_tri_precond;
+int  spmv_mi355x_gmres_tri(spmv_mi355x_matrix * A, const void * b_host, void * x_out_host, int restart,
+		const spmv_mi355x_tri_precond * M, double tol, long max_iterations,
+		double * history_out /* may be NULL: max_iterations doubles */, spmv_mi355x_gmres_info * info /* may be NULL */);
 
 /* Row-partitioned (multi-GPU) form of the same two solvers: one process per GPU owns the row block [row_offset,
  * row_offset + m_local) of A, b and x. The solver keeps every vector device-resident and local; the two things that cross

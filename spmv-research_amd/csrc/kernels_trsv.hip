@@ -1,4 +1,4 @@
-// The two kernels of the sparse triangular solve T x = b over the level-sliced layout of trsv.hpp. One lane owns one row:
+// The three kernels of the sparse triangular solve T x = b over the level-sliced layout of trsv.hpp. One lane owns one row:
 //   s = b[i];  for each kept off-diagonal entry (i, j, a) in stored order: s = fma(-a, x[j], s);  x[i] = s / d_i  (or s under UNIT)
 // in the handle's precision, with an IEEE division. A row's result depends on its own entry order only, never on which lane,
 // workgroup or launch computes it, so every plan gives the bits of the sequential loop (tests/trsv_reference.c).
@@ -6,9 +6,11 @@
 // trsv_level_kernel: one level, one lane per row, any number of workgroups. Every x[j] it reads belongs to an earlier level and was
 // written by an earlier launch on the same stream: the launch boundary is the only ordering between workgroups anywhere in this file.
 // trsv_chain_kernel: a run of consecutive thin levels in ONE workgroup, which walks them with a barrier in between.
+// trsv_blocked_kernel: the whole solve of a blocked handle, one workgroup per block of rows, each walking its own block's levels with
+// its block's part of x in LDS. No workgroup reads what another one writes.
 //
-// x is read and written inside one launch by both kernels (in the chain kernel the reads DEPEND on the writes), and b may be x:
-// neither pointer is const, __restrict__ or loaded through a non-temporal / read-only path.
+// x is read and written inside one launch by the first two kernels (in the chain kernel the reads DEPEND on the writes), and b may be
+// x in all three: neither pointer is const, __restrict__ or loaded through a non-temporal / read-only path.
 
 #include "trsv.hpp"
 
@@ -24,13 +26,14 @@ struct TrsvTyped {
 	const T * diag;
 	const int * level_ptr;
 	const int * level_slice;
+	const int * block_level;
 };
 
 template <typename T>
 static TrsvTyped<T>
 typed(const TrsvArrays & a)
 {
-	return TrsvTyped<T>{(const T *) a.val, a.col, a.slice_ptr, a.len, a.perm, (const T *) a.diag, a.level_ptr, a.level_slice};
+	return TrsvTyped<T>{(const T *) a.val, a.col, a.slice_ptr, a.len, a.perm, (const T *) a.diag, a.level_ptr, a.level_slice, a.block_level};
 }
 
 // What a row needs that does not depend on x: where it is, b[i], the diagonal and its first TRSV_UNROLL entries. The chain kernel
@@ -103,21 +106,29 @@ trsv_head(const TrsvTyped<T> & a, int pos0, int rows, int slice0, int q, const T
 	}
 }
 
+// x[i] of the row whose head is h; xg is what the stored columns index: x itself, or the block's part of x in LDS
 template <typename T, bool UNIT>
-__device__ __forceinline__ void
-trsv_finish(const TrsvTyped<T> & a, const TrsvHead<T> & h, T * x)
+__device__ __forceinline__ T
+trsv_value(const TrsvTyped<T> & a, const TrsvHead<T> & h, const T * xg)
 {
 	T s = h.s;
 	if (h.cnt > 0)
-		s = trsv_apply<T>(x, h.cnt, 0, h.a, h.c, s);
+		s = trsv_apply<T>(xg, h.cnt, 0, h.a, h.c, s);
 	for (int k = TRSV_UNROLL; k < h.cnt; k += TRSV_UNROLL)
 	{
 		T av[TRSV_UNROLL];
 		int cv[TRSV_UNROLL];
 		trsv_entries<T>(a, h.base, h.lanes, h.cnt, k, av, cv);
-		s = trsv_apply<T>(x, h.cnt, k, av, cv, s);
+		s = trsv_apply<T>(xg, h.cnt, k, av, cv, s);
 	}
-	x[h.i] = UNIT ? s : s / h.d;
+	return UNIT ? s : s / h.d;
+}
+
+template <typename T, bool UNIT>
+__device__ __forceinline__ void
+trsv_finish(const TrsvTyped<T> & a, const TrsvHead<T> & h, T * x)
+{
+	x[h.i] = trsv_value<T, UNIT>(a, h, x);
 }
 
 template <typename T, bool UNIT>
@@ -179,6 +190,66 @@ trsv_chain_kernel(TrsvTyped<T> a, int l0, int l1, const T * b, T * x)
 	}
 }
 
+// ONE WORKGROUP PER BLOCK of block_rows rows; workgroup blk walks the levels block_level[blk] .. block_level[blk + 1] - 1 of its own
+// block and keeps the block's part of x in LDS (xs, min(block_rows, n) values of dynamic LDS), which the stored block-local columns
+// index directly. Every x[j] a row gathers is a row of the same block and an earlier level: it is read from xs, never from global
+// memory. Nothing in this launch reads global x at all; x is only stored to, for the caller.
+// The loop over the levels and the barrier in it are uniform per workgroup: every thread executes every barrier of its block, whether
+// or not a level has a row for it, and nothing returns before the last one. Different workgroups have different trip counts and share
+// nothing: no flag, no atomic, no ordering between them.
+// What orders level l's writes before level l + 1's reads: both are LDS accesses of one workgroup, and __syncthreads() is exactly
+// that hand-off (every wave waits for its own LDS operations, lgkmcnt(0), before it arrives at s_barrier, and no LDS read is moved
+// across it). The chain kernel's s_waitcnt vmcnt(0) is absent ON PURPOSE: it drains the global stores of x because that kernel reads
+// them back through the L1; here nobody reads them, so they stay in flight across the levels and only the end of the kernel waits
+// for them. xs is never initialised: a row reads only slots that an earlier level of this launch wrote.
+// b may be x: a thread reads b[i] (in trsv_head, possibly a level ahead) before the same thread writes x[i], and no other thread of
+// any workgroup touches element i.
+// As in the chain kernel a thread's first row of the next level is begun before the barrier, so its loads (position, length, b[i],
+// diagonal, first entries) fly across it and only LDS reads follow the barrier.
+template <typename T, bool UNIT>
+__global__ __launch_bounds__(TRSV_BLOCKED_THREADS_MAX) void
+trsv_blocked_kernel(TrsvTyped<T> a, int block_rows, const T * b, T * x)
+{
+	extern __shared__ __align__(16) unsigned char trsv_lds[];
+	T * xs = reinterpret_cast<T *>(trsv_lds);
+	const int t = threadIdx.x;
+	const int row0 = blockIdx.x * block_rows;       // < n < 2^31
+	const int l0 = a.block_level[blockIdx.x], l1 = a.block_level[blockIdx.x + 1];
+	int pos0 = a.level_ptr[l0], end = a.level_ptr[l0 + 1], slice0 = a.level_slice[l0];
+	TrsvHead<T> h;
+	bool have = t < end - pos0;
+	if (have)
+		trsv_head<T, UNIT>(a, pos0, end - pos0, slice0, t, b, h);
+	for (int l = l0; l < l1; l++)
+	{
+		const int rows = end - pos0;
+		if (have)
+		{
+			const T v = trsv_value<T, UNIT>(a, h, xs);
+			xs[h.i - row0] = v;
+			x[h.i] = v;
+		}
+		for (int q = t + blockDim.x; q < rows; q += blockDim.x)
+		{
+			TrsvHead<T> g;
+			trsv_head<T, UNIT>(a, pos0, rows, slice0, q, b, g);
+			const T v = trsv_value<T, UNIT>(a, g, xs);
+			xs[g.i - row0] = v;
+			x[g.i] = v;
+		}
+		if (l + 1 < l1)
+		{
+			pos0 = end;
+			end = a.level_ptr[l + 2];
+			slice0 = a.level_slice[l + 1];
+			have = t < end - pos0;
+			if (have)
+				trsv_head<T, UNIT>(a, pos0, end - pos0, slice0, t, b, h);
+		}
+		__syncthreads();
+	}
+}
+
 template <typename T, bool UNIT>
 static void
 level_launch(const TrsvArrays & a, const TrsvStep & s, const void * b, void * x, hipStream_t st)
@@ -213,6 +284,39 @@ launch_trsv_chain(bool f32, bool unit, const TrsvArrays & a, const TrsvStep & s,
 	else
 		unit ? chain_launch<double, true>(a, s, b, x, st) : chain_launch<double, false>(a, s, b, x, st);
 	return 0;
+}
+
+template <typename T, bool UNIT>
+static int
+blocked_launch(const TrsvArrays & a, long blocks, int threads, long block_rows, long n, const void * b, void * x, hipStream_t st)
+{
+	const int lds_bytes = (int) (std::min(block_rows, n) * (long) sizeof(T));
+	// more than 64 KiB of dynamic LDS has to be granted per kernel function, once per device
+	static int granted[64] = {0};
+	int dev = 0;
+	HIP_TRY(hipGetDevice(&dev));
+	dev = dev < 0 || dev >= 64 ? 0 : dev;
+	if (lds_bytes > granted[dev])
+	{
+		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&trsv_blocked_kernel<T, UNIT>),
+				hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+		granted[dev] = lds_bytes;
+	}
+	hipLaunchKernelGGL((trsv_blocked_kernel<T, UNIT>), dim3((unsigned) blocks), dim3(threads), lds_bytes, st, typed<T>(a),
+			(int) block_rows, (const T *) b, (T *) x);
+	HIP_TRY(hipGetLastError());
+	return 0;
+}
+
+int
+launch_trsv_blocked(bool f32, bool unit, const TrsvArrays & a, long blocks, int threads, long block_rows, long n, const void * b,
+		void * x, hipStream_t st)
+{
+	if (f32)
+		return unit ? blocked_launch<float, true>(a, blocks, threads, block_rows, n, b, x, st)
+		            : blocked_launch<float, false>(a, blocks, threads, block_rows, n, b, x, st);
+	return unit ? blocked_launch<double, true>(a, blocks, threads, block_rows, n, b, x, st)
+	            : blocked_launch<double, false>(a, blocks, threads, block_rows, n, b, x, st);
 }
 
 }  // namespace spmv

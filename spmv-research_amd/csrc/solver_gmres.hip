@@ -40,6 +40,17 @@
 // m - 1 of every cycle and one more after the loop: whichever comes first after a stop or at max_iterations applies the partial
 // cycle, every later one finds nothing pending. A restart (SpMV, gmres_residual, gmres_restart) is predicated on `done`.
 //
+// THE TRIANGULAR PRECONDITIONER (spmv_mi355x_gmres_tri, MODE = GMRES_TRI). M v = second^-1 (scale o (first^-1 v)), each part
+// optional, the two solves being spmv_mi355x_trsv handles of any kind. The finish and restart kernels write v only, as without a
+// preconditioner; behind them the host enqueues on the same stream: first (v -> z), gmres_scale_kernel on z, second in place on z,
+// and then the SpMV of z. At a cycle end gmres_combine_kernel writes u to z, the same steps run on it and gmres_add_kernel does
+// x += z; when the scale is the last part (no second) it is multiplied in there, the form the minv path has, which also keeps
+// precond = (NULL, s, NULL) bit for bit the solve with minv = s.
+// Why the freeze survives: the triangular solves and the scale kernel know nothing of `done` and run however far the host is ahead,
+// but everything they write is z, scratch that only the next SpMV or gmres_add_kernel reads. x, the basis and the state are written
+// only by kernels that honour `done` or the pending count: gmres_add_kernel adds nothing when napply is 0, so the pending cycle
+// is applied exactly once here too.
+//
 // DEVIATION worth knowing: gmres_finish writes v_{j+1} (and z) in every block whenever hn is finite and > 0, also in a step whose
 // verdict, reached by block 0 alone after the serial rotation chain, is stop 1 or 4. Nothing reads that vector after a stop.
 
@@ -50,12 +61,14 @@
 
 #include "common.hpp"
 #include "solvers_common.hpp"
+#include "trsv.hpp"
 #include "../../include/spmv_mi355x.h"
 
 namespace spmv {
 
 constexpr int GMRES_MAX_RESTART = 128;
 constexpr int GMRES_TILE = 8;         // basis vectors per pass of the dots: 16 accumulator VGPRs in fp64
+enum { GMRES_PLAIN = 0, GMRES_MINV = 1, GMRES_TRI = 2 };     // M of "M v": none, a diagonal, triangular solves
 
 struct GmresState {
 	double beta0;                 // |b|
@@ -298,6 +311,49 @@ gmres_apply_kernel(const int * __restrict__ napply, const T * __restrict__ V, co
 	}
 }
 
+// GMRES_TRI: out = scale o in, elementwise; `in` may be `out`
+template <typename T>
+__global__ __launch_bounds__(VB) void
+gmres_scale_kernel(const T * __restrict__ scale, const T * in, T * out, long n)
+{
+	GRID_STRIDE(e, n)
+		out[e] = scale[e] * in[e];
+}
+
+// GMRES_TRI: u = y_0 v_0 + ... + y_{p-1} v_{p-1}, p = napply, into the scratch vector
+template <typename T>
+__global__ __launch_bounds__(VB) void
+gmres_combine_kernel(const int * __restrict__ napply, const T * __restrict__ V, const double * __restrict__ y, T * __restrict__ u_out,
+		long n)
+{
+	const int p = *napply;
+	if (p == 0)
+		return;
+	GRID_STRIDE(e, n)
+	{
+		T u = 0;
+		const T * v = V + e;
+		#pragma unroll 4
+		for (int i = 0; i < p; i++)
+			u += (T) y[i] * v[(long) i * n];
+		u_out[e] = u;
+	}
+}
+
+// GMRES_TRI: x += z, or x += scale o z when the scale is the last part of M; nothing when no column was pending
+template <typename T, bool SCALE>
+__global__ __launch_bounds__(VB) void
+gmres_add_kernel(const int * __restrict__ napply, const T * __restrict__ z, const T * __restrict__ scale, T * __restrict__ x, long n)
+{
+	if (*napply == 0)
+		return;
+	GRID_STRIDE(e, n)
+	{
+		const T u = z[e];
+		x[e] = x[e] + (SCALE ? scale[e] * u : u);
+	}
+}
+
 // r = b - q (q = A x) into v_0; partial of |r|^2
 template <typename T>
 __global__ __launch_bounds__(VB) void
@@ -381,11 +437,15 @@ gmres_final_kernel(const T * __restrict__ b, T * __restrict__ q, const T * __res
 
 // ------------------------------------------------------------------------------------------------ host side
 
-template <typename T, bool PRE>
+// minv_host: the inverse diagonal under GMRES_MINV, the scale of M (or NULL) under GMRES_TRI
+template <typename T, int MODE>
 static int
 gmres_solve(spmv_mi355x_matrix * A, const void * b_host, void * x_host, int m, const void * minv_host, double tol,
-		long max_iterations, double * history_host, spmv_mi355x_gmres_info * info)
+		long max_iterations, double * history_host, spmv_mi355x_gmres_info * info, spmv_mi355x_trsv * first = nullptr,
+		spmv_mi355x_trsv * second = nullptr)
 {
+	constexpr bool PRE = MODE == GMRES_MINV;      // what the fused kernels see: under GMRES_TRI they write v only
+	constexpr bool TRI = MODE == GMRES_TRI;
 	const auto t_start = std::chrono::steady_clock::now();
 	const long n = spmv_mi355x_rows(A);
 	hipStream_t stream = nullptr;
@@ -398,11 +458,10 @@ gmres_solve(spmv_mi355x_matrix * A, const void * b_host, void * x_host, int m, c
 	for (T ** p : {&b, &x, &w})
 		ABI_TRY(buf.alloc(p, nbytes));
 	ABI_TRY(buf.alloc(&V, nbytes * (size_t) (m + 1)));
-	if (PRE)
-	{
+	if (PRE || TRI)
 		ABI_TRY(buf.alloc(&z, nbytes));
+	if (PRE || (TRI && minv_host))
 		ABI_TRY(buf.alloc(&minv, nbytes));
-	}
 	// one fp64 block: R (m * m), cs, sn (m each), g (m + 1), y, c1, c2 (m each)
 	const size_t small_count = (size_t) m * m + 6 * (size_t) m + 1;
 	double * small, * part, * history = nullptr;
@@ -424,7 +483,7 @@ gmres_solve(spmv_mi355x_matrix * A, const void * b_host, void * x_host, int m, c
 	ABI_TRY(gate.init());
 
 	HIP_TRY(hipMemcpyAsync(b, b_host, nbytes, hipMemcpyHostToDevice, stream));
-	if (PRE)
+	if (minv)
 		HIP_TRY(hipMemcpyAsync(minv, minv_host, nbytes, hipMemcpyHostToDevice, stream));
 	HIP_TRY(hipMemsetAsync(part, 0, part_bytes, stream));
 	HIP_TRY(hipMemsetAsync(small, 0, sizeof(double) * small_count, stream));
@@ -441,15 +500,45 @@ gmres_solve(spmv_mi355x_matrix * A, const void * b_host, void * x_host, int m, c
 	};
 	// the state of the moment is st[s & 1]; every transition (an inner step, a restart) reads it, writes the other slot and adds 1
 	long s = 0;
+	// GMRES_TRI: z = M in, part by part; `in` may be z. With defer_scale a scale that is M's last part is left to the caller.
+	auto precond = [&](const T * in, bool defer_scale) {
+		const T * src = in;
+		if (first)
+		{
+			ABI_TRY(spmv_mi355x_trsv_solve_device_async(first, src, z, stream));
+			src = z;
+		}
+		if (minv && !(defer_scale && !second))
+		{
+			hipLaunchKernelGGL((gmres_scale_kernel<T>), grid, block, 0, stream, minv, src, z, n);
+			src = z;
+		}
+		if (second)
+			ABI_TRY(spmv_mi355x_trsv_solve_device_async(second, src, z, stream));
+		return 0;
+	};
 	auto cycle_end = [&]() {
 		hipLaunchKernelGGL(gmres_solve_y_kernel, one, block, 0, stream, st + (s & 1), R, g, m, y, napply);
-		hipLaunchKernelGGL((gmres_apply_kernel<T, PRE>), grid, block, 0, stream, napply, V, y, minv, x, n);
+		if (!TRI)
+		{
+			hipLaunchKernelGGL((gmres_apply_kernel<T, PRE>), grid, block, 0, stream, napply, V, y, minv, x, n);
+			return 0;
+		}
+		hipLaunchKernelGGL((gmres_combine_kernel<T>), grid, block, 0, stream, napply, V, y, z, n);
+		ABI_TRY(precond(z, true));
+		if (minv && !second)
+			hipLaunchKernelGGL((gmres_add_kernel<T, true>), grid, block, 0, stream, napply, z, minv, x, n);
+		else
+			hipLaunchKernelGGL((gmres_add_kernel<T, false>), grid, block, 0, stream, napply, z, minv, x, n);
+		return 0;
 	};
 
 	hipLaunchKernelGGL((gmres_start_kernel<T>), grid, block, 0, stream, b, V, n, part, s_bb);
 	hipLaunchKernelGGL((gmres_restart_kernel<T, PRE>), grid, block, 0, stream, st + (s & 1), st + ((s + 1) & 1), V, z, minv, n, nb,
 			part, s_bb, 1, g);
 	s++;
+	if (TRI)
+		ABI_TRY(precond(V, false));
 	HIP_TRY(hipGetLastError());
 
 	long it = 0;
@@ -461,7 +550,7 @@ gmres_solve(spmv_mi355x_matrix * A, const void * b_host, void * x_host, int m, c
 			break;
 		const int j = (int) (it % m);
 		GmresState * cur = st + (s & 1), * nxt = st + ((s + 1) & 1);
-		ABI_TRY(spmv(PRE ? z : V + (size_t) j * n, w));
+		ABI_TRY(spmv(PRE || TRI ? z : V + (size_t) j * n, w));
 		hipLaunchKernelGGL((gmres_dots_kernel<T>), grid, block, 0, stream, cur, V, w, n, j + 1, part);
 		hipLaunchKernelGGL(gmres_reduce_kernel, dim3(j + 1), block, 0, stream, cur, part, nb, c1);
 		hipLaunchKernelGGL((gmres_update_kernel<T, false>), grid, block, 0, stream, cur, V, w, n, j + 1, c1, part, s_nrm);
@@ -470,9 +559,11 @@ gmres_solve(spmv_mi355x_matrix * A, const void * b_host, void * x_host, int m, c
 		hipLaunchKernelGGL((gmres_finish_kernel<T, PRE>), grid, block, 0, stream, cur, nxt, V + (size_t) (j + 1) * n, z, w, minv, n,
 				nb, j, m, c1, c2, R, cs, sn, g, tol, part, s_nrm, history, it, gate.dev);
 		s++;
+		if (TRI && j < m - 1)
+			ABI_TRY(precond(V + (size_t) (j + 1) * n, false));
 		if (j == m - 1)
 		{
-			cycle_end();
+			ABI_TRY(cycle_end());
 			if (it + 1 < max_iterations)
 			{
 				cur = st + (s & 1), nxt = st + ((s + 1) & 1);
@@ -480,10 +571,12 @@ gmres_solve(spmv_mi355x_matrix * A, const void * b_host, void * x_host, int m, c
 				hipLaunchKernelGGL((gmres_residual_kernel<T>), grid, block, 0, stream, cur, b, w, V, n, part, s_rr);
 				hipLaunchKernelGGL((gmres_restart_kernel<T, PRE>), grid, block, 0, stream, cur, nxt, V, z, minv, n, nb, part, s_rr, 0, g);
 				s++;
+				if (TRI)
+					ABI_TRY(precond(V, false));
 			}
 		}
 	}
-	cycle_end();                      // the partial cycle of a stop or of max_iterations, if no cycle end above has met it
+	ABI_TRY(cycle_end());             // the partial cycle of a stop or of max_iterations, if no cycle end above has met it
 	HIP_TRY(hipGetLastError());
 
 	// the explicit norms of the returned x: |b - A x| and |x|. w is free now; x stays as it froze.
@@ -531,6 +624,55 @@ gmres_bad_minv(const void * minv_host, long n)
 	return -1;
 }
 
+// the first entry of a scale that is not finite or is zero, or -1
+template <typename T>
+static long
+gmres_bad_scale(const void * scale_host, long n)
+{
+	const T * d = (const T *) scale_host;
+	for (long i = 0; i < n; i++)
+		if (d[i] == 0 || !std::isfinite(d[i]))
+			return i;
+	return -1;
+}
+
+// what both entries check first, in the order of the header: the scalars, the NULL pointers, the shape
+static int
+gmres_check_common(const char * what, spmv_mi355x_matrix * A, const void * b_host, void * x_out_host, int restart, double tol,
+		long max_iterations, spmv_mi355x_gmres_info * info)
+{
+	// the checks that need no handle come first, so each can be met (and tested) on its own
+	if (!info_size_ok(what, info))
+		return 1;
+	if (restart < 1 || restart > GMRES_MAX_RESTART)
+	{
+		set_error("%s: restart must be 1 .. %d (got %d)", what, GMRES_MAX_RESTART, restart);
+		return 1;
+	}
+	if (!(tol >= 0) || !std::isfinite(tol))
+	{
+		set_error("%s: tol must be finite and >= 0 (got %g)", what, tol);
+		return 1;
+	}
+	if (max_iterations < 0)
+	{
+		set_error("%s: max_iterations < 0", what);
+		return 1;
+	}
+	if (!A || !b_host || !x_out_host)
+	{
+		set_error("%s: NULL argument (%s%s%s )", what, !A ? " A" : "", !b_host ? " b" : "", !x_out_host ? " x_out" : "");
+		return 1;
+	}
+	const long m = spmv_mi355x_rows(A), n = spmv_mi355x_cols(A);
+	if (m != n)
+	{
+		set_error("%s: the matrix must be square: the handle is %ld x %ld (a row block of a larger matrix is not served)", what, m, n);
+		return 1;
+	}
+	return 0;
+}
+
 }  // namespace spmv
 
 extern "C" int
@@ -538,35 +680,9 @@ spmv_mi355x_gmres(spmv_mi355x_matrix * A, const void * b_host, void * x_out_host
 		long max_iterations, double * history_out, spmv_mi355x_gmres_info * info)
 {
 	using namespace spmv;
-	// the checks that need no handle come first, so each can be met (and tested) on its own
-	if (!info_size_ok("gmres", info))
+	if (gmres_check_common("gmres", A, b_host, x_out_host, restart, tol, max_iterations, info))
 		return 1;
-	if (restart < 1 || restart > GMRES_MAX_RESTART)
-	{
-		set_error("gmres: restart must be 1 .. %d (got %d)", GMRES_MAX_RESTART, restart);
-		return 1;
-	}
-	if (!(tol >= 0) || !std::isfinite(tol))
-	{
-		set_error("gmres: tol must be finite and >= 0 (got %g)", tol);
-		return 1;
-	}
-	if (max_iterations < 0)
-	{
-		set_error("gmres: max_iterations < 0");
-		return 1;
-	}
-	if (!A || !b_host || !x_out_host)
-	{
-		set_error("gmres: NULL argument (%s%s%s )", !A ? " A" : "", !b_host ? " b" : "", !x_out_host ? " x_out" : "");
-		return 1;
-	}
-	const long m = spmv_mi355x_rows(A), n = spmv_mi355x_cols(A);
-	if (m != n)
-	{
-		set_error("gmres: the matrix must be square: the handle is %ld x %ld (a row block of a larger matrix is not served)", m, n);
-		return 1;
-	}
+	const long n = spmv_mi355x_cols(A);
 	const bool f32 = spmv_mi355x_precision(A) == SPMV_MI355X_F32;
 	if (minv_host)
 	{
@@ -580,8 +696,67 @@ spmv_mi355x_gmres(spmv_mi355x_matrix * A, const void * b_host, void * x_out_host
 	}
 	HIP_TRY(hipSetDevice(spmv_mi355x_device(A)));
 	if (f32)
-		return minv_host ? gmres_solve<float, true>(A, b_host, x_out_host, restart, minv_host, tol, max_iterations, history_out, info)
-		                 : gmres_solve<float, false>(A, b_host, x_out_host, restart, nullptr, tol, max_iterations, history_out, info);
-	return minv_host ? gmres_solve<double, true>(A, b_host, x_out_host, restart, minv_host, tol, max_iterations, history_out, info)
-	                 : gmres_solve<double, false>(A, b_host, x_out_host, restart, nullptr, tol, max_iterations, history_out, info);
+		return minv_host ? gmres_solve<float, GMRES_MINV>(A, b_host, x_out_host, restart, minv_host, tol, max_iterations, history_out, info)
+		                 : gmres_solve<float, GMRES_PLAIN>(A, b_host, x_out_host, restart, nullptr, tol, max_iterations, history_out, info);
+	return minv_host ? gmres_solve<double, GMRES_MINV>(A, b_host, x_out_host, restart, minv_host, tol, max_iterations, history_out, info)
+	                 : gmres_solve<double, GMRES_PLAIN>(A, b_host, x_out_host, restart, nullptr, tol, max_iterations, history_out, info);
+}
+
+extern "C" int
+spmv_mi355x_gmres_tri(spmv_mi355x_matrix * A, const void * b_host, void * x_out_host, int restart, const spmv_mi355x_tri_precond * M,
+		double tol, long max_iterations, double * history_out, spmv_mi355x_gmres_info * info)
+{
+	using namespace spmv;
+	if (gmres_check_common("gmres_tri", A, b_host, x_out_host, restart, tol, max_iterations, info))
+		return 1;
+	if (!M || M->struct_size < sizeof(spmv_mi355x_tri_precond))
+	{
+		if (!M)
+			set_error("gmres_tri: NULL preconditioner M");
+		else
+			set_error("gmres_tri: M->struct_size = %u is smaller than sizeof(spmv_mi355x_tri_precond) = %zu", M->struct_size,
+					sizeof(spmv_mi355x_tri_precond));
+		return 1;
+	}
+	if (!M->first && !M->scale_host && !M->second)
+	{
+		set_error("gmres_tri: M has no first, no scale and no second: for a solve without a preconditioner call spmv_mi355x_gmres");
+		return 1;
+	}
+	const long n = spmv_mi355x_cols(A);
+	const int precision = spmv_mi355x_precision(A), device = spmv_mi355x_device(A);
+	const bool f32 = precision == SPMV_MI355X_F32;
+	const spmv_mi355x_trsv * parts[2] = {M->first, M->second};
+	for (int k = 0; k < 2; k++)
+	{
+		const spmv_mi355x_trsv * T = parts[k];
+		const char * name = k ? "second" : "first";
+		if (!T)
+			continue;
+		if (T->n != n)
+			set_error("gmres_tri: M->%s is a triangular solve of %ld rows, the matrix has %ld", name, T->n, n);
+		else if (T->precision != precision)
+			set_error("gmres_tri: M->%s has precision %d, the matrix %d: both must be the same", name, T->precision, precision);
+		else if (T->device != device)
+			set_error("gmres_tri: M->%s lives on device %d, the matrix on device %d", name, T->device, device);
+		else
+			continue;
+		return 1;
+	}
+	if (M->scale_host)
+	{
+		const long bad = f32 ? gmres_bad_scale<float>(M->scale_host, n) : gmres_bad_scale<double>(M->scale_host, n);
+		if (bad >= 0)
+		{
+			set_error("gmres_tri: scale[%ld] = %g: every entry of the scale must be finite and non-zero", bad,
+					f32 ? (double) ((const float *) M->scale_host)[bad] : ((const double *) M->scale_host)[bad]);
+			return 1;
+		}
+	}
+	HIP_TRY(hipSetDevice(device));
+	if (f32)
+		return gmres_solve<float, GMRES_TRI>(A, b_host, x_out_host, restart, M->scale_host, tol, max_iterations, history_out, info,
+				M->first, M->second);
+	return gmres_solve<double, GMRES_TRI>(A, b_host, x_out_host, restart, M->scale_host, tol, max_iterations, history_out, info,
+			M->first, M->second);
 }

@@ -7,6 +7,11 @@
 // (trsv_level_kernel). The launches of a solve go to one stream in level order and that order is the only thing that orders
 // workgroups: no flag is spun on, there is no grid barrier, no cooperative or persistent kernel and no captured graph. A workgroup
 // never waits for another one, so a solve cannot hang whatever else runs on the device.
+//
+// THE BLOCKED PLAN (trsv_create_blocked). Block b owns the rows [b B, min(n, (b + 1) B)); a kept entry (i, j) whose column lies in
+// another block is dropped, and the level rule runs over what is left, block by block. No row of a block depends on a row of another
+// one, so all blocks are solved by ONE launch with one workgroup per block (trsv_blocked_kernel), and again no workgroup waits for
+// another one. What is lost is the dropped couplings: the handle solves the block-diagonal part of the triangle, exactly.
 
 #include <cmath>
 #include <cstring>
@@ -24,10 +29,13 @@ struct TrsvAnalysis {
 	std::vector<TrsvStep> plan;
 	long levels = 0, max_level_rows = 0;
 	int chain_rows = 0;
+	// the blocked plan: level_of_row, level_ptr and level_slice number the levels through all blocks, `levels` is their count
+	std::vector<int32_t> block_level;      // blocks + 1
+	long block_rows = 0, blocks = 0, max_block_levels = 0, nnz_dropped = 0;
 };
 
 static bool
-trsv_scalars_ok(const char * what, int uplo, const int * diag, const int * precision, long n, int chain_rows)
+trsv_scalars_ok(const char * what, int uplo, const int * diag, const int * precision, long n, long chain_rows, bool blocked = false)
 {
 	if (uplo != SPMV_MI355X_LOWER && uplo != SPMV_MI355X_UPPER)
 		set_error("%s: uplo must be SPMV_MI355X_LOWER (0) or SPMV_MI355X_UPPER (1) (got %d)", what, uplo);
@@ -37,8 +45,10 @@ trsv_scalars_ok(const char * what, int uplo, const int * diag, const int * preci
 		set_error("%s: unknown precision %d", what, *precision);
 	else if (n < 0 || n >= 0x7fffffffL)
 		set_error("%s: n = %ld out of range [0, 2^31 - 1)", what, n);
-	else if (chain_rows < 0 || chain_rows > TRSV_CHAIN_ROWS_MAX)
-		set_error("%s: chain_rows must be 0 (the default) or 1 .. %d (got %d)", what, TRSV_CHAIN_ROWS_MAX, chain_rows);
+	else if (blocked && (chain_rows < 0 || chain_rows > TRSV_BLOCK_ROWS_MAX))
+		set_error("%s: block_rows must be 0 (the default) or 1 .. %d (got %ld)", what, TRSV_BLOCK_ROWS_MAX, chain_rows);
+	else if (!blocked && (chain_rows < 0 || chain_rows > TRSV_CHAIN_ROWS_MAX))
+		set_error("%s: chain_rows must be 0 (the default) or 1 .. %d (got %ld)", what, TRSV_CHAIN_ROWS_MAX, chain_rows);
 	else
 		return true;
 	return false;
@@ -76,11 +86,18 @@ trsv_check_pattern(const char * what, long n, const int32_t * rp, const int32_t 
 	return 0;
 }
 
-// is entry (i, c) a kept off-diagonal entry, i.e. a dependency of row i?
+// is entry (i, c) an off-diagonal entry of the chosen triangle?
 static inline bool
 trsv_dep(int uplo, long i, long c)
 {
 	return uplo == SPMV_MI355X_LOWER ? c < i : c > i;
+}
+
+// is it kept, i.e. a dependency of row i? B = block_rows of a blocked handle (the column must lie in the row's block), 0 otherwise
+static inline bool
+trsv_dep(int uplo, long i, long c, long B)
+{
+	return trsv_dep(uplo, i, c) && (B == 0 || c / B == i / B);
 }
 
 // O(nnz). The pattern has been checked.
@@ -146,21 +163,68 @@ trsv_analysis(int uplo, long n, const int32_t * rp, const int32_t * ci, int chai
 	}
 }
 
+// The blocked plan, O(nnz); block_rows = 0 is the default. The blocks are independent of each other.
+static void
+trsv_analysis_blocked(int uplo, long n, const int32_t * rp, const int32_t * ci, long block_rows, TrsvAnalysis & an)
+{
+	const long B = block_rows ? block_rows : TRSV_BLOCK_ROWS_DEFAULT;
+	const long blocks = (n + B - 1) / B;
+	const bool lower = uplo == SPMV_MI355X_LOWER;
+	an.block_rows = B;
+	an.blocks = blocks;
+	an.level_of_row.assign((size_t) n, 0);
+	an.block_level.assign((size_t) blocks + 1, 0);
+	int32_t * level = an.level_of_row.data();
+	long dropped = 0;
+	// the level of a row WITHIN its block, and the levels of every block
+	#pragma omp parallel for num_threads(spmv::host_threads()) reduction(+ : dropped) schedule(dynamic, 16)
+	for (long blk = 0; blk < blocks; blk++)
+	{
+		const long r0 = blk * B, r1 = std::min(n, r0 + B);
+		int32_t top = -1;
+		for (long t = r0; t < r1; t++)
+		{
+			const long i = lower ? t : r1 - 1 - (t - r0);
+			int32_t lv = 0;
+			for (long j = rp[i]; j < rp[i + 1]; j++)
+				if (trsv_dep(uplo, i, ci[j], B))
+					lv = std::max(lv, level[ci[j]] + 1);
+				else if (trsv_dep(uplo, i, ci[j]))
+					dropped++;
+			level[i] = lv;
+			top = std::max(top, lv);
+		}
+		an.block_level[blk + 1] = top + 1;
+	}
+	an.nnz_dropped = dropped;
+	an.max_block_levels = 0;
+	for (long blk = 0; blk < blocks; blk++)
+	{
+		an.max_block_levels = std::max<long>(an.max_block_levels, an.block_level[blk + 1]);
+		an.block_level[blk + 1] += an.block_level[blk];
+	}
+	an.levels = blocks ? an.block_level[blocks] : 0;
+	// from here on level_of_row numbers the levels through all blocks; the callers that report it subtract block_level again
+	#pragma omp parallel for num_threads(spmv::host_threads()) schedule(static, 4096)
+	for (long i = 0; i < n; i++)
+		level[i] += an.block_level[i / B];
+	an.level_ptr.assign((size_t) an.levels + 1, 0);
+	an.level_slice.assign((size_t) an.levels + 1, 0);
+	for (long i = 0; i < n; i++)
+		an.level_ptr[level[i] + 1]++;
+	an.max_level_rows = 0;
+	for (long l = 0; l < an.levels; l++)
+	{
+		const int32_t rows = an.level_ptr[l + 1];
+		an.max_level_rows = std::max<long>(an.max_level_rows, rows);
+		an.level_ptr[l + 1] = an.level_ptr[l] + rows;
+		an.level_slice[l + 1] = an.level_slice[l] + (rows + TRSV_SLICE - 1) / TRSV_SLICE;
+	}
+}
+
 }  // namespace spmv
 
 using namespace spmv;
-
-struct spmv_mi355x_trsv {
-	int uplo = 0, diag = 0, precision = 0, device = 0;
-	bool f32 = false;
-	long n = 0, nnz_kept = 0, levels = 0, max_level_rows = 0;
-	int chain_rows = 0;
-	std::vector<TrsvStep> plan;
-	TrsvArrays arr = {};
-	void * owned[8] = {};                 // the device arrays behind arr
-	void * d_b = nullptr, * d_x = nullptr;     // the vectors of the host-buffer solve, allocated at its first call
-	double mem_footprint = 0;
-};
 
 namespace spmv {
 
@@ -168,7 +232,7 @@ namespace spmv {
 // non-zero after narrowing to the handle's precision, and be the only entry with column i. The first bad row is reported.
 template <typename T>
 static int
-trsv_check_diagonal(long n, const int32_t * rp, const int32_t * ci, const double * va)
+trsv_check_diagonal(const char * what, long n, const int32_t * rp, const int32_t * ci, const double * va)
 {
 	long bad = n;
 	#pragma omp parallel for num_threads(spmv::host_threads()) reduction(min : bad) schedule(static, 4096)
@@ -198,11 +262,11 @@ trsv_check_diagonal(long n, const int32_t * rp, const int32_t * ci, const double
 			count++;
 		}
 	if (at < 0)
-		set_error("trsv_create: row %ld has no diagonal entry (SPMV_MI355X_DIAG_STORED needs one in every row)", bad);
+		set_error("%s: row %ld has no diagonal entry (SPMV_MI355X_DIAG_STORED needs one in every row)", what, bad);
 	else if (count > 1)
-		set_error("trsv_create: row %ld stores %ld entries with column %ld: the diagonal must be stored once", bad, count, bad);
+		set_error("%s: row %ld stores %ld entries with column %ld: the diagonal must be stored once", what, bad, count, bad);
 	else
-		set_error("trsv_create: the diagonal of row %ld is %g in the handle's precision (from %g): it must be finite and non-zero", bad,
+		set_error("%s: the diagonal of row %ld is %g in the handle's precision (from %g): it must be finite and non-zero", what, bad,
 				(double) (T) va[at], va[at]);
 	return 1;
 }
@@ -214,6 +278,7 @@ trsv_build(spmv_mi355x_trsv * H, const TrsvAnalysis & an, const int32_t * rp, co
 	const long n = H->n, levels = an.levels;
 	const long slices = levels ? an.level_slice[levels] : 0;
 	const bool stored = H->diag == SPMV_MI355X_DIAG_STORED;
+	const long B = H->block_rows;         // 0: a global handle
 	std::vector<int32_t> perm((size_t) n), len((size_t) n);
 	std::vector<T> diag(stored ? (size_t) n : 0);
 	{
@@ -230,7 +295,7 @@ trsv_build(spmv_mi355x_trsv * H, const TrsvAnalysis & an, const int32_t * rp, co
 		bool have = false;
 		for (long j = rp[i]; j < rp[i + 1]; j++)
 		{
-			c += trsv_dep(H->uplo, i, ci[j]);
+			c += trsv_dep(H->uplo, i, ci[j], B);
 			if (stored && !have && ci[j] == i)
 			{
 				diag[p] = (T) va[j];
@@ -276,23 +341,24 @@ trsv_build(spmv_mi355x_trsv * H, const TrsvAnalysis & an, const int32_t * rp, co
 			const long i = perm[p0 + r];
 			int64_t e = slice_ptr[s] + r;
 			for (long j = rp[i]; j < rp[i + 1]; j++)
-				if (trsv_dep(H->uplo, i, ci[j]))
+				if (trsv_dep(H->uplo, i, ci[j], B))
 				{
 					val[e] = (T) va[j];              // narrowed as spmv_mi355x_create narrows
-					col[e] = ci[j];
+					col[e] = B ? (int32_t) (ci[j] - i / B * B) : ci[j];     // blocked: the column within the block
 					e += lanes;
 				}
 		}
 	}
-	struct Up { const void * src; size_t bytes; } ups[8] = {
+	struct Up { const void * src; size_t bytes; } ups[9] = {
 		{val.data(), stored_entries * sizeof(T)}, {col.data(), stored_entries * sizeof(int32_t)},
 		{slice_ptr.data(), slice_ptr.size() * sizeof(int64_t)}, {len.data(), (size_t) n * sizeof(int32_t)},
 		{perm.data(), (size_t) n * sizeof(int32_t)}, {diag.data(), diag.size() * sizeof(T)},
-		{an.level_ptr.data(), an.level_ptr.size() * sizeof(int32_t)}, {an.level_slice.data(), an.level_slice.size() * sizeof(int32_t)}};
+		{an.level_ptr.data(), an.level_ptr.size() * sizeof(int32_t)}, {an.level_slice.data(), an.level_slice.size() * sizeof(int32_t)},
+		{an.block_level.data(), an.block_level.size() * sizeof(int32_t)}};
 	H->mem_footprint = 0;
-	for (int k = 0; k < 8; k++)
+	for (int k = 0; k < 9; k++)
 	{
-		if (k == 5 && !stored)
+		if ((k == 5 && !stored) || (k == 8 && !B))
 			continue;
 		if (upload_bytes(ups[k].src, ups[k].bytes, 0, &H->owned[k]))
 			return 1;
@@ -306,6 +372,7 @@ trsv_build(spmv_mi355x_trsv * H, const TrsvAnalysis & an, const int32_t * rp, co
 	H->arr.diag = H->owned[5];
 	H->arr.level_ptr = (const int *) H->owned[6];
 	H->arr.level_slice = (const int *) H->owned[7];
+	H->arr.block_level = (const int *) H->owned[8];
 	return 0;
 }
 
@@ -322,6 +389,110 @@ trsv_free(spmv_mi355x_trsv * H)
 	delete H;
 }
 
+// The checks 1 to 3 and the analysis of both analyze entries; rows = chain_rows, or block_rows of the blocked form. level_of_row_out
+// receives the levels as the caller counts them: within the row's block for the blocked form.
+static int
+trsv_analyze_checked(const char * what, bool blocked, int uplo, long n, const int32_t * row_ptr, const int32_t * col_idx, long rows,
+		int32_t ** level_of_row_out, TrsvAnalysis & an)
+{
+	if (level_of_row_out)
+		*level_of_row_out = nullptr;
+	if (!trsv_scalars_ok(what, uplo, nullptr, nullptr, n, rows, blocked))
+		return 1;
+	if (!row_ptr || (!col_idx && row_ptr[n] > 0))
+	{
+		set_error("%s: NULL argument (%s%s )", what, !row_ptr ? " row_ptr" : "", !col_idx ? " col_idx" : "");
+		return 1;
+	}
+	if (trsv_check_pattern(what, n, row_ptr, col_idx))
+		return 1;
+	if (blocked)
+		trsv_analysis_blocked(uplo, n, row_ptr, col_idx, rows, an);
+	else
+		trsv_analysis(uplo, n, row_ptr, col_idx, (int) rows, an);
+	if (level_of_row_out)
+	{
+		int32_t * lv = (int32_t *) malloc(std::max<size_t>((size_t) n, 1) * sizeof(int32_t));
+		if (!lv)
+		{
+			set_error("%s: out of host memory (%ld levels of rows)", what, n);
+			return 1;
+		}
+		for (long i = 0; i < n; i++)
+			lv[i] = an.level_of_row[i] - (blocked ? an.block_level[i / an.block_rows] : 0);
+		*level_of_row_out = lv;
+	}
+	return 0;
+}
+
+// both create entries; rows = chain_rows, or block_rows of the blocked form
+static int
+trsv_create(const char * what, bool blocked, spmv_mi355x_trsv ** out, int uplo, int diag, int precision, long n,
+		const int32_t * row_ptr, const int32_t * col_idx, const double * values, long rows, int device)
+{
+	if (out)
+		*out = nullptr;
+	// 1. scalars, 2. NULL pointers, 3. the pattern, 4. the diagonal: all on the host; 5. the device
+	if (!trsv_scalars_ok(what, uplo, &diag, &precision, n, rows, blocked))
+		return 1;
+	const bool entries = row_ptr && row_ptr[n] > 0;
+	if (!out || !row_ptr || (entries && (!col_idx || !values)))
+	{
+		set_error("%s: NULL argument (%s%s%s%s )", what, !out ? " out" : "", !row_ptr ? " row_ptr" : "",
+				entries && !col_idx ? " col_idx" : "", entries && !values ? " values" : "");
+		return 1;
+	}
+	if (trsv_check_pattern(what, n, row_ptr, col_idx))
+		return 1;
+	const bool f32 = precision == SPMV_MI355X_F32;
+	if (diag == SPMV_MI355X_DIAG_STORED && (f32 ? trsv_check_diagonal<float>(what, n, row_ptr, col_idx, values)
+	                                            : trsv_check_diagonal<double>(what, n, row_ptr, col_idx, values)))
+		return 1;
+	int ndev = 0;
+	spmv_mi355x_device_count(&ndev);
+	if (ndev < 1)
+	{
+		set_error("%s: no HIP device available: this engine has no CPU fallback", what);
+		return 1;
+	}
+	if (device < 0)
+		HIP_TRY(hipGetDevice(&device));
+	if (device >= ndev)
+	{
+		set_error("%s: device %d out of range (%d devices)", what, device, ndev);
+		return 1;
+	}
+	HIP_TRY(hipSetDevice(device));
+	TrsvAnalysis an;
+	if (blocked)
+		trsv_analysis_blocked(uplo, n, row_ptr, col_idx, rows, an);
+	else
+		trsv_analysis(uplo, n, row_ptr, col_idx, (int) rows, an);
+	spmv_mi355x_trsv * H = new spmv_mi355x_trsv();
+	H->uplo = uplo;
+	H->diag = diag;
+	H->precision = precision;
+	H->f32 = f32;
+	H->device = device;
+	H->n = n;
+	H->levels = blocked ? an.max_block_levels : an.levels;
+	H->max_level_rows = an.max_level_rows;
+	H->chain_rows = an.chain_rows;
+	H->plan = an.plan;
+	H->block_rows = an.block_rows;
+	H->blocks = an.blocks;
+	H->nnz_dropped = an.nnz_dropped;
+	// one width for the whole launch: the widest level of any block in whole waves, at least one wave
+	H->threads = (int) std::min<long>(TRSV_BLOCKED_THREADS_MAX, std::max<long>(WAVE, (an.max_level_rows + WAVE - 1) / WAVE * WAVE));
+	if (f32 ? trsv_build<float>(H, an, row_ptr, col_idx, values) : trsv_build<double>(H, an, row_ptr, col_idx, values))
+	{
+		trsv_free(H);
+		return 1;
+	}
+	*out = H;
+	return 0;
+}
+
 }  // namespace spmv
 
 extern "C" {
@@ -330,31 +501,9 @@ int
 spmv_mi355x_trsv_analyze(int uplo, long n, const int32_t * row_ptr, const int32_t * col_idx, int chain_rows,
 		int32_t ** level_of_row_out, long * levels_out, long * launches_out, long * max_level_rows_out, int * chain_rows_used_out)
 {
-	if (level_of_row_out)
-		*level_of_row_out = nullptr;
-	if (!trsv_scalars_ok("trsv_analyze", uplo, nullptr, nullptr, n, chain_rows))
-		return 1;
-	if (!row_ptr || (!col_idx && row_ptr[n] > 0))
-	{
-		set_error("trsv_analyze: NULL argument (%s%s )", !row_ptr ? " row_ptr" : "", !col_idx ? " col_idx" : "");
-		return 1;
-	}
-	if (trsv_check_pattern("trsv_analyze", n, row_ptr, col_idx))
-		return 1;
 	TrsvAnalysis an;
-	trsv_analysis(uplo, n, row_ptr, col_idx, chain_rows, an);
-	if (level_of_row_out)
-	{
-		int32_t * lv = (int32_t *) malloc(std::max<size_t>((size_t) n, 1) * sizeof(int32_t));
-		if (!lv)
-		{
-			set_error("trsv_analyze: out of host memory (%ld levels of rows)", n);
-			return 1;
-		}
-		if (n)
-			memcpy(lv, an.level_of_row.data(), (size_t) n * sizeof(int32_t));
-		*level_of_row_out = lv;
-	}
+	if (trsv_analyze_checked("trsv_analyze", false, uplo, n, row_ptr, col_idx, chain_rows, level_of_row_out, an))
+		return 1;
 	if (levels_out)
 		*levels_out = an.levels;
 	if (launches_out)
@@ -367,61 +516,57 @@ spmv_mi355x_trsv_analyze(int uplo, long n, const int32_t * row_ptr, const int32_
 }
 
 int
+spmv_mi355x_trsv_analyze_blocked(int uplo, long n, const int32_t * row_ptr, const int32_t * col_idx, long block_rows,
+		int32_t ** level_of_row_out, long * blocks_out, long * max_block_levels_out, long * max_level_rows_out, long * nnz_dropped_out,
+		long * block_rows_used_out)
+{
+	TrsvAnalysis an;
+	if (trsv_analyze_checked("trsv_analyze_blocked", true, uplo, n, row_ptr, col_idx, block_rows, level_of_row_out, an))
+		return 1;
+	if (blocks_out)
+		*blocks_out = an.blocks;
+	if (max_block_levels_out)
+		*max_block_levels_out = an.max_block_levels;
+	if (max_level_rows_out)
+		*max_level_rows_out = an.max_level_rows;
+	if (nnz_dropped_out)
+		*nnz_dropped_out = an.nnz_dropped;
+	if (block_rows_used_out)
+		*block_rows_used_out = an.block_rows;
+	return 0;
+}
+
+int
 spmv_mi355x_trsv_create(spmv_mi355x_trsv ** out, int uplo, int diag, int precision, long n, const int32_t * row_ptr,
 		const int32_t * col_idx, const double * values, int chain_rows, int device)
 {
-	if (out)
-		*out = nullptr;
-	// 1. scalars, 2. NULL pointers, 3. the pattern, 4. the diagonal: all on the host; 5. the device
-	if (!trsv_scalars_ok("trsv_create", uplo, &diag, &precision, n, chain_rows))
-		return 1;
-	const bool entries = row_ptr && row_ptr[n] > 0;
-	if (!out || !row_ptr || (entries && (!col_idx || !values)))
+	return trsv_create("trsv_create", false, out, uplo, diag, precision, n, row_ptr, col_idx, values, chain_rows, device);
+}
+
+int
+spmv_mi355x_trsv_create_blocked(spmv_mi355x_trsv ** out, int uplo, int diag, int precision, long n, const int32_t * row_ptr,
+		const int32_t * col_idx, const double * values, long block_rows, int device)
+{
+	return trsv_create("trsv_create_blocked", true, out, uplo, diag, precision, n, row_ptr, col_idx, values, block_rows, device);
+}
+
+int
+spmv_mi355x_trsv_block_info(const spmv_mi355x_trsv * T, long * block_rows_out, long * blocks_out, long * max_block_levels_out,
+		long * nnz_dropped_out)
+{
+	if (!T)
 	{
-		set_error("trsv_create: NULL argument (%s%s%s%s )", !out ? " out" : "", !row_ptr ? " row_ptr" : "",
-				entries && !col_idx ? " col_idx" : "", entries && !values ? " values" : "");
+		set_error("trsv_block_info: NULL handle");
 		return 1;
 	}
-	if (trsv_check_pattern("trsv_create", n, row_ptr, col_idx))
-		return 1;
-	const bool f32 = precision == SPMV_MI355X_F32;
-	if (diag == SPMV_MI355X_DIAG_STORED &&
-	    (f32 ? trsv_check_diagonal<float>(n, row_ptr, col_idx, values) : trsv_check_diagonal<double>(n, row_ptr, col_idx, values)))
-		return 1;
-	int ndev = 0;
-	spmv_mi355x_device_count(&ndev);
-	if (ndev < 1)
-	{
-		set_error("trsv_create: no HIP device available: this engine has no CPU fallback");
-		return 1;
-	}
-	if (device < 0)
-		HIP_TRY(hipGetDevice(&device));
-	if (device >= ndev)
-	{
-		set_error("trsv_create: device %d out of range (%d devices)", device, ndev);
-		return 1;
-	}
-	HIP_TRY(hipSetDevice(device));
-	TrsvAnalysis an;
-	trsv_analysis(uplo, n, row_ptr, col_idx, chain_rows, an);
-	spmv_mi355x_trsv * H = new spmv_mi355x_trsv();
-	H->uplo = uplo;
-	H->diag = diag;
-	H->precision = precision;
-	H->f32 = f32;
-	H->device = device;
-	H->n = n;
-	H->levels = an.levels;
-	H->max_level_rows = an.max_level_rows;
-	H->chain_rows = an.chain_rows;
-	H->plan = an.plan;
-	if (f32 ? trsv_build<float>(H, an, row_ptr, col_idx, values) : trsv_build<double>(H, an, row_ptr, col_idx, values))
-	{
-		trsv_free(H);
-		return 1;
-	}
-	*out = H;
+	if (block_rows_out)
+		*block_rows_out = T->block_rows;
+	if (blocks_out)
+		*blocks_out = T->blocks;
+	if (max_block_levels_out)
+		*max_block_levels_out = T->block_rows ? T->levels : 0;
+	if (nnz_dropped_out)
+		*nnz_dropped_out = T->nnz_dropped;
 	return 0;
 }
 
@@ -443,7 +588,7 @@ spmv_mi355x_trsv_solve_device_async(spmv_mi355x_trsv * T, const void * b_dev, vo
 		set_error("trsv_solve: NULL argument (%s%s%s )", !T ? " T" : "", T && !b_dev ? " b" : "", T && !x_dev ? " x" : "");
 		return 1;
 	}
-	if (T->plan.empty())
+	if (T->block_rows ? T->n == 0 : T->plan.empty())
 		return 0;
 	int cur = -1;
 	HIP_TRY(hipGetDevice(&cur));
@@ -451,6 +596,8 @@ spmv_mi355x_trsv_solve_device_async(spmv_mi355x_trsv * T, const void * b_dev, vo
 		HIP_TRY(hipSetDevice(T->device));
 	hipStream_t st = (hipStream_t) hip_stream;
 	const bool unit = T->diag == SPMV_MI355X_DIAG_UNIT;
+	if (T->block_rows)
+		return launch_trsv_blocked(T->f32, unit, T->arr, T->blocks, T->threads, T->block_rows, T->n, b_dev, x_dev, st);
 	for (const TrsvStep & s : T->plan)
 		s.chain ? launch_trsv_chain(T->f32, unit, T->arr, s, b_dev, x_dev, st) : launch_trsv_level(T->f32, unit, T->arr, s, b_dev, x_dev, st);
 	HIP_TRY(hipGetLastError());
@@ -495,11 +642,11 @@ spmv_mi355x_trsv_info(const spmv_mi355x_trsv * T, long * n_out, long * nnz_kept_
 	if (levels_out)
 		*levels_out = T->levels;
 	if (launches_out)
-		*launches_out = (long) T->plan.size();
+		*launches_out = T->block_rows ? (T->n > 0 ? 1 : 0) : (long) T->plan.size();
 	if (max_level_rows_out)
 		*max_level_rows_out = T->max_level_rows;
 	if (chain_rows_out)
-		*chain_rows_out = T->chain_rows;
+		*chain_rows_out = T->block_rows ? 0 : T->chain_rows;
 	return 0;
 }
 

@@ -9,7 +9,16 @@
 // contiguous, a long row pads its own slice only, and a level of one row stores that row without padding. len[p] is the row's own
 // entry count: the kernels stop there, padding is never read. diag[p] is the stored diagonal of row perm[p] in the handle's
 // precision (absent under DIAG_UNIT); it is divided by, never inverted.
+//
+// THE BLOCKED FORM (spmv_mi355x_trsv_create_blocked). The rows are cut into contiguous blocks of block_rows rows, the kept entries
+// that couple two blocks are dropped, and every block has its own levels. The layout is the one above with the positions ordered by
+// (block, level within the block, row): the levels are numbered through all blocks in that order, block b owns the levels
+// block_level[b] .. block_level[b + 1] - 1, and since a slice never straddles a level it never straddles a block either. col holds
+// the column WITHIN the block (j - b * block_rows): the one kernel of this form keeps its block's part of x in LDS and indexes it
+// with the stored column.
 #pragma once
+
+#include <vector>
 
 #include "common.hpp"
 
@@ -20,6 +29,9 @@ constexpr int TRSV_LEVEL_BLOCK = 256;     // threads per workgroup of the level 
 constexpr int TRSV_CHAIN_BLOCK_MAX = 1024;
 constexpr int TRSV_CHAIN_ROWS_DEFAULT = 256;      // profiles/r16_trsv.txt: 256 <= 64 < 1024 << 4096 on both large workloads
 constexpr int TRSV_CHAIN_ROWS_MAX = 65536;
+constexpr int TRSV_BLOCK_ROWS_DEFAULT = 4096;     // NOT from a sweep yet: profiles/r18_trsv_blocked.txt says what was measured
+constexpr int TRSV_BLOCK_ROWS_MAX = 16384;        // 16384 fp64 values = 128 KiB of the 160 KiB of LDS a workgroup may declare
+constexpr int TRSV_BLOCKED_THREADS_MAX = 1024;
 
 struct TrsvArrays {
 	const void * val;                 // values in the handle's precision, slice by slice
@@ -30,6 +42,7 @@ struct TrsvArrays {
 	const void * diag;                // n, by position; nullptr under DIAG_UNIT
 	const int * level_ptr;            // levels + 1
 	const int * level_slice;          // levels + 1
+	const int * block_level;          // blocked handles: blocks + 1; else nullptr
 };
 
 // one launch of the plan
@@ -43,5 +56,27 @@ struct TrsvStep {
 // b and x may be the same vector (b[i] is read by the one lane that writes x[i])
 int launch_trsv_level(bool f32, bool unit, const TrsvArrays & a, const TrsvStep & s, const void * b, void * x, hipStream_t st);
 int launch_trsv_chain(bool f32, bool unit, const TrsvArrays & a, const TrsvStep & s, const void * b, void * x, hipStream_t st);
+// the whole solve of a blocked handle: `blocks` workgroups of `threads` threads, block_rows values of x in LDS each
+int launch_trsv_blocked(bool f32, bool unit, const TrsvArrays & a, long blocks, int threads, long block_rows, long n, const void * b,
+		void * x, hipStream_t st);
+
+}  // namespace spmv
+
+struct spmv_mi355x_trsv {
+	int uplo = 0, diag = 0, precision = 0, device = 0;
+	bool f32 = false;
+	long n = 0, nnz_kept = 0, levels = 0, max_level_rows = 0;
+	int chain_rows = 0;
+	std::vector<spmv::TrsvStep> plan;     // global handles
+	// blocked handles (block_rows > 0): one launch, no plan; levels = the most levels of any block
+	long block_rows = 0, blocks = 0, nnz_dropped = 0;
+	int threads = 0;
+	spmv::TrsvArrays arr = {};
+	void * owned[9] = {};                 // the device arrays behind arr
+	void * d_b = nullptr, * d_x = nullptr;     // the vectors of the host-buffer solve, allocated at its first call
+	double mem_footprint = 0;
+};
+
+namespace spmv {
 
 }  // namespace spmv

@@ -64,6 +64,7 @@ SYMBOLS = [
     "spmv_mi355x_update_values_prepare_transposed", "spmv_mi355x_update_values_count",
     "spmv_mi355x_trsv_analyze", "spmv_mi355x_trsv_create", "spmv_mi355x_trsv_destroy", "spmv_mi355x_trsv_solve_device_async",
     "spmv_mi355x_trsv_solve", "spmv_mi355x_trsv_info", "spmv_mi355x_trsv_mem_footprint", "spmv_mi355x_time_trsv_device",
+    "spmv_mi355x_trsv_analyze_blocked", "spmv_mi355x_trsv_create_blocked", "spmv_mi355x_trsv_block_info", "spmv_mi355x_gmres_tri",
 ]
 
 _lib = None
@@ -103,6 +104,9 @@ def lib():
         L.spmv_mi355x_gmres.restype = C.c_int
         L.spmv_mi355x_gmres.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_long,
                                         C.c_void_p, C.POINTER(GmresInfo)]
+        L.spmv_mi355x_gmres_tri.restype = C.c_int
+        L.spmv_mi355x_gmres_tri.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(TriPrecond), C.c_double, C.c_long,
+                                            C.c_void_p, C.POINTER(GmresInfo)]
         _lib = L
     return _lib
 
@@ -252,21 +256,48 @@ def trsv_analyze(row_ptr, col_idx, n, uplo, chain_rows=0):
                 chain_rows=used.value)
 
 
+def trsv_analyze_blocked(row_ptr, col_idx, n, uplo, block_rows=0):
+    """What a blocked TriangularSolve derives from the pattern, on the host (spmv_mi355x_trsv_analyze_blocked): dict(level_of_row,
+    blocks, max_block_levels, max_level_rows, nnz_dropped, block_rows), level_of_row being the level of each row within its block and
+    block_rows the size used (the default when 0 was passed)."""
+    row_ptr = np.ascontiguousarray(row_ptr, np.int32)
+    col_idx = np.ascontiguousarray(col_idx, np.int32)
+    lv = C.POINTER(C.c_int32)()
+    blocks, levels, widest, dropped, used = C.c_long(), C.c_long(), C.c_long(), C.c_long(), C.c_long()
+    _check(lib().spmv_mi355x_trsv_analyze_blocked(C.c_int(_UPLO[uplo]), C.c_long(n), _p(row_ptr), _p(col_idx), C.c_long(block_rows),
+                                                  C.byref(lv), C.byref(blocks), C.byref(levels), C.byref(widest), C.byref(dropped),
+                                                  C.byref(used)))
+    level_of_row = np.ctypeslib.as_array(lv, shape=(max(n, 1),))[:n].copy()
+    lib().spmv_mi355x_free(lv)
+    return dict(level_of_row=level_of_row, blocks=blocks.value, max_block_levels=levels.value, max_level_rows=widest.value,
+                nnz_dropped=dropped.value, block_rows=used.value)
+
+
 class TriangularSolve:
     """T x = b for one triangle of a square CSR matrix (include/spmv_mi355x.h "sparse triangular solve"): uplo "lower" keeps the
     entries with column <= row, "upper" those with column >= row; diag "stored" divides by the stored diagonal, "unit" takes 1 and
-    ignores what is stored there. Bit-identical to the sequential loop whatever the plan."""
+    ignores what is stored there. Bit-identical to the sequential loop whatever the plan. block_rows = None gives the global handle;
+    0 (the default size) or a size > 0 gives the blocked form, which drops the entries that couple different blocks of block_rows
+    rows and solves what is left in one launch (spmv_mi355x_trsv_create_blocked)."""
 
-    def __init__(self, row_ptr, col_idx, values, n, uplo="lower", diag="stored", dtype=np.float64, chain_rows=0, device=-1):
+    def __init__(self, row_ptr, col_idx, values, n, uplo="lower", diag="stored", dtype=np.float64, chain_rows=0, device=-1,
+                 block_rows=None):
+        if block_rows is not None and chain_rows != 0:
+            raise ValueError("chain_rows belongs to the global plan: it cannot be combined with block_rows")
         row_ptr = np.ascontiguousarray(row_ptr, np.int32)
         col_idx = np.ascontiguousarray(col_idx, np.int32)
         values = np.ascontiguousarray(values, np.float64)
         self.dtype = np.dtype(dtype)
         self.n = int(n)
         self.h = C.c_void_p()
-        _check(lib().spmv_mi355x_trsv_create(C.byref(self.h), C.c_int(_UPLO[uplo]), C.c_int(_DIAG[diag]),
-                                             F64 if self.dtype == np.float64 else F32, C.c_long(n), _p(row_ptr), _p(col_idx), _p(values),
-                                             C.c_int(chain_rows), C.c_int(device)))
+        if block_rows is None:
+            _check(lib().spmv_mi355x_trsv_create(C.byref(self.h), C.c_int(_UPLO[uplo]), C.c_int(_DIAG[diag]),
+                                                 F64 if self.dtype == np.float64 else F32, C.c_long(n), _p(row_ptr), _p(col_idx),
+                                                 _p(values), C.c_int(chain_rows), C.c_int(device)))
+        else:
+            _check(lib().spmv_mi355x_trsv_create_blocked(C.byref(self.h), C.c_int(_UPLO[uplo]), C.c_int(_DIAG[diag]),
+                                                         F64 if self.dtype == np.float64 else F32, C.c_long(n), _p(row_ptr),
+                                                         _p(col_idx), _p(values), C.c_long(block_rows), C.c_int(device)))
         self.mem_footprint = lib().spmv_mi355x_trsv_mem_footprint(self.h)
 
     @property
@@ -277,6 +308,12 @@ class TriangularSolve:
                                            C.byref(chain)))
         return dict(n=n.value, nnz_kept=kept.value, levels=levels.value, launches=launches.value, max_level_rows=widest.value,
                     chain_rows=chain.value)
+
+    def block_info(self):
+        """dict(block_rows, blocks, max_block_levels, nnz_dropped) of spmv_mi355x_trsv_block_info; all 0 for a global handle"""
+        rows, blocks, levels, dropped = C.c_long(), C.c_long(), C.c_long(), C.c_long()
+        _check(lib().spmv_mi355x_trsv_block_info(self.h, C.byref(rows), C.byref(blocks), C.byref(levels), C.byref(dropped)))
+        return dict(block_rows=rows.value, blocks=blocks.value, max_block_levels=levels.value, nnz_dropped=dropped.value)
 
     def solve(self, b):
         """x of T x = b for a host vector b of n values (spmv_mi355x_trsv_solve; blocking)"""
@@ -335,6 +372,11 @@ class GmresInfo(C.Structure):
     _fields_ = [("struct_size", C.c_uint), ("iterations", C.c_long), ("stop", C.c_int), ("restarts", C.c_long), ("rnorm", C.c_double),
                 ("rnorm0", C.c_double), ("prnorm", C.c_double), ("xnorm", C.c_double), ("spmv_calls", C.c_long),
                 ("seconds", C.c_double)]
+
+
+class TriPrecond(C.Structure):
+    """spmv_mi355x_tri_precond (include/spmv_mi355x.h)"""
+    _fields_ = [("struct_size", C.c_uint), ("first", C.c_void_p), ("scale_host", C.c_void_p), ("second", C.c_void_p)]
 
 
 SPMV_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p)
@@ -734,14 +776,28 @@ class Matrix:
         out["history"] = hist[:info.iterations] if history else None
         return out
 
-    def gmres(self, b, restart=30, minv=None, tol=1e-12, max_iterations=1000, history=True):
+    def gmres(self, b, restart=30, minv=None, tol=1e-12, max_iterations=1000, history=True, precond=None):
         """A x = b by restarted GMRES(restart) for any square matrix (spmv_mi355x_gmres): a dict of the spmv_mi355x_gmres_info fields
         plus x (rows values) and history (|g| after each inner step, shape (iterations,), or None). `minv`, when given, is the inverse
         of a diagonal right preconditioner: rows values, every one finite and > 0 (checked by the library, like `restart` and the
-        shape of the handle)."""
+        shape of the handle). `precond` = (first, scale, second) instead applies second^-1 (scale * (first^-1 v)) (spmv_mi355x_gmres_tri):
+        first / second are TriangularSolve handles or None, scale an array of rows values or None."""
         b = np.ascontiguousarray(b, self.dtype)
         if b.shape != (self.m,):
             raise ValueError(f"b must have {self.m} values, got {b.shape}")
+        if precond is not None and minv is not None:
+            raise ValueError("minv and precond are two forms of the one right preconditioner: give one of them")
+        if precond is not None:
+            first, scale, second = precond
+            for T in (first, second):
+                if T is not None and not isinstance(T, TriangularSolve):
+                    raise ValueError("precond = (first, scale, second): first and second are TriangularSolve handles or None")
+            if scale is not None:
+                scale = np.ascontiguousarray(scale, self.dtype)
+                if scale.shape != (self.m,):
+                    raise ValueError(f"the scale of precond must have {self.m} values, got {scale.shape}")
+            M = TriPrecond(C.sizeof(TriPrecond), None if first is None else first.h, None if scale is None else _p(scale),
+                           None if second is None else second.h)
         if minv is not None:
             minv = np.ascontiguousarray(minv, self.dtype)
             if minv.shape != (self.m,):
@@ -750,8 +806,12 @@ class Matrix:
         hist = np.zeros(max(max_iterations, 1), np.float64) if history else None
         info = GmresInfo()
         info.struct_size = C.sizeof(GmresInfo)
-        _check(lib().spmv_mi355x_gmres(self.h, _p(b), _p(x), restart, None if minv is None else _p(minv), tol, max_iterations,
-                                       _p(hist) if history else None, C.byref(info)))
+        if precond is not None:
+            _check(lib().spmv_mi355x_gmres_tri(self.h, _p(b), _p(x), restart, C.byref(M), tol, max_iterations,
+                                               _p(hist) if history else None, C.byref(info)))
+        else:
+            _check(lib().spmv_mi355x_gmres(self.h, _p(b), _p(x), restart, None if minv is None else _p(minv), tol, max_iterations,
+                                           _p(hist) if history else None, C.byref(info)))
         out = {k: getattr(info, k) for k, _ in GmresInfo._fields_ if k != "struct_size"}
         out["x"] = x[:self.m]
         out["history"] = hist[:info.iterations] if history else None

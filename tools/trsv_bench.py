@@ -9,10 +9,16 @@ alternating window by window, it times
   trsv:   time_device of one TriangularSolve handle per chain_rows value, `reps` back-to-back solves under HIP events, reps
           calibrated so that a leg lasts about --leg-ms.
 The medians over the windows are reported with their spreads, and the ratio solve / floor.
+With --block-rows the blocked form (spmv_mi355x_trsv_create_blocked) of the same triangle is timed beside them, one handle per block
+size, in the same process and the same alternating windows: per size the blocks, the most levels of a block, the share of the
+triangle's off-diagonal entries that the blocks drop, ms, the ratio to the floor and the ratio to the global plan of the same run
+(the first --chain-rows value). A blocked handle solves a different, easier system: the ratio says what the launch plan costs, what
+the dropped entries cost a solver is tools/gmres_bench.py's question.
 
     python tools/trsv_bench.py                                       # cant, nlpkkt240, stencil160, fp64
     python tools/trsv_bench.py --runs cant:f64,cant:f32,stencil40:f64 --windows 7 --chain-rows 64,256,1024,4096
     python tools/trsv_bench.py --runs nlpkkt240:f64 --scale 0.25
+    python tools/trsv_bench.py --runs cant:f64,cant:f32,stencil160:f64,nlpkkt240:f64 --chain-rows 256 --block-rows 1024,2048,4096,8192,16384
 One JSON line per run and a table at the end.
 """
 import argparse
@@ -77,6 +83,10 @@ def run(E, torch, name, rp, ci, va, n, dts, data, args):
         t0 = time.perf_counter()
         handles[c] = E.TriangularSolve(rp, ci, va, n, "lower", "stored" if stored else "unit", np_dtype, chain_rows=c)
         create_s[c] = time.perf_counter() - t0
+    for B in args.block_rows:                             # keyed ("b", B): the blocked handles ride in the same windows
+        t0 = time.perf_counter()
+        handles[("b", B)] = E.TriangularSolve(rp, ci, va, n, "lower", "stored" if stored else "unit", np_dtype, block_rows=B)
+        create_s[("b", B)] = time.perf_counter() - t0
     infos = {c: T.info for c, T in handles.items()}
     reps = {}
     for c, T in handles.items():                          # the first solve warms up, the second calibrates
@@ -97,9 +107,22 @@ def run(E, torch, name, rp, ci, va, n, dts, data, args):
     rec = dict(workload=name, dtype=dts, data=data, n=int(n), nnz_kept=int(first["nnz_kept"]), diag="stored" if stored else "unit",
                levels=int(first["levels"]), max_level_rows=int(first["max_level_rows"]), floor_format=M.format_name,
                spmv_ms=round(float(np.median(legs["spmv"])), 5), spmv_spread=[round(min(legs["spmv"]), 5), round(max(legs["spmv"]), 5)],
-               windows=args.windows, triangle_seconds=round(t_tri, 2), sweep=[])
+               windows=args.windows, triangle_seconds=round(t_tri, 2), sweep=[], blocked=[])
+    global_ms = float(np.median(legs[args.chain_rows[0]]))
+    off_diagonal = int(first["nnz_kept"]) - (n if stored else 0)
     for c, T in handles.items():
         ts = legs[c]
+        if isinstance(c, tuple):
+            blk = T.block_info()
+            rec["blocked"].append(dict(block_rows=int(blk["block_rows"]), blocks=int(blk["blocks"]),
+                                       max_block_levels=int(blk["max_block_levels"]), max_level_rows=int(infos[c]["max_level_rows"]),
+                                       dropped_share=round(blk["nnz_dropped"] / max(off_diagonal, 1), 4), reps=reps[c],
+                                       ms=round(float(np.median(ts)), 5), spread=[round(min(ts), 5), round(max(ts), 5)],
+                                       over_floor=round(float(np.median(ts)) / rec["spmv_ms"], 2),
+                                       over_global=round(float(np.median(ts)) / global_ms, 4), create_seconds=round(create_s[c], 2),
+                                       mem_footprint=int(T.mem_footprint)))
+            T.close()
+            continue
         rec["sweep"].append(dict(chain_rows=int(infos[c]["chain_rows"]), launches=int(infos[c]["launches"]), reps=reps[c],
                                  ms=round(float(np.median(ts)), 5), spread=[round(min(ts), 5), round(max(ts), 5)],
                                  over_floor=round(float(np.median(ts)) / rec["spmv_ms"], 2), create_seconds=round(create_s[c], 2),
@@ -115,6 +138,7 @@ def main():
     ap.add_argument("--runs", default="cant:f64,nlpkkt240:f64,stencil160:f64", help="workload|stencil<N>:f64|f32,...")
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--chain-rows", default="64,256,1024,4096", help="the thresholds to sweep, first = the one the header line reports")
+    ap.add_argument("--block-rows", default="", help="block sizes of the blocked form to time beside the plans, e.g. 1024,2048,4096,8192,16384")
     ap.add_argument("--reps", type=int, default=20, help="SpMV launches per timed floor leg")
     ap.add_argument("--leg-ms", type=float, default=40.0, help="solves per timed leg: as many as last about this long (3 .. 200)")
     ap.add_argument("--scale", type=float, default=1.0, help="shrink the workload twins")
@@ -122,6 +146,7 @@ def main():
     if args.windows < 5:
         ap.error("--windows: at least 5")
     args.chain_rows = [int(c) for c in args.chain_rows.split(",")]
+    args.block_rows = [int(c) for c in args.block_rows.split(",") if c]
     os.environ.setdefault("OMP_NUM_THREADS", "16")
     import torch
     if not torch.cuda.is_available():
@@ -152,6 +177,14 @@ def main():
                     f"{r['spmv_ms']:9.4f}") if k == 0 else " " * 65
             print(f"{head} | {s['chain_rows']:10d} {s['launches']:8d} {s['ms']:9.4f} {s['spread'][0]:9.4f} ..{s['spread'][1]:8.4f} "
                   f"{s['over_floor']:8.2f}")
+    if args.block_rows:
+        print(f"{'workload':11s} {'dtype':5s} | {'block_rows':>10s} {'blocks':>7s} {'levels':>7s} {'widest':>7s} {'dropped':>8s} {'trsv ms':>9s} "
+              f"{'spread':>19s} {'/ floor':>8s} {'/ global':>9s}")
+        for r in rows:
+            for s in r["blocked"]:
+                print(f"{r['workload']:11s} {r['dtype']:5s} | {s['block_rows']:10d} {s['blocks']:7d} {s['max_block_levels']:7d} "
+                      f"{s['max_level_rows']:7d} {100 * s['dropped_share']:7.2f}% {s['ms']:9.4f} {s['spread'][0]:9.4f} ..{s['spread'][1]:8.4f} "
+                      f"{s['over_floor']:8.2f} {s['over_global']:9.4f}")
 
 
 if __name__ == "__main__":

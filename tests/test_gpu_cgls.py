@@ -8,7 +8,8 @@ computed once per (shape, damp) and are read-only.
 Test matrices: every row has min(6, n) entries at distinct random columns, uniform in (-0.5, 0.5); then A[i % m, i % n] += 4 for
 i < max(m, n). cond(A) <= 1.7 at every shape used (asserted below), and the restatement reaches |s| <= 1e-12 |s0| in <= 21
 iterations. Shapes: the smallest that exercise the solver's grid, nb = max(ceil(m / 1024), ceil(n / 1024)) blocks striding over
-vectors of both lengths (tall 3 and 2, wide 1 and 3, one row past a block, below a block, and 1).
+vectors of both lengths (tall 3 and 2, wide 1 and 3, one row past a block, below a block, and 1). A grid of 257 blocks of which 255
+have no element of the short vectors: test_gpu_solver_sizes.py.
 
 Bounds, where the issue behind this file left a scale open:
   * |x - x*| / |x*| <= kappa^2 * tol with kappa^2 taken as 3 (|(A^t A + damp)^-1| * |s|): 3e-12 (fp64, tol 1e-12), 3e-5 (fp32, 1e-5).
@@ -61,6 +62,30 @@ def np_transpose(rp, ci, va, m, n):
     return rp_t, rows[order].astype(np.int32), np.ascontiguousarray(va[order], np.float64)
 
 
+def restate(A, At, b, damp, tol, max_iterations, dtype):
+    """the recurrences in numpy: vectors in `dtype`, dots and scalars in fp64. A and At are matrices of `dtype`, dense or
+    scipy.sparse (only A @ v and At @ v are taken). Returns (x, history rows (|r|, |s|), |s0|)."""
+    dt = np.dtype(dtype).type
+    dot = lambda v: float(v.astype(np.float64) @ v.astype(np.float64))
+    x, r = np.zeros(A.shape[1], dt), b.astype(dt)
+    s = At @ r
+    p, gamma = s.copy(), dot(s)
+    gamma0, hist = gamma, []
+    for _ in range(max_iterations):
+        q = A @ p
+        alpha = dt(gamma / (dot(q) + damp * dot(p)))
+        x = x + alpha * p
+        r = r - alpha * q
+        s = At @ r - dt(damp) * x
+        gamma_new = dot(s)
+        p = s + dt(gamma_new / gamma) * p
+        gamma = gamma_new
+        hist.append((np.sqrt(dot(r)), np.sqrt(gamma)))
+        if np.sqrt(gamma) <= tol * np.sqrt(gamma0):
+            break
+    return x, np.array(hist), np.sqrt(gamma0)
+
+
 class Problem:
     def __init__(self, m, n):
         rng = np.random.default_rng(1000 * m + n)
@@ -97,29 +122,11 @@ class Problem:
 
     @functools.lru_cache(maxsize=None)
     def restatement(self, dtype, damp, tol, max_iterations=300):
-        """the recurrences in numpy: vectors in `dtype`, dots and scalars in fp64. Returns (x, history rows (|r|, |s|), |s0|)."""
-        dt = np.dtype(dtype).type
-        A = self.D.astype(dt)
-        dot = lambda v: float(v.astype(np.float64) @ v.astype(np.float64))
-        x, r = np.zeros(self.n, dt), self.b.astype(dt)
-        s = A.T @ r
-        p, gamma = s.copy(), dot(s)
-        gamma0, hist = gamma, []
-        for _ in range(max_iterations):
-            q = A @ p
-            alpha = dt(gamma / (dot(q) + damp * dot(p)))
-            x = x + alpha * p
-            r = r - alpha * q
-            s = A.T @ r - dt(damp) * x
-            gamma_new = dot(s)
-            p = s + dt(gamma_new / gamma) * p
-            gamma = gamma_new
-            hist.append((np.sqrt(dot(r)), np.sqrt(gamma)))
-            if np.sqrt(gamma) <= tol * np.sqrt(gamma0):
-                break
-        hist = np.array(hist)
+        """restate() on the dense matrix. Returns (x, history rows (|r|, |s|), |s0|)."""
+        A = self.D.astype(dtype)
+        x, hist, s0 = restate(A, A.T, self.b, damp, tol, max_iterations, dtype)
         hist.setflags(write=False)
-        return x, hist, np.sqrt(gamma0)
+        return x, hist, s0
 
 
 @functools.lru_cache(maxsize=None)

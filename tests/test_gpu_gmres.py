@@ -11,7 +11,8 @@ j != i, an entry uniform in (-1, 1); d = 1.5 for n >= 700 and 2.0 below. Nothing
 for n in {2000, 1025, 700} and restart in {20, 7}: fp64 at tol 1e-12 stops after 104 .. 125 inner steps, past 2 * POLL = 64 (the
 host's run-ahead and its stop on the progress word are exercised), in the middle of a cycle in all but one case (the pending-columns
 path is exercised; nsym(700) with minv at m = 20 stops at step 120, the end of one), after >= 5 restarts at m = 20 and >= 14 at m = 7; fp32 at tol 1e-5 stops after 41 .. 51. Shapes: the smallest that exercise several
-blocks of the vector kernels (1024 rows each), one row past a block, below a block, and 1.
+blocks of the vector kernels (1024 rows each), one row past a block, below a block, and 1 (the second trip of the partial sums and
+the cap of the grid need 262 145 and 1 049 601 unknowns: test_gpu_solver_sizes.py).
 
 The preconditioner under test: minv_i = (1 / |d_ii|) (1 + 0.5 sin(i)). It is a RIGHT preconditioner: the residual stays the true one.
 
@@ -74,13 +75,14 @@ def nsym(n):
     return D
 
 
-def restate(A, b, m, minv, tol, max_iterations, dtype):
-    """the header's recurrences in numpy: vectors in `dtype`, dots and scalars in fp64. A is a dense matrix of `dtype`.
+def restate(A, b, m, minv, tol, max_iterations, dtype, dot=None):
+    """the header's recurrences in numpy: vectors in `dtype`, dots and scalars in fp64. A is a matrix of `dtype`, dense or
+    scipy.sparse (only A @ v is taken). `dot` replaces the fp64 dot product (test_solver_size_cases.py: a dot that loses rows).
     Returns (x, history, stop, restarts)."""
     dt = np.dtype(dtype).type
     n = len(b)
     b = b.astype(dt)
-    dot = lambda u, v: float(u.astype(np.float64) @ v.astype(np.float64))
+    dot = dot or (lambda u, v: float(u.astype(np.float64) @ v.astype(np.float64)))
     M = (lambda v: v) if minv is None else (lambda v, d=minv.astype(dt): d * v)
     x = np.zeros(n, dt)
     beta0 = np.sqrt(dot(b, b))

@@ -10,7 +10,8 @@ zero diagonal entries (pcg and pbicgstab refuse the matrix) and n2 negative eige
 cond(A - shift I) <= 20 for the shifts used (asserted below from the eigenvalues of A), and the restatement reaches
 phibar <= 1e-12 beta1 in at most 125 iterations: past 2 * POLL = 64, so the host's run-ahead and its stop on the progress word are
 exercised. Shapes: the smallest that exercise several blocks of the vector kernels (1024 rows each), one row past a block, below a
-block, and 1.
+block, and 1 (the second trip of the partial sums and the cap of the grid need 262 145 and 1 049 601 unknowns:
+test_gpu_solver_sizes.py).
 
 The preconditioner under test: minv_i = (1 / |d_ii|, or 1 where d_ii = 0) * (1 + 0.5 sin(i)), within [0.125, 1.5].
 
@@ -80,13 +81,14 @@ def kkt(n1, n2):
     return D
 
 
-def restate(A, b, shift, minv, tol, max_iterations, dtype):
-    """the header's recurrences in numpy: vectors in `dtype`, dots and scalars in fp64. A is a dense matrix of `dtype`.
+def restate(A, b, shift, minv, tol, max_iterations, dtype, dot=None):
+    """the header's recurrences in numpy: vectors in `dtype`, dots and scalars in fp64. A is a matrix of `dtype`, dense or
+    scipy.sparse (only A @ v is taken). `dot` replaces the fp64 dot product (test_solver_size_cases.py: a dot that loses rows).
     Returns (x, history, beta1, stop)."""
     dt = np.dtype(dtype).type
     n = len(b)
     b = b.astype(dt)
-    dot = lambda u, v: float(u.astype(np.float64) @ v.astype(np.float64))
+    dot = dot or (lambda u, v: float(u.astype(np.float64) @ v.astype(np.float64)))
     M = (lambda v: v) if minv is None else (lambda v, d=minv.astype(dt): d * v)
     x, r1, y = np.zeros(n, dt), b, M(b)
     beta1 = dot(b, y)

@@ -583,8 +583,8 @@ int  spmv_mi355x_gmres(spmv_mi355x_matrix * A, const void * b_host, void * x_out
 
 /* ---- sparse triangular solve: level-scheduled L x = b and U x = b handles --------------------------------------------------------- */
 /* What applies Gauss-Seidel / SSOR (A's own triangles) and ILU(0) / IC(0) (the caller's factors): T x = b for one triangle T of a
- * square n x n matrix given as CSR (csrc/trsv.hip, csrc/kernels_trsv.hip). spmv_mi355x_gmres_tri (below) is the one
- * solver that calls it.
+ * square n x n matrix given as CSR (csrc/trsv.hip, csrc/kernels_trsv.hip). spmv_mi355x_gmres_tri and
+ * spmv_mi355x_pcg_tri (below) are the solvers that call it.
  * WHICH TRIANGLE. uplo = SPMV_MI355X_LOWER keeps the entries with column <= row, SPMV_MI355X_UPPER those with column >= row; entries
  * on the other side are ignored, so one CSR array holding both ILU factors (unit L below, U on and above the diagonal) serves two
  * handles, and the CSR of A serves both halves of a Gauss-Seidel sweep. diag = SPMV_MI355X_DIAG_STORED reads d_i from row i;
@@ -628,7 +628,8 @@ int  spmv_mi355x_gmres(spmv_mi355x_matrix * A, const void * b_host, void * x_out
  *     trsv_analyze makes the checks 1 to 3 that apply to its arguments. The solve entries refuse a NULL handle and, for n > 0, a NULL
  *     vector; trsv_info a NULL handle; trsv_mem_footprint(NULL) is 0; trsv_destroy(NULL) is rc 0.
  *   - NOT CHECKABLE: that b_dev / x_dev hold n values on the right device.
- *   - NOT BUILT: wiring into pcg / pbicgstab / minres (gmres has it: spmv_mi355x_gmres_tri); the ILU(0) / IC(0) factorization itself; a solve
+ *   - NOT BUILT: wiring into pbicgstab / minres (gmres and CG have it: spmv_mi355x_gmres_tri, spmv_mi355x_pcg_tri); the ILU(0) /
+ *     IC(0) factorization itself; a solve
  *     with T^t over T's layout; multi-RHS; update_values for a trsv handle; GPU-side analysis; graph capture; a row-partitioned form;
  *     a "sync-free" variant in which workgroups wait for each other inside one launch. */
 typedef struct spmv_mi355x_trsv spmv_mi355x_trsv;   /* opaque */
@@ -697,7 +698,8 @@ int  spmv_mi355x_trsv_block_info(const spmv_mi355x_trsv * T, long * block_rows_o
  *     2. first, scale_host and second are all NULL (the message points to spmv_mi355x_gmres);
  *     3. a handle's n differs from rows(), or its precision or its device from A's (first before second);
  *     4. a scale entry that is not finite or is zero (the message names the first such index).
- *   - NOT BUILT: the same for pcg / pbicgstab / minres, left preconditioning, a preconditioner that changes between steps. */
+ *   - NOT BUILT: the same for pbicgstab / minres (CG has it: spmv_mi355x_pcg_tri below), left preconditioning, a preconditioner
+ *     that changes between steps. */
 typedef struct {
 	unsigned struct_size;         /* in: sizeof(spmv_mi355x_tri_precond) */
 	spmv_mi355x_trsv * first;     /* may be NULL */
@@ -707,6 +709,70 @@ typedef struct {
 int  spmv_mi355x_gmres_tri(spmv_mi355x_matrix * A, const void * b_host, void * x_out_host, int restart,
 		const spmv_mi355x_tri_precond * M, double tol, long max_iterations,
 		double * history_out /* may be NULL: max_iterations doubles */, spmv_mi355x_gmres_info * info /* may be NULL */);
+
+/* ---- CG preconditioned by triangular solves (SGS / IC(0)), tol-based ------------------------------------------------------------- */
+/* A x = b from x0 = 0 for a square SYMMETRIC POSITIVE DEFINITE matrix by preconditioned conjugate gradients, the CG member of the
+ * tol-based family (cgls, minres, gmres: `tol`, stop codes, explicit norms in info, frozen on the device at the stop, any handle),
+ * with M^-1 v = second^-1 ( scale o ( first^-1 v ) ) given as the spmv_mi355x_tri_precond that spmv_mi355x_gmres_tri takes: each of
+ * the three parts may be NULL, the two solves are spmv_mi355x_trsv handles of any kind, blocked or global, and scale is a vector
+ * (csrc/solver_pcg_tri.hip). M == NULL, or a struct with three NULL parts, means z = r: no z vector is stored, no
+ * extra launch is issued and r.z is r.r, the plain CG. spmv_mi355x_pcg (above) is another solver: the reference harness's
+ * preconditioned_cg() to the letter, Jacobi only, no tol. The recurrences, every scalar and every dot fp64, vectors in the handle's
+ * precision:
+ *     x = 0; r = b; rnorm0 = |b|                     (0: stop 3, x = 0, every norm 0; not finite: stop 4)
+ *     z = M^-1 r; p = z; rz = r.z                    (not finite or <= 0: stop 4, 0 iterations, x = 0)
+ *     loop k = 1, 2, ... while k <= max_iterations:
+ *         q = A p; pq = p.q                          (not finite or <= 0: stop 4; x, iterations, history as before this body)
+ *         alpha = rz / pq; x += alpha p; r -= alpha q; rr = r.r; history[k-1] = sqrt(rr); iterations = k
+ *         if tol > 0 and sqrt(rr) <= tol rnorm0: stop 1;  else if rr == 0: stop 5
+ *         z = M^-1 r; rz' = r.z                      (not finite or <= 0: stop 4; this body's x is kept)
+ *         beta = rz' / rz; rz = rz'; p = z + beta p
+ * Two ways to fill M:
+ *     SGS of an SPD A:        first = LOWER / STORED handle of A's CSR, scale = diag(A), second = UPPER / STORED handle of A's CSR
+ *     the caller's IC(0):     first = LOWER / STORED handle of L, no scale, second = UPPER / STORED handle of the CSR of L^t
+ *   - per iteration: 1 SpMV, the launches of the two solves and at most one scale kernel, and 4 vector kernels (3 without M).
+ *   - b_host, x_out_host and M->scale_host: rows() values of the handle's precision.
+ *   - any format and layout serves (the solver only calls spmv_mi355x_spmv_device_async): value_storage = 1, 7-byte values and
+ *     symmetric_input = 1 included; on handles whose SpMV is deterministic the whole solve is, bit for bit. The solver's vectors
+ *     are plain allocations. M = (NULL, ones, NULL) returns the bits of M = NULL.
+ *   - the handles of M are used, not owned: they must outlive the call, and one handle serves one solve at a time.
+ *   - tol == 0 is legal and means "never stop on the tolerance". max_iterations == 0 returns x = 0, stop 2 and rnorm = rnorm0.
+ *   - history_out (may be NULL): max_iterations doubles; entry k = |r| of the recurrence after body k + 1; entries >=
+ *     info->iterations stay 0.
+ *   - after a stop the solve is frozen on the device: x, iterations and the history are those of the body at which the rule fired,
+ *     however far the host had run ahead (at most 64 bodies).
+ *   - rc 1 with a last_error that names pcg_tri, caller buffers and info untouched, in this order, the first three before any
+ *     device is touched and before the NULL checks:
+ *     1. info->struct_size < 8;
+ *     2. tol negative or not finite;
+ *     3. max_iterations < 0;
+ *     4. A, b or x_out is NULL;
+ *     5. rows() != cols() (the message gives both; this also refuses row-block handles);
+ *     6. M is not NULL and M->struct_size < sizeof(spmv_mi355x_tri_precond);
+ *     7. a handle's n differs from rows(), or its precision or its device from A's (first before second);
+ *     8. a scale entry that is not finite or is zero (the message names the first such index). A negative one is legal and ends
+ *        in stop 4.
+ *   - NOT CHECKABLE: that A and M are symmetric positive definite. Blocked handles give a symmetric M only when both use the same
+ *     block_rows (a global handle counts as block_rows >= n). Stop 4 catches only what the two inner products reveal.
+ *   - NOT BUILT: multi-RHS, the row-partitioned form, device-pointer b / x, a non-zero x0. */
+typedef struct {
+	unsigned struct_size;   /* in: sizeof(spmv_mi355x_pcg_tri_info) */
+	long   iterations;      /* completed loop bodies */
+	int    stop;            /* 1 = |r| <= tol * |b| (tol > 0)
+	                           2 = max_iterations reached
+	                           3 = b == 0: x = 0, 0 iterations
+	                           4 = breakdown: |b|, r.z or p.q not finite, or r.z or p.q <= 0
+	                           5 = r == 0 exactly */
+	double rnorm;           /* |b - A x_out|, EXPLICIT (one SpMV after the loop) */
+	double rnorm0;          /* |b| */
+	double prnorm;          /* |r| of the recurrence at the stop */
+	double xnorm;           /* |x_out| */
+	long   spmv_calls;      /* every launch, the host's run-ahead and the explicit one included */
+	double seconds;
+} spmv_mi355x_pcg_tri_info;
+int  spmv_mi355x_pcg_tri(spmv_mi355x_matrix * A, const void * b_host, void * x_out_host,
+		const spmv_mi355x_tri_precond * M /* may be NULL */, double tol, long max_iterations,
+		double * history_out /* may be NULL: max_iterations doubles */, spmv_mi355x_pcg_tri_info * info /* may be NULL */);
 
 /* Row-partitioned (multi-GPU) form of the same two solvers: one process per GPU owns the row block [row_offset,
  * row_offset + m_local) of A, b and x. The solver keeps every vector device-resident and local; the two things that cross

@@ -42,8 +42,8 @@
 //
 // THE TRIANGULAR PRECONDITIONER (spmv_mi355x_gmres_tri, MODE = GMRES_TRI). M v = second^-1 (scale o (first^-1 v)), each part
 // optional, the two solves being spmv_mi355x_trsv handles of any kind. The finish and restart kernels write v only, as without a
-// preconditioner; behind them the host enqueues on the same stream: first (v -> z), gmres_scale_kernel on z, second in place on z,
-// and then the SpMV of z. At a cycle end gmres_combine_kernel writes u to z, the same steps run on it and gmres_add_kernel does
+// preconditioner; behind them the host enqueues on the same stream (tri_precond.hpp, shared with solver_pcg_tri.hip): first
+// (v -> z), tri_scale_kernel on z, second in place on z, and then the SpMV of z. At a cycle end gmres_combine_kernel writes u to z, the same steps run on it and gmres_add_kernel does
 // x += z; when the scale is the last part (no second) it is multiplied in there, the form the minv path has, which also keeps
 // precond = (NULL, s, NULL) bit for bit the solve with minv = s.
 // Why the freeze survives: the triangular solves and the scale kernel know nothing of `done` and run however far the host is ahead,
@@ -61,6 +61,7 @@
 
 #include "common.hpp"
 #include "solvers_common.hpp"
+#include "tri_precond.hpp"
 #include "trsv.hpp"
 #include "../../include/spmv_mi355x.h"
 
@@ -311,15 +312,6 @@ gmres_apply_kernel(const int * __restrict__ napply, const T * __restrict__ V, co
 	}
 }
 
-// GMRES_TRI: out = scale o in, elementwise; `in` may be `out`
-template <typename T>
-__global__ __launch_bounds__(VB) void
-gmres_scale_kernel(const T * __restrict__ scale, const T * in, T * out, long n)
-{
-	GRID_STRIDE(e, n)
-		out[e] = scale[e] * in[e];
-}
-
 // GMRES_TRI: u = y_0 v_0 + ... + y_{p-1} v_{p-1}, p = napply, into the scratch vector
 template <typename T>
 __global__ __launch_bounds__(VB) void
@@ -502,20 +494,7 @@ gmres_solve(spmv_mi355x_matrix * A, const void * b_host, void * x_host, int m, c
 	long s = 0;
 	// GMRES_TRI: z = M in, part by part; `in` may be z. With defer_scale a scale that is M's last part is left to the caller.
 	auto precond = [&](const T * in, bool defer_scale) {
-		const T * src = in;
-		if (first)
-		{
-			ABI_TRY(spmv_mi355x_trsv_solve_device_async(first, src, z, stream));
-			src = z;
-		}
-		if (minv && !(defer_scale && !second))
-		{
-			hipLaunchKernelGGL((gmres_scale_kernel<T>), grid, block, 0, stream, minv, src, z, n);
-			src = z;
-		}
-		if (second)
-			ABI_TRY(spmv_mi355x_trsv_solve_device_async(second, src, z, stream));
-		return 0;
+		return tri_precond_enqueue<T>(first, minv, second, in, z, n, defer_scale, grid, stream);
 	};
 	auto cycle_end = [&]() {
 		hipLaunchKernelGGL(gmres_solve_y_kernel, one, block, 0, stream, st + (s & 1), R, g, m, y, napply);
@@ -624,18 +603,6 @@ gmres_bad_minv(const void * minv_host, long n)
 	return -1;
 }
 
-// the first entry of a scale that is not finite or is zero, or -1
-template <typename T>
-static long
-gmres_bad_scale(const void * scale_host, long n)
-{
-	const T * d = (const T *) scale_host;
-	for (long i = 0; i < n; i++)
-		if (d[i] == 0 || !std::isfinite(d[i]))
-			return i;
-	return -1;
-}
-
 // what both entries check first, in the order of the header: the scalars, the NULL pointers, the shape
 static int
 gmres_check_common(const char * what, spmv_mi355x_matrix * A, const void * b_host, void * x_out_host, int restart, double tol,
@@ -709,50 +676,22 @@ spmv_mi355x_gmres_tri(spmv_mi355x_matrix * A, const void * b_host, void * x_out_
 	using namespace spmv;
 	if (gmres_check_common("gmres_tri", A, b_host, x_out_host, restart, tol, max_iterations, info))
 		return 1;
-	if (!M || M->struct_size < sizeof(spmv_mi355x_tri_precond))
+	if (!M)
 	{
-		if (!M)
-			set_error("gmres_tri: NULL preconditioner M");
-		else
-			set_error("gmres_tri: M->struct_size = %u is smaller than sizeof(spmv_mi355x_tri_precond) = %zu", M->struct_size,
-					sizeof(spmv_mi355x_tri_precond));
+		set_error("gmres_tri: NULL preconditioner M");
 		return 1;
 	}
+	if (!tri_precond_size_ok("gmres_tri", M))
+		return 1;
 	if (!M->first && !M->scale_host && !M->second)
 	{
 		set_error("gmres_tri: M has no first, no scale and no second: for a solve without a preconditioner call spmv_mi355x_gmres");
 		return 1;
 	}
-	const long n = spmv_mi355x_cols(A);
 	const int precision = spmv_mi355x_precision(A), device = spmv_mi355x_device(A);
 	const bool f32 = precision == SPMV_MI355X_F32;
-	const spmv_mi355x_trsv * parts[2] = {M->first, M->second};
-	for (int k = 0; k < 2; k++)
-	{
-		const spmv_mi355x_trsv * T = parts[k];
-		const char * name = k ? "second" : "first";
-		if (!T)
-			continue;
-		if (T->n != n)
-			set_error("gmres_tri: M->%s is a triangular solve of %ld rows, the matrix has %ld", name, T->n, n);
-		else if (T->precision != precision)
-			set_error("gmres_tri: M->%s has precision %d, the matrix %d: both must be the same", name, T->precision, precision);
-		else if (T->device != device)
-			set_error("gmres_tri: M->%s lives on device %d, the matrix on device %d", name, T->device, device);
-		else
-			continue;
+	if (!tri_precond_parts_ok("gmres_tri", M, spmv_mi355x_cols(A), precision, device))
 		return 1;
-	}
-	if (M->scale_host)
-	{
-		const long bad = f32 ? gmres_bad_scale<float>(M->scale_host, n) : gmres_bad_scale<double>(M->scale_host, n);
-		if (bad >= 0)
-		{
-			set_error("gmres_tri: scale[%ld] = %g: every entry of the scale must be finite and non-zero", bad,
-					f32 ? (double) ((const float *) M->scale_host)[bad] : ((const double *) M->scale_host)[bad]);
-			return 1;
-		}
-	}
 	HIP_TRY(hipSetDevice(device));
 	if (f32)
 		return gmres_solve<float, GMRES_TRI>(A, b_host, x_out_host, restart, M->scale_host, tol, max_iterations, history_out, info,

@@ -1,0 +1,413 @@
+// Device-resident preconditioned CG of the tol-based family (MINRES, GMRES, CGLS): A x = b from x0 = 0 for a square SYMMETRIC
+// POSITIVE DEFINITE matrix over one handle of A, preconditioned by M^-1 v = second^-1 (scale o (first^-1 v)), a
+// spmv_mi355x_tri_precond with each part optional (the SGS of A, the caller's IC(0), a Jacobi scale, nothing).
+//
+// The recurrences, every scalar and every dot fp64, vectors in the handle's precision:
+//   x = 0; r = b; rnorm0 = |b|                     (0: stop 3, x = 0, every norm 0; not finite: stop 4)
+//   z = M^-1 r; p = z; rz = r.z                    (not finite or <= 0: stop 4, 0 iterations, x = 0)
+//   loop k = 1, 2, ... while k <= max_iterations:
+//       q = A p; pq = p.q                          (not finite or <= 0: stop 4; x, iterations, history as before this body)
+//       alpha = rz / pq; x += alpha p; r -= alpha q; rr = r.r; history[k-1] = sqrt(rr); iterations = k
+//       if tol > 0 and sqrt(rr) <= tol rnorm0: stop 1;  else if rr == 0: stop 5
+//       z = M^-1 r; rz' = r.z                      (not finite or <= 0: stop 4; this body's x is kept)
+//       beta = rz' / rz; rz = rz'; p = z + beta p
+// Built like solver_minres.hip: the state ping-pongs between two slots, dots are two-stage and deterministic (every block of the
+// consumer re-sums the partials in the same order), a device `done` flag predicates every later vector kernel off, and the host
+// loop is ProgressGate of solvers_common.hpp.
+// Per iteration: 1 SpMV + M's own launches + 4 vector launches, 3 without a preconditioner
+//   q = A p | pcg_tri_dot (partials of p.q) | pcg_tri_update (alpha; x += alpha p; r -= alpha q; partials of r.r) |
+//   [ z = M^-1 r: first, tri_scale_kernel, second (tri_precond.hpp) | pcg_tri_dot (partials of r.z) ] |
+//   pcg_tri_direction (the verdicts, beta, the next state, the history row, the progress word; p = z + beta p).
+// Without a preconditioner z is r: no z is stored, nothing is launched for it and rz' is the rr of pcg_tri_update, so
+// precond = (NULL, ones, NULL) returns the bits of precond = NULL.
+// A cut with fewer launches would have to form a dot product and consume it in the same launch, which needs a grid-wide barrier:
+// p.q must be complete before alpha, r.r (and r.z) before beta. Three reductions with their consumers are four launches.
+// Stored vectors, n values each: b, x, r, p, q, and z when M has a part; the scale when given.
+//
+// BREAKDOWN of p.q. pcg_tri_update reaches the verdict in every block from the same partials and touches no vector;
+// pcg_tri_direction, the only kernel that writes the state, re-sums the same partials, reaches the same verdict and records
+// done / stop 4 with k unchanged.
+//
+// THE FREEZE. The SpMV, the triangular solves and the scale kernel know nothing of `done` and run however far the host is ahead;
+// what they write is q and z, scratch that only the predicated kernels read. x, r, p, the state and the history are written only
+// by kernels that return at once when `done` is set. So after a stop nothing the caller sees moves.
+
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "common.hpp"
+#include "solvers_common.hpp"
+#include "tri_precond.hpp"
+#include "trsv.hpp"
+#include "../../include/spmv_mi355x.h"
+
+namespace spmv {
+
+struct PcgTriState {
+	double rnorm0;                // |b|
+	double rz;                    // r.z of the running direction
+	double rr;                    // r.r of the recurrence after body k
+	long k;                       // completed loop bodies
+	int done;                     // a stop rule fired: every later vector kernel is predicated off
+	int stop;                     // 0 while running, else 1 / 3 / 4 / 5 of spmv_mi355x_pcg_tri_info.stop (2 is the host's: never done)
+};
+
+// one producer kernel per slot
+enum { T_BB = 0, T_PQ, T_RR, T_RZ, T_ER, T_XX, PCG_TRI_SLOTS };
+
+// a positive finite number: what p.q and r.z must be
+__device__ __forceinline__ bool
+pcg_tri_positive(double v)
+{
+	return v > 0 && v < INFINITY;
+}
+
+// r = b; x = 0; without a preconditioner also p = b; partial BB = b.b
+template <typename T, bool PRE>
+__global__ __launch_bounds__(VB) void
+pcg_tri_start_kernel(const T * __restrict__ b, T * __restrict__ r, T * __restrict__ p, T * __restrict__ x, long n,
+		double * __restrict__ part)
+{
+	double bb = 0;
+	GRID_STRIDE(i, n)
+	{
+		const T bi = b[i];
+		r[i] = bi;
+		x[i] = 0;
+		if (!PRE)
+			p[i] = bi;
+		bb = fma((double) bi, (double) bi, bb);
+	}
+	store_partial(part, T_BB, bb);
+}
+
+// 1 block. b.b == 0: x = 0 is the solution (stop 3); not finite: stop 4. Without a preconditioner rz = b.b.
+__global__ __launch_bounds__(VB) void
+pcg_tri_init_state_kernel(PcgTriState * __restrict__ st_p, int nb, const double * __restrict__ part)
+{
+	const double bb = sum_partials(part, T_BB, nb);
+	if (threadIdx.x == 0)
+	{
+		PcgTriState st;
+		const bool bad = !(bb >= 0) || !(bb < INFINITY);
+		st.rnorm0 = bad ? 0 : sqrt(bb);
+		st.rz = bb;
+		st.rr = bb;
+		st.k = 0;
+		st.done = bad || bb == 0;
+		st.stop = bad ? 4 : bb == 0 ? 3 : 0;
+		st_p[0] = st;
+		st_p[1] = st;
+	}
+}
+
+// partial of u.v into `slot`: p.q, and r.z under a preconditioner
+template <typename T>
+__global__ __launch_bounds__(VB) void
+pcg_tri_dot_kernel(const PcgTriState * __restrict__ st_p, const T * __restrict__ u, const T * __restrict__ v, long n,
+		double * __restrict__ part, int slot)
+{
+	if (st_p->done)
+		return;
+	double s = 0;
+	GRID_STRIDE(i, n)
+		s = fma((double) u[i], (double) v[i], s);
+	store_partial(part, slot, s);
+}
+
+// With a preconditioner, the start: rz = r.z from the partials, p = z. Block 0 writes the next state (stop 4: rz not positive).
+template <typename T>
+__global__ __launch_bounds__(VB) void
+pcg_tri_begin_kernel(const PcgTriState * __restrict__ st_p, PcgTriState * __restrict__ st_next, T * __restrict__ p,
+		const T * __restrict__ z, long n, int nb, const double * __restrict__ part)
+{
+	const PcgTriState st = *st_p;
+	if (st.done)
+	{
+		if (blockIdx.x == 0 && threadIdx.x == 0)
+			*st_next = st;
+		return;
+	}
+	const double rz = sum_partials(part, T_RZ, nb);
+	const bool ok = pcg_tri_positive(rz);
+	if (ok)
+		GRID_STRIDE(i, n)
+			p[i] = z[i];
+	if (blockIdx.x == 0 && threadIdx.x == 0)
+	{
+		PcgTriState nx = st;
+		nx.rz = rz;
+		nx.stop = ok ? 0 : 4;
+		nx.done = !ok;
+		*st_next = nx;
+	}
+}
+
+// alpha = rz / (p.q) identically in every block; x += alpha p; r -= alpha q; partial RR = r.r. p.q not positive: nothing is touched.
+template <typename T>
+__global__ __launch_bounds__(VB) void
+pcg_tri_update_kernel(const PcgTriState * __restrict__ st_p, T * __restrict__ x, T * __restrict__ r, const T * __restrict__ p,
+		const T * __restrict__ q, long n, int nb, double * __restrict__ part)
+{
+	const PcgTriState st = *st_p;
+	if (st.done)
+		return;
+	const double pq = sum_partials(part, T_PQ, nb);
+	if (!pcg_tri_positive(pq))
+		return;
+	const T alpha = (T) (st.rz / pq);
+	double rr = 0;
+	GRID_STRIDE(i, n)
+	{
+		x[i] = x[i] + alpha * p[i];
+		const T ri = r[i] - alpha * q[i];
+		r[i] = ri;
+		rr = fma((double) ri, (double) ri, rr);
+	}
+	store_partial(part, T_RR, rr);
+}
+
+// The verdicts of the body, identically in every block; p = z + beta p (z = r without a preconditioner) when the solve goes on.
+// Block 0 writes the next state, the history row and the progress word.
+template <typename T, bool PRE>
+__global__ __launch_bounds__(VB) void
+pcg_tri_direction_kernel(const PcgTriState * __restrict__ st_p, PcgTriState * __restrict__ st_next, T * __restrict__ p,
+		const T * __restrict__ z, long n, int nb, double tol, const double * __restrict__ part, double * __restrict__ history,
+		long it, volatile long * host_progress)
+{
+	const PcgTriState st = *st_p;
+	const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
+	if (st.done)
+	{
+		if (lead)
+		{
+			*st_next = st;
+			post_progress(host_progress, it + 1, st.k);
+		}
+		return;
+	}
+	PcgTriState nx = st;
+	if (!pcg_tri_positive(sum_partials(part, T_PQ, nb)))
+	{
+		if (lead)
+		{
+			nx.done = 1;                              // x, k and the history of the last good body
+			nx.stop = 4;
+			*st_next = nx;
+			post_progress(host_progress, it + 1, nx.k);
+		}
+		return;
+	}
+	const double rr = sum_partials(part, T_RR, nb);
+	const double rnorm = sqrt(rr);
+	nx.rr = rr;
+	nx.k = st.k + 1;
+	if (tol > 0 && rnorm <= tol * st.rnorm0)
+		nx.stop = 1;
+	else if (rr == 0)
+		nx.stop = 5;
+	else
+	{
+		const double rz = PRE ? sum_partials(part, T_RZ, nb) : rr;
+		if (!pcg_tri_positive(rz))
+			nx.stop = 4;                              // this body's x is kept
+		else
+		{
+			const T beta = (T) (rz / st.rz);
+			nx.rz = rz;
+			GRID_STRIDE(i, n)
+				p[i] = z[i] + beta * p[i];
+		}
+	}
+	if (lead)
+	{
+		if (history)
+			history[st.k] = rnorm;
+		nx.done = nx.stop != 0;
+		*st_next = nx;
+		post_progress(host_progress, it + 1, nx.done ? nx.k : -1);
+	}
+}
+
+// the tail's explicit residual: q = b - q (q = A x); partials ER = |b - A x|^2 and XX = |x|^2
+template <typename T>
+__global__ __launch_bounds__(VB) void
+pcg_tri_final_kernel(const T * __restrict__ b, T * __restrict__ q, const T * __restrict__ x, long n, double * __restrict__ part)
+{
+	double rr = 0, xx = 0;
+	GRID_STRIDE(i, n)
+	{
+		const T xi = x[i];
+		const T ri = b[i] - q[i];
+		q[i] = ri;
+		rr = fma((double) ri, (double) ri, rr);
+		xx = fma((double) xi, (double) xi, xx);
+	}
+	store_partial(part, T_ER, rr);
+	store_partial(part, T_XX, xx);
+}
+
+// ------------------------------------------------------------------------------------------------ host side
+
+// PRE: M has at least one part. scale_host: the scale of M or NULL.
+template <typename T, bool PRE>
+static int
+pcg_tri_solve(spmv_mi355x_matrix * A, const void * b_host, void * x_host, spmv_mi355x_trsv * first, const void * scale_host,
+		spmv_mi355x_trsv * second, double tol, long max_iterations, double * history_host, spmv_mi355x_pcg_tri_info * info)
+{
+	const auto t_start = std::chrono::steady_clock::now();
+	const long n = spmv_mi355x_rows(A);
+	hipStream_t stream = nullptr;
+	ProgressGate gate;                // outlives buf, whose hipFree waits for the kernels that post to it
+	DeviceBuffers buf;
+	const size_t nbytes = (size_t) n * sizeof(T);
+
+	// plain allocations, the SpMV output included: see solve() in solvers.hip
+	T * b, * x, * r, * p, * q, * z = nullptr, * scale = nullptr;
+	for (T ** v : {&b, &x, &r, &p, &q})
+		ABI_TRY(buf.alloc(v, nbytes));
+	if (PRE)
+		ABI_TRY(buf.alloc(&z, nbytes));
+	if (scale_host)
+		ABI_TRY(buf.alloc(&scale, nbytes));
+	double * part, * history = nullptr;
+	PcgTriState * st;
+	ABI_TRY(buf.alloc(&part, sizeof(double) * PCG_TRI_SLOTS * MAX_PART));
+	ABI_TRY(buf.alloc(&st, 2 * sizeof(PcgTriState)));
+	const size_t hist_bytes = sizeof(double) * (size_t) max_iterations;
+	if (history_host && max_iterations > 0)
+	{
+		ABI_TRY(buf.alloc(&history, hist_bytes));
+		HIP_TRY(hipMemsetAsync(history, 0, hist_bytes, stream));
+	}
+	ABI_TRY(gate.init());
+
+	HIP_TRY(hipMemcpyAsync(b, b_host, nbytes, hipMemcpyHostToDevice, stream));
+	if (scale)
+		HIP_TRY(hipMemcpyAsync(scale, scale_host, nbytes, hipMemcpyHostToDevice, stream));
+	HIP_TRY(hipMemsetAsync(part, 0, sizeof(double) * PCG_TRI_SLOTS * MAX_PART, stream));
+
+	const int nb = solver_blocks(n);
+	const dim3 grid(nb), block(VB), one(1);
+	long spmv_calls = 0;
+	auto spmv = [&](const T * in, T * out) {
+		spmv_calls++;
+		return spmv_mi355x_spmv_device_async(A, in, out, 0, stream);
+	};
+	// the state of the moment is st[s & 1]; every transition (the start under a preconditioner, a loop body) reads it, writes the
+	// other slot and adds 1
+	long s = 0;
+	// z = M^-1 r and the partials of r.z
+	auto precondition = [&]() {
+		ABI_TRY(tri_precond_enqueue<T>(first, scale, second, r, z, n, false, grid, stream));
+		hipLaunchKernelGGL((pcg_tri_dot_kernel<T>), grid, block, 0, stream, st + (s & 1), r, z, n, part, (int) T_RZ);
+		return 0;
+	};
+
+	hipLaunchKernelGGL((pcg_tri_start_kernel<T, PRE>), grid, block, 0, stream, b, r, p, x, n, part);
+	hipLaunchKernelGGL(pcg_tri_init_state_kernel, one, block, 0, stream, st, nb, part);
+	if (PRE)
+	{
+		ABI_TRY(precondition());
+		hipLaunchKernelGGL((pcg_tri_begin_kernel<T>), grid, block, 0, stream, st + (s & 1), st + ((s + 1) & 1), p, z, n, nb, part);
+		s++;
+	}
+	HIP_TRY(hipGetLastError());
+
+	long it = 0;
+	for (; it < max_iterations; it++)
+	{
+		bool stop;
+		ABI_TRY(gate.wait(it, "pcg_tri", stream, &stop));
+		if (stop)
+			break;
+		PcgTriState * cur = st + (s & 1), * nxt = st + ((s + 1) & 1);
+		ABI_TRY(spmv(p, q));
+		hipLaunchKernelGGL((pcg_tri_dot_kernel<T>), grid, block, 0, stream, cur, p, q, n, part, (int) T_PQ);
+		hipLaunchKernelGGL((pcg_tri_update_kernel<T>), grid, block, 0, stream, cur, x, r, p, q, n, nb, part);
+		if (PRE)
+			ABI_TRY(precondition());
+		hipLaunchKernelGGL((pcg_tri_direction_kernel<T, PRE>), grid, block, 0, stream, cur, nxt, p, PRE ? z : r, n, nb, tol, part,
+				history, it, gate.dev);
+		s++;
+	}
+	HIP_TRY(hipGetLastError());
+
+	// the explicit norms of the returned x: |b - A x| and |x|. q is free now; x stays as it froze.
+	PcgTriState * fin = st + (s & 1);
+	ABI_TRY(spmv(x, q));
+	hipLaunchKernelGGL((pcg_tri_final_kernel<T>), grid, block, 0, stream, b, q, x, n, part);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(x_host, x, nbytes, hipMemcpyDeviceToHost, stream));
+	PcgTriState st_host;
+	std::vector<double> part_host((size_t) PCG_TRI_SLOTS * MAX_PART);
+	HIP_TRY(hipMemcpyAsync(&st_host, fin, sizeof(PcgTriState), hipMemcpyDeviceToHost, stream));
+	HIP_TRY(hipMemcpyAsync(part_host.data(), part, sizeof(double) * PCG_TRI_SLOTS * MAX_PART, hipMemcpyDeviceToHost, stream));
+	if (history)
+		HIP_TRY(hipMemcpyAsync(history_host, history, hist_bytes, hipMemcpyDeviceToHost, stream));
+	HIP_TRY(hipStreamSynchronize(stream));
+	if (info)
+	{
+		auto norm_of = [&](int slot) { return std::sqrt(host_sum(part_host.data(), (size_t) slot * MAX_PART, nb)); };
+		spmv_mi355x_pcg_tri_info out;
+		memset(&out, 0, sizeof(out));
+		out.iterations = st_host.k;
+		out.stop = st_host.done ? st_host.stop : 2;
+		out.rnorm = norm_of(T_ER);
+		out.rnorm0 = norm_of(T_BB);
+		out.prnorm = std::sqrt(st_host.rr);
+		out.xnorm = norm_of(T_XX);
+		out.spmv_calls = spmv_calls;
+		out.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
+		put_info(info, info->struct_size, out);
+	}
+	return 0;
+}
+
+}  // namespace spmv
+
+extern "C" int
+spmv_mi355x_pcg_tri(spmv_mi355x_matrix * A, const void * b_host, void * x_out_host, const spmv_mi355x_tri_precond * M, double tol,
+		long max_iterations, double * history_out, spmv_mi355x_pcg_tri_info * info)
+{
+	using namespace spmv;
+	// the checks that need no handle come first, so each can be met (and tested) on its own
+	if (!info_size_ok("pcg_tri", info))
+		return 1;
+	if (!(tol >= 0) || !std::isfinite(tol))
+	{
+		set_error("pcg_tri: tol must be finite and >= 0 (got %g)", tol);
+		return 1;
+	}
+	if (max_iterations < 0)
+	{
+		set_error("pcg_tri: max_iterations < 0");
+		return 1;
+	}
+	if (!A || !b_host || !x_out_host)
+	{
+		set_error("pcg_tri: NULL argument (%s%s%s )", !A ? " A" : "", !b_host ? " b" : "", !x_out_host ? " x_out" : "");
+		return 1;
+	}
+	const long m = spmv_mi355x_rows(A), n = spmv_mi355x_cols(A);
+	if (m != n)
+	{
+		set_error("pcg_tri: the matrix must be square and symmetric positive definite: the handle is %ld x %ld (a row block of a "
+				"larger matrix is not served)", m, n);
+		return 1;
+	}
+	const int precision = spmv_mi355x_precision(A), device = spmv_mi355x_device(A);
+	if (M && (!tri_precond_size_ok("pcg_tri", M) || !tri_precond_parts_ok("pcg_tri", M, n, precision, device)))
+		return 1;
+	spmv_mi355x_trsv * first = M ? M->first : nullptr, * second = M ? M->second : nullptr;
+	const void * scale = M ? M->scale_host : nullptr;
+	HIP_TRY(hipSetDevice(device));
+	const bool pre = first || scale || second;
+	if (precision == SPMV_MI355X_F32)
+		return pre ? pcg_tri_solve<float, true>(A, b_host, x_out_host, first, scale, second, tol, max_iterations, history_out, info)
+		           : pcg_tri_solve<float, false>(A, b_host, x_out_host, nullptr, nullptr, nullptr, tol, max_iterations, history_out, info);
+	return pre ? pcg_tri_solve<double, true>(A, b_host, x_out_host, first, scale, second, tol, max_iterations, history_out, info)
+	           : pcg_tri_solve<double, false>(A, b_host, x_out_host, nullptr, nullptr, nullptr, tol, max_iterations, history_out, info);
+}

@@ -65,6 +65,7 @@ SYMBOLS = [
     "spmv_mi355x_trsv_analyze", "spmv_mi355x_trsv_create", "spmv_mi355x_trsv_destroy", "spmv_mi355x_trsv_solve_device_async",
     "spmv_mi355x_trsv_solve", "spmv_mi355x_trsv_info", "spmv_mi355x_trsv_mem_footprint", "spmv_mi355x_time_trsv_device",
     "spmv_mi355x_trsv_analyze_blocked", "spmv_mi355x_trsv_create_blocked", "spmv_mi355x_trsv_block_info", "spmv_mi355x_gmres_tri",
+    "spmv_mi355x_pcg_tri",
 ]
 
 _lib = None
@@ -107,6 +108,9 @@ def lib():
         L.spmv_mi355x_gmres_tri.restype = C.c_int
         L.spmv_mi355x_gmres_tri.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(TriPrecond), C.c_double, C.c_long,
                                             C.c_void_p, C.POINTER(GmresInfo)]
+        L.spmv_mi355x_pcg_tri.restype = C.c_int
+        L.spmv_mi355x_pcg_tri.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TriPrecond), C.c_double, C.c_long,
+                                          C.c_void_p, C.POINTER(PcgTriInfo)]
         _lib = L
     return _lib
 
@@ -347,6 +351,40 @@ class TriangularSolve:
             pass
 
 
+def sgs_precond(row_ptr, col_idx, values, n, dtype=np.float64, block_rows=None, **trsv_opts):
+    """(first, scale, second) of the symmetric Gauss-Seidel preconditioner of A for Matrix.gmres(precond=...) and Matrix.pcg_tri:
+    the LOWER / STORED and UPPER / STORED TriangularSolve handles of A's CSR with diag(A) as the scale between them. block_rows =
+    None gives global handles, otherwise blocked handles with that size on both sides (the same size keeps M symmetric). The
+    diagonal is the first stored entry of row i with column i, the solvers' rule. trsv_opts go to both TriangularSolve handles
+    (chain_rows, device). The caller closes the two handles."""
+    row_ptr = np.ascontiguousarray(row_ptr, np.int32)
+    col_idx = np.ascontiguousarray(col_idx, np.int32)
+    values = np.ascontiguousarray(values, np.float64)
+    rows = np.repeat(np.arange(n), np.diff(row_ptr))
+    at = np.nonzero(col_idx == rows)[0]
+    at = at[np.unique(rows[at], return_index=True)[1]]               # the first of every row
+    if at.size != n:
+        raise ValueError(f"sgs_precond: {n - at.size} rows store no diagonal entry")
+    first = TriangularSolve(row_ptr, col_idx, values, n, uplo="lower", dtype=dtype, block_rows=block_rows, **trsv_opts)
+    second = TriangularSolve(row_ptr, col_idx, values, n, uplo="upper", dtype=dtype, block_rows=block_rows, **trsv_opts)
+    return first, values[at].astype(dtype), second
+
+
+def _tri_precond(precond, m, dtype):
+    """the TriPrecond of precond = (first, scale, second), and the scale array it points into (to be kept alive)"""
+    first, scale, second = precond
+    for T in (first, second):
+        if T is not None and not isinstance(T, TriangularSolve):
+            raise ValueError("precond = (first, scale, second): first and second are TriangularSolve handles or None")
+    if scale is not None:
+        scale = np.ascontiguousarray(scale, dtype)
+        if scale.shape != (m,):
+            raise ValueError(f"the scale of precond must have {m} values, got {scale.shape}")
+    M = TriPrecond(C.sizeof(TriPrecond), None if first is None else first.h, None if scale is None else _p(scale),
+                   None if second is None else second.h)
+    return M, scale
+
+
 class SolverInfo(C.Structure):
     """spmv_mi355x_solver_info (include/spmv_mi355x.h)"""
     _fields_ = [("struct_size", C.c_uint), ("iterations", C.c_long), ("error", C.c_double), ("error_best", C.c_double),
@@ -372,6 +410,12 @@ class GmresInfo(C.Structure):
     _fields_ = [("struct_size", C.c_uint), ("iterations", C.c_long), ("stop", C.c_int), ("restarts", C.c_long), ("rnorm", C.c_double),
                 ("rnorm0", C.c_double), ("prnorm", C.c_double), ("xnorm", C.c_double), ("spmv_calls", C.c_long),
                 ("seconds", C.c_double)]
+
+
+class PcgTriInfo(C.Structure):
+    """spmv_mi355x_pcg_tri_info (include/spmv_mi355x.h)"""
+    _fields_ = [("struct_size", C.c_uint), ("iterations", C.c_long), ("stop", C.c_int), ("rnorm", C.c_double), ("rnorm0", C.c_double),
+                ("prnorm", C.c_double), ("xnorm", C.c_double), ("spmv_calls", C.c_long), ("seconds", C.c_double)]
 
 
 class TriPrecond(C.Structure):
@@ -788,16 +832,7 @@ class Matrix:
         if precond is not None and minv is not None:
             raise ValueError("minv and precond are two forms of the one right preconditioner: give one of them")
         if precond is not None:
-            first, scale, second = precond
-            for T in (first, second):
-                if T is not None and not isinstance(T, TriangularSolve):
-                    raise ValueError("precond = (first, scale, second): first and second are TriangularSolve handles or None")
-            if scale is not None:
-                scale = np.ascontiguousarray(scale, self.dtype)
-                if scale.shape != (self.m,):
-                    raise ValueError(f"the scale of precond must have {self.m} values, got {scale.shape}")
-            M = TriPrecond(C.sizeof(TriPrecond), None if first is None else first.h, None if scale is None else _p(scale),
-                           None if second is None else second.h)
+            M, scale = _tri_precond(precond, self.m, self.dtype)
         if minv is not None:
             minv = np.ascontiguousarray(minv, self.dtype)
             if minv.shape != (self.m,):
@@ -813,6 +848,29 @@ class Matrix:
             _check(lib().spmv_mi355x_gmres(self.h, _p(b), _p(x), restart, None if minv is None else _p(minv), tol, max_iterations,
                                            _p(hist) if history else None, C.byref(info)))
         out = {k: getattr(info, k) for k, _ in GmresInfo._fields_ if k != "struct_size"}
+        out["x"] = x[:self.m]
+        out["history"] = hist[:info.iterations] if history else None
+        return out
+
+    def pcg_tri(self, b, precond=None, tol=1e-12, max_iterations=1000, history=True):
+        """A x = b by preconditioned CG for a square symmetric positive definite matrix (spmv_mi355x_pcg_tri): a dict of the
+        spmv_mi355x_pcg_tri_info fields plus x (rows values) and history (|r| of the recurrence after each iteration, shape
+        (iterations,), or None). `precond` = (first, scale, second) applies second^-1 (scale * (first^-1 v)) as M^-1: first / second
+        are TriangularSolve handles or None, scale an array of rows values or None (sgs_precond builds the SGS of A); None is the
+        plain CG."""
+        b = np.ascontiguousarray(b, self.dtype)
+        if b.shape != (self.m,):
+            raise ValueError(f"b must have {self.m} values, got {b.shape}")
+        M = None
+        if precond is not None:
+            M, scale = _tri_precond(precond, self.m, self.dtype)
+        x = np.zeros(max(self.m, 1), self.dtype)
+        hist = np.zeros(max(max_iterations, 1), np.float64) if history else None
+        info = PcgTriInfo()
+        info.struct_size = C.sizeof(PcgTriInfo)
+        _check(lib().spmv_mi355x_pcg_tri(self.h, _p(b), _p(x), None if M is None else C.byref(M), tol, max_iterations,
+                                         _p(hist) if history else None, C.byref(info)))
+        out = {k: getattr(info, k) for k, _ in PcgTriInfo._fields_ if k != "struct_size"}
         out["x"] = x[:self.m]
         out["history"] = hist[:info.iterations] if history else None
         return out

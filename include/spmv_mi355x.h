@@ -774,6 +774,76 @@ int  spmv_mi355x_pcg_tri(spmv_mi355x_matrix * A, const void * b_host, void * x_o
 		const spmv_mi355x_tri_precond * M /* may be NULL */, double tol, long max_iterations,
 		double * history_out /* may be NULL: max_iterations doubles */, spmv_mi355x_pcg_tri_info * info /* may be NULL */);
 
+/* ---- FSAI: a factorized sparse approximate inverse built on the GPU, applied as two SpMVs ---------------------------------------- */
+/* For a square SYMMETRIC POSITIVE DEFINITE A and a lower triangular pattern P the handle holds the sparse lower triangular G on P with
+ * G A G^t ~ I and diag(G A G^t) = 1 (Kolotilina-Yeremin), and applies M^-1 v = G^t (G v): two SpMVs over two ordinary handles, G built
+ * by spmv_mi355x_create and G^t by the same call with opts.transpose = 1. No triangular solve, no level schedule, no ordering between
+ * workgroups (csrc/fsai.hip, csrc/kernels_fsai.hip). Rows of G do not depend on each other.
+ * THE ARITHMETIC, fp64 whatever the handle's precision. Of A only the entries with column <= row are read. For row i with pattern
+ * columns J = (j_1 < ... < j_s = i):
+ *     gather   S[a][b] = A(j_a, j_b) for b <= a, taken from row j_a of A at column j_b; an absent entry is 0, a stored 0 is a 0
+ *     Cholesky for k = 1..s, for a = k..s:  for p = 1..k-1 ascending  S[a][k] = fma(-C[a][p], C[k][p], S[a][k]);
+ *                                           then C[k][k] = sqrt(S[k][k]) and C[a][k] = S[a][k] / C[k][k] (IEEE division)
+ *     solve    C^t g = e_s:  g_s = 1 / C[s][s];  for k = s-1..1:  t = 0; for a = k+1..s ascending t = fma(C[a][k], g_a, t);
+ *                                                                 g_k = -t / C[k][k]
+ * Row i of G is g on the columns J (the textbook g^ / sqrt(g^_s) with S g^ = e_s). Every S[a][k] has its own sequential chain, so
+ * the bits do not depend on how lanes are mapped to elements: tests/fsai_reference.c is the same arithmetic as one loop.
+ * BREAKDOWN: a pivot S[k][k] that is <= 0 or not finite. The whole row then becomes g_i = 1 / sqrt(A(i, i)) with an explicit 0 in every
+ * other entry, and the row is counted in fallback_rows. Nothing aborts.
+ *   - the pattern: pat_row_ptr / pat_col_idx, a CSR whose rows hold strictly ascending columns, all <= the row, the last one the row
+ *     itself, at most SPMV_MI355X_FSAI_MAX_ROW entries each (the packed triangle of a row lives in LDS: 66 KiB at 128). Both NULL =
+ *     the lower triangle of A's own pattern, each row sorted by the library. spmv_mi355x_fsai_pattern (host only, O(work) with a
+ *     marker array) returns the pattern of tril(A~)^power for power 1..3, A~ = the pattern of A's lower triangle with the diagonal
+ *     added: columns ascending, arrays malloc'ed, released with spmv_mi355x_free. It refuses n out of range, power outside 1..3, NULL
+ *     arrays and a bad CSR (create's checks), with the prefix fsai_pattern.
+ *   - stored: G's fp64 values on the host in the pattern's entry order (spmv_mi355x_fsai_values), the two handles (values narrowed as
+ *     create narrows them; format and opts are the caller's, for both) and one scratch vector of n values for G v.
+ *     spmv_mi355x_fsai_matrices lends the two handles: they belong to F and die with it (both NULL when n == 0).
+ *   - fsai_apply_device_async: out = G^t (G in) enqueued on the stream; in == out is legal (G in is in the scratch vector before out is
+ *     written). One apply at a time per handle. fsai_apply is the blocking form on host vectors of the handle's precision.
+ *   - fsai_info: n, nnz of the pattern, max_row = its longest row, fallback_rows, the seconds of the row kernel and of the whole
+ *     setup; fsai_setup_split: the kernel, the download of G and the two creates, in seconds. Any out pointer may be NULL.
+ *   - n == 0 is legal everywhere: no handle is built, apply does nothing.
+ *   - rc 1 with a last_error that starts with "fsai_create:", in this order, all but the last on the host before any device is touched:
+ *     1. the scalars: an unknown precision or format, n < 0 or n >= 2^31 - 1, opts->struct_size not set, and opts that set transpose,
+ *        symmetric_input or a row block / column filter (row_begin, row_end, col_filter_mode); opts->value_storage under create's rule;
+ *     2. NULL pointers: out, row_ptr, col_idx or values of a matrix with entries, a pattern given as one array of the two;
+ *     3. A's pattern, as create checks it: row_ptr from 0 and monotone, columns in [0, n);
+ *     4. a column stored twice in one row of A's lower triangle (which value A(i, j) has would not be defined);
+ *     5. the pattern: pat_row_ptr from 0 and monotone, columns in [0, row], strictly ascending, the last column equal to the row,
+ *        and a row with more than SPMV_MI355X_FSAI_MAX_ROW entries (the message gives the row and its count);
+ *     6. the diagonal of A: the first stored entry with column i must exist, be finite and be > 0 (the message names the first bad row);
+ *     7. the device, and whatever spmv_mi355x_create refuses for the format and opts (its message after the prefix).
+ *   - NOT CHECKABLE: that A is symmetric and positive definite. Only the lower triangle is read; an indefinite A shows, if at all, as
+ *     fallback_rows > 0.
+ *   - NOT BUILT: update_values for an fsai handle (new values of A need a new handle), gmres / minres / pbicgstab wiring, multi-RHS,
+ *     the row-partitioned form, adaptive patterns, a pattern with entries above the diagonal.
+ * spmv_mi355x_pcg_fsai is spmv_mi355x_pcg_tri with z = M^-1 r = fsai_apply_device_async: the same recurrences, kernels, stop codes,
+ * history, spmv_mi355x_pcg_tri_info and freeze (the two SpMVs of an apply write only F's scratch vector and z, scratch that only the
+ * predicated kernels read). info.spmv_calls counts the products with A, not those with G and G^t. Per iteration: 3 SpMVs and 4
+ * vector kernels. rc 1 with a last_error that starts with "pcg_fsai:": first items 1 to 5 of spmv_mi355x_pcg_tri, then F == NULL (the
+ * message points to spmv_mi355x_pcg_tri), then F's n, precision or device differing from A's, in that order. */
+#define SPMV_MI355X_FSAI_MAX_ROW 128
+typedef struct spmv_mi355x_fsai spmv_mi355x_fsai;   /* opaque */
+int  spmv_mi355x_fsai_pattern(long n, const int32_t * row_ptr, const int32_t * col_idx, int power,
+		int32_t ** row_ptr_out, int32_t ** col_idx_out /* malloc'ed; spmv_mi355x_free */);
+int  spmv_mi355x_fsai_create(spmv_mi355x_fsai ** out, int format, int precision, long n,
+		const int32_t * row_ptr, const int32_t * col_idx, const double * values_fp64,
+		const int32_t * pat_row_ptr, const int32_t * pat_col_idx /* both NULL = tril(A) */, const spmv_mi355x_opts * opts /* may be NULL */);
+int  spmv_mi355x_fsai_destroy(spmv_mi355x_fsai * F);
+int  spmv_mi355x_fsai_apply_device_async(spmv_mi355x_fsai * F, const void * in_dev, void * out_dev, void * hip_stream);
+int  spmv_mi355x_fsai_apply(spmv_mi355x_fsai * F, const void * in_host, void * out_host);       /* blocking */
+int  spmv_mi355x_fsai_values(const spmv_mi355x_fsai * F, double * out /* nnz doubles, pattern order */);
+int  spmv_mi355x_fsai_matrices(const spmv_mi355x_fsai * F, spmv_mi355x_matrix ** G_out, spmv_mi355x_matrix ** Gt_out);   /* borrowed */
+int  spmv_mi355x_fsai_info(const spmv_mi355x_fsai * F, long * n_out, long * nnz_out, long * max_row_out, long * fallback_rows_out,
+		double * kernel_seconds_out, double * setup_seconds_out);                                /* any out pointer may be NULL */
+int  spmv_mi355x_fsai_setup_split(const spmv_mi355x_fsai * F, double * kernel_seconds_out, double * download_seconds_out,
+		double * create_g_seconds_out, double * create_gt_seconds_out);                          /* any out pointer may be NULL */
+double spmv_mi355x_fsai_mem_footprint(const spmv_mi355x_fsai * F);    /* the two handles and the scratch vector, bytes */
+int  spmv_mi355x_pcg_fsai(spmv_mi355x_matrix * A, const void * b_host, void * x_out_host, spmv_mi355x_fsai * F, double tol,
+		long max_iterations, double * history_out /* may be NULL: max_iterations doubles */,
+		spmv_mi355x_pcg_tri_info * info /* may be NULL */);
+
 /* Row-partitioned (multi-GPU) form of the same two solvers: one process per GPU owns the row block [row_offset,
  * row_offset + m_local) of A, b and x. The solver keeps every vector device-resident and local; the two things that cross
  * ranks are handed to the caller, who has the communicator (torch.distributed / RCCL in bench-level code):

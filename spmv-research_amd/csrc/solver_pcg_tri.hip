@@ -31,6 +31,11 @@
 // THE FREEZE. The SpMV, the triangular solves and the scale kernel know nothing of `done` and run however far the host is ahead;
 // what they write is q and z, scratch that only the predicated kernels read. x, r, p, the state and the history are written only
 // by kernels that return at once when `done` is set. So after a stop nothing the caller sees moves.
+//
+// TWO ENTRIES, ONE BODY. pcg_tri_solve takes "enqueue z = M^-1 r" as a callable: TriApply (spmv_mi355x_pcg_tri: tri_precond.hpp's
+// three parts) or FsaiApply (spmv_mi355x_pcg_fsai: the two SpMVs G^t (G r) of an fsai handle, fsai.hip). The freeze carries over:
+// the two SpMVs know nothing of `done` either, and what they write is the fsai handle's scratch vector and z. Per iteration of
+// pcg_fsai: 3 SpMVs (A, G, G^t) and the 4 vector launches.
 
 #include <chrono>
 #include <cmath>
@@ -39,6 +44,7 @@
 
 #include "common.hpp"
 #include "solvers_common.hpp"
+#include "fsai.hpp"
 #include "tri_precond.hpp"
 #include "trsv.hpp"
 #include "../../include/spmv_mi355x.h"
@@ -251,11 +257,13 @@ pcg_tri_final_kernel(const T * __restrict__ b, T * __restrict__ q, const T * __r
 
 // ------------------------------------------------------------------------------------------------ host side
 
-// PRE: M has at least one part. scale_host: the scale of M or NULL.
-template <typename T, bool PRE>
+// PRE: there is a preconditioner. scale_host: the scale of M or NULL; the solve keeps its device copy. apply(r, z, scale, n, grid,
+// stream) enqueues z = M^-1 r on the stream and returns 0 or 1 (error set): the triangular parts of pcg_tri, the two SpMVs of
+// pcg_fsai. It is never called without PRE. `what` names the caller in the gate's message.
+template <typename T, bool PRE, typename Apply>
 static int
-pcg_tri_solve(spmv_mi355x_matrix * A, const void * b_host, void * x_host, spmv_mi355x_trsv * first, const void * scale_host,
-		spmv_mi355x_trsv * second, double tol, long max_iterations, double * history_host, spmv_mi355x_pcg_tri_info * info)
+pcg_tri_solve(const char * what, spmv_mi355x_matrix * A, const void * b_host, void * x_host, const void * scale_host, Apply apply,
+		double tol, long max_iterations, double * history_host, spmv_mi355x_pcg_tri_info * info)
 {
 	const auto t_start = std::chrono::steady_clock::now();
 	const long n = spmv_mi355x_rows(A);
@@ -301,7 +309,7 @@ pcg_tri_solve(spmv_mi355x_matrix * A, const void * b_host, void * x_host, spmv_m
 	long s = 0;
 	// z = M^-1 r and the partials of r.z
 	auto precondition = [&]() {
-		ABI_TRY(tri_precond_enqueue<T>(first, scale, second, r, z, n, false, grid, stream));
+		ABI_TRY(apply((const T *) r, z, (const T *) scale, n, grid, stream));
 		hipLaunchKernelGGL((pcg_tri_dot_kernel<T>), grid, block, 0, stream, st + (s & 1), r, z, n, part, (int) T_RZ);
 		return 0;
 	};
@@ -320,7 +328,7 @@ pcg_tri_solve(spmv_mi355x_matrix * A, const void * b_host, void * x_host, spmv_m
 	for (; it < max_iterations; it++)
 	{
 		bool stop;
-		ABI_TRY(gate.wait(it, "pcg_tri", stream, &stop));
+		ABI_TRY(gate.wait(it, what, stream, &stop));
 		if (stop)
 			break;
 		PcgTriState * cur = st + (s & 1), * nxt = st + ((s + 1) & 1);
@@ -366,6 +374,59 @@ pcg_tri_solve(spmv_mi355x_matrix * A, const void * b_host, void * x_host, spmv_m
 	return 0;
 }
 
+// the checks of both entries that need no preconditioner: items 1 to 5 of the header, with the caller's name as the prefix
+static bool
+pcg_tri_arguments_ok(const char * what, spmv_mi355x_matrix * A, const void * b_host, void * x_out_host, double tol, long max_iterations,
+		const spmv_mi355x_pcg_tri_info * info)
+{
+	// the checks that need no handle come first, so each can be met (and tested) on its own
+	if (!info_size_ok(what, info))
+		return false;
+	if (!(tol >= 0) || !std::isfinite(tol))
+	{
+		set_error("%s: tol must be finite and >= 0 (got %g)", what, tol);
+		return false;
+	}
+	if (max_iterations < 0)
+	{
+		set_error("%s: max_iterations < 0", what);
+		return false;
+	}
+	if (!A || !b_host || !x_out_host)
+	{
+		set_error("%s: NULL argument (%s%s%s )", what, !A ? " A" : "", !b_host ? " b" : "", !x_out_host ? " x_out" : "");
+		return false;
+	}
+	const long m = spmv_mi355x_rows(A), n = spmv_mi355x_cols(A);
+	if (m != n)
+	{
+		set_error("%s: the matrix must be square and symmetric positive definite: the handle is %ld x %ld (a row block of a "
+				"larger matrix is not served)", what, m, n);
+		return false;
+	}
+	return true;
+}
+
+// z = M^-1 r of pcg_tri: second^-1 (scale o (first^-1 r)), tri_precond.hpp
+struct TriApply {
+	spmv_mi355x_trsv * first, * second;
+	template <typename T>
+	int operator()(const T * r, T * z, const T * scale, long n, dim3 grid, hipStream_t stream) const
+	{
+		return tri_precond_enqueue<T>(first, scale, second, r, z, n, false, grid, stream);
+	}
+};
+
+// z = M^-1 r of pcg_fsai: G^t (G r). The two SpMVs write the handle's scratch vector and z, nothing else.
+struct FsaiApply {
+	spmv_mi355x_fsai * F;
+	template <typename T>
+	int operator()(const T * r, T * z, const T *, long, dim3, hipStream_t stream) const
+	{
+		return spmv_mi355x_fsai_apply_device_async(F, r, z, stream);
+	}
+};
+
 }  // namespace spmv
 
 extern "C" int
@@ -373,31 +434,9 @@ spmv_mi355x_pcg_tri(spmv_mi355x_matrix * A, const void * b_host, void * x_out_ho
 		long max_iterations, double * history_out, spmv_mi355x_pcg_tri_info * info)
 {
 	using namespace spmv;
-	// the checks that need no handle come first, so each can be met (and tested) on its own
-	if (!info_size_ok("pcg_tri", info))
+	if (!pcg_tri_arguments_ok("pcg_tri", A, b_host, x_out_host, tol, max_iterations, info))
 		return 1;
-	if (!(tol >= 0) || !std::isfinite(tol))
-	{
-		set_error("pcg_tri: tol must be finite and >= 0 (got %g)", tol);
-		return 1;
-	}
-	if (max_iterations < 0)
-	{
-		set_error("pcg_tri: max_iterations < 0");
-		return 1;
-	}
-	if (!A || !b_host || !x_out_host)
-	{
-		set_error("pcg_tri: NULL argument (%s%s%s )", !A ? " A" : "", !b_host ? " b" : "", !x_out_host ? " x_out" : "");
-		return 1;
-	}
-	const long m = spmv_mi355x_rows(A), n = spmv_mi355x_cols(A);
-	if (m != n)
-	{
-		set_error("pcg_tri: the matrix must be square and symmetric positive definite: the handle is %ld x %ld (a row block of a "
-				"larger matrix is not served)", m, n);
-		return 1;
-	}
+	const long n = spmv_mi355x_cols(A);
 	const int precision = spmv_mi355x_precision(A), device = spmv_mi355x_device(A);
 	if (M && (!tri_precond_size_ok("pcg_tri", M) || !tri_precond_parts_ok("pcg_tri", M, n, precision, device)))
 		return 1;
@@ -405,9 +444,39 @@ spmv_mi355x_pcg_tri(spmv_mi355x_matrix * A, const void * b_host, void * x_out_ho
 	const void * scale = M ? M->scale_host : nullptr;
 	HIP_TRY(hipSetDevice(device));
 	const bool pre = first || scale || second;
+	const TriApply apply = {first, second};
 	if (precision == SPMV_MI355X_F32)
-		return pre ? pcg_tri_solve<float, true>(A, b_host, x_out_host, first, scale, second, tol, max_iterations, history_out, info)
-		           : pcg_tri_solve<float, false>(A, b_host, x_out_host, nullptr, nullptr, nullptr, tol, max_iterations, history_out, info);
-	return pre ? pcg_tri_solve<double, true>(A, b_host, x_out_host, first, scale, second, tol, max_iterations, history_out, info)
-	           : pcg_tri_solve<double, false>(A, b_host, x_out_host, nullptr, nullptr, nullptr, tol, max_iterations, history_out, info);
+		return pre ? pcg_tri_solve<float, true>("pcg_tri", A, b_host, x_out_host, scale, apply, tol, max_iterations, history_out, info)
+		           : pcg_tri_solve<float, false>("pcg_tri", A, b_host, x_out_host, nullptr, apply, tol, max_iterations, history_out, info);
+	return pre ? pcg_tri_solve<double, true>("pcg_tri", A, b_host, x_out_host, scale, apply, tol, max_iterations, history_out, info)
+	           : pcg_tri_solve<double, false>("pcg_tri", A, b_host, x_out_host, nullptr, apply, tol, max_iterations, history_out, info);
+}
+
+extern "C" int
+spmv_mi355x_pcg_fsai(spmv_mi355x_matrix * A, const void * b_host, void * x_out_host, spmv_mi355x_fsai * F, double tol,
+		long max_iterations, double * history_out, spmv_mi355x_pcg_tri_info * info)
+{
+	using namespace spmv;
+	if (!pcg_tri_arguments_ok("pcg_fsai", A, b_host, x_out_host, tol, max_iterations, info))
+		return 1;
+	if (!F)
+	{
+		set_error("pcg_fsai: F is NULL: spmv_mi355x_pcg_tri with M = NULL is the solve without a preconditioner");
+		return 1;
+	}
+	const long n = spmv_mi355x_cols(A);
+	const int precision = spmv_mi355x_precision(A), device = spmv_mi355x_device(A);
+	if (F->n != n)
+		set_error("pcg_fsai: F is a preconditioner of %ld rows, the matrix has %ld", F->n, n);
+	else if (F->precision != precision)
+		set_error("pcg_fsai: F has precision %d, the matrix %d: both must be the same", F->precision, precision);
+	else if (F->device != device)
+		set_error("pcg_fsai: F lives on device %d, the matrix on device %d", F->device, device);
+	if (F->n != n || F->precision != precision || F->device != device)
+		return 1;
+	HIP_TRY(hipSetDevice(device));
+	const FsaiApply apply = {F};
+	if (precision == SPMV_MI355X_F32)
+		return pcg_tri_solve<float, true>("pcg_fsai", A, b_host, x_out_host, nullptr, apply, tol, max_iterations, history_out, info);
+	return pcg_tri_solve<double, true>("pcg_fsai", A, b_host, x_out_host, nullptr, apply, tol, max_iterations, history_out, info);
 }

@@ -66,6 +66,9 @@ SYMBOLS = [
     "spmv_mi355x_trsv_solve", "spmv_mi355x_trsv_info", "spmv_mi355x_trsv_mem_footprint", "spmv_mi355x_time_trsv_device",
     "spmv_mi355x_trsv_analyze_blocked", "spmv_mi355x_trsv_create_blocked", "spmv_mi355x_trsv_block_info", "spmv_mi355x_gmres_tri",
     "spmv_mi355x_pcg_tri",
+    "spmv_mi355x_fsai_pattern", "spmv_mi355x_fsai_create", "spmv_mi355x_fsai_destroy", "spmv_mi355x_fsai_apply_device_async",
+    "spmv_mi355x_fsai_apply", "spmv_mi355x_fsai_values", "spmv_mi355x_fsai_matrices", "spmv_mi355x_fsai_info",
+    "spmv_mi355x_fsai_setup_split", "spmv_mi355x_fsai_mem_footprint", "spmv_mi355x_pcg_fsai",
 ]
 
 _lib = None
@@ -111,6 +114,10 @@ def lib():
         L.spmv_mi355x_pcg_tri.restype = C.c_int
         L.spmv_mi355x_pcg_tri.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TriPrecond), C.c_double, C.c_long,
                                           C.c_void_p, C.POINTER(PcgTriInfo)]
+        L.spmv_mi355x_pcg_fsai.restype = C.c_int
+        L.spmv_mi355x_pcg_fsai.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_long, C.c_void_p,
+                                           C.POINTER(PcgTriInfo)]
+        L.spmv_mi355x_fsai_mem_footprint.restype = C.c_double
         _lib = L
     return _lib
 
@@ -370,6 +377,97 @@ def sgs_precond(row_ptr, col_idx, values, n, dtype=np.float64, block_rows=None, 
     return first, values[at].astype(dtype), second
 
 
+FSAI_MAX_ROW = 128
+
+
+def fsai_pattern(row_ptr, col_idx, n, power=1):
+    """(row_ptr, col_idx) of the pattern of tril(A~)^power, A~ = the lower triangle of A's pattern with the diagonal added, columns
+    ascending (spmv_mi355x_fsai_pattern; host only). power is 1, 2 or 3."""
+    row_ptr = np.ascontiguousarray(row_ptr, np.int32)
+    col_idx = np.ascontiguousarray(col_idx, np.int32)
+    rp, ci = C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)()
+    _check(lib().spmv_mi355x_fsai_pattern(C.c_long(n), _p(row_ptr), _p(col_idx), C.c_int(power), C.byref(rp), C.byref(ci)))
+    out_rp = np.ctypeslib.as_array(rp, shape=(n + 1,)).copy()
+    out_ci = np.ctypeslib.as_array(ci, shape=(max(int(out_rp[n]), 1),))[:out_rp[n]].copy()
+    lib().spmv_mi355x_free(rp)
+    lib().spmv_mi355x_free(ci)
+    return out_rp, out_ci
+
+
+class Fsai:
+    """The factorized sparse approximate inverse of a symmetric positive definite matrix (include/spmv_mi355x.h "FSAI"): a lower
+    triangular G on `pattern` = (row_ptr, col_idx), or on the lower triangle of A's own pattern when None, with G A G^t ~ I, built
+    on the GPU. apply(v) is G^t (G v), two SpMVs over the handles G and Gt, which are built in `fmt` with `opts`.
+    Matrix.pcg_tri(b, precond=<Fsai>) preconditions CG with it."""
+
+    def __init__(self, row_ptr, col_idx, values, n, pattern=None, fmt="sell_c_sigma", dtype=np.float64, **opts):
+        row_ptr = np.ascontiguousarray(row_ptr, np.int32)
+        col_idx = np.ascontiguousarray(col_idx, np.int32)
+        values = np.ascontiguousarray(values, np.float64)
+        prp = pci = None
+        if pattern is not None:
+            prp = np.ascontiguousarray(pattern[0], np.int32)
+            pci = np.ascontiguousarray(pattern[1], np.int32)
+        self.dtype = np.dtype(dtype)
+        self.n = int(n)
+        self.h = C.c_void_p()
+        o = _make_opts(opts)
+        fmt_id = FORMATS[fmt] if isinstance(fmt, str) else fmt
+        _check(lib().spmv_mi355x_fsai_create(C.byref(self.h), fmt_id, F64 if self.dtype == np.float64 else F32, C.c_long(n),
+                                             _p(row_ptr), _p(col_idx), _p(values), None if prp is None else _p(prp),
+                                             None if pci is None else _p(pci), C.byref(o)))
+        self.mem_footprint = lib().spmv_mi355x_fsai_mem_footprint(self.h)
+        g, gt = C.c_void_p(), C.c_void_p()
+        _check(lib().spmv_mi355x_fsai_matrices(self.h, C.byref(g), C.byref(gt)))
+        # Matrix objects over the borrowed handles: they never destroy them (close() of a borrowed Matrix only forgets the handle)
+        self.G = Matrix(None, None, None, 0, 0, fmt, dtype, _handle=g, _borrowed=True) if g else None
+        self.Gt = Matrix(None, None, None, 0, 0, fmt, dtype, _handle=gt, _borrowed=True) if gt else None
+
+    def info(self):
+        """dict(n, nnz, max_row, fallback_rows, kernel_seconds, setup_seconds, download_seconds, create_g_seconds,
+        create_gt_seconds) of spmv_mi355x_fsai_info and spmv_mi355x_fsai_setup_split"""
+        n, nnz, widest, fell = C.c_long(), C.c_long(), C.c_long(), C.c_long()
+        kernel, setup, down, cg, cgt = C.c_double(), C.c_double(), C.c_double(), C.c_double(), C.c_double()
+        _check(lib().spmv_mi355x_fsai_info(self.h, C.byref(n), C.byref(nnz), C.byref(widest), C.byref(fell), C.byref(kernel),
+                                           C.byref(setup)))
+        _check(lib().spmv_mi355x_fsai_setup_split(self.h, None, C.byref(down), C.byref(cg), C.byref(cgt)))
+        return dict(n=n.value, nnz=nnz.value, max_row=widest.value, fallback_rows=fell.value, kernel_seconds=kernel.value,
+                    setup_seconds=setup.value, download_seconds=down.value, create_g_seconds=cg.value, create_gt_seconds=cgt.value)
+
+    def values(self):
+        """G's values in fp64, in the pattern's entry order, whatever the handle's precision"""
+        out = np.zeros(max(self.info()["nnz"], 1))
+        _check(lib().spmv_mi355x_fsai_values(self.h, _p(out)))
+        return out[:self.info()["nnz"]]
+
+    def apply(self, v):
+        """G^t (G v) for a host vector of n values (spmv_mi355x_fsai_apply; blocking)"""
+        v = np.ascontiguousarray(v, self.dtype)
+        if v.shape != (self.n,):
+            raise ValueError(f"v must have {self.n} values, got {v.shape}")
+        out = np.full(max(self.n, 1), np.nan, self.dtype)
+        _check(lib().spmv_mi355x_fsai_apply(self.h, _p(v), _p(out)))
+        return out[:self.n]
+
+    def apply_device(self, in_ptr, out_ptr, stream=None):
+        """The same on device pointers (in_ptr == out_ptr: in place), enqueued on `stream` (spmv_mi355x_fsai_apply_device_async)"""
+        _check(lib().spmv_mi355x_fsai_apply_device_async(self.h, C.c_void_p(in_ptr), C.c_void_p(out_ptr), C.c_void_p(stream or 0)))
+
+    def close(self):
+        if getattr(self, "h", None) is not None and self.h:
+            for M in (self.G, self.Gt):
+                if M is not None:
+                    M.close()
+            lib().spmv_mi355x_fsai_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _tri_precond(precond, m, dtype):
     """the TriPrecond of precond = (first, scale, second), and the scale array it points into (to be kept alive)"""
     first, scale, second = precond
@@ -514,8 +612,9 @@ class Matrix:
     transpose of the CSR it is given (include/spmv_mi355x.h "transposed handles"): m and n are then those of the transpose, and
     `transposed` is 1."""
 
-    def __init__(self, row_ptr, col_idx, values, m, n, fmt="csr_vector", dtype=np.float64, _handle=None, **opts):
-        if _handle is not None:                        # CsrStream.finish(): the handle exists already
+    def __init__(self, row_ptr, col_idx, values, m, n, fmt="csr_vector", dtype=np.float64, _handle=None, _borrowed=False, **opts):
+        self._borrowed = _borrowed                     # Fsai.G / Fsai.Gt: the handle belongs to another object and is never destroyed here
+        if _handle is not None:                        # CsrStream.finish(), Fsai: the handle exists already
             self.dtype = np.dtype(dtype)
             self.h = _handle
             self._describe()
@@ -857,11 +956,22 @@ class Matrix:
         spmv_mi355x_pcg_tri_info fields plus x (rows values) and history (|r| of the recurrence after each iteration, shape
         (iterations,), or None). `precond` = (first, scale, second) applies second^-1 (scale * (first^-1 v)) as M^-1: first / second
         are TriangularSolve handles or None, scale an array of rows values or None (sgs_precond builds the SGS of A); None is the
-        plain CG."""
+        plain CG. An Fsai object as `precond` applies its G^t (G v) instead (spmv_mi355x_pcg_fsai)."""
         b = np.ascontiguousarray(b, self.dtype)
         if b.shape != (self.m,):
             raise ValueError(f"b must have {self.m} values, got {b.shape}")
         M = None
+        if isinstance(precond, Fsai):
+            x = np.zeros(max(self.m, 1), self.dtype)
+            hist = np.zeros(max(max_iterations, 1), np.float64) if history else None
+            info = PcgTriInfo()
+            info.struct_size = C.sizeof(PcgTriInfo)
+            _check(lib().spmv_mi355x_pcg_fsai(self.h, _p(b), _p(x), precond.h, tol, max_iterations, _p(hist) if history else None,
+                                              C.byref(info)))
+            out = {k: getattr(info, k) for k, _ in PcgTriInfo._fields_ if k != "struct_size"}
+            out["x"] = x[:self.m]
+            out["history"] = hist[:info.iterations] if history else None
+            return out
         if precond is not None:
             M, scale = _tri_precond(precond, self.m, self.dtype)
         x = np.zeros(max(self.m, 1), self.dtype)
@@ -877,7 +987,8 @@ class Matrix:
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h:
-            lib().spmv_mi355x_destroy(self.h)
+            if not getattr(self, "_borrowed", False):
+                lib().spmv_mi355x_destroy(self.h)
             self.h = None
 
     def __del__(self):

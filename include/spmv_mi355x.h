@@ -844,6 +844,62 @@ int  spmv_mi355x_pcg_fsai(spmv_mi355x_matrix * A, const void * b_host, void * x_
 		long max_iterations, double * history_out /* may be NULL: max_iterations doubles */,
 		spmv_mi355x_pcg_tri_info * info /* may be NULL */);
 
+/* ---- SpGEMM: C = A B on the GPU, the pattern once, the values per value set ---------------------------------------------------- */
+/* C = A B for A m x k and B k x n, both int32 CSR with fp64 values. A plan finds the pattern of C once (spgemm_create, "symbolic")
+ * and recomputes C's values for every new set of A's and B's values on the same patterns (spgemm_multiply, "numeric"): update_values'
+ * rule, same pattern, new numbers, no rebuild. The values come out in the entry order of C's CSR, so they are what
+ * spmv_mi355x_update_values_device of a handle of C takes. Row-wise (Gustavson) with a hash table per row of C, in LDS where it fits
+ * and in a per-workgroup slab of global memory where it does not (csrc/spgemm.hip, csrc/kernels_spgemm.hip).
+ * THE PATTERN. Column j is stored in row i of C exactly when some stored A(i, l) meets a stored B(l, j). Stored zeros and numerical
+ * cancellation do not remove an entry. Columns ascend within a row; c_row_ptr[0] = 0.
+ * THE VALUES. acc = +0.0 for every entry of row i; then for the entries p of row i of A in STORED order, for every entry q of B's
+ * row col(p):  acc[col(q)] = fma(a_p, b_q, acc[col(q)]). Each C(i, j) is one fma chain in the order of A's entries, so the product is
+ * deterministic and bit-identical to that loop run sequentially (tests/spgemm_reference.c), whatever lane takes which entry.
+ * THE INPUTS. A's rows may be unsorted and may hold a column twice: both occurrences are steps of the chain. B's rows may be unsorted
+ * but must not hold a column twice (the products of one step must land on distinct entries): such a B is refused at create.
+ * LIMITS. m, k, n < 2^31 - 1 and nnz(C) < 2^31. No cap on the width of a row; empty rows and empty matrices are legal.
+ *   - spgemm_create(device = -1: the current one): the plan keeps A's, B's and C's patterns on the device, the numeric bins' row lists
+ *     and, if C has rows wider than 2048, the slab of their tables. The values never stay: spgemm_multiply stages them for the call.
+ *   - spgemm_pattern: c_row_ptr (m + 1) and c_col_idx (nnz_c, from spgemm_info) into the caller's arrays.
+ *   - spgemm_multiply: host arrays, blocking. spgemm_multiply_device_async: device arrays of nnz_a, nnz_b and nnz_c doubles, enqueued
+ *     on the stream; one multiply at a time per plan. Where C has no entries both return at once and touch no pointer (NULL is legal).
+ *   - spgemm_info: struct_size is set by the caller, at most that many bytes are written. products = the sum over A's entries of the
+ *     length of the row of B they meet; max_row_products and max_row_c = the largest per row; the rows per bin of csrc/spgemm.hpp on
+ *     min(products, n) (symbolic_bin_rows: the counting pass) and on C's true width (numeric_bin_rows: the pass that writes the
+ *     columns, and the numeric one); symbolic_probes = the probes beyond the first over all insertions
+ *     of the counting pass; symbolic_seconds = the device part of create, multiply_seconds = the kernels of the last spgemm_multiply;
+ *     device_bytes = what the plan holds. (The struct is spmv_mi355x_spgemm_stats: C has one name space for functions and typedefs.)
+ *   - rc 1 with a last_error that starts with "spgemm_create:", in this order, all but the last two on the host before any HIP call:
+ *     1. m, k or n < 0 or >= 2^31 - 1;
+ *     2. NULL: out, a_row_ptr, b_row_ptr, and the col_idx of a matrix that has entries;
+ *     3. a pattern: row_ptr from 0 and monotone, A's columns in [0, k), B's in [0, n) (A first, then B);
+ *     4. a column twice in a row of B (the message names the row and the column);
+ *     5. the device;
+ *     6. symbolic: nnz(C) >= 2^31, before C is allocated; "spgemm: internal: table overflow in row ..." if a probe ever found its
+ *        table full (tables hold at least twice the row's bound, so it cannot; the bound on the probes makes a bug a message).
+ *   - NOT BUILT: fsai_pattern on the device, a fused triple product, fp32 accumulation, the row-partitioned form, numerical
+ *     dropping, C = A B + D. */
+#define SPMV_MI355X_SPGEMM_BINS 7
+typedef struct spmv_mi355x_spgemm spmv_mi355x_spgemm;   /* opaque */
+typedef struct {
+	unsigned struct_size;   /* in: sizeof of the caller's struct; out: bytes written */
+	long   m, k, n, nnz_a, nnz_b, nnz_c;
+	long   products, max_row_products, max_row_c;
+	long   symbolic_bin_rows[SPMV_MI355X_SPGEMM_BINS], numeric_bin_rows[SPMV_MI355X_SPGEMM_BINS];
+	long   symbolic_probes;
+	double symbolic_seconds, multiply_seconds;
+	double device_bytes;
+} spmv_mi355x_spgemm_stats;
+int  spmv_mi355x_spgemm_create(spmv_mi355x_spgemm ** out, int device /* -1: current */, long m, long k, long n,
+		const int32_t * a_row_ptr, const int32_t * a_col_idx, const int32_t * b_row_ptr, const int32_t * b_col_idx);   /* symbolic */
+int  spmv_mi355x_spgemm_destroy(spmv_mi355x_spgemm * P);
+int  spmv_mi355x_spgemm_pattern(const spmv_mi355x_spgemm * P, int32_t * c_row_ptr_out /* m+1 */, int32_t * c_col_idx_out /* nnz_c */);
+int  spmv_mi355x_spgemm_multiply(spmv_mi355x_spgemm * P, const double * a_values, const double * b_values,
+		double * c_values_out);                                                                   /* host, blocking */
+int  spmv_mi355x_spgemm_multiply_device_async(spmv_mi355x_spgemm * P, const double * a_values_dev, const double * b_values_dev,
+		double * c_values_dev, void * hip_stream);
+int  spmv_mi355x_spgemm_info(const spmv_mi355x_spgemm * P, spmv_mi355x_spgemm_stats * info /* struct_size first */);
+
 /* Row-partitioned (multi-GPU) form of the same two solvers: one process per GPU owns the row block [row_offset,
  * row_offset + m_local) of A, b and x. The solver keeps every vector device-resident and local; the two things that cross
  * ranks are handed to the caller, who has the communicator (torch.distributed / RCCL in bench-level code):

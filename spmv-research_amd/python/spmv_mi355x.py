@@ -69,6 +69,8 @@ SYMBOLS = [
     "spmv_mi355x_fsai_pattern", "spmv_mi355x_fsai_create", "spmv_mi355x_fsai_destroy", "spmv_mi355x_fsai_apply_device_async",
     "spmv_mi355x_fsai_apply", "spmv_mi355x_fsai_values", "spmv_mi355x_fsai_matrices", "spmv_mi355x_fsai_info",
     "spmv_mi355x_fsai_setup_split", "spmv_mi355x_fsai_mem_footprint", "spmv_mi355x_pcg_fsai",
+    "spmv_mi355x_spgemm_create", "spmv_mi355x_spgemm_destroy", "spmv_mi355x_spgemm_pattern", "spmv_mi355x_spgemm_multiply",
+    "spmv_mi355x_spgemm_multiply_device_async", "spmv_mi355x_spgemm_info",
 ]
 
 _lib = None
@@ -466,6 +468,92 @@ class Fsai:
             self.close()
         except Exception:
             pass
+
+
+class SpgemmStats(C.Structure):
+    """spmv_mi355x_spgemm_stats (include/spmv_mi355x.h "SpGEMM")"""
+    _fields_ = [("struct_size", C.c_uint), ("m", C.c_long), ("k", C.c_long), ("n", C.c_long), ("nnz_a", C.c_long),
+                ("nnz_b", C.c_long), ("nnz_c", C.c_long), ("products", C.c_long), ("max_row_products", C.c_long),
+                ("max_row_c", C.c_long), ("symbolic_bin_rows", C.c_long * 7), ("numeric_bin_rows", C.c_long * 7),
+                ("symbolic_probes", C.c_long), ("symbolic_seconds", C.c_double), ("multiply_seconds", C.c_double),
+                ("device_bytes", C.c_double)]
+
+
+class SpGemm:
+    """The plan of C = A B for A m x k and B k x n, int32 CSR (include/spmv_mi355x.h "SpGEMM"): the pattern of C is found once, on the
+    GPU, here; multiply(a_values, b_values) computes C's fp64 values for one set of A's and B's values, in the entry order of
+    (row_ptr, col_idx), bit for bit the sequential fma loop of the header. The plan holds patterns, never values."""
+
+    def __init__(self, a_row_ptr, a_col_idx, m, k, b_row_ptr, b_col_idx, n, device=-1):
+        a_rp = np.ascontiguousarray(a_row_ptr, np.int32)
+        a_ci = np.ascontiguousarray(a_col_idx, np.int32)
+        b_rp = np.ascontiguousarray(b_row_ptr, np.int32)
+        b_ci = np.ascontiguousarray(b_col_idx, np.int32)
+        self.h = C.c_void_p()
+        _check(lib().spmv_mi355x_spgemm_create(C.byref(self.h), C.c_int(device), C.c_long(m), C.c_long(k), C.c_long(n), _p(a_rp),
+                                               _p(a_ci), _p(b_rp), _p(b_ci)))
+        st = self.info()
+        self.shape = (st["m"], st["n"])
+        self.nnz, self.nnz_a, self.nnz_b = st["nnz_c"], st["nnz_a"], st["nnz_b"]
+        self.row_ptr = np.zeros(st["m"] + 1, np.int32)
+        self.col_idx = np.zeros(self.nnz, np.int32)
+        _check(lib().spmv_mi355x_spgemm_pattern(self.h, _p(self.row_ptr), _p(self.col_idx) if self.nnz else None))
+        for a in (self.row_ptr, self.col_idx):
+            a.setflags(write=False)
+
+    def info(self):
+        """dict of spmv_mi355x_spgemm_stats: m, k, n, nnz_a, nnz_b, nnz_c, products, max_row_products, max_row_c, symbolic_bin_rows,
+        numeric_bin_rows (lists, one count per bin of csrc/spgemm.hpp), symbolic_probes, symbolic_seconds, multiply_seconds,
+        device_bytes"""
+        st = SpgemmStats()
+        st.struct_size = C.sizeof(SpgemmStats)
+        _check(lib().spmv_mi355x_spgemm_info(self.h, C.byref(st)))
+        out = {}
+        for name, ctype in SpgemmStats._fields_[1:]:
+            v = getattr(st, name)
+            out[name] = list(v) if hasattr(v, "__len__") else v
+        return out
+
+    def multiply(self, a_values, b_values):
+        """C's fp64 values in C's entry order for these values of A and B (spmv_mi355x_spgemm_multiply; blocking)"""
+        a = np.ascontiguousarray(a_values, np.float64)
+        b = np.ascontiguousarray(b_values, np.float64)
+        if a.shape != (self.nnz_a,) or b.shape != (self.nnz_b,):
+            raise ValueError(f"a_values and b_values must have {self.nnz_a} and {self.nnz_b} entries, got {a.shape} and {b.shape}")
+        out = np.full(max(self.nnz, 1), np.nan)
+        _check(lib().spmv_mi355x_spgemm_multiply(self.h, _p(a), _p(b), _p(out)))
+        return out[:self.nnz]
+
+    def multiply_device(self, a_ptr, b_ptr, c_ptr, stream=0):
+        """The same on device pointers to nnz_a, nnz_b and nnz fp64 values, enqueued on `stream`
+        (spmv_mi355x_spgemm_multiply_device_async); c_ptr is what Matrix.update_values_device of a handle of C takes"""
+        _check(lib().spmv_mi355x_spgemm_multiply_device_async(self.h, C.c_void_p(a_ptr), C.c_void_p(b_ptr), C.c_void_p(c_ptr),
+                                                              C.c_void_p(stream or 0)))
+
+    def close(self):
+        if getattr(self, "h", None) is not None and self.h:
+            lib().spmv_mi355x_spgemm_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def spgemm(A, B, device=-1):
+    """(row_ptr, col_idx, values) of C = A B for A = (row_ptr, col_idx, values, m, k) and B = (row_ptr, col_idx, values, k, n):
+    one plan, one multiply"""
+    a_rp, a_ci, a_va, m, k = A
+    b_rp, b_ci, b_va, kb, n = B
+    if k != kb:
+        raise ValueError(f"A is {m} x {k} and B is {kb} x {n}")
+    P = SpGemm(a_rp, a_ci, m, k, b_rp, b_ci, n, device)
+    try:
+        return P.row_ptr, P.col_idx, P.multiply(a_va, b_va)
+    finally:
+        P.close()
 
 
 def _tri_precond(precond, m, dtype):

@@ -900,6 +900,110 @@ int  spmv_mi355x_spgemm_multiply_device_async(spmv_mi355x_spgemm * P, const doub
 		double * c_values_dev, void * hip_stream);
 int  spmv_mi355x_spgemm_info(const spmv_mi355x_spgemm * P, spmv_mi355x_spgemm_stats * info /* struct_size first */);
 
+/* ---- AMG: a smoothed-aggregation multilevel preconditioner built on the GPU -------------------------------------------------------- */
+/* For a square SYMMETRIC POSITIVE DEFINITE A (int32 CSR, both triangles) the handle holds a hierarchy A_0 = A, A_1, ... with
+ * prolongators P_l and restrictions R_l = P_l^t, and applies one V(nu, nu) cycle z = M^-1 v, M symmetric positive definite. The
+ * products are SpGEMM plans, the restriction is the device transposition, every operator is an ordinary handle in the caller's
+ * format, opts and precision (csrc/amg.hip, csrc/kernels_amg.hip).
+ * THE HIERARCHY, fp64 whatever the handle's precision, the arithmetic exactly as written (no contraction), so that the sequential
+ * loops of tests/amg_reference.c reproduce it bit for bit. For level l = 0, 1, ... with A_l of n_l rows:
+ *   1. d_i = the first stored a_ii;  rho = max_i (sum_j |a_ij|, in stored order) / d_i;  omega = 4 / (3 rho).
+ *   2. strength: for j != i, j in S(i) iff a_ij * a_ij >= (theta * theta) * (d_i * d_j).
+ *   3. roots = a maximal independent set at distance 2 in S, in synchronous rounds. A node's state is 0 (out), 1 (undecided) or 2
+ *      (root), its key (state << 62) | ((h >> 1) << 31) | i with h = (uint32) (i * 0x9E3779B1u). A round takes the max key over
+ *      {i} + S(i) twice (each sweep reads one buffer and writes another); an undecided node whose result is its own key becomes a
+ *      root, one whose result carries state 2 goes out. Rounds repeat until no node is undecided (the host reads one counter per
+ *      round; more than 1024 rounds are an error). A node without strong neighbours becomes a root of its own.
+ *   4. aggregates: roots are numbered in index order. Pass 1: a node with a root in S(i) takes that root's aggregate. Pass 2: a node
+ *      still free takes the aggregate of the strong neighbour assigned in pass 1 with the largest |a_ij|, ties to the smallest j.
+ *   5. T_ij = 1 iff agg(i) = j;  AT = A_l T by an SpGEMM plan;  P_ij = (agg(i) == j ? 1.0 : 0.0) - (omega / d_i) * AT_ij on AT's
+ *      pattern (the stored diagonal puts T's pattern inside AT's).
+ *   6. R = P^t in the transposition's contractual order;  A_{l+1} = R (A_l P) by two SpGEMM plans.
+ * Level l is the last when n_l <= coarse_rows, or l + 1 == max_levels, or step 4 returned more than 0.9 n_l aggregates (a stall:
+ * steps 5 and 6 are not run). A last level of at most 128 rows is factorised once, A = L L^t, packed and dense in fp64:
+ *      for k = 0..n-1, for a = k..n-1:  s = A(a, k);  for p = 0..k-1 ascending  s = fma(-L(a, p), L(k, p), s);
+ *                                       then L(k, k) = sqrt(s) for a = k and L(a, k) = s / L(k, k) below it
+ * (an absent entry is 0). A pivot s that is <= 0 or not finite abandons the factor: the level takes the sweeps, coarse_kind = 2.
+ * THE CYCLE, vectors in the handle's precision, w = (omega / d) narrowed, nu = sweeps. Below the last level:
+ *      x = w o b;  nu - 1 times x = x + w o (b - A x);  r = b - A x;  b_{l+1} = R r;  x += P cycle(l + 1)  (y += A x of the handle);
+ *      nu times x = x + w o (b - A x)
+ * and on the last level either L y = b, L^t x = y in fp64, column by column,
+ *      for k = 0..n-1:   y_k = y_k / L(k, k);  for a > k  y_a = fma(-L(a, k), y_k, y_a)
+ *      for k = n-1..0:   x_k = y_k / L(k, k);  for a < k  y_a = fma(-L(k, a), x_k, y_a)
+ * or x = w o b and coarse_sweeps - 1 of the same sweep. One level with nu = 1 costs 4 SpMVs and 3 vector launches.
+ *   - amg_create: amg_opts NULL = the defaults below; opts NULL = create's defaults. The handle of A_0 is built here and lent by
+ *     amg_level_matrices, so a caller keeps one copy of A. n == 0 is legal: no level, apply does nothing.
+ *   - amg_apply_device_async: out = M^-1 in, enqueued on the stream; in == out is legal (in is copied first). One apply at a time per
+ *     handle. amg_apply is the blocking form on host vectors of the handle's precision.
+ *   - amg_info: struct_size is set by the caller, at most that many bytes are written. Per level rows, nnz of A_l, nnz of P_l (0 on
+ *     the last), omega, rho, MIS rounds and aggregates (0 where step 3 was not run); operator complexity = sum nnz(A_l) / nnz(A_0),
+ *     grid complexity = sum n_l / n_0; coarse_kind SPMV_MI355X_AMG_COARSE_*; stalled; SpMVs and launches (SpMVs included) of one
+ *     apply; the seconds of the setup, split into coarsening (steps 1 to 5's kernels), SpGEMM, transposition, handle creation and
+ *     downloads. (The struct is spmv_mi355x_amg_stats: C has one name space for functions and typedefs.)
+ *   - amg_level_matrices: borrowed handles of A_l, P_l, R_l (P and R NULL on the last level); they die with M.
+ *     amg_aggregates: n_l int32, empty (nothing written) where step 3 was not run. amg_level_csr: the fp64 CSR the handles of
+ *     A_l (which = SPMV_MI355X_AMG_A) or P_l (SPMV_MI355X_AMG_P) were built from, sizes from amg_info; any out pointer may be NULL.
+ *   - rc 1 with a last_error that starts with "amg_create:", in this order, all but the last on the host before any device is touched:
+ *     1. the scalars: opts->struct_size or amg_opts->struct_size not set, an unknown precision or format, n < 0 or n >= 2^31 - 1,
+ *        opts that set transpose, symmetric_input or a row block / column filter, opts->value_storage under create's rule; then
+ *        theta not finite or outside [0, 1], max_levels outside 1..16, coarse_rows outside 1..128, sweeps outside 1..4,
+ *        coarse_sweeps outside 1..64;
+ *     2. NULL pointers: out, row_ptr, col_idx or values of a matrix with entries;
+ *     3. A's pattern, as create checks it: row_ptr from 0 and monotone, columns in [0, n);
+ *     4. a column stored twice in a row (the message names the row and the column);
+ *     5. the diagonal: every row must store a_ii, finite and > 0 (the message names the first bad row);
+ *     6. the device, whatever spmv_mi355x_create and spmv_mi355x_spgemm_create refuse (their message after the prefix), a coarse
+ *        diagonal that is not positive and a MIS that did not end.
+ *   - NOT CHECKABLE: that A is symmetric and positive definite. An indefinite A shows, if at all, as a coarse diagonal that is not
+ *     positive, as coarse_kind = 2, or as stop 4 of the solver.
+ *   - NOT BUILT: update_values for a hierarchy (the obvious sequel: keep the aggregates and the three plans of a level, redo the
+ *     numeric passes), W- and K-cycles, filtered prolongator smoothing, near-null-space vectors other than the constant, gmres /
+ *     minres / multi-RHS wiring, the row-partitioned form, folding the small levels into one launch. The setup routes patterns
+ *     through the host (spgemm_create and create take host arrays); the split in amg_info shows what that costs.
+ * spmv_mi355x_pcg_amg is spmv_mi355x_pcg_tri with z = M^-1 r = amg_apply_device_async: the same recurrences, kernels, stop codes,
+ * history, spmv_mi355x_pcg_tri_info and freeze (the SpMVs and vector kernels of a cycle write only the hierarchy's own vectors and
+ * z). info.spmv_calls counts the products with A of the recurrence, not those of the cycle. rc 1 with a last_error that starts with
+ * "pcg_amg:": first items 1 to 5 of spmv_mi355x_pcg_tri, then M == NULL (the message points to spmv_mi355x_pcg_tri), then M's n,
+ * precision or device differing from A's, in that order. */
+#define SPMV_MI355X_AMG_MAX_LEVELS 16
+enum { SPMV_MI355X_AMG_COARSE_DENSE = 0, SPMV_MI355X_AMG_COARSE_SWEEPS = 1, SPMV_MI355X_AMG_COARSE_SWEEPS_AFTER_PIVOT = 2 };
+enum { SPMV_MI355X_AMG_A = 0, SPMV_MI355X_AMG_P = 1 };
+typedef struct spmv_mi355x_amg spmv_mi355x_amg;   /* opaque */
+typedef struct {
+	int    struct_size;    /* sizeof(spmv_mi355x_amg_opts) */
+	double theta;          /* strength threshold, default 0.08, in [0, 1] */
+	int    max_levels;     /* default 10, 1..16 */
+	int    coarse_rows;    /* default 128, 1..128: a level of at most this many rows is the last */
+	int    sweeps;         /* nu, default 1, 1..4 */
+	int    coarse_sweeps;  /* default 4, 1..64: damped-Jacobi sweeps of a last level that is not factorised */
+} spmv_mi355x_amg_opts;
+typedef struct {
+	unsigned struct_size;   /* in: sizeof of the caller's struct; out: bytes written */
+	int    levels, coarse_kind, stalled;
+	long   rows[SPMV_MI355X_AMG_MAX_LEVELS], nnz[SPMV_MI355X_AMG_MAX_LEVELS], nnz_p[SPMV_MI355X_AMG_MAX_LEVELS];
+	long   aggregates[SPMV_MI355X_AMG_MAX_LEVELS], mis_rounds[SPMV_MI355X_AMG_MAX_LEVELS];
+	double omega[SPMV_MI355X_AMG_MAX_LEVELS], rho[SPMV_MI355X_AMG_MAX_LEVELS];
+	double operator_complexity, grid_complexity;
+	long   spmvs_per_apply, launches_per_apply;
+	double setup_seconds, coarsen_seconds, spgemm_seconds, transpose_seconds, create_seconds, download_seconds;
+} spmv_mi355x_amg_stats;
+int  spmv_mi355x_amg_create(spmv_mi355x_amg ** out, int format, int precision, long n,
+		const int32_t * row_ptr, const int32_t * col_idx, const double * values_fp64,
+		const spmv_mi355x_amg_opts * amg_opts /* NULL = defaults */, const spmv_mi355x_opts * opts /* may be NULL */);
+int  spmv_mi355x_amg_destroy(spmv_mi355x_amg * M);
+int  spmv_mi355x_amg_apply_device_async(spmv_mi355x_amg * M, const void * in_dev, void * out_dev, void * hip_stream);
+int  spmv_mi355x_amg_apply(spmv_mi355x_amg * M, const void * in_host, void * out_host);          /* blocking */
+int  spmv_mi355x_amg_info(const spmv_mi355x_amg * M, spmv_mi355x_amg_stats * info /* struct_size first */);
+int  spmv_mi355x_amg_level_matrices(const spmv_mi355x_amg * M, int level, spmv_mi355x_matrix ** A_out, spmv_mi355x_matrix ** P_out,
+		spmv_mi355x_matrix ** R_out);                                                             /* borrowed */
+int  spmv_mi355x_amg_aggregates(const spmv_mi355x_amg * M, int level, int32_t * out /* rows[level] */);
+int  spmv_mi355x_amg_level_csr(const spmv_mi355x_amg * M, int level, int which, int32_t * row_ptr_out, int32_t * col_idx_out,
+		double * values_out);
+double spmv_mi355x_amg_mem_footprint(const spmv_mi355x_amg * M);     /* the handles, the vectors and the dense factor, bytes */
+int  spmv_mi355x_pcg_amg(spmv_mi355x_matrix * A, const void * b_host, void * x_out_host, spmv_mi355x_amg * M, double tol,
+		long max_iterations, double * history_out /* may be NULL: max_iterations doubles */,
+		spmv_mi355x_pcg_tri_info * info /* may be NULL */);
+
 /* Row-partitioned (multi-GPU) form of the same two solvers: one process per GPU owns the row block [row_offset,
  * row_offset + m_local) of A, b and x. The solver keeps every vector device-resident and local; the two things that cross
  * ranks are handed to the caller, who has the communicator (torch.distributed / RCCL in bench-level code):

@@ -1,0 +1,750 @@
+// Smoothed-aggregation AMG handles (include/spmv_mi355x.h "AMG"): the checks of amg_create in the header's order, the hierarchy
+// level by level (upload A_l, steps 1 to 5 on the device with kernels_amg.hip, the products through SpGEMM plans whose values never
+// leave the device, R by the device transposition, downloads for the handles that spmv_mi355x_create builds from host arrays), the
+// dense factor of the last level, the cycle and the C ABI.
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "handle.hpp"
+#include "amg.hpp"
+#include "spgemm.hpp"
+#include "solvers_common.hpp"
+
+namespace spmv {
+
+static double
+amg_since(std::chrono::steady_clock::time_point t0)
+{
+	return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+}
+
+static bool
+amg_scalars_ok(const char * what, int format, int precision, long n, const spmv_mi355x_opts & o, const spmv_mi355x_amg_opts & a)
+{
+	if (precision != SPMV_MI355X_F64 && precision != SPMV_MI355X_F32)
+		set_error("%s: unknown precision %d", what, precision);
+	else if (format < 0 || format >= SPMV_MI355X_NUM_FORMATS)
+		set_error("%s: unknown format %d", what, format);
+	else if (n < 0 || n >= 0x7fffffffL)
+		set_error("%s: n = %ld out of range [0, 2^31 - 1)", what, n);
+	else if (o.transpose)
+		set_error("%s: opts->transpose = %d: the library builds R from the CSR of P^t itself", what, o.transpose);
+	else if (o.symmetric_input)
+		set_error("%s: opts->symmetric_input = %d: A comes with both triangles, P and R are not symmetric", what, o.symmetric_input);
+	else if (o.row_begin || o.row_end || o.col_filter_mode)
+		set_error("%s: opts name a row block or a column filter (row_begin %ld, row_end %ld, col_filter_mode %d): the "
+				"row-partitioned form is not built", what, o.row_begin, o.row_end, o.col_filter_mode);
+	else if (value_storage_check(what, o, format, precision))
+		;                                     // create's own rule and message for opts->value_storage
+	else if (!std::isfinite(a.theta) || a.theta < 0 || a.theta > 1)
+		set_error("%s: amg_opts->theta = %g: it must be finite and lie in [0, 1]", what, a.theta);
+	else if (a.max_levels < 1 || a.max_levels > SPMV_MI355X_AMG_MAX_LEVELS)
+		set_error("%s: amg_opts->max_levels = %d out of range 1..%d", what, a.max_levels, SPMV_MI355X_AMG_MAX_LEVELS);
+	else if (a.coarse_rows < 1 || a.coarse_rows > AMG_DENSE_MAX)
+		set_error("%s: amg_opts->coarse_rows = %d out of range 1..%d", what, a.coarse_rows, AMG_DENSE_MAX);
+	else if (a.sweeps < 1 || a.sweeps > 4)
+		set_error("%s: amg_opts->sweeps = %d out of range 1..4", what, a.sweeps);
+	else if (a.coarse_sweeps < 1 || a.coarse_sweeps > 64)
+		set_error("%s: amg_opts->coarse_sweeps = %d out of range 1..64", what, a.coarse_sweeps);
+	else
+		return true;
+	return false;
+}
+
+// 3. row_ptr from 0 and monotone, columns in [0, n); 4. no column twice in a row; 5. a stored, finite, positive diagonal
+static int
+amg_check_matrix(const char * what, long n, const int32_t * rp, const int32_t * ci, const double * va)
+{
+	if (rp[0] != 0)
+	{
+		set_error("%s: row_ptr must start at 0 (got %d)", what, rp[0]);
+		return 1;
+	}
+	for (long i = 0; i < n; i++)
+		if (rp[i + 1] < rp[i])
+		{
+			set_error("%s: row_ptr is not monotone at row %ld", what, i);
+			return 1;
+		}
+	for (long j = 0; j < rp[n]; j++)
+		if (ci[j] < 0 || ci[j] >= n)
+		{
+			set_error("%s: column index %d out of range [0,%ld) at entry %ld", what, ci[j], n, j);
+			return 1;
+		}
+	std::vector<int32_t> mark((size_t) n, -1);
+	for (long i = 0; i < n; i++)
+		for (long j = rp[i]; j < rp[i + 1]; j++)
+		{
+			if (mark[ci[j]] == i)
+			{
+				set_error("%s: row %ld of A stores column %d twice: which value A(%ld, %d) has is not defined", what, i, ci[j], i, ci[j]);
+				return 1;
+			}
+			mark[ci[j]] = (int32_t) i;
+		}
+	for (long i = 0; i < n; i++)
+	{
+		long at = -1;
+		for (long j = rp[i]; j < rp[i + 1] && at < 0; j++)
+			if (ci[j] == i)
+				at = j;
+		if (at < 0)
+		{
+			set_error("%s: row %ld of A has no diagonal entry", what, i);
+			return 1;
+		}
+		if (!std::isfinite(va[at]) || !(va[at] > 0))
+		{
+			set_error("%s: the diagonal of row %ld of A is %g: it must be finite and > 0", what, i, va[at]);
+			return 1;
+		}
+	}
+	return 0;
+}
+
+static void
+amg_free(spmv_mi355x_amg * M)
+{
+	for (AmgLevel & L : M->lev)
+	{
+		for (spmv_mi355x_matrix * h : {L.A, L.P, L.R})
+			if (h)
+				spmv_mi355x_destroy(h);
+		for (void * p : {L.w, L.b, L.x, L.t})
+			if (p)
+				(void) hipFree(p);
+	}
+	for (void * p : {(void *) M->d_factor, M->d_in, M->d_out})
+		if (p)
+			(void) hipFree(p);
+	delete M;
+}
+
+// the plan of a product and its values on the device: c = A B with a_va and b_va resident
+struct AmgProduct {
+	spmv_mi355x_spgemm * plan = nullptr;
+	~AmgProduct()
+	{
+		if (plan)
+			spmv_mi355x_spgemm_destroy(plan);
+	}
+	int run(int device, long m, long k, long n, const int32_t * a_rp, const int32_t * a_ci, const double * a_va_dev, const int32_t * b_rp,
+			const int32_t * b_ci, const double * b_va_dev, DeviceBuffers & buf, double ** c_va_dev)
+	{
+		ABI_TRY(spmv_mi355x_spgemm_create(&plan, device, m, k, n, a_rp, a_ci, b_rp, b_ci));
+		ABI_TRY(buf.alloc(c_va_dev, (size_t) std::max<long>(plan->nnz_c, 1) * 8));
+		ABI_TRY(spmv_mi355x_spgemm_multiply_device_async(plan, a_va_dev, b_va_dev, *c_va_dev, nullptr));
+		HIP_TRY(hipStreamSynchronize(nullptr));
+		return 0;
+	}
+	// C's pattern on the host
+	int pattern(std::vector<int32_t> & rp, std::vector<int32_t> & ci) const
+	{
+		rp = plan->c_rp;
+		ci.assign((size_t) std::max<long>(plan->nnz_c, 1), 0);
+		return spmv_mi355x_spgemm_pattern(plan, rp.data(), ci.data());
+	}
+};
+
+// Level l of M: steps 1 to 4, and unless the level turns out to be the last, steps 5 and 6, the handles of P and R and the CSR of
+// level l + 1. *last_out says which.
+static int
+amg_build_level(spmv_mi355x_amg * M, int l, const spmv_mi355x_opts & o, bool * last_out)
+{
+	AmgLevel & L = M->lev[(size_t) l];
+	const long n = L.n, nnz = L.nnz;
+	const double theta2 = M->opts.theta * M->opts.theta;
+	DeviceBuffers buf;
+	int * d_rp, * d_ci, * d_state, * d_flag, * d_id, * d_agg1, * d_agg2, * d_count;
+	double * d_va, * d_d, * d_part;
+	unsigned long long * d_key[3];
+	void * d_scan;
+
+	auto t0 = std::chrono::steady_clock::now();
+	ABI_TRY(buf.alloc(&d_rp, (size_t) (n + 1) * 4));
+	ABI_TRY(buf.alloc(&d_ci, (size_t) std::max<long>(nnz, 1) * 4));
+	ABI_TRY(buf.alloc(&d_va, (size_t) std::max<long>(nnz, 1) * 8));
+	ABI_TRY(buf.alloc(&d_d, (size_t) n * 8));
+	ABI_TRY(buf.alloc(&d_part, (size_t) AMG_MAX_GRID * 8));
+	HIP_TRY(hipMemcpy(d_rp, L.rp.data(), (size_t) (n + 1) * 4, hipMemcpyHostToDevice));
+	HIP_TRY(hipMemcpy(d_ci, L.ci.data(), (size_t) nnz * 4, hipMemcpyHostToDevice));
+	HIP_TRY(hipMemcpy(d_va, L.va.data(), (size_t) nnz * 8, hipMemcpyHostToDevice));
+	const AmgCsr a = {d_rp, d_ci, d_va, n};
+
+	// 1. the diagonal and the damping
+	ABI_TRY(launch_amg_diag(a, d_d, d_part, nullptr));
+	std::vector<double> d((size_t) n), part((size_t) amg_grid(n));
+	HIP_TRY(hipMemcpy(d.data(), d_d, (size_t) n * 8, hipMemcpyDeviceToHost));
+	HIP_TRY(hipMemcpy(part.data(), d_part, part.size() * 8, hipMemcpyDeviceToHost));
+	for (long i = 0; i < n; i++)
+		if (!std::isfinite(d[i]) || !(d[i] > 0))
+		{
+			set_error("amg_create: the diagonal of row %ld of level %d is %g: the matrix is not positive definite", i, l, d[i]);
+			return 1;
+		}
+	L.rho = *std::max_element(part.begin(), part.end());
+	if (!std::isfinite(L.rho) || !(L.rho > 0))
+	{
+		set_error("amg_create: level %d: max_i sum_j |a_ij| / a_ii = %g is not a positive finite number", l, L.rho);
+		return 1;
+	}
+	L.omega = 4.0 / (3.0 * L.rho);
+	const size_t vbytes = (size_t) n * (M->f32 ? 4 : 8);
+	{
+		std::vector<double> w8;
+		std::vector<float> w4;
+		if (M->f32)
+		{
+			w4.resize((size_t) n);
+			for (long i = 0; i < n; i++)
+				w4[i] = (float) (L.omega / d[i]);
+		}
+		else
+		{
+			w8.resize((size_t) n);
+			for (long i = 0; i < n; i++)
+				w8[i] = L.omega / d[i];
+		}
+		// level 0 solves into the caller's vector; its b is the copy of `in` that an apply in place works on
+		for (void ** v : {&L.w, &L.b, &L.t, &L.x})
+			if (l > 0 || v != &L.x)
+			{
+				ABI_TRY(dev_alloc_bytes(v, vbytes));
+				M->vector_bytes += (double) vbytes;
+			}
+		HIP_TRY(hipMemcpy(L.w, M->f32 ? (const void *) w4.data() : (const void *) w8.data(), vbytes, hipMemcpyHostToDevice));
+	}
+	M->coarsen_seconds += amg_since(t0);
+
+	bool last = n <= M->opts.coarse_rows || l + 1 == M->opts.max_levels;
+	if (last)
+	{
+		*last_out = true;
+		return 0;
+	}
+
+	// 3. the roots: rounds of two sweeps and the verdicts, one counter per round
+	t0 = std::chrono::steady_clock::now();
+	ABI_TRY(buf.alloc(&d_state, (size_t) n * 4));
+	ABI_TRY(buf.alloc(&d_flag, (size_t) n * 4));
+	ABI_TRY(buf.alloc(&d_id, (size_t) n * 4));
+	ABI_TRY(buf.alloc(&d_agg1, (size_t) n * 4));
+	ABI_TRY(buf.alloc(&d_agg2, (size_t) n * 4));
+	ABI_TRY(buf.alloc(&d_count, (size_t) AMG_MIS_ROUND_CAP * 4));
+	for (auto & k : d_key)
+		ABI_TRY(buf.alloc(&k, (size_t) n * 8));
+	const size_t scan_bytes = amg_scan_bytes(n);
+	ABI_TRY(buf.alloc(&d_scan, scan_bytes));
+	HIP_TRY(hipMemsetAsync(d_count, 0, (size_t) AMG_MIS_ROUND_CAP * 4, nullptr));
+	ABI_TRY(launch_amg_mis_init(n, d_state, d_key[0], nullptr));
+	int undecided = 1;
+	while (undecided > 0)
+	{
+		if (L.mis_rounds == AMG_MIS_ROUND_CAP)
+		{
+			set_error("amg_create: internal: level %d: %d nodes are still undecided after %d rounds of the independent set", l, undecided,
+					AMG_MIS_ROUND_CAP);
+			return 1;
+		}
+		ABI_TRY(launch_amg_mis_sweep(a, d_d, theta2, d_key[0], d_key[1], nullptr));
+		ABI_TRY(launch_amg_mis_sweep(a, d_d, theta2, d_key[1], d_key[2], nullptr));
+		ABI_TRY(launch_amg_mis_decide(n, d_state, d_key[0], d_key[2], d_count + L.mis_rounds, nullptr));
+		HIP_TRY(hipMemcpy(&undecided, d_count + L.mis_rounds, 4, hipMemcpyDeviceToHost));
+		L.mis_rounds++;
+	}
+	// 4. the aggregates
+	ABI_TRY(launch_amg_number_roots(n, d_state, d_flag, d_id, d_scan, scan_bytes, nullptr));
+	ABI_TRY(launch_amg_agg_pass1(a, d_d, theta2, d_state, d_id, d_agg1, nullptr));
+	ABI_TRY(launch_amg_agg_pass2(a, d_d, theta2, d_agg1, d_agg2, nullptr));
+	int last_id = 0, last_flag = 0;
+	HIP_TRY(hipMemcpy(&last_id, d_id + (n - 1), 4, hipMemcpyDeviceToHost));
+	HIP_TRY(hipMemcpy(&last_flag, d_flag + (n - 1), 4, hipMemcpyDeviceToHost));
+	const long nc = (long) last_id + last_flag;
+	L.aggregates = nc;
+	L.agg.assign((size_t) n, 0);
+	HIP_TRY(hipMemcpy(L.agg.data(), d_agg2, (size_t) n * 4, hipMemcpyDeviceToHost));
+	M->coarsen_seconds += amg_since(t0);
+	for (long i = 0; i < n; i++)
+		if (L.agg[i] < 0 || L.agg[i] >= nc)
+		{
+			set_error("amg_create: internal: level %d: row %ld was left without an aggregate (%d of %ld)", l, i, L.agg[i], nc);
+			return 1;
+		}
+	if ((double) nc > 0.9 * (double) n)
+	{
+		M->stalled = 1;
+		*last_out = true;
+		return 0;
+	}
+
+	// 5. A T on the device, then P's values on its pattern
+	t0 = std::chrono::steady_clock::now();
+	std::vector<int32_t> t_rp((size_t) n + 1);
+	for (long i = 0; i <= n; i++)
+		t_rp[i] = (int32_t) i;
+	double * d_ones, * d_at, * d_p;
+	{
+		std::vector<double> ones((size_t) n, 1.0);
+		ABI_TRY(buf.alloc(&d_ones, (size_t) n * 8));
+		HIP_TRY(hipMemcpy(d_ones, ones.data(), (size_t) n * 8, hipMemcpyHostToDevice));
+	}
+	AmgProduct at;
+	ABI_TRY(at.run(M->device, n, n, nc, L.rp.data(), L.ci.data(), d_va, t_rp.data(), L.agg.data(), d_ones, buf, &d_at));
+	M->spgemm_seconds += amg_since(t0);
+	t0 = std::chrono::steady_clock::now();
+	const long nnz_p = at.plan->nnz_c;
+	ABI_TRY(buf.alloc(&d_p, (size_t) nnz_p * 8));
+	ABI_TRY(launch_amg_prolong(n, at.plan->d_c_rp, at.plan->d_c_ci, d_at, d_agg2, d_d, L.omega, d_p, nullptr));
+	HIP_TRY(hipStreamSynchronize(nullptr));
+	M->coarsen_seconds += amg_since(t0);
+
+	// 6. R = P^t on the device
+	t0 = std::chrono::steady_clock::now();
+	int * d_r_rp = nullptr, * d_r_ci = nullptr;
+	double * d_r_va = nullptr;
+	ABI_TRY(transpose_csr_device(n, nc, nnz_p, at.plan->d_c_rp, at.plan->d_c_ci, d_p, &d_r_rp, &d_r_ci, &d_r_va));
+	for (void * p : {(void *) d_r_rp, (void *) d_r_ci, (void *) d_r_va})
+		buf.ptrs.push_back(p);
+	HIP_TRY(hipStreamSynchronize(nullptr));
+	M->transpose_seconds += amg_since(t0);
+
+	t0 = std::chrono::steady_clock::now();
+	L.nnz_p = nnz_p;
+	ABI_TRY(at.pattern(L.p_rp, L.p_ci));
+	L.p_va.assign((size_t) nnz_p, 0.0);
+	std::vector<int32_t> r_rp((size_t) nc + 1), r_ci((size_t) nnz_p);
+	std::vector<double> r_va((size_t) nnz_p);
+	HIP_TRY(hipMemcpy(L.p_va.data(), d_p, (size_t) nnz_p * 8, hipMemcpyDeviceToHost));
+	HIP_TRY(hipMemcpy(r_rp.data(), d_r_rp, (size_t) (nc + 1) * 4, hipMemcpyDeviceToHost));
+	HIP_TRY(hipMemcpy(r_ci.data(), d_r_ci, (size_t) nnz_p * 4, hipMemcpyDeviceToHost));
+	HIP_TRY(hipMemcpy(r_va.data(), d_r_va, (size_t) nnz_p * 8, hipMemcpyDeviceToHost));
+	M->download_seconds += amg_since(t0);
+
+	// A_{l+1} = R (A_l P)
+	t0 = std::chrono::steady_clock::now();
+	double * d_ap, * d_ac;
+	AmgProduct ap, ac;
+	ABI_TRY(ap.run(M->device, n, n, nc, L.rp.data(), L.ci.data(), d_va, L.p_rp.data(), L.p_ci.data(), d_p, buf, &d_ap));
+	std::vector<int32_t> ap_rp, ap_ci;
+	ABI_TRY(ap.pattern(ap_rp, ap_ci));
+	ABI_TRY(ac.run(M->device, nc, n, nc, r_rp.data(), r_ci.data(), d_r_va, ap_rp.data(), ap_ci.data(), d_ap, buf, &d_ac));
+	M->spgemm_seconds += amg_since(t0);
+	t0 = std::chrono::steady_clock::now();
+	M->lev.emplace_back();                            // reserved in amg_create: L stays valid
+	AmgLevel & C = M->lev.back();
+	C.n = nc;
+	C.nnz = ac.plan->nnz_c;
+	ABI_TRY(ac.pattern(C.rp, C.ci));
+	C.va.assign((size_t) std::max<long>(C.nnz, 1), 0.0);
+	HIP_TRY(hipMemcpy(C.va.data(), d_ac, (size_t) C.nnz * 8, hipMemcpyDeviceToHost));
+	M->download_seconds += amg_since(t0);
+
+	// the handles of P and R, values narrowed as create narrows them
+	t0 = std::chrono::steady_clock::now();
+	ABI_TRY(spmv_mi355x_create(&L.P, M->format, M->precision, n, nc, nnz_p, L.p_rp.data(), L.p_ci.data(), L.p_va.data(), &o));
+	ABI_TRY(spmv_mi355x_create(&L.R, M->format, M->precision, nc, n, nnz_p, r_rp.data(), r_ci.data(), r_va.data(), &o));
+	M->create_seconds += amg_since(t0);
+	*last_out = false;
+	return 0;
+}
+
+// The packed factor of the last level, row-major lower triangle; false when a pivot is not positive.
+static bool
+amg_factor(const AmgLevel & L, std::vector<double> & F)
+{
+	const long n = L.n;
+	std::vector<double> S((size_t) (n * (n + 1) / 2), 0.0);
+	for (long i = 0; i < n; i++)
+		for (long e = L.rp[i]; e < L.rp[i + 1]; e++)
+			if (L.ci[e] <= i)
+				S[(size_t) (i * (i + 1) / 2 + L.ci[e])] = L.va[e];
+	F.assign(S.size(), 0.0);
+	for (long k = 0; k < n; k++)
+		for (long a = k; a < n; a++)
+		{
+			double s = S[(size_t) (a * (a + 1) / 2 + k)];
+			for (long p = 0; p < k; p++)
+				s = std::fma(-F[(size_t) (a * (a + 1) / 2 + p)], F[(size_t) (k * (k + 1) / 2 + p)], s);
+			if (a == k)
+			{
+				if (!std::isfinite(s) || !(s > 0))
+					return false;
+				F[(size_t) (k * (k + 1) / 2 + k)] = std::sqrt(s);
+			}
+			else
+				F[(size_t) (a * (a + 1) / 2 + k)] = s / F[(size_t) (k * (k + 1) / 2 + k)];
+		}
+	return true;
+}
+
+static int
+amg_build(spmv_mi355x_amg * M, const spmv_mi355x_opts & o)
+{
+	for (int l = 0;; l++)
+	{
+		bool last = true;
+		ABI_TRY(amg_build_level(M, l, o, &last));
+		AmgLevel & L = M->lev[(size_t) l];
+		const auto t0 = std::chrono::steady_clock::now();
+		ABI_TRY(spmv_mi355x_create(&L.A, M->format, M->precision, L.n, L.n, L.nnz, L.rp.data(), L.ci.data(), L.va.data(), &o));
+		M->create_seconds += amg_since(t0);
+		if (last)
+			break;
+	}
+	M->levels = (int) M->lev.size();
+	const AmgLevel & Z = M->lev.back();
+	const int nu = M->opts.sweeps, cs = M->opts.coarse_sweeps;
+	M->coarse_kind = SPMV_MI355X_AMG_COARSE_SWEEPS;
+	if (Z.n <= AMG_DENSE_MAX)
+	{
+		std::vector<double> F;
+		if (amg_factor(Z, F))
+		{
+			M->coarse_kind = SPMV_MI355X_AMG_COARSE_DENSE;
+			ABI_TRY(dev_alloc_bytes((void **) &M->d_factor, F.size() * 8));
+			HIP_TRY(hipMemcpy(M->d_factor, F.data(), F.size() * 8, hipMemcpyHostToDevice));
+			M->vector_bytes += (double) F.size() * 8;
+		}
+		else
+			M->coarse_kind = SPMV_MI355X_AMG_COARSE_SWEEPS_AFTER_PIVOT;
+	}
+	M->spmvs = (long) (M->levels - 1) * (2 * nu + 2) + (M->coarse_kind == SPMV_MI355X_AMG_COARSE_DENSE ? 0 : cs - 1);
+	M->launches = M->spmvs + (long) (M->levels - 1) * (2 * nu + 1) + (M->coarse_kind == SPMV_MI355X_AMG_COARSE_DENSE ? 1 : cs);
+	return 0;
+}
+
+}  // namespace spmv
+
+using namespace spmv;
+
+extern "C" {
+
+int
+spmv_mi355x_amg_create(spmv_mi355x_amg ** out, int format, int precision, long n, const int32_t * row_ptr, const int32_t * col_idx,
+		const double * values, const spmv_mi355x_amg_opts * amg_opts, const spmv_mi355x_opts * opts_in)
+{
+	const char * what = "amg_create";
+	const auto t_start = std::chrono::steady_clock::now();
+	if (out)
+		*out = nullptr;
+	// 1. the scalars
+	spmv_mi355x_opts o;
+	memset(&o, 0, sizeof(o));
+	o.device = -1;
+	if (opts_in)
+	{
+		const size_t sz = std::min<size_t>(sizeof(o), (size_t) std::max(opts_in->struct_size, 0));
+		if (sz < 8)
+		{
+			set_error("%s: opts->struct_size not set", what);
+			return 1;
+		}
+		memcpy(&o, opts_in, sz);
+	}
+	o.struct_size = (int) sizeof(o);
+	spmv_mi355x_amg_opts a = {(int) sizeof(spmv_mi355x_amg_opts), 0.08, 10, 128, 1, 4};
+	if (amg_opts)
+	{
+		const size_t sz = std::min<size_t>(sizeof(a), (size_t) std::max(amg_opts->struct_size, 0));
+		if (sz < 8)
+		{
+			set_error("%s: amg_opts->struct_size not set", what);
+			return 1;
+		}
+		memcpy(&a, amg_opts, sz);
+		a.struct_size = (int) sizeof(a);
+	}
+	if (!amg_scalars_ok(what, format, precision, n, o, a))
+		return 1;
+	// 2. NULL pointers
+	const bool entries = row_ptr && row_ptr[n] > 0;
+	if (!out || !row_ptr || (entries && (!col_idx || !values)))
+	{
+		set_error("%s: NULL argument (%s%s%s%s )", what, !out ? " out" : "", !row_ptr ? " row_ptr" : "", entries && !col_idx ? " col_idx" : "",
+				entries && !values ? " values" : "");
+		return 1;
+	}
+	// 3. to 5. the pattern, no column twice, the diagonal
+	if (amg_check_matrix(what, n, row_ptr, col_idx, values))
+		return 1;
+	// 6. the device
+	int ndev = 0;
+	spmv_mi355x_device_count(&ndev);
+	if (ndev < 1)
+	{
+		set_error("%s: no HIP device available: this engine has no CPU fallback", what);
+		return 1;
+	}
+	int device = o.device;
+	if (device < 0)
+		HIP_TRY(hipGetDevice(&device));
+	if (device >= ndev)
+	{
+		set_error("%s: device %d out of range (%d devices)", what, device, ndev);
+		return 1;
+	}
+	HIP_TRY(hipSetDevice(device));
+	o.device = device;
+
+	spmv_mi355x_amg * M = new spmv_mi355x_amg();
+	M->precision = precision;
+	M->f32 = precision == SPMV_MI355X_F32;
+	M->device = device;
+	M->format = format;
+	M->n = n;
+	M->opts = a;
+	if (n > 0)
+	{
+		M->lev.reserve(SPMV_MI355X_AMG_MAX_LEVELS + 1);
+		M->lev.emplace_back();
+		AmgLevel & L = M->lev[0];
+		L.n = n;
+		L.nnz = row_ptr[n];
+		L.rp.assign(row_ptr, row_ptr + n + 1);
+		L.ci.assign(col_idx, col_idx + L.nnz);
+		L.va.assign(values, values + L.nnz);
+		if (amg_build(M, o))
+		{
+			std::string msg = spmv_mi355x_last_error();
+			amg_free(M);
+			if (msg.rfind("amg_create:", 0) != 0)
+				set_error("%s: %s", what, msg.c_str());
+			return 1;
+		}
+	}
+	M->setup_seconds = amg_since(t_start);
+	*out = M;
+	return 0;
+}
+
+int
+spmv_mi355x_amg_destroy(spmv_mi355x_amg * M)
+{
+	if (!M)
+		return 0;
+	(void) hipSetDevice(M->device);
+	amg_free(M);
+	return 0;
+}
+
+int
+spmv_mi355x_amg_apply_device_async(spmv_mi355x_amg * M, const void * in_dev, void * out_dev, void * hip_stream)
+{
+	if (!M || (M->n > 0 && (!in_dev || !out_dev)))
+	{
+		set_error("amg_apply: NULL argument (%s%s%s )", !M ? " M" : "", M && !in_dev ? " in" : "", M && !out_dev ? " out" : "");
+		return 1;
+	}
+	if (M->n == 0)
+		return 0;
+	hipStream_t st = (hipStream_t) hip_stream;
+	const bool f32 = M->f32;
+	const int nl = M->levels, nu = M->opts.sweeps;
+	if (in_dev == out_dev)
+	{
+		// level 0 reads b after it has written x: an apply in place works on a copy of `in`
+		HIP_TRY(hipMemcpyAsync(M->lev[0].b, in_dev, (size_t) M->n * (f32 ? 4 : 8), hipMemcpyDeviceToDevice, st));
+		in_dev = M->lev[0].b;
+	}
+	auto rhs = [&](int l) { return l == 0 ? in_dev : (const void *) M->lev[(size_t) l].b; };
+	auto sol = [&](int l) { return l == 0 ? out_dev : M->lev[(size_t) l].x; };
+	auto sweep = [&](int l) {
+		AmgLevel & L = M->lev[(size_t) l];
+		ABI_TRY(spmv_mi355x_spmv_device_async(L.A, sol(l), L.t, 0, st));
+		return launch_amg_sweep(f32, L.w, rhs(l), L.t, sol(l), L.n, st);
+	};
+	for (int l = 0; l < nl - 1; l++)
+	{
+		AmgLevel & L = M->lev[(size_t) l];
+		ABI_TRY(launch_amg_first(f32, L.w, rhs(l), sol(l), L.n, st));
+		for (int s = 1; s < nu; s++)
+			ABI_TRY(sweep(l));
+		ABI_TRY(spmv_mi355x_spmv_device_async(L.A, sol(l), L.t, 0, st));
+		ABI_TRY(launch_amg_residual(f32, rhs(l), L.t, L.n, st));
+		ABI_TRY(spmv_mi355x_spmv_device_async(L.R, L.t, M->lev[(size_t) l + 1].b, 0, st));
+	}
+	{
+		const int l = nl - 1;
+		AmgLevel & L = M->lev[(size_t) l];
+		if (M->coarse_kind == SPMV_MI355X_AMG_COARSE_DENSE)
+			ABI_TRY(launch_amg_dense_solve(f32, M->d_factor, rhs(l), sol(l), (int) L.n, st));
+		else
+		{
+			ABI_TRY(launch_amg_first(f32, L.w, rhs(l), sol(l), L.n, st));
+			for (int s = 1; s < M->opts.coarse_sweeps; s++)
+				ABI_TRY(sweep(l));
+		}
+	}
+	for (int l = nl - 2; l >= 0; l--)
+	{
+		AmgLevel & L = M->lev[(size_t) l];
+		ABI_TRY(spmv_mi355x_spmv_device_async(L.P, M->lev[(size_t) l + 1].x, sol(l), 1, st));
+		for (int s = 0; s < nu; s++)
+			ABI_TRY(sweep(l));
+	}
+	return 0;
+}
+
+int
+spmv_mi355x_amg_apply(spmv_mi355x_amg * M, const void * in_host, void * out_host)
+{
+	if (!M || (M->n > 0 && (!in_host || !out_host)))
+	{
+		set_error("amg_apply: NULL argument (%s%s%s )", !M ? " M" : "", M && !in_host ? " in" : "", M && !out_host ? " out" : "");
+		return 1;
+	}
+	if (M->n == 0)
+		return 0;
+	HIP_TRY(hipSetDevice(M->device));
+	const size_t bytes = (size_t) M->n * (M->f32 ? 4 : 8);
+	if (!M->d_in && (dev_alloc_bytes(&M->d_in, bytes) || dev_alloc_bytes(&M->d_out, bytes)))
+		return 1;
+	HIP_TRY(hipMemcpyAsync(M->d_in, in_host, bytes, hipMemcpyHostToDevice, nullptr));
+	if (spmv_mi355x_amg_apply_device_async(M, M->d_in, M->d_out, nullptr))
+		return 1;
+	HIP_TRY(hipMemcpyAsync(out_host, M->d_out, bytes, hipMemcpyDeviceToHost, nullptr));
+	HIP_TRY(hipStreamSynchronize(nullptr));
+	return 0;
+}
+
+int
+spmv_mi355x_amg_info(const spmv_mi355x_amg * M, spmv_mi355x_amg_stats * info)
+{
+	if (!M || !info)
+	{
+		set_error("amg_info: NULL %s", !M ? "handle" : "info");
+		return 1;
+	}
+	if (!info_size_ok("amg_info", info))
+		return 1;
+	spmv_mi355x_amg_stats s;
+	memset(&s, 0, sizeof(s));
+	s.levels = M->levels;
+	s.coarse_kind = M->coarse_kind;
+	s.stalled = M->stalled;
+	double nnz_sum = 0, rows_sum = 0;
+	for (int l = 0; l < M->levels; l++)
+	{
+		const AmgLevel & L = M->lev[(size_t) l];
+		s.rows[l] = L.n;
+		s.nnz[l] = L.nnz;
+		s.nnz_p[l] = L.nnz_p;
+		s.aggregates[l] = L.aggregates;
+		s.mis_rounds[l] = L.mis_rounds;
+		s.omega[l] = L.omega;
+		s.rho[l] = L.rho;
+		nnz_sum += (double) L.nnz;
+		rows_sum += (double) L.n;
+	}
+	if (M->levels > 0)
+	{
+		s.operator_complexity = nnz_sum / (double) M->lev[0].nnz;
+		s.grid_complexity = rows_sum / (double) M->lev[0].n;
+	}
+	s.spmvs_per_apply = M->spmvs;
+	s.launches_per_apply = M->launches;
+	s.setup_seconds = M->setup_seconds;
+	s.coarsen_seconds = M->coarsen_seconds;
+	s.spgemm_seconds = M->spgemm_seconds;
+	s.transpose_seconds = M->transpose_seconds;
+	s.create_seconds = M->create_seconds;
+	s.download_seconds = M->download_seconds;
+	put_info(info, info->struct_size, s);
+	return 0;
+}
+
+static const AmgLevel *
+amg_level_of(const char * what, const spmv_mi355x_amg * M, int level)
+{
+	if (!M)
+	{
+		set_error("%s: NULL handle", what);
+		return nullptr;
+	}
+	if (level < 0 || level >= M->levels)
+	{
+		set_error("%s: level %d out of range: the hierarchy has %d", what, level, M->levels);
+		return nullptr;
+	}
+	return &M->lev[(size_t) level];
+}
+
+int
+spmv_mi355x_amg_level_matrices(const spmv_mi355x_amg * M, int level, spmv_mi355x_matrix ** A_out, spmv_mi355x_matrix ** P_out,
+		spmv_mi355x_matrix ** R_out)
+{
+	const AmgLevel * L = amg_level_of("amg_level_matrices", M, level);
+	if (!L)
+		return 1;
+	if (A_out)
+		*A_out = L->A;
+	if (P_out)
+		*P_out = L->P;
+	if (R_out)
+		*R_out = L->R;
+	return 0;
+}
+
+int
+spmv_mi355x_amg_aggregates(const spmv_mi355x_amg * M, int level, int32_t * out)
+{
+	const AmgLevel * L = amg_level_of("amg_aggregates", M, level);
+	if (!L)
+		return 1;
+	if (!L->agg.empty() && !out)
+	{
+		set_error("amg_aggregates: NULL out");
+		return 1;
+	}
+	if (!L->agg.empty())
+		memcpy(out, L->agg.data(), L->agg.size() * sizeof(int32_t));
+	return 0;
+}
+
+int
+spmv_mi355x_amg_level_csr(const spmv_mi355x_amg * M, int level, int which, int32_t * row_ptr_out, int32_t * col_idx_out, double * values_out)
+{
+	const AmgLevel * L = amg_level_of("amg_level_csr", M, level);
+	if (!L)
+		return 1;
+	if (which != SPMV_MI355X_AMG_A && which != SPMV_MI355X_AMG_P)
+	{
+		set_error("amg_level_csr: which = %d: SPMV_MI355X_AMG_A or SPMV_MI355X_AMG_P", which);
+		return 1;
+	}
+	const bool p = which == SPMV_MI355X_AMG_P;
+	if (p && !L->P)
+	{
+		set_error("amg_level_csr: level %d is the last: it has no prolongator", level);
+		return 1;
+	}
+	const long nnz = p ? L->nnz_p : L->nnz;
+	if (row_ptr_out)
+		memcpy(row_ptr_out, (p ? L->p_rp : L->rp).data(), (size_t) (L->n + 1) * sizeof(int32_t));
+	if (col_idx_out && nnz > 0)
+		memcpy(col_idx_out, (p ? L->p_ci : L->ci).data(), (size_t) nnz * sizeof(int32_t));
+	if (values_out && nnz > 0)
+		memcpy(values_out, (p ? L->p_va : L->va).data(), (size_t) nnz * sizeof(double));
+	return 0;
+}
+
+double
+spmv_mi355x_amg_mem_footprint(const spmv_mi355x_amg * M)
+{
+	if (!M)
+		return 0;
+	double bytes = M->vector_bytes;
+	for (const AmgLevel & L : M->lev)
+		for (const spmv_mi355x_matrix * h : {L.A, L.P, L.R})
+			if (h)
+				bytes += spmv_mi355x_mem_footprint(h);
+	return bytes;
+}
+
+}  // extern "C"

@@ -1,0 +1,100 @@
+// Smoothed-aggregation AMG (include/spmv_mi355x.h "AMG"): what amg.hip (the checks, the hierarchy, the C ABI), kernels_amg.hip (the
+// setup kernels of steps 1 to 5, the cycle's vector kernels, the dense coarsest solve) and solver_pcg_tri.hip (pcg_amg) share.
+//
+// THE MAPPING. Every setup kernel is one lane per row of A_l, AMG_TB lanes per workgroup, at most AMG_MAX_GRID workgroups which walk
+// the rows with a grid stride: beyond AMG_TB * AMG_MAX_GRID = 262 144 rows a workgroup takes a second trip. A lane walks its row in
+// stored order; rows of A_l hold a handful of entries (a stencil, a Galerkin product of one), so a wave per row would idle. The
+// cycle's vector kernels are the solvers' (VB lanes, solver_blocks workgroups, GRID_STRIDE). The dense solve is one workgroup of
+// AMG_DENSE_MAX lanes, lane a owning y_a; its loops hold one barrier per column and run n trips in every lane.
+// No atomics on values (the one atomic is the integer count of undecided nodes, one add per workgroup), no flags, nothing spins; a
+// launch boundary is the only ordering between workgroups.
+//     kernel                     VGPRs   LDS        scratch
+//     amg_diag_kernel              20    2 048 B       0
+//     amg_mis_init_kernel          13        0         0
+//     amg_mis_sweep_kernel         18        0         0
+//     amg_mis_decide_kernel        18    1 024 B       0
+//     amg_root_flag_kernel         16        0         0
+//     amg_agg_pass1_kernel         18        0         0
+//     amg_agg_pass2_kernel         24        0         0
+//     amg_prolong_kernel           24        0         0
+//     amg_first / sweep / residual <= 22     0         0
+//     amg_dense_solve_kernel       20   67 072 B       0
+// (-Rpass-analysis=kernel-resource-usage, gfx950; profiles/r23_amg.txt has the compiler's own table.)
+#pragma once
+
+#include <vector>
+
+#include "common.hpp"
+#include "../../include/spmv_mi355x.h"
+
+namespace spmv {
+
+constexpr int AMG_TB = 256;
+constexpr int AMG_MAX_GRID = 1024;                        // workgroups per setup launch; more rows are walked with a grid stride
+constexpr int AMG_DENSE_MAX = 128;                        // rows of a dense coarsest level: 128 * 129 / 2 doubles = 66 048 B of LDS
+constexpr int AMG_MIS_ROUND_CAP = 1024;                   // every round decides a node, real counts are below 20: a bug becomes a message
+constexpr unsigned AMG_HASH_MUL = 0x9E3779B1u;            // SPGEMM_HASH_MUL
+
+// A_l on the device
+struct AmgCsr {
+	const int * rp;
+	const int * ci;
+	const double * va;
+	long n;
+};
+
+inline int
+amg_grid(long n)
+{
+	return (int) std::min<long>(AMG_MAX_GRID, std::max<long>(1, (n + AMG_TB - 1) / AMG_TB));
+}
+
+// step 1: d[i] = the first stored a_ii; part[workgroup] = the workgroup's max of (sum_j |a_ij|) / d_i; amg_grid(n) partials
+int launch_amg_diag(const AmgCsr & a, double * d, double * part, hipStream_t st);
+// step 3: state = 1 and key0 = the key of every node
+int launch_amg_mis_init(long n, int * state, unsigned long long * key0, hipStream_t st);
+// out[i] = max(in[i], in[j] for j in S(i))
+int launch_amg_mis_sweep(const AmgCsr & a, const double * d, double theta2, const unsigned long long * in, unsigned long long * out,
+		hipStream_t st);
+// the verdicts of a round: state and key0 of every undecided node; *undecided += the nodes still undecided (zeroed by the caller)
+int launch_amg_mis_decide(long n, int * state, unsigned long long * key0, const unsigned long long * key2, int * undecided, hipStream_t st);
+// step 4: id = the exclusive scan of (state == 2); scan_tmp / scan_bytes as hipcub wants them (amg_scan_bytes)
+size_t amg_scan_bytes(long n);
+int launch_amg_number_roots(long n, const int * state, int * flag, int * id, void * scan_tmp, size_t scan_bytes, hipStream_t st);
+int launch_amg_agg_pass1(const AmgCsr & a, const double * d, double theta2, const int * state, const int * id, int * agg1, hipStream_t st);
+int launch_amg_agg_pass2(const AmgCsr & a, const double * d, double theta2, const int * agg1, int * agg2, hipStream_t st);
+// step 5: p_va from the CSR of A T
+int launch_amg_prolong(long n, const int * at_rp, const int * at_ci, const double * at_va, const int * agg, const double * d, double omega,
+		double * p_va, hipStream_t st);
+// the cycle: x = w o b;  x += w o (b - t);  t = b - t
+int launch_amg_first(bool f32, const void * w, const void * b, void * x, long n, hipStream_t st);
+int launch_amg_sweep(bool f32, const void * w, const void * b, const void * t, void * x, long n, hipStream_t st);
+int launch_amg_residual(bool f32, const void * b, void * t, long n, hipStream_t st);
+// x = (L L^t)^-1 b for the packed factor L of n <= AMG_DENSE_MAX rows (row-major lower triangle, fp64)
+int launch_amg_dense_solve(bool f32, const double * L, const void * b, void * x, int n, hipStream_t st);
+
+struct AmgLevel {
+	long n = 0, nnz = 0, nnz_p = 0, aggregates = 0;
+	int mis_rounds = 0;
+	double omega = 0, rho = 0;
+	std::vector<int32_t> rp, ci, p_rp, p_ci, agg;         // the host copies level_csr and aggregates return
+	std::vector<double> va, p_va;
+	spmv_mi355x_matrix * A = nullptr, * P = nullptr, * R = nullptr;
+	void * w = nullptr, * b = nullptr, * x = nullptr, * t = nullptr;   // n values of the handle's precision each; x is NULL on level 0
+};
+
+}  // namespace spmv
+
+struct spmv_mi355x_amg {
+	int precision = 0, device = 0, format = 0;
+	bool f32 = false;
+	long n = 0;
+	spmv_mi355x_amg_opts opts = {};
+	int levels = 0, coarse_kind = 0, stalled = 0;
+	std::vector<spmv::AmgLevel> lev;
+	double * d_factor = nullptr;                          // the packed Cholesky factor of a dense last level
+	void * d_in = nullptr, * d_out = nullptr;             // the vectors of the host-buffer apply, allocated at its first call
+	long spmvs = 0, launches = 0;
+	double setup_seconds = 0, coarsen_seconds = 0, spgemm_seconds = 0, transpose_seconds = 0, create_seconds = 0, download_seconds = 0;
+	double vector_bytes = 0;
+};

@@ -1,0 +1,399 @@
+// The kernels of the smoothed-aggregation AMG (include/spmv_mi355x.h "AMG", amg.hpp for the mapping): steps 1 to 5 of the setup, one
+// lane per row; the three vector kernels of the cycle; the dense coarsest solve. The arithmetic is the header's, as written: this
+// file is compiled with contraction off, and every fma in it is spelled out.
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+
+#include "amg.hpp"
+#include "solvers_common.hpp"
+
+#pragma clang fp contract(off)
+
+namespace spmv {
+
+#define AMG_ROWS(i, n) for (long i = (long) blockIdx.x * AMG_TB + threadIdx.x; i < (n); i += (long) gridDim.x * AMG_TB)
+
+// j in S(i), j != i: a_ij^2 >= theta^2 (d_i d_j). No sqrt, no contraction.
+__device__ __forceinline__ bool
+amg_strong(double a, double di, double dj, double theta2)
+{
+	return a * a >= theta2 * (di * dj);
+}
+
+__device__ __forceinline__ unsigned long long
+amg_key(int state, long i)
+{
+	const unsigned h = (unsigned) i * AMG_HASH_MUL;
+	return ((unsigned long long) state << 62) | ((unsigned long long) (h >> 1) << 31) | (unsigned long long) i;
+}
+
+__global__ __launch_bounds__(AMG_TB) void
+amg_diag_kernel(AmgCsr a, double * __restrict__ d, double * __restrict__ part)
+{
+	__shared__ double sh[AMG_TB];
+	double worst = 0;
+	AMG_ROWS(i, a.n)
+	{
+		double di = 0, sum = 0;
+		bool found = false;
+		for (int e = a.rp[i]; e < a.rp[i + 1]; e++)
+		{
+			const double v = a.va[e];
+			if (!found && a.ci[e] == i)
+			{
+				di = v;
+				found = true;
+			}
+			sum = sum + fabs(v);
+		}
+		d[i] = di;
+		worst = fmax(worst, sum / di);
+	}
+	sh[threadIdx.x] = worst;
+	__syncthreads();
+	for (int s = AMG_TB / 2; s > 0; s >>= 1)
+	{
+		if ((int) threadIdx.x < s)
+			sh[threadIdx.x] = fmax(sh[threadIdx.x], sh[threadIdx.x + s]);
+		__syncthreads();
+	}
+	if (threadIdx.x == 0)
+		part[blockIdx.x] = sh[0];
+}
+
+__global__ __launch_bounds__(AMG_TB) void
+amg_mis_init_kernel(long n, int * __restrict__ state, unsigned long long * __restrict__ key0)
+{
+	AMG_ROWS(i, n)
+	{
+		state[i] = 1;
+		key0[i] = amg_key(1, i);
+	}
+}
+
+__global__ __launch_bounds__(AMG_TB) void
+amg_mis_sweep_kernel(AmgCsr a, const double * __restrict__ d, double theta2, const unsigned long long * __restrict__ in,
+		unsigned long long * __restrict__ out)
+{
+	AMG_ROWS(i, a.n)
+	{
+		const double di = d[i];
+		unsigned long long best = in[i];
+		for (int e = a.rp[i]; e < a.rp[i + 1]; e++)
+		{
+			const int j = a.ci[e];
+			if (j != i && amg_strong(a.va[e], di, d[j], theta2))
+				best = max(best, in[j]);
+		}
+		out[i] = best;
+	}
+}
+
+__global__ __launch_bounds__(AMG_TB) void
+amg_mis_decide_kernel(long n, int * __restrict__ state, unsigned long long * __restrict__ key0, const unsigned long long * __restrict__ key2,
+		int * __restrict__ undecided)
+{
+	__shared__ int sh[AMG_TB];
+	int left = 0;
+	AMG_ROWS(i, n)
+	{
+		if (state[i] != 1)
+			continue;
+		const unsigned long long k = key2[i];
+		int s = 1;
+		if (k == key0[i])
+			s = 2;
+		else if ((k >> 62) == 2)
+			s = 0;
+		if (s != 1)
+		{
+			state[i] = s;
+			key0[i] = amg_key(s, i);
+		}
+		else
+			left++;
+	}
+	sh[threadIdx.x] = left;
+	__syncthreads();
+	for (int s = AMG_TB / 2; s > 0; s >>= 1)
+	{
+		if ((int) threadIdx.x < s)
+			sh[threadIdx.x] += sh[threadIdx.x + s];
+		__syncthreads();
+	}
+	if (threadIdx.x == 0 && sh[0] > 0)
+		atomicAdd(undecided, sh[0]);                      // an integer count: its sum does not depend on the order
+}
+
+__global__ __launch_bounds__(AMG_TB) void
+amg_root_flag_kernel(long n, const int * __restrict__ state, int * __restrict__ flag)
+{
+	AMG_ROWS(i, n)
+		flag[i] = state[i] == 2;
+}
+
+// a root takes its own number; a node with a root in S(i) that root's (roots lie more than 2 apart: there is at most one); else -1
+__global__ __launch_bounds__(AMG_TB) void
+amg_agg_pass1_kernel(AmgCsr a, const double * __restrict__ d, double theta2, const int * __restrict__ state, const int * __restrict__ id,
+		int * __restrict__ agg1)
+{
+	AMG_ROWS(i, a.n)
+	{
+		int g = -1;
+		if (state[i] == 2)
+			g = id[i];
+		else
+		{
+			const double di = d[i];
+			for (int e = a.rp[i]; e < a.rp[i + 1]; e++)
+			{
+				const int j = a.ci[e];
+				if (j != i && state[j] == 2 && amg_strong(a.va[e], di, d[j], theta2))
+					g = id[j];
+			}
+		}
+		agg1[i] = g;
+	}
+}
+
+// a node still free takes the aggregate of its assigned strong neighbour with the largest |a_ij|, ties to the smallest j
+__global__ __launch_bounds__(AMG_TB) void
+amg_agg_pass2_kernel(AmgCsr a, const double * __restrict__ d, double theta2, const int * __restrict__ agg1, int * __restrict__ agg2)
+{
+	AMG_ROWS(i, a.n)
+	{
+		int g = agg1[i];
+		if (g < 0)
+		{
+			const double di = d[i];
+			double best = -1.0;
+			int best_j = 0x7fffffff;
+			for (int e = a.rp[i]; e < a.rp[i + 1]; e++)
+			{
+				const int j = a.ci[e];
+				const double v = a.va[e];
+				if (j == i || agg1[j] < 0 || !amg_strong(v, di, d[j], theta2))
+					continue;
+				const double m = fabs(v);
+				if (m > best || (m == best && j < best_j))
+				{
+					best = m;
+					best_j = j;
+					g = agg1[j];
+				}
+			}
+		}
+		agg2[i] = g;
+	}
+}
+
+// P_ij = (agg(i) == j ? 1 : 0) - (omega / d_i) * (A T)_ij over the entries of row i of A T
+__global__ __launch_bounds__(AMG_TB) void
+amg_prolong_kernel(long n, const int * __restrict__ at_rp, const int * __restrict__ at_ci, const double * __restrict__ at_va,
+		const int * __restrict__ agg, const double * __restrict__ d, double omega, double * __restrict__ p_va)
+{
+	AMG_ROWS(i, n)
+	{
+		const double scale = omega / d[i];
+		const int g = agg[i];
+		for (int e = at_rp[i]; e < at_rp[i + 1]; e++)
+			p_va[e] = (at_ci[e] == g ? 1.0 : 0.0) - scale * at_va[e];
+	}
+}
+
+// ---- the cycle -----------------------------------------------------------------------------------------------------------------------
+
+template <typename T>
+__global__ __launch_bounds__(VB) void
+amg_first_kernel(const T * __restrict__ w, const T * __restrict__ b, T * __restrict__ x, long n)
+{
+	GRID_STRIDE(i, n)
+		x[i] = w[i] * b[i];
+}
+
+template <typename T>
+__global__ __launch_bounds__(VB) void
+amg_sweep_kernel(const T * __restrict__ w, const T * __restrict__ b, const T * __restrict__ t, T * __restrict__ x, long n)
+{
+	GRID_STRIDE(i, n)
+		x[i] = x[i] + w[i] * (b[i] - t[i]);
+}
+
+template <typename T>
+__global__ __launch_bounds__(VB) void
+amg_residual_kernel(const T * __restrict__ b, T * __restrict__ t, long n)
+{
+	GRID_STRIDE(i, n)
+		t[i] = b[i] - t[i];
+}
+
+// L y = b column by column, then L^t x = y: lane a keeps y_a in a register, the lane of the column posts y_k / L_kk, one barrier,
+// and the lanes below (above, on the way back) take their fma. Every lane runs all n trips of both loops.
+template <typename T>
+__global__ __launch_bounds__(AMG_DENSE_MAX) void
+amg_dense_solve_kernel(const double * __restrict__ Lg, const T * __restrict__ b, T * __restrict__ x, int n)
+{
+	__shared__ double L[AMG_DENSE_MAX * (AMG_DENSE_MAX + 1) / 2];
+	__shared__ double piv[AMG_DENSE_MAX];
+	const int a = threadIdx.x;
+	const int row = a * (a + 1) / 2;
+	for (int e = a; e < n * (n + 1) / 2; e += AMG_DENSE_MAX)
+		L[e] = Lg[e];
+	double y = a < n ? (double) b[a] : 0.0;
+	__syncthreads();
+	for (int k = 0; k < n; k++)
+	{
+		if (a == k)
+			piv[k] = y / L[row + k];
+		__syncthreads();
+		if (a > k && a < n)
+			y = fma(-L[row + k], piv[k], y);
+	}
+	y = a < n ? piv[a] : 0.0;
+	__syncthreads();
+	for (int k = n - 1; k >= 0; k--)
+	{
+		if (a == k)
+			piv[k] = y / L[row + k];
+		__syncthreads();
+		if (a < k)
+			y = fma(-L[k * (k + 1) / 2 + a], piv[k], y);
+	}
+	if (a < n)
+		x[a] = (T) piv[a];
+}
+
+// ---- launchers -----------------------------------------------------------------------------------------------------------------------
+
+#define AMG_LAUNCH(kernel, n, st, ...)                                                          \
+	do {                                                                                        \
+		if ((n) > 0)                                                                            \
+			hipLaunchKernelGGL(kernel, dim3(amg_grid(n)), dim3(AMG_TB), 0, st, __VA_ARGS__);    \
+		HIP_TRY(hipGetLastError());                                                             \
+		return 0;                                                                               \
+	} while (0)
+
+int
+launch_amg_diag(const AmgCsr & a, double * d, double * part, hipStream_t st)
+{
+	AMG_LAUNCH(amg_diag_kernel, a.n, st, a, d, part);
+}
+
+int
+launch_amg_mis_init(long n, int * state, unsigned long long * key0, hipStream_t st)
+{
+	AMG_LAUNCH(amg_mis_init_kernel, n, st, n, state, key0);
+}
+
+int
+launch_amg_mis_sweep(const AmgCsr & a, const double * d, double theta2, const unsigned long long * in, unsigned long long * out, hipStream_t st)
+{
+	AMG_LAUNCH(amg_mis_sweep_kernel, a.n, st, a, d, theta2, in, out);
+}
+
+int
+launch_amg_mis_decide(long n, int * state, unsigned long long * key0, const unsigned long long * key2, int * undecided, hipStream_t st)
+{
+	AMG_LAUNCH(amg_mis_decide_kernel, n, st, n, state, key0, key2, undecided);
+}
+
+size_t
+amg_scan_bytes(long n)
+{
+	size_t bytes = 0;
+	(void) hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, (const int *) nullptr, (int *) nullptr, (int) n);
+	return bytes;
+}
+
+int
+launch_amg_number_roots(long n, const int * state, int * flag, int * id, void * scan_tmp, size_t scan_bytes, hipStream_t st)
+{
+	if (n <= 0)
+		return 0;
+	hipLaunchKernelGGL(amg_root_flag_kernel, dim3(amg_grid(n)), dim3(AMG_TB), 0, st, n, state, flag);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, (const int *) flag, id, (int) n, st));
+	return 0;
+}
+
+int
+launch_amg_agg_pass1(const AmgCsr & a, const double * d, double theta2, const int * state, const int * id, int * agg1, hipStream_t st)
+{
+	AMG_LAUNCH(amg_agg_pass1_kernel, a.n, st, a, d, theta2, state, id, agg1);
+}
+
+int
+launch_amg_agg_pass2(const AmgCsr & a, const double * d, double theta2, const int * agg1, int * agg2, hipStream_t st)
+{
+	AMG_LAUNCH(amg_agg_pass2_kernel, a.n, st, a, d, theta2, agg1, agg2);
+}
+
+int
+launch_amg_prolong(long n, const int * at_rp, const int * at_ci, const double * at_va, const int * agg, const double * d, double omega,
+		double * p_va, hipStream_t st)
+{
+	AMG_LAUNCH(amg_prolong_kernel, n, st, n, at_rp, at_ci, at_va, agg, d, omega, p_va);
+}
+
+int
+launch_amg_first(bool f32, const void * w, const void * b, void * x, long n, hipStream_t st)
+{
+	if (n > 0)
+	{
+		if (f32)
+			hipLaunchKernelGGL((amg_first_kernel<float>), dim3(solver_blocks(n)), dim3(VB), 0, st, (const float *) w, (const float *) b,
+					(float *) x, n);
+		else
+			hipLaunchKernelGGL((amg_first_kernel<double>), dim3(solver_blocks(n)), dim3(VB), 0, st, (const double *) w, (const double *) b,
+					(double *) x, n);
+	}
+	HIP_TRY(hipGetLastError());
+	return 0;
+}
+
+int
+launch_amg_sweep(bool f32, const void * w, const void * b, const void * t, void * x, long n, hipStream_t st)
+{
+	if (n > 0)
+	{
+		if (f32)
+			hipLaunchKernelGGL((amg_sweep_kernel<float>), dim3(solver_blocks(n)), dim3(VB), 0, st, (const float *) w, (const float *) b,
+					(const float *) t, (float *) x, n);
+		else
+			hipLaunchKernelGGL((amg_sweep_kernel<double>), dim3(solver_blocks(n)), dim3(VB), 0, st, (const double *) w, (const double *) b,
+					(const double *) t, (double *) x, n);
+	}
+	HIP_TRY(hipGetLastError());
+	return 0;
+}
+
+int
+launch_amg_residual(bool f32, const void * b, void * t, long n, hipStream_t st)
+{
+	if (n > 0)
+	{
+		if (f32)
+			hipLaunchKernelGGL((amg_residual_kernel<float>), dim3(solver_blocks(n)), dim3(VB), 0, st, (const float *) b, (float *) t, n);
+		else
+			hipLaunchKernelGGL((amg_residual_kernel<double>), dim3(solver_blocks(n)), dim3(VB), 0, st, (const double *) b, (double *) t, n);
+	}
+	HIP_TRY(hipGetLastError());
+	return 0;
+}
+
+int
+launch_amg_dense_solve(bool f32, const double * L, const void * b, void * x, int n, hipStream_t st)
+{
+	if (n > 0)
+	{
+		if (f32)
+			hipLaunchKernelGGL((amg_dense_solve_kernel<float>), dim3(1), dim3(AMG_DENSE_MAX), 0, st, L, (const float *) b, (float *) x, n);
+		else
+			hipLaunchKernelGGL((amg_dense_solve_kernel<double>), dim3(1), dim3(AMG_DENSE_MAX), 0, st, L, (const double *) b, (double *) x, n);
+	}
+	HIP_TRY(hipGetLastError());
+	return 0;
+}
+
+}  // namespace spmv

@@ -32,10 +32,11 @@
 // what they write is q and z, scratch that only the predicated kernels read. x, r, p, the state and the history are written only
 // by kernels that return at once when `done` is set. So after a stop nothing the caller sees moves.
 //
-// TWO ENTRIES, ONE BODY. pcg_tri_solve takes "enqueue z = M^-1 r" as a callable: TriApply (spmv_mi355x_pcg_tri: tri_precond.hpp's
+// THREE ENTRIES, ONE BODY. pcg_tri_solve takes "enqueue z = M^-1 r" as a callable: TriApply (spmv_mi355x_pcg_tri: tri_precond.hpp's
 // three parts) or FsaiApply (spmv_mi355x_pcg_fsai: the two SpMVs G^t (G r) of an fsai handle, fsai.hip). The freeze carries over:
 // the two SpMVs know nothing of `done` either, and what they write is the fsai handle's scratch vector and z. Per iteration of
-// pcg_fsai: 3 SpMVs (A, G, G^t) and the 4 vector launches.
+// pcg_fsai: 3 SpMVs (A, G, G^t) and the 4 vector launches. AmgApply (spmv_mi355x_pcg_amg: one V cycle of an amg handle, amg.hip) is
+// the third: the cycle's SpMVs and vector kernels write the hierarchy's own vectors and z, so the freeze holds for it as well.
 
 #include <chrono>
 #include <cmath>
@@ -44,6 +45,7 @@
 
 #include "common.hpp"
 #include "solvers_common.hpp"
+#include "amg.hpp"
 #include "fsai.hpp"
 #include "tri_precond.hpp"
 #include "trsv.hpp"
@@ -427,6 +429,16 @@ struct FsaiApply {
 	}
 };
 
+// z = M^-1 r of pcg_amg: one V cycle of an amg handle. Its SpMVs and vector kernels write the hierarchy's own vectors and z, nothing else.
+struct AmgApply {
+	spmv_mi355x_amg * M;
+	template <typename T>
+	int operator()(const T * r, T * z, const T *, long, dim3, hipStream_t stream) const
+	{
+		return spmv_mi355x_amg_apply_device_async(M, r, z, stream);
+	}
+};
+
 }  // namespace spmv
 
 extern "C" int
@@ -479,4 +491,33 @@ spmv_mi355x_pcg_fsai(spmv_mi355x_matrix * A, const void * b_host, void * x_out_h
 	if (precision == SPMV_MI355X_F32)
 		return pcg_tri_solve<float, true>("pcg_fsai", A, b_host, x_out_host, nullptr, apply, tol, max_iterations, history_out, info);
 	return pcg_tri_solve<double, true>("pcg_fsai", A, b_host, x_out_host, nullptr, apply, tol, max_iterations, history_out, info);
+}
+
+extern "C" int
+spmv_mi355x_pcg_amg(spmv_mi355x_matrix * A, const void * b_host, void * x_out_host, spmv_mi355x_amg * M, double tol,
+		long max_iterations, double * history_out, spmv_mi355x_pcg_tri_info * info)
+{
+	using namespace spmv;
+	if (!pcg_tri_arguments_ok("pcg_amg", A, b_host, x_out_host, tol, max_iterations, info))
+		return 1;
+	if (!M)
+	{
+		set_error("pcg_amg: M is NULL: spmv_mi355x_pcg_tri with M = NULL is the solve without a preconditioner");
+		return 1;
+	}
+	const long n = spmv_mi355x_cols(A);
+	const int precision = spmv_mi355x_precision(A), device = spmv_mi355x_device(A);
+	if (M->n != n)
+		set_error("pcg_amg: M is a preconditioner of %ld rows, the matrix has %ld", M->n, n);
+	else if (M->precision != precision)
+		set_error("pcg_amg: M has precision %d, the matrix %d: both must be the same", M->precision, precision);
+	else if (M->device != device)
+		set_error("pcg_amg: M lives on device %d, the matrix on device %d", M->device, device);
+	if (M->n != n || M->precision != precision || M->device != device)
+		return 1;
+	HIP_TRY(hipSetDevice(device));
+	const AmgApply apply = {M};
+	if (precision == SPMV_MI355X_F32)
+		return pcg_tri_solve<float, true>("pcg_amg", A, b_host, x_out_host, nullptr, apply, tol, max_iterations, history_out, info);
+	return pcg_tri_solve<double, true>("pcg_amg", A, b_host, x_out_host, nullptr, apply, tol, max_iterations, history_out, info);
 }

@@ -71,6 +71,9 @@ SYMBOLS = [
     "spmv_mi355x_fsai_setup_split", "spmv_mi355x_fsai_mem_footprint", "spmv_mi355x_pcg_fsai",
     "spmv_mi355x_spgemm_create", "spmv_mi355x_spgemm_destroy", "spmv_mi355x_spgemm_pattern", "spmv_mi355x_spgemm_multiply",
     "spmv_mi355x_spgemm_multiply_device_async", "spmv_mi355x_spgemm_info",
+    "spmv_mi355x_amg_create", "spmv_mi355x_amg_destroy", "spmv_mi355x_amg_apply_device_async", "spmv_mi355x_amg_apply",
+    "spmv_mi355x_amg_info", "spmv_mi355x_amg_level_matrices", "spmv_mi355x_amg_aggregates", "spmv_mi355x_amg_level_csr",
+    "spmv_mi355x_amg_mem_footprint", "spmv_mi355x_pcg_amg",
 ]
 
 _lib = None
@@ -120,6 +123,10 @@ def lib():
         L.spmv_mi355x_pcg_fsai.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_long, C.c_void_p,
                                            C.POINTER(PcgTriInfo)]
         L.spmv_mi355x_fsai_mem_footprint.restype = C.c_double
+        L.spmv_mi355x_pcg_amg.restype = C.c_int
+        L.spmv_mi355x_pcg_amg.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_long, C.c_void_p,
+                                          C.POINTER(PcgTriInfo)]
+        L.spmv_mi355x_amg_mem_footprint.restype = C.c_double
         _lib = L
     return _lib
 
@@ -461,6 +468,125 @@ class Fsai:
                 if M is not None:
                     M.close()
             lib().spmv_mi355x_fsai_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class AmgOpts(C.Structure):
+    """spmv_mi355x_amg_opts (include/spmv_mi355x.h "AMG")"""
+    _fields_ = [("struct_size", C.c_int), ("theta", C.c_double), ("max_levels", C.c_int), ("coarse_rows", C.c_int),
+                ("sweeps", C.c_int), ("coarse_sweeps", C.c_int)]
+
+
+AMG_MAX_LEVELS = 16
+AMG_DEFAULTS = dict(theta=0.08, max_levels=10, coarse_rows=128, sweeps=1, coarse_sweeps=4)
+AMG_COARSE_KINDS = ("dense", "sweeps", "sweeps after a failed pivot")
+AMG_A, AMG_P = 0, 1
+
+
+class AmgStats(C.Structure):
+    """spmv_mi355x_amg_stats (include/spmv_mi355x.h "AMG")"""
+    _fields_ = [("struct_size", C.c_uint), ("levels", C.c_int), ("coarse_kind", C.c_int), ("stalled", C.c_int),
+                ("rows", C.c_long * AMG_MAX_LEVELS), ("nnz", C.c_long * AMG_MAX_LEVELS), ("nnz_p", C.c_long * AMG_MAX_LEVELS),
+                ("aggregates", C.c_long * AMG_MAX_LEVELS), ("mis_rounds", C.c_long * AMG_MAX_LEVELS),
+                ("omega", C.c_double * AMG_MAX_LEVELS), ("rho", C.c_double * AMG_MAX_LEVELS),
+                ("operator_complexity", C.c_double), ("grid_complexity", C.c_double),
+                ("spmvs_per_apply", C.c_long), ("launches_per_apply", C.c_long),
+                ("setup_seconds", C.c_double), ("coarsen_seconds", C.c_double), ("spgemm_seconds", C.c_double),
+                ("transpose_seconds", C.c_double), ("create_seconds", C.c_double), ("download_seconds", C.c_double)]
+
+
+class Amg:
+    """The smoothed-aggregation multilevel preconditioner of a symmetric positive definite matrix (include/spmv_mi355x.h "AMG"),
+    built on the GPU: apply(v) is one V(sweeps, sweeps) cycle over handles built in `fmt` with `opts`. `.A` is the borrowed handle of
+    A itself, `.levels` the number of levels. Matrix.pcg_tri(b, precond=<Amg>) preconditions CG with it."""
+
+    def __init__(self, row_ptr, col_idx, values, n, fmt="sell_c_sigma", dtype=np.float64, theta=AMG_DEFAULTS["theta"],
+                 max_levels=AMG_DEFAULTS["max_levels"], coarse_rows=AMG_DEFAULTS["coarse_rows"], sweeps=AMG_DEFAULTS["sweeps"],
+                 coarse_sweeps=AMG_DEFAULTS["coarse_sweeps"], **opts):
+        row_ptr = np.ascontiguousarray(row_ptr, np.int32)
+        col_idx = np.ascontiguousarray(col_idx, np.int32)
+        values = np.ascontiguousarray(values, np.float64)
+        self.dtype = np.dtype(dtype)
+        self.n = int(n)
+        self.fmt = fmt
+        self.h = C.c_void_p()
+        self._lent = []
+        o = _make_opts(opts)
+        a = AmgOpts(C.sizeof(AmgOpts), theta, max_levels, coarse_rows, sweeps, coarse_sweeps)
+        fmt_id = FORMATS[fmt] if isinstance(fmt, str) else fmt
+        _check(lib().spmv_mi355x_amg_create(C.byref(self.h), fmt_id, F64 if self.dtype == np.float64 else F32, C.c_long(n),
+                                            _p(row_ptr), _p(col_idx), _p(values), C.byref(a), C.byref(o)))
+        self.mem_footprint = lib().spmv_mi355x_amg_mem_footprint(self.h)
+        self.levels = self.info()["levels"]
+        self.A = self.level_matrices(0)[0] if self.levels else None
+
+    def info(self):
+        """dict of spmv_mi355x_amg_stats: the per-level arrays cut to `levels` entries, coarse_kind also as coarse ("dense",
+        "sweeps", "sweeps after a failed pivot")"""
+        s = AmgStats()
+        s.struct_size = C.sizeof(AmgStats)
+        _check(lib().spmv_mi355x_amg_info(self.h, C.byref(s)))
+        out = {}
+        for k, t in AmgStats._fields_:
+            if k != "struct_size":
+                v = getattr(s, k)
+                out[k] = list(v)[:s.levels] if hasattr(v, "__len__") else v
+        out["coarse"] = AMG_COARSE_KINDS[s.coarse_kind]
+        return out
+
+    def level_matrices(self, level):
+        """(A_l, P_l, R_l) as Matrix objects over borrowed handles; P and R are None on the last level"""
+        ptrs = [C.c_void_p(), C.c_void_p(), C.c_void_p()]
+        _check(lib().spmv_mi355x_amg_level_matrices(self.h, C.c_int(level), *[C.byref(q) for q in ptrs]))
+        out = tuple(Matrix(None, None, None, 0, 0, self.fmt, self.dtype, _handle=q, _borrowed=True) if q else None for q in ptrs)
+        self._lent.extend(M for M in out if M is not None)
+        return out
+
+    def aggregates(self, level):
+        """the aggregate of every row of level `level` (int32); empty where the level was not coarsened"""
+        info = self.info()
+        if not 0 <= level < info["levels"]:
+            raise IndexError(f"level {level} of {info['levels']}")
+        out = np.full(max(info["rows"][level], 1), -1, np.int32)
+        _check(lib().spmv_mi355x_amg_aggregates(self.h, C.c_int(level), _p(out)))
+        return out[:info["rows"][level] if info["mis_rounds"][level] else 0]
+
+    def level_csr(self, level, which="A"):
+        """(row_ptr, col_idx, values) in fp64 of A_l (which = "A") or P_l ("P"): what the handles were built from"""
+        info = self.info()
+        if not 0 <= level < info["levels"]:
+            raise IndexError(f"level {level} of {info['levels']}")
+        nnz = info["nnz_p" if which == "P" else "nnz"][level]
+        rp = np.zeros(info["rows"][level] + 1, np.int32)
+        ci, va = np.zeros(max(nnz, 1), np.int32), np.zeros(max(nnz, 1))
+        _check(lib().spmv_mi355x_amg_level_csr(self.h, C.c_int(level), C.c_int(AMG_P if which == "P" else AMG_A), _p(rp), _p(ci), _p(va)))
+        return rp, ci[:nnz], va[:nnz]
+
+    def apply(self, v):
+        """one cycle M^-1 v for a host vector of n values (spmv_mi355x_amg_apply; blocking)"""
+        v = np.ascontiguousarray(v, self.dtype)
+        if v.shape != (self.n,):
+            raise ValueError(f"v must have {self.n} values, got {v.shape}")
+        out = np.full(max(self.n, 1), np.nan, self.dtype)
+        _check(lib().spmv_mi355x_amg_apply(self.h, _p(v), _p(out)))
+        return out[:self.n]
+
+    def apply_device(self, in_ptr, out_ptr, stream=None):
+        """The same on device pointers (in_ptr == out_ptr: in place), enqueued on `stream` (spmv_mi355x_amg_apply_device_async)"""
+        _check(lib().spmv_mi355x_amg_apply_device_async(self.h, C.c_void_p(in_ptr), C.c_void_p(out_ptr), C.c_void_p(stream or 0)))
+
+    def close(self):
+        if getattr(self, "h", None) is not None and self.h:
+            for M in self._lent:
+                M.close()
+            self._lent = []
+            lib().spmv_mi355x_amg_destroy(self.h)
             self.h = None
 
     def __del__(self):
@@ -1044,18 +1170,19 @@ class Matrix:
         spmv_mi355x_pcg_tri_info fields plus x (rows values) and history (|r| of the recurrence after each iteration, shape
         (iterations,), or None). `precond` = (first, scale, second) applies second^-1 (scale * (first^-1 v)) as M^-1: first / second
         are TriangularSolve handles or None, scale an array of rows values or None (sgs_precond builds the SGS of A); None is the
-        plain CG. An Fsai object as `precond` applies its G^t (G v) instead (spmv_mi355x_pcg_fsai)."""
+        plain CG. An Fsai object as `precond` applies its G^t (G v) instead (spmv_mi355x_pcg_fsai), an Amg object its V cycle
+        (spmv_mi355x_pcg_amg)."""
         b = np.ascontiguousarray(b, self.dtype)
         if b.shape != (self.m,):
             raise ValueError(f"b must have {self.m} values, got {b.shape}")
         M = None
-        if isinstance(precond, Fsai):
+        if isinstance(precond, (Fsai, Amg)):
             x = np.zeros(max(self.m, 1), self.dtype)
             hist = np.zeros(max(max_iterations, 1), np.float64) if history else None
             info = PcgTriInfo()
             info.struct_size = C.sizeof(PcgTriInfo)
-            _check(lib().spmv_mi355x_pcg_fsai(self.h, _p(b), _p(x), precond.h, tol, max_iterations, _p(hist) if history else None,
-                                              C.byref(info)))
+            solve = lib().spmv_mi355x_pcg_fsai if isinstance(precond, Fsai) else lib().spmv_mi355x_pcg_amg
+            _check(solve(self.h, _p(b), _p(x), precond.h, tol, max_iterations, _p(hist) if history else None, C.byref(info)))
             out = {k: getattr(info, k) for k, _ in PcgTriInfo._fields_ if k != "struct_size"}
             out["x"] = x[:self.m]
             out["history"] = hist[:info.iterations] if history else None

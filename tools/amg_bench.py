@@ -1,0 +1,172 @@
+"""What the smoothed-aggregation AMG (spmv_mi355x_amg_*; include/spmv_mi355x.h "AMG") buys the tol-based CG in iterations AND in
+seconds, what it costs to set up, and what one cycle costs against one SpMV of A. Follows tools/fsai_bench.py: one sell_c_sigma handle
+of A, tol 1e-8, and for every variant
+    none | fsai = Fsai on tril(A) | amg t=<theta> = Amg with every theta of --theta
+in one process, alternating window by window (window 0 warms every leg up and is dropped):
+  spmv:      time_device(A), HIP events over --reps back-to-back launches;
+  apply:     for the preconditioned variants, HIP events over --reps back-to-back apply_device calls;
+  solve:     the whole call to --tol: iterations, stop, info.seconds (the setup is not in it);
+  iteration: a call with tol = 0 and max_iterations = --steps, minus a call with max_iterations = 0, over --steps.
+Operators:
+  stencil<N>   the 27-point stencil of tools/solver_bench.py with --stencil-diag on the diagonal (27: cond 53). Its off-diagonals
+               are -1 against a diagonal of 27: a_ij^2 / (d_i d_j) = 1 / 729 = 0.0014 lies below theta^2 = 0.0064 of the default
+               theta, so the default hierarchy stalls at one level; 0.03 (0.0009) makes all 26 neighbours strong.
+  grid2d<N>    the 5-point Laplacian on an N x N grid plus --shift on the diagonal (4 + shift, four neighbours of -1): the operator on
+               which the one-level counts grow with N.
+The setup of every handle is reported once (it is not repeated per window): for AMG the split of amg_info (coarsening kernels, SpGEMM,
+transposition, handle creation, downloads), the rows per level and the operator complexity. The medians over the windows are
+reported with their min .. max spreads. No threshold is set and no speed is promised.
+
+    python tools/amg_bench.py                                        # stencil160 fp64
+    python tools/amg_bench.py --runs grid2d2000:f64 --theta 0.08
+One JSON line per variant, and a table at the end."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "spmv-research_amd", "python"), os.path.join(ROOT, "tools")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+
+def grid2d(k, shift):
+    """(row_ptr, col_idx, values, n) of the 5-point operator on a k x k grid: 4 + shift on the diagonal, -1 to the four neighbours"""
+    import scipy.sparse as sp
+    I, E = sp.identity(k, format="csr"), sp.diags([-np.ones(k - 1), -np.ones(k - 1)], [-1, 1], format="csr")
+    A = (sp.kron(I, E) + sp.kron(E, I) + (4.0 + shift) * sp.identity(k * k, format="csr")).tocsr()
+    A.sort_indices()
+    return A.indptr.astype(np.int32), A.indices.astype(np.int32), A.data.astype(np.float64), k * k
+
+
+def run(E, torch, workload, dts, args):
+    if workload.startswith("stencil"):
+        from solver_bench import stencil27
+        rp, ci, va, n = stencil27(int(workload[len("stencil"):]), args.stencil_diag)
+    elif workload.startswith("grid2d"):
+        rp, ci, va, n = grid2d(int(workload[len("grid2d"):]), args.shift)
+    else:
+        raise SystemExit(f"amg_bench.py runs on stencil<N> and grid2d<N>, not on {workload}")
+    rp = np.asarray(rp, np.int32)
+    np_dtype = np.float32 if dts == "f32" else np.float64
+    tdt = torch.float32 if dts == "f32" else torch.float64
+    MA = E.Matrix(rp, ci, va, n, n, "sell_c_sigma", np_dtype)
+    xa = (torch.rand(n, device="cuda", dtype=torch.float64) * 2 - 1).to(tdt)
+    ya = torch.empty(n + 64, dtype=tdt, device="cuda")
+    stream = torch.cuda.current_stream()
+    b = np.random.default_rng(7).uniform(-1, 1, n).astype(np_dtype)
+    variants = [("none", None, {})]
+    t0 = time.perf_counter()
+    F = E.Fsai(rp, ci, va, n, None, "sell_c_sigma", np_dtype)
+    variants.append(("fsai", F, dict(setup_seconds=round(F.info()["setup_seconds"], 4), wall_setup_seconds=round(time.perf_counter() - t0, 4))))
+    print(f"# built fsai: {variants[-1][2]}", flush=True)
+    for theta in args.theta:
+        t0 = time.perf_counter()
+        M = E.Amg(rp, ci, va, n, "sell_c_sigma", np_dtype, theta=theta, sweeps=args.sweeps)
+        wall = time.perf_counter() - t0
+        info = M.info()
+        extra = dict(theta=theta, sweeps=args.sweeps, levels=info["levels"], rows=info["rows"], nnz=info["nnz"], mis_rounds=info["mis_rounds"],
+                     coarse=info["coarse"], stalled=info["stalled"], operator_complexity=round(info["operator_complexity"], 4),
+                     grid_complexity=round(info["grid_complexity"], 4), spmvs_per_apply=info["spmvs_per_apply"],
+                     launches_per_apply=info["launches_per_apply"], wall_setup_seconds=round(wall, 4),
+                     **{k: round(info[k], 4) for k in ("setup_seconds", "coarsen_seconds", "spgemm_seconds", "transpose_seconds",
+                                                       "create_seconds", "download_seconds")},
+                     mem_over_a=round(M.mem_footprint / MA.mem_footprint, 3))
+        variants.append((f"amg t={theta:g}", M, extra))
+        print(f"# built {variants[-1][0]}: {extra}", flush=True)
+    solve = lambda M, tol, steps: MA.pcg_tri(b, precond=M, tol=tol, max_iterations=steps, history=False)
+
+    def time_apply(M):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for _ in range(args.reps):
+            M.apply_device(xa.data_ptr(), ya.data_ptr(), stream.cuda_stream)
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1) / args.reps
+
+    legs = {name: {k: [] for k in ("spmv", "seconds", "iter_ms", "ratio", "apply", "apply_ratio")} for name, _, _ in variants}
+    last = {}
+    for w in range(args.windows + 1):                         # window 0 warms every leg up and is dropped
+        for name, M, _ in variants:
+            t_a = MA.time_device(xa.data_ptr(), ya.data_ptr(), args.reps, stream.cuda_stream)
+            torch.cuda.synchronize()
+            t_f = time_apply(M) if M is not None else float("nan")
+            r = solve(M, args.tol, args.max_iterations)
+            fixed = solve(M, 0.0, 0)["seconds"]
+            s = solve(M, 0.0, args.steps)
+            # a preconditioned solve may reach r = 0 or lose r.z > 0 in the rounding floor before --steps: then the leg is not timed
+            t_c = (s["seconds"] - fixed) * 1e3 / args.steps if (s["iterations"], s["stop"]) == (args.steps, 2) else float("nan")
+            last[name] = r
+            if w:
+                for key, t in zip(legs[name], (t_a, r["seconds"], t_c, t_c / t_a, t_f, t_f / t_a)):
+                    legs[name][key].append(t)
+        print(f"# window {w} done", flush=True)
+    rows = []
+    for name, M, extra in variants:
+        r = last[name]
+        rec = dict(workload=workload, dtype=dts, format=MA.format_name, n=int(n), nnz_a=int(MA.nnz), precond=name, tol=args.tol,
+                   iterations=int(r["iterations"]), stop=int(r["stop"]), rnorm_over_b=float(r["rnorm"] / r["rnorm0"]),
+                   windows=args.windows, steps=args.steps, reps=args.reps, **extra)
+        for key, ts in legs[name].items():
+            if np.isnan(ts).all():
+                continue
+            rec[key] = round(float(np.nanmedian(ts)), 5)
+            rec[key + "_spread"] = [round(float(np.nanmin(ts)), 5), round(float(np.nanmax(ts)), 5)]
+        print(json.dumps(rec), flush=True)
+        rows.append(rec)
+    for _, M, _ in variants:
+        if M is not None:
+            M.close()
+    MA.close()
+    return rows
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--runs", default="stencil160:f64", help="stencil<N>:f64|f32 or grid2d<N>:f64|f32, comma separated")
+    ap.add_argument("--theta", default="0.08,0.03", help="the strength thresholds of the AMG variants")
+    ap.add_argument("--sweeps", type=int, default=1, help="nu of the V(nu, nu) cycle")
+    ap.add_argument("--windows", type=int, default=7)
+    ap.add_argument("--tol", type=float, default=1e-8, help="the tolerance of the solve leg")
+    ap.add_argument("--max-iterations", type=int, default=5000, help="the cap of the solve leg")
+    ap.add_argument("--steps", type=int, default=50, help="iterations of the tol = 0 leg")
+    ap.add_argument("--reps", type=int, default=50, help="launches per timed SpMV / apply leg")
+    ap.add_argument("--stencil-diag", type=float, default=27.0, help="the diagonal of stencil<N> (26 neighbours of -1)")
+    ap.add_argument("--shift", type=float, default=0.001, help="the shift of grid2d<N>: 4 + shift on the diagonal")
+    args = ap.parse_args()
+    if args.windows < 5:
+        ap.error("--windows: at least 5")
+    args.theta = [float(v) for v in args.theta.split(",") if v != ""]
+    os.environ.setdefault("OMP_NUM_THREADS", "16")
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("amg_bench.py needs a GPU: the engine has no CPU path")
+    import spmv_mi355x as E
+    rows = []
+    for item in args.runs.split(","):
+        w, dts = item.split(":")[:2]
+        rows += run(E, torch, w, dts, args)
+    nan = float("nan")
+    print(f"{'workload':11s} {'dtype':5s} {'precond':>11s} {'iters':>6s} {'stop':>4s} {'seconds':>9s} {'spread':>19s} {'ms/iter':>8s} "
+          f"{'spmv ms':>8s} {'iter / spmv':>11s} {'apply ms':>9s} {'apply / spmv':>12s}")
+    for r in rows:
+        print(f"{r['workload']:11s} {r['dtype']:5s} {r['precond']:>11s} {r['iterations']:6d} {r['stop']:4d} {r['seconds']:9.4f} "
+              f"{r['seconds_spread'][0]:9.4f} ..{r['seconds_spread'][1]:8.4f} {r.get('iter_ms', nan):8.4f} {r['spmv']:8.4f} "
+              f"{r.get('ratio', nan):11.2f} {r.get('apply', nan):9.4f} {r.get('apply_ratio', nan):12.2f}")
+    print(f"{'workload':11s} {'precond':>11s} {'levels':>6s} {'coarse':>7s} {'op cx':>6s} {'spmvs':>5s} {'launches':>8s} {'setup s':>8s} {'coarsen':>8s} "
+          f"{'spgemm':>8s} {'transp':>8s} {'handles':>8s} {'download':>8s} {'wall s':>8s}  rows")
+    for r in rows:
+        if "levels" in r:
+            print(f"{r['workload']:11s} {r['precond']:>11s} {r['levels']:6d} {r['coarse'][:7]:>7s} {r['operator_complexity']:6.3f} "
+                  f"{r['spmvs_per_apply']:5d} {r['launches_per_apply']:8d} {r['setup_seconds']:8.3f} {r['coarsen_seconds']:8.3f} "
+                  f"{r['spgemm_seconds']:8.3f} {r['transpose_seconds']:8.3f} {r['create_seconds']:8.3f} {r['download_seconds']:8.3f} "
+                  f"{r['wall_setup_seconds']:8.3f}  {r['rows']}")
+
+
+if __name__ == "__main__":
+    main()

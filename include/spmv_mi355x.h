@@ -956,8 +956,8 @@ int  spmv_mi355x_spgemm_info(const spmv_mi355x_spgemm * P, spmv_mi355x_spgemm_st
  *        diagonal that is not positive and a MIS that did not end.
  *   - NOT CHECKABLE: that A is symmetric and positive definite. An indefinite A shows, if at all, as a coarse diagonal that is not
  *     positive, as coarse_kind = 2, or as stop 4 of the solver.
- *   - NOT BUILT: update_values for a hierarchy (the obvious sequel: keep the aggregates and the three plans of a level, redo the
- *     numeric passes), W- and K-cycles, filtered prolongator smoothing, near-null-space vectors other than the constant, gmres /
+ *   - NOT BUILT: update_values for a hierarchy that re-aggregates (what is built keeps the aggregates and redoes the numeric
+ *     passes: "new values for a hierarchy" below), W- and K-cycles, filtered prolongator smoothing, near-null-space vectors other than the constant, gmres /
  *     minres / multi-RHS wiring, the row-partitioned form, folding the small levels into one launch. The setup routes patterns
  *     through the host (spgemm_create and create take host arrays); the split in amg_info shows what that costs.
  * spmv_mi355x_pcg_amg is spmv_mi355x_pcg_tri with z = M^-1 r = amg_apply_device_async: the same recurrences, kernels, stop codes,
@@ -1003,6 +1003,60 @@ double spmv_mi355x_amg_mem_footprint(const spmv_mi355x_amg * M);     /* the hand
 int  spmv_mi355x_pcg_amg(spmv_mi355x_matrix * A, const void * b_host, void * x_out_host, spmv_mi355x_amg * M, double tol,
 		long max_iterations, double * history_out /* may be NULL: max_iterations doubles */,
 		spmv_mi355x_pcg_tri_info * info /* may be NULL */);
+
+/* ---- AMG: new values for a hierarchy --------------------------------------------------------------------------------------------- */
+/* update_values' rule for the hierarchy: same pattern, new numbers, the SAME AGGREGATES, no rebuild. prepare once, then update any
+ * number of times; a caller who never updates pays nothing. values are nnz(A_0) fp64 numbers in the entry order of the CSR amg_create
+ * was given.
+ * FROZEN, exactly what amg_create found from the first values: the number of levels and their rows, stalled, the aggregates, the
+ * patterns of A_l, P_l and R_l, theta, sweeps and coarse_sweeps.
+ * RECOMPUTED from the new values by steps 1, 5 and 6 above in the same pinned fp64 arithmetic: d, rho and omega of every level,
+ * w = omega / d narrowed to the handle's precision, P_l, R_l = P_l^t, A_{l+1} = R (A_l P), the dense factor of a last level of at most
+ * 128 rows and with it coarse_kind (only DENSE <-> SWEEPS_AFTER_PIVOT can flip); spmvs_per_apply and launches_per_apply follow.
+ * THE CONTRACT.
+ *   1. Same structure: a hierarchy created from V1 and updated with V2 is indistinguishable from amg_create on V2 whenever amg_create
+ *      on V2 would find the same levels and aggregates: amg_level_csr's values and amg_info's omega and rho are equal to the bit,
+ *      amg_apply gives the same bits, and every handle is byte for byte the created one (update_values' own contract).
+ *   2. Otherwise the hierarchy is, bit for bit, that of the sequential loops of tests/amg_update_reference.c, which take the
+ *      aggregates as given.
+ * amg_level_csr returns the new values afterwards (they are downloaded when asked for), amg_aggregates what it returned before; the
+ * level-0 handle stays the lent one, same pointer, and holds V2; amg_info's seconds stay those of create.
+ *   - amg_update_values_prepare, once (a second call does nothing): first every handle's update_values_state; one that takes no update
+ *     (the _unit merge layout of uniform values, col_blocks) gives rc 1, "amg_update_values_prepare: level l: A|P|R: <the handle's
+ *     reason>", the hierarchy untouched and usable. Then per coarsened level the three SpGEMM plans (A T, A P, R (A P)) are rebuilt
+ *     from the host patterns and aggregates the hierarchy keeps, the entry map P -> R is derived by the transposition's own order,
+ *     update_values_prepare runs on A_l, P_l and R_l, and the value arrays of A_l, A T, P, R and A P are allocated. None of it is
+ *     counted in amg_mem_footprint (as the handles' maps are not); amg_update_info reports the bytes and the seconds. n == 0 and
+ *     one-level hierarchies are legal.
+ *   - amg_update_values_device: ordered on hip_stream, blocking (as update_values_device). Per level one kernel computes d, the row
+ *     sums over d and the count of bad diagonals (the host reads the count and at most 1024 partial maxima), one computes w, the
+ *     handle of A_l is refreshed, and below the last level the plans' numeric passes, step 5's kernel, the gather into R's order and
+ *     the refresh of P_l and R_l follow. A dense last level is factorised on the device; a failed pivot sets coarse_kind = 2, as
+ *     create does. amg_update_values uploads the values once and calls it.
+ *   - rc 1 with a last_error that starts with "amg_update_values:" and the hierarchy untouched: a NULL handle or values; update before
+ *     prepare; a handle that takes no update; values that are not 8-byte aligned; a diagonal of level 0 that is not positive and
+ *     finite ("the diagonal of row i of level 0 ...").
+ *   - a bad diagonal or a rho that is not finite on a COARSER level is found after the finer levels were rewritten: rc 1 and state 3.
+ *     amg_apply, amg_apply_device_async and pcg_amg then refuse (rc 1, a message naming the failed update) until an update succeeds.
+ *   - amg_update_values_state, host-only: 0 = cannot (last_error says why; NULL: 0), 1 = prepare is missing, 2 = ready, 3 = the last
+ *     update failed below level 0.
+ *   - amg_update_info: struct_size is set by the caller. prepared, failed, the updates so far, the bytes prepare keeps and its
+ *     seconds, and of the last update its seconds, split into the SpGEMM numeric passes and the handles' update_values_device
+ *     (the rest: steps 1 and 5, the weights, the gather, the factor and the host's reads).
+ *   - NOT BUILT: re-aggregating when the strength pattern drifts (the caller decides and calls amg_create), update_values for fsai
+ *     and trsv handles, an asynchronous update, the row-partitioned form, filtered smoothing, W- and K-cycles. */
+typedef struct {
+	unsigned struct_size;   /* in: sizeof of the caller's struct; out: bytes written */
+	int    prepared, failed;
+	long   updates;
+	double prepare_bytes, prepare_seconds;
+	double update_seconds, spgemm_seconds, handle_seconds;   /* of the last update */
+} spmv_mi355x_amg_update_stats;
+int  spmv_mi355x_amg_update_values_prepare(spmv_mi355x_amg * M);
+int  spmv_mi355x_amg_update_values(spmv_mi355x_amg * M, const double * values_fp64_host);
+int  spmv_mi355x_amg_update_values_device(spmv_mi355x_amg * M, const double * values_fp64_dev, void * hip_stream);
+int  spmv_mi355x_amg_update_values_state(const spmv_mi355x_amg * M);
+int  spmv_mi355x_amg_update_info(const spmv_mi355x_amg * M, spmv_mi355x_amg_update_stats * info /* struct_size first */);
 
 /* Row-partitioned (multi-GPU) form of the same two solvers: one process per GPU owns the row block [row_offset,
  * row_offset + m_local) of A, b and x. The solver keeps every vector device-resident and local; the two things that cross

@@ -1,7 +1,9 @@
 // Smoothed-aggregation AMG handles (include/spmv_mi355x.h "AMG"): the checks of amg_create in the header's order, the hierarchy
 // level by level (upload A_l, steps 1 to 5 on the device with kernels_amg.hip, the products through SpGEMM plans whose values never
 // leave the device, R by the device transposition, downloads for the handles that spmv_mi355x_create builds from host arrays), the
-// dense factor of the last level, the cycle and the C ABI.
+// dense factor of the last level, the cycle and the C ABI. New values for a hierarchy (amg_update_values*): prepare builds the three
+// plans of every coarsened level once more and keeps them with the aggregates, the entry map P -> R and the value arrays; an update
+// redoes steps 1, 5 and 6 and the factor on the device and refreshes every handle in place.
 
 #include <algorithm>
 #include <chrono>
@@ -109,8 +111,24 @@ amg_check_matrix(const char * what, long n, const int32_t * rp, const int32_t * 
 }
 
 static void
+amg_update_free(AmgUpdate * u)
+{
+	if (!u)
+		return;
+	for (AmgUpdateLevel & U : u->lev)
+		for (spmv_mi355x_spgemm * p : {U.at, U.ap, U.ac})
+			if (p)
+				spmv_mi355x_spgemm_destroy(p);
+	for (void * p : u->owned)
+		(void) hipFree(p);
+	delete u;
+}
+
+static void
 amg_free(spmv_mi355x_amg * M)
 {
+	amg_update_free(M->upd);
+	M->upd = nullptr;
 	for (AmgLevel & L : M->lev)
 	{
 		for (spmv_mi355x_matrix * h : {L.A, L.P, L.R})
@@ -419,6 +437,295 @@ amg_build(spmv_mi355x_amg * M, const spmv_mi355x_opts & o)
 	return 0;
 }
 
+// ---- new values for a hierarchy ------------------------------------------------------------------------------------------------------
+
+static const char * const AMG_OPERATOR_NAMES[3] = {"A", "P", "R"};
+
+// 0 and an error "<what>: level l: X: <the handle's reason>" if a handle of the hierarchy takes no update, else 1
+static int
+amg_handles_updatable(const char * what, const spmv_mi355x_amg * M)
+{
+	for (int l = 0; l < M->levels; l++)
+	{
+		const AmgLevel & L = M->lev[(size_t) l];
+		const spmv_mi355x_matrix * const h[3] = {L.A, L.P, L.R};
+		for (int k = 0; k < 3; k++)
+			if (h[k] && spmv_mi355x_update_values_state(h[k]) == 0)
+			{
+				const std::string why = spmv_mi355x_last_error();
+				set_error("%s: level %d: %s: %s", what, l, AMG_OPERATOR_NAMES[k], why.c_str());
+				return 0;
+			}
+	}
+	return 1;
+}
+
+template <typename T>
+static int
+amg_keep(AmgUpdate * u, T ** out, size_t count, const T * host = nullptr)
+{
+	void * p = nullptr;
+	const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
+	ABI_TRY(dev_alloc_bytes(&p, bytes));
+	u->owned.push_back(p);
+	u->bytes += (double) bytes;
+	*out = (T *) p;
+	if (host && count)
+		HIP_TRY(hipMemcpy(p, host, count * sizeof(T), hipMemcpyHostToDevice));
+	return 0;
+}
+
+static int
+amg_plan(AmgUpdate * u, spmv_mi355x_spgemm ** plan, int device, long m, long k, long n, const int32_t * a_rp, const int32_t * a_ci,
+		const int32_t * b_rp, const int32_t * b_ci)
+{
+	ABI_TRY(spmv_mi355x_spgemm_create(plan, device, m, k, n, a_rp, a_ci, b_rp, b_ci));
+	u->bytes += (double) (*plan)->device_bytes;
+	return 0;
+}
+
+// what prepare keeps of level l (AmgUpdateLevel); u->lev has an entry per level already
+static int
+amg_prepare_level(spmv_mi355x_amg * M, AmgUpdate * u, int l)
+{
+	AmgLevel & L = M->lev[(size_t) l];
+	AmgUpdateLevel & U = u->lev[(size_t) l];
+	const long n = L.n;
+	ABI_TRY(amg_keep(u, &U.d_va, (size_t) L.nnz));
+	ABI_TRY(amg_keep(u, &U.d_d, (size_t) n));
+	ABI_TRY(spmv_mi355x_update_values_prepare(L.A, L.rp.data()));
+	if (!L.P)
+	{
+		int * d_rp, * d_ci;
+		ABI_TRY(amg_keep(u, &d_rp, (size_t) n + 1, (const int *) L.rp.data()));
+		ABI_TRY(amg_keep(u, &d_ci, (size_t) L.nnz, (const int *) L.ci.data()));
+		U.d_rp = d_rp;
+		U.d_ci = d_ci;
+		return 0;
+	}
+	const long nc = L.aggregates, nnz_p = L.nnz_p;
+	const AmgLevel & C = M->lev[(size_t) l + 1];
+	// A T: its pattern is P's, its copy of A_l's pattern serves step 1
+	std::vector<int32_t> t_rp((size_t) n + 1);
+	for (long i = 0; i <= n; i++)
+		t_rp[(size_t) i] = (int32_t) i;
+	ABI_TRY(amg_plan(u, &U.at, M->device, n, n, nc, L.rp.data(), L.ci.data(), t_rp.data(), L.agg.data()));
+	U.d_rp = U.at->d_a_rp;
+	U.d_ci = U.at->d_a_ci;
+	if (U.at->nnz_c != nnz_p || U.at->c_rp != L.p_rp)
+	{
+		set_error("amg_update_values_prepare: internal: level %d: the pattern of A T (%ld entries) is not that of P (%ld)", l, U.at->nnz_c, nnz_p);
+		return 1;
+	}
+	{
+		const std::vector<double> ones((size_t) n, 1.0);
+		ABI_TRY(amg_keep(u, &U.d_ones, (size_t) n, ones.data()));
+	}
+	ABI_TRY(amg_keep(u, &U.d_agg, (size_t) n, (const int *) L.agg.data()));
+	ABI_TRY(amg_keep(u, &U.d_at, (size_t) nnz_p));
+	ABI_TRY(amg_keep(u, &U.d_p, (size_t) nnz_p));
+	ABI_TRY(amg_keep(u, &U.d_r, (size_t) nnz_p));
+	// the entry map P -> R and R's pattern, in the transposition's own order
+	int * d_r_rp = nullptr;
+	long lnnz = 0;
+	ABI_TRY(transpose_entry_map(true, n, nc, nnz_p, L.p_rp.data(), L.p_ci.data(), 0, nc, &d_r_rp, &U.d_src, &lnnz));
+	u->owned.push_back(d_r_rp);
+	u->owned.push_back(U.d_src);
+	u->bytes += (double) (nc + 1) * 4 + (double) std::max<long>(lnnz, 1) * 4;
+	if (lnnz != nnz_p)
+	{
+		set_error("amg_update_values_prepare: internal: level %d: the transposition of P has %ld entries, P has %ld", l, lnnz, nnz_p);
+		return 1;
+	}
+	std::vector<int32_t> r_rp((size_t) nc + 1), r_ci((size_t) std::max<long>(nnz_p, 1)), row_of((size_t) std::max<long>(nnz_p, 1));
+	std::vector<unsigned> src((size_t) std::max<long>(nnz_p, 1));
+	HIP_TRY(hipMemcpy(r_rp.data(), d_r_rp, (size_t) (nc + 1) * 4, hipMemcpyDeviceToHost));
+	HIP_TRY(hipMemcpy(src.data(), U.d_src, (size_t) nnz_p * 4, hipMemcpyDeviceToHost));
+	for (long i = 0; i < n; i++)
+		for (long e = L.p_rp[(size_t) i]; e < L.p_rp[(size_t) i + 1]; e++)
+			row_of[(size_t) e] = (int32_t) i;
+	for (long e = 0; e < nnz_p; e++)
+	{
+		if ((long) src[(size_t) e] >= nnz_p)
+		{
+			set_error("amg_update_values_prepare: internal: level %d: entry %ld of the map P -> R is %u of %ld", l, e, src[(size_t) e], nnz_p);
+			return 1;
+		}
+		r_ci[(size_t) e] = row_of[src[(size_t) e]];
+	}
+	// A P and R (A P): the second must come back with the pattern of level l + 1
+	ABI_TRY(amg_plan(u, &U.ap, M->device, n, n, nc, L.rp.data(), L.ci.data(), L.p_rp.data(), L.p_ci.data()));
+	std::vector<int32_t> ap_rp((size_t) n + 1), ap_ci((size_t) std::max<long>(U.ap->nnz_c, 1));
+	ABI_TRY(spmv_mi355x_spgemm_pattern(U.ap, ap_rp.data(), ap_ci.data()));
+	ABI_TRY(amg_keep(u, &U.d_ap, (size_t) U.ap->nnz_c));
+	ABI_TRY(amg_plan(u, &U.ac, M->device, nc, n, nc, r_rp.data(), r_ci.data(), ap_rp.data(), ap_ci.data()));
+	std::vector<int32_t> c_rp((size_t) nc + 1), c_ci((size_t) std::max<long>(U.ac->nnz_c, 1));
+	ABI_TRY(spmv_mi355x_spgemm_pattern(U.ac, c_rp.data(), c_ci.data()));
+	c_ci.resize((size_t) U.ac->nnz_c);
+	if (U.ac->nnz_c != C.nnz || U.ac->c_rp != C.rp || !std::equal(c_ci.begin(), c_ci.end(), C.ci.begin()))
+	{
+		set_error("amg_update_values_prepare: internal: level %d: R (A P) has another pattern than level %d (%ld entries, %ld)", l, l + 1,
+				U.ac->nnz_c, C.nnz);
+		return 1;
+	}
+	ABI_TRY(spmv_mi355x_update_values_prepare(L.P, L.p_rp.data()));
+	ABI_TRY(spmv_mi355x_update_values_prepare(L.R, r_rp.data()));
+	return 0;
+}
+
+// the host copies level_csr returns, brought up to the device's after an update
+static int
+amg_refresh_host(spmv_mi355x_amg * M)
+{
+	AmgUpdate * u = M->upd;
+	if (!u || !u->host_stale)
+		return 0;
+	HIP_TRY(hipSetDevice(M->device));
+	for (int l = 0; l < M->levels; l++)
+	{
+		AmgLevel & L = M->lev[(size_t) l];
+		const AmgUpdateLevel & U = u->lev[(size_t) l];
+		if (L.nnz > 0)
+			HIP_TRY(hipMemcpy(L.va.data(), U.d_va, (size_t) L.nnz * 8, hipMemcpyDeviceToHost));
+		if (L.P && L.nnz_p > 0)
+			HIP_TRY(hipMemcpy(L.p_va.data(), U.d_p, (size_t) L.nnz_p * 8, hipMemcpyDeviceToHost));
+	}
+	u->host_stale = false;
+	return 0;
+}
+
+// step 1 of level l on `va`: d into the level's array; *bad_out = the bad diagonals, *rho_out = the largest partial
+static int
+amg_update_diag(spmv_mi355x_amg * M, int l, const double * va, hipStream_t st, int * bad_out, double * rho_out)
+{
+	AmgUpdate * u = M->upd;
+	const AmgUpdateLevel & U = u->lev[(size_t) l];
+	const long n = M->lev[(size_t) l].n;
+	const AmgCsr a = {U.d_rp, U.d_ci, va, n};
+	ABI_TRY(launch_amg_diag_check(a, U.d_d, u->d_part, u->d_count + l, st));
+	double part[AMG_MAX_GRID];
+	HIP_TRY(hipMemcpyAsync(bad_out, u->d_count + l, 4, hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipMemcpyAsync(part, u->d_part, (size_t) amg_grid(n) * 8, hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipStreamSynchronize(st));
+	*rho_out = *std::max_element(part, part + amg_grid(n));
+	return 0;
+}
+
+// the first row of level l whose diagonal is not positive and finite (an error path: n doubles come to the host)
+static int
+amg_first_bad_row(spmv_mi355x_amg * M, int l, long * row_out, double * d_out)
+{
+	const long n = M->lev[(size_t) l].n;
+	std::vector<double> d((size_t) n);
+	HIP_TRY(hipMemcpy(d.data(), M->upd->lev[(size_t) l].d_d, (size_t) n * 8, hipMemcpyDeviceToHost));
+	*row_out = -1;
+	for (long i = 0; i < n && *row_out < 0; i++)
+		if (!std::isfinite(d[(size_t) i]) || !(d[(size_t) i] > 0))
+		{
+			*row_out = i;
+			*d_out = d[(size_t) i];
+		}
+	return 0;
+}
+
+// Levels 0, 1, ... from the values of level 0 in u->lev[0].d_va; level 0's step 1 has run and passed (rho0). 1 = error set: the
+// hierarchy is partly rewritten.
+static int
+amg_update_levels(spmv_mi355x_amg * M, double rho0, hipStream_t st)
+{
+	AmgUpdate * u = M->upd;
+	const bool f32 = M->f32;
+	for (int l = 0; l < M->levels; l++)
+	{
+		AmgLevel & L = M->lev[(size_t) l];
+		AmgUpdateLevel & U = u->lev[(size_t) l];
+		const long n = L.n;
+		double rho = rho0;
+		if (l > 0)
+		{
+			int bad = 0;
+			ABI_TRY(amg_update_diag(M, l, U.d_va, st, &bad, &rho));
+			if (bad > 0)
+			{
+				long row = -1;
+				double d = 0;
+				ABI_TRY(amg_first_bad_row(M, l, &row, &d));
+				set_error("amg_update_values: the diagonal of row %ld of level %d is %g: the matrix is not positive definite", row, l, d);
+				return 1;
+			}
+			if (!std::isfinite(rho) || !(rho > 0))
+			{
+				set_error("amg_update_values: level %d: max_i sum_j |a_ij| / a_ii = %g is not a positive finite number", l, rho);
+				return 1;
+			}
+		}
+		L.rho = rho;
+		L.omega = 4.0 / (3.0 * L.rho);
+		ABI_TRY(launch_amg_weights(f32, n, U.d_d, L.omega, L.w, st));
+		auto t0 = std::chrono::steady_clock::now();
+		ABI_TRY(spmv_mi355x_update_values_device(L.A, U.d_va, st));
+		u->handle_seconds += amg_since(t0);
+		if (!L.P)
+			continue;
+		AmgUpdateLevel & C = u->lev[(size_t) l + 1];
+		t0 = std::chrono::steady_clock::now();
+		ABI_TRY(spmv_mi355x_spgemm_multiply_device_async(U.at, U.d_va, U.d_ones, U.d_at, st));
+		HIP_TRY(hipStreamSynchronize(st));
+		u->spgemm_seconds += amg_since(t0);
+		ABI_TRY(launch_amg_prolong(n, U.at->d_c_rp, U.at->d_c_ci, U.d_at, U.d_agg, U.d_d, L.omega, U.d_p, st));
+		ABI_TRY(transpose_gather_values(U.d_src, U.d_p, L.nnz_p, U.d_r, st));
+		HIP_TRY(hipStreamSynchronize(st));
+		t0 = std::chrono::steady_clock::now();
+		ABI_TRY(spmv_mi355x_spgemm_multiply_device_async(U.ap, U.d_va, U.d_p, U.d_ap, st));
+		ABI_TRY(spmv_mi355x_spgemm_multiply_device_async(U.ac, U.d_r, U.d_ap, C.d_va, st));
+		HIP_TRY(hipStreamSynchronize(st));
+		u->spgemm_seconds += amg_since(t0);
+		t0 = std::chrono::steady_clock::now();
+		ABI_TRY(spmv_mi355x_update_values_device(L.P, U.d_p, st));
+		ABI_TRY(spmv_mi355x_update_values_device(L.R, U.d_r, st));
+		u->handle_seconds += amg_since(t0);
+	}
+	// the last level: its factor, if it is small enough to have one
+	const AmgLevel & Z = M->lev.back();
+	const AmgUpdateLevel & UZ = u->lev.back();
+	if (Z.n <= AMG_DENSE_MAX)
+	{
+		int * d_failed = u->d_count + M->levels;
+		int failed = 0;
+		const size_t fbytes = (size_t) (Z.n * (Z.n + 1) / 2) * 8;
+		const AmgCsr a = {UZ.d_rp, UZ.d_ci, UZ.d_va, Z.n};
+		ABI_TRY(launch_amg_dense_factor(a, u->d_factor, d_failed, st));
+		HIP_TRY(hipMemcpyAsync(&failed, d_failed, 4, hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipStreamSynchronize(st));
+		if (failed)
+		{
+			// as create leaves it: no factor, the level takes the sweeps
+			if (M->d_factor)
+			{
+				(void) hipFree(M->d_factor);
+				M->d_factor = nullptr;
+				M->vector_bytes -= (double) fbytes;
+			}
+			M->coarse_kind = SPMV_MI355X_AMG_COARSE_SWEEPS_AFTER_PIVOT;
+		}
+		else
+		{
+			if (!M->d_factor)
+			{
+				ABI_TRY(dev_alloc_bytes((void **) &M->d_factor, fbytes));
+				M->vector_bytes += (double) fbytes;
+			}
+			HIP_TRY(hipMemcpyAsync(M->d_factor, u->d_factor, fbytes, hipMemcpyDeviceToDevice, st));
+			HIP_TRY(hipStreamSynchronize(st));
+			M->coarse_kind = SPMV_MI355X_AMG_COARSE_DENSE;
+		}
+	}
+	const int nu = M->opts.sweeps, cs = M->opts.coarse_sweeps;
+	M->spmvs = (long) (M->levels - 1) * (2 * nu + 2) + (M->coarse_kind == SPMV_MI355X_AMG_COARSE_DENSE ? 0 : cs - 1);
+	M->launches = M->spmvs + (long) (M->levels - 1) * (2 * nu + 1) + (M->coarse_kind == SPMV_MI355X_AMG_COARSE_DENSE ? 1 : cs);
+	return 0;
+}
+
 }  // namespace spmv
 
 using namespace spmv;
@@ -543,6 +850,12 @@ spmv_mi355x_amg_apply_device_async(spmv_mi355x_amg * M, const void * in_dev, voi
 	}
 	if (M->n == 0)
 		return 0;
+	if (M->update_failed)
+	{
+		set_error("amg_apply: the last amg_update_values of this hierarchy failed below level 0 and left it half rewritten: update it "
+				"with values it accepts first");
+		return 1;
+	}
 	hipStream_t st = (hipStream_t) hip_stream;
 	const bool f32 = M->f32;
 	const int nl = M->levels, nu = M->opts.sweeps;
@@ -725,12 +1038,179 @@ spmv_mi355x_amg_level_csr(const spmv_mi355x_amg * M, int level, int which, int32
 		return 1;
 	}
 	const long nnz = p ? L->nnz_p : L->nnz;
+	// after an update the values live on the device: they come to the host when somebody asks
+	if (values_out && nnz > 0 && amg_refresh_host(const_cast<spmv_mi355x_amg *>(M)))
+		return 1;
 	if (row_ptr_out)
 		memcpy(row_ptr_out, (p ? L->p_rp : L->rp).data(), (size_t) (L->n + 1) * sizeof(int32_t));
 	if (col_idx_out && nnz > 0)
 		memcpy(col_idx_out, (p ? L->p_ci : L->ci).data(), (size_t) nnz * sizeof(int32_t));
 	if (values_out && nnz > 0)
 		memcpy(values_out, (p ? L->p_va : L->va).data(), (size_t) nnz * sizeof(double));
+	return 0;
+}
+
+int
+spmv_mi355x_amg_update_values_state(const spmv_mi355x_amg * M)
+{
+	if (!M)
+	{
+		set_error("amg_update_values_state: NULL handle");
+		return 0;
+	}
+	if (!amg_handles_updatable("amg_update_values", M))
+		return 0;
+	return M->update_failed ? 3 : M->upd ? 2 : 1;
+}
+
+int
+spmv_mi355x_amg_update_values_prepare(spmv_mi355x_amg * M)
+{
+	const char * what = "amg_update_values_prepare";
+	if (!M)
+	{
+		set_error("%s: NULL handle", what);
+		return 1;
+	}
+	if (!amg_handles_updatable(what, M))
+		return 1;
+	if (M->upd)
+		return 0;
+	const auto t0 = std::chrono::steady_clock::now();
+	HIP_TRY(hipSetDevice(M->device));
+	AmgUpdate * u = new AmgUpdate();
+	u->lev.resize((size_t) M->levels);
+	int rc = amg_keep(u, &u->d_part, (size_t) AMG_MAX_GRID) || amg_keep(u, &u->d_count, (size_t) SPMV_MI355X_AMG_MAX_LEVELS + 1)
+			|| amg_keep(u, &u->d_factor, (size_t) AMG_DENSE_MAX * (AMG_DENSE_MAX + 1) / 2);
+	for (int l = 0; l < M->levels && !rc; l++)
+		rc = amg_prepare_level(M, u, l);
+	if (rc)
+	{
+		const std::string msg = spmv_mi355x_last_error();
+		amg_update_free(u);
+		if (msg.rfind("amg_update_values_prepare:", 0) != 0)
+			set_error("%s: %s", what, msg.c_str());
+		return 1;
+	}
+	u->prepare_seconds = amg_since(t0);
+	M->upd = u;
+	return 0;
+}
+
+int
+spmv_mi355x_amg_update_values_device(spmv_mi355x_amg * M, const double * values_dev, void * hip_stream)
+{
+	const char * what = "amg_update_values";
+	if (!M || (M->n > 0 && M->lev[0].nnz > 0 && !values_dev))
+	{
+		set_error("%s: NULL %s", what, !M ? "handle" : "values");
+		return 1;
+	}
+	if (!amg_handles_updatable(what, M))
+		return 1;
+	AmgUpdate * u = M->upd;
+	if (!u)
+	{
+		set_error("%s: spmv_mi355x_amg_update_values_prepare has not been called on this hierarchy", what);
+		return 1;
+	}
+	if (reinterpret_cast<uintptr_t>(values_dev) & 7)
+	{
+		set_error("%s: the values must be 8-byte aligned", what);
+		return 1;
+	}
+	if (M->n == 0)
+		return 0;
+	hipStream_t st = (hipStream_t) hip_stream;
+	const auto t0 = std::chrono::steady_clock::now();
+	HIP_TRY(hipSetDevice(M->device));
+	// level 0 is checked on the caller's array before anything of the hierarchy is written
+	HIP_TRY(hipMemsetAsync(u->d_count, 0, (size_t) (SPMV_MI355X_AMG_MAX_LEVELS + 1) * 4, st));
+	int bad = 0;
+	double rho = 0;
+	ABI_TRY(amg_update_diag(M, 0, values_dev, st, &bad, &rho));
+	if (bad > 0)
+	{
+		long row = -1;
+		double d = 0;
+		ABI_TRY(amg_first_bad_row(M, 0, &row, &d));
+		set_error("%s: the diagonal of row %ld of level 0 is %g: it must be finite and > 0 (the hierarchy is unchanged)", what, row, d);
+		return 1;
+	}
+	if (!std::isfinite(rho) || !(rho > 0))
+	{
+		set_error("%s: level 0: max_i sum_j |a_ij| / a_ii = %g is not a positive finite number (the hierarchy is unchanged)", what, rho);
+		return 1;
+	}
+	HIP_TRY(hipMemcpyAsync(u->lev[0].d_va, values_dev, (size_t) M->lev[0].nnz * 8, hipMemcpyDeviceToDevice, st));
+	u->spgemm_seconds = u->handle_seconds = 0;
+	u->host_stale = true;
+	M->update_failed = true;                              // until every level is through
+	if (amg_update_levels(M, rho, st))
+	{
+		const std::string msg = spmv_mi355x_last_error();
+		if (msg.rfind("amg_update_values:", 0) != 0)
+			set_error("%s: %s", what, msg.c_str());
+		(void) hipStreamSynchronize(st);
+		return 1;
+	}
+	M->update_failed = false;
+	u->updates++;
+	u->update_seconds = amg_since(t0);
+	return 0;
+}
+
+int
+spmv_mi355x_amg_update_values(spmv_mi355x_amg * M, const double * values_host)
+{
+	const char * what = "amg_update_values";
+	if (!M || (M->n > 0 && M->lev[0].nnz > 0 && !values_host))
+	{
+		set_error("%s: NULL %s", what, !M ? "handle" : "values");
+		return 1;
+	}
+	if (!amg_handles_updatable(what, M))
+		return 1;
+	if (!M->upd)
+	{
+		set_error("%s: spmv_mi355x_amg_update_values_prepare has not been called on this hierarchy", what);
+		return 1;
+	}
+	if (M->n == 0)
+		return 0;
+	HIP_TRY(hipSetDevice(M->device));
+	DeviceBuffers tmp;
+	double * d_va = nullptr;
+	const size_t count = (size_t) M->lev[0].nnz;
+	ABI_TRY(tmp.alloc(&d_va, count * 8));
+	HIP_TRY(hipMemcpy(d_va, values_host, count * 8, hipMemcpyHostToDevice));
+	return spmv_mi355x_amg_update_values_device(M, d_va, nullptr);
+}
+
+int
+spmv_mi355x_amg_update_info(const spmv_mi355x_amg * M, spmv_mi355x_amg_update_stats * info)
+{
+	if (!M || !info)
+	{
+		set_error("amg_update_info: NULL %s", !M ? "handle" : "info");
+		return 1;
+	}
+	if (!info_size_ok("amg_update_info", info))
+		return 1;
+	spmv_mi355x_amg_update_stats s;
+	memset(&s, 0, sizeof(s));
+	s.prepared = M->upd != nullptr;
+	s.failed = M->update_failed;
+	if (const AmgUpdate * u = M->upd)
+	{
+		s.updates = u->updates;
+		s.prepare_bytes = u->bytes;
+		s.prepare_seconds = u->prepare_seconds;
+		s.update_seconds = u->update_seconds;
+		s.spgemm_seconds = u->spgemm_seconds;
+		s.handle_seconds = u->handle_seconds;
+	}
+	put_info(info, info->struct_size, s);
 	return 0;
 }
 

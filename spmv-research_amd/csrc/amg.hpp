@@ -19,7 +19,16 @@
 //     amg_prolong_kernel           24        0         0
 //     amg_first / sweep / residual <= 22     0         0
 //     amg_dense_solve_kernel       20   67 072 B       0
-// (-Rpass-analysis=kernel-resource-usage, gfx950; profiles/r23_amg.txt has the compiler's own table.)
+//     amg_diag_check_kernel        22    3 072 B       0
+//     amg_weights_kernel           16        0         0
+//     amg_dense_factor_kernel      46   66 056 B       0
+// (-Rpass-analysis=kernel-resource-usage, gfx950; profiles/r23_amg.txt and profiles/r24_amg_update.txt have the compiler's own table.)
+// AN UPDATE OF THE VALUES (amg_update_values*) keeps, from prepare on, what AmgUpdate below lists: per coarsened level the three SpGEMM
+// plans (their device patterns serve step 1 and launch_amg_prolong too), agg, the entry map P -> R and the value arrays. An update is
+// per level amg_diag_check_kernel (the host reads one count and amg_grid(n) partials), amg_weights_kernel, the numeric passes of the
+// plans, amg_prolong_kernel, the gather into R's order and the handles' update_values_device; a dense last level is factorised by
+// amg_dense_factor_kernel, one workgroup of AMG_DENSE_MAX lanes with the packed triangle in LDS, two barriers per column, n trips in
+// every lane, a failed pivot raised by a plain store.
 #pragma once
 
 #include <vector>
@@ -73,6 +82,34 @@ int launch_amg_residual(bool f32, const void * b, void * t, long n, hipStream_t 
 // x = (L L^t)^-1 b for the packed factor L of n <= AMG_DENSE_MAX rows (row-major lower triangle, fp64)
 int launch_amg_dense_solve(bool f32, const double * L, const void * b, void * x, int n, hipStream_t st);
 
+// an update: step 1 with *bad += the rows whose diagonal is absent, not finite or <= 0 (zeroed by the caller); d and part as above
+int launch_amg_diag_check(const AmgCsr & a, double * d, double * part, int * bad, hipStream_t st);
+// w[i] = omega / d[i] in fp64, narrowed to the handle's precision
+int launch_amg_weights(bool f32, long n, const double * d, double omega, void * w, hipStream_t st);
+// the packed factor of a.n <= AMG_DENSE_MAX rows into F; *failed = 1 at a pivot that is <= 0 or not finite (zeroed by the caller)
+int launch_amg_dense_factor(const AmgCsr & a, double * F, int * failed, hipStream_t st);
+
+// what amg_update_values_prepare keeps of level l, all on the device
+struct AmgUpdateLevel {
+	spmv_mi355x_spgemm * at = nullptr, * ap = nullptr, * ac = nullptr;   // A T, A P, R (A P); NULL on the last level
+	const int * d_rp = nullptr, * d_ci = nullptr;         // A_l's pattern: the plan's copy, or the level's own on the last level
+	int * d_agg = nullptr;
+	unsigned * d_src = nullptr;                           // entry e of R is entry d_src[e] of P
+	double * d_va = nullptr, * d_d = nullptr;             // A_l's values (level 0: a copy of the caller's), the diagonal
+	double * d_ones = nullptr, * d_at = nullptr, * d_p = nullptr, * d_r = nullptr, * d_ap = nullptr;
+};
+
+struct AmgUpdate {
+	std::vector<AmgUpdateLevel> lev;
+	std::vector<void *> owned;                            // every device allocation but the plans'
+	double * d_part = nullptr, * d_factor = nullptr;      // step 1's partials; the factor before it is known to be one
+	int * d_count = nullptr;                              // the bad diagonals of every level, then the pivot flag
+	double bytes = 0, prepare_seconds = 0;
+	long updates = 0;
+	double update_seconds = 0, spgemm_seconds = 0, handle_seconds = 0;   // of the last update
+	bool host_stale = false;                              // the host copies of the values lag behind the device's
+};
+
 struct AmgLevel {
 	long n = 0, nnz = 0, nnz_p = 0, aggregates = 0;
 	int mis_rounds = 0;
@@ -97,4 +134,6 @@ struct spmv_mi355x_amg {
 	long spmvs = 0, launches = 0;
 	double setup_seconds = 0, coarsen_seconds = 0, spgemm_seconds = 0, transpose_seconds = 0, create_seconds = 0, download_seconds = 0;
 	double vector_bytes = 0;
+	spmv::AmgUpdate * upd = nullptr;                      // amg_update_values_prepare's; NULL before it
+	bool update_failed = false;                           // the last update stopped below level 0: apply refuses
 };

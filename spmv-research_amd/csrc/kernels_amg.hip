@@ -1,6 +1,7 @@
 // The kernels of the smoothed-aggregation AMG (include/spmv_mi355x.h "AMG", amg.hpp for the mapping): steps 1 to 5 of the setup, one
-// lane per row; the three vector kernels of the cycle; the dense coarsest solve. The arithmetic is the header's, as written: this
-// file is compiled with contraction off, and every fma in it is spelled out.
+// lane per row; the three vector kernels of the cycle; the dense coarsest solve; and what an update of the values adds (the checked
+// step 1, the weights, the dense factor). The arithmetic is the header's, as written: this file is compiled with contraction off,
+// and every fma in it is spelled out.
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
@@ -60,6 +61,62 @@ amg_diag_kernel(AmgCsr a, double * __restrict__ d, double * __restrict__ part)
 	}
 	if (threadIdx.x == 0)
 		part[blockIdx.x] = sh[0];
+}
+
+// step 1 for an update: amg_diag_kernel's d and partials, operation for operation, and *bad += the rows whose diagonal is absent, not
+// finite or <= 0 (zeroed by the caller)
+__global__ __launch_bounds__(AMG_TB) void
+amg_diag_check_kernel(AmgCsr a, double * __restrict__ d, double * __restrict__ part, int * __restrict__ bad)
+{
+	__shared__ double sh[AMG_TB];
+	__shared__ int shb[AMG_TB];
+	double worst = 0;
+	int wrong = 0;
+	AMG_ROWS(i, a.n)
+	{
+		double di = 0, sum = 0;
+		bool found = false;
+		for (int e = a.rp[i]; e < a.rp[i + 1]; e++)
+		{
+			const double v = a.va[e];
+			if (!found && a.ci[e] == i)
+			{
+				di = v;
+				found = true;
+			}
+			sum = sum + fabs(v);
+		}
+		d[i] = di;
+		worst = fmax(worst, sum / di);
+		wrong += !(isfinite(di) && di > 0);
+	}
+	sh[threadIdx.x] = worst;
+	shb[threadIdx.x] = wrong;
+	__syncthreads();
+	for (int s = AMG_TB / 2; s > 0; s >>= 1)
+	{
+		if ((int) threadIdx.x < s)
+		{
+			sh[threadIdx.x] = fmax(sh[threadIdx.x], sh[threadIdx.x + s]);
+			shb[threadIdx.x] += shb[threadIdx.x + s];
+		}
+		__syncthreads();
+	}
+	if (threadIdx.x == 0)
+	{
+		part[blockIdx.x] = sh[0];
+		if (shb[0] > 0)
+			atomicAdd(bad, shb[0]);                           // an integer count: its sum does not depend on the order
+	}
+}
+
+// w_i = omega / d_i, an IEEE division in fp64, narrowed to the handle's precision: the host loop of amg_build_level
+template <typename T>
+__global__ __launch_bounds__(AMG_TB) void
+amg_weights_kernel(long n, const double * __restrict__ d, double omega, T * __restrict__ w)
+{
+	AMG_ROWS(i, n)
+		w[i] = (T) (omega / d[i]);
 }
 
 __global__ __launch_bounds__(AMG_TB) void
@@ -264,6 +321,58 @@ amg_dense_solve_kernel(const double * __restrict__ Lg, const T * __restrict__ b,
 		x[a] = (T) piv[a];
 }
 
+// The packed factor of the header's loop, in place in LDS: the lower triangle of the CSR is scattered into the triangle (an absent
+// entry is 0), then for column k lane a >= k runs its fma chain over the finished columns p < k, lane k posts its pivot, one barrier,
+// lane k keeps sqrt(pivot) and the lanes below divide by it, one barrier. A pivot that is <= 0 or not finite raises *failed (a plain
+// store; zeroed by the caller) and the loop goes on: every lane runs all n trips and meets every barrier, the factor is then not used.
+__global__ __launch_bounds__(AMG_DENSE_MAX) void
+amg_dense_factor_kernel(AmgCsr A, double * __restrict__ Fg, int * __restrict__ failed)
+{
+	__shared__ double S[AMG_DENSE_MAX * (AMG_DENSE_MAX + 1) / 2];
+	__shared__ double piv;
+	const int n = (int) A.n;
+	const int a = threadIdx.x;
+	const int row = a * (a + 1) / 2;
+	const int len = n * (n + 1) / 2;
+	for (int e = a; e < len; e += AMG_DENSE_MAX)
+		S[e] = 0.0;
+	__syncthreads();
+	if (a < n)
+		for (int e = A.rp[a]; e < A.rp[a + 1]; e++)
+		{
+			const int j = A.ci[e];
+			if (j >= 0 && j <= a)
+				S[row + j] = A.va[e];
+		}
+	__syncthreads();
+	for (int k = 0; k < n; k++)
+	{
+		const int rk = k * (k + 1) / 2;
+		double s = 0.0;
+		if (a >= k && a < n)
+		{
+			s = S[row + k];
+			for (int p = 0; p < k; p++)
+				s = fma(-S[row + p], S[rk + p], s);
+		}
+		if (a == k)
+		{
+			piv = s;
+			if (!(isfinite(s) && s > 0))
+				*failed = 1;
+		}
+		__syncthreads();
+		const double root = sqrt(piv);
+		if (a == k)
+			S[rk + k] = root;
+		else if (a > k && a < n)
+			S[row + k] = s / root;
+		__syncthreads();
+	}
+	for (int e = a; e < len; e += AMG_DENSE_MAX)
+		Fg[e] = S[e];
+}
+
 // ---- launchers -----------------------------------------------------------------------------------------------------------------------
 
 #define AMG_LAUNCH(kernel, n, st, ...)                                                          \
@@ -278,6 +387,29 @@ int
 launch_amg_diag(const AmgCsr & a, double * d, double * part, hipStream_t st)
 {
 	AMG_LAUNCH(amg_diag_kernel, a.n, st, a, d, part);
+}
+
+int
+launch_amg_diag_check(const AmgCsr & a, double * d, double * part, int * bad, hipStream_t st)
+{
+	AMG_LAUNCH(amg_diag_check_kernel, a.n, st, a, d, part, bad);
+}
+
+int
+launch_amg_weights(bool f32, long n, const double * d, double omega, void * w, hipStream_t st)
+{
+	if (f32)
+		AMG_LAUNCH(amg_weights_kernel<float>, n, st, n, d, omega, (float *) w);
+	AMG_LAUNCH(amg_weights_kernel<double>, n, st, n, d, omega, (double *) w);
+}
+
+int
+launch_amg_dense_factor(const AmgCsr & a, double * F, int * failed, hipStream_t st)
+{
+	if (a.n > 0 && a.n <= AMG_DENSE_MAX)
+		hipLaunchKernelGGL(amg_dense_factor_kernel, dim3(1), dim3(AMG_DENSE_MAX), 0, st, a, F, failed);
+	HIP_TRY(hipGetLastError());
+	return 0;
 }
 
 int

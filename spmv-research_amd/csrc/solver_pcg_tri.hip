@@ -515,6 +515,12 @@ spmv_mi355x_pcg_amg(spmv_mi355x_matrix * A, const void * b_host, void * x_out_ho
 		set_error("pcg_amg: M lives on device %d, the matrix on device %d", M->device, device);
 	if (M->n != n || M->precision != precision || M->device != device)
 		return 1;
+	if (M->update_failed)
+	{
+		set_error("pcg_amg: the last amg_update_values of M failed below level 0 and left it half rewritten: update it with values it "
+				"accepts first");
+		return 1;
+	}
 	HIP_TRY(hipSetDevice(device));
 	const AmgApply apply = {M};
 	if (precision == SPMV_MI355X_F32)

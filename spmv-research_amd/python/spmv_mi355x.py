@@ -74,6 +74,8 @@ SYMBOLS = [
     "spmv_mi355x_amg_create", "spmv_mi355x_amg_destroy", "spmv_mi355x_amg_apply_device_async", "spmv_mi355x_amg_apply",
     "spmv_mi355x_amg_info", "spmv_mi355x_amg_level_matrices", "spmv_mi355x_amg_aggregates", "spmv_mi355x_amg_level_csr",
     "spmv_mi355x_amg_mem_footprint", "spmv_mi355x_pcg_amg",
+    "spmv_mi355x_amg_update_values_prepare", "spmv_mi355x_amg_update_values", "spmv_mi355x_amg_update_values_device",
+    "spmv_mi355x_amg_update_values_state", "spmv_mi355x_amg_update_info",
 ]
 
 _lib = None
@@ -127,6 +129,15 @@ def lib():
         L.spmv_mi355x_pcg_amg.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_long, C.c_void_p,
                                           C.POINTER(PcgTriInfo)]
         L.spmv_mi355x_amg_mem_footprint.restype = C.c_double
+        for f in ("spmv_mi355x_amg_update_values_prepare", "spmv_mi355x_amg_update_values_state"):
+            getattr(L, f).restype = C.c_int
+            getattr(L, f).argtypes = [C.c_void_p]
+        L.spmv_mi355x_amg_update_values.restype = C.c_int
+        L.spmv_mi355x_amg_update_values.argtypes = [C.c_void_p, C.c_void_p]
+        L.spmv_mi355x_amg_update_values_device.restype = C.c_int
+        L.spmv_mi355x_amg_update_values_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.spmv_mi355x_amg_update_info.restype = C.c_int
+        L.spmv_mi355x_amg_update_info.argtypes = [C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -501,6 +512,13 @@ class AmgStats(C.Structure):
                 ("transpose_seconds", C.c_double), ("create_seconds", C.c_double), ("download_seconds", C.c_double)]
 
 
+class AmgUpdateStats(C.Structure):
+    """spmv_mi355x_amg_update_stats (include/spmv_mi355x.h "AMG: new values for a hierarchy")"""
+    _fields_ = [("struct_size", C.c_uint), ("prepared", C.c_int), ("failed", C.c_int), ("updates", C.c_long),
+                ("prepare_bytes", C.c_double), ("prepare_seconds", C.c_double),
+                ("update_seconds", C.c_double), ("spgemm_seconds", C.c_double), ("handle_seconds", C.c_double)]
+
+
 class Amg:
     """The smoothed-aggregation multilevel preconditioner of a symmetric positive definite matrix (include/spmv_mi355x.h "AMG"),
     built on the GPU: apply(v) is one V(sweeps, sweeps) cycle over handles built in `fmt` with `opts`. `.A` is the borrowed handle of
@@ -580,6 +598,35 @@ class Amg:
     def apply_device(self, in_ptr, out_ptr, stream=None):
         """The same on device pointers (in_ptr == out_ptr: in place), enqueued on `stream` (spmv_mi355x_amg_apply_device_async)"""
         _check(lib().spmv_mi355x_amg_apply_device_async(self.h, C.c_void_p(in_ptr), C.c_void_p(out_ptr), C.c_void_p(stream or 0)))
+
+    def update_values_prepare(self):
+        """once, before the first update_values: keeps the SpGEMM plans, the aggregates and the value arrays of every level on the
+        device (spmv_mi355x_amg_update_values_prepare)"""
+        _check(lib().spmv_mi355x_amg_update_values_prepare(self.h))
+
+    def update_values(self, values):
+        """new values of A in the entry order of the CSR given at creation: the aggregates and every pattern stay, the numbers of
+        every level are recomputed on the device (spmv_mi355x_amg_update_values; blocking)"""
+        values = np.ascontiguousarray(values, np.float64)
+        nnz = self.info()["nnz"][0] if self.levels else 0
+        if values.shape != (nnz,):
+            raise ValueError(f"values must have {nnz} entries, got {values.shape}")
+        _check(lib().spmv_mi355x_amg_update_values(self.h, _p(values)))
+
+    def update_values_device(self, ptr, stream=0):
+        """The same from nnz(A) fp64 values on the device, ordered on `stream`; blocking (spmv_mi355x_amg_update_values_device)"""
+        _check(lib().spmv_mi355x_amg_update_values_device(self.h, C.c_void_p(ptr), C.c_void_p(stream or 0)))
+
+    def update_values_state(self):
+        """0 = cannot be updated (last_error says why), 1 = update_values_prepare is missing, 2 = ready, 3 = the last update failed"""
+        return lib().spmv_mi355x_amg_update_values_state(self.h)
+
+    def update_info(self):
+        """dict of spmv_mi355x_amg_update_stats"""
+        s = AmgUpdateStats()
+        s.struct_size = C.sizeof(AmgUpdateStats)
+        _check(lib().spmv_mi355x_amg_update_info(self.h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in AmgUpdateStats._fields_ if k != "struct_size"}
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h:

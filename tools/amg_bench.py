@@ -19,7 +19,13 @@ reported with their min .. max spreads. No threshold is set and no speed is prom
 
     python tools/amg_bench.py                                        # stencil160 fp64
     python tools/amg_bench.py --runs grid2d2000:f64 --theta 0.08
-One JSON line per variant, and a table at the end."""
+    python tools/amg_bench.py --update                               # grid2d2000 and stencil160, fp64, theta 0.03
+One JSON line per variant, and a table at the end.
+
+--update times the other thing a caller with changing values can do: per theta, amg_create on every window (its setup_seconds: the
+yardstick) against amg_update_values_prepare once and amg_update_values_device per window with the values already resident,
+alternating between two value sets; the update's seconds are split into the SpGEMM numeric passes, the handles' blocking
+update_values_device and the rest (amg_update_info). Medians over the windows with their spreads."""
 import argparse
 import json
 import os
@@ -126,10 +132,66 @@ def run(E, torch, workload, dts, args):
     return rows
 
 
+def run_update(E, torch, workload, dts, args):
+    """--update: amg_create against amg_update_values_prepare (once) and amg_update_values_device with the values resident, per theta.
+    Every window creates a hierarchy from scratch (the yardstick: create is what a caller without update pays per value set) and
+    updates the prepared one, alternating between 0.7 V1 and V1 so that every update meets other numbers; window 0 is dropped."""
+    if workload.startswith("stencil"):
+        from solver_bench import stencil27
+        rp, ci, va, n = stencil27(int(workload[len("stencil"):]), args.stencil_diag)
+    elif workload.startswith("grid2d"):
+        rp, ci, va, n = grid2d(int(workload[len("grid2d"):]), args.shift)
+    else:
+        raise SystemExit(f"amg_bench.py runs on stencil<N> and grid2d<N>, not on {workload}")
+    rp, va = np.asarray(rp, np.int32), np.asarray(va, np.float64)
+    np_dtype = np.float32 if dts == "f32" else np.float64
+    resident = [torch.from_numpy(np.array(0.7 * va)).cuda(), torch.from_numpy(np.array(va)).cuda()]
+    rows = []
+    for theta in args.theta:
+        make = lambda: E.Amg(rp, ci, va, n, "sell_c_sigma", np_dtype, theta=theta, sweeps=args.sweeps)
+        M = make()
+        t0 = time.perf_counter()
+        M.update_values_prepare()
+        prepare_wall = time.perf_counter() - t0
+        info = M.info()
+        legs = {k: [] for k in ("create", "create_wall", "update", "update_wall", "spgemm", "handles", "rest")}
+        for w in range(args.windows + 1):
+            t0 = time.perf_counter()
+            N = make()
+            create_wall = time.perf_counter() - t0
+            create = N.info()["setup_seconds"]
+            N.close()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            M.update_values_device(resident[w % 2].data_ptr())
+            update_wall = time.perf_counter() - t0
+            u = M.update_info()
+            if w:
+                for key, t in zip(legs, (create, create_wall, u["update_seconds"], update_wall, u["spgemm_seconds"], u["handle_seconds"],
+                                         u["update_seconds"] - u["spgemm_seconds"] - u["handle_seconds"])):
+                    legs[key].append(t)
+            print(f"# update window {w} done", flush=True)
+        u = M.update_info()
+        rec = dict(workload=workload, dtype=dts, leg="update", theta=theta, n=int(n), nnz_a=int(rp[-1]), levels=info["levels"], rows=info["rows"],
+                   coarse=M.info()["coarse"], windows=args.windows, prepare_seconds=round(u["prepare_seconds"], 5),
+                   prepare_wall_seconds=round(prepare_wall, 5), prepare_bytes_over_footprint=round(u["prepare_bytes"] / M.mem_footprint, 3))
+        for key, ts in legs.items():
+            rec[key] = round(float(np.median(ts)), 6)
+            rec[key + "_spread"] = [round(float(np.min(ts)), 6), round(float(np.max(ts)), 6)]
+        rec["create_over_update"] = round(rec["create"] / rec["update"], 2)
+        print(json.dumps(rec), flush=True)
+        rows.append(rec)
+        M.close()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--runs", default="stencil160:f64", help="stencil<N>:f64|f32 or grid2d<N>:f64|f32, comma separated")
-    ap.add_argument("--theta", default="0.08,0.03", help="the strength thresholds of the AMG variants")
+    ap.add_argument("--runs", default=None, help="stencil<N>:f64|f32 or grid2d<N>:f64|f32, comma separated (default stencil160:f64; "
+                    "with --update grid2d2000:f64,stencil160:f64)")
+    ap.add_argument("--theta", default=None, help="the strength thresholds of the AMG variants (default 0.08,0.03; with --update 0.03)")
+    ap.add_argument("--update", action="store_true", help="time amg_create against update_values_prepare and update_values_device "
+                    "instead of the solves")
     ap.add_argument("--sweeps", type=int, default=1, help="nu of the V(nu, nu) cycle")
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--tol", type=float, default=1e-8, help="the tolerance of the solve leg")
@@ -141,7 +203,8 @@ def main():
     args = ap.parse_args()
     if args.windows < 5:
         ap.error("--windows: at least 5")
-    args.theta = [float(v) for v in args.theta.split(",") if v != ""]
+    args.runs = args.runs or ("grid2d2000:f64,stencil160:f64" if args.update else "stencil160:f64")
+    args.theta = [float(v) for v in (args.theta or ("0.03" if args.update else "0.08,0.03")).split(",") if v != ""]
     os.environ.setdefault("OMP_NUM_THREADS", "16")
     import torch
     if not torch.cuda.is_available():
@@ -150,7 +213,16 @@ def main():
     rows = []
     for item in args.runs.split(","):
         w, dts = item.split(":")[:2]
-        rows += run(E, torch, w, dts, args)
+        rows += (run_update if args.update else run)(E, torch, w, dts, args)
+    if args.update:
+        print(f"{'workload':11s} {'dtype':5s} {'theta':>6s} {'levels':>6s} {'create s':>9s} {'spread':>19s} {'prepare s':>9s} {'update s':>9s} "
+              f"{'spread':>19s} {'spgemm':>8s} {'handles':>8s} {'rest':>8s} {'create / update':>15s} {'kept / footprint':>16s}")
+        for r in rows:
+            print(f"{r['workload']:11s} {r['dtype']:5s} {r['theta']:6g} {r['levels']:6d} {r['create']:9.4f} {r['create_spread'][0]:9.4f} .."
+                  f"{r['create_spread'][1]:8.4f} {r['prepare_seconds']:9.4f} {r['update']:9.4f} {r['update_spread'][0]:9.4f} .."
+                  f"{r['update_spread'][1]:8.4f} {r['spgemm']:8.4f} {r['handles']:8.4f} {r['rest']:8.4f} {r['create_over_update']:15.2f} "
+                  f"{r['prepare_bytes_over_footprint']:16.3f}")
+        return
     nan = float("nan")
     print(f"{'workload':11s} {'dtype':5s} {'precond':>11s} {'iters':>6s} {'stop':>4s} {'seconds':>9s} {'spread':>19s} {'ms/iter':>8s} "
           f"{'spmv ms':>8s} {'iter / spmv':>11s} {'apply ms':>9s} {'apply / spmv':>12s}")

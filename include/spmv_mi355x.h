@@ -305,6 +305,18 @@ int  spmv_mi355x_download_y(spmv_mi355x_matrix * A, void * y_host);
 /* y_dev = A * x_dev (beta == 0) or y_dev += A * x_dev (beta == 1), enqueued on hip_stream (a hipStream_t passed
  * as void*, NULL = the default stream); returns after enqueue. */
 int  spmv_mi355x_spmv_device_async(spmv_mi355x_matrix * A, const void * x_dev, void * y_dev, int beta, void * hip_stream);
+/* Special values (y = A x and y += A x; every format, layout, precision and value storage; the host-buffer call and spmm alike):
+ *   1. confinement: y[i] is non-finite exactly for the rows i that STORE an entry in a column j whose x[j] is Inf or NaN — a
+ *      stored value times Inf or NaN is never finite, a stored 0.0 gives NaN as in the sequential loop — or that store a
+ *      non-finite value (a value may also narrow to Inf in fp32 storage). Every other row is finite and as accurate as on finite
+ *      input (bit-identical to the sequential CSR loop for the row-sequential kernels). The padding of the SELL layouts (a 0.0 at a
+ *      valid column) never multiplies the x of a column the row does not store — an empty row's sum
+ *      is dropped, the delta layout masks the padding steps of the slices that hold rows of different lengths, the LDS-window
+ *      layout points its padding at a zero of its own. Whether a reached row holds +Inf, -Inf or NaN is not specified.
+ *   2. beta == 0 overwrites y whatever it held, NaN included; beta == 1 adds to it.
+ *   3. subnormal inputs and products are computed, not flushed, in fp64 and fp32, the atomic layouts included.
+ * The triangular solves propagate likewise: a non-finite b[i] reaches x[i] and the rows that depend on it, nothing else.
+ * (tests/test_gpu_special_values.py) */
 /* Time `iters` back-to-back launches with HIP events recorded on the stream the kernels run on; ms per iteration. */
 int  spmv_mi355x_time_device(spmv_mi355x_matrix * A, const void * x_dev, void * y_dev, int iters,
 		void * hip_stream, double * ms_per_iter_out);

@@ -125,6 +125,69 @@ build_sell(spmv_mi355x_matrix * A, const int * rp, const int * ci, const double 
 	return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------- row lengths
+// What keeps value padding from reading x (launch.hpp: launch_sell): the stored entries of every sorted row, and per slice whether it
+// holds a row shorter than its longest. Both follow from the row pointer and the builder's row_of_sorted alone, so one small pass on the
+// device serves the host builders, the GPU builders and the handles made from a device-resident CSR alike; the layouts' bytes stay
+// what they were. The rows of a slice are sorted by length, descending: the slice's first row is its longest, its last its shortest.
+constexpr int LEN_BLOCK = 256;
+
+__global__ __launch_bounds__(LEN_BLOCK) void
+sell_row_len_kernel(const int * __restrict__ rp, const int * __restrict__ row_of_sorted, long m, long count, int * __restrict__ len)
+{
+	const long i = blockIdx.x * (long) LEN_BLOCK + threadIdx.x;
+	if (i >= count)
+		return;
+	int l = 0;
+	if (i < m)
+	{
+		const int o = row_of_sorted[i];
+		l = rp[o + 1] - rp[o];
+	}
+	len[i] = l;
+}
+
+__global__ __launch_bounds__(LEN_BLOCK) void
+sell_pad_bits_kernel(const int * __restrict__ len, long num_slices, int C, long words, unsigned * __restrict__ bits)
+{
+	const long w = blockIdx.x * (long) LEN_BLOCK + threadIdx.x;
+	if (w >= words)
+		return;
+	unsigned b = 0;
+	for (int k = 0; k < 32; k++)
+	{
+		const long s = w * 32 + k;
+		if (s < num_slices && len[s * C + C - 1] < len[s * C])
+			b |= 1u << k;
+	}
+	bits[w] = b;
+}
+
+// rp: the local CSR's row pointer, on the host or (rp_on_device) where the builder read it; A->sell_c, sell_slices, d_row_of_sorted are set
+static int
+sell_row_lengths(spmv_mi355x_matrix * A, const int * rp, bool rp_on_device)
+{
+	const long m = A->m, num_slices = A->sell_slices;
+	const long count = num_slices * A->sell_c, words = (num_slices + 31) / 32;
+	if (dev_alloc(&A->d_sell_len, (size_t) (count + words)))
+		return 1;
+	if (count == 0)
+		return 0;
+	int * d_rp = nullptr;
+	if (!rp_on_device && upload_ints(rp, (size_t) m + 1, &d_rp))
+		return 1;
+	hipLaunchKernelGGL(sell_row_len_kernel, dim3((unsigned) ((count + LEN_BLOCK - 1) / LEN_BLOCK)), dim3(LEN_BLOCK), 0, 0, rp_on_device ? rp : d_rp,
+			A->d_row_of_sorted, m, count, A->d_sell_len);
+	hipLaunchKernelGGL(sell_pad_bits_kernel, dim3((unsigned) ((words + LEN_BLOCK - 1) / LEN_BLOCK)), dim3(LEN_BLOCK), 0, 0, A->d_sell_len, num_slices, A->sell_c,
+			words, reinterpret_cast<unsigned *>(A->d_sell_len + count));
+	const hipError_t e1 = hipGetLastError(), e2 = hipDeviceSynchronize();
+	if (d_rp)
+		(void) hipFree(d_rp);
+	HIP_TRY(e1);
+	HIP_TRY(e2);
+	return 0;
+}
+
 // mode 5 of the delta layout: the EXCEPTION lanes of a slice (64 equally long rows rows[0..63]) — those whose columns are not
 // column_k[reference r] + (first column - reference's first column) at every step — and whether some lane's difference does not fit a
 // signed byte (`hard`): the host twin of sell5_exceptions() in convert_sell.hip
@@ -411,7 +474,7 @@ build_sell_delta(spmv_mi355x_matrix * A, int sell_values, const int * rp, const 
 			{
 				const long i = sl * C + r;
 				double v = 0.0;
-				int c = base;                              // padding: value 0 times a column some lane really uses
+				int c = base;                              // padding: value 0 at a column some lane really uses (not this row's: the kernels mask it, sell_row_lengths)
 				if (i < m)
 				{
 					int o = row_of_sorted[i];
@@ -754,14 +817,14 @@ build_sell_family(spmv_mi355x_matrix * A, const spmv_mi355x_opts & o, const int 
 	}
 	if (A->sell_delta)
 	{
-		rc = build_sell_delta(A, sell_values_env(o.sell_values), rp, ci, va);
+		rc = build_sell_delta(A, sell_values_env(o.sell_values), rp, ci, va) || sell_row_lengths(A, rp, false);
 		A->sell_v7_active = !rc && sell_v7_wanted(A->val_f32, sell_values_env(o.sell_values), A->sell_nnz_ext);
 		sell_delta_names(A);
 		return rc;
 	}
 	snprintf(A->format_name, sizeof(A->format_name), "MI355X_SELL_%d_%ld_%s", C, sigma, pf);
 	snprintf(A->kernel_name, sizeof(A->kernel_name), "sell_kernel");
-	return build_sell(A, rp, ci, va);
+	return build_sell(A, rp, ci, va) || sell_row_lengths(A, rp, false);
 }
 
 
@@ -800,6 +863,8 @@ build_sell_delta_resident(spmv_mi355x_matrix * A, const spmv_mi355x_opts & o, co
 	if (sell_delta_convert_resident(A->val_f32, m, A->n, A->nnz, sigma, sell_values_env(o.sell_values), d_rp, d_ci, d_va, r))
 		return 1;
 	sell_delta_install(A, r);
+	if (sell_row_lengths(A, d_rp, true))
+		return 1;
 	A->sell_v7_active = sell_v7_wanted(A->val_f32, sell_values_env(o.sell_values), A->sell_nnz_ext);
 	sell_delta_names(A);
 	return 0;

@@ -65,6 +65,8 @@ struct spmv_mi355x_matrix {
 	long sell_sigma = 0, sell_slices = 0, sell_nnz_ext = 0;
 	int64_t * d_slice_ptr = nullptr;
 	int * d_row_of_sorted = nullptr;
+	int * d_sell_len = nullptr;            // plain and delta layouts: the length of every sorted row, then one bit per slice that holds value
+	                                       //   padding (launch.hpp: sell_row_lengths); what keeps padding from reading x. Not in mem_footprint
 	bool sell_delta = false;               // delta-compressed column indices (C = 64 only)
 	bool convert_on_device = true;         // build the delta layout on the GPU (convert_sell.hip) or on the host
 	int sell_split = 1;                    // waves sharing one slice (delta format): 1, 2 or 4

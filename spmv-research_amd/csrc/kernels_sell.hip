@@ -9,7 +9,8 @@
 // wavefront read 64 consecutive values / column indices per step:
 //       element (row r of the slice, column k)  ->  slice_ptr[s] + k*C + r
 // One wavefront owns one slice. With C = 64 a lane owns a row and walks it left to right with one FMA per element
-// (padding multiplies 0 by a valid x entry), i.e. y is bit-identical to the sequential CSR row loop. With C = 32 / 16 the
+// (padding multiplies 0 by the x entry of the row's own last column; an empty row has none, is padded with column 0 and has its sum
+// dropped: row_len, launch.hpp), i.e. y is bit-identical to the sequential CSR row loop, for x that holds Inf or NaN too. With C = 32 / 16 the
 // wave covers 2 / 4 consecutive columns per step (lane = (k % TPR)*C + r); the TPR partial sums of a row are combined by
 // a fixed xor-butterfly. The slice width is padded to a multiple of TPR. Smaller C = more wavefronts and shorter
 // dependent chains for small matrices, at the cost of the butterfly.
@@ -28,7 +29,7 @@ constexpr int SELL_WAVES = SELL_BLOCK / WAVE;
 template <typename T, int C, bool NT>
 __global__ __launch_bounds__(SELL_BLOCK) void
 sell_kernel(const int64_t * __restrict__ slice_ptr, const int * __restrict__ col, const T * __restrict__ val,
-		const int * __restrict__ row_of_sorted, const T * __restrict__ x, T * __restrict__ y,
+		const int * __restrict__ row_of_sorted, const int * __restrict__ row_len, const T * __restrict__ x, T * __restrict__ y,
 		int m, int num_slices, int beta, XcdMap map)
 {
 	unsigned tile = xcd_tile(blockIdx.x, map);
@@ -122,6 +123,10 @@ sell_kernel(const int64_t * __restrict__ slice_ptr, const int * __restrict__ col
 		const long sorted_row = (long) slice * C + lane;
 		if (sorted_row < m)
 		{
+			// the padding of a row multiplies 0 by the row's own last column; an empty row has none and is padded with column 0, which is
+			// not its own: what it summed (0 * x[0], NaN when x[0] is not finite) is dropped
+			if (row_len[sorted_row] == 0)
+				s0 = 0;
 			T * yp = y + row_of_sorted[sorted_row];
 			*yp = beta ? *yp + s0 : s0;
 		}
@@ -135,7 +140,7 @@ constexpr int SELL_WIDE_C = 256;
 template <typename T, bool NT>
 __global__ __launch_bounds__(SELL_WIDE_C) void
 sell_wide_kernel(const int64_t * __restrict__ slice_ptr, const int * __restrict__ col, const T * __restrict__ val,
-		const int * __restrict__ row_of_sorted, const T * __restrict__ x, T * __restrict__ y,
+		const int * __restrict__ row_of_sorted, const int * __restrict__ row_len, const T * __restrict__ x, T * __restrict__ y,
 		int m, int num_slices, int beta, XcdMap map)
 {
 	constexpr int C = SELL_WIDE_C;
@@ -160,6 +165,8 @@ sell_wide_kernel(const int64_t * __restrict__ slice_ptr, const int * __restrict_
 	const long sorted_row = (long) slice * C + threadIdx.x;
 	if (sorted_row < m)
 	{
+		if (row_len[sorted_row] == 0)          // an empty row's padding is not a column of its own (sell_kernel)
+			s = 0;
 		T * yp = y + row_of_sorted[sorted_row];
 		*yp = beta ? *yp + s : s;
 	}
@@ -176,15 +183,42 @@ sell_wide_kernel(const int64_t * __restrict__ slice_ptr, const int * __restrict_
 // HBM bytes per non-zero drop by up to 24 % (fp64) / 37 % (fp32) below the CSR-normalised "algorithmic" 12 / 8 bytes.
 // The value readers and index decoders live in sell_delta_read.hpp, shared with the multi-vector kernel (kernels_sell_spmm.hip).
 
-template <typename T, int MODE, bool NT, bool V7, int NSTEPS = 4, typename S = T>
+// PAD: the slice holds rows shorter than its width (modes 1, 2 and 4 only: the others need equally long rows). Their padding steps store
+// 0.0 and a column that some OTHER row of the slice uses, so x is kept out of them: a lane's steps from `len` (its row's length) on
+// take 0 in place of x[column]. The instantiations without PAD are what they were.
+template <typename T, int MODE, bool NT, bool V7, int NSTEPS = 4, typename S = T, bool PAD = false>
 __device__ __forceinline__ void
 sell_delta_group(const unsigned char * __restrict__ gp /* uniform */, const SellVals<T, NT, V7, S> & vals, int g, int lane, const T * __restrict__ x, T & s,
-		int off = 0)
+		int off = 0, int len = 0)
 {
 	int c[4];
 	sell_group_cols<MODE, NT>(gp, lane, off, c);
 	const int c0 = c[0], c1 = c[1], c2 = c[2], c3 = c[3];
-	if (NSTEPS == 4)
+	if (PAD)
+	{
+		// (the gathers themselves stay unconditional: every stored column is a valid one)
+		T v[4] = {T(0), T(0), T(0), T(0)};
+		if (NSTEPS == 4)
+			vals.group(g, v);
+		else
+		{
+			T tv[3];
+			sell_tail_values<T, NT, NSTEPS>(vals.tail(g), lane, tv);
+			v[0] = tv[0];
+			v[1] = tv[1];
+			v[2] = tv[2];
+		}
+		const int left = len - 4 * g;                       // real steps of this lane from the group's first on
+		const T x0 = left > 0 ? x[c0] : T(0);
+		const T x1 = (NSTEPS > 1 && left > 1) ? x[c1] : T(0);
+		const T x2 = (NSTEPS > 2 && left > 2) ? x[c2] : T(0);
+		const T x3 = (NSTEPS > 3 && left > 3) ? x[c3] : T(0);
+		s = fma_t<T>(v[0], x0, s);
+		if (NSTEPS > 1) s = fma_t<T>(v[1], x1, s);
+		if (NSTEPS > 2) s = fma_t<T>(v[2], x2, s);
+		if (NSTEPS > 3) s = fma_t<T>(v[3], x3, s);
+	}
+	else if (NSTEPS == 4)
 	{
 		T v[4];
 		vals.group(g, v);
@@ -302,11 +336,12 @@ sell_delta_piped(const unsigned char * __restrict__ ip, const SellVals<T, NT, V7
 	}
 }
 
-// groups g0, g0+gs, g0+2gs, ... of one slice (gs = 1: the whole slice, in order)
-template <typename T, int MODE, bool NT, bool V7, typename S = T>
+// groups g0, g0+gs, g0+2gs, ... of one slice (gs = 1: the whole slice, in order). PAD (sell_delta_group): the lane's row holds `len`
+// entries; such a slice takes the in-place readers below in every mode, without the index words fetched a trip ahead.
+template <typename T, int MODE, bool NT, bool PAD, bool V7, typename S>
 __device__ __forceinline__ T
 sell_delta_slice(const unsigned char * __restrict__ ip, const SellVals<T, NT, V7, S> & vals, int width, int lane, const T * __restrict__ x,
-		int g0 = 0, int gs = 1)
+		int g0 = 0, int gs = 1, int len = 0)
 {
 	constexpr long GB = sell_group_bytes(MODE);
 	const int groups = (width + 3) / 4;     // index groups cover the width rounded up to 4 steps, values only the real steps
@@ -320,7 +355,7 @@ sell_delta_slice(const unsigned char * __restrict__ ip, const SellVals<T, NT, V7
 	T s = 0;
 	int g = g0;
 	const int last = groups - 1;            // the last group holds `rem` (1..4) steps
-	if constexpr (MODE == 1 || MODE == 2)
+	if constexpr ((MODE == 1 || MODE == 2) && !PAD)
 	{
 		const int full = rem == 4 ? groups : last;
 		const int n = full > g0 ? (full - g0 + gs - 1) / gs : 0;
@@ -331,34 +366,34 @@ sell_delta_slice(const unsigned char * __restrict__ ip, const SellVals<T, NT, V7
 	// loads of a trip are independent of its FMAs, so the compiler issues all of them first; deeper trips measured 2-3 % faster than
 	// pairs alone on the twin (1 152-1 185 against 1 198-1 207 us, profiles/r03_sell_value_pairs.txt).
 	const int full_end = rem == 4 ? groups : last;
-	for (; g + 3 * gs < full_end; g += 4 * gs)
+	for (; !PAD && g + 3 * gs < full_end; g += 4 * gs)               // (a padded slice goes by pairs: the few there are get no deeper trips of their own)
 	{
-		sell_delta_group<T, MODE, NT, V7>(ip + (size_t) g * GB, vals, g, lane, x, s, off);
-		sell_delta_group<T, MODE, NT, V7>(ip + (size_t) (g + gs) * GB, vals, g + gs, lane, x, s, off);
-		sell_delta_group<T, MODE, NT, V7>(ip + (size_t) (g + 2 * gs) * GB, vals, g + 2 * gs, lane, x, s, off);
-		sell_delta_group<T, MODE, NT, V7>(ip + (size_t) (g + 3 * gs) * GB, vals, g + 3 * gs, lane, x, s, off);
+		sell_delta_group<T, MODE, NT, V7, 4, S, PAD>(ip + (size_t) g * GB, vals, g, lane, x, s, off, len);
+		sell_delta_group<T, MODE, NT, V7, 4, S, PAD>(ip + (size_t) (g + gs) * GB, vals, g + gs, lane, x, s, off, len);
+		sell_delta_group<T, MODE, NT, V7, 4, S, PAD>(ip + (size_t) (g + 2 * gs) * GB, vals, g + 2 * gs, lane, x, s, off, len);
+		sell_delta_group<T, MODE, NT, V7, 4, S, PAD>(ip + (size_t) (g + 3 * gs) * GB, vals, g + 3 * gs, lane, x, s, off, len);
 	}
-	for (; g + 2 * gs < full_end; g += 3 * gs)
+	for (; !PAD && g + 2 * gs < full_end; g += 3 * gs)
 	{
-		sell_delta_group<T, MODE, NT, V7>(ip + (size_t) g * GB, vals, g, lane, x, s, off);
-		sell_delta_group<T, MODE, NT, V7>(ip + (size_t) (g + gs) * GB, vals, g + gs, lane, x, s, off);
-		sell_delta_group<T, MODE, NT, V7>(ip + (size_t) (g + 2 * gs) * GB, vals, g + 2 * gs, lane, x, s, off);
+		sell_delta_group<T, MODE, NT, V7, 4, S, PAD>(ip + (size_t) g * GB, vals, g, lane, x, s, off, len);
+		sell_delta_group<T, MODE, NT, V7, 4, S, PAD>(ip + (size_t) (g + gs) * GB, vals, g + gs, lane, x, s, off, len);
+		sell_delta_group<T, MODE, NT, V7, 4, S, PAD>(ip + (size_t) (g + 2 * gs) * GB, vals, g + 2 * gs, lane, x, s, off, len);
 	}
 	for (; g + gs < (rem == 4 ? groups : last); g += 2 * gs)    // 8 steps in flight per trip
 	{
-		sell_delta_group<T, MODE, NT, V7>(ip + (size_t) g * GB, vals, g, lane, x, s, off);
-		sell_delta_group<T, MODE, NT, V7>(ip + (size_t) (g + gs) * GB, vals, g + gs, lane, x, s, off);
+		sell_delta_group<T, MODE, NT, V7, 4, S, PAD>(ip + (size_t) g * GB, vals, g, lane, x, s, off, len);
+		sell_delta_group<T, MODE, NT, V7, 4, S, PAD>(ip + (size_t) (g + gs) * GB, vals, g + gs, lane, x, s, off, len);
 	}
 	for (; g < (rem == 4 ? groups : last); g += gs)
-		sell_delta_group<T, MODE, NT, V7>(ip + (size_t) g * GB, vals, g, lane, x, s, off);
+		sell_delta_group<T, MODE, NT, V7, 4, S, PAD>(ip + (size_t) g * GB, vals, g, lane, x, s, off, len);
 	if (rem != 4 && g == last)
 	{
 		if (rem == 1)
-			sell_delta_group<T, MODE, NT, V7, 1>(ip + (size_t) g * GB, vals, g, lane, x, s, off);
+			sell_delta_group<T, MODE, NT, V7, 1, S, PAD>(ip + (size_t) g * GB, vals, g, lane, x, s, off, len);
 		else if (rem == 2)
-			sell_delta_group<T, MODE, NT, V7, 2>(ip + (size_t) g * GB, vals, g, lane, x, s, off);
+			sell_delta_group<T, MODE, NT, V7, 2, S, PAD>(ip + (size_t) g * GB, vals, g, lane, x, s, off, len);
 		else
-			sell_delta_group<T, MODE, NT, V7, 3>(ip + (size_t) g * GB, vals, g, lane, x, s, off);
+			sell_delta_group<T, MODE, NT, V7, 3, S, PAD>(ip + (size_t) g * GB, vals, g, lane, x, s, off, len);
 	}
 	return s;
 }
@@ -516,19 +551,30 @@ sell_delta_slice5(const unsigned char * __restrict__ ip, const SellVals<T, NT, V
 template <typename T, bool NT, bool V7, typename S = T>
 __device__ __forceinline__ T
 sell_delta_modes(int mode, const unsigned char * __restrict__ ip, const SellVals<T, NT, V7, S> & vals, int width, int lane, const T * __restrict__ x,
-		int g0, int gs)
+		int g0, int gs, bool padded /* uniform */, const int * __restrict__ slice_len /* uniform */)
 {
 	if (mode == 0)
-		return sell_delta_slice<T, 0, NT>(ip, vals, width, lane, x, g0, gs);
-	if (mode == 1)
-		return sell_delta_slice<T, 1, NT>(ip, vals, width, lane, x, g0, gs);
-	if (mode == 2)
-		return sell_delta_slice<T, 2, NT>(ip, vals, width, lane, x, g0, gs);
+		return sell_delta_slice<T, 0, NT, false>(ip, vals, width, lane, x, g0, gs);
 	if (mode == 3)
-		return sell_delta_slice<T, 3, NT>(ip, vals, width, lane, x, g0, gs);
+		return sell_delta_slice<T, 3, NT, false>(ip, vals, width, lane, x, g0, gs);
 	if (mode == 5)
 		return sell_delta_slice5<T, NT>(ip, vals, width, lane, x, g0, gs);
-	return sell_delta_slice<T, 4, NT>(ip, vals, width, lane, x, g0, gs);
+	// the modes with a column per lane and step are the ones whose slices may hold rows of different lengths: the few that do go to
+	// the readers that mask the padding steps (sell_delta_group)
+	if (padded)
+	{
+		const int len = slice_len[lane];
+		if (mode == 1)
+			return sell_delta_slice<T, 1, NT, true>(ip, vals, width, lane, x, g0, gs, len);
+		if (mode == 2)
+			return sell_delta_slice<T, 2, NT, true>(ip, vals, width, lane, x, g0, gs, len);
+		return sell_delta_slice<T, 4, NT, true>(ip, vals, width, lane, x, g0, gs, len);
+	}
+	if (mode == 1)
+		return sell_delta_slice<T, 1, NT, false>(ip, vals, width, lane, x, g0, gs);
+	if (mode == 2)
+		return sell_delta_slice<T, 2, NT, false>(ip, vals, width, lane, x, g0, gs);
+	return sell_delta_slice<T, 4, NT, false>(ip, vals, width, lane, x, g0, gs);
 }
 
 // one slice from its two descriptor words (sell_delta_layout.hpp): V7 = the handle holds slices with 7-byte values, each one flagged in
@@ -536,19 +582,22 @@ sell_delta_modes(int mode, const unsigned char * __restrict__ ip, const SellVals
 template <typename T, bool NT, bool V7, typename S = T>
 __device__ __forceinline__ T
 sell_delta_one(const int64_t * __restrict__ desc, int slice, const unsigned char * __restrict__ idx, const S * __restrict__ val, int lane,
-		const T * __restrict__ x, int g0, int gs)
+		const T * __restrict__ x, int g0, int gs, const int * __restrict__ row_len, int num_slices)
 {
 	const int64_t v_off = desc[2 * slice];
 	const int64_t i_word = desc[2 * slice + 1];
 	const int64_t v_next = desc[2 * slice + 2];
+	// whether the slice holds value padding (launch.hpp: sell_pad_bits): uniform, a scalar load beside the descriptor's
+	const bool padded = (sell_pad_bits(row_len, num_slices, WAVE)[slice >> 5] >> (slice & 31)) & 1u;
+	const int * slice_len = row_len + (long) slice * WAVE;          // the lengths of the slice's 64 rows (uniform)
 	const int mode = sell_desc_mode(i_word);
 	const unsigned char * ip = idx + sell_desc_idx(i_word);
 	const S * vp = val + v_off + 2 * lane;
 	if (V7 && sell_desc_v7(i_word))
 		return sell_delta_modes<T, NT, V7>(mode, ip, SellVals<T, NT, V7, S>{vp, lane, (unsigned) (sell_v7_e0(i_word) - 1) << 20},
-				(int) sell_slice_width(v_next - v_off, true), lane, x, g0, gs);
+				(int) sell_slice_width(v_next - v_off, true), lane, x, g0, gs, padded, slice_len);
 	return sell_delta_modes<T, NT, false>(mode, ip, SellVals<T, NT, false, S>{vp, lane, 0u}, (int) sell_slice_width(v_next - v_off, false), lane, x,
-			g0, gs);
+			g0, gs, padded, slice_len);
 }
 
 // sell_delta_kernel has a workgroup size of its own (launch.hpp: SELL_DELTA_WAVES), apart from the SELL_WAVES that
@@ -582,7 +631,7 @@ sell_delta_tile_map(const XcdMap & mp, int num_slices)
 template <typename T, bool NT, bool V7, int W = sell_delta_waves<T>()>
 __global__ __launch_bounds__(W * WAVE) void
 sell_delta_kernel(const int64_t * __restrict__ desc, const unsigned char * __restrict__ idx, const T * __restrict__ val,
-		const int * __restrict__ row_of_sorted, const T * __restrict__ x, T * __restrict__ y,
+		const int * __restrict__ row_of_sorted, const int * __restrict__ row_len, const T * __restrict__ x, T * __restrict__ y,
 		int m, int num_slices, int beta, XcdMap map)
 {
 	unsigned tile = xcd_tile(blockIdx.x, map);
@@ -592,7 +641,7 @@ sell_delta_kernel(const int64_t * __restrict__ desc, const unsigned char * __res
 	const int slice = __builtin_amdgcn_readfirstlane((int) (tile * W + threadIdx.x / WAVE));
 	if (slice >= num_slices)
 		return;
-	const T s = sell_delta_one<T, NT, V7>(desc, slice, idx, val, lane, x, 0, 1);
+	const T s = sell_delta_one<T, NT, V7>(desc, slice, idx, val, lane, x, 0, 1, row_len, num_slices);
 	const long sorted_row = (long) slice * WAVE + lane;
 	if (sorted_row < m)
 	{
@@ -607,7 +656,7 @@ sell_delta_kernel(const int64_t * __restrict__ desc, const unsigned char * __res
 template <typename T, int S, bool NT, bool V7>
 __global__ __launch_bounds__(SELL_BLOCK) void
 sell_delta_split_kernel(const int64_t * __restrict__ desc, const unsigned char * __restrict__ idx, const T * __restrict__ val,
-		const int * __restrict__ row_of_sorted, const T * __restrict__ x, T * __restrict__ y,
+		const int * __restrict__ row_of_sorted, const int * __restrict__ row_len, const T * __restrict__ x, T * __restrict__ y,
 		int m, int num_slices, int beta, XcdMap map)
 {
 	constexpr int SPB = SELL_WAVES / S;      // slices per workgroup
@@ -621,7 +670,7 @@ sell_delta_split_kernel(const int64_t * __restrict__ desc, const unsigned char *
 	const int slice = __builtin_amdgcn_readfirstlane((int) (tile * SPB + wave / S));
 	T s = 0;
 	if (slice < num_slices)
-		s = sell_delta_one<T, NT, V7>(desc, slice, idx, val, lane, x, w, S);
+		s = sell_delta_one<T, NT, V7>(desc, slice, idx, val, lane, x, w, S, row_len, num_slices);
 	s_part[wave][lane] = s;
 	__syncthreads();
 	if (w == 0 && slice < num_slices)
@@ -646,7 +695,7 @@ sell_delta_split_kernel(const int64_t * __restrict__ desc, const unsigned char *
 template <bool NT>
 __global__ __launch_bounds__(SELL_BLOCK) void
 sell_delta_mixed_kernel(const int64_t * __restrict__ desc, const unsigned char * __restrict__ idx, const float * __restrict__ val,
-		const int * __restrict__ row_of_sorted, const double * __restrict__ x, double * __restrict__ y,
+		const int * __restrict__ row_of_sorted, const int * __restrict__ row_len, const double * __restrict__ x, double * __restrict__ y,
 		int m, int num_slices, int beta, XcdMap map)
 {
 	unsigned tile = xcd_tile(blockIdx.x, map);
@@ -656,7 +705,7 @@ sell_delta_mixed_kernel(const int64_t * __restrict__ desc, const unsigned char *
 	const int slice = __builtin_amdgcn_readfirstlane((int) (tile * SELL_WAVES + threadIdx.x / WAVE));
 	if (slice >= num_slices)
 		return;
-	const double s = sell_delta_one<double, NT, false>(desc, slice, idx, val, lane, x, 0, 1);
+	const double s = sell_delta_one<double, NT, false>(desc, slice, idx, val, lane, x, 0, 1, row_len, num_slices);
 	const long sorted_row = (long) slice * WAVE + lane;
 	if (sorted_row < m)
 	{
@@ -669,7 +718,7 @@ sell_delta_mixed_kernel(const int64_t * __restrict__ desc, const unsigned char *
 template <int S, bool NT>
 __global__ __launch_bounds__(SELL_BLOCK) void
 sell_delta_mixed_split_kernel(const int64_t * __restrict__ desc, const unsigned char * __restrict__ idx, const float * __restrict__ val,
-		const int * __restrict__ row_of_sorted, const double * __restrict__ x, double * __restrict__ y,
+		const int * __restrict__ row_of_sorted, const int * __restrict__ row_len, const double * __restrict__ x, double * __restrict__ y,
 		int m, int num_slices, int beta, XcdMap map)
 {
 	constexpr int SPB = SELL_WAVES / S;
@@ -683,7 +732,7 @@ sell_delta_mixed_split_kernel(const int64_t * __restrict__ desc, const unsigned 
 	const int slice = __builtin_amdgcn_readfirstlane((int) (tile * SPB + wave / S));
 	double s = 0;
 	if (slice < num_slices)
-		s = sell_delta_one<double, NT, false>(desc, slice, idx, val, lane, x, w, S);
+		s = sell_delta_one<double, NT, false>(desc, slice, idx, val, lane, x, w, S, row_len, num_slices);
 	s_part[wave][lane] = s;
 	__syncthreads();
 	if (w == 0 && slice < num_slices)
@@ -704,7 +753,7 @@ sell_delta_mixed_split_kernel(const int64_t * __restrict__ desc, const unsigned 
 // MIXED: T = double over values stored as float (sell_delta_mixed_kernel); V7 is then false
 template <typename T, bool V7, bool MIXED = false>
 static int
-sell_delta_launch(int S, const int64_t * desc, const unsigned char * idx, const void * val, const int * row_of_sorted, const void * x, void * y,
+sell_delta_launch(int S, const int64_t * desc, const unsigned char * idx, const void * val, const int * row_of_sorted, const int * row_len, const void * x, void * y,
 		int m, int num_slices, const LaunchCfg & cfg, hipStream_t stream, long * grid_out)
 {
 	unsigned grid = xcd_grid(cfg.map);
@@ -714,7 +763,7 @@ sell_delta_launch(int S, const int64_t * desc, const unsigned char * idx, const 
 		return 0;
 	typedef std::conditional_t<MIXED, float, T> SV;
 	#define SELLD_LAUNCH(K) hipLaunchKernelGGL(K, dim3(grid), dim3(SELL_BLOCK), 0, stream, desc, idx, (const SV *) val, \
-			row_of_sorted, (const T *) x, (T *) y, m, num_slices, cfg.beta, cfg.map)
+			row_of_sorted, row_len, (const T *) x, (T *) y, m, num_slices, cfg.beta, cfg.map)
 	if (S != 1 && S != 2 && S != 4)
 	{
 		set_error("sell_delta: waves per slice must be 1, 2 or 4 (got %d)", S);
@@ -747,7 +796,7 @@ sell_delta_launch(int S, const int64_t * desc, const unsigned char * idx, const 
 		if (grid_out)
 			*grid_out = grid;
 		#define SELLD_LAUNCH1(K) hipLaunchKernelGGL(K, dim3(grid), dim3(W * WAVE), 0, stream, desc, idx, (const T *) val, \
-				row_of_sorted, (const T *) x, (T *) y, m, num_slices, cfg.beta, map1)
+				row_of_sorted, row_len, (const T *) x, (T *) y, m, num_slices, cfg.beta, map1)
 		if (cfg.nt) SELLD_LAUNCH1((sell_delta_kernel<T, true, V7>));
 		else        SELLD_LAUNCH1((sell_delta_kernel<T, false, V7>));
 		#undef SELLD_LAUNCH1
@@ -769,7 +818,7 @@ sell_delta_launch(int S, const int64_t * desc, const unsigned char * idx, const 
 
 int
 launch_sell_delta(bool f32, bool val_f32, int waves_per_slice, bool v7, const int64_t * desc, const unsigned char * idx, const void * val, const int * row_of_sorted,
-		const void * x, void * y, int m, int num_slices, const LaunchCfg & cfg, hipStream_t stream, long * grid_out)
+		const int * row_len, const void * x, void * y, int m, int num_slices, const LaunchCfg & cfg, hipStream_t stream, long * grid_out)
 {
 	if (val_f32 && v7)
 	{
@@ -782,15 +831,15 @@ launch_sell_delta(bool f32, bool val_f32, int waves_per_slice, bool v7, const in
 		return 1;
 	}
 	if (val_f32 && !f32)
-		return sell_delta_launch<double, false, true>(waves_per_slice, desc, idx, val, row_of_sorted, x, y, m, num_slices, cfg, stream, grid_out);
-	return f32 ? sell_delta_launch<float, false>(waves_per_slice, desc, idx, val, row_of_sorted, x, y, m, num_slices, cfg, stream, grid_out)
-	     : v7  ? sell_delta_launch<double, true>(waves_per_slice, desc, idx, val, row_of_sorted, x, y, m, num_slices, cfg, stream, grid_out)
-	           : sell_delta_launch<double, false>(waves_per_slice, desc, idx, val, row_of_sorted, x, y, m, num_slices, cfg, stream, grid_out);
+		return sell_delta_launch<double, false, true>(waves_per_slice, desc, idx, val, row_of_sorted, row_len, x, y, m, num_slices, cfg, stream, grid_out);
+	return f32 ? sell_delta_launch<float, false>(waves_per_slice, desc, idx, val, row_of_sorted, row_len, x, y, m, num_slices, cfg, stream, grid_out)
+	     : v7  ? sell_delta_launch<double, true>(waves_per_slice, desc, idx, val, row_of_sorted, row_len, x, y, m, num_slices, cfg, stream, grid_out)
+	           : sell_delta_launch<double, false>(waves_per_slice, desc, idx, val, row_of_sorted, row_len, x, y, m, num_slices, cfg, stream, grid_out);
 }
 
 template <typename T, int C>
 static int
-sell_launch_c(const int64_t * slice_ptr, const int * col, const void * val, const int * row_of_sorted, const void * x, void * y,
+sell_launch_c(const int64_t * slice_ptr, const int * col, const void * val, const int * row_of_sorted, const int * row_len, const void * x, void * y,
 		int m, int num_slices, const LaunchCfg & cfg, hipStream_t stream, long * grid_out)
 {
 	unsigned grid = xcd_grid(cfg.map);
@@ -800,17 +849,17 @@ sell_launch_c(const int64_t * slice_ptr, const int * col, const void * val, cons
 		return 0;
 	if (cfg.nt)
 		hipLaunchKernelGGL((sell_kernel<T, C, true>), dim3(grid), dim3(SELL_BLOCK), 0, stream, slice_ptr, col, (const T *) val,
-				row_of_sorted, (const T *) x, (T *) y, m, num_slices, cfg.beta, cfg.map);
+				row_of_sorted, row_len, (const T *) x, (T *) y, m, num_slices, cfg.beta, cfg.map);
 	else
 		hipLaunchKernelGGL((sell_kernel<T, C, false>), dim3(grid), dim3(SELL_BLOCK), 0, stream, slice_ptr, col, (const T *) val,
-				row_of_sorted, (const T *) x, (T *) y, m, num_slices, cfg.beta, cfg.map);
+				row_of_sorted, row_len, (const T *) x, (T *) y, m, num_slices, cfg.beta, cfg.map);
 	HIP_TRY(hipGetLastError());
 	return 0;
 }
 
 template <typename T>
 static int
-sell_dispatch(int C, const int64_t * slice_ptr, const int * col, const void * val, const int * row_of_sorted, const void * x, void * y,
+sell_dispatch(int C, const int64_t * slice_ptr, const int * col, const void * val, const int * row_of_sorted, const int * row_len, const void * x, void * y,
 		int m, int num_slices, const LaunchCfg & cfg, hipStream_t stream, long * grid_out)
 {
 	if (C == SELL_WIDE_C)
@@ -822,18 +871,18 @@ sell_dispatch(int C, const int64_t * slice_ptr, const int * col, const void * va
 			return 0;
 		if (cfg.nt)
 			hipLaunchKernelGGL((sell_wide_kernel<T, true>), dim3(grid), dim3(SELL_WIDE_C), 0, stream, slice_ptr, col, (const T *) val, row_of_sorted,
-					(const T *) x, (T *) y, m, num_slices, cfg.beta, cfg.map);
+					row_len, (const T *) x, (T *) y, m, num_slices, cfg.beta, cfg.map);
 		else
 			hipLaunchKernelGGL((sell_wide_kernel<T, false>), dim3(grid), dim3(SELL_WIDE_C), 0, stream, slice_ptr, col, (const T *) val, row_of_sorted,
-					(const T *) x, (T *) y, m, num_slices, cfg.beta, cfg.map);
+					row_len, (const T *) x, (T *) y, m, num_slices, cfg.beta, cfg.map);
 		HIP_TRY(hipGetLastError());
 		return 0;
 	}
 	switch (C)
 	{
-		case 16: return sell_launch_c<T, 16>(slice_ptr, col, val, row_of_sorted, x, y, m, num_slices, cfg, stream, grid_out);
-		case 32: return sell_launch_c<T, 32>(slice_ptr, col, val, row_of_sorted, x, y, m, num_slices, cfg, stream, grid_out);
-		case 64: return sell_launch_c<T, 64>(slice_ptr, col, val, row_of_sorted, x, y, m, num_slices, cfg, stream, grid_out);
+		case 16: return sell_launch_c<T, 16>(slice_ptr, col, val, row_of_sorted, row_len, x, y, m, num_slices, cfg, stream, grid_out);
+		case 32: return sell_launch_c<T, 32>(slice_ptr, col, val, row_of_sorted, row_len, x, y, m, num_slices, cfg, stream, grid_out);
+		case 64: return sell_launch_c<T, 64>(slice_ptr, col, val, row_of_sorted, row_len, x, y, m, num_slices, cfg, stream, grid_out);
 	}
 	set_error("sell: C must be 16, 32, 64 or 256 (got %d)", C);
 	return 1;
@@ -841,10 +890,10 @@ sell_dispatch(int C, const int64_t * slice_ptr, const int * col, const void * va
 
 int
 launch_sell(bool f32, int C, const int64_t * slice_ptr, const int * col, const void * val, const int * row_of_sorted,
-		const void * x, void * y, int m, int num_slices, const LaunchCfg & cfg, hipStream_t stream, long * grid_out)
+		const int * row_len, const void * x, void * y, int m, int num_slices, const LaunchCfg & cfg, hipStream_t stream, long * grid_out)
 {
-	return f32 ? sell_dispatch<float>(C, slice_ptr, col, val, row_of_sorted, x, y, m, num_slices, cfg, stream, grid_out)
-	           : sell_dispatch<double>(C, slice_ptr, col, val, row_of_sorted, x, y, m, num_slices, cfg, stream, grid_out);
+	return f32 ? sell_dispatch<float>(C, slice_ptr, col, val, row_of_sorted, row_len, x, y, m, num_slices, cfg, stream, grid_out)
+	           : sell_dispatch<double>(C, slice_ptr, col, val, row_of_sorted, row_len, x, y, m, num_slices, cfg, stream, grid_out);
 }
 
 }  // namespace spmv

@@ -81,9 +81,11 @@ struct SpmmCols5 {
 };
 
 // NG full groups g[0..NG) of a slice: all loads of the trip first (indices, values, then the gathers), then the FMAs step by step
-template <typename T, int K, int VW, int NG, bool NT, bool V7, typename Cols, typename SV = T>
+// PAD: the slice holds rows shorter than its width (kernels_sell.hip: sell_delta_group): the steps of a lane from `len`, its row's length, on
+// are padding — 0.0 times a column of some other row — and take zeros in place of that row of X
+template <typename T, int K, int VW, int NG, bool NT, bool V7, bool PAD, typename Cols, typename SV = T>
 __device__ __forceinline__ void
-spmm_trip(const Cols & cols, const SellVals<T, NT, V7, SV> & vals, const int (&g)[NG], const T * __restrict__ X, long ldx, T (&acc)[K])
+spmm_trip(const Cols & cols, const SellVals<T, NT, V7, SV> & vals, const int (&g)[NG], const T * __restrict__ X, long ldx, T (&acc)[K], int len)
 {
 	int c[NG][4];
 	T v[NG][4];
@@ -99,6 +101,16 @@ spmm_trip(const Cols & cols, const SellVals<T, NT, V7, SV> & vals, const int (&g
 		#pragma unroll
 		for (int t = 0; t < 4; t++)
 			spmm_gather<T, K, VW>(X + (long) c[u][t] * ldx, xv[u][t]);
+	if constexpr (PAD)
+	{
+		#pragma unroll
+		for (int u = 0; u < NG; u++)
+			#pragma unroll
+			for (int t = 0; t < 4; t++)
+				#pragma unroll
+				for (int j = 0; j < K; j++)
+					xv[u][t][j] = 4 * g[u] + t < len ? xv[u][t][j] : T(0);
+	}
 	#pragma unroll
 	for (int u = 0; u < NG; u++)
 		#pragma unroll
@@ -109,9 +121,9 @@ spmm_trip(const Cols & cols, const SellVals<T, NT, V7, SV> & vals, const int (&g
 }
 
 // the last group of a slice whose width is not a multiple of 4: NSTEPS (1..3) real steps
-template <typename T, int K, int VW, int NSTEPS, bool NT, bool V7, typename Cols, typename SV = T>
+template <typename T, int K, int VW, int NSTEPS, bool NT, bool V7, bool PAD, typename Cols, typename SV = T>
 __device__ __forceinline__ void
-spmm_tail(const Cols & cols, const SellVals<T, NT, V7, SV> & vals, int g, int lane, const T * __restrict__ X, long ldx, T (&acc)[K])
+spmm_tail(const Cols & cols, const SellVals<T, NT, V7, SV> & vals, int g, int lane, const T * __restrict__ X, long ldx, T (&acc)[K], int len)
 {
 	int c[4];
 	cols(g, c);
@@ -121,6 +133,14 @@ spmm_tail(const Cols & cols, const SellVals<T, NT, V7, SV> & vals, int g, int la
 	#pragma unroll
 	for (int t = 0; t < NSTEPS; t++)
 		spmm_gather<T, K, VW>(X + (long) c[t] * ldx, xv[t]);
+	if constexpr (PAD)
+	{
+		#pragma unroll
+		for (int t = 0; t < NSTEPS; t++)
+			#pragma unroll
+			for (int j = 0; j < K; j++)
+				xv[t][j] = 4 * g + t < len ? xv[t][j] : T(0);
+	}
 	#pragma unroll
 	for (int t = 0; t < NSTEPS; t++)
 		#pragma unroll
@@ -129,12 +149,12 @@ spmm_tail(const Cols & cols, const SellVals<T, NT, V7, SV> & vals, int g, int la
 }
 
 // groups g0, g0 + gs, ... of one slice in order (gs = 1: the whole slice), then its tail group if this wave's sequence reaches it
-template <typename T, int K, int VW, bool NT, bool V7, typename Cols, typename SV = T>
+template <typename T, int K, int VW, bool NT, bool V7, bool PAD = false, typename Cols, typename SV = T>
 __device__ __forceinline__ void
 spmm_walk(const Cols & cols, const SellVals<T, NT, V7, SV> & vals, int width, int lane, const T * __restrict__ X, long ldx, T (&acc)[K], int g0,
-		int gs)
+		int gs, int len = 0)
 {
-	constexpr int NG = spmm_trip_groups<T, K>();
+	constexpr int NG = PAD ? 1 : spmm_trip_groups<T, K>();     // (a padded slice goes group by group: the few there are get no deep trips of their own)
 	const int groups = (width + 3) / 4;            // index groups cover the width rounded up to 4 steps, values only the real steps
 	const int rem = width - 4 * (groups - 1);
 	const int last = groups - 1;
@@ -146,30 +166,30 @@ spmm_walk(const Cols & cols, const SellVals<T, NT, V7, SV> & vals, int width, in
 		#pragma unroll
 		for (int u = 0; u < NG; u++)
 			gg[u] = g + u * gs;
-		spmm_trip<T, K, VW, NG, NT, V7>(cols, vals, gg, X, ldx, acc);
+		spmm_trip<T, K, VW, NG, NT, V7, PAD>(cols, vals, gg, X, ldx, acc, len);
 	}
 	if constexpr (NG >= 4)
 		if (g + gs < full)
 		{
 			const int gg[2] = {g, g + gs};
-			spmm_trip<T, K, VW, 2, NT, V7>(cols, vals, gg, X, ldx, acc);
+			spmm_trip<T, K, VW, 2, NT, V7, PAD>(cols, vals, gg, X, ldx, acc, len);
 			g += 2 * gs;
 		}
 	if constexpr (NG >= 2)
 		if (g < full)
 		{
 			const int gg[1] = {g};
-			spmm_trip<T, K, VW, 1, NT, V7>(cols, vals, gg, X, ldx, acc);
+			spmm_trip<T, K, VW, 1, NT, V7, PAD>(cols, vals, gg, X, ldx, acc, len);
 			g += gs;
 		}
 	if (rem != 4 && g == last)
 	{
 		if (rem == 1)
-			spmm_tail<T, K, VW, 1, NT, V7>(cols, vals, g, lane, X, ldx, acc);
+			spmm_tail<T, K, VW, 1, NT, V7, PAD>(cols, vals, g, lane, X, ldx, acc, len);
 		else if (rem == 2)
-			spmm_tail<T, K, VW, 2, NT, V7>(cols, vals, g, lane, X, ldx, acc);
+			spmm_tail<T, K, VW, 2, NT, V7, PAD>(cols, vals, g, lane, X, ldx, acc, len);
 		else
-			spmm_tail<T, K, VW, 3, NT, V7>(cols, vals, g, lane, X, ldx, acc);
+			spmm_tail<T, K, VW, 3, NT, V7, PAD>(cols, vals, g, lane, X, ldx, acc, len);
 	}
 }
 
@@ -177,10 +197,21 @@ spmm_walk(const Cols & cols, const SellVals<T, NT, V7, SV> & vals, int width, in
 template <typename T, int K, int VW, bool NT, bool V7, typename SV = T>
 __device__ __forceinline__ void
 spmm_modes(int mode, const unsigned char * __restrict__ ip, const SellVals<T, NT, V7, SV> & vals, int width, int lane, const T * __restrict__ X,
-		long ldx, T (&acc)[K], int g0, int gs)
+		long ldx, T (&acc)[K], int g0, int gs, bool padded /* uniform */, const int * __restrict__ slice_len /* uniform */)
 {
 	if (mode == 0)
 		spmm_walk<T, K, VW, NT, V7>(SpmmCols<0, NT>{ip, lane, lane}, vals, width, lane, X, ldx, acc, g0, gs);
+	else if (padded && (mode == 1 || mode == 2 || mode == 4))
+	{
+		// rows of different lengths (only the modes with a column per lane and step hold such slices): the padding steps masked
+		const int len = slice_len[lane];
+		if (mode == 1)
+			spmm_walk<T, K, VW, NT, V7, true>(SpmmCols<1, NT>{ip, lane, 0}, vals, width, lane, X, ldx, acc, g0, gs, len);
+		else if (mode == 2)
+			spmm_walk<T, K, VW, NT, V7, true>(SpmmCols<2, NT>{ip, lane, 0}, vals, width, lane, X, ldx, acc, g0, gs, len);
+		else
+			spmm_walk<T, K, VW, NT, V7, true>(SpmmCols<4, NT>{ip, lane, 0}, vals, width, lane, X, ldx, acc, g0, gs, len);
+	}
 	else if (mode == 1)
 		spmm_walk<T, K, VW, NT, V7>(SpmmCols<1, NT>{ip, lane, 0}, vals, width, lane, X, ldx, acc, g0, gs);
 	else if (mode == 2)
@@ -212,7 +243,7 @@ spmm_modes(int mode, const unsigned char * __restrict__ ip, const SellVals<T, NT
 template <typename T, int K, int VW, int S, bool NT, bool V7>
 __global__ __launch_bounds__(SPMM_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) void
 sell_delta_spmm_kernel(const int64_t * __restrict__ desc, const unsigned char * __restrict__ idx, const T * __restrict__ val,
-		const int * __restrict__ row_of_sorted, const T * __restrict__ X, long ldx, T * __restrict__ Y, long ldy, int m, int num_slices,
+		const int * __restrict__ row_of_sorted, const int * __restrict__ row_len, const T * __restrict__ X, long ldx, T * __restrict__ Y, long ldy, int m, int num_slices,
 		int beta, XcdMap map)
 {
 	constexpr int SPB = SPMM_WAVES / S;            // slices per workgroup
@@ -235,6 +266,8 @@ sell_delta_spmm_kernel(const int64_t * __restrict__ desc, const unsigned char * 
 		const int64_t i_word = desc[2 * slice + 1];
 		const int64_t v_next = desc[2 * slice + 2];
 		const int mode = sell_desc_mode(i_word);
+		const bool padded = (sell_pad_bits(row_len, num_slices, WAVE)[slice >> 5] >> (slice & 31)) & 1u;     // the slice holds value padding (launch.hpp)
+		const int * slice_len = row_len + (long) slice * WAVE;          // the lengths of the slice's 64 rows (uniform)
 		const unsigned char * ip = idx + sell_desc_idx(i_word);
 		const T * vp = val + v_off + 2 * lane;
 		bool done = false;
@@ -242,12 +275,12 @@ sell_delta_spmm_kernel(const int64_t * __restrict__ desc, const unsigned char * 
 			if (sell_desc_v7(i_word))
 			{
 				spmm_modes<T, K, VW, NT, true>(mode, ip, SellVals<T, NT, true>{vp, lane, (unsigned) (sell_v7_e0(i_word) - 1) << 20},
-						(int) sell_slice_width(v_next - v_off, true), lane, X, ldx, acc, w, S);
+						(int) sell_slice_width(v_next - v_off, true), lane, X, ldx, acc, w, S, padded, slice_len);
 				done = true;
 			}
 		if (!done)
 			spmm_modes<T, K, VW, NT, false>(mode, ip, SellVals<T, NT, false>{vp, lane, 0u}, (int) sell_slice_width(v_next - v_off, false), lane, X,
-					ldx, acc, w, S);
+					ldx, acc, w, S, padded, slice_len);
 	}
 	if constexpr (S > 1)
 	{
@@ -283,7 +316,7 @@ sell_delta_spmm_kernel(const int64_t * __restrict__ desc, const unsigned char * 
 template <int K, int VW, int S, bool NT>
 __global__ __launch_bounds__(SPMM_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) void
 sell_delta_mixed_spmm_kernel(const int64_t * __restrict__ desc, const unsigned char * __restrict__ idx, const float * __restrict__ val,
-		const int * __restrict__ row_of_sorted, const double * __restrict__ X, long ldx, double * __restrict__ Y, long ldy, int m,
+		const int * __restrict__ row_of_sorted, const int * __restrict__ row_len, const double * __restrict__ X, long ldx, double * __restrict__ Y, long ldy, int m,
 		int num_slices, int beta, XcdMap map)
 {
 	typedef double T;
@@ -307,10 +340,12 @@ sell_delta_mixed_spmm_kernel(const int64_t * __restrict__ desc, const unsigned c
 		const int64_t i_word = desc[2 * slice + 1];
 		const int64_t v_next = desc[2 * slice + 2];
 		const int mode = sell_desc_mode(i_word);
+		const bool padded = (sell_pad_bits(row_len, num_slices, WAVE)[slice >> 5] >> (slice & 31)) & 1u;     // the slice holds value padding (launch.hpp)
+		const int * slice_len = row_len + (long) slice * WAVE;          // the lengths of the slice's 64 rows (uniform)
 		const unsigned char * ip = idx + sell_desc_idx(i_word);
 		const float * vp = val + v_off + 2 * lane;
 		spmm_modes<T, K, VW, NT, false>(mode, ip, SellVals<T, NT, false, float>{vp, lane, 0u}, (int) sell_slice_width(v_next - v_off, false), lane, X,
-				ldx, acc, w, S);
+				ldx, acc, w, S, padded, slice_len);
 	}
 	if constexpr (S > 1)
 	{
@@ -346,6 +381,7 @@ struct SpmmArgs {
 	const unsigned char * idx;
 	const void * val;
 	const int * row_of_sorted;
+	const int * row_len;
 	int m, num_slices;
 };
 
@@ -357,10 +393,10 @@ spmm_launch(int S, const SpmmArgs & a, const void * X, long ldx, void * Y, long 
 	#define SPMM_LAUNCH(S_, NT_) do { \
 			if constexpr (MIXED) \
 				hipLaunchKernelGGL((sell_delta_mixed_spmm_kernel<K, VW, S_, NT_>), dim3(grid), dim3(SPMM_BLOCK), 0, stream, a.desc, a.idx, \
-						(const float *) a.val, a.row_of_sorted, (const double *) X, ldx, (double *) Y, ldy, a.m, a.num_slices, cfg.beta, cfg.map); \
+						(const float *) a.val, a.row_of_sorted, a.row_len, (const double *) X, ldx, (double *) Y, ldy, a.m, a.num_slices, cfg.beta, cfg.map); \
 			else \
 				hipLaunchKernelGGL((sell_delta_spmm_kernel<T, K, VW, S_, NT_, V7>), dim3(grid), dim3(SPMM_BLOCK), 0, stream, a.desc, a.idx, \
-						(const T *) a.val, a.row_of_sorted, (const T *) X, ldx, (T *) Y, ldy, a.m, a.num_slices, cfg.beta, cfg.map); \
+						(const T *) a.val, a.row_of_sorted, a.row_len, (const T *) X, ldx, (T *) Y, ldy, a.m, a.num_slices, cfg.beta, cfg.map); \
 		} while (0)
 	if (S == 1)
 	{
@@ -422,11 +458,11 @@ spmm_passes(int S, const SpmmArgs & a, int k, const void * X, long ldx, void * Y
 
 int
 launch_sell_delta_spmm(bool f32, bool val_f32, int waves_per_slice, bool v7, const int64_t * desc, const unsigned char * idx, const void * val,
-		const int * row_of_sorted, int k, const void * X, long ldx, void * Y, long ldy, int m, int num_slices, const LaunchCfg & cfg,
-		hipStream_t stream, long * grid_out)
+		const int * row_of_sorted, const int * row_len, int k, const void * X, long ldx, void * Y, long ldy, int m, int num_slices,
+		const LaunchCfg & cfg, hipStream_t stream, long * grid_out)
 {
 	if (k == 1 && ldx == 1 && ldy == 1)            // one contiguous vector: the single-vector kernel itself
-		return launch_sell_delta(f32, val_f32, waves_per_slice, v7, desc, idx, val, row_of_sorted, X, Y, m, num_slices, cfg, stream, grid_out);
+		return launch_sell_delta(f32, val_f32, waves_per_slice, v7, desc, idx, val, row_of_sorted, row_len, X, Y, m, num_slices, cfg, stream, grid_out);
 	if (val_f32 && v7)
 	{
 		set_error("sell_delta_spmm: 7-byte values are fp64 only");
@@ -442,7 +478,7 @@ launch_sell_delta_spmm(bool f32, bool val_f32, int waves_per_slice, bool v7, con
 		*grid_out = grid;
 	if (grid == 0)
 		return 0;
-	const SpmmArgs a{desc, idx, val, row_of_sorted, m, num_slices};
+	const SpmmArgs a{desc, idx, val, row_of_sorted, row_len, m, num_slices};
 	if (val_f32 && !f32)
 		return spmm_passes<double, false, true>(waves_per_slice, a, k, X, ldx, Y, ldy, cfg, grid, stream);
 	return f32 ? spmm_passes<float, false>(waves_per_slice, a, k, X, ldx, Y, ldy, cfg, grid, stream)

@@ -65,7 +65,13 @@ int launch_merge(bool f32, int items_per_thread, const int * row_ptr, const int 
 		const LaunchCfg & cfg, hipStream_t stream, long * grid_out);
 
 // ---- SELL-C-sigma (kernels_sell.hip)
-int launch_sell(bool f32, int C, const int64_t * slice_ptr, const int * col, const void * val, const int * row_of_sorted,
+// row_len (build_sell.hip: sell_row_lengths): [num_slices * C] the stored entries of every sorted row (0 past the last row), then
+// [(num_slices + 31) / 32] words with bit s % 32 of word s / 32 set when slice s holds a row shorter than its longest one, i.e. value
+// padding. Padding is 0.0 times some valid column, and 0 * Inf is NaN: the kernels keep x out of every padding position with these
+// (include/spmv_mi355x.h "special values"). An empty row has no column of its own, so its sum is dropped; the delta kernels mask the
+// padding steps of the flagged slices.
+__host__ __device__ inline const unsigned * sell_pad_bits(const int * row_len, long num_slices, int C) { return reinterpret_cast<const unsigned *>(row_len + (long) num_slices * C); }
+int launch_sell(bool f32, int C, const int64_t * slice_ptr, const int * col, const void * val, const int * row_of_sorted, const int * row_len,
 		const void * x, void * y, int m, int num_slices, const LaunchCfg & cfg, hipStream_t stream, long * grid_out);
 
 // SELL-64-sigma with delta-compressed column indices (layout: sell_delta_layout.hpp)
@@ -73,14 +79,14 @@ int launch_sell(bool f32, int C, const int64_t * slice_ptr, const int * col, con
 // f32: x and y are float; val_f32: the value array is float. val_f32 without f32 = fp32 values under fp64 vectors (opts.value_storage):
 // the fp32 handle's arrays, the fp64 kernel's arithmetic (sell_delta_mixed_kernel)
 int launch_sell_delta(bool f32, bool val_f32, int waves_per_slice, bool v7, const int64_t * desc, const unsigned char * idx, const void * val, const int * row_of_sorted,
-		const void * x, void * y, int m, int num_slices, const LaunchCfg & cfg, hipStream_t stream, long * grid_out);
+		const int * row_len, const void * x, void * y, int m, int num_slices, const LaunchCfg & cfg, hipStream_t stream, long * grid_out);
 
 // Y = A X (beta 0) / Y += A X (beta 1) for k vectors on the same layout (kernels_sell_spmm.hip): X holds the cols() rows of k values at
 // X + c * ldx, Y the rows at Y + r * ldy. One launch per pass of 8, 4, 2 or 1 columns (8 per pass, then the binary remainder of k);
 // k == 1 with ldx == ldy == 1 is launch_sell_delta itself. Column j is bit-identical to launch_sell_delta on column j.
 int launch_sell_delta_spmm(bool f32, bool val_f32, int waves_per_slice, bool v7, const int64_t * desc, const unsigned char * idx, const void * val,
-		const int * row_of_sorted, int k, const void * X, long ldx, void * Y, long ldy, int m, int num_slices, const LaunchCfg & cfg,
-		hipStream_t stream, long * grid_out);
+		const int * row_of_sorted, const int * row_len, int k, const void * X, long ldx, void * Y, long ldy, int m, int num_slices,
+		const LaunchCfg & cfg, hipStream_t stream, long * grid_out);
 // columns of the next pass of a multi-vector product with `remaining` columns left on a layout whose pass serves at most `cap`
 // (8, 4, 2 or 1): the largest power of two <= min(cap, remaining). Every layout's launcher and spmv_mi355x_spmm_plan walk k with it.
 inline int

@@ -371,9 +371,9 @@ spmv_mi355x_spmv_device_async(spmv_mi355x_matrix * A, const void * x, void * y, 
 			     ? launch_sell_window(A->f32, A->sell_split, A->sellw_ns, A->d_sellw_grp, A->d_sell_desc, (const unsigned short *) A->d_sell_idx, A->d_val,
 					A->d_row_of_sorted, x, y, (int) A->m, A->sellw_lds, cfg, st, &grid)
 			     : A->sell_delta
-			     ? launch_sell_delta(A->f32, A->val_f32, A->sell_split, A->sell_v7_slices > 0, A->d_sell_desc, A->d_sell_idx, A->d_val, A->d_row_of_sorted, x, y, (int) A->m,
+			     ? launch_sell_delta(A->f32, A->val_f32, A->sell_split, A->sell_v7_slices > 0, A->d_sell_desc, A->d_sell_idx, A->d_val, A->d_row_of_sorted, A->d_sell_len, x, y, (int) A->m,
 					(int) A->sell_slices, cfg, st, &grid)
-			     : launch_sell(A->f32, A->sell_c, A->d_slice_ptr, A->d_col, A->d_val, A->d_row_of_sorted, x, y, (int) A->m,
+			     : launch_sell(A->f32, A->sell_c, A->d_slice_ptr, A->d_col, A->d_val, A->d_row_of_sorted, A->d_sell_len, x, y, (int) A->m,
 					(int) A->sell_slices, cfg, st, &grid);
 			break;
 		case SPMV_MI355X_COO:
@@ -505,7 +505,7 @@ spmm_enqueue(spmv_mi355x_matrix * A, int k, const void * X, long ldx, void * Y, 
 		cfg.beta = beta ? 1 : 0;
 		long grid = 0;
 		const int rc = launch_sell_delta_spmm(A->f32, A->val_f32, A->sell_split, A->sell_v7_slices > 0, A->d_sell_desc, A->d_sell_idx, A->d_val, A->d_row_of_sorted,
-				k, X, ldx, Y, ldy, (int) A->m, (int) A->sell_slices, cfg, st, &grid);
+				A->d_sell_len, k, X, ldx, Y, ldy, (int) A->m, (int) A->sell_slices, cfg, st, &grid);
 		A->last_grid = grid;
 		return rc;
 	}

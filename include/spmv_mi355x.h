@@ -969,8 +969,9 @@ int  spmv_mi355x_spgemm_info(const spmv_mi355x_spgemm * P, spmv_mi355x_spgemm_st
  *   - NOT CHECKABLE: that A is symmetric and positive definite. An indefinite A shows, if at all, as a coarse diagonal that is not
  *     positive, as coarse_kind = 2, or as stop 4 of the solver.
  *   - NOT BUILT: update_values for a hierarchy that re-aggregates (what is built keeps the aggregates and redoes the numeric
- *     passes: "new values for a hierarchy" below), W- and K-cycles, filtered prolongator smoothing, near-null-space vectors other than the constant, gmres /
- *     minres / multi-RHS wiring, the row-partitioned form, folding the small levels into one launch. The setup routes patterns
+ *     passes: "new values for a hierarchy" below), W- and K-cycles, more than one near-null vector (block coarse unknowns,
+ *     elasticity), filtering with a threshold of its own, gmres / minres / multi-RHS wiring, the row-partitioned form, folding the
+ *     small levels into one launch. The setup routes patterns
  *     through the host (spgemm_create and create take host arrays); the split in amg_info shows what that costs.
  * spmv_mi355x_pcg_amg is spmv_mi355x_pcg_tri with z = M^-1 r = amg_apply_device_async: the same recurrences, kernels, stop codes,
  * history, spmv_mi355x_pcg_tri_info and freeze (the SpMVs and vector kernels of a cycle write only the hierarchy's own vectors and
@@ -979,7 +980,7 @@ int  spmv_mi355x_spgemm_info(const spmv_mi355x_spgemm * P, spmv_mi355x_spgemm_st
  * precision or device differing from A's, in that order. */
 #define SPMV_MI355X_AMG_MAX_LEVELS 16
 enum { SPMV_MI355X_AMG_COARSE_DENSE = 0, SPMV_MI355X_AMG_COARSE_SWEEPS = 1, SPMV_MI355X_AMG_COARSE_SWEEPS_AFTER_PIVOT = 2 };
-enum { SPMV_MI355X_AMG_A = 0, SPMV_MI355X_AMG_P = 1 };
+enum { SPMV_MI355X_AMG_A = 0, SPMV_MI355X_AMG_P = 1, SPMV_MI355X_AMG_AF = 2 };
 typedef struct spmv_mi355x_amg spmv_mi355x_amg;   /* opaque */
 typedef struct {
 	int    struct_size;    /* sizeof(spmv_mi355x_amg_opts) */
@@ -1056,7 +1057,7 @@ int  spmv_mi355x_pcg_amg(spmv_mi355x_matrix * A, const void * b_host, void * x_o
  *     seconds, and of the last update its seconds, split into the SpGEMM numeric passes and the handles' update_values_device
  *     (the rest: steps 1 and 5, the weights, the gather, the factor and the host's reads).
  *   - NOT BUILT: re-aggregating when the strength pattern drifts (the caller decides and calls amg_create), update_values for fsai
- *     and trsv handles, an asynchronous update, the row-partitioned form, filtered smoothing, W- and K-cycles. */
+ *     and trsv handles, an asynchronous update, the row-partitioned form, W- and K-cycles. */
 typedef struct {
 	unsigned struct_size;   /* in: sizeof of the caller's struct; out: bytes written */
 	int    prepared, failed;
@@ -1069,6 +1070,53 @@ int  spmv_mi355x_amg_update_values(spmv_mi355x_amg * M, const double * values_fp
 int  spmv_mi355x_amg_update_values_device(spmv_mi355x_amg * M, const double * values_fp64_dev, void * hip_stream);
 int  spmv_mi355x_amg_update_values_state(const spmv_mi355x_amg * M);
 int  spmv_mi355x_amg_update_info(const spmv_mi355x_amg * M, spmv_mi355x_amg_update_stats * info /* struct_size first */);
+
+/* ---- AMG: a caller's near-null vector and filtered prolongator smoothing -------------------------------------------------------- */
+/* spmv_mi355x_amg_create_with is amg_create with two options for step 5, the prolongator. prolongator_opts NULL, or
+ * {filtered = 0, near_null = NULL}, gives the hierarchy of amg_create bit for bit, with the same launches. Steps 1 to 4 and 6, the
+ * stopping rules, the cycle and its weights w = omega / d of step 1 are untouched; the Galerkin product stays R (A_l P) with the
+ * unfiltered A_l. The arithmetic is fp64, every product and sum rounded on its own (tests/amg_prolongator_reference.c):
+ *   5a. filter (filtered = 1; otherwise A_F = A_l, dF = d, omega_p = omega). Row i keeps, in stored order, the first stored a_ii and
+ *       every j in S(i) of step 2; lump = +0.0, then lump = lump + a_ij over every other entry in stored order; dF_i = d_i + lump.
+ *       A dF_i that is not finite or not > 0 sends the row back to ALL its entries and dF_i = d_i (counted in unfiltered_rows).
+ *       A_F has the kept entries in A's stored order with dF_i at the diagonal's position;
+ *       rho_p = max_i (sum_j |aF_ij|, stored order) / dF_i;  omega_p = 4 / (3 rho_p).
+ *   5b. tentative prolongator (near_null given; otherwise t_i = 1.0 and nothing is carried down). With b the level's vector
+ *       (b_0 = near_null), for aggregate a over its members in ascending i: s = +0.0; s = s + b_i * b_i; nrm_a = sqrt(s);
+ *       t_i = b_i / nrm_agg(i), an IEEE division; b_{l+1}[a] = nrm_a. T has the pattern of step 5 and the values t.
+ *   5c. AT = A_F T by an SpGEMM plan; P_ij = (agg(i) == j ? t_i : 0.0) - (omega_p / dF_i) * AT_ij on AT's pattern.
+ *   - everything of "AMG" above works on such a handle; amg_level_csr takes which = SPMV_MI355X_AMG_AF, the filtered operator of a
+ *     coarsened level (refused where filtered = 0 and on a level without a prolongator; its entry count is nnz_filtered).
+ *   - amg_prolongator_info: struct_size is set by the caller. filtered, has_near_null, and per coarsened level nnz_filtered,
+ *     unfiltered_rows, omega_p, rho_p (with filtered = 0: nnz, 0, omega, rho; 0 on a level without a prolongator).
+ *   - amg_near_null: b_l, rows[level] doubles; nothing is written where no near-null vector was given.
+ *   - rc 1 with a last_error that starts with "amg_create_with:", in amg_create's order. Among the scalars, after the amg_opts ones:
+ *     prolongator_opts->struct_size not set, then filtered outside 0..1. After item 5: every near_null[i] must be finite and not 0
+ *     (the message names the first row). Under item 6: a rho_p that is not a positive finite number, and an aggregate whose norm is
+ *     not a positive finite number (b * b underflowed to 0 or overflowed; the message names the level and the aggregate).
+ *   - new values (amg_update_values*): frozen in addition are the kept pattern of every A_F, fall-back rows included, its entry map
+ *     into A_l, and t and b_l of every level (they depend on near_null and the aggregates only). Recomputed: lump, dF, rho_p,
+ *     omega_p, A_F's values, P, R, A_{l+1}. A lumped diagonal that is not finite or not > 0 on a row that was filtered at create is a
+ *     bad diagonal of that level: on level 0 it is found before anything is written, below it gives state 3. The updated hierarchy
+ *     equals amg_create_with on the new values bit for bit whenever that would find the same aggregates AND the same kept patterns;
+ *     otherwise it equals the update loops of tests/amg_prolongator_reference.c. */
+typedef struct {
+	int            struct_size;  /* sizeof(spmv_mi355x_amg_prolongator_opts) */
+	int            filtered;     /* 0 (default) or 1 */
+	const double * near_null;    /* n fp64 values on the host, or NULL (default): the constant, un-normalised */
+} spmv_mi355x_amg_prolongator_opts;
+typedef struct {
+	unsigned struct_size;   /* in: sizeof of the caller's struct; out: bytes written */
+	int    filtered, has_near_null;
+	long   nnz_filtered[SPMV_MI355X_AMG_MAX_LEVELS], unfiltered_rows[SPMV_MI355X_AMG_MAX_LEVELS];
+	double omega_p[SPMV_MI355X_AMG_MAX_LEVELS], rho_p[SPMV_MI355X_AMG_MAX_LEVELS];
+} spmv_mi355x_amg_prolongator_stats;
+int  spmv_mi355x_amg_create_with(spmv_mi355x_amg ** out, int format, int precision, long n,
+		const int32_t * row_ptr, const int32_t * col_idx, const double * values_fp64,
+		const spmv_mi355x_amg_opts * amg_opts /* NULL = defaults */,
+		const spmv_mi355x_amg_prolongator_opts * prolongator_opts /* NULL = defaults */, const spmv_mi355x_opts * opts /* may be NULL */);
+int  spmv_mi355x_amg_prolongator_info(const spmv_mi355x_amg * M, spmv_mi355x_amg_prolongator_stats * info /* struct_size first */);
+int  spmv_mi355x_amg_near_null(const spmv_mi355x_amg * M, int level, double * out /* rows[level] */);
 
 /* Row-partitioned (multi-GPU) form of the same two solvers: one process per GPU owns the row block [row_offset,
  * row_offset + m_local) of A, b and x. The solver keeps every vector device-resident and local; the two things that cross

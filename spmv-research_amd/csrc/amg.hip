@@ -3,7 +3,8 @@
 // leave the device, R by the device transposition, downloads for the handles that spmv_mi355x_create builds from host arrays), the
 // dense factor of the last level, the cycle and the C ABI. New values for a hierarchy (amg_update_values*): prepare builds the three
 // plans of every coarsened level once more and keeps them with the aggregates, the entry map P -> R and the value arrays; an update
-// redoes steps 1, 5 and 6 and the factor on the device and refreshes every handle in place.
+// redoes steps 1, 5 and 6 and the factor on the device and refreshes every handle in place. amg_create_with (a caller's near-null
+// vector, filtered prolongator smoothing) replaces step 5 by amg_prolongator_with; with its defaults it is amg_create.
 
 #include <algorithm>
 #include <chrono>
@@ -170,6 +171,120 @@ struct AmgProduct {
 	}
 };
 
+// Steps 5a to 5c of level l for a hierarchy of amg_create_with: A_F (filtered), t and the next level's vector (near_null), AT = A_F T
+// in `at` and P's values in *d_p_out. a, d_d and d_agg are the level's on the device, d_ones n ones.
+static int
+amg_prolongator_with(spmv_mi355x_amg * M, int l, const AmgCsr & a, const double * d_d, const int * d_agg, double theta2,
+		const std::vector<int32_t> & t_rp, const double * d_ones, DeviceBuffers & buf, AmgProduct & at, std::vector<double> & nrm, double ** d_p_out)
+{
+	AmgLevel & L = M->lev[(size_t) l];
+	const long n = L.n, nc = L.aggregates;
+	auto t0 = std::chrono::steady_clock::now();
+	const int32_t * f_rp = L.rp.data(), * f_ci = L.ci.data();
+	const double * d_fva = a.va, * d_df = d_d;
+	L.nnz_f = L.nnz;
+	L.omega_p = L.omega;
+	L.rho_p = L.rho;
+	if (M->filtered)
+	{
+		int * d_kept, * d_fb, * d_frp, * d_fci, * d_map;
+		double * d_dfw, * d_fv, * d_part;
+		void * d_scan;
+		const size_t scan_bytes = amg_scan_bytes(n + 1);
+		ABI_TRY(buf.alloc(&d_kept, (size_t) (n + 1) * 4));
+		ABI_TRY(buf.alloc(&d_frp, (size_t) (n + 1) * 4));
+		ABI_TRY(buf.alloc(&d_fb, (size_t) n * 4));
+		ABI_TRY(buf.alloc(&d_dfw, (size_t) n * 8));
+		ABI_TRY(buf.alloc(&d_part, (size_t) AMG_MAX_GRID * 8));
+		ABI_TRY(buf.alloc(&d_scan, scan_bytes));
+		HIP_TRY(hipMemsetAsync(d_kept, 0, (size_t) (n + 1) * 4, nullptr));
+		ABI_TRY(launch_amg_filter_count(a, d_d, theta2, d_kept, d_fb, d_dfw, nullptr));
+		ABI_TRY(launch_amg_offsets(n + 1, d_kept, d_frp, d_scan, scan_bytes, nullptr));
+		L.f_rp.assign((size_t) n + 1, 0);
+		L.f_fb.assign((size_t) n, 0);
+		HIP_TRY(hipMemcpy(L.f_rp.data(), d_frp, (size_t) (n + 1) * 4, hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(L.f_fb.data(), d_fb, (size_t) n * 4, hipMemcpyDeviceToHost));
+		L.nnz_f = L.f_rp[(size_t) n];
+		if (L.nnz_f < n || L.nnz_f > L.nnz)
+		{
+			set_error("amg_create_with: internal: level %d: the filtered operator has %ld entries, A has %ld in %ld rows", l, L.nnz_f, L.nnz, n);
+			return 1;
+		}
+		L.unfiltered_rows = 0;
+		for (long i = 0; i < n; i++)
+			L.unfiltered_rows += L.f_fb[(size_t) i] != 0;
+		ABI_TRY(buf.alloc(&d_fci, (size_t) L.nnz_f * 4));
+		ABI_TRY(buf.alloc(&d_fv, (size_t) L.nnz_f * 8));
+		ABI_TRY(buf.alloc(&d_map, (size_t) L.nnz_f * 4));
+		ABI_TRY(launch_amg_filter_fill(a, d_d, theta2, d_frp, d_fb, d_dfw, d_fci, d_fv, d_map, d_part, nullptr));
+		L.f_ci.assign((size_t) L.nnz_f, 0);
+		L.f_map.assign((size_t) L.nnz_f, 0);
+		L.f_va.assign((size_t) L.nnz_f, 0.0);
+		std::vector<double> part((size_t) amg_grid(n));
+		HIP_TRY(hipMemcpy(L.f_ci.data(), d_fci, (size_t) L.nnz_f * 4, hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(L.f_map.data(), d_map, (size_t) L.nnz_f * 4, hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(L.f_va.data(), d_fv, (size_t) L.nnz_f * 8, hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(part.data(), d_part, part.size() * 8, hipMemcpyDeviceToHost));
+		L.rho_p = *std::max_element(part.begin(), part.end());
+		if (!std::isfinite(L.rho_p) || !(L.rho_p > 0))
+		{
+			set_error("amg_create_with: level %d: max_i sum_j |aF_ij| / dF_i = %g is not a positive finite number", l, L.rho_p);
+			return 1;
+		}
+		L.omega_p = 4.0 / (3.0 * L.rho_p);
+		f_rp = L.f_rp.data();
+		f_ci = L.f_ci.data();
+		d_fva = d_fv;
+		d_df = d_dfw;
+	}
+	M->coarsen_seconds += amg_since(t0);
+	t0 = std::chrono::steady_clock::now();
+	ABI_TRY(spmv_mi355x_spgemm_create(&at.plan, M->device, n, n, nc, f_rp, f_ci, t_rp.data(), L.agg.data()));
+	M->spgemm_seconds += amg_since(t0);
+	const double * d_t = d_ones;
+	if (M->has_nn)
+	{
+		// the members of every aggregate in ascending order, with their b: the transposition of T's pattern
+		t0 = std::chrono::steady_clock::now();
+		double * d_b, * d_nrm, * d_tw, * d_mb = nullptr;
+		int * d_mrp = nullptr, * d_mci = nullptr;
+		ABI_TRY(buf.alloc(&d_b, (size_t) n * 8));
+		ABI_TRY(buf.alloc(&d_nrm, (size_t) nc * 8));
+		ABI_TRY(buf.alloc(&d_tw, (size_t) n * 8));
+		HIP_TRY(hipMemcpy(d_b, L.nn.data(), (size_t) n * 8, hipMemcpyHostToDevice));
+		ABI_TRY(transpose_csr_device(n, nc, n, at.plan->d_b_rp, at.plan->d_b_ci, d_b, &d_mrp, &d_mci, &d_mb));
+		for (void * p : {(void *) d_mrp, (void *) d_mci, (void *) d_mb})
+			buf.ptrs.push_back(p);
+		ABI_TRY(launch_amg_agg_norm(nc, d_mrp, d_mb, d_nrm, nullptr));
+		ABI_TRY(launch_amg_tentative(n, d_b, d_agg, d_nrm, d_tw, nullptr));
+		nrm.assign((size_t) nc, 0.0);
+		L.tv.assign((size_t) n, 0.0);
+		HIP_TRY(hipMemcpy(nrm.data(), d_nrm, (size_t) nc * 8, hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(L.tv.data(), d_tw, (size_t) n * 8, hipMemcpyDeviceToHost));
+		for (long g = 0; g < nc; g++)
+			if (!std::isfinite(nrm[(size_t) g]) || !(nrm[(size_t) g] > 0))
+			{
+				set_error("amg_create_with: level %d: the norm of the near-null vector over aggregate %ld is %g: it must be a positive finite "
+						"number (b * b underflowed or overflowed)", l, g, nrm[(size_t) g]);
+				return 1;
+			}
+		d_t = d_tw;
+		M->coarsen_seconds += amg_since(t0);
+	}
+	t0 = std::chrono::steady_clock::now();
+	double * d_at;
+	ABI_TRY(buf.alloc(&d_at, (size_t) std::max<long>(at.plan->nnz_c, 1) * 8));
+	ABI_TRY(spmv_mi355x_spgemm_multiply_device_async(at.plan, d_fva, d_t, d_at, nullptr));
+	HIP_TRY(hipStreamSynchronize(nullptr));
+	M->spgemm_seconds += amg_since(t0);
+	t0 = std::chrono::steady_clock::now();
+	ABI_TRY(buf.alloc(d_p_out, (size_t) std::max<long>(at.plan->nnz_c, 1) * 8));
+	ABI_TRY(launch_amg_prolong_t(n, at.plan->d_c_rp, at.plan->d_c_ci, d_at, d_agg, d_t, d_df, L.omega_p, *d_p_out, nullptr));
+	HIP_TRY(hipStreamSynchronize(nullptr));
+	M->coarsen_seconds += amg_since(t0);
+	return 0;
+}
+
 // Level l of M: steps 1 to 4, and unless the level turns out to be the last, steps 5 and 6, the handles of P and R and the CSR of
 // level l + 1. *last_out says which.
 static int
@@ -313,14 +428,23 @@ amg_build_level(spmv_mi355x_amg * M, int l, const spmv_mi355x_opts & o, bool * l
 		HIP_TRY(hipMemcpy(d_ones, ones.data(), (size_t) n * 8, hipMemcpyHostToDevice));
 	}
 	AmgProduct at;
-	ABI_TRY(at.run(M->device, n, n, nc, L.rp.data(), L.ci.data(), d_va, t_rp.data(), L.agg.data(), d_ones, buf, &d_at));
-	M->spgemm_seconds += amg_since(t0);
-	t0 = std::chrono::steady_clock::now();
+	std::vector<double> nrm;                              // b_{l+1} of a near-null vector
+	if (!M->filtered && !M->has_nn)
+	{
+		ABI_TRY(at.run(M->device, n, n, nc, L.rp.data(), L.ci.data(), d_va, t_rp.data(), L.agg.data(), d_ones, buf, &d_at));
+		M->spgemm_seconds += amg_since(t0);
+		t0 = std::chrono::steady_clock::now();
+		ABI_TRY(buf.alloc(&d_p, (size_t) at.plan->nnz_c * 8));
+		ABI_TRY(launch_amg_prolong(n, at.plan->d_c_rp, at.plan->d_c_ci, d_at, d_agg2, d_d, L.omega, d_p, nullptr));
+		HIP_TRY(hipStreamSynchronize(nullptr));
+		M->coarsen_seconds += amg_since(t0);
+		L.nnz_f = nnz;
+		L.omega_p = L.omega;
+		L.rho_p = L.rho;
+	}
+	else
+		ABI_TRY(amg_prolongator_with(M, l, a, d_d, d_agg2, theta2, t_rp, d_ones, buf, at, nrm, &d_p));
 	const long nnz_p = at.plan->nnz_c;
-	ABI_TRY(buf.alloc(&d_p, (size_t) nnz_p * 8));
-	ABI_TRY(launch_amg_prolong(n, at.plan->d_c_rp, at.plan->d_c_ci, d_at, d_agg2, d_d, L.omega, d_p, nullptr));
-	HIP_TRY(hipStreamSynchronize(nullptr));
-	M->coarsen_seconds += amg_since(t0);
 
 	// 6. R = P^t on the device
 	t0 = std::chrono::steady_clock::now();
@@ -357,6 +481,7 @@ amg_build_level(spmv_mi355x_amg * M, int l, const spmv_mi355x_opts & o, bool * l
 	M->lev.emplace_back();                            // reserved in amg_create: L stays valid
 	AmgLevel & C = M->lev.back();
 	C.n = nc;
+	C.nn = nrm;
 	C.nnz = ac.plan->nnz_c;
 	ABI_TRY(ac.pattern(C.rp, C.ci));
 	C.va.assign((size_t) std::max<long>(C.nnz, 1), 0.0);
@@ -509,9 +634,20 @@ amg_prepare_level(spmv_mi355x_amg * M, AmgUpdate * u, int l)
 	std::vector<int32_t> t_rp((size_t) n + 1);
 	for (long i = 0; i <= n; i++)
 		t_rp[(size_t) i] = (int32_t) i;
-	ABI_TRY(amg_plan(u, &U.at, M->device, n, n, nc, L.rp.data(), L.ci.data(), t_rp.data(), L.agg.data()));
-	U.d_rp = U.at->d_a_rp;
+	ABI_TRY(amg_plan(u, &U.at, M->device, n, n, nc, M->filtered ? L.f_rp.data() : L.rp.data(), M->filtered ? L.f_ci.data() : L.ci.data(),
+			t_rp.data(), L.agg.data()));
+	U.d_rp = U.at->d_a_rp;                                // filtered: A_F's pattern; A_l's own comes with the plan of A P below
 	U.d_ci = U.at->d_a_ci;
+	if (M->filtered)
+	{
+		U.d_f_rp = U.at->d_a_rp;
+		ABI_TRY(amg_keep(u, &U.d_map, (size_t) L.nnz_f, (const int *) L.f_map.data()));
+		ABI_TRY(amg_keep(u, &U.d_fb, (size_t) n, (const int *) L.f_fb.data()));
+		ABI_TRY(amg_keep(u, &U.d_fva, (size_t) L.nnz_f));
+		ABI_TRY(amg_keep(u, &U.d_df, (size_t) n));
+	}
+	if (M->has_nn)
+		ABI_TRY(amg_keep(u, &U.d_t, (size_t) n, L.tv.data()));
 	if (U.at->nnz_c != nnz_p || U.at->c_rp != L.p_rp)
 	{
 		set_error("amg_update_values_prepare: internal: level %d: the pattern of A T (%ld entries) is not that of P (%ld)", l, U.at->nnz_c, nnz_p);
@@ -555,6 +691,11 @@ amg_prepare_level(spmv_mi355x_amg * M, AmgUpdate * u, int l)
 	}
 	// A P and R (A P): the second must come back with the pattern of level l + 1
 	ABI_TRY(amg_plan(u, &U.ap, M->device, n, n, nc, L.rp.data(), L.ci.data(), L.p_rp.data(), L.p_ci.data()));
+	if (M->filtered)
+	{
+		U.d_rp = U.ap->d_a_rp;
+		U.d_ci = U.ap->d_a_ci;
+	}
 	std::vector<int32_t> ap_rp((size_t) n + 1), ap_ci((size_t) std::max<long>(U.ap->nnz_c, 1));
 	ABI_TRY(spmv_mi355x_spgemm_pattern(U.ap, ap_rp.data(), ap_ci.data()));
 	ABI_TRY(amg_keep(u, &U.d_ap, (size_t) U.ap->nnz_c));
@@ -589,6 +730,8 @@ amg_refresh_host(spmv_mi355x_amg * M)
 			HIP_TRY(hipMemcpy(L.va.data(), U.d_va, (size_t) L.nnz * 8, hipMemcpyDeviceToHost));
 		if (L.P && L.nnz_p > 0)
 			HIP_TRY(hipMemcpy(L.p_va.data(), U.d_p, (size_t) L.nnz_p * 8, hipMemcpyDeviceToHost));
+		if (L.P && M->filtered && L.nnz_f > 0)
+			HIP_TRY(hipMemcpy(L.f_va.data(), U.d_fva, (size_t) L.nnz_f * 8, hipMemcpyDeviceToHost));
 	}
 	u->host_stale = false;
 	return 0;
@@ -621,6 +764,43 @@ amg_first_bad_row(spmv_mi355x_amg * M, int l, long * row_out, double * d_out)
 	*row_out = -1;
 	for (long i = 0; i < n && *row_out < 0; i++)
 		if (!std::isfinite(d[(size_t) i]) || !(d[(size_t) i] > 0))
+		{
+			*row_out = i;
+			*d_out = d[(size_t) i];
+		}
+	return 0;
+}
+
+// step 5a of the coarsened level l on `va` over the frozen kept pattern: dF into the level's array, A_F's values into f_va (NULL: the
+// check alone); *bad_out = the rows filtered at create whose lumped diagonal is bad, *rho_out = the largest partial
+static int
+amg_update_filter(spmv_mi355x_amg * M, int l, const double * va, double * f_va, hipStream_t st, int * bad_out, double * rho_out)
+{
+	AmgUpdate * u = M->upd;
+	const AmgUpdateLevel & U = u->lev[(size_t) l];
+	const long n = M->lev[(size_t) l].n;
+	const AmgCsr a = {U.d_rp, U.d_ci, va, n};
+	int * d_bad = u->d_count + SPMV_MI355X_AMG_MAX_LEVELS + 1 + l;
+	HIP_TRY(hipMemsetAsync(d_bad, 0, 4, st));
+	ABI_TRY(launch_amg_filter_values(a, U.d_d, U.d_f_rp, U.d_map, U.d_fb, U.d_df, f_va, u->d_part, d_bad, st));
+	double part[AMG_MAX_GRID];
+	HIP_TRY(hipMemcpyAsync(bad_out, d_bad, 4, hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipMemcpyAsync(part, u->d_part, (size_t) amg_grid(n) * 8, hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipStreamSynchronize(st));
+	*rho_out = *std::max_element(part, part + amg_grid(n));
+	return 0;
+}
+
+// the first row of level l that was filtered at create and whose lumped diagonal is not positive and finite (an error path)
+static int
+amg_first_bad_lump(spmv_mi355x_amg * M, int l, long * row_out, double * d_out)
+{
+	const AmgLevel & L = M->lev[(size_t) l];
+	std::vector<double> d((size_t) L.n);
+	HIP_TRY(hipMemcpy(d.data(), M->upd->lev[(size_t) l].d_df, (size_t) L.n * 8, hipMemcpyDeviceToHost));
+	*row_out = -1;
+	for (long i = 0; i < L.n && *row_out < 0; i++)
+		if (!L.f_fb[(size_t) i] && (!std::isfinite(d[(size_t) i]) || !(d[(size_t) i] > 0)))
 		{
 			*row_out = i;
 			*d_out = d[(size_t) i];
@@ -668,11 +848,38 @@ amg_update_levels(spmv_mi355x_amg * M, double rho0, hipStream_t st)
 		if (!L.P)
 			continue;
 		AmgUpdateLevel & C = u->lev[(size_t) l + 1];
+		const bool with = M->filtered || M->has_nn;
+		L.omega_p = L.omega;
+		L.rho_p = L.rho;
+		if (M->filtered)
+		{
+			int bad = 0;
+			ABI_TRY(amg_update_filter(M, l, U.d_va, U.d_fva, st, &bad, &L.rho_p));
+			if (bad > 0)
+			{
+				long row = -1;
+				double d = 0;
+				ABI_TRY(amg_first_bad_lump(M, l, &row, &d));
+				set_error("amg_update_values: the lumped diagonal of row %ld of level %d is %g: the row was filtered at create and cannot "
+						"fall back now", row, l, d);
+				return 1;
+			}
+			if (!std::isfinite(L.rho_p) || !(L.rho_p > 0))
+			{
+				set_error("amg_update_values: level %d: max_i sum_j |aF_ij| / dF_i = %g is not a positive finite number", l, L.rho_p);
+				return 1;
+			}
+			L.omega_p = 4.0 / (3.0 * L.rho_p);
+		}
 		t0 = std::chrono::steady_clock::now();
-		ABI_TRY(spmv_mi355x_spgemm_multiply_device_async(U.at, U.d_va, U.d_ones, U.d_at, st));
+		ABI_TRY(spmv_mi355x_spgemm_multiply_device_async(U.at, M->filtered ? U.d_fva : U.d_va, M->has_nn ? U.d_t : U.d_ones, U.d_at, st));
 		HIP_TRY(hipStreamSynchronize(st));
 		u->spgemm_seconds += amg_since(t0);
-		ABI_TRY(launch_amg_prolong(n, U.at->d_c_rp, U.at->d_c_ci, U.d_at, U.d_agg, U.d_d, L.omega, U.d_p, st));
+		if (with)
+			ABI_TRY(launch_amg_prolong_t(n, U.at->d_c_rp, U.at->d_c_ci, U.d_at, U.d_agg, M->has_nn ? U.d_t : U.d_ones,
+					M->filtered ? U.d_df : U.d_d, L.omega_p, U.d_p, st));
+		else
+			ABI_TRY(launch_amg_prolong(n, U.at->d_c_rp, U.at->d_c_ci, U.d_at, U.d_agg, U.d_d, L.omega, U.d_p, st));
 		ABI_TRY(transpose_gather_values(U.d_src, U.d_p, L.nnz_p, U.d_r, st));
 		HIP_TRY(hipStreamSynchronize(st));
 		t0 = std::chrono::steady_clock::now();
@@ -732,11 +939,14 @@ using namespace spmv;
 
 extern "C" {
 
-int
-spmv_mi355x_amg_create(spmv_mi355x_amg ** out, int format, int precision, long n, const int32_t * row_ptr, const int32_t * col_idx,
-		const double * values, const spmv_mi355x_amg_opts * amg_opts, const spmv_mi355x_opts * opts_in)
+static const AmgLevel * amg_level_of(const char * what, const spmv_mi355x_amg * M, int level);
+
+// amg_create (popts_in == NULL, what = "amg_create") and amg_create_with
+static int
+amg_create_impl(const char * what, spmv_mi355x_amg ** out, int format, int precision, long n, const int32_t * row_ptr, const int32_t * col_idx,
+		const double * values, const spmv_mi355x_amg_opts * amg_opts, const spmv_mi355x_amg_prolongator_opts * popts_in,
+		const spmv_mi355x_opts * opts_in)
 {
-	const char * what = "amg_create";
 	const auto t_start = std::chrono::steady_clock::now();
 	if (out)
 		*out = nullptr;
@@ -769,6 +979,22 @@ spmv_mi355x_amg_create(spmv_mi355x_amg ** out, int format, int precision, long n
 	}
 	if (!amg_scalars_ok(what, format, precision, n, o, a))
 		return 1;
+	spmv_mi355x_amg_prolongator_opts po = {(int) sizeof(spmv_mi355x_amg_prolongator_opts), 0, nullptr};
+	if (popts_in)
+	{
+		const size_t sz = std::min<size_t>(sizeof(po), (size_t) std::max(popts_in->struct_size, 0));
+		if (sz < 8)
+		{
+			set_error("%s: prolongator_opts->struct_size not set", what);
+			return 1;
+		}
+		memcpy(&po, popts_in, sz);
+		if (po.filtered < 0 || po.filtered > 1)
+		{
+			set_error("%s: prolongator_opts->filtered = %d out of range 0..1", what, po.filtered);
+			return 1;
+		}
+	}
 	// 2. NULL pointers
 	const bool entries = row_ptr && row_ptr[n] > 0;
 	if (!out || !row_ptr || (entries && (!col_idx || !values)))
@@ -780,6 +1006,13 @@ spmv_mi355x_amg_create(spmv_mi355x_amg ** out, int format, int precision, long n
 	// 3. to 5. the pattern, no column twice, the diagonal
 	if (amg_check_matrix(what, n, row_ptr, col_idx, values))
 		return 1;
+	// the near-null vector: finite and not 0
+	for (long i = 0; po.near_null && i < n; i++)
+		if (!std::isfinite(po.near_null[i]) || po.near_null[i] == 0)
+		{
+			set_error("%s: near_null[%ld] = %g: every entry must be finite and not 0", what, i, po.near_null[i]);
+			return 1;
+		}
 	// 6. the device
 	int ndev = 0;
 	spmv_mi355x_device_count(&ndev);
@@ -806,6 +1039,8 @@ spmv_mi355x_amg_create(spmv_mi355x_amg ** out, int format, int precision, long n
 	M->format = format;
 	M->n = n;
 	M->opts = a;
+	M->filtered = po.filtered != 0;
+	M->has_nn = po.near_null != nullptr;
 	if (n > 0)
 	{
 		M->lev.reserve(SPMV_MI355X_AMG_MAX_LEVELS + 1);
@@ -816,17 +1051,80 @@ spmv_mi355x_amg_create(spmv_mi355x_amg ** out, int format, int precision, long n
 		L.rp.assign(row_ptr, row_ptr + n + 1);
 		L.ci.assign(col_idx, col_idx + L.nnz);
 		L.va.assign(values, values + L.nnz);
+		if (po.near_null)
+			L.nn.assign(po.near_null, po.near_null + n);
 		if (amg_build(M, o))
 		{
 			std::string msg = spmv_mi355x_last_error();
 			amg_free(M);
-			if (msg.rfind("amg_create:", 0) != 0)
-				set_error("%s: %s", what, msg.c_str());
+			for (const char * own : {"amg_create: ", "amg_create_with: "})
+				if (msg.rfind(own, 0) == 0)
+					msg = msg.substr(strlen(own));
+			set_error("%s: %s", what, msg.c_str());
 			return 1;
 		}
 	}
 	M->setup_seconds = amg_since(t_start);
 	*out = M;
+	return 0;
+}
+
+int
+spmv_mi355x_amg_create(spmv_mi355x_amg ** out, int format, int precision, long n, const int32_t * row_ptr, const int32_t * col_idx,
+		const double * values, const spmv_mi355x_amg_opts * amg_opts, const spmv_mi355x_opts * opts_in)
+{
+	return amg_create_impl("amg_create", out, format, precision, n, row_ptr, col_idx, values, amg_opts, nullptr, opts_in);
+}
+
+int
+spmv_mi355x_amg_create_with(spmv_mi355x_amg ** out, int format, int precision, long n, const int32_t * row_ptr, const int32_t * col_idx,
+		const double * values, const spmv_mi355x_amg_opts * amg_opts, const spmv_mi355x_amg_prolongator_opts * prolongator_opts,
+		const spmv_mi355x_opts * opts_in)
+{
+	return amg_create_impl("amg_create_with", out, format, precision, n, row_ptr, col_idx, values, amg_opts, prolongator_opts, opts_in);
+}
+
+int
+spmv_mi355x_amg_prolongator_info(const spmv_mi355x_amg * M, spmv_mi355x_amg_prolongator_stats * info)
+{
+	if (!M || !info)
+	{
+		set_error("amg_prolongator_info: NULL %s", !M ? "handle" : "info");
+		return 1;
+	}
+	if (!info_size_ok("amg_prolongator_info", info))
+		return 1;
+	spmv_mi355x_amg_prolongator_stats s;
+	memset(&s, 0, sizeof(s));
+	s.filtered = M->filtered;
+	s.has_near_null = M->has_nn;
+	for (int l = 0; l < M->levels; l++)
+	{
+		const AmgLevel & L = M->lev[(size_t) l];
+		if (!L.P)
+			continue;
+		s.nnz_filtered[l] = L.nnz_f;
+		s.unfiltered_rows[l] = L.unfiltered_rows;
+		s.omega_p[l] = L.omega_p;
+		s.rho_p[l] = L.rho_p;
+	}
+	put_info(info, info->struct_size, s);
+	return 0;
+}
+
+int
+spmv_mi355x_amg_near_null(const spmv_mi355x_amg * M, int level, double * out)
+{
+	const AmgLevel * L = amg_level_of("amg_near_null", M, level);
+	if (!L)
+		return 1;
+	if (!L->nn.empty() && !out)
+	{
+		set_error("amg_near_null: NULL out");
+		return 1;
+	}
+	if (!L->nn.empty())
+		memcpy(out, L->nn.data(), L->nn.size() * sizeof(double));
 	return 0;
 }
 
@@ -1026,10 +1324,32 @@ spmv_mi355x_amg_level_csr(const spmv_mi355x_amg * M, int level, int which, int32
 	const AmgLevel * L = amg_level_of("amg_level_csr", M, level);
 	if (!L)
 		return 1;
-	if (which != SPMV_MI355X_AMG_A && which != SPMV_MI355X_AMG_P)
+	if (which != SPMV_MI355X_AMG_A && which != SPMV_MI355X_AMG_P && which != SPMV_MI355X_AMG_AF)
 	{
-		set_error("amg_level_csr: which = %d: SPMV_MI355X_AMG_A or SPMV_MI355X_AMG_P", which);
+		set_error("amg_level_csr: which = %d: SPMV_MI355X_AMG_A, SPMV_MI355X_AMG_P or SPMV_MI355X_AMG_AF", which);
 		return 1;
+	}
+	if (which == SPMV_MI355X_AMG_AF)
+	{
+		if (!M->filtered)
+		{
+			set_error("amg_level_csr: SPMV_MI355X_AMG_AF: the hierarchy was built with filtered = 0");
+			return 1;
+		}
+		if (!L->P)
+		{
+			set_error("amg_level_csr: level %d is the last: it has no filtered operator", level);
+			return 1;
+		}
+		if (values_out && L->nnz_f > 0 && amg_refresh_host(const_cast<spmv_mi355x_amg *>(M)))
+			return 1;
+		if (row_ptr_out)
+			memcpy(row_ptr_out, L->f_rp.data(), (size_t) (L->n + 1) * sizeof(int32_t));
+		if (col_idx_out && L->nnz_f > 0)
+			memcpy(col_idx_out, L->f_ci.data(), (size_t) L->nnz_f * sizeof(int32_t));
+		if (values_out && L->nnz_f > 0)
+			memcpy(values_out, L->f_va.data(), (size_t) L->nnz_f * sizeof(double));
+		return 0;
 	}
 	const bool p = which == SPMV_MI355X_AMG_P;
 	if (p && !L->P)
@@ -1080,7 +1400,7 @@ spmv_mi355x_amg_update_values_prepare(spmv_mi355x_amg * M)
 	HIP_TRY(hipSetDevice(M->device));
 	AmgUpdate * u = new AmgUpdate();
 	u->lev.resize((size_t) M->levels);
-	int rc = amg_keep(u, &u->d_part, (size_t) AMG_MAX_GRID) || amg_keep(u, &u->d_count, (size_t) SPMV_MI355X_AMG_MAX_LEVELS + 1)
+	int rc = amg_keep(u, &u->d_part, (size_t) AMG_MAX_GRID) || amg_keep(u, &u->d_count, (size_t) 2 * (SPMV_MI355X_AMG_MAX_LEVELS + 1))
 			|| amg_keep(u, &u->d_factor, (size_t) AMG_DENSE_MAX * (AMG_DENSE_MAX + 1) / 2);
 	for (int l = 0; l < M->levels && !rc; l++)
 		rc = amg_prepare_level(M, u, l);
@@ -1141,6 +1461,20 @@ spmv_mi355x_amg_update_values_device(spmv_mi355x_amg * M, const double * values_
 	{
 		set_error("%s: level 0: max_i sum_j |a_ij| / a_ii = %g is not a positive finite number (the hierarchy is unchanged)", what, rho);
 		return 1;
+	}
+	if (M->filtered && M->lev[0].P)
+	{
+		double rho_p = 0;
+		ABI_TRY(amg_update_filter(M, 0, values_dev, nullptr, st, &bad, &rho_p));
+		if (bad > 0)
+		{
+			long row = -1;
+			double d = 0;
+			ABI_TRY(amg_first_bad_lump(M, 0, &row, &d));
+			set_error("%s: the lumped diagonal of row %ld of level 0 is %g: the row was filtered at create and cannot fall back now (the "
+					"hierarchy is unchanged)", what, row, d);
+			return 1;
+		}
 	}
 	HIP_TRY(hipMemcpyAsync(u->lev[0].d_va, values_dev, (size_t) M->lev[0].nnz * 8, hipMemcpyDeviceToDevice, st));
 	u->spgemm_seconds = u->handle_seconds = 0;

@@ -22,7 +22,21 @@
 //     amg_diag_check_kernel        22    3 072 B       0
 //     amg_weights_kernel           16        0         0
 //     amg_dense_factor_kernel      46   66 056 B       0
-// (-Rpass-analysis=kernel-resource-usage, gfx950; profiles/r23_amg.txt and profiles/r24_amg_update.txt have the compiler's own table.)
+//     amg_filter_count_kernel      22        0         0
+//     amg_filter_fill_kernel       30    2 048 B       0
+//     amg_filter_values_kernel     21    3 072 B       0
+//     amg_agg_norm_kernel          14        0         0
+//     amg_tentative_kernel         20        0         0
+//     amg_prolong_t_kernel         24        0         0
+// (-Rpass-analysis=kernel-resource-usage, gfx950; profiles/r23_amg.txt, profiles/r24_amg_update.txt and
+// profiles/r25_amg_prolongator.txt have the compiler's own table.)
+// STEPS 5a TO 5c (amg_create_with; the header's "AMG: a caller's near-null vector and filtered prolongator smoothing"). Filtered: a
+// count pass (kept entries, the lump and the fall-back per row), hipcub's exclusive scan over n + 1 counts, a fill pass (A_F's columns,
+// values, the int32 map into A_l, the partials of rho_p). Near-null: the device transposition of T's pattern with b as its values
+// lists every aggregate's members in ascending order (its sort by column is stable); one lane per aggregate sums b * b sequentially,
+// one lane per row divides. amg_prolong_t_kernel reads t and dF. A handle built with the defaults runs none of them and launches what
+// amg_create launches. An update keeps A_F's pattern, the map, the fall-back rows and t, and runs amg_filter_values_kernel (lump, dF,
+// A_F's values, the partials, the count of bad lumped diagonals) before the plan of A_F T.
 // AN UPDATE OF THE VALUES (amg_update_values*) keeps, from prepare on, what AmgUpdate below lists: per coarsened level the three SpGEMM
 // plans (their device patterns serve step 1 and launch_amg_prolong too), agg, the entry map P -> R and the value arrays. An update is
 // per level amg_diag_check_kernel (the host reads one count and amg_grid(n) partials), amg_weights_kernel, the numeric passes of the
@@ -75,6 +89,23 @@ int launch_amg_agg_pass2(const AmgCsr & a, const double * d, double theta2, cons
 // step 5: p_va from the CSR of A T
 int launch_amg_prolong(long n, const int * at_rp, const int * at_ci, const double * at_va, const int * agg, const double * d, double omega,
 		double * p_va, hipStream_t st);
+// step 5a, count: kept[i] entries stay in row i of A_F, fb[i] = the row fell back to all its entries, df[i] = the lumped diagonal
+int launch_amg_filter_count(const AmgCsr & a, const double * d, double theta2, int * kept, int * fb, double * df, hipStream_t st);
+// out = the exclusive scan of in[0 .. count); scan_tmp / scan_bytes as hipcub wants them (amg_scan_bytes(count))
+int launch_amg_offsets(long count, const int * in, int * out, void * scan_tmp, size_t scan_bytes, hipStream_t st);
+// step 5a, fill: A_F's columns, values and entry map into A_l, and amg_grid(n) partials of (sum_j |aF_ij|) / dF_i
+int launch_amg_filter_fill(const AmgCsr & a, const double * d, double theta2, const int * f_rp, const int * fb, const double * df, int * f_ci,
+		double * f_va, int * map, double * part, hipStream_t st);
+// step 5a for an update on the frozen kept pattern: df, f_va (NULL: not written) and the partials; *bad += the rows filtered at create
+// whose lumped diagonal is not finite or not > 0 (zeroed by the caller)
+int launch_amg_filter_values(const AmgCsr & a, const double * d, const int * f_rp, const int * map, const int * fb, double * df, double * f_va,
+		double * part, int * bad, hipStream_t st);
+// step 5b: nrm[g] over the members of aggregate g (m_rp, m_b: the transposition of T's pattern with b as its values); t = b / nrm[agg]
+int launch_amg_agg_norm(long nc, const int * m_rp, const double * m_b, double * nrm, hipStream_t st);
+int launch_amg_tentative(long n, const double * b, const int * agg, const double * nrm, double * t, hipStream_t st);
+// step 5c: p_va from the CSR of A_F T, t and dF
+int launch_amg_prolong_t(long n, const int * at_rp, const int * at_ci, const double * at_va, const int * agg, const double * t, const double * df,
+		double omega_p, double * p_va, hipStream_t st);
 // the cycle: x = w o b;  x += w o (b - t);  t = b - t
 int launch_amg_first(bool f32, const void * w, const void * b, void * x, long n, hipStream_t st);
 int launch_amg_sweep(bool f32, const void * w, const void * b, const void * t, void * x, long n, hipStream_t st);
@@ -97,6 +128,11 @@ struct AmgUpdateLevel {
 	unsigned * d_src = nullptr;                           // entry e of R is entry d_src[e] of P
 	double * d_va = nullptr, * d_d = nullptr;             // A_l's values (level 0: a copy of the caller's), the diagonal
 	double * d_ones = nullptr, * d_at = nullptr, * d_p = nullptr, * d_r = nullptr, * d_ap = nullptr;
+	// a hierarchy of amg_create_with: A_F's row pointer, its entry map into A_l and the rows that fell back (filtered); A_F's values and
+	// the lumped diagonal; t of a near-null vector (else d_ones serves)
+	const int * d_f_rp = nullptr;
+	int * d_map = nullptr, * d_fb = nullptr;
+	double * d_fva = nullptr, * d_df = nullptr, * d_t = nullptr;
 };
 
 struct AmgUpdate {
@@ -116,6 +152,11 @@ struct AmgLevel {
 	double omega = 0, rho = 0;
 	std::vector<int32_t> rp, ci, p_rp, p_ci, agg;         // the host copies level_csr and aggregates return
 	std::vector<double> va, p_va;
+	// amg_create_with: A_F of a coarsened level (filtered), its map into A_l and the rows that fell back; b_l and t (near_null)
+	long nnz_f = 0, unfiltered_rows = 0;
+	double omega_p = 0, rho_p = 0;
+	std::vector<int32_t> f_rp, f_ci, f_map, f_fb;
+	std::vector<double> f_va, nn, tv;
 	spmv_mi355x_matrix * A = nullptr, * P = nullptr, * R = nullptr;
 	void * w = nullptr, * b = nullptr, * x = nullptr, * t = nullptr;   // n values of the handle's precision each; x is NULL on level 0
 };
@@ -128,6 +169,7 @@ struct spmv_mi355x_amg {
 	long n = 0;
 	spmv_mi355x_amg_opts opts = {};
 	int levels = 0, coarse_kind = 0, stalled = 0;
+	bool filtered = false, has_nn = false;                // spmv_mi355x_amg_prolongator_opts
 	std::vector<spmv::AmgLevel> lev;
 	double * d_factor = nullptr;                          // the packed Cholesky factor of a dense last level
 	void * d_in = nullptr, * d_out = nullptr;             // the vectors of the host-buffer apply, allocated at its first call

@@ -1,6 +1,7 @@
 // The kernels of the smoothed-aggregation AMG (include/spmv_mi355x.h "AMG", amg.hpp for the mapping): steps 1 to 5 of the setup, one
 // lane per row; the three vector kernels of the cycle; the dense coarsest solve; and what an update of the values adds (the checked
-// step 1, the weights, the dense factor). The arithmetic is the header's, as written: this file is compiled with contraction off,
+// step 1, the weights, the dense factor); and steps 5a to 5c of amg_create_with (the filter, the aggregate norms of a near-null
+// vector, the prolongator from both). The arithmetic is the header's, as written: this file is compiled with contraction off,
 // and every fma in it is spelled out.
 #include <hipcub/hipcub.hpp>
 
@@ -259,6 +260,204 @@ amg_prolong_kernel(long n, const int * __restrict__ at_rp, const int * __restric
 	}
 }
 
+// ---- steps 5a to 5c: the filtered operator, the tentative prolongator of a near-null vector, the prolongator from both ---------------
+
+// 5a, the count pass: kept[i] = the entries row i keeps (the first stored a_ii and S(i)), dF_i = d_i + lump with lump the sum of the
+// others in stored order from +0.0; a dF_i that is not finite or not > 0 sends the row back to all its entries and d_i (fb[i] = 1)
+__global__ __launch_bounds__(AMG_TB) void
+amg_filter_count_kernel(AmgCsr a, const double * __restrict__ d, double theta2, int * __restrict__ kept, int * __restrict__ fb,
+		double * __restrict__ df)
+{
+	AMG_ROWS(i, a.n)
+	{
+		const double di = d[i];
+		double lump = 0.0;
+		int keep = 0;
+		bool found = false;
+		for (int e = a.rp[i]; e < a.rp[i + 1]; e++)
+		{
+			const int j = a.ci[e];
+			const double v = a.va[e];
+			bool k;
+			if (j == i)
+			{
+				k = !found;
+				found = true;
+			}
+			else
+				k = amg_strong(v, di, d[j], theta2);
+			if (k)
+				keep++;
+			else
+				lump = lump + v;
+		}
+		const double dl = di + lump;
+		const bool back = !(isfinite(dl) && dl > 0);
+		kept[i] = back ? a.rp[i + 1] - a.rp[i] : keep;
+		fb[i] = back;
+		df[i] = back ? di : dl;
+	}
+}
+
+// 5a, the fill pass: A_F's columns and values in A's stored order with dF_i at the diagonal's position, the map of A_F's entries
+// into A's, and part[workgroup] = the workgroup's max of (sum_j |aF_ij|) / dF_i as amg_diag_kernel writes its own
+__global__ __launch_bounds__(AMG_TB) void
+amg_filter_fill_kernel(AmgCsr a, const double * __restrict__ d, double theta2, const int * __restrict__ f_rp, const int * __restrict__ fb,
+		const double * __restrict__ df, int * __restrict__ f_ci, double * __restrict__ f_va, int * __restrict__ map, double * __restrict__ part)
+{
+	__shared__ double sh[AMG_TB];
+	double worst = 0;
+	AMG_ROWS(i, a.n)
+	{
+		const double di = d[i], dfi = df[i];
+		const bool all = fb[i] != 0;
+		const int q1 = f_rp[i + 1];
+		double sum = 0;
+		int q = f_rp[i];
+		bool found = false;
+		for (int e = a.rp[i]; e < a.rp[i + 1]; e++)
+		{
+			const int j = a.ci[e];
+			double v = a.va[e];
+			bool k;
+			if (j == i)
+			{
+				k = !found;
+				if (k)
+					v = dfi;
+				found = true;
+			}
+			else
+				k = amg_strong(v, di, d[j], theta2);
+			if ((k || all) && q < q1)
+			{
+				f_ci[q] = j;
+				f_va[q] = v;
+				map[q] = e;
+				q++;
+				sum = sum + fabs(v);
+			}
+		}
+		worst = fmax(worst, sum / dfi);
+	}
+	sh[threadIdx.x] = worst;
+	__syncthreads();
+	for (int s = AMG_TB / 2; s > 0; s >>= 1)
+	{
+		if ((int) threadIdx.x < s)
+			sh[threadIdx.x] = fmax(sh[threadIdx.x], sh[threadIdx.x + s]);
+		__syncthreads();
+	}
+	if (threadIdx.x == 0)
+		part[blockIdx.x] = sh[0];
+}
+
+// 5a for an update, the kept pattern frozen: the entries of row i that the map does not name are lumped in stored order, dF_i and
+// A_F's values follow as above (f_va NULL: only dF and the count, the check of level 0), *bad += the rows filtered at create
+// (fb[i] == 0) whose dF_i is not finite or not > 0 (zeroed by the caller)
+__global__ __launch_bounds__(AMG_TB) void
+amg_filter_values_kernel(AmgCsr a, const double * __restrict__ d, const int * __restrict__ f_rp, const int * __restrict__ map,
+		const int * __restrict__ fb, double * __restrict__ df, double * __restrict__ f_va, double * __restrict__ part, int * __restrict__ bad)
+{
+	__shared__ double sh[AMG_TB];
+	__shared__ int shb[AMG_TB];
+	double worst = 0;
+	int wrong = 0;
+	AMG_ROWS(i, a.n)
+	{
+		const double di = d[i];
+		const int q1 = f_rp[i + 1];
+		double lump = 0.0;
+		int q = f_rp[i];
+		for (int e = a.rp[i]; e < a.rp[i + 1]; e++)
+		{
+			if (q < q1 && map[q] == e)
+				q++;
+			else
+				lump = lump + a.va[e];
+		}
+		const double dfi = fb[i] ? di : di + lump;
+		df[i] = dfi;
+		wrong += !(isfinite(dfi) && dfi > 0);
+		if (f_va)
+		{
+			double sum = 0;
+			bool found = false;
+			for (q = f_rp[i]; q < q1; q++)
+			{
+				const int e = map[q];
+				double v = a.va[e];
+				if (!found && a.ci[e] == i)
+				{
+					v = dfi;
+					found = true;
+				}
+				f_va[q] = v;
+				sum = sum + fabs(v);
+			}
+			worst = fmax(worst, sum / dfi);
+		}
+	}
+	sh[threadIdx.x] = worst;
+	shb[threadIdx.x] = wrong;
+	__syncthreads();
+	for (int s = AMG_TB / 2; s > 0; s >>= 1)
+	{
+		if ((int) threadIdx.x < s)
+		{
+			sh[threadIdx.x] = fmax(sh[threadIdx.x], sh[threadIdx.x + s]);
+			shb[threadIdx.x] += shb[threadIdx.x + s];
+		}
+		__syncthreads();
+	}
+	if (threadIdx.x == 0)
+	{
+		part[blockIdx.x] = sh[0];
+		if (shb[0] > 0)
+			atomicAdd(bad, shb[0]);                           // an integer count: its sum does not depend on the order
+	}
+}
+
+// 5b: one lane per aggregate over its members' b in ascending row order (the transposition of T's pattern carries them):
+// s = +0.0, s = s + b_i * b_i, nrm = sqrt(s)
+__global__ __launch_bounds__(AMG_TB) void
+amg_agg_norm_kernel(long nc, const int * __restrict__ m_rp, const double * __restrict__ m_b, double * __restrict__ nrm)
+{
+	AMG_ROWS(g, nc)
+	{
+		double s = 0.0;
+		for (int e = m_rp[g]; e < m_rp[g + 1]; e++)
+		{
+			const double b = m_b[e];
+			s = s + b * b;
+		}
+		nrm[g] = sqrt(s);
+	}
+}
+
+// 5b: t_i = b_i / nrm_agg(i), an IEEE division
+__global__ __launch_bounds__(AMG_TB) void
+amg_tentative_kernel(long n, const double * __restrict__ b, const int * __restrict__ agg, const double * __restrict__ nrm,
+		double * __restrict__ t)
+{
+	AMG_ROWS(i, n)
+		t[i] = b[i] / nrm[agg[i]];
+}
+
+// 5c: P_ij = (agg(i) == j ? t_i : 0) - (omega_p / dF_i) * (A_F T)_ij over the entries of row i of A_F T
+__global__ __launch_bounds__(AMG_TB) void
+amg_prolong_t_kernel(long n, const int * __restrict__ at_rp, const int * __restrict__ at_ci, const double * __restrict__ at_va,
+		const int * __restrict__ agg, const double * __restrict__ t, const double * __restrict__ df, double omega_p, double * __restrict__ p_va)
+{
+	AMG_ROWS(i, n)
+	{
+		const double scale = omega_p / df[i], ti = t[i];
+		const int g = agg[i];
+		for (int e = at_rp[i]; e < at_rp[i + 1]; e++)
+			p_va[e] = (at_ci[e] == g ? ti : 0.0) - scale * at_va[e];
+	}
+}
+
 // ---- the cycle -----------------------------------------------------------------------------------------------------------------------
 
 template <typename T>
@@ -466,6 +665,54 @@ launch_amg_prolong(long n, const int * at_rp, const int * at_ci, const double * 
 		double * p_va, hipStream_t st)
 {
 	AMG_LAUNCH(amg_prolong_kernel, n, st, n, at_rp, at_ci, at_va, agg, d, omega, p_va);
+}
+
+int
+launch_amg_filter_count(const AmgCsr & a, const double * d, double theta2, int * kept, int * fb, double * df, hipStream_t st)
+{
+	AMG_LAUNCH(amg_filter_count_kernel, a.n, st, a, d, theta2, kept, fb, df);
+}
+
+int
+launch_amg_offsets(long count, const int * in, int * out, void * scan_tmp, size_t scan_bytes, hipStream_t st)
+{
+	if (count <= 0)
+		return 0;
+	HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, in, out, (int) count, st));
+	return 0;
+}
+
+int
+launch_amg_filter_fill(const AmgCsr & a, const double * d, double theta2, const int * f_rp, const int * fb, const double * df, int * f_ci,
+		double * f_va, int * map, double * part, hipStream_t st)
+{
+	AMG_LAUNCH(amg_filter_fill_kernel, a.n, st, a, d, theta2, f_rp, fb, df, f_ci, f_va, map, part);
+}
+
+int
+launch_amg_filter_values(const AmgCsr & a, const double * d, const int * f_rp, const int * map, const int * fb, double * df, double * f_va,
+		double * part, int * bad, hipStream_t st)
+{
+	AMG_LAUNCH(amg_filter_values_kernel, a.n, st, a, d, f_rp, map, fb, df, f_va, part, bad);
+}
+
+int
+launch_amg_agg_norm(long nc, const int * m_rp, const double * m_b, double * nrm, hipStream_t st)
+{
+	AMG_LAUNCH(amg_agg_norm_kernel, nc, st, nc, m_rp, m_b, nrm);
+}
+
+int
+launch_amg_tentative(long n, const double * b, const int * agg, const double * nrm, double * t, hipStream_t st)
+{
+	AMG_LAUNCH(amg_tentative_kernel, n, st, n, b, agg, nrm, t);
+}
+
+int
+launch_amg_prolong_t(long n, const int * at_rp, const int * at_ci, const double * at_va, const int * agg, const double * t, const double * df,
+		double omega_p, double * p_va, hipStream_t st)
+{
+	AMG_LAUNCH(amg_prolong_t_kernel, n, st, n, at_rp, at_ci, at_va, agg, t, df, omega_p, p_va);
 }
 
 int

@@ -76,6 +76,7 @@ SYMBOLS = [
     "spmv_mi355x_amg_mem_footprint", "spmv_mi355x_pcg_amg",
     "spmv_mi355x_amg_update_values_prepare", "spmv_mi355x_amg_update_values", "spmv_mi355x_amg_update_values_device",
     "spmv_mi355x_amg_update_values_state", "spmv_mi355x_amg_update_info",
+    "spmv_mi355x_amg_create_with", "spmv_mi355x_amg_prolongator_info", "spmv_mi355x_amg_near_null",
 ]
 
 _lib = None
@@ -497,7 +498,7 @@ class AmgOpts(C.Structure):
 AMG_MAX_LEVELS = 16
 AMG_DEFAULTS = dict(theta=0.08, max_levels=10, coarse_rows=128, sweeps=1, coarse_sweeps=4)
 AMG_COARSE_KINDS = ("dense", "sweeps", "sweeps after a failed pivot")
-AMG_A, AMG_P = 0, 1
+AMG_A, AMG_P, AMG_AF = 0, 1, 2
 
 
 class AmgStats(C.Structure):
@@ -512,6 +513,18 @@ class AmgStats(C.Structure):
                 ("transpose_seconds", C.c_double), ("create_seconds", C.c_double), ("download_seconds", C.c_double)]
 
 
+class AmgProlongatorOpts(C.Structure):
+    """spmv_mi355x_amg_prolongator_opts (include/spmv_mi355x.h "AMG: a caller's near-null vector and filtered prolongator smoothing")"""
+    _fields_ = [("struct_size", C.c_int), ("filtered", C.c_int), ("near_null", C.c_void_p)]
+
+
+class AmgProlongatorStats(C.Structure):
+    """spmv_mi355x_amg_prolongator_stats"""
+    _fields_ = [("struct_size", C.c_uint), ("filtered", C.c_int), ("has_near_null", C.c_int),
+                ("nnz_filtered", C.c_long * AMG_MAX_LEVELS), ("unfiltered_rows", C.c_long * AMG_MAX_LEVELS),
+                ("omega_p", C.c_double * AMG_MAX_LEVELS), ("rho_p", C.c_double * AMG_MAX_LEVELS)]
+
+
 class AmgUpdateStats(C.Structure):
     """spmv_mi355x_amg_update_stats (include/spmv_mi355x.h "AMG: new values for a hierarchy")"""
     _fields_ = [("struct_size", C.c_uint), ("prepared", C.c_int), ("failed", C.c_int), ("updates", C.c_long),
@@ -522,7 +535,8 @@ class AmgUpdateStats(C.Structure):
 class Amg:
     """The smoothed-aggregation multilevel preconditioner of a symmetric positive definite matrix (include/spmv_mi355x.h "AMG"),
     built on the GPU: apply(v) is one V(sweeps, sweeps) cycle over handles built in `fmt` with `opts`. `.A` is the borrowed handle of
-    A itself, `.levels` the number of levels. Matrix.pcg_tri(b, precond=<Amg>) preconditions CG with it."""
+    A itself, `.levels` the number of levels. Matrix.pcg_tri(b, precond=<Amg>) preconditions CG with it. Amg.build(...) is the same
+    with a caller's near-null vector and / or filtered prolongator smoothing (spmv_mi355x_amg_create_with)."""
 
     def __init__(self, row_ptr, col_idx, values, n, fmt="sell_c_sigma", dtype=np.float64, theta=AMG_DEFAULTS["theta"],
                  max_levels=AMG_DEFAULTS["max_levels"], coarse_rows=AMG_DEFAULTS["coarse_rows"], sweeps=AMG_DEFAULTS["sweeps"],
@@ -538,11 +552,53 @@ class Amg:
         o = _make_opts(opts)
         a = AmgOpts(C.sizeof(AmgOpts), theta, max_levels, coarse_rows, sweeps, coarse_sweeps)
         fmt_id = FORMATS[fmt] if isinstance(fmt, str) else fmt
-        _check(lib().spmv_mi355x_amg_create(C.byref(self.h), fmt_id, F64 if self.dtype == np.float64 else F32, C.c_long(n),
-                                            _p(row_ptr), _p(col_idx), _p(values), C.byref(a), C.byref(o)))
+        head = (C.byref(self.h), fmt_id, F64 if self.dtype == np.float64 else F32, C.c_long(n), _p(row_ptr), _p(col_idx), _p(values),
+                C.byref(a))
+        with_ = getattr(self, "_prolongator", None)                  # set by Amg.build alone
+        if with_ is None:
+            _check(lib().spmv_mi355x_amg_create(*head, C.byref(o)))
+        else:
+            near_null, filtered = with_
+            if near_null is not None:
+                near_null = np.ascontiguousarray(near_null, np.float64)
+                if near_null.shape != (self.n,):
+                    raise ValueError(f"near_null must have {self.n} values, got {near_null.shape}")
+            po = AmgProlongatorOpts(C.sizeof(AmgProlongatorOpts), int(filtered), None if near_null is None else near_null.ctypes.data)
+            _check(lib().spmv_mi355x_amg_create_with(*head, C.byref(po), C.byref(o)))
         self.mem_footprint = lib().spmv_mi355x_amg_mem_footprint(self.h)
         self.levels = self.info()["levels"]
         self.A = self.level_matrices(0)[0] if self.levels else None
+
+    @classmethod
+    def build(cls, row_ptr, col_idx, values, n, near_null=None, filtered=False, fmt="sell_c_sigma", dtype=np.float64, **kw):
+        """An Amg through spmv_mi355x_amg_create_with: near_null = n fp64 values that the tentative prolongator carries instead of the
+        constant (None: the constant), filtered = True smooths the prolongator with the filtered operator A_F. The other arguments
+        are __init__'s (theta, max_levels, ..., **opts)."""
+        self = cls.__new__(cls)
+        self._prolongator = (near_null, filtered)
+        self.__init__(row_ptr, col_idx, values, n, fmt, dtype, **kw)
+        return self
+
+    def prolongator_info(self):
+        """dict of spmv_mi355x_amg_prolongator_stats, the per-level arrays cut to `levels` entries"""
+        s = AmgProlongatorStats()
+        s.struct_size = C.sizeof(AmgProlongatorStats)
+        _check(lib().spmv_mi355x_amg_prolongator_info(self.h, C.byref(s)))
+        out = {}
+        for k, _ in AmgProlongatorStats._fields_:
+            if k != "struct_size":
+                v = getattr(s, k)
+                out[k] = list(v)[:self.levels] if hasattr(v, "__len__") else v
+        return out
+
+    def near_null(self, level):
+        """b_l, the near-null vector of level `level` (fp64); empty where none was given"""
+        info = self.info()
+        if not 0 <= level < info["levels"]:
+            raise IndexError(f"level {level} of {info['levels']}")
+        out = np.zeros(max(info["rows"][level], 1))
+        _check(lib().spmv_mi355x_amg_near_null(self.h, C.c_int(level), _p(out)))
+        return out[:info["rows"][level] if self.prolongator_info()["has_near_null"] else 0]
 
     def info(self):
         """dict of spmv_mi355x_amg_stats: the per-level arrays cut to `levels` entries, coarse_kind also as coarse ("dense",
@@ -576,14 +632,16 @@ class Amg:
         return out[:info["rows"][level] if info["mis_rounds"][level] else 0]
 
     def level_csr(self, level, which="A"):
-        """(row_ptr, col_idx, values) in fp64 of A_l (which = "A") or P_l ("P"): what the handles were built from"""
+        """(row_ptr, col_idx, values) in fp64 of A_l (which = "A") or P_l ("P"): what the handles were built from; "AF": the filtered
+        operator of a coarsened level of a hierarchy built with filtered = True"""
         info = self.info()
         if not 0 <= level < info["levels"]:
             raise IndexError(f"level {level} of {info['levels']}")
-        nnz = info["nnz_p" if which == "P" else "nnz"][level]
+        nnz = self.prolongator_info()["nnz_filtered"][level] if which == "AF" else info["nnz_p" if which == "P" else "nnz"][level]
         rp = np.zeros(info["rows"][level] + 1, np.int32)
         ci, va = np.zeros(max(nnz, 1), np.int32), np.zeros(max(nnz, 1))
-        _check(lib().spmv_mi355x_amg_level_csr(self.h, C.c_int(level), C.c_int(AMG_P if which == "P" else AMG_A), _p(rp), _p(ci), _p(va)))
+        _check(lib().spmv_mi355x_amg_level_csr(self.h, C.c_int(level), C.c_int({"A": AMG_A, "P": AMG_P, "AF": AMG_AF}[which]), _p(rp), _p(ci),
+                                               _p(va)))
         return rp, ci[:nnz], va[:nnz]
 
     def apply(self, v):

@@ -20,7 +20,13 @@ reported with their min .. max spreads. No threshold is set and no speed is prom
     python tools/amg_bench.py                                        # stencil160 fp64
     python tools/amg_bench.py --runs grid2d2000:f64 --theta 0.08
     python tools/amg_bench.py --update                               # grid2d2000 and stencil160, fp64, theta 0.03
+    python tools/amg_bench.py --runs grid2d2000:f64 --theta 0.08 --filtered --near-null
 One JSON line per variant, and a table at the end.
+
+--filtered adds, per theta, the hierarchy of spmv_mi355x_amg_create_with with filtered = 1 ("amg t=<theta> F") beside the default one.
+--near-null adds the symmetrically scaled operator S A S of the workload, s = 1 + 0.5 U(-1, 1) from a fixed seed, with a handle of
+its own and the same b: per theta the default hierarchy on it ("amg t=<theta> S") and the one given near_null = 1 / s ("... S+nn"),
+beside the unscaled legs. Their spmv, solve and iteration legs run on the scaled handle.
 
 --update times the other thing a caller with changing values can do: per theta, amg_create on every window (its setup_seconds: the
 yardstick) against amg_update_values_prepare once and amg_update_values_device per window with the values already resident,
@@ -65,26 +71,45 @@ def run(E, torch, workload, dts, args):
     ya = torch.empty(n + 64, dtype=tdt, device="cuda")
     stream = torch.cuda.current_stream()
     b = np.random.default_rng(7).uniform(-1, 1, n).astype(np_dtype)
-    variants = [("none", None, {})]
+    variants = [("none", None, {}, MA)]                       # (name, preconditioner, what its setup reports, the handle of A it solves)
     t0 = time.perf_counter()
     F = E.Fsai(rp, ci, va, n, None, "sell_c_sigma", np_dtype)
-    variants.append(("fsai", F, dict(setup_seconds=round(F.info()["setup_seconds"], 4), wall_setup_seconds=round(time.perf_counter() - t0, 4))))
+    variants.append(("fsai", F, dict(setup_seconds=round(F.info()["setup_seconds"], 4), wall_setup_seconds=round(time.perf_counter() - t0, 4)),
+                     MA))
     print(f"# built fsai: {variants[-1][2]}", flush=True)
+    MS = s = vs = None
+    if args.near_null:
+        s = 1 + 0.5 * np.random.default_rng(25).uniform(-1, 1, n)
+        vs = np.asarray(va, np.float64) * (s[np.repeat(np.arange(n), np.diff(rp))] * s[np.asarray(ci)])
+        MS = E.Matrix(rp, ci, vs, n, n, "sell_c_sigma", np_dtype)
+    builds = []                                               # (suffix, values, near_null, filtered, the handle of A), per theta
     for theta in args.theta:
+        builds.append((theta, "", va, None, None, MA))
+        if args.filtered:
+            builds.append((theta, " F", va, None, True, MA))
+        if args.near_null:
+            builds.append((theta, " S", vs, None, None, MS))
+            builds.append((theta, " S+nn", vs, 1.0 / s, False, MS))
+    for theta, suffix, values, near_null, filtered, H in builds:
         t0 = time.perf_counter()
-        M = E.Amg(rp, ci, va, n, "sell_c_sigma", np_dtype, theta=theta, sweeps=args.sweeps)
+        if filtered is None:
+            M = E.Amg(rp, ci, values, n, "sell_c_sigma", np_dtype, theta=theta, sweeps=args.sweeps)
+        else:
+            M = E.Amg.build(rp, ci, values, n, near_null, filtered, "sell_c_sigma", np_dtype, theta=theta, sweeps=args.sweeps)
         wall = time.perf_counter() - t0
-        info = M.info()
+        info, pinfo = M.info(), M.prolongator_info()
         extra = dict(theta=theta, sweeps=args.sweeps, levels=info["levels"], rows=info["rows"], nnz=info["nnz"], mis_rounds=info["mis_rounds"],
+                     entries_per_row=[round(z / max(r, 1), 1) for z, r in zip(info["nnz"], info["rows"])], filtered=pinfo["filtered"],
+                     near_null=pinfo["has_near_null"], nnz_filtered=pinfo["nnz_filtered"], unfiltered_rows=pinfo["unfiltered_rows"],
                      coarse=info["coarse"], stalled=info["stalled"], operator_complexity=round(info["operator_complexity"], 4),
                      grid_complexity=round(info["grid_complexity"], 4), spmvs_per_apply=info["spmvs_per_apply"],
                      launches_per_apply=info["launches_per_apply"], wall_setup_seconds=round(wall, 4),
                      **{k: round(info[k], 4) for k in ("setup_seconds", "coarsen_seconds", "spgemm_seconds", "transpose_seconds",
                                                        "create_seconds", "download_seconds")},
                      mem_over_a=round(M.mem_footprint / MA.mem_footprint, 3))
-        variants.append((f"amg t={theta:g}", M, extra))
+        variants.append((f"amg t={theta:g}{suffix}", M, extra, H))
         print(f"# built {variants[-1][0]}: {extra}", flush=True)
-    solve = lambda M, tol, steps: MA.pcg_tri(b, precond=M, tol=tol, max_iterations=steps, history=False)
+    solve = lambda H, M, tol, steps: H.pcg_tri(b, precond=M, tol=tol, max_iterations=steps, history=False)
 
     def time_apply(M):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -95,25 +120,25 @@ def run(E, torch, workload, dts, args):
         e1.synchronize()
         return e0.elapsed_time(e1) / args.reps
 
-    legs = {name: {k: [] for k in ("spmv", "seconds", "iter_ms", "ratio", "apply", "apply_ratio")} for name, _, _ in variants}
+    legs = {name: {k: [] for k in ("spmv", "seconds", "iter_ms", "ratio", "apply", "apply_ratio")} for name, _, _, _ in variants}
     last = {}
     for w in range(args.windows + 1):                         # window 0 warms every leg up and is dropped
-        for name, M, _ in variants:
-            t_a = MA.time_device(xa.data_ptr(), ya.data_ptr(), args.reps, stream.cuda_stream)
+        for name, M, _, H in variants:
+            t_a = H.time_device(xa.data_ptr(), ya.data_ptr(), args.reps, stream.cuda_stream)
             torch.cuda.synchronize()
             t_f = time_apply(M) if M is not None else float("nan")
-            r = solve(M, args.tol, args.max_iterations)
-            fixed = solve(M, 0.0, 0)["seconds"]
-            s = solve(M, 0.0, args.steps)
+            r = solve(H, M, args.tol, args.max_iterations)
+            fixed = solve(H, M, 0.0, 0)["seconds"]
+            st = solve(H, M, 0.0, args.steps)
             # a preconditioned solve may reach r = 0 or lose r.z > 0 in the rounding floor before --steps: then the leg is not timed
-            t_c = (s["seconds"] - fixed) * 1e3 / args.steps if (s["iterations"], s["stop"]) == (args.steps, 2) else float("nan")
+            t_c = (st["seconds"] - fixed) * 1e3 / args.steps if (st["iterations"], st["stop"]) == (args.steps, 2) else float("nan")
             last[name] = r
             if w:
                 for key, t in zip(legs[name], (t_a, r["seconds"], t_c, t_c / t_a, t_f, t_f / t_a)):
                     legs[name][key].append(t)
         print(f"# window {w} done", flush=True)
     rows = []
-    for name, M, extra in variants:
+    for name, M, extra, _ in variants:
         r = last[name]
         rec = dict(workload=workload, dtype=dts, format=MA.format_name, n=int(n), nnz_a=int(MA.nnz), precond=name, tol=args.tol,
                    iterations=int(r["iterations"]), stop=int(r["stop"]), rnorm_over_b=float(r["rnorm"] / r["rnorm0"]),
@@ -125,10 +150,12 @@ def run(E, torch, workload, dts, args):
             rec[key + "_spread"] = [round(float(np.nanmin(ts)), 5), round(float(np.nanmax(ts)), 5)]
         print(json.dumps(rec), flush=True)
         rows.append(rec)
-    for _, M, _ in variants:
+    for _, M, _, _ in variants:
         if M is not None:
             M.close()
     MA.close()
+    if MS is not None:
+        MS.close()
     return rows
 
 
@@ -192,6 +219,9 @@ def main():
     ap.add_argument("--theta", default=None, help="the strength thresholds of the AMG variants (default 0.08,0.03; with --update 0.03)")
     ap.add_argument("--update", action="store_true", help="time amg_create against update_values_prepare and update_values_device "
                     "instead of the solves")
+    ap.add_argument("--filtered", action="store_true", help="per theta also the hierarchy with filtered prolongator smoothing")
+    ap.add_argument("--near-null", action="store_true", help="also S A S of the workload (s = 1 +- 0.5, a fixed seed): per theta the "
+                    "default hierarchy on it and the one given near_null = 1 / s")
     ap.add_argument("--sweeps", type=int, default=1, help="nu of the V(nu, nu) cycle")
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--tol", type=float, default=1e-8, help="the tolerance of the solve leg")
@@ -224,20 +254,20 @@ def main():
                   f"{r['prepare_bytes_over_footprint']:16.3f}")
         return
     nan = float("nan")
-    print(f"{'workload':11s} {'dtype':5s} {'precond':>11s} {'iters':>6s} {'stop':>4s} {'seconds':>9s} {'spread':>19s} {'ms/iter':>8s} "
+    print(f"{'workload':11s} {'dtype':5s} {'precond':>16s} {'iters':>6s} {'stop':>4s} {'seconds':>9s} {'spread':>19s} {'ms/iter':>8s} "
           f"{'spmv ms':>8s} {'iter / spmv':>11s} {'apply ms':>9s} {'apply / spmv':>12s}")
     for r in rows:
-        print(f"{r['workload']:11s} {r['dtype']:5s} {r['precond']:>11s} {r['iterations']:6d} {r['stop']:4d} {r['seconds']:9.4f} "
+        print(f"{r['workload']:11s} {r['dtype']:5s} {r['precond']:>16s} {r['iterations']:6d} {r['stop']:4d} {r['seconds']:9.4f} "
               f"{r['seconds_spread'][0]:9.4f} ..{r['seconds_spread'][1]:8.4f} {r.get('iter_ms', nan):8.4f} {r['spmv']:8.4f} "
               f"{r.get('ratio', nan):11.2f} {r.get('apply', nan):9.4f} {r.get('apply_ratio', nan):12.2f}")
-    print(f"{'workload':11s} {'precond':>11s} {'levels':>6s} {'coarse':>7s} {'op cx':>6s} {'spmvs':>5s} {'launches':>8s} {'setup s':>8s} {'coarsen':>8s} "
+    print(f"{'workload':11s} {'precond':>16s} {'levels':>6s} {'coarse':>7s} {'op cx':>6s} {'spmvs':>5s} {'launches':>8s} {'setup s':>8s} {'coarsen':>8s} "
           f"{'spgemm':>8s} {'transp':>8s} {'handles':>8s} {'download':>8s} {'wall s':>8s}  rows")
     for r in rows:
         if "levels" in r:
-            print(f"{r['workload']:11s} {r['precond']:>11s} {r['levels']:6d} {r['coarse'][:7]:>7s} {r['operator_complexity']:6.3f} "
+            print(f"{r['workload']:11s} {r['precond']:>16s} {r['levels']:6d} {r['coarse'][:7]:>7s} {r['operator_complexity']:6.3f} "
                   f"{r['spmvs_per_apply']:5d} {r['launches_per_apply']:8d} {r['setup_seconds']:8.3f} {r['coarsen_seconds']:8.3f} "
                   f"{r['spgemm_seconds']:8.3f} {r['transpose_seconds']:8.3f} {r['create_seconds']:8.3f} {r['download_seconds']:8.3f} "
-                  f"{r['wall_setup_seconds']:8.3f}  {r['rows']}")
+                  f"{r['wall_setup_seconds']:8.3f}  {r['rows']}  entries per row {r['entries_per_row']}")
 
 
 if __name__ == "__main__":

@@ -766,7 +766,8 @@ int  spmv_mi355x_gmres_tri(spmv_mi355x_matrix * A, const void * b_host, void * x
  *        in stop 4.
  *   - NOT CHECKABLE: that A and M are symmetric positive definite. Blocked handles give a symmetric M only when both use the same
  *     block_rows (a global handle counts as block_rows >= n). Stop 4 catches only what the two inner products reveal.
- *   - NOT BUILT: multi-RHS, the row-partitioned form, device-pointer b / x, a non-zero x0. */
+ *   - NOT BUILT: the row-partitioned form, device-pointer b / x, a non-zero x0, a k-column triangular solve (k right-hand sides
+ *     with M = NULL or a scale alone: spmv_mi355x_pcg_tri_multi below). */
 typedef struct {
 	unsigned struct_size;   /* in: sizeof(spmv_mi355x_pcg_tri_info) */
 	long   iterations;      /* completed loop bodies */
@@ -828,7 +829,7 @@ int  spmv_mi355x_pcg_tri(spmv_mi355x_matrix * A, const void * b_host, void * x_o
  *     7. the device, and whatever spmv_mi355x_create refuses for the format and opts (its message after the prefix).
  *   - NOT CHECKABLE: that A is symmetric and positive definite. Only the lower triangle is read; an indefinite A shows, if at all, as
  *     fallback_rows > 0.
- *   - NOT BUILT: update_values for an fsai handle (new values of A need a new handle), gmres / minres / pbicgstab wiring, multi-RHS,
+ *   - NOT BUILT: update_values for an fsai handle (new values of A need a new handle), gmres / minres / pbicgstab wiring,
  *     the row-partitioned form, adaptive patterns, a pattern with entries above the diagonal.
  * spmv_mi355x_pcg_fsai is spmv_mi355x_pcg_tri with z = M^-1 r = fsai_apply_device_async: the same recurrences, kernels, stop codes,
  * history, spmv_mi355x_pcg_tri_info and freeze (the two SpMVs of an apply write only F's scratch vector and z, scratch that only the
@@ -970,8 +971,9 @@ int  spmv_mi355x_spgemm_info(const spmv_mi355x_spgemm * P, spmv_mi355x_spgemm_st
  *     positive, as coarse_kind = 2, or as stop 4 of the solver.
  *   - NOT BUILT: update_values for a hierarchy that re-aggregates (what is built keeps the aggregates and redoes the numeric
  *     passes: "new values for a hierarchy" below), W- and K-cycles, more than one near-null vector (block coarse unknowns,
- *     elasticity), filtering with a threshold of its own, gmres / minres / multi-RHS wiring, the row-partitioned form, folding the
- *     small levels into one launch. The setup routes patterns
+ *     elasticity), filtering with a threshold of its own, gmres / minres / multi-RHS wiring other than CG's (k right-hand sides
+ *     through the cycle and through CG: spmv_mi355x_amg_apply_multi and spmv_mi355x_pcg_amg_multi below), the row-partitioned
+ *     form, folding the small levels into one launch. The setup routes patterns
  *     through the host (spgemm_create and create take host arrays); the split in amg_info shows what that costs.
  * spmv_mi355x_pcg_amg is spmv_mi355x_pcg_tri with z = M^-1 r = amg_apply_device_async: the same recurrences, kernels, stop codes,
  * history, spmv_mi355x_pcg_tri_info and freeze (the SpMVs and vector kernels of a cycle write only the hierarchy's own vectors and
@@ -1117,6 +1119,54 @@ int  spmv_mi355x_amg_create_with(spmv_mi355x_amg ** out, int format, int precisi
 		const spmv_mi355x_amg_prolongator_opts * prolongator_opts /* NULL = defaults */, const spmv_mi355x_opts * opts /* may be NULL */);
 int  spmv_mi355x_amg_prolongator_info(const spmv_mi355x_amg * M, spmv_mi355x_amg_prolongator_stats * info /* struct_size first */);
 int  spmv_mi355x_amg_near_null(const spmv_mi355x_amg * M, int level, double * out /* rows[level] */);
+
+/* ---- k right-hand sides through one AMG or FSAI cycle and one tol-based CG -------------------------------------------------------- */
+/* k independent systems A x_j = b_j on one handle. Not block CG: every column keeps the recurrences, the stop codes
+ * 1 to 5, the breakdown rules and the freeze of spmv_mi355x_pcg_tri. What the columns share is one spmv_mi355x_spmm_device_async per
+ * SpMV of the single call, every launch, and every pass over A_l, R_l and P_l of a hierarchy.
+ * THE CONTRACT of every call below: on handles whose SpMV is deterministic, column j returns the bits of the single-vector call on
+ * column j. No single-vector entry point goes through these kernels.
+ * Every k-column block is row-major: row i at ptr + i * ld, ld >= k counted in values of the handle's precision.
+ *   - amg_apply_multi_device_async: out = M^-1 in for the k columns, the schedule of amg_apply_device_async with every SpMV as one
+ *     SpMM (beta = 1 for the prolongation) and every vector launch as one launch per chunk of 8, 4, 2 or 1 columns (k = 8s, then the
+ *     binary remainder, as the SpMM splits it). A dense last level is solved by one workgroup per chunk, which loads the packed factor
+ *     into LDS once for up to 8 columns. Level 0 reads `in` and writes `out` through their own ld; in == out needs ldin == ldout and
+ *     works on a copy. The hierarchy owns the per-level blocks: they are allocated at the first multi apply, counted in
+ *     amg_mem_footprint, and replaced when a larger k arrives, WHICH SYNCHRONISES THE DEVICE. One multi apply per hierarchy at a time.
+ *     amg_update_values* keeps working: the blocks hold no matrix data. amg_apply_multi is the blocking host form with ld = k.
+ *     rc 1 with "amg_apply_multi:": a NULL argument, k < 1, ld < k, in == out with ldin != ldout, a hierarchy whose last update failed.
+ *     n == 0 returns 0.
+ *   - amg_apply_multi_plan (host only, touches no device): matrix_passes_out = the sum over the cycle's products of what
+ *     spmv_mi355x_spmm_plan reports for that level's handle and k; launches_out = those passes plus the vector and dense launches
+ *     (the single cycle's, once per chunk). k = 1 reports spmvs_per_apply and launches_per_apply.
+ *   - fsai_apply_multi_device_async / fsai_apply_multi: out = G^t (G in) as two SpMMs with an n x k scratch block that grows on demand
+ *     (growing synchronises); in == out is legal with ldin == ldout.
+ *   - pcg_tri_multi / pcg_fsai_multi / pcg_amg_multi: B_host and X_out_host are rows() x k, ld = k. history_out (may be NULL):
+ *     k * max_iterations doubles, column j's rows at history_out + j * max_iterations. infos (may be NULL): k spmv_mi355x_pcg_tri_info,
+ *     EACH with struct_size set. Per column they carry what the single solve carries; the explicit |b - A x| and |x| come from one
+ *     final SpMM; spmv_calls (SpMM calls) and seconds are the call's, equal in every element. pcg_tri_multi serves M = NULL and an M
+ *     with a scale alone (Jacobi); an M with first or second set is REFUSED: there is no k-column triangular solve.
+ *     A stopped column is frozen while the others run: its x, r, p, state and history are stored back unchanged or not at all. b_j = 0
+ *     stops with 3, a NaN in b_j with 4 at 0 iterations and x_j = 0; neither disturbs its neighbours. The host stops enqueueing once
+ *     every column has stopped (with the single solve's polling lag). Per iteration: 1 SpMM, M's own launches, 4 vector launches per
+ *     chunk (3 without a preconditioner, when no z is stored).
+ *     rc 1 before any device is touched, in this order: k < 1; an infos[j].struct_size < 8; tol negative or not finite;
+ *     max_iterations < 0; (pcg_tri_multi) M with a triangular part; A, B or X_out NULL; then the single entries' checks in their order.
+ *   - NOT BUILT: a k-column triangular solve (SGS / IC(0) for k columns), block CG, routing the single solves through these kernels. */
+int  spmv_mi355x_amg_apply_multi_device_async(spmv_mi355x_amg * M, int k, const void * in_dev, long ldin, void * out_dev, long ldout,
+		void * hip_stream);
+int  spmv_mi355x_amg_apply_multi(spmv_mi355x_amg * M, int k, const void * in_host, void * out_host);          /* blocking, ld = k */
+int  spmv_mi355x_amg_apply_multi_plan(const spmv_mi355x_amg * M, int k, long * matrix_passes_out, long * launches_out);
+int  spmv_mi355x_fsai_apply_multi_device_async(spmv_mi355x_fsai * F, int k, const void * in_dev, long ldin, void * out_dev, long ldout,
+		void * hip_stream);
+int  spmv_mi355x_fsai_apply_multi(spmv_mi355x_fsai * F, int k, const void * in_host, void * out_host);        /* blocking, ld = k */
+int  spmv_mi355x_pcg_tri_multi(spmv_mi355x_matrix * A, int k, const void * B_host, void * X_out_host,
+		const spmv_mi355x_tri_precond * M /* may be NULL; a scale alone */, double tol, long max_iterations,
+		double * history_out /* may be NULL: k * max_iterations doubles */, spmv_mi355x_pcg_tri_info * infos /* may be NULL: k of them */);
+int  spmv_mi355x_pcg_fsai_multi(spmv_mi355x_matrix * A, int k, const void * B_host, void * X_out_host, spmv_mi355x_fsai * F, double tol,
+		long max_iterations, double * history_out, spmv_mi355x_pcg_tri_info * infos);
+int  spmv_mi355x_pcg_amg_multi(spmv_mi355x_matrix * A, int k, const void * B_host, void * X_out_host, spmv_mi355x_amg * M, double tol,
+		long max_iterations, double * history_out, spmv_mi355x_pcg_tri_info * infos);
 
 /* Row-partitioned (multi-GPU) form of the same two solvers: one process per GPU owns the row block [row_offset,
  * row_offset + m_local) of A, b and x. The solver keeps every vector device-resident and local; the two things that cross

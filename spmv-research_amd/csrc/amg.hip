@@ -139,9 +139,13 @@ amg_free(spmv_mi355x_amg * M)
 			if (p)
 				(void) hipFree(p);
 	}
-	for (void * p : {(void *) M->d_factor, M->d_in, M->d_out})
+	for (void * p : {(void *) M->d_factor, M->d_in, M->d_out, M->d_in_multi, M->d_out_multi})
 		if (p)
 			(void) hipFree(p);
+	for (const std::vector<void *> * v : {&M->mb, &M->mx, &M->mt})
+		for (void * p : *v)
+			if (p)
+				(void) hipFree(p);
 	delete M;
 }
 
@@ -1221,6 +1225,214 @@ spmv_mi355x_amg_apply(spmv_mi355x_amg * M, const void * in_host, void * out_host
 		return 1;
 	HIP_TRY(hipMemcpyAsync(out_host, M->d_out, bytes, hipMemcpyDeviceToHost, nullptr));
 	HIP_TRY(hipStreamSynchronize(nullptr));
+	return 0;
+}
+
+// the checks every k-column entry shares, in the single apply's wording; *empty: n == 0, nothing to do
+static bool
+amg_multi_arguments_ok(const char * what, spmv_mi355x_amg * M, int k, const void * in, long ldin, void * out, long ldout, bool * empty)
+{
+	*empty = false;
+	if (!M || (M->n > 0 && (!in || !out)))
+	{
+		set_error("%s: NULL argument (%s%s%s )", what, !M ? " M" : "", M && !in ? " in" : "", M && !out ? " out" : "");
+		return false;
+	}
+	if (k < 1)
+	{
+		set_error("%s: k = %d: at least one column is needed", what, k);
+		return false;
+	}
+	if (ldin < k || ldout < k)
+	{
+		set_error("%s: ldin = %ld, ldout = %ld: both must be >= k = %d", what, ldin, ldout, k);
+		return false;
+	}
+	if (M->n == 0)
+	{
+		*empty = true;
+		return true;
+	}
+	if (M->update_failed)
+	{
+		set_error("%s: the last amg_update_values of this hierarchy failed below level 0 and left it half rewritten: update it with "
+				"values it accepts first", what);
+		return false;
+	}
+	return true;
+}
+
+// the per-level blocks for k columns; a larger k frees the smaller blocks after the device has finished with them
+static int
+amg_multi_reserve(spmv_mi355x_amg * M, int k)
+{
+	if (k <= M->multi_k)
+		return 0;
+	HIP_TRY(hipDeviceSynchronize());
+	for (std::vector<void *> * v : {&M->mb, &M->mx, &M->mt})
+	{
+		for (void * p : *v)
+			if (p)
+				(void) hipFree(p);
+		v->assign((size_t) M->levels, nullptr);
+	}
+	M->vector_bytes -= M->multi_bytes;
+	M->multi_bytes = 0;
+	M->multi_k = 0;
+	for (int l = 0; l < M->levels; l++)
+	{
+		const size_t bytes = (size_t) M->lev[(size_t) l].n * (size_t) k * (M->f32 ? 4 : 8);
+		for (std::vector<void *> * v : {&M->mb, &M->mx, &M->mt})
+		{
+			if (l == 0 && v == &M->mx)
+				continue;
+			ABI_TRY(dev_alloc_bytes(&(*v)[(size_t) l], bytes));
+			M->multi_bytes += (double) bytes;
+		}
+	}
+	M->vector_bytes += M->multi_bytes;
+	M->multi_k = k;
+	return 0;
+}
+
+int
+spmv_mi355x_amg_apply_multi_device_async(spmv_mi355x_amg * M, int k, const void * in_dev, long ldin, void * out_dev, long ldout,
+		void * hip_stream)
+{
+	bool empty;
+	if (!amg_multi_arguments_ok("amg_apply_multi", M, k, in_dev, ldin, out_dev, ldout, &empty))
+		return 1;
+	if (in_dev == out_dev && ldin != ldout)
+	{
+		set_error("amg_apply_multi: in == out needs ldin == ldout (got %ld and %ld)", ldin, ldout);
+		return 1;
+	}
+	if (empty)
+		return 0;
+	ABI_TRY(amg_multi_reserve(M, k));
+	hipStream_t st = (hipStream_t) hip_stream;
+	const bool f32 = M->f32;
+	const size_t vs = f32 ? 4 : 8;
+	const int nl = M->levels, nu = M->opts.sweeps;
+	const long ld = k;                                                // of the hierarchy's blocks, whatever k they were allocated for
+	if (in_dev == out_dev)
+	{
+		// level 0 reads b after it has written x: an apply in place works on a copy of the k columns of `in`
+		HIP_TRY(hipMemcpy2DAsync(M->mb[0], (size_t) ld * vs, in_dev, (size_t) ldin * vs, (size_t) k * vs, (size_t) M->n,
+				hipMemcpyDeviceToDevice, st));
+		in_dev = M->mb[0];
+		ldin = ld;
+	}
+	auto rhs = [&](int l) { return l == 0 ? in_dev : (const void *) M->mb[(size_t) l]; };
+	auto sol = [&](int l) { return l == 0 ? out_dev : M->mx[(size_t) l]; };
+	auto ldb = [&](int l) { return l == 0 ? ldin : ld; };
+	auto ldx = [&](int l) { return l == 0 ? ldout : ld; };
+	auto sweep = [&](int l) {
+		AmgLevel & L = M->lev[(size_t) l];
+		ABI_TRY(spmv_mi355x_spmm_device_async(L.A, k, sol(l), ldx(l), M->mt[(size_t) l], ld, 0, st));
+		return launch_amg_sweep_multi(f32, k, L.w, rhs(l), ldb(l), M->mt[(size_t) l], ld, sol(l), ldx(l), L.n, st);
+	};
+	for (int l = 0; l < nl - 1; l++)
+	{
+		AmgLevel & L = M->lev[(size_t) l];
+		ABI_TRY(launch_amg_first_multi(f32, k, L.w, rhs(l), ldb(l), sol(l), ldx(l), L.n, st));
+		for (int s = 1; s < nu; s++)
+			ABI_TRY(sweep(l));
+		ABI_TRY(spmv_mi355x_spmm_device_async(L.A, k, sol(l), ldx(l), M->mt[(size_t) l], ld, 0, st));
+		ABI_TRY(launch_amg_residual_multi(f32, k, rhs(l), ldb(l), M->mt[(size_t) l], ld, L.n, st));
+		ABI_TRY(spmv_mi355x_spmm_device_async(L.R, k, M->mt[(size_t) l], ld, M->mb[(size_t) l + 1], ld, 0, st));
+	}
+	{
+		const int l = nl - 1;
+		AmgLevel & L = M->lev[(size_t) l];
+		if (M->coarse_kind == SPMV_MI355X_AMG_COARSE_DENSE)
+			ABI_TRY(launch_amg_dense_solve_multi(f32, k, M->d_factor, rhs(l), ldb(l), sol(l), ldx(l), (int) L.n, st));
+		else
+		{
+			ABI_TRY(launch_amg_first_multi(f32, k, L.w, rhs(l), ldb(l), sol(l), ldx(l), L.n, st));
+			for (int s = 1; s < M->opts.coarse_sweeps; s++)
+				ABI_TRY(sweep(l));
+		}
+	}
+	for (int l = nl - 2; l >= 0; l--)
+	{
+		AmgLevel & L = M->lev[(size_t) l];
+		ABI_TRY(spmv_mi355x_spmm_device_async(L.P, k, M->mx[(size_t) l + 1], ld, sol(l), ldx(l), 1, st));
+		for (int s = 0; s < nu; s++)
+			ABI_TRY(sweep(l));
+	}
+	return 0;
+}
+
+int
+spmv_mi355x_amg_apply_multi(spmv_mi355x_amg * M, int k, const void * in_host, void * out_host)
+{
+	bool empty;
+	if (!amg_multi_arguments_ok("amg_apply_multi", M, k, in_host, k, out_host, k, &empty))
+		return 1;
+	if (empty)
+		return 0;
+	HIP_TRY(hipSetDevice(M->device));
+	const size_t bytes = (size_t) M->n * (size_t) k * (M->f32 ? 4 : 8);
+	if (k > M->multi_host_k)
+	{
+		HIP_TRY(hipDeviceSynchronize());
+		for (void ** p : {&M->d_in_multi, &M->d_out_multi})
+		{
+			if (*p)
+				(void) hipFree(*p);
+			*p = nullptr;
+		}
+		M->multi_host_k = 0;
+		if (dev_alloc_bytes(&M->d_in_multi, bytes) || dev_alloc_bytes(&M->d_out_multi, bytes))
+			return 1;
+		M->multi_host_k = k;
+	}
+	HIP_TRY(hipMemcpyAsync(M->d_in_multi, in_host, bytes, hipMemcpyHostToDevice, nullptr));
+	if (spmv_mi355x_amg_apply_multi_device_async(M, k, M->d_in_multi, k, M->d_out_multi, k, nullptr))
+		return 1;
+	HIP_TRY(hipMemcpyAsync(out_host, M->d_out_multi, bytes, hipMemcpyDeviceToHost, nullptr));
+	HIP_TRY(hipStreamSynchronize(nullptr));
+	return 0;
+}
+
+// Host only. The cycle's products are, per coarsened level, 2 nu with A_l, one with R_l and one with P_l, and coarse_sweeps - 1 with the
+// A of a last level that is not factorised; its vector launches are those of the single cycle, once per chunk of k.
+int
+spmv_mi355x_amg_apply_multi_plan(const spmv_mi355x_amg * M, int k, long * matrix_passes_out, long * launches_out)
+{
+	if (!M || !matrix_passes_out || !launches_out)
+	{
+		set_error("amg_apply_multi_plan: NULL argument (%s%s%s )", !M ? " M" : "", !matrix_passes_out ? " matrix_passes_out" : "",
+				!launches_out ? " launches_out" : "");
+		return 1;
+	}
+	if (k < 1)
+	{
+		set_error("amg_apply_multi_plan: k = %d: at least one column is needed", k);
+		return 1;
+	}
+	long passes = 0;
+	const int nu = M->opts.sweeps, cs = M->opts.coarse_sweeps;
+	const bool dense = M->coarse_kind == SPMV_MI355X_AMG_COARSE_DENSE;
+	for (int l = 0; l < M->levels; l++)
+	{
+		const AmgLevel & L = M->lev[(size_t) l];
+		const bool last = l == M->levels - 1;
+		const struct { spmv_mi355x_matrix * h; long times; } products[] = {{L.A, last ? (dense ? 0 : cs - 1) : 2 * nu}, {L.R, last ? 0 : 1},
+				{L.P, last ? 0 : 1}};
+		for (const auto & pr : products)
+		{
+			if (!pr.times)
+				continue;
+			int p = 0, cols = 0;
+			ABI_TRY(spmv_mi355x_spmm_plan(pr.h, k, &p, &cols));
+			passes += pr.times * p;
+		}
+	}
+	const long chunks = (long) column_chunks(k).size();
+	*matrix_passes_out = passes;
+	*launches_out = M->levels > 0 ? passes + chunks * (M->launches - M->spmvs) : 0;
 	return 0;
 }
 

@@ -6,6 +6,11 @@
 // stored order; rows of A_l hold a handful of entries (a stencil, a Galerkin product of one), so a wave per row would idle. The
 // cycle's vector kernels are the solvers' (VB lanes, solver_blocks workgroups, GRID_STRIDE). The dense solve is one workgroup of
 // AMG_DENSE_MAX lanes, lane a owning y_a; its loops hold one barrier per column and run n trips in every lane.
+// THE CYCLE FOR k COLUMNS (amg_apply_multi*): the same schedule over row-major blocks, every SpMV one SpMM, every vector launch one
+// launch per chunk of KC in {8, 4, 2, 1} columns (k = 8s, then the binary remainder); a thread owns row i of its chunk. The dense
+// solve is one workgroup per chunk: the triangle (66 048 B) goes into LDS once, piv is [AMG_DENSE_MAX][KC] (8 KiB at KC = 8), lane a
+// keeps y_a of every column, and there is one barrier per column of L in each direction whatever KC is. The hierarchy owns the
+// per-level blocks (mb, mx, mt below); the first multi apply allocates them and a larger k replaces them, which synchronises the device.
 // No atomics on values (the one atomic is the integer count of undecided nodes, one add per workgroup), no flags, nothing spins; a
 // launch boundary is the only ordering between workgroups.
 //     kernel                     VGPRs   LDS        scratch
@@ -28,6 +33,10 @@
 //     amg_agg_norm_kernel          14        0         0
 //     amg_tentative_kernel         20        0         0
 //     amg_prolong_t_kernel         24        0         0
+//     amg_first / sweep / residual_multi <KC = 8 / 4 / 2 / 1>, the largest of fp32 and fp64
+//                          62 / 38 / 26 / 26     0         0
+//     amg_dense_solve_multi_kernel <KC = 8 / 4 / 2 / 1>
+//                          40 / 30 / 26 / 20   74 240 / 70 144 / 68 096 / 67 072 B   0
 // (-Rpass-analysis=kernel-resource-usage, gfx950; profiles/r23_amg.txt, profiles/r24_amg_update.txt and
 // profiles/r25_amg_prolongator.txt have the compiler's own table.)
 // STEPS 5a TO 5c (amg_create_with; the header's "AMG: a caller's near-null vector and filtered prolongator smoothing"). Filtered: a
@@ -112,6 +121,12 @@ int launch_amg_sweep(bool f32, const void * w, const void * b, const void * t, v
 int launch_amg_residual(bool f32, const void * b, void * t, long n, hipStream_t st);
 // x = (L L^t)^-1 b for the packed factor L of n <= AMG_DENSE_MAX rows (row-major lower triangle, fp64)
 int launch_amg_dense_solve(bool f32, const double * L, const void * b, void * x, int n, hipStream_t st);
+// the same four for the k columns of row-major blocks (row i at ptr + i * ld), one launch per chunk of 8, 4, 2 or 1 columns
+int launch_amg_first_multi(bool f32, int k, const void * w, const void * b, long ldb, void * x, long ldx, long n, hipStream_t st);
+int launch_amg_sweep_multi(bool f32, int k, const void * w, const void * b, long ldb, const void * t, long ldt, void * x, long ldx, long n,
+		hipStream_t st);
+int launch_amg_residual_multi(bool f32, int k, const void * b, long ldb, void * t, long ldt, long n, hipStream_t st);
+int launch_amg_dense_solve_multi(bool f32, int k, const double * L, const void * b, long ldb, void * x, long ldx, int n, hipStream_t st);
 
 // an update: step 1 with *bad += the rows whose diagonal is absent, not finite or <= 0 (zeroed by the caller); d and part as above
 int launch_amg_diag_check(const AmgCsr & a, double * d, double * part, int * bad, hipStream_t st);
@@ -176,6 +191,12 @@ struct spmv_mi355x_amg {
 	long spmvs = 0, launches = 0;
 	double setup_seconds = 0, coarsen_seconds = 0, spgemm_seconds = 0, transpose_seconds = 0, create_seconds = 0, download_seconds = 0;
 	double vector_bytes = 0;
+	// apply_multi: per level the blocks b, x and t, room for rows x multi_k values each, used with ld = k of the call (x is NULL on level 0, whose b serves an
+	// apply in place); allocated at the first multi apply, regrown (after a device synchronisation) when a larger k arrives
+	std::vector<void *> mb, mx, mt;
+	int multi_k = 0, multi_host_k = 0;
+	double multi_bytes = 0;                               // of mb, mx and mt: part of vector_bytes
+	void * d_in_multi = nullptr, * d_out_multi = nullptr; // the blocks of the host-buffer apply_multi, n x multi_host_k
 	spmv::AmgUpdate * upd = nullptr;                      // amg_update_values_prepare's; NULL before it
 	bool update_failed = false;                           // the last update stopped below level 0: apply refuses
 };

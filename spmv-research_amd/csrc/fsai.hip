@@ -203,7 +203,7 @@ fsai_free(spmv_mi355x_fsai * F)
 		spmv_mi355x_destroy(F->G);
 	if (F->Gt)
 		spmv_mi355x_destroy(F->Gt);
-	for (void * p : {F->d_scratch, F->d_in, F->d_out})
+	for (void * p : {F->d_scratch, F->d_in, F->d_out, F->d_scratch_multi, F->d_in_multi, F->d_out_multi})
 		if (p)
 			(void) hipFree(p);
 	delete F;
@@ -496,6 +496,89 @@ spmv_mi355x_fsai_apply(spmv_mi355x_fsai * F, const void * in_host, void * out_ho
 	if (spmv_mi355x_fsai_apply_device_async(F, F->d_in, F->d_out, nullptr))
 		return 1;
 	HIP_TRY(hipMemcpyAsync(out_host, F->d_out, bytes, hipMemcpyDeviceToHost, nullptr));
+	HIP_TRY(hipStreamSynchronize(nullptr));
+	return 0;
+}
+
+// in == out with equal ld is legal as in the single apply: the first SpMM has left `in` behind when the second writes `out`
+int
+spmv_mi355x_fsai_apply_multi_device_async(spmv_mi355x_fsai * F, int k, const void * in_dev, long ldin, void * out_dev, long ldout,
+		void * hip_stream)
+{
+	if (!F || (F->n > 0 && (!in_dev || !out_dev)))
+	{
+		set_error("fsai_apply_multi: NULL argument (%s%s%s )", !F ? " F" : "", F && !in_dev ? " in" : "", F && !out_dev ? " out" : "");
+		return 1;
+	}
+	if (k < 1)
+	{
+		set_error("fsai_apply_multi: k = %d: at least one column is needed", k);
+		return 1;
+	}
+	if (ldin < k || ldout < k)
+	{
+		set_error("fsai_apply_multi: ldin = %ld, ldout = %ld: both must be >= k = %d", ldin, ldout, k);
+		return 1;
+	}
+	if (in_dev == out_dev && ldin != ldout)
+	{
+		set_error("fsai_apply_multi: in == out needs ldin == ldout (got %ld and %ld)", ldin, ldout);
+		return 1;
+	}
+	if (F->n == 0)
+		return 0;
+	if (k > F->multi_k)
+	{
+		// growing waits for whatever still reads the smaller block
+		HIP_TRY(hipDeviceSynchronize());
+		if (F->d_scratch_multi)
+			(void) hipFree(F->d_scratch_multi);
+		F->d_scratch_multi = nullptr;
+		F->multi_k = 0;
+		if (dev_alloc_bytes(&F->d_scratch_multi, (size_t) F->n * (size_t) k * (F->f32 ? 4 : 8)))
+			return 1;
+		F->multi_k = k;
+	}
+	if (spmv_mi355x_spmm_device_async(F->G, k, in_dev, ldin, F->d_scratch_multi, k, 0, hip_stream))
+		return 1;
+	return spmv_mi355x_spmm_device_async(F->Gt, k, F->d_scratch_multi, k, out_dev, ldout, 0, hip_stream);
+}
+
+int
+spmv_mi355x_fsai_apply_multi(spmv_mi355x_fsai * F, int k, const void * in_host, void * out_host)
+{
+	if (!F || (F->n > 0 && (!in_host || !out_host)))
+	{
+		set_error("fsai_apply_multi: NULL argument (%s%s%s )", !F ? " F" : "", F && !in_host ? " in" : "", F && !out_host ? " out" : "");
+		return 1;
+	}
+	if (k < 1)
+	{
+		set_error("fsai_apply_multi: k = %d: at least one column is needed", k);
+		return 1;
+	}
+	if (F->n == 0)
+		return 0;
+	HIP_TRY(hipSetDevice(F->device));
+	const size_t bytes = (size_t) F->n * (size_t) k * (F->f32 ? 4 : 8);
+	if (k > F->multi_host_k)
+	{
+		HIP_TRY(hipDeviceSynchronize());
+		for (void ** p : {&F->d_in_multi, &F->d_out_multi})
+		{
+			if (*p)
+				(void) hipFree(*p);
+			*p = nullptr;
+		}
+		F->multi_host_k = 0;
+		if (dev_alloc_bytes(&F->d_in_multi, bytes) || dev_alloc_bytes(&F->d_out_multi, bytes))
+			return 1;
+		F->multi_host_k = k;
+	}
+	HIP_TRY(hipMemcpyAsync(F->d_in_multi, in_host, bytes, hipMemcpyHostToDevice, nullptr));
+	if (spmv_mi355x_fsai_apply_multi_device_async(F, k, F->d_in_multi, k, F->d_out_multi, k, nullptr))
+		return 1;
+	HIP_TRY(hipMemcpyAsync(out_host, F->d_out_multi, bytes, hipMemcpyDeviceToHost, nullptr));
 	HIP_TRY(hipStreamSynchronize(nullptr));
 	return 0;
 }

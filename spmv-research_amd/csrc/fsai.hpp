@@ -61,4 +61,7 @@ struct spmv_mi355x_fsai {
 	spmv_mi355x_matrix * G = nullptr, * Gt = nullptr;     // both NULL when n == 0
 	void * d_scratch = nullptr;       // n values of the handle's precision: G in
 	void * d_in = nullptr, * d_out = nullptr;             // the vectors of the host-buffer apply, allocated at its first call
+	// apply_multi: n x multi_k values between the two SpMMs, and the blocks of the host-buffer form; they grow with the largest k seen
+	void * d_scratch_multi = nullptr, * d_in_multi = nullptr, * d_out_multi = nullptr;
+	int multi_k = 0, multi_host_k = 0;
 };

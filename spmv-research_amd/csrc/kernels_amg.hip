@@ -775,4 +775,182 @@ launch_amg_dense_solve(bool f32, const double * L, const void * b, void * x, int
 	return 0;
 }
 
+// ---- the cycle for k columns ---------------------------------------------------------------------------------------------------------
+// The three vector kernels and the dense solve for a chunk of KC in {8, 4, 2, 1} columns c0.. of row-major blocks (row i at ptr + i * ld).
+// A thread owns row i of its chunk: it reads w[i] once and KC contiguous values per block, as one vector load where the block's base,
+// its ld and c0 are multiples of KC. Per element the expressions are those of the single kernels above, so column j holds their bits.
+
+template <typename T, int KC>
+__device__ __forceinline__ bool
+amg_row_vec(const T * p, long ld, int c0)
+{
+	return ld % KC == 0 && c0 % KC == 0 && (size_t) p % (KC * sizeof(T)) == 0;
+}
+
+template <typename T, int KC>
+__global__ __launch_bounds__(VB) void
+amg_first_multi_kernel(const T * __restrict__ w, const T * __restrict__ b, long ldb, T * __restrict__ x, long ldx, int c0, long n)
+{
+	const bool vb = amg_row_vec<T, KC>(b, ldb, c0), vx = amg_row_vec<T, KC>(x, ldx, c0);
+	GRID_STRIDE(i, n)
+	{
+		const T wi = w[i];
+		T bv[KC], xv[KC];
+		load_row<T, KC>(bv, b + i * ldb + c0, vb);
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+			xv[c] = wi * bv[c];
+		store_row<T, KC>(x + i * ldx + c0, xv, vx);
+	}
+}
+
+// b and x may be the caller's blocks with their own ld; t is the hierarchy's
+template <typename T, int KC>
+__global__ __launch_bounds__(VB) void
+amg_sweep_multi_kernel(const T * __restrict__ w, const T * __restrict__ b, long ldb, const T * __restrict__ t, long ldt, T * __restrict__ x,
+		long ldx, int c0, long n)
+{
+	const bool vb = amg_row_vec<T, KC>(b, ldb, c0), vt = amg_row_vec<T, KC>(t, ldt, c0), vx = amg_row_vec<T, KC>(x, ldx, c0);
+	GRID_STRIDE(i, n)
+	{
+		const T wi = w[i];
+		T bv[KC], tv[KC], xv[KC];
+		load_row<T, KC>(bv, b + i * ldb + c0, vb);
+		load_row<T, KC>(tv, t + i * ldt + c0, vt);
+		load_row<T, KC>(xv, x + i * ldx + c0, vx);
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+			xv[c] = xv[c] + wi * (bv[c] - tv[c]);
+		store_row<T, KC>(x + i * ldx + c0, xv, vx);
+	}
+}
+
+template <typename T, int KC>
+__global__ __launch_bounds__(VB) void
+amg_residual_multi_kernel(const T * __restrict__ b, long ldb, T * __restrict__ t, long ldt, int c0, long n)
+{
+	const bool vb = amg_row_vec<T, KC>(b, ldb, c0), vt = amg_row_vec<T, KC>(t, ldt, c0);
+	GRID_STRIDE(i, n)
+	{
+		T bv[KC], tv[KC];
+		load_row<T, KC>(bv, b + i * ldb + c0, vb);
+		load_row<T, KC>(tv, t + i * ldt + c0, vt);
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+			tv[c] = bv[c] - tv[c];
+		store_row<T, KC>(t + i * ldt + c0, tv, vt);
+	}
+}
+
+// amg_dense_solve_kernel for the KC columns c0..: the packed factor goes into LDS once, lane a keeps y_a of every column in registers,
+// the lane of column k of L posts KC quotients, and there is still one barrier per column of L in each direction. Per column of the
+// block the division and the fma chain are the single kernel's.
+template <typename T, int KC>
+__global__ __launch_bounds__(AMG_DENSE_MAX) void
+amg_dense_solve_multi_kernel(const double * __restrict__ Lg, const T * __restrict__ b, long ldb, T * __restrict__ x, long ldx, int c0, int n)
+{
+	__shared__ double L[AMG_DENSE_MAX * (AMG_DENSE_MAX + 1) / 2];
+	__shared__ double piv[AMG_DENSE_MAX][KC];
+	const int a = threadIdx.x;
+	const int row = a * (a + 1) / 2;
+	for (int e = a; e < n * (n + 1) / 2; e += AMG_DENSE_MAX)
+		L[e] = Lg[e];
+	double y[KC];
+	#pragma unroll
+	for (int c = 0; c < KC; c++)
+		y[c] = a < n ? (double) b[(long) a * ldb + c0 + c] : 0.0;
+	__syncthreads();
+	for (int k = 0; k < n; k++)
+	{
+		if (a == k)
+		{
+			const double d = L[row + k];
+			#pragma unroll
+			for (int c = 0; c < KC; c++)
+				piv[k][c] = y[c] / d;
+		}
+		__syncthreads();
+		if (a > k && a < n)
+		{
+			const double l = L[row + k];
+			#pragma unroll
+			for (int c = 0; c < KC; c++)
+				y[c] = fma(-l, piv[k][c], y[c]);
+		}
+	}
+	#pragma unroll
+	for (int c = 0; c < KC; c++)
+		y[c] = a < n ? piv[a][c] : 0.0;
+	__syncthreads();
+	for (int k = n - 1; k >= 0; k--)
+	{
+		if (a == k)
+		{
+			const double d = L[row + k];
+			#pragma unroll
+			for (int c = 0; c < KC; c++)
+				piv[k][c] = y[c] / d;
+		}
+		__syncthreads();
+		if (a < k)
+		{
+			const double l = L[k * (k + 1) / 2 + a];
+			#pragma unroll
+			for (int c = 0; c < KC; c++)
+				y[c] = fma(-l, piv[k][c], y[c]);
+		}
+	}
+	if (a < n)
+	{
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+			x[(long) a * ldx + c0 + c] = (T) piv[a][c];
+	}
+}
+
+// one launch per chunk of k, in column order
+#define AMG_MULTI(kernel, grid, block, ...)                                                                                              \
+	if (n > 0)                                                                                                                           \
+		for_chunks(column_chunks(k), [&](int c0, auto kc) {                                                                              \
+			constexpr int KC = decltype(kc)::value;                                                                                      \
+			if (f32)                                                                                                                     \
+			{                                                                                                                            \
+				typedef float T;                                                                                                         \
+				hipLaunchKernelGGL((kernel<T, KC>), dim3(grid), dim3(block), 0, st, __VA_ARGS__);                                         \
+			}                                                                                                                            \
+			else                                                                                                                         \
+			{                                                                                                                            \
+				typedef double T;                                                                                                        \
+				hipLaunchKernelGGL((kernel<T, KC>), dim3(grid), dim3(block), 0, st, __VA_ARGS__);                                         \
+			}                                                                                                                            \
+			return 0;                                                                                                                    \
+		});                                                                                                                              \
+	HIP_TRY(hipGetLastError());                                                                                                          \
+	return 0
+
+int
+launch_amg_first_multi(bool f32, int k, const void * w, const void * b, long ldb, void * x, long ldx, long n, hipStream_t st)
+{
+	AMG_MULTI(amg_first_multi_kernel, solver_blocks(n), VB, (const T *) w, (const T *) b, ldb, (T *) x, ldx, c0, n);
+}
+
+int
+launch_amg_sweep_multi(bool f32, int k, const void * w, const void * b, long ldb, const void * t, long ldt, void * x, long ldx, long n,
+		hipStream_t st)
+{
+	AMG_MULTI(amg_sweep_multi_kernel, solver_blocks(n), VB, (const T *) w, (const T *) b, ldb, (const T *) t, ldt, (T *) x, ldx, c0, n);
+}
+
+int
+launch_amg_residual_multi(bool f32, int k, const void * b, long ldb, void * t, long ldt, long n, hipStream_t st)
+{
+	AMG_MULTI(amg_residual_multi_kernel, solver_blocks(n), VB, (const T *) b, ldb, (T *) t, ldt, c0, n);
+}
+
+int
+launch_amg_dense_solve_multi(bool f32, int k, const double * L, const void * b, long ldb, void * x, long ldx, int n, hipStream_t st)
+{
+	AMG_MULTI(amg_dense_solve_multi_kernel, 1, AMG_DENSE_MAX, L, (const T *) b, ldb, (T *) x, ldx, c0, n);
+}
+
 }  // namespace spmv

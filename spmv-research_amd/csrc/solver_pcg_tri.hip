@@ -439,6 +439,596 @@ struct AmgApply {
 	}
 };
 
+// ------------------------------------------------------------------------------------------------ k right-hand sides
+// spmv_mi355x_pcg_tri_multi / _pcg_fsai_multi / _pcg_amg_multi: k independent solves A x_j = b_j, each with the recurrences, stop rules
+// and freeze above, sharing one SpMM per SpMV of the single solve, the preconditioner's k-column apply and every launch. This is not
+// block CG. Every vector is a row-major n x k block (ld = k); a vector kernel serves a chunk of KC in {8, 4, 2, 1} columns c0.. and a
+// thread owns row i of its chunk (solvers_common.hpp). The state is PcgTriState[2][k], the partials are [k][PCG_TRI_SLOTS][MAX_PART].
+// BIT FOR BIT. Per column the grid, the rows per (block, thread), the shuffle tree and the order over the partials are the single
+// kernels', and every element update is the same T expression, so on a handle with a deterministic SpMV column j returns what the
+// single solve of b_j returns.
+// THE FREEZE PER COLUMN. Each column has its own `done`. A done column's x, r and p are stored back as loaded, its state is copied, its
+// partials and its history are not written; the SpMM and the preconditioner go on computing it into q, z and their own scratch. The
+// last chunk of pcg_tri_direction_multi posts progress: the loop count at which the last column stopped once every column is done.
+// Per iteration: 1 SpMM + M's own launches + 4 vector launches per chunk, 3 without a preconditioner (no z is stored then).
+
+static_assert((int) PCG_TRI_SLOTS == (int) NUM_SLOTS, "part_at() lays the partials out by NUM_SLOTS");
+
+template <int KC>
+__device__ __forceinline__ unsigned
+pcg_tri_live(const PcgTriState * __restrict__ st_p, int c0)
+{
+	unsigned live = 0;
+	#pragma unroll
+	for (int c = 0; c < KC; c++)
+		if (!st_p[c0 + c].done)
+			live |= 1u << c;
+	return live;
+}
+
+// pcg_tri_start_kernel for the chunk's columns
+template <typename T, int KC, bool PRE>
+__global__ __launch_bounds__(VB) void
+pcg_tri_start_multi_kernel(const T * __restrict__ b, T * __restrict__ r, T * __restrict__ p, T * __restrict__ x, long n, long ld, int c0,
+		double * __restrict__ part)
+{
+	const bool vec = ld % KC == 0 && c0 % KC == 0;
+	double bb[KC] = {};
+	GRID_STRIDE(i, n)
+	{
+		const long o = i * ld + c0;
+		T bv[KC], zero[KC];
+		load_row(bv, b + o, vec);
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+		{
+			zero[c] = 0;
+			bb[c] = fma((double) bv[c], (double) bv[c], bb[c]);
+		}
+		store_row(r + o, bv, vec);
+		store_row(x + o, zero, vec);
+		if (!PRE)
+			store_row(p + o, bv, vec);
+	}
+	store_partials_n<KC, 1>(part, c0, {T_BB}, bb, ~0u);
+}
+
+// 1 block: pcg_tri_init_state_kernel for the chunk's columns
+template <int KC>
+__global__ __launch_bounds__(VB) void
+pcg_tri_init_state_multi_kernel(PcgTriState * __restrict__ st_p, int k, int c0, int nb, const double * __restrict__ part)
+{
+	double bbv[KC];
+	sum_partials_n<KC, 1>(part, c0, {T_BB}, nb, bbv);
+	if (threadIdx.x == 0)
+	{
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+		{
+			const double bb = bbv[c];
+			PcgTriState st;
+			const bool bad = !(bb >= 0) || !(bb < INFINITY);
+			st.rnorm0 = bad ? 0 : sqrt(bb);
+			st.rz = bb;
+			st.rr = bb;
+			st.k = 0;
+			st.done = bad || bb == 0;
+			st.stop = bad ? 4 : bb == 0 ? 3 : 0;
+			st_p[c0 + c] = st;
+			st_p[k + c0 + c] = st;
+		}
+	}
+}
+
+// partials of u.v into `slot` for the chunk's live columns
+template <typename T, int KC>
+__global__ __launch_bounds__(VB) void
+pcg_tri_dot_multi_kernel(const PcgTriState * __restrict__ st_p, const T * __restrict__ u, const T * __restrict__ v, long n, long ld, int c0,
+		double * __restrict__ part, int slot)
+{
+	const unsigned live = pcg_tri_live<KC>(st_p, c0);
+	if (!live)
+		return;
+	const bool vec = ld % KC == 0 && c0 % KC == 0;
+	double s[KC] = {};
+	GRID_STRIDE(i, n)
+	{
+		const long o = i * ld + c0;
+		T uv[KC], vv[KC];
+		load_row(uv, u + o, vec);
+		load_row(vv, v + o, vec);
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+			s[c] = fma((double) uv[c], (double) vv[c], s[c]);
+	}
+	store_partials_n<KC, 1>(part, c0, {slot}, s, live);
+}
+
+// pcg_tri_begin_kernel for the chunk's columns: rz = r.z, p = z where rz is positive; block 0 writes the next states
+template <typename T, int KC>
+__global__ __launch_bounds__(VB) void
+pcg_tri_begin_multi_kernel(const PcgTriState * __restrict__ st_p, PcgTriState * __restrict__ st_next, T * __restrict__ p,
+		const T * __restrict__ z, long n, long ld, int c0, int nb, const double * __restrict__ part)
+{
+	const unsigned live = pcg_tri_live<KC>(st_p, c0);
+	const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
+	double rz[KC] = {};
+	unsigned ok = 0;
+	if (live)
+	{
+		sum_partials_n<KC, 1>(part, c0, {T_RZ}, nb, rz);
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+			if ((live >> c & 1) && pcg_tri_positive(rz[c]))
+				ok |= 1u << c;
+	}
+	if (ok)
+	{
+		const bool vec = ld % KC == 0 && c0 % KC == 0;
+		GRID_STRIDE(i, n)
+		{
+			const long o = i * ld + c0;
+			T pv[KC], zv[KC];
+			load_row(pv, p + o, vec);
+			load_row(zv, z + o, vec);
+			#pragma unroll
+			for (int c = 0; c < KC; c++)
+				if (ok >> c & 1)
+					pv[c] = zv[c];
+			store_row(p + o, pv, vec);
+		}
+	}
+	if (lead)
+	{
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+		{
+			PcgTriState nx = st_p[c0 + c];
+			if (live >> c & 1)
+			{
+				nx.rz = rz[c];
+				nx.stop = (ok >> c & 1) ? 0 : 4;
+				nx.done = !(ok >> c & 1);
+			}
+			st_next[c0 + c] = nx;
+		}
+	}
+}
+
+// pcg_tri_update_kernel for the chunk's columns: a column whose p.q is not positive is left as it is, like a done one
+template <typename T, int KC>
+__global__ __launch_bounds__(VB) void
+pcg_tri_update_multi_kernel(const PcgTriState * __restrict__ st_p, T * __restrict__ x, T * __restrict__ r, const T * __restrict__ p,
+		const T * __restrict__ q, long n, long ld, int c0, int nb, double * __restrict__ part)
+{
+	const unsigned live = pcg_tri_live<KC>(st_p, c0);
+	if (!live)
+		return;
+	double pq[KC];
+	sum_partials_n<KC, 1>(part, c0, {T_PQ}, nb, pq);
+	unsigned act = 0;
+	T alpha[KC];
+	#pragma unroll
+	for (int c = 0; c < KC; c++)
+	{
+		if ((live >> c & 1) && pcg_tri_positive(pq[c]))
+			act |= 1u << c;
+		alpha[c] = (T) (st_p[c0 + c].rz / pq[c]);
+	}
+	if (!act)
+		return;
+	const bool vec = ld % KC == 0 && c0 % KC == 0;
+	double rr[KC] = {};
+	GRID_STRIDE(i, n)
+	{
+		const long o = i * ld + c0;
+		T xv[KC], rv[KC], pv[KC], qv[KC];
+		load_row(xv, x + o, vec);
+		load_row(rv, r + o, vec);
+		load_row(pv, p + o, vec);
+		load_row(qv, q + o, vec);
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+		{
+			const T xi = xv[c] + alpha[c] * pv[c];
+			const T ri = rv[c] - alpha[c] * qv[c];
+			rr[c] = fma((double) ri, (double) ri, rr[c]);
+			if (act >> c & 1)
+			{
+				xv[c] = xi;
+				rv[c] = ri;
+			}
+		}
+		store_row(x + o, xv, vec);
+		store_row(r + o, rv, vec);
+	}
+	store_partials_n<KC, 1>(part, c0, {T_RR}, rr, act);
+}
+
+// (iterations finished, the loop count at which the last column stopped, or -1 while one runs) from the next states of all k columns:
+// the earlier chunks wrote theirs in earlier launches, this thread wrote its own chunk's
+__device__ __forceinline__ void
+pcg_tri_post_columns(const PcgTriState * st_next, int k, long it, volatile long * host_progress)
+{
+	long broke_at = 0;
+	for (int c = 0; c < k; c++)
+	{
+		if (!st_next[c].done)
+		{
+			broke_at = -1;
+			break;
+		}
+		broke_at = st_next[c].k > broke_at ? st_next[c].k : broke_at;
+	}
+	post_progress(host_progress, it + 1, broke_at);
+}
+
+// pcg_tri_direction_kernel for the chunk's columns; history row of column j at history + j * hist_ld. The last chunk posts progress.
+template <typename T, int KC, bool PRE>
+__global__ __launch_bounds__(VB) void
+pcg_tri_direction_multi_kernel(const PcgTriState * __restrict__ st_p, PcgTriState * __restrict__ st_next, T * __restrict__ p,
+		const T * __restrict__ z, long n, long ld, int c0, int k, int nb, double tol, const double * __restrict__ part,
+		double * __restrict__ history, long hist_ld, long it, volatile long * host_progress)
+{
+	const unsigned live = pcg_tri_live<KC>(st_p, c0);
+	const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
+	PcgTriState nx[KC];
+	double rnorm[KC] = {};
+	unsigned wrote = 0, go = 0;                       // columns that completed a body; columns whose p moves
+	T beta[KC];
+	#pragma unroll
+	for (int c = 0; c < KC; c++)
+	{
+		nx[c] = st_p[c0 + c];
+		beta[c] = 0;
+	}
+	if (live)
+	{
+		double sums[3 * KC];
+		sum_partials_n<KC, 3>(part, c0, {T_PQ, T_RR, T_RZ}, nb, sums);
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+		{
+			if (!(live >> c & 1))
+				continue;
+			if (!pcg_tri_positive(sums[c]))
+			{
+				nx[c].done = 1;                           // x, k and the history of the last good body
+				nx[c].stop = 4;
+				continue;
+			}
+			const double rr = sums[KC + c];
+			rnorm[c] = sqrt(rr);
+			wrote |= 1u << c;
+			nx[c].rr = rr;
+			nx[c].k = nx[c].k + 1;
+			if (tol > 0 && rnorm[c] <= tol * nx[c].rnorm0)
+				nx[c].stop = 1;
+			else if (rr == 0)
+				nx[c].stop = 5;
+			else
+			{
+				const double rz = PRE ? sums[2 * KC + c] : rr;
+				if (!pcg_tri_positive(rz))
+					nx[c].stop = 4;                           // this body's x is kept
+				else
+				{
+					beta[c] = (T) (rz / nx[c].rz);
+					nx[c].rz = rz;
+					go |= 1u << c;
+				}
+			}
+			nx[c].done = nx[c].stop != 0;
+		}
+	}
+	if (go)
+	{
+		const bool vec = ld % KC == 0 && c0 % KC == 0;
+		GRID_STRIDE(i, n)
+		{
+			const long o = i * ld + c0;
+			T pv[KC], zv[KC];
+			load_row(pv, p + o, vec);
+			load_row(zv, z + o, vec);
+			#pragma unroll
+			for (int c = 0; c < KC; c++)
+			{
+				const T pi = zv[c] + beta[c] * pv[c];
+				if (go >> c & 1)
+					pv[c] = pi;
+			}
+			store_row(p + o, pv, vec);
+		}
+	}
+	if (lead)
+	{
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+		{
+			if (history && (wrote >> c & 1))
+				history[(long) (c0 + c) * hist_ld + st_p[c0 + c].k] = rnorm[c];
+			st_next[c0 + c] = nx[c];
+		}
+		if (c0 + KC == k)
+			pcg_tri_post_columns(st_next, k, it, host_progress);
+	}
+}
+
+// pcg_tri_final_kernel for the chunk's columns
+template <typename T, int KC>
+__global__ __launch_bounds__(VB) void
+pcg_tri_final_multi_kernel(const T * __restrict__ b, T * __restrict__ q, const T * __restrict__ x, long n, long ld, int c0,
+		double * __restrict__ part)
+{
+	const bool vec = ld % KC == 0 && c0 % KC == 0;
+	double acc[2 * KC] = {};
+	GRID_STRIDE(i, n)
+	{
+		const long o = i * ld + c0;
+		T bv[KC], qv[KC], xv[KC];
+		load_row(bv, b + o, vec);
+		load_row(qv, q + o, vec);
+		load_row(xv, x + o, vec);
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+		{
+			const T ri = bv[c] - qv[c];
+			qv[c] = ri;
+			acc[c] = fma((double) ri, (double) ri, acc[c]);
+			acc[KC + c] = fma((double) xv[c], (double) xv[c], acc[KC + c]);
+		}
+		store_row(q + o, qv, vec);
+	}
+	store_partials_n<KC, 2>(part, c0, {T_ER, T_XX}, acc, ~0u);
+}
+
+// z = scale o r for the chunk's columns: tri_scale_kernel's product per element
+template <typename T, int KC>
+__global__ __launch_bounds__(VB) void
+pcg_tri_scale_multi_kernel(const T * __restrict__ scale, const T * __restrict__ in, T * __restrict__ out, long n, long ld, int c0)
+{
+	const bool vec = ld % KC == 0 && c0 % KC == 0;
+	GRID_STRIDE(i, n)
+	{
+		const long o = i * ld + c0;
+		const T si = scale[i];
+		T v[KC];
+		load_row(v, in + o, vec);
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+			v[c] = si * v[c];
+		store_row(out + o, v, vec);
+	}
+}
+
+// pcg_tri_solve for k columns. apply(r, z, scale, n, k, chunks, grid, stream) enqueues Z = M^-1 R on blocks with ld = k.
+template <typename T, bool PRE, typename Apply>
+static int
+pcg_tri_multi_solve(const char * what, spmv_mi355x_matrix * A, int k, const void * b_host, void * x_host, const void * scale_host,
+		Apply apply, double tol, long max_iterations, double * history_host, spmv_mi355x_pcg_tri_info * infos)
+{
+	const auto t_start = std::chrono::steady_clock::now();
+	const long n = spmv_mi355x_rows(A);
+	const long ld = k;
+	hipStream_t stream = nullptr;
+	ProgressGate gate;                // outlives buf, whose hipFree waits for the kernels that post to it
+	DeviceBuffers buf;
+	const size_t nbytes = (size_t) n * (size_t) k * sizeof(T);
+
+	T * b, * x, * r, * p, * q, * z = nullptr, * scale = nullptr;
+	for (T ** v : {&b, &x, &r, &p, &q})
+		ABI_TRY(buf.alloc(v, nbytes));
+	if (PRE)
+		ABI_TRY(buf.alloc(&z, nbytes));
+	if (scale_host)
+		ABI_TRY(buf.alloc(&scale, (size_t) n * sizeof(T)));
+	double * part, * history = nullptr;
+	PcgTriState * st;
+	const size_t part_bytes = sizeof(double) * (size_t) k * PCG_TRI_SLOTS * MAX_PART;
+	ABI_TRY(buf.alloc(&part, part_bytes));
+	ABI_TRY(buf.alloc(&st, 2 * (size_t) k * sizeof(PcgTriState)));
+	const size_t hist_bytes = sizeof(double) * (size_t) k * (size_t) max_iterations;
+	if (history_host && max_iterations > 0)
+	{
+		ABI_TRY(buf.alloc(&history, hist_bytes));
+		HIP_TRY(hipMemsetAsync(history, 0, hist_bytes, stream));
+	}
+	ABI_TRY(gate.init());
+
+	HIP_TRY(hipMemcpyAsync(b, b_host, nbytes, hipMemcpyHostToDevice, stream));
+	if (scale)
+		HIP_TRY(hipMemcpyAsync(scale, scale_host, (size_t) n * sizeof(T), hipMemcpyHostToDevice, stream));
+	HIP_TRY(hipMemsetAsync(part, 0, part_bytes, stream));
+
+	const int nb = solver_blocks(n);
+	const dim3 grid(nb), block(VB), one(1);
+	const std::vector<Chunk> chunks = column_chunks(k);
+	long spmm_calls = 0;
+	auto spmm = [&](const T * in, T * out) {
+		spmm_calls++;
+		return spmv_mi355x_spmm_device_async(A, k, in, ld, out, ld, 0, stream);
+	};
+	// the states of the moment are st[s & 1][0 .. k); every transition reads them, writes the other k and adds 1
+	long s = 0;
+	auto states = [&](long which) { return st + (which & 1) * (long) k; };
+	auto dot = [&](const T * u, const T * v, int slot) {
+		for_chunks(chunks, [&](int c0, auto kc) {
+			constexpr int KC = decltype(kc)::value;
+			hipLaunchKernelGGL((pcg_tri_dot_multi_kernel<T, KC>), grid, block, 0, stream, states(s), u, v, n, ld, c0, part, slot);
+			return 0;
+		});
+	};
+	// Z = M^-1 R and the partials of r.z
+	auto precondition = [&]() {
+		ABI_TRY(apply((const T *) r, z, (const T *) scale, n, k, chunks, grid, stream));
+		dot(r, z, (int) T_RZ);
+		return 0;
+	};
+
+	for_chunks(chunks, [&](int c0, auto kc) {
+		constexpr int KC = decltype(kc)::value;
+		hipLaunchKernelGGL((pcg_tri_start_multi_kernel<T, KC, PRE>), grid, block, 0, stream, b, r, p, x, n, ld, c0, part);
+		hipLaunchKernelGGL((pcg_tri_init_state_multi_kernel<KC>), one, block, 0, stream, st, k, c0, nb, part);
+		return 0;
+	});
+	if (PRE)
+	{
+		ABI_TRY(precondition());
+		for_chunks(chunks, [&](int c0, auto kc) {
+			constexpr int KC = decltype(kc)::value;
+			hipLaunchKernelGGL((pcg_tri_begin_multi_kernel<T, KC>), grid, block, 0, stream, states(s), states(s + 1), p, z, n, ld, c0, nb, part);
+			return 0;
+		});
+		s++;
+	}
+	HIP_TRY(hipGetLastError());
+
+	long it = 0;
+	for (; it < max_iterations; it++)
+	{
+		bool stop;
+		ABI_TRY(gate.wait(it, what, stream, &stop));
+		if (stop)
+			break;
+		ABI_TRY(spmm(p, q));
+		dot(p, q, (int) T_PQ);
+		for_chunks(chunks, [&](int c0, auto kc) {
+			constexpr int KC = decltype(kc)::value;
+			hipLaunchKernelGGL((pcg_tri_update_multi_kernel<T, KC>), grid, block, 0, stream, states(s), x, r, p, q, n, ld, c0, nb, part);
+			return 0;
+		});
+		if (PRE)
+			ABI_TRY(precondition());
+		for_chunks(chunks, [&](int c0, auto kc) {
+			constexpr int KC = decltype(kc)::value;
+			hipLaunchKernelGGL((pcg_tri_direction_multi_kernel<T, KC, PRE>), grid, block, 0, stream, states(s), states(s + 1), p,
+					PRE ? (const T *) z : (const T *) r, n, ld, c0, k, nb, tol, part, history, max_iterations, it, gate.dev);
+			return 0;
+		});
+		s++;
+	}
+	HIP_TRY(hipGetLastError());
+
+	// the explicit norms of the returned columns: one SpMM, q is free now
+	ABI_TRY(spmm(x, q));
+	for_chunks(chunks, [&](int c0, auto kc) {
+		constexpr int KC = decltype(kc)::value;
+		hipLaunchKernelGGL((pcg_tri_final_multi_kernel<T, KC>), grid, block, 0, stream, b, q, x, n, ld, c0, part);
+		return 0;
+	});
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(x_host, x, nbytes, hipMemcpyDeviceToHost, stream));
+	std::vector<PcgTriState> st_host((size_t) k);
+	std::vector<double> part_host((size_t) k * PCG_TRI_SLOTS * MAX_PART);
+	HIP_TRY(hipMemcpyAsync(st_host.data(), states(s), (size_t) k * sizeof(PcgTriState), hipMemcpyDeviceToHost, stream));
+	HIP_TRY(hipMemcpyAsync(part_host.data(), part, part_bytes, hipMemcpyDeviceToHost, stream));
+	if (history)
+		HIP_TRY(hipMemcpyAsync(history_host, history, hist_bytes, hipMemcpyDeviceToHost, stream));
+	HIP_TRY(hipStreamSynchronize(stream));
+	if (infos)
+	{
+		const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
+		for (int j = 0; j < k; j++)
+		{
+			auto norm_of = [&](int slot) { return std::sqrt(host_sum(part_host.data(), (size_t) part_at(j, slot), nb)); };
+			spmv_mi355x_pcg_tri_info out;
+			memset(&out, 0, sizeof(out));
+			out.iterations = st_host[(size_t) j].k;
+			out.stop = st_host[(size_t) j].done ? st_host[(size_t) j].stop : 2;
+			out.rnorm = norm_of(T_ER);
+			out.rnorm0 = norm_of(T_BB);
+			out.prnorm = std::sqrt(st_host[(size_t) j].rr);
+			out.xnorm = norm_of(T_XX);
+			out.spmv_calls = spmm_calls;
+			out.seconds = seconds;
+			put_info(infos + j, infos[j].struct_size, out);
+		}
+	}
+	return 0;
+}
+
+// pcg_tri_arguments_ok for k columns: its checks in its order and wording, with k < 1 first and every info's struct_size. `tri`: M
+// of pcg_tri_multi has a triangular part, which needs no handle to see.
+static bool
+pcg_tri_multi_arguments_ok(const char * what, spmv_mi355x_matrix * A, int k, const void * b_host, void * x_out_host, double tol,
+		long max_iterations, const spmv_mi355x_pcg_tri_info * infos, bool tri)
+{
+	if (k < 1)
+	{
+		set_error("%s: k = %d: at least one right-hand side is needed", what, k);
+		return false;
+	}
+	for (int j = 0; infos && j < k; j++)
+		if (infos[j].struct_size < 8)
+		{
+			set_error("%s: infos[%d].struct_size not set", what, j);
+			return false;
+		}
+	if (!(tol >= 0) || !std::isfinite(tol))
+	{
+		set_error("%s: tol must be finite and >= 0 (got %g)", what, tol);
+		return false;
+	}
+	if (max_iterations < 0)
+	{
+		set_error("%s: max_iterations < 0", what);
+		return false;
+	}
+	if (tri)
+	{
+		set_error("%s: M has a triangular part (first or second): there is no k-column triangular solve, only M = NULL or a scale alone "
+				"is served; solve the columns one by one with spmv_mi355x_pcg_tri", what);
+		return false;
+	}
+	if (!A || !b_host || !x_out_host)
+	{
+		set_error("%s: NULL argument (%s%s%s )", what, !A ? " A" : "", !b_host ? " B" : "", !x_out_host ? " X_out" : "");
+		return false;
+	}
+	const long m = spmv_mi355x_rows(A), n = spmv_mi355x_cols(A);
+	if (m != n)
+	{
+		set_error("%s: the matrix must be square and symmetric positive definite: the handle is %ld x %ld (a row block of a "
+				"larger matrix is not served)", what, m, n);
+		return false;
+	}
+	return true;
+}
+
+// Z = scale o R: the Jacobi scale of pcg_tri_multi
+struct ScaleApplyMulti {
+	template <typename T>
+	int operator()(const T * r, T * z, const T * scale, long n, int k, const std::vector<Chunk> & chunks, dim3 grid, hipStream_t stream) const
+	{
+		for_chunks(chunks, [&](int c0, auto kc) {
+			constexpr int KC = decltype(kc)::value;
+			hipLaunchKernelGGL((pcg_tri_scale_multi_kernel<T, KC>), grid, dim3(VB), 0, stream, scale, r, z, n, (long) k, c0);
+			return 0;
+		});
+		return 0;
+	}
+};
+
+// Z = G^t (G R): the two SpMMs write the fsai handle's scratch block and z
+struct FsaiApplyMulti {
+	spmv_mi355x_fsai * F;
+	template <typename T>
+	int operator()(const T * r, T * z, const T *, long, int k, const std::vector<Chunk> &, dim3, hipStream_t stream) const
+	{
+		return spmv_mi355x_fsai_apply_multi_device_async(F, k, r, k, z, k, stream);
+	}
+};
+
+// one V cycle for the k columns: it writes the hierarchy's own blocks and z
+struct AmgApplyMulti {
+	spmv_mi355x_amg * M;
+	template <typename T>
+	int operator()(const T * r, T * z, const T *, long, int k, const std::vector<Chunk> &, dim3, hipStream_t stream) const
+	{
+		return spmv_mi355x_amg_apply_multi_device_async(M, k, r, k, z, k, stream);
+	}
+};
+
 }  // namespace spmv
 
 extern "C" int
@@ -526,4 +1116,99 @@ spmv_mi355x_pcg_amg(spmv_mi355x_matrix * A, const void * b_host, void * x_out_ho
 	if (precision == SPMV_MI355X_F32)
 		return pcg_tri_solve<float, true>("pcg_amg", A, b_host, x_out_host, nullptr, apply, tol, max_iterations, history_out, info);
 	return pcg_tri_solve<double, true>("pcg_amg", A, b_host, x_out_host, nullptr, apply, tol, max_iterations, history_out, info);
+}
+
+extern "C" int
+spmv_mi355x_pcg_tri_multi(spmv_mi355x_matrix * A, int k, const void * B_host, void * X_out_host, const spmv_mi355x_tri_precond * M,
+		double tol, long max_iterations, double * history_out, spmv_mi355x_pcg_tri_info * infos)
+{
+	using namespace spmv;
+	const bool sized = M && M->struct_size >= sizeof(spmv_mi355x_tri_precond);
+	if (!pcg_tri_multi_arguments_ok("pcg_tri_multi", A, k, B_host, X_out_host, tol, max_iterations, infos,
+			sized && (M->first || M->second)))
+		return 1;
+	const long n = spmv_mi355x_cols(A);
+	const int precision = spmv_mi355x_precision(A), device = spmv_mi355x_device(A);
+	if (M && (!tri_precond_size_ok("pcg_tri_multi", M) || !tri_precond_parts_ok("pcg_tri_multi", M, n, precision, device)))
+		return 1;
+	const void * scale = M ? M->scale_host : nullptr;
+	HIP_TRY(hipSetDevice(device));
+	const ScaleApplyMulti apply;
+	if (precision == SPMV_MI355X_F32)
+		return scale ? pcg_tri_multi_solve<float, true>("pcg_tri_multi", A, k, B_host, X_out_host, scale, apply, tol, max_iterations,
+				               history_out, infos)
+		             : pcg_tri_multi_solve<float, false>("pcg_tri_multi", A, k, B_host, X_out_host, nullptr, apply, tol, max_iterations,
+				               history_out, infos);
+	return scale ? pcg_tri_multi_solve<double, true>("pcg_tri_multi", A, k, B_host, X_out_host, scale, apply, tol, max_iterations,
+			               history_out, infos)
+	             : pcg_tri_multi_solve<double, false>("pcg_tri_multi", A, k, B_host, X_out_host, nullptr, apply, tol, max_iterations,
+			               history_out, infos);
+}
+
+extern "C" int
+spmv_mi355x_pcg_fsai_multi(spmv_mi355x_matrix * A, int k, const void * B_host, void * X_out_host, spmv_mi355x_fsai * F, double tol,
+		long max_iterations, double * history_out, spmv_mi355x_pcg_tri_info * infos)
+{
+	using namespace spmv;
+	if (!pcg_tri_multi_arguments_ok("pcg_fsai_multi", A, k, B_host, X_out_host, tol, max_iterations, infos, false))
+		return 1;
+	if (!F)
+	{
+		set_error("pcg_fsai_multi: F is NULL: spmv_mi355x_pcg_tri_multi with M = NULL is the solve without a preconditioner");
+		return 1;
+	}
+	const long n = spmv_mi355x_cols(A);
+	const int precision = spmv_mi355x_precision(A), device = spmv_mi355x_device(A);
+	if (F->n != n)
+		set_error("pcg_fsai_multi: F is a preconditioner of %ld rows, the matrix has %ld", F->n, n);
+	else if (F->precision != precision)
+		set_error("pcg_fsai_multi: F has precision %d, the matrix %d: both must be the same", F->precision, precision);
+	else if (F->device != device)
+		set_error("pcg_fsai_multi: F lives on device %d, the matrix on device %d", F->device, device);
+	if (F->n != n || F->precision != precision || F->device != device)
+		return 1;
+	HIP_TRY(hipSetDevice(device));
+	const FsaiApplyMulti apply = {F};
+	if (precision == SPMV_MI355X_F32)
+		return pcg_tri_multi_solve<float, true>("pcg_fsai_multi", A, k, B_host, X_out_host, nullptr, apply, tol, max_iterations, history_out,
+				infos);
+	return pcg_tri_multi_solve<double, true>("pcg_fsai_multi", A, k, B_host, X_out_host, nullptr, apply, tol, max_iterations, history_out,
+			infos);
+}
+
+extern "C" int
+spmv_mi355x_pcg_amg_multi(spmv_mi355x_matrix * A, int k, const void * B_host, void * X_out_host, spmv_mi355x_amg * M, double tol,
+		long max_iterations, double * history_out, spmv_mi355x_pcg_tri_info * infos)
+{
+	using namespace spmv;
+	if (!pcg_tri_multi_arguments_ok("pcg_amg_multi", A, k, B_host, X_out_host, tol, max_iterations, infos, false))
+		return 1;
+	if (!M)
+	{
+		set_error("pcg_amg_multi: M is NULL: spmv_mi355x_pcg_tri_multi with M = NULL is the solve without a preconditioner");
+		return 1;
+	}
+	const long n = spmv_mi355x_cols(A);
+	const int precision = spmv_mi355x_precision(A), device = spmv_mi355x_device(A);
+	if (M->n != n)
+		set_error("pcg_amg_multi: M is a preconditioner of %ld rows, the matrix has %ld", M->n, n);
+	else if (M->precision != precision)
+		set_error("pcg_amg_multi: M has precision %d, the matrix %d: both must be the same", M->precision, precision);
+	else if (M->device != device)
+		set_error("pcg_amg_multi: M lives on device %d, the matrix on device %d", M->device, device);
+	if (M->n != n || M->precision != precision || M->device != device)
+		return 1;
+	if (M->update_failed)
+	{
+		set_error("pcg_amg_multi: the last amg_update_values of M failed below level 0 and left it half rewritten: update it with values "
+				"it accepts first");
+		return 1;
+	}
+	HIP_TRY(hipSetDevice(device));
+	const AmgApplyMulti apply = {M};
+	if (precision == SPMV_MI355X_F32)
+		return pcg_tri_multi_solve<float, true>("pcg_amg_multi", A, k, B_host, X_out_host, nullptr, apply, tol, max_iterations, history_out,
+				infos);
+	return pcg_tri_multi_solve<double, true>("pcg_amg_multi", A, k, B_host, X_out_host, nullptr, apply, tol, max_iterations, history_out,
+			infos);
 }

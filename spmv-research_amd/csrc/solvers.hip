@@ -53,131 +53,6 @@
 
 namespace spmv {
 
-constexpr int MAX_KC = 8;          // columns per chunk
-
-// block_sum() for N values at once: each value goes through the same shuffle tree and the same in-order sum of the
-// VB / WAVE wave partials, behind one set of barriers.
-template <int N>
-__device__ __forceinline__ void
-block_sum_n(double * v)
-{
-	__shared__ double sh[N][VB / WAVE];
-	__shared__ double total[N];
-	#pragma unroll
-	for (int c = 0; c < N; c++)
-		for (int o = WAVE / 2; o > 0; o >>= 1)
-			v[c] += __shfl_down(v[c], o, WAVE);
-	__syncthreads();                       // protects sh/total against the previous call
-	if (threadIdx.x % WAVE == 0)
-	{
-		#pragma unroll
-		for (int c = 0; c < N; c++)
-			sh[c][threadIdx.x / WAVE] = v[c];
-	}
-	__syncthreads();
-	if (threadIdx.x < N)
-	{
-		double s = 0;
-		for (int w = 0; w < VB / WAVE; w++)
-			s += sh[threadIdx.x][w];
-		total[threadIdx.x] = s;
-	}
-	__syncthreads();
-	#pragma unroll
-	for (int c = 0; c < N; c++)
-		v[c] = total[c];
-}
-
-__host__ __device__ __forceinline__ long
-part_at(int col, int slot)
-{
-	return ((long) col * NUM_SLOTS + slot) * MAX_PART;
-}
-
-// sum_partials() of S slots for the KC columns c0.. : out[s * KC + c]
-template <int KC, int S>
-__device__ __forceinline__ void
-sum_partials_n(const double * __restrict__ part, int c0, const int (&slot)[S], int nb, double * out)
-{
-	#pragma unroll
-	for (int s = 0; s < S; s++)
-	{
-		#pragma unroll
-		for (int c = 0; c < KC; c++)
-		{
-			const double * p = part + part_at(c0 + c, slot[s]);
-			double v = 0;
-			for (int i = threadIdx.x; i < nb; i += VB)
-				v += p[i];
-			out[s * KC + c] = v;
-		}
-	}
-	block_sum_n<S * KC>(out);
-}
-
-// store_partial() of S slots for the KC columns c0.. from v[s * KC + c]; only the columns in `keep` are written
-template <int KC, int S>
-__device__ __forceinline__ void
-store_partials_n(double * __restrict__ part, int c0, const int (&slot)[S], double * v, unsigned keep)
-{
-	block_sum_n<S * KC>(v);
-	if (threadIdx.x == 0)
-	{
-		#pragma unroll
-		for (int s = 0; s < S; s++)
-		{
-			#pragma unroll
-			for (int c = 0; c < KC; c++)
-				if (keep >> c & 1)
-					part[part_at(c0 + c, slot[s]) + blockIdx.x] = v[s * KC + c];
-		}
-	}
-}
-
-// KC contiguous values of one row; `vec` (uniform) when the row start is KC-aligned
-template <typename T, int KC>
-__device__ __forceinline__ void
-load_row(T (&o)[KC], const T * p, bool vec)
-{
-	if constexpr (KC > 1)
-	{
-		if (vec)
-		{
-			typedef T V __attribute__((ext_vector_type(KC)));
-			const V t = *(const V *) p;
-			#pragma unroll
-			for (int c = 0; c < KC; c++)
-				o[c] = t[c];
-			return;
-		}
-	}
-	#pragma unroll
-	for (int c = 0; c < KC; c++)
-		o[c] = p[c];
-}
-
-template <typename T, int KC>
-__device__ __forceinline__ void
-store_row(T * p, const T (&o)[KC], bool vec)
-{
-	if constexpr (KC > 1)
-	{
-		if (vec)
-		{
-			typedef T V __attribute__((ext_vector_type(KC)));
-			V t;
-			#pragma unroll
-			for (int c = 0; c < KC; c++)
-				t[c] = o[c];
-			*(V *) p = t;
-			return;
-		}
-	}
-	#pragma unroll
-	for (int c = 0; c < KC; c++)
-		p[c] = o[c];
-}
-
 // the columns of the chunk that have not reached the `err < eps` break
 template <int KC>
 __device__ __forceinline__ unsigned
@@ -761,48 +636,6 @@ scatter_slots_kernel(double * __restrict__ part, SlotList sl, const double * __r
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-
-struct Chunk {
-	int c0, kc;
-};
-
-// k = 8s, then the binary remainder (the SpMM's column passes)
-static std::vector<Chunk>
-column_chunks(int k)
-{
-	std::vector<Chunk> out;
-	int c0 = 0;
-	for (; k - c0 >= MAX_KC; c0 += MAX_KC)
-		out.push_back({c0, MAX_KC});
-	for (int w = MAX_KC / 2; w >= 1; w /= 2)
-		if (k - c0 >= w)
-		{
-			out.push_back({c0, w});
-			c0 += w;
-		}
-	return out;
-}
-
-// f(c0, std::integral_constant<int, KC>) for every chunk, in column order; stops at the first f that returns nonzero
-template <typename F>
-static int
-for_chunks(const std::vector<Chunk> & chunks, F && f)
-{
-	for (const Chunk & ch : chunks)
-	{
-		int rc;
-		switch (ch.kc)
-		{
-		case 8: rc = f(ch.c0, std::integral_constant<int, 8>()); break;
-		case 4: rc = f(ch.c0, std::integral_constant<int, 4>()); break;
-		case 2: rc = f(ch.c0, std::integral_constant<int, 2>()); break;
-		default: rc = f(ch.c0, std::integral_constant<int, 1>()); break;
-		}
-		if (rc)
-			return rc;
-	}
-	return 0;
-}
 
 // The one solve behind all six entry points. `multi`: the _multi entries, whose matrix product is the SpMM for every k
 // (1 included) and whose messages carry `what`; the single entries (k = 1) use the SpMV and, with `dist` (row-partitioned,

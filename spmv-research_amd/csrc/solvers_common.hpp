@@ -1,12 +1,14 @@
 // What the Krylov solvers (solvers.hip, solver_cgls.hip, solver_minres.hip, solver_gmres.hip) share. Device side: the launch
 // shape of the vector kernels, the device state, the deterministic two-stage dot products, the post to the host progress word, the
-// explicit-residual decision. Host side: the device buffer owner, the Jacobi diagonal, and the run-ahead driver of every solve loop
-// (solver_blocks, ProgressGate, info_size_ok / put_info, host_sum).
+// explicit-residual decision, the k-column forms of the reductions and the row loads. Host side: the device buffer owner, the Jacobi
+// diagonal, the split of k columns into chunks, and the run-ahead driver of every solve loop (solver_blocks, ProgressGate,
+// info_size_ok / put_info, host_sum).
 #pragma once
 
 #include <algorithm>
 #include <chrono>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "common.hpp"
@@ -68,6 +70,135 @@ store_partial(double * __restrict__ part, int slot, double v)
 	v = block_sum(v);
 	if (threadIdx.x == 0)
 		part[(long) slot * MAX_PART + blockIdx.x] = v;
+}
+
+// ---- k columns at once (solvers.hip, the k-column solve of solver_pcg_tri.hip, the k-column cycle of kernels_amg.hip): a vector kernel serves a chunk
+// of KC in {8, 4, 2, 1} columns of a row-major block, and every per-column dot product goes through the additions of block_sum /
+// sum_partials / store_partial in their order, so a column returns the bits of the single-vector kernels whatever chunk it sits in.
+
+constexpr int MAX_KC = 8;          // columns per chunk
+
+// block_sum() for N values at once: each value goes through the same shuffle tree and the same in-order sum of the
+// VB / WAVE wave partials, behind one set of barriers.
+template <int N>
+__device__ __forceinline__ void
+block_sum_n(double * v)
+{
+	__shared__ double sh[N][VB / WAVE];
+	__shared__ double total[N];
+	#pragma unroll
+	for (int c = 0; c < N; c++)
+		for (int o = WAVE / 2; o > 0; o >>= 1)
+			v[c] += __shfl_down(v[c], o, WAVE);
+	__syncthreads();                       // protects sh/total against the previous call
+	if (threadIdx.x % WAVE == 0)
+	{
+		#pragma unroll
+		for (int c = 0; c < N; c++)
+			sh[c][threadIdx.x / WAVE] = v[c];
+	}
+	__syncthreads();
+	if (threadIdx.x < N)
+	{
+		double s = 0;
+		for (int w = 0; w < VB / WAVE; w++)
+			s += sh[threadIdx.x][w];
+		total[threadIdx.x] = s;
+	}
+	__syncthreads();
+	#pragma unroll
+	for (int c = 0; c < N; c++)
+		v[c] = total[c];
+}
+
+__host__ __device__ __forceinline__ long
+part_at(int col, int slot)
+{
+	return ((long) col * NUM_SLOTS + slot) * MAX_PART;
+}
+
+// sum_partials() of S slots for the KC columns c0.. : out[s * KC + c]
+template <int KC, int S>
+__device__ __forceinline__ void
+sum_partials_n(const double * __restrict__ part, int c0, const int (&slot)[S], int nb, double * out)
+{
+	#pragma unroll
+	for (int s = 0; s < S; s++)
+	{
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+		{
+			const double * p = part + part_at(c0 + c, slot[s]);
+			double v = 0;
+			for (int i = threadIdx.x; i < nb; i += VB)
+				v += p[i];
+			out[s * KC + c] = v;
+		}
+	}
+	block_sum_n<S * KC>(out);
+}
+
+// store_partial() of S slots for the KC columns c0.. from v[s * KC + c]; only the columns in `keep` are written
+template <int KC, int S>
+__device__ __forceinline__ void
+store_partials_n(double * __restrict__ part, int c0, const int (&slot)[S], double * v, unsigned keep)
+{
+	block_sum_n<S * KC>(v);
+	if (threadIdx.x == 0)
+	{
+		#pragma unroll
+		for (int s = 0; s < S; s++)
+		{
+			#pragma unroll
+			for (int c = 0; c < KC; c++)
+				if (keep >> c & 1)
+					part[part_at(c0 + c, slot[s]) + blockIdx.x] = v[s * KC + c];
+		}
+	}
+}
+
+// KC contiguous values of one row; `vec` (uniform) when the row start is KC-aligned
+template <typename T, int KC>
+__device__ __forceinline__ void
+load_row(T (&o)[KC], const T * p, bool vec)
+{
+	if constexpr (KC > 1)
+	{
+		if (vec)
+		{
+			typedef T V __attribute__((ext_vector_type(KC)));
+			const V t = *(const V *) p;
+			#pragma unroll
+			for (int c = 0; c < KC; c++)
+				o[c] = t[c];
+			return;
+		}
+	}
+	#pragma unroll
+	for (int c = 0; c < KC; c++)
+		o[c] = p[c];
+}
+
+template <typename T, int KC>
+__device__ __forceinline__ void
+store_row(T * p, const T (&o)[KC], bool vec)
+{
+	if constexpr (KC > 1)
+	{
+		if (vec)
+		{
+			typedef T V __attribute__((ext_vector_type(KC)));
+			V t;
+			#pragma unroll
+			for (int c = 0; c < KC; c++)
+				t[c] = o[c];
+			*(V *) p = t;
+			return;
+		}
+	}
+	#pragma unroll
+	for (int c = 0; c < KC; c++)
+		p[c] = o[c];
 }
 
 // (iterations the device has finished, loop count at the break or -1) for the host (ProgressGate below), in host-mapped pinned memory
@@ -151,6 +282,48 @@ inline int
 solver_blocks(long len)
 {
 	return (int) std::min<long>(MAX_PART, std::max<long>(1, (len + 4 * VB - 1) / (4 * VB)));
+}
+
+struct Chunk {
+	int c0, kc;
+};
+
+// k = 8s, then the binary remainder (the SpMM's column passes)
+inline std::vector<Chunk>
+column_chunks(int k)
+{
+	std::vector<Chunk> out;
+	int c0 = 0;
+	for (; k - c0 >= MAX_KC; c0 += MAX_KC)
+		out.push_back({c0, MAX_KC});
+	for (int w = MAX_KC / 2; w >= 1; w /= 2)
+		if (k - c0 >= w)
+		{
+			out.push_back({c0, w});
+			c0 += w;
+		}
+	return out;
+}
+
+// f(c0, std::integral_constant<int, KC>) for every chunk, in column order; stops at the first f that returns nonzero
+template <typename F>
+inline int
+for_chunks(const std::vector<Chunk> & chunks, F && f)
+{
+	for (const Chunk & ch : chunks)
+	{
+		int rc;
+		switch (ch.kc)
+		{
+		case 8: rc = f(ch.c0, std::integral_constant<int, 8>()); break;
+		case 4: rc = f(ch.c0, std::integral_constant<int, 4>()); break;
+		case 2: rc = f(ch.c0, std::integral_constant<int, 2>()); break;
+		default: rc = f(ch.c0, std::integral_constant<int, 1>()); break;
+		}
+		if (rc)
+			return rc;
+	}
+	return 0;
 }
 
 // The progress word that post_progress() writes, and the gate that keeps the enqueueing host at most 2*POLL iterations ahead of

@@ -77,6 +77,9 @@ SYMBOLS = [
     "spmv_mi355x_amg_update_values_prepare", "spmv_mi355x_amg_update_values", "spmv_mi355x_amg_update_values_device",
     "spmv_mi355x_amg_update_values_state", "spmv_mi355x_amg_update_info",
     "spmv_mi355x_amg_create_with", "spmv_mi355x_amg_prolongator_info", "spmv_mi355x_amg_near_null",
+    "spmv_mi355x_amg_apply_multi_device_async", "spmv_mi355x_amg_apply_multi", "spmv_mi355x_amg_apply_multi_plan",
+    "spmv_mi355x_fsai_apply_multi_device_async", "spmv_mi355x_fsai_apply_multi",
+    "spmv_mi355x_pcg_tri_multi", "spmv_mi355x_pcg_fsai_multi", "spmv_mi355x_pcg_amg_multi",
 ]
 
 _lib = None
@@ -139,6 +142,21 @@ def lib():
         L.spmv_mi355x_amg_update_values_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.spmv_mi355x_amg_update_info.restype = C.c_int
         L.spmv_mi355x_amg_update_info.argtypes = [C.c_void_p, C.c_void_p]
+        for f in ("spmv_mi355x_amg_apply_multi_device_async", "spmv_mi355x_fsai_apply_multi_device_async"):
+            getattr(L, f).restype = C.c_int
+            getattr(L, f).argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_void_p]
+        for f in ("spmv_mi355x_amg_apply_multi", "spmv_mi355x_fsai_apply_multi"):
+            getattr(L, f).restype = C.c_int
+            getattr(L, f).argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.spmv_mi355x_amg_apply_multi_plan.restype = C.c_int
+        L.spmv_mi355x_amg_apply_multi_plan.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_long), C.POINTER(C.c_long)]
+        L.spmv_mi355x_pcg_tri_multi.restype = C.c_int
+        L.spmv_mi355x_pcg_tri_multi.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(TriPrecond), C.c_double, C.c_long,
+                                                C.c_void_p, C.c_void_p]
+        for f in ("spmv_mi355x_pcg_fsai_multi", "spmv_mi355x_pcg_amg_multi"):
+            getattr(L, f).restype = C.c_int
+            getattr(L, f).argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_long, C.c_void_p,
+                                      C.c_void_p]
         _lib = L
     return _lib
 
@@ -474,6 +492,21 @@ class Fsai:
         """The same on device pointers (in_ptr == out_ptr: in place), enqueued on `stream` (spmv_mi355x_fsai_apply_device_async)"""
         _check(lib().spmv_mi355x_fsai_apply_device_async(self.h, C.c_void_p(in_ptr), C.c_void_p(out_ptr), C.c_void_p(stream or 0)))
 
+    def apply_multi(self, V):
+        """G^t (G V) for the k columns of a host block of shape (n, k) (spmv_mi355x_fsai_apply_multi; blocking): column j holds the
+        bits of apply(V[:, j]) on a deterministic layout"""
+        V = np.ascontiguousarray(V, self.dtype)
+        if V.ndim != 2 or V.shape[0] != self.n or V.shape[1] < 1:
+            raise ValueError(f"V must have shape ({self.n}, k) with k >= 1, got {V.shape}")
+        out = np.zeros(V.shape, self.dtype)
+        _check(lib().spmv_mi355x_fsai_apply_multi(self.h, V.shape[1], _p(V), _p(out)))
+        return out
+
+    def apply_multi_device(self, k, in_ptr, ldin, out_ptr, ldout, stream=None):
+        """The same on device blocks, row i at ptr + i * ld values (in_ptr == out_ptr with ldin == ldout: in place), enqueued on
+        `stream` (spmv_mi355x_fsai_apply_multi_device_async)"""
+        _check(lib().spmv_mi355x_fsai_apply_multi_device_async(self.h, k, in_ptr, ldin, out_ptr, ldout, stream or 0))
+
     def close(self):
         if getattr(self, "h", None) is not None and self.h:
             for M in (self.G, self.Gt):
@@ -656,6 +689,27 @@ class Amg:
     def apply_device(self, in_ptr, out_ptr, stream=None):
         """The same on device pointers (in_ptr == out_ptr: in place), enqueued on `stream` (spmv_mi355x_amg_apply_device_async)"""
         _check(lib().spmv_mi355x_amg_apply_device_async(self.h, C.c_void_p(in_ptr), C.c_void_p(out_ptr), C.c_void_p(stream or 0)))
+
+    def apply_multi(self, V):
+        """one cycle M^-1 V for the k columns of a host block of shape (n, k) (spmv_mi355x_amg_apply_multi; blocking): column j holds
+        the bits of apply(V[:, j]) on a deterministic layout"""
+        V = np.ascontiguousarray(V, self.dtype)
+        if V.ndim != 2 or V.shape[0] != self.n or V.shape[1] < 1:
+            raise ValueError(f"V must have shape ({self.n}, k) with k >= 1, got {V.shape}")
+        out = np.zeros(V.shape, self.dtype)
+        _check(lib().spmv_mi355x_amg_apply_multi(self.h, V.shape[1], _p(V), _p(out)))
+        return out
+
+    def apply_multi_device(self, k, in_ptr, ldin, out_ptr, ldout, stream=None):
+        """The same on device blocks, row i at ptr + i * ld values (in_ptr == out_ptr with ldin == ldout: in place), enqueued on
+        `stream` (spmv_mi355x_amg_apply_multi_device_async)"""
+        _check(lib().spmv_mi355x_amg_apply_multi_device_async(self.h, k, in_ptr, ldin, out_ptr, ldout, stream or 0))
+
+    def apply_multi_plan(self, k):
+        """(matrix passes, launches) of one k-column cycle (spmv_mi355x_amg_apply_multi_plan; touches no device)"""
+        passes, launches = C.c_long(0), C.c_long(0)
+        _check(lib().spmv_mi355x_amg_apply_multi_plan(self.h, k, C.byref(passes), C.byref(launches)))
+        return passes.value, launches.value
 
     def update_values_prepare(self):
         """once, before the first update_values: keeps the SpGEMM plans, the aggregates and the value arrays of every level on the
@@ -1303,6 +1357,38 @@ class Matrix:
         out = {k: getattr(info, k) for k, _ in PcgTriInfo._fields_ if k != "struct_size"}
         out["x"] = x[:self.m]
         out["history"] = hist[:info.iterations] if history else None
+        return out
+
+    def pcg_tri_multi(self, B, precond=None, tol=1e-12, max_iterations=1000, history=True):
+        """pcg_tri for the k columns of B (shape (rows, k)) in one solve with one SpMM per iteration (spmv_mi355x_pcg_tri_multi,
+        _pcg_fsai_multi, _pcg_amg_multi): a list of k dicts shaped like pcg_tri's, element j bit-identical to pcg_tri(B[:, j], precond)
+        on a deterministic handle; spmv_calls and seconds are the call's. `precond` is None, (None, scale, None), an Fsai or an Amg;
+        one with a TriangularSolve part raises the library's refusal (there is no k-column triangular solve)."""
+        B = np.ascontiguousarray(B, self.dtype)
+        if B.ndim != 2 or B.shape[0] != self.m or B.shape[1] < 1:
+            raise ValueError(f"B must have shape ({self.m}, k) with k >= 1, got {B.shape}")
+        k = B.shape[1]
+        X = np.zeros((max(self.m, 1), k), self.dtype)
+        hist = np.zeros(k * max(max_iterations, 1), np.float64) if history else None
+        infos = (PcgTriInfo * k)()
+        for j in range(k):
+            infos[j].struct_size = C.sizeof(PcgTriInfo)
+        hp = _p(hist) if history else None
+        if isinstance(precond, (Fsai, Amg)):
+            solve = lib().spmv_mi355x_pcg_fsai_multi if isinstance(precond, Fsai) else lib().spmv_mi355x_pcg_amg_multi
+            _check(solve(self.h, k, _p(B), _p(X), precond.h, tol, max_iterations, hp, infos))
+        else:
+            M = None
+            if precond is not None:
+                M, scale = _tri_precond(precond, self.m, self.dtype)
+            _check(lib().spmv_mi355x_pcg_tri_multi(self.h, k, _p(B), _p(X), None if M is None else C.byref(M), tol, max_iterations, hp,
+                                                   infos))
+        out = []
+        for j in range(k):
+            d = {f: getattr(infos[j], f) for f, _ in PcgTriInfo._fields_ if f != "struct_size"}
+            d["x"] = X[:self.m, j].copy()
+            d["history"] = hist[j * max_iterations:j * max_iterations + d["iterations"]].copy() if history else None
+            out.append(d)
         return out
 
     def close(self):

@@ -1125,7 +1125,8 @@ int  spmv_mi355x_amg_near_null(const spmv_mi355x_amg * M, int level, double * ou
  * 1 to 5, the breakdown rules and the freeze of spmv_mi355x_pcg_tri. What the columns share is one spmv_mi355x_spmm_device_async per
  * SpMV of the single call, every launch, and every pass over A_l, R_l and P_l of a hierarchy.
  * THE CONTRACT of every call below: on handles whose SpMV is deterministic, column j returns the bits of the single-vector call on
- * column j. No single-vector entry point goes through these kernels.
+ * column j. No single-vector entry point goes through the SpMM or a k-column apply; the vector kernels of the solve are one set, of
+ * which the single-vector solve is k = 1.
  * Every k-column block is row-major: row i at ptr + i * ld, ld >= k counted in values of the handle's precision.
  *   - amg_apply_multi_device_async: out = M^-1 in for the k columns, the schedule of amg_apply_device_async with every SpMV as one
  *     SpMM (beta = 1 for the prolongation) and every vector launch as one launch per chunk of 8, 4, 2 or 1 columns (k = 8s, then the

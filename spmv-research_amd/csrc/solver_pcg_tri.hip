@@ -14,29 +14,44 @@
 // Built like solver_minres.hip: the state ping-pongs between two slots, dots are two-stage and deterministic (every block of the
 // consumer re-sums the partials in the same order), a device `done` flag predicates every later vector kernel off, and the host
 // loop is ProgressGate of solvers_common.hpp.
-// Per iteration: 1 SpMV + M's own launches + 4 vector launches, 3 without a preconditioner
+//
+// ONE BODY, SIX ENTRIES. spmv_mi355x_pcg_tri / _pcg_fsai / _pcg_amg and their _multi forms all run pcg_tri_solve over k columns: k
+// independent solves A x_j = b_j, each with the recurrences, stop rules and freeze of this comment, sharing every launch. This is not
+// block CG. The single entries are k = 1. Every vector is a row-major n x k block (ld = k); a vector kernel serves a chunk of KC in
+// {8, 4, 2, 1} columns c0.. and a thread owns row i of its chunk (solvers_common.hpp). The state is PcgTriState[2][k], the partials
+// are [k][PCG_TRI_SLOTS][MAX_PART], the history row of column j starts at j * max_iterations. An entry passes in the two things that
+// differ:
+//   the matrix product q = A p   SpmvProduct (the single entries) or SpmmProduct (the _multi entries, also for k = 1)
+//   enqueue z = M^-1 r           TriApply (pcg_tri: the three parts of tri_precond.hpp on an n x 1 block, so triangular parts are served
+//                                for k = 1 only), ScaleApplyMulti (pcg_tri_multi: a Jacobi scale), FsaiApply / FsaiApplyMulti (the two
+//                                SpMVs or SpMMs G^t (G r) of an fsai handle, fsai.hip), AmgApply / AmgApplyMulti (one V cycle of an amg
+//                                handle, amg.hip)
+// so a single solve uses neither the SpMM nor a k-column apply, which are other kernels and allocate k-column blocks of their own.
+// BIT FOR BIT. Per column the grid, the rows per (block, thread), the shuffle tree and the order over the partials do not depend on the
+// chunk a column sits in, and every element update is the same T expression, so on a handle with a deterministic SpMV column j of a
+// _multi call returns what the single call on b_j returns.
+//
+// Per iteration: 1 SpMV (SpMM) + M's own launches + 4 vector launches per chunk, 3 without a preconditioner
 //   q = A p | pcg_tri_dot (partials of p.q) | pcg_tri_update (alpha; x += alpha p; r -= alpha q; partials of r.r) |
-//   [ z = M^-1 r: first, tri_scale_kernel, second (tri_precond.hpp) | pcg_tri_dot (partials of r.z) ] |
+//   [ z = M^-1 r | pcg_tri_dot (partials of r.z) ] |
 //   pcg_tri_direction (the verdicts, beta, the next state, the history row, the progress word; p = z + beta p).
+// pcg_fsai: 3 SpMVs (A, G, G^t) and the 4 vector launches.
 // Without a preconditioner z is r: no z is stored, nothing is launched for it and rz' is the rr of pcg_tri_update, so
 // precond = (NULL, ones, NULL) returns the bits of precond = NULL.
 // A cut with fewer launches would have to form a dot product and consume it in the same launch, which needs a grid-wide barrier:
 // p.q must be complete before alpha, r.r (and r.z) before beta. Three reductions with their consumers are four launches.
-// Stored vectors, n values each: b, x, r, p, q, and z when M has a part; the scale when given.
+// Stored blocks, n x k values each: b, x, r, p, q, and z when M has a part; the scale (n values) when given.
 //
-// BREAKDOWN of p.q. pcg_tri_update reaches the verdict in every block from the same partials and touches no vector;
-// pcg_tri_direction, the only kernel that writes the state, re-sums the same partials, reaches the same verdict and records
+// BREAKDOWN of p.q. pcg_tri_update reaches the verdict in every block from the same partials and leaves the column's vectors as they
+// are; pcg_tri_direction, the only kernel that writes the state, re-sums the same partials, reaches the same verdict and records
 // done / stop 4 with k unchanged.
 //
-// THE FREEZE. The SpMV, the triangular solves and the scale kernel know nothing of `done` and run however far the host is ahead;
-// what they write is q and z, scratch that only the predicated kernels read. x, r, p, the state and the history are written only
-// by kernels that return at once when `done` is set. So after a stop nothing the caller sees moves.
-//
-// THREE ENTRIES, ONE BODY. pcg_tri_solve takes "enqueue z = M^-1 r" as a callable: TriApply (spmv_mi355x_pcg_tri: tri_precond.hpp's
-// three parts) or FsaiApply (spmv_mi355x_pcg_fsai: the two SpMVs G^t (G r) of an fsai handle, fsai.hip). The freeze carries over:
-// the two SpMVs know nothing of `done` either, and what they write is the fsai handle's scratch vector and z. Per iteration of
-// pcg_fsai: 3 SpMVs (A, G, G^t) and the 4 vector launches. AmgApply (spmv_mi355x_pcg_amg: one V cycle of an amg handle, amg.hip) is
-// the third: the cycle's SpMVs and vector kernels write the hierarchy's own vectors and z, so the freeze holds for it as well.
+// THE FREEZE, PER COLUMN. The matrix product and the preconditioner (triangular solves, scale kernel, the SpMVs of an fsai apply, the
+// SpMVs and vector kernels of an amg cycle) know nothing of `done` and run however far the host is ahead; what they write is q, z and
+// the preconditioner handle's own scratch, which only the predicated kernels read. Each column has its own `done`: a done column's
+// x, r and p are stored back as loaded, its state is copied, its partials and its history are not written. So after a stop nothing
+// the caller sees of that column moves. The last chunk of pcg_tri_direction posts progress: the loop count at which the last column
+// stopped once every column is done.
 
 #include <chrono>
 #include <cmath>
@@ -72,386 +87,6 @@ pcg_tri_positive(double v)
 	return v > 0 && v < INFINITY;
 }
 
-// r = b; x = 0; without a preconditioner also p = b; partial BB = b.b
-template <typename T, bool PRE>
-__global__ __launch_bounds__(VB) void
-pcg_tri_start_kernel(const T * __restrict__ b, T * __restrict__ r, T * __restrict__ p, T * __restrict__ x, long n,
-		double * __restrict__ part)
-{
-	double bb = 0;
-	GRID_STRIDE(i, n)
-	{
-		const T bi = b[i];
-		r[i] = bi;
-		x[i] = 0;
-		if (!PRE)
-			p[i] = bi;
-		bb = fma((double) bi, (double) bi, bb);
-	}
-	store_partial(part, T_BB, bb);
-}
-
-// 1 block. b.b == 0: x = 0 is the solution (stop 3); not finite: stop 4. Without a preconditioner rz = b.b.
-__global__ __launch_bounds__(VB) void
-pcg_tri_init_state_kernel(PcgTriState * __restrict__ st_p, int nb, const double * __restrict__ part)
-{
-	const double bb = sum_partials(part, T_BB, nb);
-	if (threadIdx.x == 0)
-	{
-		PcgTriState st;
-		const bool bad = !(bb >= 0) || !(bb < INFINITY);
-		st.rnorm0 = bad ? 0 : sqrt(bb);
-		st.rz = bb;
-		st.rr = bb;
-		st.k = 0;
-		st.done = bad || bb == 0;
-		st.stop = bad ? 4 : bb == 0 ? 3 : 0;
-		st_p[0] = st;
-		st_p[1] = st;
-	}
-}
-
-// partial of u.v into `slot`: p.q, and r.z under a preconditioner
-template <typename T>
-__global__ __launch_bounds__(VB) void
-pcg_tri_dot_kernel(const PcgTriState * __restrict__ st_p, const T * __restrict__ u, const T * __restrict__ v, long n,
-		double * __restrict__ part, int slot)
-{
-	if (st_p->done)
-		return;
-	double s = 0;
-	GRID_STRIDE(i, n)
-		s = fma((double) u[i], (double) v[i], s);
-	store_partial(part, slot, s);
-}
-
-// With a preconditioner, the start: rz = r.z from the partials, p = z. Block 0 writes the next state (stop 4: rz not positive).
-template <typename T>
-__global__ __launch_bounds__(VB) void
-pcg_tri_begin_kernel(const PcgTriState * __restrict__ st_p, PcgTriState * __restrict__ st_next, T * __restrict__ p,
-		const T * __restrict__ z, long n, int nb, const double * __restrict__ part)
-{
-	const PcgTriState st = *st_p;
-	if (st.done)
-	{
-		if (blockIdx.x == 0 && threadIdx.x == 0)
-			*st_next = st;
-		return;
-	}
-	const double rz = sum_partials(part, T_RZ, nb);
-	const bool ok = pcg_tri_positive(rz);
-	if (ok)
-		GRID_STRIDE(i, n)
-			p[i] = z[i];
-	if (blockIdx.x == 0 && threadIdx.x == 0)
-	{
-		PcgTriState nx = st;
-		nx.rz = rz;
-		nx.stop = ok ? 0 : 4;
-		nx.done = !ok;
-		*st_next = nx;
-	}
-}
-
-// alpha = rz / (p.q) identically in every block; x += alpha p; r -= alpha q; partial RR = r.r. p.q not positive: nothing is touched.
-template <typename T>
-__global__ __launch_bounds__(VB) void
-pcg_tri_update_kernel(const PcgTriState * __restrict__ st_p, T * __restrict__ x, T * __restrict__ r, const T * __restrict__ p,
-		const T * __restrict__ q, long n, int nb, double * __restrict__ part)
-{
-	const PcgTriState st = *st_p;
-	if (st.done)
-		return;
-	const double pq = sum_partials(part, T_PQ, nb);
-	if (!pcg_tri_positive(pq))
-		return;
-	const T alpha = (T) (st.rz / pq);
-	double rr = 0;
-	GRID_STRIDE(i, n)
-	{
-		x[i] = x[i] + alpha * p[i];
-		const T ri = r[i] - alpha * q[i];
-		r[i] = ri;
-		rr = fma((double) ri, (double) ri, rr);
-	}
-	store_partial(part, T_RR, rr);
-}
-
-// The verdicts of the body, identically in every block; p = z + beta p (z = r without a preconditioner) when the solve goes on.
-// Block 0 writes the next state, the history row and the progress word.
-template <typename T, bool PRE>
-__global__ __launch_bounds__(VB) void
-pcg_tri_direction_kernel(const PcgTriState * __restrict__ st_p, PcgTriState * __restrict__ st_next, T * __restrict__ p,
-		const T * __restrict__ z, long n, int nb, double tol, const double * __restrict__ part, double * __restrict__ history,
-		long it, volatile long * host_progress)
-{
-	const PcgTriState st = *st_p;
-	const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
-	if (st.done)
-	{
-		if (lead)
-		{
-			*st_next = st;
-			post_progress(host_progress, it + 1, st.k);
-		}
-		return;
-	}
-	PcgTriState nx = st;
-	if (!pcg_tri_positive(sum_partials(part, T_PQ, nb)))
-	{
-		if (lead)
-		{
-			nx.done = 1;                              // x, k and the history of the last good body
-			nx.stop = 4;
-			*st_next = nx;
-			post_progress(host_progress, it + 1, nx.k);
-		}
-		return;
-	}
-	const double rr = sum_partials(part, T_RR, nb);
-	const double rnorm = sqrt(rr);
-	nx.rr = rr;
-	nx.k = st.k + 1;
-	if (tol > 0 && rnorm <= tol * st.rnorm0)
-		nx.stop = 1;
-	else if (rr == 0)
-		nx.stop = 5;
-	else
-	{
-		const double rz = PRE ? sum_partials(part, T_RZ, nb) : rr;
-		if (!pcg_tri_positive(rz))
-			nx.stop = 4;                              // this body's x is kept
-		else
-		{
-			const T beta = (T) (rz / st.rz);
-			nx.rz = rz;
-			GRID_STRIDE(i, n)
-				p[i] = z[i] + beta * p[i];
-		}
-	}
-	if (lead)
-	{
-		if (history)
-			history[st.k] = rnorm;
-		nx.done = nx.stop != 0;
-		*st_next = nx;
-		post_progress(host_progress, it + 1, nx.done ? nx.k : -1);
-	}
-}
-
-// the tail's explicit residual: q = b - q (q = A x); partials ER = |b - A x|^2 and XX = |x|^2
-template <typename T>
-__global__ __launch_bounds__(VB) void
-pcg_tri_final_kernel(const T * __restrict__ b, T * __restrict__ q, const T * __restrict__ x, long n, double * __restrict__ part)
-{
-	double rr = 0, xx = 0;
-	GRID_STRIDE(i, n)
-	{
-		const T xi = x[i];
-		const T ri = b[i] - q[i];
-		q[i] = ri;
-		rr = fma((double) ri, (double) ri, rr);
-		xx = fma((double) xi, (double) xi, xx);
-	}
-	store_partial(part, T_ER, rr);
-	store_partial(part, T_XX, xx);
-}
-
-// ------------------------------------------------------------------------------------------------ host side
-
-// PRE: there is a preconditioner. scale_host: the scale of M or NULL; the solve keeps its device copy. apply(r, z, scale, n, grid,
-// stream) enqueues z = M^-1 r on the stream and returns 0 or 1 (error set): the triangular parts of pcg_tri, the two SpMVs of
-// pcg_fsai. It is never called without PRE. `what` names the caller in the gate's message.
-template <typename T, bool PRE, typename Apply>
-static int
-pcg_tri_solve(const char * what, spmv_mi355x_matrix * A, const void * b_host, void * x_host, const void * scale_host, Apply apply,
-		double tol, long max_iterations, double * history_host, spmv_mi355x_pcg_tri_info * info)
-{
-	const auto t_start = std::chrono::steady_clock::now();
-	const long n = spmv_mi355x_rows(A);
-	hipStream_t stream = nullptr;
-	ProgressGate gate;                // outlives buf, whose hipFree waits for the kernels that post to it
-	DeviceBuffers buf;
-	const size_t nbytes = (size_t) n * sizeof(T);
-
-	// plain allocations, the SpMV output included: see solve() in solvers.hip
-	T * b, * x, * r, * p, * q, * z = nullptr, * scale = nullptr;
-	for (T ** v : {&b, &x, &r, &p, &q})
-		ABI_TRY(buf.alloc(v, nbytes));
-	if (PRE)
-		ABI_TRY(buf.alloc(&z, nbytes));
-	if (scale_host)
-		ABI_TRY(buf.alloc(&scale, nbytes));
-	double * part, * history = nullptr;
-	PcgTriState * st;
-	ABI_TRY(buf.alloc(&part, sizeof(double) * PCG_TRI_SLOTS * MAX_PART));
-	ABI_TRY(buf.alloc(&st, 2 * sizeof(PcgTriState)));
-	const size_t hist_bytes = sizeof(double) * (size_t) max_iterations;
-	if (history_host && max_iterations > 0)
-	{
-		ABI_TRY(buf.alloc(&history, hist_bytes));
-		HIP_TRY(hipMemsetAsync(history, 0, hist_bytes, stream));
-	}
-	ABI_TRY(gate.init());
-
-	HIP_TRY(hipMemcpyAsync(b, b_host, nbytes, hipMemcpyHostToDevice, stream));
-	if (scale)
-		HIP_TRY(hipMemcpyAsync(scale, scale_host, nbytes, hipMemcpyHostToDevice, stream));
-	HIP_TRY(hipMemsetAsync(part, 0, sizeof(double) * PCG_TRI_SLOTS * MAX_PART, stream));
-
-	const int nb = solver_blocks(n);
-	const dim3 grid(nb), block(VB), one(1);
-	long spmv_calls = 0;
-	auto spmv = [&](const T * in, T * out) {
-		spmv_calls++;
-		return spmv_mi355x_spmv_device_async(A, in, out, 0, stream);
-	};
-	// the state of the moment is st[s & 1]; every transition (the start under a preconditioner, a loop body) reads it, writes the
-	// other slot and adds 1
-	long s = 0;
-	// z = M^-1 r and the partials of r.z
-	auto precondition = [&]() {
-		ABI_TRY(apply((const T *) r, z, (const T *) scale, n, grid, stream));
-		hipLaunchKernelGGL((pcg_tri_dot_kernel<T>), grid, block, 0, stream, st + (s & 1), r, z, n, part, (int) T_RZ);
-		return 0;
-	};
-
-	hipLaunchKernelGGL((pcg_tri_start_kernel<T, PRE>), grid, block, 0, stream, b, r, p, x, n, part);
-	hipLaunchKernelGGL(pcg_tri_init_state_kernel, one, block, 0, stream, st, nb, part);
-	if (PRE)
-	{
-		ABI_TRY(precondition());
-		hipLaunchKernelGGL((pcg_tri_begin_kernel<T>), grid, block, 0, stream, st + (s & 1), st + ((s + 1) & 1), p, z, n, nb, part);
-		s++;
-	}
-	HIP_TRY(hipGetLastError());
-
-	long it = 0;
-	for (; it < max_iterations; it++)
-	{
-		bool stop;
-		ABI_TRY(gate.wait(it, what, stream, &stop));
-		if (stop)
-			break;
-		PcgTriState * cur = st + (s & 1), * nxt = st + ((s + 1) & 1);
-		ABI_TRY(spmv(p, q));
-		hipLaunchKernelGGL((pcg_tri_dot_kernel<T>), grid, block, 0, stream, cur, p, q, n, part, (int) T_PQ);
-		hipLaunchKernelGGL((pcg_tri_update_kernel<T>), grid, block, 0, stream, cur, x, r, p, q, n, nb, part);
-		if (PRE)
-			ABI_TRY(precondition());
-		hipLaunchKernelGGL((pcg_tri_direction_kernel<T, PRE>), grid, block, 0, stream, cur, nxt, p, PRE ? z : r, n, nb, tol, part,
-				history, it, gate.dev);
-		s++;
-	}
-	HIP_TRY(hipGetLastError());
-
-	// the explicit norms of the returned x: |b - A x| and |x|. q is free now; x stays as it froze.
-	PcgTriState * fin = st + (s & 1);
-	ABI_TRY(spmv(x, q));
-	hipLaunchKernelGGL((pcg_tri_final_kernel<T>), grid, block, 0, stream, b, q, x, n, part);
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipMemcpyAsync(x_host, x, nbytes, hipMemcpyDeviceToHost, stream));
-	PcgTriState st_host;
-	std::vector<double> part_host((size_t) PCG_TRI_SLOTS * MAX_PART);
-	HIP_TRY(hipMemcpyAsync(&st_host, fin, sizeof(PcgTriState), hipMemcpyDeviceToHost, stream));
-	HIP_TRY(hipMemcpyAsync(part_host.data(), part, sizeof(double) * PCG_TRI_SLOTS * MAX_PART, hipMemcpyDeviceToHost, stream));
-	if (history)
-		HIP_TRY(hipMemcpyAsync(history_host, history, hist_bytes, hipMemcpyDeviceToHost, stream));
-	HIP_TRY(hipStreamSynchronize(stream));
-	if (info)
-	{
-		auto norm_of = [&](int slot) { return std::sqrt(host_sum(part_host.data(), (size_t) slot * MAX_PART, nb)); };
-		spmv_mi355x_pcg_tri_info out;
-		memset(&out, 0, sizeof(out));
-		out.iterations = st_host.k;
-		out.stop = st_host.done ? st_host.stop : 2;
-		out.rnorm = norm_of(T_ER);
-		out.rnorm0 = norm_of(T_BB);
-		out.prnorm = std::sqrt(st_host.rr);
-		out.xnorm = norm_of(T_XX);
-		out.spmv_calls = spmv_calls;
-		out.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
-		put_info(info, info->struct_size, out);
-	}
-	return 0;
-}
-
-// the checks of both entries that need no preconditioner: items 1 to 5 of the header, with the caller's name as the prefix
-static bool
-pcg_tri_arguments_ok(const char * what, spmv_mi355x_matrix * A, const void * b_host, void * x_out_host, double tol, long max_iterations,
-		const spmv_mi355x_pcg_tri_info * info)
-{
-	// the checks that need no handle come first, so each can be met (and tested) on its own
-	if (!info_size_ok(what, info))
-		return false;
-	if (!(tol >= 0) || !std::isfinite(tol))
-	{
-		set_error("%s: tol must be finite and >= 0 (got %g)", what, tol);
-		return false;
-	}
-	if (max_iterations < 0)
-	{
-		set_error("%s: max_iterations < 0", what);
-		return false;
-	}
-	if (!A || !b_host || !x_out_host)
-	{
-		set_error("%s: NULL argument (%s%s%s )", what, !A ? " A" : "", !b_host ? " b" : "", !x_out_host ? " x_out" : "");
-		return false;
-	}
-	const long m = spmv_mi355x_rows(A), n = spmv_mi355x_cols(A);
-	if (m != n)
-	{
-		set_error("%s: the matrix must be square and symmetric positive definite: the handle is %ld x %ld (a row block of a "
-				"larger matrix is not served)", what, m, n);
-		return false;
-	}
-	return true;
-}
-
-// z = M^-1 r of pcg_tri: second^-1 (scale o (first^-1 r)), tri_precond.hpp
-struct TriApply {
-	spmv_mi355x_trsv * first, * second;
-	template <typename T>
-	int operator()(const T * r, T * z, const T * scale, long n, dim3 grid, hipStream_t stream) const
-	{
-		return tri_precond_enqueue<T>(first, scale, second, r, z, n, false, grid, stream);
-	}
-};
-
-// z = M^-1 r of pcg_fsai: G^t (G r). The two SpMVs write the handle's scratch vector and z, nothing else.
-struct FsaiApply {
-	spmv_mi355x_fsai * F;
-	template <typename T>
-	int operator()(const T * r, T * z, const T *, long, dim3, hipStream_t stream) const
-	{
-		return spmv_mi355x_fsai_apply_device_async(F, r, z, stream);
-	}
-};
-
-// z = M^-1 r of pcg_amg: one V cycle of an amg handle. Its SpMVs and vector kernels write the hierarchy's own vectors and z, nothing else.
-struct AmgApply {
-	spmv_mi355x_amg * M;
-	template <typename T>
-	int operator()(const T * r, T * z, const T *, long, dim3, hipStream_t stream) const
-	{
-		return spmv_mi355x_amg_apply_device_async(M, r, z, stream);
-	}
-};
-
-// ------------------------------------------------------------------------------------------------ k right-hand sides
-// spmv_mi355x_pcg_tri_multi / _pcg_fsai_multi / _pcg_amg_multi: k independent solves A x_j = b_j, each with the recurrences, stop rules
-// and freeze above, sharing one SpMM per SpMV of the single solve, the preconditioner's k-column apply and every launch. This is not
-// block CG. Every vector is a row-major n x k block (ld = k); a vector kernel serves a chunk of KC in {8, 4, 2, 1} columns c0.. and a
-// thread owns row i of its chunk (solvers_common.hpp). The state is PcgTriState[2][k], the partials are [k][PCG_TRI_SLOTS][MAX_PART].
-// BIT FOR BIT. Per column the grid, the rows per (block, thread), the shuffle tree and the order over the partials are the single
-// kernels', and every element update is the same T expression, so on a handle with a deterministic SpMV column j returns what the
-// single solve of b_j returns.
-// THE FREEZE PER COLUMN. Each column has its own `done`. A done column's x, r and p are stored back as loaded, its state is copied, its
-// partials and its history are not written; the SpMM and the preconditioner go on computing it into q, z and their own scratch. The
-// last chunk of pcg_tri_direction_multi posts progress: the loop count at which the last column stopped once every column is done.
-// Per iteration: 1 SpMM + M's own launches + 4 vector launches per chunk, 3 without a preconditioner (no z is stored then).
-
 static_assert((int) PCG_TRI_SLOTS == (int) NUM_SLOTS, "part_at() lays the partials out by NUM_SLOTS");
 
 template <int KC>
@@ -466,10 +101,10 @@ pcg_tri_live(const PcgTriState * __restrict__ st_p, int c0)
 	return live;
 }
 
-// pcg_tri_start_kernel for the chunk's columns
+// r = b; x = 0; without a preconditioner also p = b; partial BB = b.b
 template <typename T, int KC, bool PRE>
 __global__ __launch_bounds__(VB) void
-pcg_tri_start_multi_kernel(const T * __restrict__ b, T * __restrict__ r, T * __restrict__ p, T * __restrict__ x, long n, long ld, int c0,
+pcg_tri_start_kernel(const T * __restrict__ b, T * __restrict__ r, T * __restrict__ p, T * __restrict__ x, long n, long ld, int c0,
 		double * __restrict__ part)
 {
 	const bool vec = ld % KC == 0 && c0 % KC == 0;
@@ -493,10 +128,10 @@ pcg_tri_start_multi_kernel(const T * __restrict__ b, T * __restrict__ r, T * __r
 	store_partials_n<KC, 1>(part, c0, {T_BB}, bb, ~0u);
 }
 
-// 1 block: pcg_tri_init_state_kernel for the chunk's columns
+// 1 block. b.b == 0: x = 0 is the solution (stop 3); not finite: stop 4. Without a preconditioner rz = b.b.
 template <int KC>
 __global__ __launch_bounds__(VB) void
-pcg_tri_init_state_multi_kernel(PcgTriState * __restrict__ st_p, int k, int c0, int nb, const double * __restrict__ part)
+pcg_tri_init_state_kernel(PcgTriState * __restrict__ st_p, int k, int c0, int nb, const double * __restrict__ part)
 {
 	double bbv[KC];
 	sum_partials_n<KC, 1>(part, c0, {T_BB}, nb, bbv);
@@ -520,10 +155,10 @@ pcg_tri_init_state_multi_kernel(PcgTriState * __restrict__ st_p, int k, int c0, 
 	}
 }
 
-// partials of u.v into `slot` for the chunk's live columns
+// partials of u.v into `slot` for the chunk's live columns: p.q, and r.z under a preconditioner
 template <typename T, int KC>
 __global__ __launch_bounds__(VB) void
-pcg_tri_dot_multi_kernel(const PcgTriState * __restrict__ st_p, const T * __restrict__ u, const T * __restrict__ v, long n, long ld, int c0,
+pcg_tri_dot_kernel(const PcgTriState * __restrict__ st_p, const T * __restrict__ u, const T * __restrict__ v, long n, long ld, int c0,
 		double * __restrict__ part, int slot)
 {
 	const unsigned live = pcg_tri_live<KC>(st_p, c0);
@@ -544,10 +179,11 @@ pcg_tri_dot_multi_kernel(const PcgTriState * __restrict__ st_p, const T * __rest
 	store_partials_n<KC, 1>(part, c0, {slot}, s, live);
 }
 
-// pcg_tri_begin_kernel for the chunk's columns: rz = r.z, p = z where rz is positive; block 0 writes the next states
+// With a preconditioner, the start: rz = r.z from the partials, p = z where rz is positive. Block 0 writes the next states (stop 4:
+// rz not positive).
 template <typename T, int KC>
 __global__ __launch_bounds__(VB) void
-pcg_tri_begin_multi_kernel(const PcgTriState * __restrict__ st_p, PcgTriState * __restrict__ st_next, T * __restrict__ p,
+pcg_tri_begin_kernel(const PcgTriState * __restrict__ st_p, PcgTriState * __restrict__ st_next, T * __restrict__ p,
 		const T * __restrict__ z, long n, long ld, int c0, int nb, const double * __restrict__ part)
 {
 	const unsigned live = pcg_tri_live<KC>(st_p, c0);
@@ -595,10 +231,11 @@ pcg_tri_begin_multi_kernel(const PcgTriState * __restrict__ st_p, PcgTriState * 
 	}
 }
 
-// pcg_tri_update_kernel for the chunk's columns: a column whose p.q is not positive is left as it is, like a done one
+// alpha = rz / (p.q) identically in every block; x += alpha p; r -= alpha q; partial RR = r.r. A column whose p.q is not positive is
+// left as it is, like a done one.
 template <typename T, int KC>
 __global__ __launch_bounds__(VB) void
-pcg_tri_update_multi_kernel(const PcgTriState * __restrict__ st_p, T * __restrict__ x, T * __restrict__ r, const T * __restrict__ p,
+pcg_tri_update_kernel(const PcgTriState * __restrict__ st_p, T * __restrict__ x, T * __restrict__ r, const T * __restrict__ p,
 		const T * __restrict__ q, long n, long ld, int c0, int nb, double * __restrict__ part)
 {
 	const unsigned live = pcg_tri_live<KC>(st_p, c0);
@@ -663,10 +300,11 @@ pcg_tri_post_columns(const PcgTriState * st_next, int k, long it, volatile long 
 	post_progress(host_progress, it + 1, broke_at);
 }
 
-// pcg_tri_direction_kernel for the chunk's columns; history row of column j at history + j * hist_ld. The last chunk posts progress.
+// The verdicts of the body, identically in every block; p = z + beta p (z = r without a preconditioner) for the columns that go on.
+// Block 0 writes the next states and the history rows (column j's at history + j * hist_ld); the last chunk posts progress.
 template <typename T, int KC, bool PRE>
 __global__ __launch_bounds__(VB) void
-pcg_tri_direction_multi_kernel(const PcgTriState * __restrict__ st_p, PcgTriState * __restrict__ st_next, T * __restrict__ p,
+pcg_tri_direction_kernel(const PcgTriState * __restrict__ st_p, PcgTriState * __restrict__ st_next, T * __restrict__ p,
 		const T * __restrict__ z, long n, long ld, int c0, int k, int nb, double tol, const double * __restrict__ part,
 		double * __restrict__ history, long hist_ld, long it, volatile long * host_progress)
 {
@@ -754,10 +392,10 @@ pcg_tri_direction_multi_kernel(const PcgTriState * __restrict__ st_p, PcgTriStat
 	}
 }
 
-// pcg_tri_final_kernel for the chunk's columns
+// the tail's explicit residual: q = b - q (q = A x); partials ER = |b - A x|^2 and XX = |x|^2
 template <typename T, int KC>
 __global__ __launch_bounds__(VB) void
-pcg_tri_final_multi_kernel(const T * __restrict__ b, T * __restrict__ q, const T * __restrict__ x, long n, long ld, int c0,
+pcg_tri_final_kernel(const T * __restrict__ b, T * __restrict__ q, const T * __restrict__ x, long n, long ld, int c0,
 		double * __restrict__ part)
 {
 	const bool vec = ld % KC == 0 && c0 % KC == 0;
@@ -801,11 +439,16 @@ pcg_tri_scale_multi_kernel(const T * __restrict__ scale, const T * __restrict__ 
 	}
 }
 
-// pcg_tri_solve for k columns. apply(r, z, scale, n, k, chunks, grid, stream) enqueues Z = M^-1 R on blocks with ld = k.
-template <typename T, bool PRE, typename Apply>
+// ------------------------------------------------------------------------------------------------ host side
+
+// The solve of k columns behind all six entries. PRE: there is a preconditioner. scale_host: the scale of M or NULL; the solve keeps
+// its device copy. product(A, k, in, out, stream) enqueues out = A in on n x k blocks with ld = k. apply(r, z, scale, n, k, chunks, grid,
+// stream) enqueues Z = M^-1 R on such blocks; it is never called without PRE. Both return 0 or 1 (error set). `what` names the caller
+// in the gate's message. infos: k structs or NULL.
+template <typename T, bool PRE, typename Product, typename Apply>
 static int
-pcg_tri_multi_solve(const char * what, spmv_mi355x_matrix * A, int k, const void * b_host, void * x_host, const void * scale_host,
-		Apply apply, double tol, long max_iterations, double * history_host, spmv_mi355x_pcg_tri_info * infos)
+pcg_tri_solve(const char * what, spmv_mi355x_matrix * A, int k, const void * b_host, void * x_host, const void * scale_host,
+		Product product, Apply apply, double tol, long max_iterations, double * history_host, spmv_mi355x_pcg_tri_info * infos)
 {
 	const auto t_start = std::chrono::steady_clock::now();
 	const long n = spmv_mi355x_rows(A);
@@ -815,6 +458,7 @@ pcg_tri_multi_solve(const char * what, spmv_mi355x_matrix * A, int k, const void
 	DeviceBuffers buf;
 	const size_t nbytes = (size_t) n * (size_t) k * sizeof(T);
 
+	// plain allocations, the product's output included: see solve() in solvers.hip
 	T * b, * x, * r, * p, * q, * z = nullptr, * scale = nullptr;
 	for (T ** v : {&b, &x, &r, &p, &q})
 		ABI_TRY(buf.alloc(v, nbytes));
@@ -843,18 +487,19 @@ pcg_tri_multi_solve(const char * what, spmv_mi355x_matrix * A, int k, const void
 	const int nb = solver_blocks(n);
 	const dim3 grid(nb), block(VB), one(1);
 	const std::vector<Chunk> chunks = column_chunks(k);
-	long spmm_calls = 0;
-	auto spmm = [&](const T * in, T * out) {
-		spmm_calls++;
-		return spmv_mi355x_spmm_device_async(A, k, in, ld, out, ld, 0, stream);
+	long spmv_calls = 0;
+	auto spmv = [&](const T * in, T * out) {
+		spmv_calls++;
+		return product(A, k, in, out, stream);
 	};
-	// the states of the moment are st[s & 1][0 .. k); every transition reads them, writes the other k and adds 1
+	// the states of the moment are st[s & 1][0 .. k); every transition (the start under a preconditioner, a loop body) reads them,
+	// writes the other k and adds 1
 	long s = 0;
 	auto states = [&](long which) { return st + (which & 1) * (long) k; };
 	auto dot = [&](const T * u, const T * v, int slot) {
 		for_chunks(chunks, [&](int c0, auto kc) {
 			constexpr int KC = decltype(kc)::value;
-			hipLaunchKernelGGL((pcg_tri_dot_multi_kernel<T, KC>), grid, block, 0, stream, states(s), u, v, n, ld, c0, part, slot);
+			hipLaunchKernelGGL((pcg_tri_dot_kernel<T, KC>), grid, block, 0, stream, states(s), u, v, n, ld, c0, part, slot);
 			return 0;
 		});
 	};
@@ -867,8 +512,8 @@ pcg_tri_multi_solve(const char * what, spmv_mi355x_matrix * A, int k, const void
 
 	for_chunks(chunks, [&](int c0, auto kc) {
 		constexpr int KC = decltype(kc)::value;
-		hipLaunchKernelGGL((pcg_tri_start_multi_kernel<T, KC, PRE>), grid, block, 0, stream, b, r, p, x, n, ld, c0, part);
-		hipLaunchKernelGGL((pcg_tri_init_state_multi_kernel<KC>), one, block, 0, stream, st, k, c0, nb, part);
+		hipLaunchKernelGGL((pcg_tri_start_kernel<T, KC, PRE>), grid, block, 0, stream, b, r, p, x, n, ld, c0, part);
+		hipLaunchKernelGGL((pcg_tri_init_state_kernel<KC>), one, block, 0, stream, st, k, c0, nb, part);
 		return 0;
 	});
 	if (PRE)
@@ -876,7 +521,7 @@ pcg_tri_multi_solve(const char * what, spmv_mi355x_matrix * A, int k, const void
 		ABI_TRY(precondition());
 		for_chunks(chunks, [&](int c0, auto kc) {
 			constexpr int KC = decltype(kc)::value;
-			hipLaunchKernelGGL((pcg_tri_begin_multi_kernel<T, KC>), grid, block, 0, stream, states(s), states(s + 1), p, z, n, ld, c0, nb, part);
+			hipLaunchKernelGGL((pcg_tri_begin_kernel<T, KC>), grid, block, 0, stream, states(s), states(s + 1), p, z, n, ld, c0, nb, part);
 			return 0;
 		});
 		s++;
@@ -890,18 +535,18 @@ pcg_tri_multi_solve(const char * what, spmv_mi355x_matrix * A, int k, const void
 		ABI_TRY(gate.wait(it, what, stream, &stop));
 		if (stop)
 			break;
-		ABI_TRY(spmm(p, q));
+		ABI_TRY(spmv(p, q));
 		dot(p, q, (int) T_PQ);
 		for_chunks(chunks, [&](int c0, auto kc) {
 			constexpr int KC = decltype(kc)::value;
-			hipLaunchKernelGGL((pcg_tri_update_multi_kernel<T, KC>), grid, block, 0, stream, states(s), x, r, p, q, n, ld, c0, nb, part);
+			hipLaunchKernelGGL((pcg_tri_update_kernel<T, KC>), grid, block, 0, stream, states(s), x, r, p, q, n, ld, c0, nb, part);
 			return 0;
 		});
 		if (PRE)
 			ABI_TRY(precondition());
 		for_chunks(chunks, [&](int c0, auto kc) {
 			constexpr int KC = decltype(kc)::value;
-			hipLaunchKernelGGL((pcg_tri_direction_multi_kernel<T, KC, PRE>), grid, block, 0, stream, states(s), states(s + 1), p,
+			hipLaunchKernelGGL((pcg_tri_direction_kernel<T, KC, PRE>), grid, block, 0, stream, states(s), states(s + 1), p,
 					PRE ? (const T *) z : (const T *) r, n, ld, c0, k, nb, tol, part, history, max_iterations, it, gate.dev);
 			return 0;
 		});
@@ -909,11 +554,11 @@ pcg_tri_multi_solve(const char * what, spmv_mi355x_matrix * A, int k, const void
 	}
 	HIP_TRY(hipGetLastError());
 
-	// the explicit norms of the returned columns: one SpMM, q is free now
-	ABI_TRY(spmm(x, q));
+	// the explicit norms of the returned columns, |b - A x| and |x|: one product, q is free now; x stays as it froze
+	ABI_TRY(spmv(x, q));
 	for_chunks(chunks, [&](int c0, auto kc) {
 		constexpr int KC = decltype(kc)::value;
-		hipLaunchKernelGGL((pcg_tri_final_multi_kernel<T, KC>), grid, block, 0, stream, b, q, x, n, ld, c0, part);
+		hipLaunchKernelGGL((pcg_tri_final_kernel<T, KC>), grid, block, 0, stream, b, q, x, n, ld, c0, part);
 		return 0;
 	});
 	HIP_TRY(hipGetLastError());
@@ -925,34 +570,50 @@ pcg_tri_multi_solve(const char * what, spmv_mi355x_matrix * A, int k, const void
 	if (history)
 		HIP_TRY(hipMemcpyAsync(history_host, history, hist_bytes, hipMemcpyDeviceToHost, stream));
 	HIP_TRY(hipStreamSynchronize(stream));
-	if (infos)
+	const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
+	for (int j = 0; infos && j < k; j++)
 	{
-		const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
-		for (int j = 0; j < k; j++)
-		{
-			auto norm_of = [&](int slot) { return std::sqrt(host_sum(part_host.data(), (size_t) part_at(j, slot), nb)); };
-			spmv_mi355x_pcg_tri_info out;
-			memset(&out, 0, sizeof(out));
-			out.iterations = st_host[(size_t) j].k;
-			out.stop = st_host[(size_t) j].done ? st_host[(size_t) j].stop : 2;
-			out.rnorm = norm_of(T_ER);
-			out.rnorm0 = norm_of(T_BB);
-			out.prnorm = std::sqrt(st_host[(size_t) j].rr);
-			out.xnorm = norm_of(T_XX);
-			out.spmv_calls = spmm_calls;
-			out.seconds = seconds;
-			put_info(infos + j, infos[j].struct_size, out);
-		}
+		auto norm_of = [&](int slot) { return std::sqrt(host_sum(part_host.data(), (size_t) part_at(j, slot), nb)); };
+		const PcgTriState & sj = st_host[(size_t) j];
+		spmv_mi355x_pcg_tri_info out;
+		memset(&out, 0, sizeof(out));
+		out.iterations = sj.k;
+		out.stop = sj.done ? sj.stop : 2;
+		out.rnorm = norm_of(T_ER);
+		out.rnorm0 = norm_of(T_BB);
+		out.prnorm = std::sqrt(sj.rr);
+		out.xnorm = norm_of(T_XX);
+		out.spmv_calls = spmv_calls;
+		out.seconds = seconds;
+		put_info(infos + j, infos[j].struct_size, out);
 	}
 	return 0;
 }
 
-// pcg_tri_arguments_ok for k columns: its checks in its order and wording, with k < 1 first and every info's struct_size. `tri`: M
-// of pcg_tri_multi has a triangular part, which needs no handle to see.
+// pcg_tri_solve<T, PRE> by the handle's precision and `pre`
+template <typename Product, typename Apply>
+static int
+pcg_tri_dispatch(const char * what, spmv_mi355x_matrix * A, int k, const void * b_host, void * x_host, bool pre, const void * scale_host,
+		Product product, Apply apply, double tol, long max_iterations, double * history_host, spmv_mi355x_pcg_tri_info * infos)
+{
+	HIP_TRY(hipSetDevice(spmv_mi355x_device(A)));
+	auto run = [&](auto t, auto with) {
+		return pcg_tri_solve<decltype(t), decltype(with)::value>(what, A, k, b_host, x_host, scale_host, product, apply, tol, max_iterations,
+				history_host, infos);
+	};
+	if (spmv_mi355x_precision(A) == SPMV_MI355X_F32)
+		return pre ? run(float(), std::true_type()) : run(float(), std::false_type());
+	return pre ? run(double(), std::true_type()) : run(double(), std::false_type());
+}
+
+// The checks of every entry that need no preconditioner, with the caller's name as the prefix: k < 1 and items 1 to 5 of the header.
+// `multi` picks the wording of a _multi entry (infos[j], B, X_out). `tri`: M of pcg_tri_multi has a triangular part, which needs no
+// handle to see.
 static bool
-pcg_tri_multi_arguments_ok(const char * what, spmv_mi355x_matrix * A, int k, const void * b_host, void * x_out_host, double tol,
+pcg_tri_arguments_ok(const char * what, bool multi, spmv_mi355x_matrix * A, int k, const void * b_host, void * x_out_host, double tol,
 		long max_iterations, const spmv_mi355x_pcg_tri_info * infos, bool tri)
 {
+	// the checks that need no handle come first, so each can be met (and tested) on its own
 	if (k < 1)
 	{
 		set_error("%s: k = %d: at least one right-hand side is needed", what, k);
@@ -961,7 +622,10 @@ pcg_tri_multi_arguments_ok(const char * what, spmv_mi355x_matrix * A, int k, con
 	for (int j = 0; infos && j < k; j++)
 		if (infos[j].struct_size < 8)
 		{
-			set_error("%s: infos[%d].struct_size not set", what, j);
+			if (multi)
+				set_error("%s: infos[%d].struct_size not set", what, j);
+			else
+				set_error("%s: info->struct_size not set", what);
 			return false;
 		}
 	if (!(tol >= 0) || !std::isfinite(tol))
@@ -982,7 +646,8 @@ pcg_tri_multi_arguments_ok(const char * what, spmv_mi355x_matrix * A, int k, con
 	}
 	if (!A || !b_host || !x_out_host)
 	{
-		set_error("%s: NULL argument (%s%s%s )", what, !A ? " A" : "", !b_host ? " B" : "", !x_out_host ? " X_out" : "");
+		set_error("%s: NULL argument (%s%s%s )", what, !A ? " A" : "", !b_host ? (multi ? " B" : " b") : "",
+				!x_out_host ? (multi ? " X_out" : " x_out") : "");
 		return false;
 	}
 	const long m = spmv_mi355x_rows(A), n = spmv_mi355x_cols(A);
@@ -994,6 +659,69 @@ pcg_tri_multi_arguments_ok(const char * what, spmv_mi355x_matrix * A, int k, con
 	}
 	return true;
 }
+
+// F (not NULL) against the matrix it preconditions: n, precision, device
+static bool
+pcg_tri_fsai_ok(const char * what, const spmv_mi355x_fsai * F, spmv_mi355x_matrix * A)
+{
+	const long n = spmv_mi355x_cols(A);
+	const int precision = spmv_mi355x_precision(A), device = spmv_mi355x_device(A);
+	if (F->n != n)
+		set_error("%s: F is a preconditioner of %ld rows, the matrix has %ld", what, F->n, n);
+	else if (F->precision != precision)
+		set_error("%s: F has precision %d, the matrix %d: both must be the same", what, F->precision, precision);
+	else if (F->device != device)
+		set_error("%s: F lives on device %d, the matrix on device %d", what, F->device, device);
+	else
+		return true;
+	return false;
+}
+
+// M (not NULL) against the matrix it preconditions: n, precision, device, then a failed amg_update_values
+static bool
+pcg_tri_amg_ok(const char * what, const spmv_mi355x_amg * M, spmv_mi355x_matrix * A)
+{
+	const long n = spmv_mi355x_cols(A);
+	const int precision = spmv_mi355x_precision(A), device = spmv_mi355x_device(A);
+	if (M->n != n)
+		set_error("%s: M is a preconditioner of %ld rows, the matrix has %ld", what, M->n, n);
+	else if (M->precision != precision)
+		set_error("%s: M has precision %d, the matrix %d: both must be the same", what, M->precision, precision);
+	else if (M->device != device)
+		set_error("%s: M lives on device %d, the matrix on device %d", what, M->device, device);
+	else if (M->update_failed)
+		set_error("%s: the last amg_update_values of M failed below level 0 and left it half rewritten: update it with values it "
+				"accepts first", what);
+	else
+		return true;
+	return false;
+}
+
+// q = A p of the single entries
+struct SpmvProduct {
+	int operator()(spmv_mi355x_matrix * A, int, const void * in, void * out, hipStream_t stream) const
+	{
+		return spmv_mi355x_spmv_device_async(A, in, out, 0, stream);
+	}
+};
+
+// Q = A P of the _multi entries, for every k
+struct SpmmProduct {
+	int operator()(spmv_mi355x_matrix * A, int k, const void * in, void * out, hipStream_t stream) const
+	{
+		return spmv_mi355x_spmm_device_async(A, k, in, k, out, k, 0, stream);
+	}
+};
+
+// z = M^-1 r of pcg_tri: second^-1 (scale o (first^-1 r)), tri_precond.hpp, on one column
+struct TriApply {
+	spmv_mi355x_trsv * first, * second;
+	template <typename T>
+	int operator()(const T * r, T * z, const T * scale, long n, int, const std::vector<Chunk> &, dim3 grid, hipStream_t stream) const
+	{
+		return tri_precond_enqueue<T>(first, scale, second, r, z, n, false, grid, stream);
+	}
+};
 
 // Z = scale o R: the Jacobi scale of pcg_tri_multi
 struct ScaleApplyMulti {
@@ -1009,7 +737,17 @@ struct ScaleApplyMulti {
 	}
 };
 
-// Z = G^t (G R): the two SpMMs write the fsai handle's scratch block and z
+// z = G^t (G r) of pcg_fsai. The two SpMVs write the handle's scratch vector and z, nothing else.
+struct FsaiApply {
+	spmv_mi355x_fsai * F;
+	template <typename T>
+	int operator()(const T * r, T * z, const T *, long, int, const std::vector<Chunk> &, dim3, hipStream_t stream) const
+	{
+		return spmv_mi355x_fsai_apply_device_async(F, r, z, stream);
+	}
+};
+
+// Z = G^t (G R) of pcg_fsai_multi: the two SpMMs write the fsai handle's scratch block and z
 struct FsaiApplyMulti {
 	spmv_mi355x_fsai * F;
 	template <typename T>
@@ -1019,7 +757,17 @@ struct FsaiApplyMulti {
 	}
 };
 
-// one V cycle for the k columns: it writes the hierarchy's own blocks and z
+// z = M^-1 r of pcg_amg: one V cycle of an amg handle. Its SpMVs and vector kernels write the hierarchy's own vectors and z, nothing else.
+struct AmgApply {
+	spmv_mi355x_amg * M;
+	template <typename T>
+	int operator()(const T * r, T * z, const T *, long, int, const std::vector<Chunk> &, dim3, hipStream_t stream) const
+	{
+		return spmv_mi355x_amg_apply_device_async(M, r, z, stream);
+	}
+};
+
+// one V cycle for the k columns of pcg_amg_multi: it writes the hierarchy's own blocks and z
 struct AmgApplyMulti {
 	spmv_mi355x_amg * M;
 	template <typename T>
@@ -1036,22 +784,15 @@ spmv_mi355x_pcg_tri(spmv_mi355x_matrix * A, const void * b_host, void * x_out_ho
 		long max_iterations, double * history_out, spmv_mi355x_pcg_tri_info * info)
 {
 	using namespace spmv;
-	if (!pcg_tri_arguments_ok("pcg_tri", A, b_host, x_out_host, tol, max_iterations, info))
+	if (!pcg_tri_arguments_ok("pcg_tri", false, A, 1, b_host, x_out_host, tol, max_iterations, info, false))
 		return 1;
-	const long n = spmv_mi355x_cols(A);
-	const int precision = spmv_mi355x_precision(A), device = spmv_mi355x_device(A);
-	if (M && (!tri_precond_size_ok("pcg_tri", M) || !tri_precond_parts_ok("pcg_tri", M, n, precision, device)))
+	if (M && (!tri_precond_size_ok("pcg_tri", M)
+			|| !tri_precond_parts_ok("pcg_tri", M, spmv_mi355x_cols(A), spmv_mi355x_precision(A), spmv_mi355x_device(A))))
 		return 1;
-	spmv_mi355x_trsv * first = M ? M->first : nullptr, * second = M ? M->second : nullptr;
+	const TriApply apply = {M ? M->first : nullptr, M ? M->second : nullptr};
 	const void * scale = M ? M->scale_host : nullptr;
-	HIP_TRY(hipSetDevice(device));
-	const bool pre = first || scale || second;
-	const TriApply apply = {first, second};
-	if (precision == SPMV_MI355X_F32)
-		return pre ? pcg_tri_solve<float, true>("pcg_tri", A, b_host, x_out_host, scale, apply, tol, max_iterations, history_out, info)
-		           : pcg_tri_solve<float, false>("pcg_tri", A, b_host, x_out_host, nullptr, apply, tol, max_iterations, history_out, info);
-	return pre ? pcg_tri_solve<double, true>("pcg_tri", A, b_host, x_out_host, scale, apply, tol, max_iterations, history_out, info)
-	           : pcg_tri_solve<double, false>("pcg_tri", A, b_host, x_out_host, nullptr, apply, tol, max_iterations, history_out, info);
+	return pcg_tri_dispatch("pcg_tri", A, 1, b_host, x_out_host, apply.first || scale || apply.second, scale, SpmvProduct(), apply, tol,
+			max_iterations, history_out, info);
 }
 
 extern "C" int
@@ -1059,28 +800,17 @@ spmv_mi355x_pcg_fsai(spmv_mi355x_matrix * A, const void * b_host, void * x_out_h
 		long max_iterations, double * history_out, spmv_mi355x_pcg_tri_info * info)
 {
 	using namespace spmv;
-	if (!pcg_tri_arguments_ok("pcg_fsai", A, b_host, x_out_host, tol, max_iterations, info))
+	if (!pcg_tri_arguments_ok("pcg_fsai", false, A, 1, b_host, x_out_host, tol, max_iterations, info, false))
 		return 1;
 	if (!F)
 	{
 		set_error("pcg_fsai: F is NULL: spmv_mi355x_pcg_tri with M = NULL is the solve without a preconditioner");
 		return 1;
 	}
-	const long n = spmv_mi355x_cols(A);
-	const int precision = spmv_mi355x_precision(A), device = spmv_mi355x_device(A);
-	if (F->n != n)
-		set_error("pcg_fsai: F is a preconditioner of %ld rows, the matrix has %ld", F->n, n);
-	else if (F->precision != precision)
-		set_error("pcg_fsai: F has precision %d, the matrix %d: both must be the same", F->precision, precision);
-	else if (F->device != device)
-		set_error("pcg_fsai: F lives on device %d, the matrix on device %d", F->device, device);
-	if (F->n != n || F->precision != precision || F->device != device)
+	if (!pcg_tri_fsai_ok("pcg_fsai", F, A))
 		return 1;
-	HIP_TRY(hipSetDevice(device));
-	const FsaiApply apply = {F};
-	if (precision == SPMV_MI355X_F32)
-		return pcg_tri_solve<float, true>("pcg_fsai", A, b_host, x_out_host, nullptr, apply, tol, max_iterations, history_out, info);
-	return pcg_tri_solve<double, true>("pcg_fsai", A, b_host, x_out_host, nullptr, apply, tol, max_iterations, history_out, info);
+	return pcg_tri_dispatch("pcg_fsai", A, 1, b_host, x_out_host, true, nullptr, SpmvProduct(), FsaiApply{F}, tol, max_iterations,
+			history_out, info);
 }
 
 extern "C" int
@@ -1088,34 +818,17 @@ spmv_mi355x_pcg_amg(spmv_mi355x_matrix * A, const void * b_host, void * x_out_ho
 		long max_iterations, double * history_out, spmv_mi355x_pcg_tri_info * info)
 {
 	using namespace spmv;
-	if (!pcg_tri_arguments_ok("pcg_amg", A, b_host, x_out_host, tol, max_iterations, info))
+	if (!pcg_tri_arguments_ok("pcg_amg", false, A, 1, b_host, x_out_host, tol, max_iterations, info, false))
 		return 1;
 	if (!M)
 	{
 		set_error("pcg_amg: M is NULL: spmv_mi355x_pcg_tri with M = NULL is the solve without a preconditioner");
 		return 1;
 	}
-	const long n = spmv_mi355x_cols(A);
-	const int precision = spmv_mi355x_precision(A), device = spmv_mi355x_device(A);
-	if (M->n != n)
-		set_error("pcg_amg: M is a preconditioner of %ld rows, the matrix has %ld", M->n, n);
-	else if (M->precision != precision)
-		set_error("pcg_amg: M has precision %d, the matrix %d: both must be the same", M->precision, precision);
-	else if (M->device != device)
-		set_error("pcg_amg: M lives on device %d, the matrix on device %d", M->device, device);
-	if (M->n != n || M->precision != precision || M->device != device)
+	if (!pcg_tri_amg_ok("pcg_amg", M, A))
 		return 1;
-	if (M->update_failed)
-	{
-		set_error("pcg_amg: the last amg_update_values of M failed below level 0 and left it half rewritten: update it with values it "
-				"accepts first");
-		return 1;
-	}
-	HIP_TRY(hipSetDevice(device));
-	const AmgApply apply = {M};
-	if (precision == SPMV_MI355X_F32)
-		return pcg_tri_solve<float, true>("pcg_amg", A, b_host, x_out_host, nullptr, apply, tol, max_iterations, history_out, info);
-	return pcg_tri_solve<double, true>("pcg_amg", A, b_host, x_out_host, nullptr, apply, tol, max_iterations, history_out, info);
+	return pcg_tri_dispatch("pcg_amg", A, 1, b_host, x_out_host, true, nullptr, SpmvProduct(), AmgApply{M}, tol, max_iterations,
+			history_out, info);
 }
 
 extern "C" int
@@ -1124,25 +837,15 @@ spmv_mi355x_pcg_tri_multi(spmv_mi355x_matrix * A, int k, const void * B_host, vo
 {
 	using namespace spmv;
 	const bool sized = M && M->struct_size >= sizeof(spmv_mi355x_tri_precond);
-	if (!pcg_tri_multi_arguments_ok("pcg_tri_multi", A, k, B_host, X_out_host, tol, max_iterations, infos,
+	if (!pcg_tri_arguments_ok("pcg_tri_multi", true, A, k, B_host, X_out_host, tol, max_iterations, infos,
 			sized && (M->first || M->second)))
 		return 1;
-	const long n = spmv_mi355x_cols(A);
-	const int precision = spmv_mi355x_precision(A), device = spmv_mi355x_device(A);
-	if (M && (!tri_precond_size_ok("pcg_tri_multi", M) || !tri_precond_parts_ok("pcg_tri_multi", M, n, precision, device)))
+	if (M && (!tri_precond_size_ok("pcg_tri_multi", M)
+			|| !tri_precond_parts_ok("pcg_tri_multi", M, spmv_mi355x_cols(A), spmv_mi355x_precision(A), spmv_mi355x_device(A))))
 		return 1;
 	const void * scale = M ? M->scale_host : nullptr;
-	HIP_TRY(hipSetDevice(device));
-	const ScaleApplyMulti apply;
-	if (precision == SPMV_MI355X_F32)
-		return scale ? pcg_tri_multi_solve<float, true>("pcg_tri_multi", A, k, B_host, X_out_host, scale, apply, tol, max_iterations,
-				               history_out, infos)
-		             : pcg_tri_multi_solve<float, false>("pcg_tri_multi", A, k, B_host, X_out_host, nullptr, apply, tol, max_iterations,
-				               history_out, infos);
-	return scale ? pcg_tri_multi_solve<double, true>("pcg_tri_multi", A, k, B_host, X_out_host, scale, apply, tol, max_iterations,
-			               history_out, infos)
-	             : pcg_tri_multi_solve<double, false>("pcg_tri_multi", A, k, B_host, X_out_host, nullptr, apply, tol, max_iterations,
-			               history_out, infos);
+	return pcg_tri_dispatch("pcg_tri_multi", A, k, B_host, X_out_host, scale != nullptr, scale, SpmmProduct(), ScaleApplyMulti(), tol,
+			max_iterations, history_out, infos);
 }
 
 extern "C" int
@@ -1150,30 +853,17 @@ spmv_mi355x_pcg_fsai_multi(spmv_mi355x_matrix * A, int k, const void * B_host, v
 		long max_iterations, double * history_out, spmv_mi355x_pcg_tri_info * infos)
 {
 	using namespace spmv;
-	if (!pcg_tri_multi_arguments_ok("pcg_fsai_multi", A, k, B_host, X_out_host, tol, max_iterations, infos, false))
+	if (!pcg_tri_arguments_ok("pcg_fsai_multi", true, A, k, B_host, X_out_host, tol, max_iterations, infos, false))
 		return 1;
 	if (!F)
 	{
 		set_error("pcg_fsai_multi: F is NULL: spmv_mi355x_pcg_tri_multi with M = NULL is the solve without a preconditioner");
 		return 1;
 	}
-	const long n = spmv_mi355x_cols(A);
-	const int precision = spmv_mi355x_precision(A), device = spmv_mi355x_device(A);
-	if (F->n != n)
-		set_error("pcg_fsai_multi: F is a preconditioner of %ld rows, the matrix has %ld", F->n, n);
-	else if (F->precision != precision)
-		set_error("pcg_fsai_multi: F has precision %d, the matrix %d: both must be the same", F->precision, precision);
-	else if (F->device != device)
-		set_error("pcg_fsai_multi: F lives on device %d, the matrix on device %d", F->device, device);
-	if (F->n != n || F->precision != precision || F->device != device)
+	if (!pcg_tri_fsai_ok("pcg_fsai_multi", F, A))
 		return 1;
-	HIP_TRY(hipSetDevice(device));
-	const FsaiApplyMulti apply = {F};
-	if (precision == SPMV_MI355X_F32)
-		return pcg_tri_multi_solve<float, true>("pcg_fsai_multi", A, k, B_host, X_out_host, nullptr, apply, tol, max_iterations, history_out,
-				infos);
-	return pcg_tri_multi_solve<double, true>("pcg_fsai_multi", A, k, B_host, X_out_host, nullptr, apply, tol, max_iterations, history_out,
-			infos);
+	return pcg_tri_dispatch("pcg_fsai_multi", A, k, B_host, X_out_host, true, nullptr, SpmmProduct(), FsaiApplyMulti{F}, tol,
+			max_iterations, history_out, infos);
 }
 
 extern "C" int
@@ -1181,34 +871,15 @@ spmv_mi355x_pcg_amg_multi(spmv_mi355x_matrix * A, int k, const void * B_host, vo
 		long max_iterations, double * history_out, spmv_mi355x_pcg_tri_info * infos)
 {
 	using namespace spmv;
-	if (!pcg_tri_multi_arguments_ok("pcg_amg_multi", A, k, B_host, X_out_host, tol, max_iterations, infos, false))
+	if (!pcg_tri_arguments_ok("pcg_amg_multi", true, A, k, B_host, X_out_host, tol, max_iterations, infos, false))
 		return 1;
 	if (!M)
 	{
 		set_error("pcg_amg_multi: M is NULL: spmv_mi355x_pcg_tri_multi with M = NULL is the solve without a preconditioner");
 		return 1;
 	}
-	const long n = spmv_mi355x_cols(A);
-	const int precision = spmv_mi355x_precision(A), device = spmv_mi355x_device(A);
-	if (M->n != n)
-		set_error("pcg_amg_multi: M is a preconditioner of %ld rows, the matrix has %ld", M->n, n);
-	else if (M->precision != precision)
-		set_error("pcg_amg_multi: M has precision %d, the matrix %d: both must be the same", M->precision, precision);
-	else if (M->device != device)
-		set_error("pcg_amg_multi: M lives on device %d, the matrix on device %d", M->device, device);
-	if (M->n != n || M->precision != precision || M->device != device)
+	if (!pcg_tri_amg_ok("pcg_amg_multi", M, A))
 		return 1;
-	if (M->update_failed)
-	{
-		set_error("pcg_amg_multi: the last amg_update_values of M failed below level 0 and left it half rewritten: update it with values "
-				"it accepts first");
-		return 1;
-	}
-	HIP_TRY(hipSetDevice(device));
-	const AmgApplyMulti apply = {M};
-	if (precision == SPMV_MI355X_F32)
-		return pcg_tri_multi_solve<float, true>("pcg_amg_multi", A, k, B_host, X_out_host, nullptr, apply, tol, max_iterations, history_out,
-				infos);
-	return pcg_tri_multi_solve<double, true>("pcg_amg_multi", A, k, B_host, X_out_host, nullptr, apply, tol, max_iterations, history_out,
-			infos);
+	return pcg_tri_dispatch("pcg_amg_multi", A, k, B_host, X_out_host, true, nullptr, SpmmProduct(), AmgApplyMulti{M}, tol,
+			max_iterations, history_out, infos);
 }

@@ -72,7 +72,7 @@ store_partial(double * __restrict__ part, int slot, double v)
 		part[(long) slot * MAX_PART + blockIdx.x] = v;
 }
 
-// ---- k columns at once (solvers.hip, the k-column solve of solver_pcg_tri.hip, the k-column cycle of kernels_amg.hip): a vector kernel serves a chunk
+// ---- k columns at once (solvers.hip, solver_pcg_tri.hip, the k-column cycle of kernels_amg.hip): a vector kernel serves a chunk
 // of KC in {8, 4, 2, 1} columns of a row-major block, and every per-column dot product goes through the additions of block_sum /
 // sum_partials / store_partial in their order, so a column returns the bits of the single-vector kernels whatever chunk it sits in.
 

@@ -2,11 +2,15 @@
 Amg.apply_multi* / Fsai.apply_multi* / Matrix.pcg_tri_multi against the single-vector calls on the same handles.
 
 The contract is exact: on a handle whose SpMV is deterministic, column j of every k-column call holds the bits of the single call on
-column j (shape, dtype and tobytes()). Every test first asserts that the handle's SpMV is deterministic. What the comparison checks
-is a column inside a chunk of 8, 4 or 2 columns (or behind a full chunk) against the single-vector kernels, the SpMM against the
-SpMV, the dense solve of a chunk against the single dense solve, and the freeze of one column against its neighbours' progress.
-The single calls themselves are held to the restatements and references by test_gpu_amg.py, test_gpu_fsai.py and
-test_gpu_pcg_tri.py. Every test here needs the new entry points, so none passes without the feature.
+column j (shape, dtype and tobytes()). Every test first asserts that the handle's SpMV is deterministic. The vector kernels of the
+solve are one KC-templated set (csrc/solver_pcg_tri.hip) and the single call is their k = 1, so what the comparison checks there is
+a column inside a chunk of 8, 4 or 2 columns (or behind a full chunk) against the same column in a chunk of one. At k = 1 the
+vector kernels are the same code on both sides; what differs is the matrix product and the preconditioner: the SpMM (k = 1) against
+the SpMV, apply_multi (k = 1) against the single apply, the Jacobi scale kernel for k columns against tri_precond's. Beyond that:
+the cycle's chunked vector kernels against its single-vector ones, the dense solve of a chunk against the single dense solve, and
+the freeze of one column against its neighbours' progress.
+The single calls themselves, and with them the KC = 1 kernels, are held to the restatements and references by test_gpu_amg.py,
+test_gpu_fsai.py, test_gpu_pcg_tri.py and test_gpu_pcg_tri_sizes.py. Every test here needs the _multi entry points.
 
 1. the cycle, column against single: amg_cases.CYCLE_CASES in both precisions (grid on every layout), nu = 2, a filtered hierarchy,
    a near-null vector; Fsai with power 1 and 2.            2. strided blocks, guard rows and NaN padding; in place.

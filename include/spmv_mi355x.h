@@ -642,7 +642,8 @@ int  spmv_mi355x_gmres(spmv_mi355x_matrix * A, const void * b_host, void * x_out
  *   - NOT CHECKABLE: that b_dev / x_dev hold n values on the right device.
  *   - NOT BUILT: wiring into pbicgstab / minres (gmres and CG have it: spmv_mi355x_gmres_tri, spmv_mi355x_pcg_tri); the ILU(0) /
  *     IC(0) factorization itself; a solve
- *     with T^t over T's layout; multi-RHS; update_values for a trsv handle; GPU-side analysis; graph capture; a row-partitioned form;
+ *     with T^t over T's layout (k right-hand sides ARE served: "K COLUMNS" below); update_values for a trsv handle; GPU-side analysis;
+ *     graph capture; a row-partitioned form;
  *     a "sync-free" variant in which workgroups wait for each other inside one launch. */
 typedef struct spmv_mi355x_trsv spmv_mi355x_trsv;   /* opaque */
 enum { SPMV_MI355X_LOWER = 0, SPMV_MI355X_UPPER = 1 };
@@ -693,6 +694,41 @@ int  spmv_mi355x_trsv_create_blocked(spmv_mi355x_trsv ** out, int uplo, int diag
 		const int32_t * row_ptr, const int32_t * col_idx, const double * values_fp64, long block_rows, int device /* -1 = current */);
 int  spmv_mi355x_trsv_block_info(const spmv_mi355x_trsv * T, long * block_rows_out, long * blocks_out, long * max_block_levels_out,
 		long * nnz_dropped_out);                                                               /* any out pointer may be NULL */
+
+/* K COLUMNS: T X = B for k right-hand sides over the same handle. Any handle serves, global or blocked, without
+ * being rebuilt: there is no new layout and no new analysis. B and X are row-major blocks, row i at ptr + i * ld, ld >= k counted in
+ * values of the handle's precision. The columns are solved in chunks of KC = 8, 4, 2 or 1; one chunk is one pass over the plan in
+ * which a lane still owns one row, loads the row's length, position, diagonal and every (value, column) pair ONCE, gathers the KC
+ * values of x[column] as one row of the block and runs KC fma chains in stored order and KC IEEE divisions. Per column that is
+ * exactly the expression of "THE SOLVE, PINNED TO THE BIT", so column j returns the bits of trsv_solve_device_async on column j (and
+ * of tests/trsv_reference.c) whatever k, ld and chunk it sits in. The ordering between levels is that of the single solve: launch
+ * boundaries, and workgroup barriers inside the one-workgroup launches. Nothing spins, nothing waits on another workgroup.
+ *   - chunks. A global handle: k = 8s and then the binary remainder (k = 11: 8 + 2 + 1), each chunk the plan's launches once more.
+ *     A blocked handle: the same with Kmax in the place of 8, Kmax being the largest KC in {8, 4, 2, 1} with min(block_rows, n) * KC
+ *     values <= 160 KiB, since a workgroup keeps its rows of the chunk in LDS; each chunk is one launch. At block_rows = 16384 in fp64
+ *     Kmax is 1 and k columns take k launches: served, not refused.
+ *   - k = 1 with ldb = ldx = 1 is a vector: the call is handed to trsv_solve_device_async and costs what it costs. A single column
+ *     of a wider block (ld > 1) runs the KC = 1 form of the k-column kernels.
+ *   - rows of the blocks are read and written with one vector access where ld % KC == 0, the chunk's first column is a multiple of
+ *     KC and the block's base is aligned to KC values, else value by value; the bits do not depend on it.
+ *   - solve_multi_device_async: enqueued on hip_stream. b_dev == x_dev (in place) is legal when ldb == ldx; any other overlap is not.
+ *     Only the k columns of the n rows of X are written: the ld - k padding columns of X are not touched, those of B are not read.
+ *   - trsv_solve_multi: the blocking host form with ld = k; the two device blocks are allocated at the first call and replaced when
+ *     a larger k arrives, which synchronises the device.
+ *   - trsv_solve_multi_plan (host only, touches no device): matrix_passes = the number of chunks, launches = passes * the launches
+ *     of trsv_info (so = passes for a blocked handle), max_chunk = Kmax of the handle (8 for a global one). All three are 0 at n = 0.
+ *   - time_trsv_multi_device: HIP-event timing of `iters` back-to-back k-column solves.
+ *   - rc 1 with the prefix "trsv_solve_multi:" ("trsv_solve_multi_plan:" for the plan, which makes the first two checks), on the
+ *     host before any device is touched, in this order: 1. a NULL handle; 2. k < 1; 3. ldb < k or ldx < k; 4. b == x with
+ *     ldb != ldx; 5. for n > 0 a NULL block. n = 0 is rc 0 with nothing launched.
+ *   - NOT BUILT: a chunk width other than 8 / 4 / 2 / 1 (k = 3 is two passes), column-major blocks, T^t. */
+int  spmv_mi355x_trsv_solve_multi_device_async(spmv_mi355x_trsv * T, int k, const void * b_dev, long ldb, void * x_dev, long ldx,
+		void * hip_stream);
+int  spmv_mi355x_trsv_solve_multi(spmv_mi355x_trsv * T, int k, const void * B_host, void * X_host);          /* blocking, ld = k */
+int  spmv_mi355x_trsv_solve_multi_plan(const spmv_mi355x_trsv * T, int k, long * matrix_passes_out, long * launches_out,
+		int * max_chunk_out);                                                                  /* any out pointer may be NULL */
+int  spmv_mi355x_time_trsv_multi_device(spmv_mi355x_trsv * T, int k, const void * b_dev, long ldb, void * x_dev, long ldx, int iters,
+		void * hip_stream, double * ms_per_iter_out);
 
 /* ---- GMRES(m) right-preconditioned by triangular solves ------------------------------------------------------------------------ */
 /* spmv_mi355x_gmres with M^-1 v = second^-1 ( scale o ( first^-1 v ) ) for "M v" (csrc/solver_gmres.hip): each of
@@ -766,8 +802,8 @@ int  spmv_mi355x_gmres_tri(spmv_mi355x_matrix * A, const void * b_host, void * x
  *        in stop 4.
  *   - NOT CHECKABLE: that A and M are symmetric positive definite. Blocked handles give a symmetric M only when both use the same
  *     block_rows (a global handle counts as block_rows >= n). Stop 4 catches only what the two inner products reveal.
- *   - NOT BUILT: the row-partitioned form, device-pointer b / x, a non-zero x0, a k-column triangular solve (k right-hand sides
- *     with M = NULL or a scale alone: spmv_mi355x_pcg_tri_multi below). */
+ *   - NOT BUILT: the row-partitioned form, device-pointer b / x, a non-zero x0 (k right-hand sides with any M:
+ *     spmv_mi355x_pcg_trsm_multi below). */
 typedef struct {
 	unsigned struct_size;   /* in: sizeof(spmv_mi355x_pcg_tri_info) */
 	long   iterations;      /* completed loop bodies */
@@ -1146,14 +1182,24 @@ int  spmv_mi355x_amg_near_null(const spmv_mi355x_amg * M, int level, double * ou
  *     k * max_iterations doubles, column j's rows at history_out + j * max_iterations. infos (may be NULL): k spmv_mi355x_pcg_tri_info,
  *     EACH with struct_size set. Per column they carry what the single solve carries; the explicit |b - A x| and |x| come from one
  *     final SpMM; spmv_calls (SpMM calls) and seconds are the call's, equal in every element. pcg_tri_multi serves M = NULL and an M
- *     with a scale alone (Jacobi); an M with first or second set is REFUSED: there is no k-column triangular solve.
+ *     with a scale alone (Jacobi); an M with first or second set is REFUSED there, with the message it has always had:
+ *     spmv_mi355x_pcg_trsm_multi is the entry that serves it.
+ *   - pcg_trsm_multi: pcg_tri_multi for ANY M: NULL, a scale alone, or any mix of blocked and global trsv handles (SGS of A, the
+ *     caller's IC(0)). Z = second^-1 (scale o (first^-1 R)) on the n x k block, the triangular parts by spmv_mi355x_trsv_solve_multi_
+ *     device_async ("K COLUMNS" of the triangular solve), which reads every (value, column) pair of a factor once per chunk of
+ *     columns. The same signature, infos and history as pcg_tri_multi and its checks in its order without the triangular refusal;
+ *     then M->struct_size and the parts of M as spmv_mi355x_pcg_tri checks them (6 to 8). On a handle with a deterministic SpMV
+ *     column j returns the bits of spmv_mi355x_pcg_tri on b_j with the same M: x, history and every info field but spmv_calls and
+ *     seconds; with M = NULL or a scale alone the bits of pcg_tri_multi. The triangular solves know nothing of a column's stop:
+ *     they write only Z.
  *     A stopped column is frozen while the others run: its x, r, p, state and history are stored back unchanged or not at all. b_j = 0
  *     stops with 3, a NaN in b_j with 4 at 0 iterations and x_j = 0; neither disturbs its neighbours. The host stops enqueueing once
  *     every column has stopped (with the single solve's polling lag). Per iteration: 1 SpMM, M's own launches, 4 vector launches per
  *     chunk (3 without a preconditioner, when no z is stored).
  *     rc 1 before any device is touched, in this order: k < 1; an infos[j].struct_size < 8; tol negative or not finite;
  *     max_iterations < 0; (pcg_tri_multi) M with a triangular part; A, B or X_out NULL; then the single entries' checks in their order.
- *   - NOT BUILT: a k-column triangular solve (SGS / IC(0) for k columns), block CG, routing the single solves through these kernels. */
+ *   - NOT BUILT: block CG, k-column GMRES (gmres_tri stays single-vector), routing the single triangular solve through the k-column
+ *     kernels. */
 int  spmv_mi355x_amg_apply_multi_device_async(spmv_mi355x_amg * M, int k, const void * in_dev, long ldin, void * out_dev, long ldout,
 		void * hip_stream);
 int  spmv_mi355x_amg_apply_multi(spmv_mi355x_amg * M, int k, const void * in_host, void * out_host);          /* blocking, ld = k */
@@ -1163,6 +1209,9 @@ int  spmv_mi355x_fsai_apply_multi_device_async(spmv_mi355x_fsai * F, int k, cons
 int  spmv_mi355x_fsai_apply_multi(spmv_mi355x_fsai * F, int k, const void * in_host, void * out_host);        /* blocking, ld = k */
 int  spmv_mi355x_pcg_tri_multi(spmv_mi355x_matrix * A, int k, const void * B_host, void * X_out_host,
 		const spmv_mi355x_tri_precond * M /* may be NULL; a scale alone */, double tol, long max_iterations,
+		double * history_out /* may be NULL: k * max_iterations doubles */, spmv_mi355x_pcg_tri_info * infos /* may be NULL: k of them */);
+int  spmv_mi355x_pcg_trsm_multi(spmv_mi355x_matrix * A, int k, const void * B_host, void * X_out_host,
+		const spmv_mi355x_tri_precond * M /* may be NULL; any parts */, double tol, long max_iterations,
 		double * history_out /* may be NULL: k * max_iterations doubles */, spmv_mi355x_pcg_tri_info * infos /* may be NULL: k of them */);
 int  spmv_mi355x_pcg_fsai_multi(spmv_mi355x_matrix * A, int k, const void * B_host, void * X_out_host, spmv_mi355x_fsai * F, double tol,
 		long max_iterations, double * history_out, spmv_mi355x_pcg_tri_info * infos);

@@ -8,10 +8,16 @@
 // trsv_chain_kernel: a run of consecutive thin levels in ONE workgroup, which walks them with a barrier in between.
 // trsv_blocked_kernel: the whole solve of a blocked handle, one workgroup per block of rows, each walking its own block's levels with
 // its block's part of x in LDS. No workgroup reads what another one writes.
+// Each has a k-column form (trsv_*_multi_kernel, at the end of this file) that solves T X = B for a chunk of 8, 4, 2 or 1 columns
+// of a row-major block in one pass over the same arrays. The single-vector kernels are not routed through those: they stay as they
+// are, and the k-column forms return their bits column by column.
 //
 // x is read and written inside one launch by the first two kernels (in the chain kernel the reads DEPEND on the writes), and b may be
 // x in all three: neither pointer is const, __restrict__ or loaded through a non-temporal / read-only path.
 
+#include <type_traits>
+
+#include "solvers_common.hpp"
 #include "trsv.hpp"
 
 namespace spmv {
@@ -317,6 +323,326 @@ launch_trsv_blocked(bool f32, bool unit, const TrsvArrays & a, long blocks, int 
 		            : blocked_launch<float, false>(a, blocks, threads, block_rows, n, b, x, st);
 	return unit ? blocked_launch<double, true>(a, blocks, threads, block_rows, n, b, x, st)
 	            : blocked_launch<double, false>(a, blocks, threads, block_rows, n, b, x, st);
+}
+
+// ------------------------------------------------------------------------------------------------ k columns
+// T X = B for a chunk of KC in {8, 4, 2, 1} columns of row-major blocks (row i at b + i * ldb and x + i * ldx, both pointers already
+// at the chunk's first column), over the same layout and the same plan. One lane still owns one row: it loads len, perm, the
+// diagonal and every (a, col) pair ONCE and keeps KC partial sums; the KC values of x[col] are one row of the block, gathered by
+// load_row (one vector load where the rows are KC-aligned, vb / vx, else KC scalar loads). Per column the fma chain runs in stored
+// order and ends in the same IEEE division, so column j returns the bits of the single kernels on column j whatever chunk it sits in.
+// The ordering between levels is that of the single kernels, word for word: the launch boundary (level), s_waitcnt vmcnt(0) +
+// __syncthreads() (chain), __syncthreads() over LDS (blocked). The head prefetch across the barrier is KEPT for every KC: the head
+// holds KC sums in place of one (16 VGPRs at KC = 8 in fp64), and nothing of it reads x.
+// In place (b == x, ldb == ldx): a lane reads its own row of b (in the head) before it writes its own row of x, and no other lane
+// touches that row's KC columns.
+// Registers: the gathers of one trip are U * KC values, so U shrinks as KC * sizeof(T) grows (trsv_unroll_multi); the order of the
+// fmas does not depend on U. profiles/r28_trsv_multi.txt has the compiler's resource table: no instantiation uses scratch.
+
+template <typename T, int KC>
+constexpr int
+trsv_unroll_multi()
+{
+	return KC * sizeof(T) > 32 ? 2 : TRSV_UNROLL;      // at most 64 bytes (16 VGPRs) of gathered x per entry slot
+}
+
+template <typename T>
+struct TrsvBlock {
+	const T * b;
+	T * x;
+	long ldb, ldx;
+	bool vb, vx;                      // every row of the chunk is KC-aligned: vector access
+};
+
+template <typename T, int KC>
+struct TrsvHeadMulti {
+	static constexpr int U = trsv_unroll_multi<T, KC>();
+	int cnt, i, lanes;
+	int64_t base;
+	T d;
+	T s[KC];
+	T a[U];
+	int c[U];
+};
+
+template <typename T, int U>
+__device__ __forceinline__ void
+trsv_entries_n(const TrsvTyped<T> & a, int64_t base, int lanes, int cnt, int k, T (&av)[U], int (&cv)[U])
+{
+	#pragma unroll
+	for (int j = 0; j < U; j++)
+	{
+		const int64_t e = base + (int64_t) (k + j < cnt ? k + j : k) * lanes;
+		av[j] = a.val[e];
+		cv[j] = a.col[e];
+	}
+}
+
+// xg + col * ldg is the row of x that a stored column names: the block itself (ldg = ldx), or the workgroup's part of it in LDS
+// (ldg = KC)
+template <typename T, int KC, int U>
+__device__ __forceinline__ void
+trsv_apply_multi(const T * xg, long ldg, bool vg, int cnt, int k, const T (&av)[U], const int (&cv)[U], T (&s)[KC])
+{
+	T xv[U][KC];
+	#pragma unroll
+	for (int j = 0; j < U; j++)
+		load_row(xv[j], xg + (long) cv[j] * ldg, vg);
+	#pragma unroll
+	for (int j = 0; j < U; j++)
+		if (k + j < cnt)
+		{
+			#pragma unroll
+			for (int c = 0; c < KC; c++)
+				s[c] = fma_t<T>(-av[j], xv[j][c], s[c]);
+		}
+}
+
+template <typename T, bool UNIT, int KC>
+__device__ __forceinline__ void
+trsv_head_multi(const TrsvTyped<T> & a, int pos0, int rows, int slice0, int q, const TrsvBlock<T> & blk, TrsvHeadMulti<T, KC> & h)
+{
+	constexpr int U = TrsvHeadMulti<T, KC>::U;
+	const int p = pos0 + q;
+	const int first = q & ~(TRSV_SLICE - 1);
+	h.lanes = rows - first < TRSV_SLICE ? rows - first : TRSV_SLICE;
+	h.base = a.slice_ptr[slice0 + q / TRSV_SLICE] + (q - first);
+	h.cnt = a.len[p];
+	h.i = a.perm[p];
+	load_row(h.s, blk.b + (long) h.i * blk.ldb, blk.vb);
+	h.d = UNIT ? (T) 1 : a.diag[p];
+	if (h.cnt > 0)
+		trsv_entries_n<T, U>(a, h.base, h.lanes, h.cnt, 0, h.a, h.c);
+	else
+	{
+		#pragma unroll
+		for (int j = 0; j < U; j++)
+		{
+			h.a[j] = 0;
+			h.c[j] = 0;
+		}
+	}
+}
+
+// the KC values of row h.i
+template <typename T, bool UNIT, int KC>
+__device__ __forceinline__ void
+trsv_value_multi(const TrsvTyped<T> & a, const TrsvHeadMulti<T, KC> & h, const T * xg, long ldg, bool vg, T (&v)[KC])
+{
+	constexpr int U = TrsvHeadMulti<T, KC>::U;
+	#pragma unroll
+	for (int c = 0; c < KC; c++)
+		v[c] = h.s[c];
+	if (h.cnt > 0)
+		trsv_apply_multi<T, KC, U>(xg, ldg, vg, h.cnt, 0, h.a, h.c, v);
+	for (int k = U; k < h.cnt; k += U)
+	{
+		T av[U];
+		int cv[U];
+		trsv_entries_n<T, U>(a, h.base, h.lanes, h.cnt, k, av, cv);
+		trsv_apply_multi<T, KC, U>(xg, ldg, vg, h.cnt, k, av, cv, v);
+	}
+	if (!UNIT)
+	{
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+			v[c] = v[c] / h.d;
+	}
+}
+
+template <typename T, bool UNIT, int KC>
+__device__ __forceinline__ void
+trsv_finish_multi(const TrsvTyped<T> & a, const TrsvHeadMulti<T, KC> & h, const TrsvBlock<T> & blk)
+{
+	T v[KC];
+	trsv_value_multi<T, UNIT, KC>(a, h, blk.x, blk.ldx, blk.vx, v);
+	store_row(blk.x + (long) h.i * blk.ldx, v, blk.vx);
+}
+
+template <typename T, bool UNIT, int KC>
+__device__ __forceinline__ void
+trsv_row_multi(const TrsvTyped<T> & a, int pos0, int rows, int slice0, int q, const TrsvBlock<T> & blk)
+{
+	TrsvHeadMulti<T, KC> h;
+	trsv_head_multi<T, UNIT, KC>(a, pos0, rows, slice0, q, blk, h);
+	trsv_finish_multi<T, UNIT, KC>(a, h, blk);
+}
+
+template <typename T, bool UNIT, int KC>
+__global__ __launch_bounds__(TRSV_LEVEL_BLOCK) void
+trsv_level_multi_kernel(TrsvTyped<T> a, int pos0, int rows, int slice0, TrsvBlock<T> blk)
+{
+	const int q = blockIdx.x * TRSV_LEVEL_BLOCK + threadIdx.x;
+	if (q < rows)
+		trsv_row_multi<T, UNIT, KC>(a, pos0, rows, slice0, q, blk);
+}
+
+// trsv_chain_kernel for KC columns: ONE workgroup, the same uniform loop, the same drain of the stores of x before the barrier
+template <typename T, bool UNIT, int KC>
+__global__ __launch_bounds__(TRSV_CHAIN_BLOCK_MAX) void
+trsv_chain_multi_kernel(TrsvTyped<T> a, int l0, int l1, TrsvBlock<T> blk)
+{
+	const int t = threadIdx.x;
+	int pos0 = a.level_ptr[l0], end = a.level_ptr[l0 + 1], slice0 = a.level_slice[l0];
+	TrsvHeadMulti<T, KC> h;
+	bool have = t < end - pos0;
+	if (have)
+		trsv_head_multi<T, UNIT, KC>(a, pos0, end - pos0, slice0, t, blk, h);
+	for (int l = l0; l < l1; l++)
+	{
+		const int rows = end - pos0;
+		if (have)
+			trsv_finish_multi<T, UNIT, KC>(a, h, blk);
+		for (int q = t + blockDim.x; q < rows; q += blockDim.x)
+			trsv_row_multi<T, UNIT, KC>(a, pos0, rows, slice0, q, blk);
+		if (l + 1 < l1)
+		{
+			pos0 = end;
+			end = a.level_ptr[l + 2];
+			slice0 = a.level_slice[l + 1];
+			have = t < end - pos0;
+			if (have)
+				trsv_head_multi<T, UNIT, KC>(a, pos0, end - pos0, slice0, t, blk, h);
+		}
+		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+		__syncthreads();
+	}
+}
+
+// trsv_blocked_kernel for KC columns: the block's part of X lives in LDS as xs[(i - row0) * KC + c], min(block_rows, n) * KC values,
+// and a stored block-local column names a row of KC values there. Nothing reads global x; only __syncthreads() orders the levels.
+template <typename T, bool UNIT, int KC>
+__global__ __launch_bounds__(TRSV_BLOCKED_THREADS_MAX) void
+trsv_blocked_multi_kernel(TrsvTyped<T> a, int block_rows, TrsvBlock<T> blk)
+{
+	extern __shared__ __align__(64) unsigned char trsv_lds_multi[];
+	T * xs = reinterpret_cast<T *>(trsv_lds_multi);
+	const int t = threadIdx.x;
+	const int row0 = blockIdx.x * block_rows;       // < n < 2^31
+	const int l0 = a.block_level[blockIdx.x], l1 = a.block_level[blockIdx.x + 1];
+	int pos0 = a.level_ptr[l0], end = a.level_ptr[l0 + 1], slice0 = a.level_slice[l0];
+	TrsvHeadMulti<T, KC> h;
+	bool have = t < end - pos0;
+	if (have)
+		trsv_head_multi<T, UNIT, KC>(a, pos0, end - pos0, slice0, t, blk, h);
+	for (int l = l0; l < l1; l++)
+	{
+		const int rows = end - pos0;
+		if (have)
+		{
+			T v[KC];
+			trsv_value_multi<T, UNIT, KC>(a, h, xs, KC, true, v);
+			store_row(xs + (h.i - row0) * KC, v, true);
+			store_row(blk.x + (long) h.i * blk.ldx, v, blk.vx);
+		}
+		for (int q = t + blockDim.x; q < rows; q += blockDim.x)
+		{
+			TrsvHeadMulti<T, KC> g;
+			T v[KC];
+			trsv_head_multi<T, UNIT, KC>(a, pos0, rows, slice0, q, blk, g);
+			trsv_value_multi<T, UNIT, KC>(a, g, xs, KC, true, v);
+			store_row(xs + (g.i - row0) * KC, v, true);
+			store_row(blk.x + (long) g.i * blk.ldx, v, blk.vx);
+		}
+		if (l + 1 < l1)
+		{
+			pos0 = end;
+			end = a.level_ptr[l + 2];
+			slice0 = a.level_slice[l + 1];
+			have = t < end - pos0;
+			if (have)
+				trsv_head_multi<T, UNIT, KC>(a, pos0, end - pos0, slice0, t, blk, h);
+		}
+		__syncthreads();
+	}
+}
+
+// the chunk's view of the two blocks: vector access when ld % KC == 0, c0 % KC == 0 and the block's base is aligned to KC values
+template <typename T, int KC>
+static TrsvBlock<T>
+trsv_block(const TrsvCols & c)
+{
+	auto vec = [&](const void * base, long ld) {
+		return KC > 1 && ld % KC == 0 && c.c0 % KC == 0 && (uintptr_t) base % (KC * sizeof(T)) == 0;
+	};
+	return TrsvBlock<T>{(const T *) c.b + c.c0, (T *) c.x + c.c0, c.ldb, c.ldx, vec(c.b, c.ldb), vec(c.x, c.ldx)};
+}
+
+// f(T(), bool_constant<UNIT>, integral_constant<int, KC>) for the handle's precision and diagonal and the chunk's width
+template <typename F>
+static int
+trsv_multi_dispatch(bool f32, bool unit, int kc, F && f)
+{
+	auto by_kc = [&](auto t, auto u) {
+		switch (kc)
+		{
+		case 8: return f(t, u, std::integral_constant<int, 8>());
+		case 4: return f(t, u, std::integral_constant<int, 4>());
+		case 2: return f(t, u, std::integral_constant<int, 2>());
+		default: return f(t, u, std::integral_constant<int, 1>());
+		}
+	};
+	if (f32)
+		return unit ? by_kc(float(), std::true_type()) : by_kc(float(), std::false_type());
+	return unit ? by_kc(double(), std::true_type()) : by_kc(double(), std::false_type());
+}
+
+int
+launch_trsv_level_multi(bool f32, bool unit, const TrsvArrays & a, const TrsvStep & s, const TrsvCols & c, hipStream_t st)
+{
+	return trsv_multi_dispatch(f32, unit, c.kc, [&](auto t, auto u, auto kc) {
+		using T = decltype(t);
+		constexpr bool UNIT = decltype(u)::value;
+		constexpr int KC = decltype(kc)::value;
+		const unsigned grid = (unsigned) ((s.rows + TRSV_LEVEL_BLOCK - 1) / TRSV_LEVEL_BLOCK);
+		hipLaunchKernelGGL((trsv_level_multi_kernel<T, UNIT, KC>), dim3(grid), dim3(TRSV_LEVEL_BLOCK), 0, st, typed<T>(a), s.pos0, s.rows,
+				s.slice0, trsv_block<T, KC>(c));
+		return 0;
+	});
+}
+
+int
+launch_trsv_chain_multi(bool f32, bool unit, const TrsvArrays & a, const TrsvStep & s, const TrsvCols & c, hipStream_t st)
+{
+	return trsv_multi_dispatch(f32, unit, c.kc, [&](auto t, auto u, auto kc) {
+		using T = decltype(t);
+		constexpr bool UNIT = decltype(u)::value;
+		constexpr int KC = decltype(kc)::value;
+		hipLaunchKernelGGL((trsv_chain_multi_kernel<T, UNIT, KC>), dim3(1), dim3(s.block), 0, st, typed<T>(a), s.l0, s.l1,
+				trsv_block<T, KC>(c));
+		return 0;
+	});
+}
+
+template <typename T, bool UNIT, int KC>
+static int
+blocked_multi_launch(const TrsvArrays & a, long blocks, int threads, long block_rows, long n, const TrsvCols & c, hipStream_t st)
+{
+	const int lds_bytes = (int) (std::min(block_rows, n) * KC * (long) sizeof(T));
+	// as in blocked_launch: the grant is per kernel function, so per instantiation, once per device
+	static int granted[64] = {0};
+	int dev = 0;
+	HIP_TRY(hipGetDevice(&dev));
+	dev = dev < 0 || dev >= 64 ? 0 : dev;
+	if (lds_bytes > granted[dev])
+	{
+		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&trsv_blocked_multi_kernel<T, UNIT, KC>),
+				hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+		granted[dev] = lds_bytes;
+	}
+	hipLaunchKernelGGL((trsv_blocked_multi_kernel<T, UNIT, KC>), dim3((unsigned) blocks), dim3(threads), lds_bytes, st, typed<T>(a),
+			(int) block_rows, trsv_block<T, KC>(c));
+	HIP_TRY(hipGetLastError());
+	return 0;
+}
+
+int
+launch_trsv_blocked_multi(bool f32, bool unit, const TrsvArrays & a, long blocks, int threads, long block_rows, long n,
+		const TrsvCols & c, hipStream_t st)
+{
+	return trsv_multi_dispatch(f32, unit, c.kc, [&](auto t, auto u, auto kc) {
+		return blocked_multi_launch<decltype(t), decltype(u)::value, decltype(kc)::value>(a, blocks, threads, block_rows, n, c, st);
+	});
 }
 
 }  // namespace spmv

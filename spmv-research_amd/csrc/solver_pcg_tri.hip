@@ -15,7 +15,7 @@
 // consumer re-sums the partials in the same order), a device `done` flag predicates every later vector kernel off, and the host
 // loop is ProgressGate of solvers_common.hpp.
 //
-// ONE BODY, SIX ENTRIES. spmv_mi355x_pcg_tri / _pcg_fsai / _pcg_amg and their _multi forms all run pcg_tri_solve over k columns: k
+// ONE BODY, SEVEN ENTRIES. spmv_mi355x_pcg_tri / _pcg_fsai / _pcg_amg, their _multi forms and _pcg_trsm_multi all run pcg_tri_solve over k columns: k
 // independent solves A x_j = b_j, each with the recurrences, stop rules and freeze of this comment, sharing every launch. This is not
 // block CG. The single entries are k = 1. Every vector is a row-major n x k block (ld = k); a vector kernel serves a chunk of KC in
 // {8, 4, 2, 1} columns c0.. and a thread owns row i of its chunk (solvers_common.hpp). The state is PcgTriState[2][k], the partials
@@ -23,7 +23,9 @@
 // differ:
 //   the matrix product q = A p   SpmvProduct (the single entries) or SpmmProduct (the _multi entries, also for k = 1)
 //   enqueue z = M^-1 r           TriApply (pcg_tri: the three parts of tri_precond.hpp on an n x 1 block, so triangular parts are served
-//                                for k = 1 only), ScaleApplyMulti (pcg_tri_multi: a Jacobi scale), FsaiApply / FsaiApplyMulti (the two
+//                                by the single-vector kernels), ScaleApplyMulti (pcg_tri_multi: a Jacobi scale; a triangular part is
+//                                refused there), TriApplyMulti (pcg_trsm_multi: the three parts on the n x k block, the triangular ones
+//                                by the k-column solve of trsv.hip, a chunk of columns per pass), FsaiApply / FsaiApplyMulti (the two
 //                                SpMVs or SpMMs G^t (G r) of an fsai handle, fsai.hip), AmgApply / AmgApplyMulti (one V cycle of an amg
 //                                handle, amg.hip)
 // so a single solve uses neither the SpMM nor a k-column apply, which are other kernels and allocate k-column blocks of their own.
@@ -420,25 +422,6 @@ pcg_tri_final_kernel(const T * __restrict__ b, T * __restrict__ q, const T * __r
 	store_partials_n<KC, 2>(part, c0, {T_ER, T_XX}, acc, ~0u);
 }
 
-// z = scale o r for the chunk's columns: tri_scale_kernel's product per element
-template <typename T, int KC>
-__global__ __launch_bounds__(VB) void
-pcg_tri_scale_multi_kernel(const T * __restrict__ scale, const T * __restrict__ in, T * __restrict__ out, long n, long ld, int c0)
-{
-	const bool vec = ld % KC == 0 && c0 % KC == 0;
-	GRID_STRIDE(i, n)
-	{
-		const long o = i * ld + c0;
-		const T si = scale[i];
-		T v[KC];
-		load_row(v, in + o, vec);
-		#pragma unroll
-		for (int c = 0; c < KC; c++)
-			v[c] = si * v[c];
-		store_row(out + o, v, vec);
-	}
-}
-
 // ------------------------------------------------------------------------------------------------ host side
 
 // The solve of k columns behind all six entries. PRE: there is a preconditioner. scale_host: the scale of M or NULL; the solve keeps
@@ -737,6 +720,17 @@ struct ScaleApplyMulti {
 	}
 };
 
+// Z = second^-1 (scale o (first^-1 R)) of pcg_trsm_multi: the three parts of tri_precond.hpp on the n x k block, the triangular ones
+// as k-column solves. They know nothing of `done` and write only Z.
+struct TriApplyMulti {
+	spmv_mi355x_trsv * first, * second;
+	template <typename T>
+	int operator()(const T * r, T * z, const T * scale, long n, int k, const std::vector<Chunk> & chunks, dim3 grid, hipStream_t stream) const
+	{
+		return tri_precond_enqueue_multi<T>(first, scale, second, r, z, n, k, chunks, grid, stream);
+	}
+};
+
 // z = G^t (G r) of pcg_fsai. The two SpMVs write the handle's scratch vector and z, nothing else.
 struct FsaiApply {
 	spmv_mi355x_fsai * F;
@@ -846,6 +840,24 @@ spmv_mi355x_pcg_tri_multi(spmv_mi355x_matrix * A, int k, const void * B_host, vo
 	const void * scale = M ? M->scale_host : nullptr;
 	return pcg_tri_dispatch("pcg_tri_multi", A, k, B_host, X_out_host, scale != nullptr, scale, SpmmProduct(), ScaleApplyMulti(), tol,
 			max_iterations, history_out, infos);
+}
+
+// pcg_tri_multi without its refusal: any M, the triangular parts through the k-column solve. With M = NULL or a scale alone the
+// launches are those of pcg_tri_multi (TriApplyMulti then enqueues the scale kernel of ScaleApplyMulti and nothing else).
+extern "C" int
+spmv_mi355x_pcg_trsm_multi(spmv_mi355x_matrix * A, int k, const void * B_host, void * X_out_host, const spmv_mi355x_tri_precond * M,
+		double tol, long max_iterations, double * history_out, spmv_mi355x_pcg_tri_info * infos)
+{
+	using namespace spmv;
+	if (!pcg_tri_arguments_ok("pcg_trsm_multi", true, A, k, B_host, X_out_host, tol, max_iterations, infos, false))
+		return 1;
+	if (M && (!tri_precond_size_ok("pcg_trsm_multi", M)
+			|| !tri_precond_parts_ok("pcg_trsm_multi", M, spmv_mi355x_cols(A), spmv_mi355x_precision(A), spmv_mi355x_device(A))))
+		return 1;
+	const TriApplyMulti apply = {M ? M->first : nullptr, M ? M->second : nullptr};
+	const void * scale = M ? M->scale_host : nullptr;
+	return pcg_tri_dispatch("pcg_trsm_multi", A, k, B_host, X_out_host, apply.first || scale || apply.second, scale, SpmmProduct(), apply,
+			tol, max_iterations, history_out, infos);
 }
 
 extern "C" int

@@ -2,7 +2,8 @@
 // checks of the struct, with the caller's name as the prefix of every message, and the enqueue of
 //     z = second^-1 ( scale o ( first^-1 in ) )
 // part by part on one stream. Every part may be absent. The solves are spmv_mi355x_trsv handles of any kind; the scale is one
-// elementwise kernel. Nothing here knows a solver's stop flag: everything written is z.
+// elementwise kernel. Nothing here knows a solver's stop flag: everything written is z. tri_precond_enqueue_multi is the same on
+// n x k blocks (pcg_trsm_multi), with the k-column solve of trsv.hip for the triangular parts.
 #pragma once
 
 #include <cmath>
@@ -105,6 +106,53 @@ tri_precond_enqueue(spmv_mi355x_trsv * first, const T * scale, spmv_mi355x_trsv 
 	}
 	if (second)
 		ABI_TRY(spmv_mi355x_trsv_solve_device_async(second, src, z, stream));
+	return 0;
+}
+
+// out = scale o in for the chunk's columns of row-major n x k blocks: tri_scale_kernel's product per element; `in` may be `out`
+template <typename T, int KC>
+__global__ __launch_bounds__(VB) void
+pcg_tri_scale_multi_kernel(const T * __restrict__ scale, const T * in, T * out, long n, long ld, int c0)
+{
+	const bool vec = ld % KC == 0 && c0 % KC == 0;
+	GRID_STRIDE(i, n)
+	{
+		const long o = i * ld + c0;
+		const T si = scale[i];
+		T v[KC];
+		load_row(v, in + o, vec);
+		#pragma unroll
+		for (int c = 0; c < KC; c++)
+			v[c] = si * v[c];
+		store_row(out + o, v, vec);
+	}
+}
+
+// Z = second^-1 (scale o (first^-1 IN)) for the k columns of row-major n x k blocks with ld = k, enqueued on `stream`; IN may be Z.
+// The triangular parts are k-column solves (spmv_mi355x_trsv_solve_multi_device_async, chunked as the handle needs), the scale is
+// one launch per chunk of `chunks`. Per column every operation is that of tri_precond_enqueue. With no part nothing is enqueued.
+template <typename T>
+static int
+tri_precond_enqueue_multi(spmv_mi355x_trsv * first, const T * scale, spmv_mi355x_trsv * second, const T * in, T * z, long n, int k,
+		const std::vector<Chunk> & chunks, dim3 grid, hipStream_t stream)
+{
+	const T * src = in;
+	if (first)
+	{
+		ABI_TRY(spmv_mi355x_trsv_solve_multi_device_async(first, k, src, k, z, k, stream));
+		src = z;
+	}
+	if (scale)
+	{
+		for_chunks(chunks, [&](int c0, auto kc) {
+			constexpr int KC = decltype(kc)::value;
+			hipLaunchKernelGGL((pcg_tri_scale_multi_kernel<T, KC>), grid, dim3(VB), 0, stream, scale, src, z, n, (long) k, c0);
+			return 0;
+		});
+		src = z;
+	}
+	if (second)
+		ABI_TRY(spmv_mi355x_trsv_solve_multi_device_async(second, k, src, k, z, k, stream));
 	return 0;
 }
 

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "handle.hpp"
+#include "solvers_common.hpp"
 #include "trsv.hpp"
 
 namespace spmv {
@@ -386,6 +387,10 @@ trsv_free(spmv_mi355x_trsv * H)
 		(void) hipFree(H->d_b);
 	if (H->d_x)
 		(void) hipFree(H->d_x);
+	if (H->d_bk)
+		(void) hipFree(H->d_bk);
+	if (H->d_xk)
+		(void) hipFree(H->d_xk);
 	delete H;
 }
 
@@ -672,6 +677,183 @@ spmv_mi355x_time_trsv_device(spmv_mi355x_trsv * T, const void * b_dev, void * x_
 	HIP_TRY(hipEventRecord(e0, st));
 	for (int i = 0; i < iters; i++)
 		if (spmv_mi355x_trsv_solve_device_async(T, b_dev, x_dev, hip_stream))
+			return 1;
+	HIP_TRY(hipEventRecord(e1, st));
+	HIP_TRY(hipEventSynchronize(e1));
+	float ms = 0;
+	HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+	(void) hipEventDestroy(e0);
+	(void) hipEventDestroy(e1);
+	*ms_out = iters > 0 ? (double) ms / iters : 0;
+	return 0;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ k columns
+
+namespace spmv {
+
+// The passes of a k-column solve. A global handle: column_chunks(k), 8s and then the binary remainder. A blocked handle: the same
+// with Kmax = trsv_blocked_kmax() in the place of 8, since a workgroup keeps its rows of the chunk in LDS.
+static std::vector<Chunk>
+trsv_multi_chunks(const spmv_mi355x_trsv * T, int k)
+{
+	if (!T->block_rows)
+		return column_chunks(k);
+	const int kmax = trsv_blocked_kmax(T->block_rows, T->n, T->f32);
+	std::vector<Chunk> out;
+	int c0 = 0;
+	for (; k - c0 >= kmax; c0 += kmax)
+		out.push_back({c0, kmax});
+	for (int w = kmax / 2; w >= 1; w /= 2)
+		if (k - c0 >= w)
+		{
+			out.push_back({c0, w});
+			c0 += w;
+		}
+	return out;
+}
+
+// the refusals of the k-column solve entries, all on the host, in the header's order
+static bool
+trsv_multi_arguments_ok(const char * what, const spmv_mi355x_trsv * T, int k, const void * b, long ldb, const void * x, long ldx)
+{
+	if (!T)
+		set_error("%s: NULL argument ( T )", what);
+	else if (k < 1)
+		set_error("%s: k = %d: at least one column is needed", what, k);
+	else if (ldb < k || ldx < k)
+		set_error("%s: ldb = %ld, ldx = %ld: a leading dimension must be at least k = %d", what, ldb, ldx, k);
+	else if (b == x && ldb != ldx)
+		set_error("%s: b == x (in place) needs ldb == ldx (got %ld and %ld)", what, ldb, ldx);
+	else if (T->n > 0 && (!b || !x))
+		set_error("%s: NULL argument (%s%s )", what, !b ? " b" : "", !x ? " x" : "");
+	else
+		return true;
+	return false;
+}
+
+}  // namespace spmv
+
+extern "C" {
+
+int
+spmv_mi355x_trsv_solve_multi_device_async(spmv_mi355x_trsv * T, int k, const void * b_dev, long ldb, void * x_dev, long ldx,
+		void * hip_stream)
+{
+	if (!trsv_multi_arguments_ok("trsv_solve_multi", T, k, b_dev, ldb, x_dev, ldx))
+		return 1;
+	if (T->n == 0)
+		return 0;
+	// One contiguous column is a vector: the single solve with its kernels, so k = 1 costs what the single call costs. The KC = 1
+	// kernels serve a column of a wider block (ld > 1), such as the last one of k = 9; profiles/r28_trsv_multi.txt has their cost.
+	if (k == 1 && ldb == 1 && ldx == 1)
+		return spmv_mi355x_trsv_solve_device_async(T, b_dev, x_dev, hip_stream);
+	int cur = -1;
+	HIP_TRY(hipGetDevice(&cur));
+	if (cur != T->device)
+		HIP_TRY(hipSetDevice(T->device));
+	hipStream_t st = (hipStream_t) hip_stream;
+	const bool unit = T->diag == SPMV_MI355X_DIAG_UNIT;
+	for (const Chunk & ch : trsv_multi_chunks(T, k))
+	{
+		const TrsvCols cols = {b_dev, x_dev, ldb, ldx, ch.c0, ch.kc};
+		if (T->block_rows)
+		{
+			if (launch_trsv_blocked_multi(T->f32, unit, T->arr, T->blocks, T->threads, T->block_rows, T->n, cols, st))
+				return 1;
+			continue;
+		}
+		for (const TrsvStep & s : T->plan)
+			s.chain ? launch_trsv_chain_multi(T->f32, unit, T->arr, s, cols, st) : launch_trsv_level_multi(T->f32, unit, T->arr, s, cols, st);
+	}
+	HIP_TRY(hipGetLastError());
+	return 0;
+}
+
+int
+spmv_mi355x_trsv_solve_multi(spmv_mi355x_trsv * T, int k, const void * B_host, void * X_host)
+{
+	if (!trsv_multi_arguments_ok("trsv_solve_multi", T, k, B_host, k, X_host, k))
+		return 1;
+	if (T->n == 0)
+		return 0;
+	HIP_TRY(hipSetDevice(T->device));
+	if (k > T->block_k)
+	{
+		// the blocks of an earlier, smaller k may still be read by a solve in flight
+		HIP_TRY(hipDeviceSynchronize());
+		for (void ** p : {&T->d_bk, &T->d_xk})
+		{
+			if (*p)
+				(void) hipFree(*p);
+			*p = nullptr;
+		}
+		T->block_k = 0;
+		const size_t grown = (size_t) T->n * (size_t) k * (T->f32 ? 4 : 8);
+		if (dev_alloc_bytes(&T->d_bk, grown) || dev_alloc_bytes(&T->d_xk, grown))
+			return 1;
+		T->block_k = k;
+	}
+	const size_t bytes = (size_t) T->n * (size_t) k * (T->f32 ? 4 : 8);
+	HIP_TRY(hipMemcpyAsync(T->d_bk, B_host, bytes, hipMemcpyHostToDevice, nullptr));
+	if (spmv_mi355x_trsv_solve_multi_device_async(T, k, T->d_bk, k, T->d_xk, k, nullptr))
+		return 1;
+	HIP_TRY(hipMemcpyAsync(X_host, T->d_xk, bytes, hipMemcpyDeviceToHost, nullptr));
+	HIP_TRY(hipStreamSynchronize(nullptr));
+	return 0;
+}
+
+int
+spmv_mi355x_trsv_solve_multi_plan(const spmv_mi355x_trsv * T, int k, long * matrix_passes_out, long * launches_out, int * max_chunk_out)
+{
+	if (!T)
+	{
+		set_error("trsv_solve_multi_plan: NULL argument ( T )");
+		return 1;
+	}
+	if (k < 1)
+	{
+		set_error("trsv_solve_multi_plan: k = %d: at least one column is needed", k);
+		return 1;
+	}
+	long passes = 0, launches = 0;
+	int widest = 0;                   // the widest chunk the handle serves, whatever k is
+	if (T->n > 0)
+	{
+		passes = (long) trsv_multi_chunks(T, k).size();
+		launches = T->block_rows ? passes : passes * (long) T->plan.size();
+		widest = T->block_rows ? trsv_blocked_kmax(T->block_rows, T->n, T->f32) : MAX_KC;
+	}
+	if (matrix_passes_out)
+		*matrix_passes_out = passes;
+	if (launches_out)
+		*launches_out = launches;
+	if (max_chunk_out)
+		*max_chunk_out = widest;
+	return 0;
+}
+
+int
+spmv_mi355x_time_trsv_multi_device(spmv_mi355x_trsv * T, int k, const void * b_dev, long ldb, void * x_dev, long ldx, int iters,
+		void * hip_stream, double * ms_out)
+{
+	if (!T || !ms_out)
+	{
+		set_error("time_trsv_multi_device: NULL %s", !T ? "handle" : "ms_per_iter_out");
+		return 1;
+	}
+	if (!trsv_multi_arguments_ok("trsv_solve_multi", T, k, b_dev, ldb, x_dev, ldx))
+		return 1;
+	HIP_TRY(hipSetDevice(T->device));
+	hipStream_t st = (hipStream_t) hip_stream;
+	hipEvent_t e0, e1;
+	HIP_TRY(hipEventCreate(&e0));
+	HIP_TRY(hipEventCreate(&e1));
+	HIP_TRY(hipEventRecord(e0, st));
+	for (int i = 0; i < iters; i++)
+		if (spmv_mi355x_trsv_solve_multi_device_async(T, k, b_dev, ldb, x_dev, ldx, hip_stream))
 			return 1;
 	HIP_TRY(hipEventRecord(e1, st));
 	HIP_TRY(hipEventSynchronize(e1));

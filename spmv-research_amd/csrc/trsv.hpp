@@ -60,6 +60,34 @@ int launch_trsv_chain(bool f32, bool unit, const TrsvArrays & a, const TrsvStep 
 int launch_trsv_blocked(bool f32, bool unit, const TrsvArrays & a, long blocks, int threads, long block_rows, long n, const void * b,
 		void * x, hipStream_t st);
 
+// K COLUMNS. One chunk of a k-column solve: the columns c0 .. c0 + kc - 1, kc in {8, 4, 2, 1}, of the row-major blocks b and x
+// (row i at b + i * ldb and x + i * ldx, counted in values; b may be x when ldb == ldx). A chunk is one pass over the plan.
+struct TrsvCols {
+	const void * b;
+	void * x;
+	long ldb, ldx;
+	int c0, kc;
+};
+
+constexpr long TRSV_LDS_BYTES = 160 * 1024;       // what a workgroup may declare: the window rule of the SpMM
+
+int launch_trsv_level_multi(bool f32, bool unit, const TrsvArrays & a, const TrsvStep & s, const TrsvCols & c, hipStream_t st);
+int launch_trsv_chain_multi(bool f32, bool unit, const TrsvArrays & a, const TrsvStep & s, const TrsvCols & c, hipStream_t st);
+// min(block_rows, n) * kc values of x in LDS per workgroup: the caller keeps kc at or below trsv_blocked_kmax()
+int launch_trsv_blocked_multi(bool f32, bool unit, const TrsvArrays & a, long blocks, int threads, long block_rows, long n,
+		const TrsvCols & c, hipStream_t st);
+
+// the widest chunk of a blocked handle: the largest KC in {8, 4, 2, 1} whose part of X fits in LDS
+inline int
+trsv_blocked_kmax(long block_rows, long n, bool f32)
+{
+	const long rows = block_rows < n ? block_rows : n;
+	int kc = 8;
+	while (kc > 1 && rows * kc * (f32 ? 4 : 8) > TRSV_LDS_BYTES)
+		kc /= 2;
+	return kc;
+}
+
 }  // namespace spmv
 
 struct spmv_mi355x_trsv {
@@ -74,6 +102,8 @@ struct spmv_mi355x_trsv {
 	spmv::TrsvArrays arr = {};
 	void * owned[9] = {};                 // the device arrays behind arr
 	void * d_b = nullptr, * d_x = nullptr;     // the vectors of the host-buffer solve, allocated at its first call
+	void * d_bk = nullptr, * d_xk = nullptr;   // the n x block_k blocks of the host-buffer k-column solve, regrown for a larger k
+	int block_k = 0;
 	double mem_footprint = 0;
 };
 

@@ -80,6 +80,8 @@ SYMBOLS = [
     "spmv_mi355x_amg_apply_multi_device_async", "spmv_mi355x_amg_apply_multi", "spmv_mi355x_amg_apply_multi_plan",
     "spmv_mi355x_fsai_apply_multi_device_async", "spmv_mi355x_fsai_apply_multi",
     "spmv_mi355x_pcg_tri_multi", "spmv_mi355x_pcg_fsai_multi", "spmv_mi355x_pcg_amg_multi",
+    "spmv_mi355x_trsv_solve_multi_device_async", "spmv_mi355x_trsv_solve_multi", "spmv_mi355x_trsv_solve_multi_plan",
+    "spmv_mi355x_time_trsv_multi_device", "spmv_mi355x_pcg_trsm_multi",
 ]
 
 _lib = None
@@ -150,9 +152,19 @@ def lib():
             getattr(L, f).argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.spmv_mi355x_amg_apply_multi_plan.restype = C.c_int
         L.spmv_mi355x_amg_apply_multi_plan.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_long), C.POINTER(C.c_long)]
-        L.spmv_mi355x_pcg_tri_multi.restype = C.c_int
-        L.spmv_mi355x_pcg_tri_multi.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(TriPrecond), C.c_double, C.c_long,
-                                                C.c_void_p, C.c_void_p]
+        for f in ("spmv_mi355x_pcg_tri_multi", "spmv_mi355x_pcg_trsm_multi"):
+            getattr(L, f).restype = C.c_int
+            getattr(L, f).argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(TriPrecond), C.c_double, C.c_long,
+                                      C.c_void_p, C.c_void_p]
+        L.spmv_mi355x_trsv_solve_multi_device_async.restype = C.c_int
+        L.spmv_mi355x_trsv_solve_multi_device_async.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_void_p]
+        L.spmv_mi355x_trsv_solve_multi.restype = C.c_int
+        L.spmv_mi355x_trsv_solve_multi.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.spmv_mi355x_trsv_solve_multi_plan.restype = C.c_int
+        L.spmv_mi355x_trsv_solve_multi_plan.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_int)]
+        L.spmv_mi355x_time_trsv_multi_device.restype = C.c_int
+        L.spmv_mi355x_time_trsv_multi_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_int,
+                                                         C.c_void_p, C.POINTER(C.c_double)]
         for f in ("spmv_mi355x_pcg_fsai_multi", "spmv_mi355x_pcg_amg_multi"):
             getattr(L, f).restype = C.c_int
             getattr(L, f).argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_long, C.c_void_p,
@@ -383,6 +395,36 @@ class TriangularSolve:
         ms = C.c_double()
         _check(lib().spmv_mi355x_time_trsv_device(self.h, C.c_void_p(b_ptr), C.c_void_p(x_ptr), C.c_int(iters), C.c_void_p(stream or 0),
                                                   C.byref(ms)))
+        return ms.value
+
+    def solve_multi(self, B):
+        """X of T X = B for a host block B of shape (n, k), column j bit-identical to solve(B[:, j]) (spmv_mi355x_trsv_solve_multi;
+        blocking)"""
+        B = np.ascontiguousarray(B, self.dtype)
+        if B.ndim != 2 or B.shape[0] != self.n or B.shape[1] < 1:
+            raise ValueError(f"B must have shape ({self.n}, k) with k >= 1, got {B.shape}")
+        k = B.shape[1]
+        X = np.full((max(self.n, 1), k), np.nan, self.dtype)
+        _check(lib().spmv_mi355x_trsv_solve_multi(self.h, k, _p(B), _p(X)))
+        return X[:self.n]
+
+    def solve_multi_device(self, k, b_ptr, ldb, x_ptr, ldx, stream=None):
+        """The same on device pointers of row-major blocks (row i at ptr + i * ld values; b_ptr == x_ptr with ldb == ldx: in place),
+        enqueued on `stream` (spmv_mi355x_trsv_solve_multi_device_async)"""
+        _check(lib().spmv_mi355x_trsv_solve_multi_device_async(self.h, k, C.c_void_p(b_ptr), ldb, C.c_void_p(x_ptr), ldx,
+                                                               C.c_void_p(stream or 0)))
+
+    def solve_multi_plan(self, k):
+        """dict(matrix_passes, launches, max_chunk) of a k-column solve (spmv_mi355x_trsv_solve_multi_plan; host only)"""
+        passes, launches, widest = C.c_long(), C.c_long(), C.c_int()
+        _check(lib().spmv_mi355x_trsv_solve_multi_plan(self.h, k, C.byref(passes), C.byref(launches), C.byref(widest)))
+        return dict(matrix_passes=passes.value, launches=launches.value, max_chunk=widest.value)
+
+    def time_multi_device(self, k, b_ptr, ldb, x_ptr, ldx, iters, stream=None):
+        """ms per k-column solve of `iters` back-to-back solves, timed with HIP events (spmv_mi355x_time_trsv_multi_device)"""
+        ms = C.c_double()
+        _check(lib().spmv_mi355x_time_trsv_multi_device(self.h, k, C.c_void_p(b_ptr), ldb, C.c_void_p(x_ptr), ldx, iters,
+                                                        C.c_void_p(stream or 0), C.byref(ms)))
         return ms.value
 
     def close(self):
@@ -1383,6 +1425,32 @@ class Matrix:
                 M, scale = _tri_precond(precond, self.m, self.dtype)
             _check(lib().spmv_mi355x_pcg_tri_multi(self.h, k, _p(B), _p(X), None if M is None else C.byref(M), tol, max_iterations, hp,
                                                    infos))
+        out = []
+        for j in range(k):
+            d = {f: getattr(infos[j], f) for f, _ in PcgTriInfo._fields_ if f != "struct_size"}
+            d["x"] = X[:self.m, j].copy()
+            d["history"] = hist[j * max_iterations:j * max_iterations + d["iterations"]].copy() if history else None
+            out.append(d)
+        return out
+
+    def pcg_trsm_multi(self, B, precond=None, tol=1e-12, max_iterations=1000, history=True):
+        """pcg_tri for the k columns of B (shape (rows, k)) with ANY (first, scale, second) that pcg_tri takes, e.g. what sgs_precond
+        returns: the triangular parts run as k-column solves (spmv_mi355x_pcg_trsm_multi). A list of k dicts shaped like pcg_tri's,
+        element j bit-identical to pcg_tri(B[:, j], precond) on a deterministic handle; spmv_calls and seconds are the call's."""
+        B = np.ascontiguousarray(B, self.dtype)
+        if B.ndim != 2 or B.shape[0] != self.m or B.shape[1] < 1:
+            raise ValueError(f"B must have shape ({self.m}, k) with k >= 1, got {B.shape}")
+        k = B.shape[1]
+        M = None
+        if precond is not None:
+            M, scale = _tri_precond(precond, self.m, self.dtype)
+        X = np.zeros((max(self.m, 1), k), self.dtype)
+        hist = np.zeros(k * max(max_iterations, 1), np.float64) if history else None
+        infos = (PcgTriInfo * k)()
+        for j in range(k):
+            infos[j].struct_size = C.sizeof(PcgTriInfo)
+        _check(lib().spmv_mi355x_pcg_trsm_multi(self.h, k, _p(B), _p(X), None if M is None else C.byref(M), tol, max_iterations,
+                                                _p(hist) if history else None, infos))
         out = []
         for j in range(k):
             d = {f: getattr(infos[j], f) for f, _ in PcgTriInfo._fields_ if f != "struct_size"}

@@ -2,6 +2,8 @@
 (Matrix.pcg_tri) on the same handles in the same run, and the same for the AMG cycle alone (Amg.apply_multi_device against k calls of
 Amg.apply_device). Follows tools/amg_bench.py: one sell_c_sigma handle of A, and for every preconditioner
     none | jacobi = (None, 1 / diag(A), None) | fsai = Fsai on tril(A) | amg t=<theta> = Amg with every theta of --theta
+(--precond picks among them; sgs, not in the default list, adds the global SGS of A, sgs_precond, and with --block-rows a blocked
+SGS per size: their k-column solves go through Matrix.pcg_trsm_multi and the k-column triangular solve)
 and every k of --rhs, in one process, alternating window by window (window 0 warms every leg up and is dropped):
   solve:  per window the kmax single solves of the columns of B (seeded uniform), each to --tol with the cap --max-iterations, then
           the k-column solve of B[:, :k] for every k. Reported per k: info.seconds of the k-column solve over k, the mean of
@@ -14,6 +16,7 @@ Each figure is the median over the windows with its min .. max spread. No thresh
 
     python tools/pcg_tri_multi_bench.py                                   # grid2d2000:f64 and stencil160:f64, k = 1, 2, 4, 8
     python tools/pcg_tri_multi_bench.py --runs grid2d2000:f64 --rhs 1,4 --theta 0.08
+    python tools/pcg_tri_multi_bench.py --runs stencil160:f64 --precond sgs,amg --block-rows 4096 --theta 0.08
 One JSON line per (workload, preconditioner, k), and two tables at the end."""
 import argparse
 import json
@@ -51,9 +54,19 @@ def run(E, torch, workload, dts, args):
     rows_of = np.repeat(np.arange(n), np.diff(rp))
     diag = np.zeros(n)
     diag[rows_of[ci == rows_of]] = va[ci == rows_of]
-    variants = [("none", None), ("jacobi", (None, (1.0 / diag).astype(np_dtype), None)),
-                ("fsai", E.Fsai(rp, ci, va, n, None, "sell_c_sigma", np_dtype))]
-    for theta in args.theta:
+    variants = []
+    if "none" in args.precond:
+        variants.append(("none", None))
+    if "jacobi" in args.precond:
+        variants.append(("jacobi", (None, (1.0 / diag).astype(np_dtype), None)))
+    if "sgs" in args.precond:                                 # the global SGS of A, and a blocked one per --block-rows value
+        for size in [None] + args.block_rows:
+            variants.append(("sgs" if size is None else f"sgs B={size}", E.sgs_precond(rp, ci, va, n, dtype=np_dtype, block_rows=size)))
+            print(f"# built {variants[-1][0]}: launches per solve {variants[-1][1][0].info['launches']} + {variants[-1][1][2].info['launches']}",
+                  flush=True)
+    if "fsai" in args.precond:
+        variants.append(("fsai", E.Fsai(rp, ci, va, n, None, "sell_c_sigma", np_dtype)))
+    for theta in args.theta if "amg" in args.precond else ():
         variants.append((f"amg t={theta:g}", E.Amg(rp, ci, va, n, "sell_c_sigma", np_dtype, theta=theta, sweeps=args.sweeps)))
         info = variants[-1][1].info()
         print(f"# built {variants[-1][0]}: rows {info['rows']}, coarse {info['coarse']}, spmvs {info['spmvs_per_apply']}, "
@@ -90,8 +103,8 @@ def run(E, torch, workload, dts, args):
         for name, M in variants:
             single = [MA.pcg_tri(c, precond=M, tol=args.tol, max_iterations=args.max_iterations, history=False) for c in cols]
             for k in args.rhs:
-                got = MA.pcg_tri_multi(np.ascontiguousarray(B[:, :k]), precond=M, tol=args.tol, max_iterations=args.max_iterations,
-                                       history=False)
+                solve = MA.pcg_trsm_multi if name.startswith("sgs") else MA.pcg_tri_multi
+                got = solve(np.ascontiguousarray(B[:, :k]), precond=M, tol=args.tol, max_iterations=args.max_iterations, history=False)
                 t_m = got[0]["seconds"] / k
                 t_s = float(np.mean([s["seconds"] for s in single[:k]]))
                 cm = cs = float("nan")
@@ -122,8 +135,9 @@ def run(E, torch, workload, dts, args):
             print(json.dumps(rec), flush=True)
             rows.append(rec)
     for _, M in variants:
-        if hasattr(M, "close"):
-            M.close()
+        for h in M if isinstance(M, tuple) else (M,):
+            if hasattr(h, "close"):
+                h.close()
     MA.close()
     return rows
 
@@ -132,6 +146,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", default="grid2d2000:f64,stencil160:f64", help="stencil<N>:f64|f32 or grid2d<N>:f64|f32, comma separated")
     ap.add_argument("--rhs", default="1,2,4,8", help="the column counts k")
+    ap.add_argument("--precond", default="none,jacobi,fsai,amg", help="which of none, jacobi, sgs, fsai, amg to run; sgs is the global "
+                    "SGS of A through Matrix.pcg_trsm_multi")
+    ap.add_argument("--block-rows", default="", help="with --precond sgs: a blocked SGS per size beside the global one, e.g. 4096")
     ap.add_argument("--theta", default="0.08,0.03", help="the strength thresholds of the AMG variants")
     ap.add_argument("--sweeps", type=int, default=1, help="nu of the V(nu, nu) cycle")
     ap.add_argument("--windows", type=int, default=7)
@@ -145,6 +162,10 @@ def main():
         ap.error("--windows: at least 5")
     args.rhs = [int(v) for v in args.rhs.split(",") if v != ""]
     args.theta = [float(v) for v in args.theta.split(",") if v != ""]
+    args.precond = [v for v in args.precond.split(",") if v != ""]
+    if set(args.precond) - {"none", "jacobi", "sgs", "fsai", "amg"}:
+        ap.error("--precond: a comma separated list of none, jacobi, sgs, fsai, amg")
+    args.block_rows = [int(v) for v in args.block_rows.split(",") if v != ""]
     os.environ.setdefault("OMP_NUM_THREADS", "16")
     import torch
     if not torch.cuda.is_available():

@@ -14,11 +14,15 @@ size, in the same process and the same alternating windows: per size the blocks,
 triangle's off-diagonal entries that the blocks drop, ms, the ratio to the floor and the ratio to the global plan of the same run
 (the first --chain-rows value). A blocked handle solves a different, easier system: the ratio says what the launch plan costs, what
 the dropped entries cost a solver is tools/gmres_bench.py's question.
+With --rhs the k-column solve (spmv_mi355x_trsv_solve_multi_device_async) of the first --chain-rows handle and of every --block-rows
+handle is timed for each k beside the single solve of the same handle, again in the same windows: per k the passes and launches of
+the plan, ms per solve, and ms per column over the single solve's ms (1 / k when a pass costs what a single solve costs).
 
     python tools/trsv_bench.py                                       # cant, nlpkkt240, stencil160, fp64
     python tools/trsv_bench.py --runs cant:f64,cant:f32,stencil40:f64 --windows 7 --chain-rows 64,256,1024,4096
     python tools/trsv_bench.py --runs nlpkkt240:f64 --scale 0.25
     python tools/trsv_bench.py --runs cant:f64,cant:f32,stencil160:f64,nlpkkt240:f64 --chain-rows 256 --block-rows 1024,2048,4096,8192,16384
+    python tools/trsv_bench.py --runs stencil160:f64 --chain-rows 256 --block-rows 1024,2048,4096 --rhs 1,2,4,8
 One JSON line per run and a table at the end.
 """
 import argparse
@@ -95,10 +99,22 @@ def run(E, torch, name, rp, ci, va, n, dts, data, args):
         reps[c] = int(min(200, max(3, np.ceil(args.leg_ms / max(one, 1e-3)))))
     legs = {"spmv": []}
     legs.update({c: [] for c in handles})
+    # --rhs: the k-column solve of every handle beside its single solve, in the same windows. One n x max(k) block serves every k
+    # with ld = k. A k-column leg runs a k-th of the single leg's solves (at least 3), so a leg that costs k times as much lasts as long.
+    multi = {c: T for c, T in handles.items() if args.rhs and (isinstance(c, tuple) or c == args.chain_rows[0])}
+    if multi:
+        bk = (torch.rand(n * max(args.rhs), device="cuda", dtype=torch.float64) * 2 - 1).to(tdt)
+        xk = torch.empty(n * max(args.rhs), dtype=tdt, device="cuda")
+        for c, T in multi.items():
+            for k in args.rhs:
+                T.time_multi_device(k, bk.data_ptr(), k, xk.data_ptr(), k, 1, stream)          # warm-up: code objects, the LDS grant
+                legs[(c, k)] = []
     for w in range(args.windows + 1):                     # window 0 warms every leg up and is dropped
         t = {"spmv": M.time_device(x.data_ptr(), y.data_ptr(), args.reps, stream)}
         for c, T in handles.items():
             t[c] = T.time_device(b.data_ptr(), out.data_ptr(), reps[c], stream)
+            for k in args.rhs if c in multi else ():
+                t[(c, k)] = T.time_multi_device(k, bk.data_ptr(), k, xk.data_ptr(), k, max(3, reps[c] // k), stream)
         torch.cuda.synchronize()
         if w:
             for k, v in t.items():
@@ -110,6 +126,16 @@ def run(E, torch, name, rp, ci, va, n, dts, data, args):
                windows=args.windows, triangle_seconds=round(t_tri, 2), sweep=[], blocked=[])
     global_ms = float(np.median(legs[args.chain_rows[0]]))
     off_diagonal = int(first["nnz_kept"]) - (n if stored else 0)
+    rec["rhs"] = []
+    for c, T in multi.items():
+        single = legs[c]
+        for k in args.rhs:
+            ts, plan = legs[(c, k)], T.solve_multi_plan(k)
+            rec["rhs"].append(dict(block_rows=int(c[1]) if isinstance(c, tuple) else 0, k=k, passes=plan["matrix_passes"],
+                                   launches=plan["launches"], max_chunk=plan["max_chunk"], reps=max(3, reps[c] // k),
+                                   ms=round(float(np.median(ts)), 5), spread=[round(min(ts), 5), round(max(ts), 5)],
+                                   single_ms=round(float(np.median(single)), 5), single_spread=[round(min(single), 5), round(max(single), 5)],
+                                   per_column_over_single=round(float(np.median(ts)) / k / float(np.median(single)), 4)))
     for c, T in handles.items():
         ts = legs[c]
         if isinstance(c, tuple):
@@ -139,6 +165,7 @@ def main():
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--chain-rows", default="64,256,1024,4096", help="the thresholds to sweep, first = the one the header line reports")
     ap.add_argument("--block-rows", default="", help="block sizes of the blocked form to time beside the plans, e.g. 1024,2048,4096,8192,16384")
+    ap.add_argument("--rhs", default="", help="column counts of the k-column solve to time beside the single solve, e.g. 1,2,4,8")
     ap.add_argument("--reps", type=int, default=20, help="SpMV launches per timed floor leg")
     ap.add_argument("--leg-ms", type=float, default=40.0, help="solves per timed leg: as many as last about this long (3 .. 200)")
     ap.add_argument("--scale", type=float, default=1.0, help="shrink the workload twins")
@@ -147,6 +174,9 @@ def main():
         ap.error("--windows: at least 5")
     args.chain_rows = [int(c) for c in args.chain_rows.split(",")]
     args.block_rows = [int(c) for c in args.block_rows.split(",") if c]
+    args.rhs = [int(c) for c in args.rhs.split(",") if c]
+    if any(k < 1 for k in args.rhs):
+        ap.error("--rhs: column counts are at least 1")
     os.environ.setdefault("OMP_NUM_THREADS", "16")
     import torch
     if not torch.cuda.is_available():
@@ -185,6 +215,14 @@ def main():
                 print(f"{r['workload']:11s} {r['dtype']:5s} | {s['block_rows']:10d} {s['blocks']:7d} {s['max_block_levels']:7d} "
                       f"{s['max_level_rows']:7d} {100 * s['dropped_share']:7.2f}% {s['ms']:9.4f} {s['spread'][0]:9.4f} ..{s['spread'][1]:8.4f} "
                       f"{s['over_floor']:8.2f} {s['over_global']:9.4f}")
+    if args.rhs:
+        print(f"{'workload':11s} {'dtype':5s} | {'block_rows':>10s} {'k':>3s} {'passes':>6s} {'launches':>8s} {'solve ms':>9s} {'spread':>19s} "
+              f"{'single ms':>9s} {'spread':>19s} {'per column / single':>19s}")
+        for r in rows:
+            for s in r["rhs"]:
+                print(f"{r['workload']:11s} {r['dtype']:5s} | {s['block_rows'] or 'global':>10} {s['k']:3d} {s['passes']:6d} {s['launches']:8d} "
+                      f"{s['ms']:9.4f} {s['spread'][0]:9.4f} ..{s['spread'][1]:8.4f} {s['single_ms']:9.4f} {s['single_spread'][0]:9.4f} .."
+                      f"{s['single_spread'][1]:8.4f} {s['per_column_over_single']:19.4f}")
 
 
 if __name__ == "__main__":

@@ -594,7 +594,7 @@ int  spmv_mi355x_gmres(spmv_mi355x_matrix * A, const void * b_host, void * x_out
 		double * history_out /* may be NULL: max_iterations doubles */, spmv_mi355x_gmres_info * info /* may be NULL */);
 
 /* ---- sparse triangular solve: level-scheduled L x = b and U x = b handles --------------------------------------------------------- */
-/* What applies Gauss-Seidel / SSOR (A's own triangles) and ILU(0) / IC(0) (the caller's factors): T x = b for one triangle T of a
+/* What applies Gauss-Seidel / SSOR (A's own triangles) and ILU(0) / IC(0) (the caller's factors, or spmv_mi355x_ilu0's): T x = b for one triangle T of a
  * square n x n matrix given as CSR (csrc/trsv.hip, csrc/kernels_trsv.hip). spmv_mi355x_gmres_tri and
  * spmv_mi355x_pcg_tri (below) are the solvers that call it.
  * WHICH TRIANGLE. uplo = SPMV_MI355X_LOWER keeps the entries with column <= row, SPMV_MI355X_UPPER those with column >= row; entries
@@ -640,8 +640,7 @@ int  spmv_mi355x_gmres(spmv_mi355x_matrix * A, const void * b_host, void * x_out
  *     trsv_analyze makes the checks 1 to 3 that apply to its arguments. The solve entries refuse a NULL handle and, for n > 0, a NULL
  *     vector; trsv_info a NULL handle; trsv_mem_footprint(NULL) is 0; trsv_destroy(NULL) is rc 0.
  *   - NOT CHECKABLE: that b_dev / x_dev hold n values on the right device.
- *   - NOT BUILT: wiring into pbicgstab / minres (gmres and CG have it: spmv_mi355x_gmres_tri, spmv_mi355x_pcg_tri); the ILU(0) /
- *     IC(0) factorization itself; a solve
+ *   - NOT BUILT: wiring into pbicgstab / minres (gmres and CG have it: spmv_mi355x_gmres_tri, spmv_mi355x_pcg_tri); a solve
  *     with T^t over T's layout (k right-hand sides ARE served: "K COLUMNS" below); update_values for a trsv handle; GPU-side analysis;
  *     graph capture; a row-partitioned form;
  *     a "sync-free" variant in which workgroups wait for each other inside one launch. */
@@ -730,12 +729,87 @@ int  spmv_mi355x_trsv_solve_multi_plan(const spmv_mi355x_trsv * T, int k, long *
 int  spmv_mi355x_time_trsv_multi_device(spmv_mi355x_trsv * T, int k, const void * b_dev, long ldb, void * x_dev, long ldx, int iters,
 		void * hip_stream, double * ms_per_iter_out);
 
+/* ---- ILU(0): factorize A on the GPU for the triangular preconditioners ------------------------------------------------------------ */
+/* The incomplete LU factorization of a square matrix on its own pattern, computed on the device, so that the strongest preconditioner
+ * the triangular solves apply no longer has to come from the caller (csrc/ilu0.hip, csrc/kernels_ilu0.hip). The handle
+ * is built from the PATTERN (create), takes numbers any number of times (factor: same pattern, new numbers, the rule of
+ * spmv_mi355x_update_values) and returns ONE value array f in A's entry order: its strictly lower part is L (unit diagonal implied),
+ * its diagonal and upper part is U. That array goes to two trsv handles, LOWER / UNIT and UPPER / STORED, with no scale in between:
+ * the "caller's ILU(0)" row of spmv_mi355x_gmres_tri. For a symmetric positive definite A, U = D L^t, so M = L U is the M of IC(0)
+ * and the same triple preconditions spmv_mi355x_pcg_tri and spmv_mi355x_pcg_trsm_multi: there is no Cholesky variant and nothing is
+ * transposed.
+ * THE FACTORIZATION, PINNED TO THE BIT. Input: int32 CSR, n x n, columns strictly ascending in every row, a stored diagonal in every
+ * row, fp64 values. The factorization is always fp64 (the trsv handles narrow f as they narrow any values). f = a copy of the values;
+ *     for i = 0 .. n-1
+ *       for each entry p of row i with column k < i, ascending k
+ *           f[p] = f[p] / f[diag(k)]                                        (an IEEE division)
+ *           for each entry q of row k with column j > k
+ *               if row i stores column j at r:   f[r] = fma(-f[p], f[q], f[r])
+ * Every f[r] receives its fmas in ascending k and no two entries q of one k step touch the same r, so the result does not depend on
+ * how the j loop or the rows of a level are spread over lanes: every plan gives the bits of the sequential loop
+ * (tests/ilu0_reference.c), run after run. A pivot f[diag(i)] that is zero or not finite once row i is finished is a BREAKDOWN: the
+ * arithmetic goes on as IEEE gives it, the lowest such row is reported by get_info (breakdown_row, -1: none), nothing spins and
+ * nothing is refused at factor time. trsv_create then refuses the bad diagonal, naming the row.
+ * THE BLOCKED FORM (block_rows >= 0): the same loop on the CSR without the off-diagonal entries that couple two blocks of B =
+ * block_rows rows, block b owning the rows [b B, min(n, (b + 1) B)). Dropped entries keep A's value in f; blocked trsv handles with
+ * the same B ignore them anyway. block_rows: -1 = global, 0 = the trsv default (4096), 1 .. 16384.
+ * THE SCHEDULE. Row i needs the finished rows k of every stored k < i of row i: the level rule of trsv_analyze(LOWER) on A's pattern,
+ * and the levels come from that routine (trsv_analyze_blocked for the blocked form, where the level WITHIN the block is the launch
+ * index, so all blocks share max_block_levels launches). Level 0 has no k step and gets no launch: launches = levels - 1 (0 when
+ * n = 0). Every factor call also enqueues one 16-byte memset (the breakdown word) and one copy kernel (f = values, and the pivots of
+ * level 0) ahead of them. The order of the launches on the stream is the only ordering between levels: no flag, no grid barrier, no
+ * persistent kernel. Inside a level the rows are independent; a row belongs to a group of 4 .. 64 lanes (chosen per level on its mean
+ * row width, as csr_vector chooses) that walks the row's k steps in order, strides over row k's entries beyond the diagonal and finds
+ * column j in row i by binary search. Step k writes what step k' > k reads through other lanes: a workgroup barrier after every step
+ * orders them, and a group never leaves its workgroup.
+ *   - create() is pattern only and deep-copies it. Stored: A's columns, per row the positions of its first kept entry, its diagonal
+ *     and its end, the rows sorted by (level, row) (level pointers on the host), f, and the breakdown word; 12 nnz + 16 n + 16 bytes,
+ *     which is ilu0_mem_footprint().
+ *   - factor (blocking, host values) and factor_device_async (device values, enqueued on hip_stream, returns at once) may be called
+ *     any number of times; each overwrites f. values_dev may be the handle's own f. One factorization at a time per handle.
+ *   - ilu0_values copies f to the host (nnz doubles) after a device synchronise; ilu0_values_device returns the device pointer, valid
+ *     until destroy and overwritten by the next factor. Both are refused before the first factor.
+ *   - get_info reads the breakdown word and therefore synchronises the device. levels / launches as above; max_level_rows = the most
+ *     rows of one launch (for a blocked handle: of one level over all blocks); nnz_dropped = the entries of A, of both triangles,
+ *     whose column lies outside the row's block (0 for a global handle); block_rows = B used and blocks = ceil(n / B), both 0 for a
+ *     global handle; factorizations = the factor calls so far. info->struct_size in: sizeof; out: the bytes written.
+ *   - rc 1 with the prefix "ilu0_create:" / "ilu0_factor:" / "ilu0_values:" / "ilu0_get_info:", everything but the last on the host
+ *     before any device is touched, in this order:
+ *     1. scalars: n < 0 (or beyond the int32 range), block_rows outside -1 .. 16384; for get_info an unset info->struct_size;
+ *     2. NULL pointers: out, row_ptr; col_idx when row_ptr[n] > 0; the handle; values for nnz > 0;
+ *     3. the pattern, as spmv_mi355x_trsv_create checks it and with its messages: row_ptr from 0 and monotone, columns in [0, n);
+ *     4. a row whose columns are not strictly ascending (the lowest such row and its first offending column are named);
+ *     5. a row without a stored diagonal (the lowest such row is named);
+ *     6. the device: without a usable one the library's "no HIP device available" message; `device` out of range.
+ *     n = 0 is rc 0 with nothing launched; ilu0_destroy(NULL) is rc 0; ilu0_mem_footprint(NULL) is 0.
+ *   - NOT CHECKABLE: that values_dev holds nnz doubles on the handle's device; that the values are those of the pattern given to create.
+ *   - NOT BUILT: IC(0) with a square-root diagonal (the same M for symmetric positive definite input); MILU and shifted variants;
+ *     ILU(k) / ILUT; pivoting; update_values for trsv handles (a refactorization still rebuilds the two trsv handles from the host
+ *     copy of f); GPU-side analysis; the row-partitioned form; running a run of thin levels as one workgroup chain, as the solve
+ *     does (every level is its own launch). */
+typedef struct spmv_mi355x_ilu0 spmv_mi355x_ilu0;   /* opaque */
+typedef struct {
+	size_t struct_size;           /* in: sizeof(spmv_mi355x_ilu0_info); out: the bytes written */
+	long n, nnz, nnz_dropped, levels, launches, max_level_rows, block_rows, blocks;
+	long breakdown_row;           /* -1: none */
+	long factorizations;
+} spmv_mi355x_ilu0_info;
+int  spmv_mi355x_ilu0_create(spmv_mi355x_ilu0 ** out, long n, const int32_t * row_ptr, const int32_t * col_idx,
+		long block_rows /* -1 = global, 0 = default (the trsv default), 1 .. 16384 */, int device /* -1 = current */);
+int  spmv_mi355x_ilu0_factor(spmv_mi355x_ilu0 * F, const double * values_host);                 /* blocking */
+int  spmv_mi355x_ilu0_factor_device_async(spmv_mi355x_ilu0 * F, const double * values_dev, void * hip_stream);
+int  spmv_mi355x_ilu0_values(spmv_mi355x_ilu0 * F, double * out_host /* nnz, A's entry order */); /* blocking */
+int  spmv_mi355x_ilu0_values_device(spmv_mi355x_ilu0 * F, const double ** f_dev_out);
+int  spmv_mi355x_ilu0_get_info(spmv_mi355x_ilu0 * F, spmv_mi355x_ilu0_info * info);             /* reads the breakdown word: synchronises */
+double spmv_mi355x_ilu0_mem_footprint(const spmv_mi355x_ilu0 * F);
+int  spmv_mi355x_ilu0_destroy(spmv_mi355x_ilu0 * F);
+
 /* ---- GMRES(m) right-preconditioned by triangular solves ------------------------------------------------------------------------ */
 /* spmv_mi355x_gmres with M^-1 v = second^-1 ( scale o ( first^-1 v ) ) for "M v" (csrc/solver_gmres.hip): each of
  * the three parts may be NULL, the two solves are spmv_mi355x_trsv handles of any kind, blocked or global, and scale is a vector.
  * The recurrences, the stop codes, the freeze, history and info are exactly those of spmv_mi355x_gmres. Two ways to fill it:
  *     SGS of A:               first = LOWER / STORED handle of A's CSR, scale = diag(A), second = UPPER / STORED handle of A's CSR
- *     the caller's ILU(0):    first = LOWER / UNIT, second = UPPER / STORED, no scale
+ *     the caller's ILU(0):    first = LOWER / UNIT, second = UPPER / STORED, no scale (spmv_mi355x_ilu0 above computes the factor)
  *   - per inner step: the launches of the two solves and one scale kernel on top of spmv_mi355x_gmres's; one scratch vector.
  *   - scale_host: rows() values of the handle's precision. M = (NULL, s, NULL) with s > 0 returns bit for bit what
  *     spmv_mi355x_gmres returns with minv = s.
@@ -778,6 +852,7 @@ int  spmv_mi355x_gmres_tri(spmv_mi355x_matrix * A, const void * b_host, void * x
  * Two ways to fill M:
  *     SGS of an SPD A:        first = LOWER / STORED handle of A's CSR, scale = diag(A), second = UPPER / STORED handle of A's CSR
  *     the caller's IC(0):     first = LOWER / STORED handle of L, no scale, second = UPPER / STORED handle of the CSR of L^t
+ *     spmv_mi355x_ilu0's f:   first = LOWER / UNIT, second = UPPER / STORED, both over f, no scale (IC(0)'s M for an SPD A)
  *   - per iteration: 1 SpMV, the launches of the two solves and at most one scale kernel, and 4 vector kernels (3 without M).
  *   - b_host, x_out_host and M->scale_host: rows() values of the handle's precision.
  *   - any format and layout serves (the solver only calls spmv_mi355x_spmv_device_async): value_storage = 1, 7-byte values and

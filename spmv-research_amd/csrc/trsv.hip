@@ -23,18 +23,6 @@
 
 namespace spmv {
 
-struct TrsvAnalysis {
-	std::vector<int32_t> level_of_row;     // n
-	std::vector<int32_t> level_ptr;        // levels + 1: positions of each level in the (level, row) order
-	std::vector<int32_t> level_slice;      // levels + 1: slices of up to TRSV_SLICE rows, none straddling a level
-	std::vector<TrsvStep> plan;
-	long levels = 0, max_level_rows = 0;
-	int chain_rows = 0;
-	// the blocked plan: level_of_row, level_ptr and level_slice number the levels through all blocks, `levels` is their count
-	std::vector<int32_t> block_level;      // blocks + 1
-	long block_rows = 0, blocks = 0, max_block_levels = 0, nnz_dropped = 0;
-};
-
 static bool
 trsv_scalars_ok(const char * what, int uplo, const int * diag, const int * precision, long n, long chain_rows, bool blocked = false)
 {
@@ -56,7 +44,7 @@ trsv_scalars_ok(const char * what, int uplo, const int * diag, const int * preci
 }
 
 // row_ptr from 0 and monotone, columns in [0, n): the checks and the messages of spmv_mi355x_create
-static int
+int
 trsv_check_pattern(const char * what, long n, const int32_t * rp, const int32_t * ci)
 {
 	if (rp[0] != 0)
@@ -102,7 +90,7 @@ trsv_dep(int uplo, long i, long c, long B)
 }
 
 // O(nnz). The pattern has been checked.
-static void
+void
 trsv_analysis(int uplo, long n, const int32_t * rp, const int32_t * ci, int chain_rows, TrsvAnalysis & an)
 {
 	an.chain_rows = chain_rows ? chain_rows : TRSV_CHAIN_ROWS_DEFAULT;
@@ -165,7 +153,7 @@ trsv_analysis(int uplo, long n, const int32_t * rp, const int32_t * ci, int chai
 }
 
 // The blocked plan, O(nnz); block_rows = 0 is the default. The blocks are independent of each other.
-static void
+void
 trsv_analysis_blocked(int uplo, long n, const int32_t * rp, const int32_t * ci, long block_rows, TrsvAnalysis & an)
 {
 	const long B = block_rows ? block_rows : TRSV_BLOCK_ROWS_DEFAULT;

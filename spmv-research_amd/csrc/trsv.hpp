@@ -109,4 +109,22 @@ struct spmv_mi355x_trsv {
 
 namespace spmv {
 
+// What the host analysis of trsv.hip derives from a pattern; ilu0.hip takes its levels from the same two routines.
+struct TrsvAnalysis {
+	std::vector<int32_t> level_of_row;     // n
+	std::vector<int32_t> level_ptr;        // levels + 1: positions of each level in the (level, row) order
+	std::vector<int32_t> level_slice;      // levels + 1: slices of up to TRSV_SLICE rows, none straddling a level
+	std::vector<TrsvStep> plan;
+	long levels = 0, max_level_rows = 0;
+	int chain_rows = 0;
+	// the blocked plan: level_of_row, level_ptr and level_slice number the levels through all blocks, `levels` is their count
+	std::vector<int32_t> block_level;      // blocks + 1
+	long block_rows = 0, blocks = 0, max_block_levels = 0, nnz_dropped = 0;
+};
+
+// trsv.hip. 0 = fine, 1 = error set with the prefix `what`.
+int trsv_check_pattern(const char * what, long n, const int32_t * rp, const int32_t * ci);
+void trsv_analysis(int uplo, long n, const int32_t * rp, const int32_t * ci, int chain_rows, TrsvAnalysis & an);
+void trsv_analysis_blocked(int uplo, long n, const int32_t * rp, const int32_t * ci, long block_rows, TrsvAnalysis & an);
+
 }  // namespace spmv

@@ -82,6 +82,8 @@ SYMBOLS = [
     "spmv_mi355x_pcg_tri_multi", "spmv_mi355x_pcg_fsai_multi", "spmv_mi355x_pcg_amg_multi",
     "spmv_mi355x_trsv_solve_multi_device_async", "spmv_mi355x_trsv_solve_multi", "spmv_mi355x_trsv_solve_multi_plan",
     "spmv_mi355x_time_trsv_multi_device", "spmv_mi355x_pcg_trsm_multi",
+    "spmv_mi355x_ilu0_create", "spmv_mi355x_ilu0_factor", "spmv_mi355x_ilu0_factor_device_async", "spmv_mi355x_ilu0_values",
+    "spmv_mi355x_ilu0_values_device", "spmv_mi355x_ilu0_get_info", "spmv_mi355x_ilu0_mem_footprint", "spmv_mi355x_ilu0_destroy",
 ]
 
 _lib = None
@@ -169,6 +171,17 @@ def lib():
             getattr(L, f).restype = C.c_int
             getattr(L, f).argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_long, C.c_void_p,
                                       C.c_void_p]
+        L.spmv_mi355x_ilu0_create.restype = C.c_int
+        L.spmv_mi355x_ilu0_create.argtypes = [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_long, C.c_int]
+        for f in ("spmv_mi355x_ilu0_factor", "spmv_mi355x_ilu0_values", "spmv_mi355x_ilu0_values_device", "spmv_mi355x_ilu0_get_info"):
+            getattr(L, f).restype = C.c_int
+            getattr(L, f).argtypes = [C.c_void_p, C.c_void_p]
+        L.spmv_mi355x_ilu0_factor_device_async.restype = C.c_int
+        L.spmv_mi355x_ilu0_factor_device_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.spmv_mi355x_ilu0_mem_footprint.restype = C.c_double
+        L.spmv_mi355x_ilu0_mem_footprint.argtypes = [C.c_void_p]
+        L.spmv_mi355x_ilu0_destroy.restype = C.c_int
+        L.spmv_mi355x_ilu0_destroy.argtypes = [C.c_void_p]
         _lib = L
     return _lib
 
@@ -456,6 +469,105 @@ def sgs_precond(row_ptr, col_idx, values, n, dtype=np.float64, block_rows=None, 
     first = TriangularSolve(row_ptr, col_idx, values, n, uplo="lower", dtype=dtype, block_rows=block_rows, **trsv_opts)
     second = TriangularSolve(row_ptr, col_idx, values, n, uplo="upper", dtype=dtype, block_rows=block_rows, **trsv_opts)
     return first, values[at].astype(dtype), second
+
+
+class Ilu0Info(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("n", C.c_long), ("nnz", C.c_long), ("nnz_dropped", C.c_long), ("levels", C.c_long),
+                ("launches", C.c_long), ("max_level_rows", C.c_long), ("block_rows", C.c_long), ("blocks", C.c_long),
+                ("breakdown_row", C.c_long), ("factorizations", C.c_long)]
+
+
+class Ilu0:
+    """The ILU(0) factorization of a square matrix on its own pattern, computed on the GPU in fp64 (include/spmv_mi355x.h "ILU(0)"):
+    built from the pattern (columns strictly ascending, a stored diagonal in every row), factor(values) any number of times. values()
+    is ONE array in A's entry order, unit L strictly below the diagonal and U on and above it, bit-identical to the sequential loop.
+    block_rows = None gives the global factorization; 0 (the default size) or a size > 0 the blocked form, which ignores the entries
+    that couple different blocks of block_rows rows. precond() gives the triple Matrix.pcg_tri, pcg_trsm_multi and gmres take."""
+
+    def __init__(self, row_ptr, col_idx, n, block_rows=None, device=-1):
+        self.row_ptr = np.ascontiguousarray(row_ptr, np.int32)
+        self.col_idx = np.ascontiguousarray(col_idx, np.int32)
+        self.n = int(n)
+        self.block_rows = block_rows
+        self.device = device
+        self.h = C.c_void_p()
+        _check(lib().spmv_mi355x_ilu0_create(C.byref(self.h), C.c_long(n), _p(self.row_ptr), _p(self.col_idx),
+                                             C.c_long(-1 if block_rows is None else block_rows), C.c_int(device)))
+        self.nnz = int(self.row_ptr[n]) if len(self.row_ptr) else 0
+        self.mem_footprint = lib().spmv_mi355x_ilu0_mem_footprint(self.h)
+
+    def factor(self, values):
+        """factorize the host values, nnz doubles in A's entry order (spmv_mi355x_ilu0_factor; blocking)"""
+        values = np.ascontiguousarray(values, np.float64)
+        if values.shape != (self.nnz,):
+            raise ValueError(f"values must have {self.nnz} entries, got {values.shape}")
+        _check(lib().spmv_mi355x_ilu0_factor(self.h, _p(values)))
+        return self
+
+    def factor_device(self, ptr, stream=None):
+        """The same on a device pointer, enqueued on `stream` (spmv_mi355x_ilu0_factor_device_async)"""
+        _check(lib().spmv_mi355x_ilu0_factor_device_async(self.h, C.c_void_p(ptr), C.c_void_p(stream or 0)))
+        return self
+
+    def values(self):
+        """f on the host: nnz doubles in A's entry order (spmv_mi355x_ilu0_values; blocking)"""
+        out = np.full(max(self.nnz, 1), np.nan)
+        _check(lib().spmv_mi355x_ilu0_values(self.h, _p(out)))
+        return out[:self.nnz]
+
+    def values_device(self):
+        """the device pointer of f (spmv_mi355x_ilu0_values_device): valid until close(), overwritten by the next factor"""
+        ptr = C.c_void_p()
+        _check(lib().spmv_mi355x_ilu0_values_device(self.h, C.byref(ptr)))
+        return ptr.value or 0
+
+    @property
+    def info(self):
+        """dict(n, nnz, nnz_dropped, levels, launches, max_level_rows, block_rows, blocks, breakdown_row, factorizations) of
+        spmv_mi355x_ilu0_get_info; reads the breakdown word, so it synchronises"""
+        r = Ilu0Info()
+        r.struct_size = C.sizeof(Ilu0Info)
+        _check(lib().spmv_mi355x_ilu0_get_info(self.h, C.byref(r)))
+        return {k: getattr(r, k) for k, _ in Ilu0Info._fields_ if k != "struct_size"}
+
+    def precond(self, dtype=np.float64, **trsv_opts):
+        """(first, None, second) for Matrix.pcg_tri, pcg_trsm_multi and gmres(precond=...): the LOWER / UNIT and UPPER / STORED
+        TriangularSolve handles over the factor's CSR, blocked with the factorization's block size when it is blocked. A breakdown
+        surfaces here as trsv_create's refusal of the bad diagonal, which names the row. The caller closes the two handles."""
+        f = self.values()
+        B = None if self.block_rows is None else self.info["block_rows"]
+        trsv_opts.setdefault("device", self.device)
+        first = TriangularSolve(self.row_ptr, self.col_idx, f, self.n, uplo="lower", diag="unit", dtype=dtype, block_rows=B,
+                                **trsv_opts)
+        try:
+            second = TriangularSolve(self.row_ptr, self.col_idx, f, self.n, uplo="upper", diag="stored", dtype=dtype, block_rows=B,
+                                     **trsv_opts)
+        except Exception:
+            first.close()
+            raise
+        return first, None, second
+
+    def close(self):
+        if getattr(self, "h", None) is not None and self.h:
+            lib().spmv_mi355x_ilu0_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def ilu0_precond(row_ptr, col_idx, values, n, dtype=np.float64, block_rows=None, **trsv_opts):
+    """(first, None, second) of the ILU(0) preconditioner of A, factorized on the GPU: the one-call form of Ilu0(...).factor(values)
+    .precond(dtype), beside sgs_precond. For a symmetric positive definite A this is IC(0)'s M. `device` of trsv_opts also places the
+    factorization. The caller closes the two handles."""
+    F = Ilu0(row_ptr, col_idx, n, block_rows=block_rows, device=trsv_opts.pop("device", -1))
+    try:
+        return F.factor(values).precond(dtype, **trsv_opts)
+    finally:
+        F.close()
 
 
 FSAI_MAX_ROW = 128

@@ -1,0 +1,181 @@
+"""What the device ILU(0) costs and what it buys (spmv_mi355x_ilu0_*; include/spmv_mi355x.h "ILU(0)").
+
+For every workload and every variant (global, and blocked at every --block-rows value) the tool reports
+  create:    seconds of spmv_mi355x_ilu0_create (host checks and analysis, uploads), once;
+  factor:    seconds of the blocking host call (upload of the values included) and of factor_device on resident values with a
+             synchronise behind it, medians over --windows calls after one warm-up, with min .. max;
+  host:      seconds of the sequential C loop of tests/ilu0_reference.c on the same values (gcc -O2), once, and whether the device
+             factor has its bits;
+  levels, launches, the share of A's entries the blocks drop.
+On the symmetric positive definite workloads it then solves A x = b with spmv_mi355x_pcg_tri to --tol under ILU(0) (each variant),
+under the global SGS of A and under no preconditioner: iterations, seconds, and ms per iteration from a tol = 0 run of --steps
+iterations minus a run of 0 iterations. On convdiff<k> it solves with gmres(--restart) under the blocked ILU(0) and the blocked SGS.
+No threshold is set and no speed is promised.
+
+Workloads: stencil<N> (the 27-point stencil of tools/solver_bench.py, --stencil-diag on the diagonal), grid2d<N> (the 5-point operator
+of tools/amg_bench.py with --shift), convdiff<k> (tools/gmres_bench.py), and any generated twin of spmv_host.gen_named such as cant
+(factorization only; its columns are sorted first, and a pattern ILU(0) refuses is reported with the refusal: the cant twin stores
+a diagonal in few of its rows, --add-diagonal factorizes A + diag(1 + row sums of |a|) instead).
+
+    python tools/ilu0_bench.py                                       # stencil160, grid2d2000, cant, convdiff1000; global and B = 4096
+    python tools/ilu0_bench.py --runs grid2d2000 --block-rows 1024,4096,16384
+    python tools/ilu0_bench.py --runs stencil160 --no-solve          # factorization only
+One JSON line per variant."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "spmv-research_amd", "python"), os.path.join(ROOT, "tools"), os.path.join(ROOT, "tests")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+
+def load(workload, args):
+    """(row_ptr, col_idx, values, n, kind): kind is "spd", "nonsymmetric" or "factor only" """
+    if workload.startswith("stencil"):
+        from solver_bench import stencil27
+        return stencil27(int(workload[len("stencil"):]), args.stencil_diag) + ("spd",)
+    if workload.startswith("grid2d"):
+        from amg_bench import grid2d
+        return grid2d(int(workload[len("grid2d"):]), args.shift) + ("spd",)
+    if workload.startswith("convdiff"):
+        from gmres_bench import convdiff_csr
+        return convdiff_csr(int(workload[len("convdiff"):])) + ("nonsymmetric",)
+    import scipy.sparse as sp
+    import spmv_host as H
+    A = H.gen_named(workload, args.scale)
+    if A["m"] != A["n"]:
+        raise SystemExit(f"{workload} is {A['m']} x {A['n']}: ILU(0) needs a square matrix")
+    S = sp.csr_matrix((A["values"], A["col_idx"], A["row_ptr"]), shape=(A["m"], A["n"]))
+    S.sum_duplicates()
+    if args.add_diagonal:                                     # A + diag(1 + the row sums of |a|): a stored, dominant diagonal in every row
+        S = (S + sp.diags(1.0 + np.asarray(abs(S).sum(axis=1)).ravel())).tocsr()
+    S.sort_indices()
+    return S.indptr.astype(np.int32), S.indices.astype(np.int32), S.data.astype(np.float64), A["n"], "factor only"
+
+
+def spread(ts):
+    return dict(median=round(float(np.median(ts)), 6), min=round(min(ts), 6), max=round(max(ts), 6))
+
+
+def factor_legs(E, torch, ic, workload, rp, ci, va, n, B, args):
+    t0 = time.perf_counter()
+    F = E.Ilu0(rp, ci, n, block_rows=B)
+    create = time.perf_counter() - t0
+    dev = torch.from_numpy(va).cuda()
+    torch.cuda.synchronize()
+    host, device = [], []
+    for w in range(args.windows + 1):                         # window 0 warms up and is dropped
+        t0 = time.perf_counter()
+        F.factor(va)
+        t1 = time.perf_counter()
+        F.factor_device(dev.data_ptr())
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        if w:
+            host.append(t1 - t0)
+            device.append(t2 - t1)
+    info = F.info
+    rec = dict(workload=workload, n=int(n), nnz=int(len(ci)), variant="global" if B is None else f"B={info['block_rows']}",
+               create_seconds=round(create, 4), factor_host_values=spread(host), factor_device_values=spread(device),
+               levels=info["levels"], launches=info["launches"], max_level_rows=info["max_level_rows"],
+               dropped_share=round(info["nnz_dropped"] / max(len(ci), 1), 4), breakdown_row=info["breakdown_row"],
+               mem_mib=round(F.mem_footprint / 2 ** 20, 1), windows=args.windows)
+    if not args.no_reference:
+        t0 = time.perf_counter()
+        want, bad = ic.reference(rp, ci, va, n, None if B is None else info["block_rows"])
+        rec["reference_seconds"] = round(time.perf_counter() - t0, 4)
+        rec["bit_identical"] = bool(np.array_equal(F.values(), want, equal_nan=True)) and bad == info["breakdown_row"]
+    return F, rec
+
+
+def pcg_legs(E, A, b, M, args):
+    r = A.pcg_tri(b, precond=M, tol=args.tol, max_iterations=args.max_iterations, history=False)
+    fixed = A.pcg_tri(b, precond=M, tol=0.0, max_iterations=0, history=False)["seconds"]
+    s = A.pcg_tri(b, precond=M, tol=0.0, max_iterations=args.steps, history=False)
+    return dict(iterations=int(r["iterations"]), stop=int(r["stop"]), seconds=round(r["seconds"], 4),
+                rnorm_over_b=float(r["rnorm"] / r["rnorm0"]), ms_per_iteration=round((s["seconds"] - fixed) * 1e3 / args.steps, 4))
+
+
+def close(M):
+    for h in M or ():
+        if h is not None and not isinstance(h, np.ndarray):
+            h.close()
+
+
+def run(E, torch, ic, workload, args):
+    rp, ci, va, n, kind = load(workload, args)
+    rp = np.asarray(rp, np.int32)
+    A = None if kind == "factor only" or args.no_solve else E.Matrix(rp, ci, va, n, n, "sell_c_sigma", np.float64)
+    b = np.random.default_rng(7).uniform(-1, 1, n)
+    variants = ([None] if kind != "nonsymmetric" else []) + list(args.block_rows)
+    for B in variants:
+        try:
+            F, rec = factor_legs(E, torch, ic, workload, rp, ci, va, n, B, args)
+        except E.SpmvError as e:
+            print(json.dumps(dict(workload=workload, variant="global" if B is None else f"B={B}", refused=str(e))), flush=True)
+            continue
+        if A is not None:
+            t0 = time.perf_counter()
+            M = F.precond()
+            rec["trsv_handles_seconds"] = round(time.perf_counter() - t0, 4)
+            rec["trsv_launches"] = M[0].info["launches"] + M[2].info["launches"]
+            if kind == "spd":
+                rec["pcg_tri"] = pcg_legs(E, A, b, M, args)
+            else:
+                g = A.gmres(b, restart=args.restart, precond=M, tol=args.tol, max_iterations=args.max_iterations, history=False)
+                rec["gmres"] = dict(restart=args.restart, iterations=int(g["iterations"]), stop=int(g["stop"]), seconds=round(g["seconds"], 4))
+            close(M)
+        F.close()
+        print(json.dumps(rec), flush=True)
+    if A is None:
+        return
+    if kind == "spd":
+        for name, M in (("sgs global", E.sgs_precond(rp, ci, va, n)), ("none", None)):
+            print(json.dumps(dict(workload=workload, variant=name, pcg_tri=pcg_legs(E, A, b, M, args))), flush=True)
+            close(M)
+    else:
+        for B in args.block_rows:
+            M = E.sgs_precond(rp, ci, va, n, block_rows=B)
+            g = A.gmres(b, restart=args.restart, precond=M, tol=args.tol, max_iterations=args.max_iterations, history=False)
+            print(json.dumps(dict(workload=workload, variant=f"sgs B={B}", gmres=dict(restart=args.restart, iterations=int(g["iterations"]),
+                                  stop=int(g["stop"]), seconds=round(g["seconds"], 4)))), flush=True)
+            close(M)
+    A.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--runs", default="stencil160,grid2d2000,cant,convdiff1000", help="workloads, comma separated")
+    ap.add_argument("--block-rows", default="4096", help="block sizes of the blocked variants, comma separated (the global one always runs)")
+    ap.add_argument("--windows", type=int, default=5)
+    ap.add_argument("--tol", type=float, default=1e-8)
+    ap.add_argument("--max-iterations", type=int, default=3000)
+    ap.add_argument("--steps", type=int, default=50, help="iterations of the tol = 0 leg")
+    ap.add_argument("--restart", type=int, default=30)
+    ap.add_argument("--stencil-diag", type=float, default=27.0)
+    ap.add_argument("--shift", type=float, default=0.001)
+    ap.add_argument("--scale", type=float, default=1.0, help="the scale of a generated twin")
+    ap.add_argument("--add-diagonal", action="store_true",
+                    help="generated twins: factorize A + diag(1 + row sums of |a|) (the cant twin stores a diagonal in few of its rows)")
+    ap.add_argument("--no-solve", action="store_true", help="factorization only")
+    ap.add_argument("--no-reference", action="store_true", help="skip the sequential loop on the host")
+    args = ap.parse_args()
+    args.block_rows = [int(v) for v in args.block_rows.split(",") if v != ""]
+    os.environ.setdefault("OMP_NUM_THREADS", "16")
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("ilu0_bench.py needs a GPU: the engine has no CPU path")
+    import ilu0_cases as ic
+    import spmv_mi355x as E
+    for workload in args.runs.split(","):
+        run(E, torch, ic, workload, args)
+
+
+if __name__ == "__main__":
+    main()

@@ -641,7 +641,8 @@ int  spmv_mi355x_gmres(spmv_mi355x_matrix * A, const void * b_host, void * x_out
  *     vector; trsv_info a NULL handle; trsv_mem_footprint(NULL) is 0; trsv_destroy(NULL) is rc 0.
  *   - NOT CHECKABLE: that b_dev / x_dev hold n values on the right device.
  *   - NOT BUILT: wiring into pbicgstab / minres (gmres and CG have it: spmv_mi355x_gmres_tri, spmv_mi355x_pcg_tri); a solve
- *     with T^t over T's layout (k right-hand sides ARE served: "K COLUMNS" below); update_values for a trsv handle; GPU-side analysis;
+ *     with T^t over T's layout (k right-hand sides ARE served: "K COLUMNS" below; new values for the same pattern too: "UPDATE_VALUES"
+ *     below); GPU-side analysis;
  *     graph capture; a row-partitioned form;
  *     a "sync-free" variant in which workgroups wait for each other inside one launch. */
 typedef struct spmv_mi355x_trsv spmv_mi355x_trsv;   /* opaque */
@@ -729,6 +730,73 @@ int  spmv_mi355x_trsv_solve_multi_plan(const spmv_mi355x_trsv * T, int k, long *
 int  spmv_mi355x_time_trsv_multi_device(spmv_mi355x_trsv * T, int k, const void * b_dev, long ldb, void * x_dev, long ldx, int iters,
 		void * hip_stream, double * ms_per_iter_out);
 
+/* UPDATE_VALUES: new numbers for the pattern a trsv handle was created with, scattered on the GPU. The rule of
+ * spmv_mi355x_update_values: same pattern, new numbers, no rebuild, and the handle comes out BYTE FOR BYTE what trsv_create /
+ * trsv_create_blocked builds from the new values: every stored value, the padding (never written: it keeps create's zeros) and the
+ * diagonal, narrowed to the handle's precision by the conversion create makes (round to nearest even). Nothing that depends on the
+ * pattern alone is redone: no analysis, no layout, no upload of the other eight arrays. What it is for: the Newton and time-stepping
+ * loops in which ilu0_factor_device_async leaves a new f on the device: f goes into the two handles without a host copy.
+ * THE ENTRY MAP (host, pattern only, once per handle). slot_src[e], one int32 per stored slot of the value array (slots of them,
+ * padding included): the entry of the CALLER'S CSR that create puts in slot e, -1 for padding. Slice s of `lanes` positions stores
+ * entry k of its lane r at slice_ptr[s] + k * lanes + r; a row's kept entries keep their stored order, duplicates are separate
+ * entries, the other triangle, the diagonal and (blocked) the entries that leave the row's block never appear. diag_src[p], one
+ * int32 per position under DIAG_STORED: the first stored entry of row perm[p] with column perm[p]. create and the map are ONE walk of
+ * the pattern in the library (csrc/trsv.hip: trsv_layout), not two statements of the layout.
+ *   - trsv_update_map: that derivation alone, no device touched and no handle needed, as trsv_analyze exposes the analysis.
+ *     block_rows = -1 gives the global form (chain_rows is checked, it does not change the layout), 0 the default block size, 1 ..
+ *     16384 that size. slot_src_out and diag_src_out are malloc'ed (at least one element; free with spmv_mi355x_free), diag_src_out
+ *     receives NULL under DIAG_UNIT; any out pointer may be NULL. rc 1 with the prefix "trsv_update_map:" in trsv_create's order and
+ *     with its messages: 1. scalars, 2. NULL pointers, 3. the pattern, 4. under DIAG_STORED a row without a diagonal entry or with two.
+ *   - trsv_update_values_prepare(T, n, row_ptr, col_idx): once per handle; a second call does nothing. Derives the map from the CSR
+ *     given, which must have the handle's pattern, uploads it and allocates one 16-byte status block and an event. The CSR fixes the
+ *     ENTRY ORDER of every later values array. The bytes (4 per slot, 4 n under DIAG_STORED, 16) are not in trsv_mem_footprint(), the
+ *     rule of the maps of spmv_mi355x_update_values_prepare; trsv_update_values_bytes() reports them (0 before prepare). n = 0 is legal.
+ *     rc 1 with the prefix "trsv_update_values_prepare:", the handle untouched and its state still 1, in this order: 1. a NULL handle;
+ *     2. a NULL row_ptr; 3. n other than the handle's; 4. a NULL col_idx when row_ptr[n] > 0; 5. the pattern checks of trsv_create
+ *     and, under DIAG_STORED, a diagonal in every row, stored once; 6. the recomputed len, perm, slice_ptr and col against the handle's
+ *     device arrays, downloaded once: the message names the lowest row whose place in the level order or whose count of kept entries
+ *     differs, else a row of the first slice whose extent differs, else the lowest row whose kept columns differ; 7. the device.
+ *   - trsv_update_values_device_async(T, values_dev, hip_stream): values_dev holds row_ptr[n] doubles in the order of the CSR given to
+ *     prepare: ALL entries, both triangles, exactly the array spmv_mi355x_ilu0_values_device returns. Enqueues one 16-byte memset (the
+ *     status word), under DIAG_STORED one check kernel, and one write kernel, then returns. The check kernel narrows every new
+ *     diagonal and reports a zero or non-finite one by atomicMin of its ROW on the status word (ILU(0)'s breakdown idiom: the result
+ *     does not depend on thread order, nothing spins); the write kernel reads the word first and writes NOTHING when it names a row,
+ *     so a refused update leaves the previous values in place, bit for bit. A DIAG_UNIT handle has no check and cannot refuse.
+ *     Ordering against solves of the same handle is the caller's job through the stream: an update and a solve of one handle are
+ *     ordered when they are enqueued on the same stream (or on streams the caller has ordered), never otherwise; one update at a
+ *     time per handle. values_dev must stay valid until the result has been taken.
+ *   - trsv_update_values_result(T, &bad_row): waits for the last async update; rc 0 with bad_row = -1, or rc 1 with the LOWEST
+ *     refused row and create's message: "trsv_update_values: the diagonal of row R is X in the handle's precision (from Y): it must
+ *     be finite and non-zero" (the one offending double is copied back for it). Asked again, it answers the same.
+ *   - trsv_update_values_device = async + result. trsv_update_values = the host form: uploads row_ptr[n] doubles into a staging buffer
+ *     that is allocated at the first call and kept (as the vectors of trsv_solve are), then the same. trsv_update_values_staged
+ *     returns that buffer (refused before the first host-form update; valid until destroy, overwritten by the next host-form update):
+ *     a second handle of the same CSR, the other half of an SGS pair, updates from it without a second upload.
+ *   - trsv_update_values_state (host only): 0 = cannot be updated (a NULL handle), 1 = prepare is missing, 2 = ready, 3 = the last
+ *     update whose result was taken was refused and the handle holds the values from before it. A later accepted update gives 2.
+ *   - trsv_stored_values (blocking, synchronises the device): the stored value array (slots values of the handle's precision, padding
+ *     included) into val_host and the n diagonals by position into diag_host (ignored under DIAG_UNIT, may be NULL); slots_out
+ *     receives slots. val_host = NULL only queries slots. Two handles with equal stored_values solve alike: the tests compare them.
+ *   - rc 1 from the update entries with the prefix "trsv_update_values:", the handle untouched, checked on the host in this order:
+ *     1. a NULL handle; 2. a NULL values array when row_ptr[n] > 0; 3. an update (or a result) before prepare; then the device.
+ *     trsv_update_values_bytes(NULL) is 0. Every earlier entry behaves as before; a handle that never calls prepare allocates
+ *     nothing more and solves exactly as before.
+ *   - NOT CHECKABLE: that values_dev holds row_ptr[n] doubles on the handle's device, in the order of prepare's CSR.
+ *   - NOT BUILT: GPU-side analysis (create still analyses on the host); update_values for FSAI; a pattern change (a new handle);
+ *     the row-partitioned form. */
+int  spmv_mi355x_trsv_update_map(int uplo, int diag, long n, const int32_t * row_ptr, const int32_t * col_idx, int chain_rows,
+		long block_rows /* -1 = global */, int32_t ** slot_src_out /* malloc'ed, spmv_mi355x_free */, long * slots_out,
+		int32_t ** diag_src_out /* malloc'ed; NULL under DIAG_UNIT */);
+int  spmv_mi355x_trsv_update_values_prepare(spmv_mi355x_trsv * T, long n, const int32_t * row_ptr, const int32_t * col_idx);
+double spmv_mi355x_trsv_update_values_bytes(const spmv_mi355x_trsv * T);
+int  spmv_mi355x_trsv_update_values_state(const spmv_mi355x_trsv * T);
+int  spmv_mi355x_trsv_update_values_device_async(spmv_mi355x_trsv * T, const double * values_fp64_dev, void * hip_stream);
+int  spmv_mi355x_trsv_update_values_result(spmv_mi355x_trsv * T, long * bad_row_out /* may be NULL */);
+int  spmv_mi355x_trsv_update_values_device(spmv_mi355x_trsv * T, const double * values_fp64_dev, void * hip_stream);   /* blocking */
+int  spmv_mi355x_trsv_update_values(spmv_mi355x_trsv * T, const double * values_fp64_host);                             /* blocking */
+int  spmv_mi355x_trsv_update_values_staged(spmv_mi355x_trsv * T, const double ** values_dev_out);
+int  spmv_mi355x_trsv_stored_values(spmv_mi355x_trsv * T, void * val_host, long * slots_out, void * diag_host);         /* blocking */
+
 /* ---- ILU(0): factorize A on the GPU for the triangular preconditioners ------------------------------------------------------------ */
 /* The incomplete LU factorization of a square matrix on its own pattern, computed on the device, so that the strongest preconditioner
  * the triangular solves apply no longer has to come from the caller (csrc/ilu0.hip, csrc/kernels_ilu0.hip). The handle
@@ -784,8 +852,8 @@ int  spmv_mi355x_time_trsv_multi_device(spmv_mi355x_trsv * T, int k, const void 
  *     n = 0 is rc 0 with nothing launched; ilu0_destroy(NULL) is rc 0; ilu0_mem_footprint(NULL) is 0.
  *   - NOT CHECKABLE: that values_dev holds nnz doubles on the handle's device; that the values are those of the pattern given to create.
  *   - NOT BUILT: IC(0) with a square-root diagonal (the same M for symmetric positive definite input); MILU and shifted variants;
- *     ILU(k) / ILUT; pivoting; update_values for trsv handles (a refactorization still rebuilds the two trsv handles from the host
- *     copy of f); GPU-side analysis; the row-partitioned form; running a run of thin levels as one workgroup chain, as the solve
+ *     ILU(k) / ILUT; pivoting; GPU-side analysis; the row-partitioned form (a refactorization no longer rebuilds the two trsv
+ *     handles: spmv_mi355x_trsv_update_values_device_async takes f where ilu0_values_device leaves it); running a run of thin levels as one workgroup chain, as the solve
  *     does (every level is its own launch). */
 typedef struct spmv_mi355x_ilu0 spmv_mi355x_ilu0;   /* opaque */
 typedef struct {
@@ -1170,7 +1238,7 @@ int  spmv_mi355x_pcg_amg(spmv_mi355x_matrix * A, const void * b_host, void * x_o
  *     seconds, and of the last update its seconds, split into the SpGEMM numeric passes and the handles' update_values_device
  *     (the rest: steps 1 and 5, the weights, the gather, the factor and the host's reads).
  *   - NOT BUILT: re-aggregating when the strength pattern drifts (the caller decides and calls amg_create), update_values for fsai
- *     and trsv handles, an asynchronous update, the row-partitioned form, W- and K-cycles. */
+ *     handles (trsv handles have it: "UPDATE_VALUES" of the triangular solve), an asynchronous update, the row-partitioned form, W- and K-cycles. */
 typedef struct {
 	unsigned struct_size;   /* in: sizeof of the caller's struct; out: bytes written */
 	int    prepared, failed;

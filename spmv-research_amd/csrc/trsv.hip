@@ -13,6 +13,7 @@
 // one, so all blocks are solved by ONE launch with one workgroup per block (trsv_blocked_kernel), and again no workgroup waits for
 // another one. What is lost is the dropped couplings: the handle solves the block-diagonal part of the triangle, exactly.
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -219,6 +220,7 @@ namespace spmv {
 
 // STORED: the diagonal of row i is the first stored entry with column i (the rule of jacobi_diagonal); it must exist, be finite and
 // non-zero after narrowing to the handle's precision, and be the only entry with column i. The first bad row is reported.
+// va == nullptr checks the pattern alone (a diagonal in every row, stored once): what update_values_prepare can know.
 template <typename T>
 static int
 trsv_check_diagonal(const char * what, long n, const int32_t * rp, const int32_t * ci, const double * va)
@@ -236,7 +238,7 @@ trsv_check_diagonal(const char * what, long n, const int32_t * rp, const int32_t
 				if (at < 0)
 					at = j;
 			}
-		const T d = at >= 0 ? (T) va[at] : (T) 0;
+		const T d = at >= 0 && va ? (T) va[at] : (T) (va ? 0 : 1);
 		if (at < 0 || twice || !std::isfinite(d) || d == 0)
 			bad = std::min(bad, i);
 	}
@@ -260,16 +262,28 @@ trsv_check_diagonal(const char * what, long n, const int32_t * rp, const int32_t
 	return 1;
 }
 
-template <typename T>
-static int
-trsv_build(spmv_mi355x_trsv * H, const TrsvAnalysis & an, const int32_t * rp, const int32_t * ci, const double * va)
+// THE LAYOUT OF trsv.hpp, WRITTEN ONCE: everything trsv_build stores except the numbers. Instead of values it yields where every
+// stored value comes from: slot_src[e] = the entry of the caller's CSR in slot e of val (-1: padding), diag_src[p] = the first stored
+// entry of row perm[p] with column perm[p] (-1: none; filled under STORED only). trsv_build narrows the values through these maps and
+// update_values (below) uploads them, so a handle updated on the GPU holds what create would have built.
+struct TrsvLayout {
+	std::vector<int32_t> perm, len, col, slot_src, diag_src;
+	std::vector<int32_t> slice_pos;       // slices + 1: slice s holds the positions [slice_pos[s], slice_pos[s + 1])
+	std::vector<int64_t> slice_ptr;       // slices + 1
+	long slices = 0, kept = 0;
+};
+
+static void
+trsv_layout(int uplo, bool stored, long B /* 0: a global handle */, long n, const TrsvAnalysis & an, const int32_t * rp,
+		const int32_t * ci, TrsvLayout & L)
 {
-	const long n = H->n, levels = an.levels;
+	const long levels = an.levels;
 	const long slices = levels ? an.level_slice[levels] : 0;
-	const bool stored = H->diag == SPMV_MI355X_DIAG_STORED;
-	const long B = H->block_rows;         // 0: a global handle
-	std::vector<int32_t> perm((size_t) n), len((size_t) n);
-	std::vector<T> diag(stored ? (size_t) n : 0);
+	L.slices = slices;
+	L.perm.assign((size_t) n, 0);
+	L.len.assign((size_t) n, 0);
+	L.diag_src.assign(stored ? (size_t) n : 0, -1);
+	std::vector<int32_t> & perm = L.perm, & len = L.len;
 	{
 		std::vector<int32_t> next(an.level_ptr.begin(), an.level_ptr.end());
 		for (long i = 0; i < n; i++)                 // ascending rows: (level, row) order
@@ -284,25 +298,26 @@ trsv_build(spmv_mi355x_trsv * H, const TrsvAnalysis & an, const int32_t * rp, co
 		bool have = false;
 		for (long j = rp[i]; j < rp[i + 1]; j++)
 		{
-			c += trsv_dep(H->uplo, i, ci[j], B);
+			c += trsv_dep(uplo, i, ci[j], B);
 			if (stored && !have && ci[j] == i)
 			{
-				diag[p] = (T) va[j];
+				L.diag_src[p] = (int32_t) j;
 				have = true;
 			}
 		}
 		len[p] = c;
 		kept += c;
 	}
-	H->nnz_kept = kept + (stored ? n : 0);
-	// slice s holds the positions [slice_pos[s], slice_pos[s + 1])
-	std::vector<int32_t> slice_pos((size_t) slices + 1, 0);
+	L.kept = kept;
+	L.slice_pos.assign((size_t) slices + 1, 0);
+	std::vector<int32_t> & slice_pos = L.slice_pos;
 	for (long l = 0; l < levels; l++)
 		for (long s = an.level_slice[l]; s < an.level_slice[l + 1]; s++)
 			slice_pos[s] = an.level_ptr[l] + (int32_t) (s - an.level_slice[l]) * TRSV_SLICE;
 	slice_pos[slices] = (int32_t) n;
 	// the last slice of a level ends where the level ends
-	std::vector<int64_t> slice_ptr((size_t) slices + 1, 0);
+	L.slice_ptr.assign((size_t) slices + 1, 0);
+	std::vector<int64_t> & slice_ptr = L.slice_ptr;
 	auto slice_end = [&](long s, long l) { return std::min<long>(slice_pos[s] + TRSV_SLICE, an.level_ptr[l + 1]); };
 	for (long l = 0; l < levels; l++)
 		for (long s = an.level_slice[l]; s < an.level_slice[l + 1]; s++)
@@ -315,8 +330,8 @@ trsv_build(spmv_mi355x_trsv * H, const TrsvAnalysis & an, const int32_t * rp, co
 	for (long s = 0; s < slices; s++)
 		slice_ptr[s + 1] += slice_ptr[s];
 	const size_t stored_entries = (size_t) slice_ptr[slices];
-	std::vector<T> val(stored_entries, (T) 0);
-	std::vector<int32_t> col(stored_entries, 0);
+	L.col.assign(stored_entries, 0);
+	L.slot_src.assign(stored_entries, -1);
 	std::vector<int32_t> level_of_slice((size_t) slices);
 	for (long l = 0; l < levels; l++)
 		for (long s = an.level_slice[l]; s < an.level_slice[l + 1]; s++)
@@ -330,14 +345,41 @@ trsv_build(spmv_mi355x_trsv * H, const TrsvAnalysis & an, const int32_t * rp, co
 			const long i = perm[p0 + r];
 			int64_t e = slice_ptr[s] + r;
 			for (long j = rp[i]; j < rp[i + 1]; j++)
-				if (trsv_dep(H->uplo, i, ci[j], B))
+				if (trsv_dep(uplo, i, ci[j], B))
 				{
-					val[e] = (T) va[j];              // narrowed as spmv_mi355x_create narrows
-					col[e] = B ? (int32_t) (ci[j] - i / B * B) : ci[j];     // blocked: the column within the block
+					L.slot_src[e] = (int32_t) j;
+					L.col[e] = B ? (int32_t) (ci[j] - i / B * B) : ci[j];     // blocked: the column within the block
 					e += lanes;
 				}
 		}
 	}
+}
+
+template <typename T>
+static int
+trsv_build(spmv_mi355x_trsv * H, const TrsvAnalysis & an, const int32_t * rp, const int32_t * ci, const double * va)
+{
+	const long n = H->n;
+	const bool stored = H->diag == SPMV_MI355X_DIAG_STORED;
+	const long B = H->block_rows;         // 0: a global handle
+	TrsvLayout L;
+	trsv_layout(H->uplo, stored, B, n, an, rp, ci, L);
+	const std::vector<int32_t> & perm = L.perm, & len = L.len, & col = L.col;
+	const std::vector<int64_t> & slice_ptr = L.slice_ptr;
+	const size_t stored_entries = L.slot_src.size();
+	H->nnz_kept = L.kept + (stored ? n : 0);
+	H->slices = L.slices;
+	H->slots = (long) stored_entries;
+	H->nnz_csr = rp[n];
+	// the numbers, through the maps; narrowed as spmv_mi355x_create narrows. Padding stays zero.
+	std::vector<T> val(stored_entries, (T) 0), diag(stored ? (size_t) n : 0);
+	#pragma omp parallel for num_threads(spmv::host_threads()) schedule(static, 4096)
+	for (size_t e = 0; e < stored_entries; e++)
+		if (L.slot_src[e] >= 0)
+			val[e] = (T) va[L.slot_src[e]];
+	#pragma omp parallel for num_threads(spmv::host_threads()) schedule(static, 4096)
+	for (size_t p = 0; p < diag.size(); p++)
+		diag[p] = (T) va[L.diag_src[p]];              // trsv_check_diagonal has seen a diagonal in every row
 	struct Up { const void * src; size_t bytes; } ups[9] = {
 		{val.data(), stored_entries * sizeof(T)}, {col.data(), stored_entries * sizeof(int32_t)},
 		{slice_ptr.data(), slice_ptr.size() * sizeof(int64_t)}, {len.data(), (size_t) n * sizeof(int32_t)},
@@ -379,6 +421,11 @@ trsv_free(spmv_mi355x_trsv * H)
 		(void) hipFree(H->d_bk);
 	if (H->d_xk)
 		(void) hipFree(H->d_xk);
+	for (void * p : {(void *) H->upd_slot_src, (void *) H->upd_diag_src, (void *) H->upd_status, (void *) H->upd_values})
+		if (p)
+			(void) hipFree(p);
+	if (H->upd_done)
+		(void) hipEventDestroy(H->upd_done);
 	delete H;
 }
 
@@ -850,6 +897,343 @@ spmv_mi355x_time_trsv_multi_device(spmv_mi355x_trsv * T, int k, const void * b_d
 	(void) hipEventDestroy(e0);
 	(void) hipEventDestroy(e1);
 	*ms_out = iters > 0 ? (double) ms / iters : 0;
+	return 0;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ update_values
+
+namespace spmv {
+
+// What update_map and update_values_prepare share: the pattern checks of create that need no values, the analysis and the layout.
+// block_rows < 0: the global form with chain_rows; else the blocked form.
+static int
+trsv_layout_checked(const char * what, int uplo, int diag, long n, const int32_t * rp, const int32_t * ci, long chain_rows, long block_rows,
+		TrsvLayout & L)
+{
+	const bool stored = diag == SPMV_MI355X_DIAG_STORED;
+	if (trsv_check_pattern(what, n, rp, ci))
+		return 1;
+	if (stored && trsv_check_diagonal<double>(what, n, rp, ci, nullptr))
+		return 1;
+	TrsvAnalysis an;
+	if (block_rows >= 0)
+		trsv_analysis_blocked(uplo, n, rp, ci, block_rows, an);
+	else
+		trsv_analysis(uplo, n, rp, ci, (int) chain_rows, an);
+	trsv_layout(uplo, stored, block_rows >= 0 ? an.block_rows : 0, n, an, rp, ci, L);
+	return 0;
+}
+
+// The recomputed layout against the handle's device arrays. 0 = the same pattern; 1 = error set, naming the lowest row whose
+// position or length differs, else a row of the first slice whose extent differs, else the lowest row whose kept columns differ.
+static int
+trsv_same_layout(const char * what, const spmv_mi355x_trsv * T, const int32_t * rp, const TrsvLayout & L)
+{
+	const long n = T->n;
+	std::vector<int32_t> len((size_t) n), perm((size_t) n), col((size_t) T->slots);
+	std::vector<int64_t> slice_ptr((size_t) T->slices + 1);
+	if (n)
+	{
+		HIP_TRY(hipMemcpy(len.data(), T->arr.len, (size_t) n * sizeof(int32_t), hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(perm.data(), T->arr.perm, (size_t) n * sizeof(int32_t), hipMemcpyDeviceToHost));
+	}
+	HIP_TRY(hipMemcpy(slice_ptr.data(), T->arr.slice_ptr, slice_ptr.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+	if (T->slots)
+		HIP_TRY(hipMemcpy(col.data(), T->arr.col, (size_t) T->slots * sizeof(int32_t), hipMemcpyDeviceToHost));
+	long bad = n;
+	#pragma omp parallel for num_threads(spmv::host_threads()) reduction(min : bad) schedule(static, 4096)
+	for (long p = 0; p < n; p++)
+		if (perm[p] != L.perm[p])
+			bad = std::min<long>(bad, std::min(perm[p], L.perm[p]));
+		else if (len[p] != L.len[p])
+			bad = std::min<long>(bad, perm[p]);
+	if (bad < n)
+	{
+		set_error("%s: the pattern is not the one the handle was created with: row %ld has another place in the level order or "
+				"another count of kept entries", what, bad);
+		return 1;
+	}
+	const long common = std::min(T->slices, L.slices);
+	long s = 0;
+	while (s <= common && slice_ptr[s] == L.slice_ptr[s])
+		s++;
+	if (s <= common || T->slices != L.slices)
+	{
+		const long at = std::min(std::max<long>(s - 1, 0), std::max<long>(L.slices - 1, 0));
+		set_error("%s: the pattern is not the one the handle was created with: the slice of row %ld has another extent (the levels "
+				"differ)", what, L.slices ? (long) L.perm[L.slice_pos[at]] : 0L);
+		return 1;
+	}
+	#pragma omp parallel for num_threads(spmv::host_threads()) reduction(min : bad) schedule(static, 4096)
+	for (long e = 0; e < T->slots; e++)
+		if (col[e] != L.col[e])
+			bad = std::min<long>(bad, std::upper_bound(rp, rp + n + 1, L.slot_src[e]) - rp - 1);
+	if (bad < n)
+	{
+		set_error("%s: the pattern is not the one the handle was created with: row %ld keeps other columns", what, bad);
+		return 1;
+	}
+	return 0;
+}
+
+// the host-side refusals of the update entries, in the header's order
+static bool
+trsv_update_arguments_ok(const spmv_mi355x_trsv * T, const void * values, bool takes_values = true)
+{
+	if (!T)
+		set_error("trsv_update_values: NULL handle");
+	else if (takes_values && !values && T->nnz_csr > 0)
+		set_error("trsv_update_values: NULL argument ( values )");
+	else if (T->upd_state == 1)
+		set_error("trsv_update_values: spmv_mi355x_trsv_update_values_prepare has not been called for this handle");
+	else
+		return true;
+	return false;
+}
+
+}  // namespace spmv
+
+extern "C" {
+
+int
+spmv_mi355x_trsv_update_map(int uplo, int diag, long n, const int32_t * row_ptr, const int32_t * col_idx, int chain_rows, long block_rows,
+		int32_t ** slot_src_out, long * slots_out, int32_t ** diag_src_out)
+{
+	const char * what = "trsv_update_map";
+	if (slot_src_out)
+		*slot_src_out = nullptr;
+	if (diag_src_out)
+		*diag_src_out = nullptr;
+	if (block_rows < -1)
+	{
+		set_error("%s: block_rows must be -1 (the global form), 0 (the default) or 1 .. %d (got %ld)", what, TRSV_BLOCK_ROWS_MAX, block_rows);
+		return 1;
+	}
+	const bool blocked = block_rows >= 0;
+	if (!trsv_scalars_ok(what, uplo, &diag, nullptr, n, blocked ? block_rows : (long) chain_rows, blocked))
+		return 1;
+	if (!row_ptr || (!col_idx && row_ptr[n] > 0))
+	{
+		set_error("%s: NULL argument (%s%s )", what, !row_ptr ? " row_ptr" : "", !col_idx ? " col_idx" : "");
+		return 1;
+	}
+	TrsvLayout L;
+	if (trsv_layout_checked(what, uplo, diag, n, row_ptr, col_idx, chain_rows, block_rows, L))
+		return 1;
+	const size_t slots = L.slot_src.size();
+	int32_t * ss = slot_src_out ? (int32_t *) malloc(std::max<size_t>(slots, 1) * sizeof(int32_t)) : nullptr;
+	const bool want_diag = diag_src_out && diag == SPMV_MI355X_DIAG_STORED;
+	int32_t * ds = want_diag ? (int32_t *) malloc(std::max<size_t>((size_t) n, 1) * sizeof(int32_t)) : nullptr;
+	if ((slot_src_out && !ss) || (want_diag && !ds))
+	{
+		free(ss);
+		free(ds);
+		set_error("%s: out of host memory (%zu slots, %ld rows)", what, slots, n);
+		return 1;
+	}
+	if (ss)
+		memcpy(ss, L.slot_src.data(), slots * sizeof(int32_t));
+	if (ds)
+		memcpy(ds, L.diag_src.data(), (size_t) n * sizeof(int32_t));
+	if (slot_src_out)
+		*slot_src_out = ss;
+	if (diag_src_out)
+		*diag_src_out = ds;
+	if (slots_out)
+		*slots_out = (long) slots;
+	return 0;
+}
+
+int
+spmv_mi355x_trsv_update_values_prepare(spmv_mi355x_trsv * T, long n, const int32_t * row_ptr, const int32_t * col_idx)
+{
+	const char * what = "trsv_update_values_prepare";
+	if (!T)
+	{
+		set_error("%s: NULL handle", what);
+		return 1;
+	}
+	if (T->upd_state != 1)
+		return 0;             // a second prepare does nothing
+	if (!row_ptr)
+	{
+		set_error("%s: NULL argument ( row_ptr )", what);
+		return 1;
+	}
+	if (n != T->n)
+	{
+		set_error("%s: the pattern is not the one the handle was created with: n = %ld, the handle has %ld rows", what, n, T->n);
+		return 1;
+	}
+	if (!col_idx && row_ptr[n] > 0)
+	{
+		set_error("%s: NULL argument ( col_idx )", what);
+		return 1;
+	}
+	TrsvLayout L;
+	if (trsv_layout_checked(what, T->uplo, T->diag, n, row_ptr, col_idx, T->chain_rows, T->block_rows ? T->block_rows : -1, L))
+		return 1;
+	HIP_TRY(hipSetDevice(T->device));
+	if (trsv_same_layout(what, T, row_ptr, L))
+		return 1;
+	const bool stored = T->diag == SPMV_MI355X_DIAG_STORED;
+	void * slot_src = nullptr, * diag_src = nullptr, * status = nullptr;
+	hipEvent_t done = nullptr;
+	const size_t slot_bytes = L.slot_src.size() * sizeof(int32_t), diag_bytes = L.diag_src.size() * sizeof(int32_t);
+	if (upload_bytes(L.slot_src.data(), slot_bytes, 0, &slot_src) || (stored && upload_bytes(L.diag_src.data(), diag_bytes, 0, &diag_src))
+			|| dev_alloc_bytes(&status, 16) || hipEventCreateWithFlags(&done, hipEventDisableTiming) != hipSuccess)
+	{
+		for (void * p : {slot_src, diag_src, status})
+			if (p)
+				(void) hipFree(p);
+		if (status && !done)
+			set_error("%s: hipEventCreate failed", what);           // the allocations have set their own message
+		return 1;
+	}
+	T->upd_slot_src = (int *) slot_src;
+	T->upd_diag_src = (int *) diag_src;
+	T->upd_status = (unsigned *) status;
+	T->upd_done = done;
+	if (stored)
+	{
+		// by row, for the message of a refusal
+		T->upd_diag_entry.assign((size_t) n, 0);
+		for (long p = 0; p < n; p++)
+			T->upd_diag_entry[L.perm[p]] = L.diag_src[p];
+	}
+	T->nnz_csr = row_ptr[n];
+	T->upd_bytes = (double) slot_bytes + (stored ? (double) diag_bytes : 0) + 16;
+	T->upd_state = 2;
+	return 0;
+}
+
+double
+spmv_mi355x_trsv_update_values_bytes(const spmv_mi355x_trsv * T)
+{
+	return T ? T->upd_bytes : 0;
+}
+
+int
+spmv_mi355x_trsv_update_values_state(const spmv_mi355x_trsv * T)
+{
+	return T ? T->upd_state : 0;
+}
+
+int
+spmv_mi355x_trsv_update_values_device_async(spmv_mi355x_trsv * T, const double * values_dev, void * hip_stream)
+{
+	if (!trsv_update_arguments_ok(T, values_dev))
+		return 1;
+	T->upd_pending = false;
+	if (T->n == 0)
+	{
+		T->upd_bad_row = -1;
+		T->upd_state = 2;
+		return 0;
+	}
+	int cur = -1;
+	HIP_TRY(hipGetDevice(&cur));
+	if (cur != T->device)
+		HIP_TRY(hipSetDevice(T->device));
+	hipStream_t st = (hipStream_t) hip_stream;
+	const bool stored = T->diag == SPMV_MI355X_DIAG_STORED;
+	HIP_TRY(hipMemsetAsync(T->upd_status, 0xff, 16, st));
+	if (stored && launch_trsv_update_check(T->f32, T->upd_diag_src, T->arr.perm, values_dev, T->upd_status, T->n, st))
+		return 1;
+	if (launch_trsv_update_write(T->f32, T->upd_slot_src, stored ? T->upd_diag_src : nullptr, values_dev, T->owned[0], T->owned[5],
+			T->upd_status, T->slots, T->n, st))
+		return 1;
+	HIP_TRY(hipEventRecord(T->upd_done, st));
+	T->upd_last = values_dev;
+	T->upd_pending = true;
+	return 0;
+}
+
+int
+spmv_mi355x_trsv_update_values_result(spmv_mi355x_trsv * T, long * bad_row_out)
+{
+	if (bad_row_out)
+		*bad_row_out = -1;
+	if (!trsv_update_arguments_ok(T, nullptr, false))
+		return 1;
+	if (T->upd_pending)
+	{
+		HIP_TRY(hipSetDevice(T->device));
+		HIP_TRY(hipEventSynchronize(T->upd_done));
+		unsigned word = TRSV_UPDATE_FINE;
+		HIP_TRY(hipMemcpy(&word, T->upd_status, sizeof(word), hipMemcpyDeviceToHost));
+		T->upd_pending = false;
+		T->upd_bad_row = word == TRSV_UPDATE_FINE ? -1 : (long) word;
+		if (T->upd_bad_row >= 0)
+			HIP_TRY(hipMemcpy(&T->upd_bad_value, T->upd_last + T->upd_diag_entry[T->upd_bad_row], sizeof(double), hipMemcpyDeviceToHost));
+		T->upd_state = T->upd_bad_row >= 0 ? 3 : 2;
+	}
+	if (T->upd_bad_row < 0 || T->upd_state != 3)
+		return 0;
+	if (bad_row_out)
+		*bad_row_out = T->upd_bad_row;
+	const double v = T->upd_bad_value;
+	set_error("trsv_update_values: the diagonal of row %ld is %g in the handle's precision (from %g): it must be finite and non-zero",
+			T->upd_bad_row, T->f32 ? (double) (float) v : v, v);
+	return 1;
+}
+
+int
+spmv_mi355x_trsv_update_values_device(spmv_mi355x_trsv * T, const double * values_dev, void * hip_stream)
+{
+	return spmv_mi355x_trsv_update_values_device_async(T, values_dev, hip_stream) || spmv_mi355x_trsv_update_values_result(T, nullptr);
+}
+
+int
+spmv_mi355x_trsv_update_values(spmv_mi355x_trsv * T, const double * values_host)
+{
+	if (!trsv_update_arguments_ok(T, values_host))
+		return 1;
+	HIP_TRY(hipSetDevice(T->device));
+	const size_t bytes = (size_t) T->nnz_csr * sizeof(double);
+	if (!T->upd_values && dev_alloc_bytes((void **) &T->upd_values, bytes))
+		return 1;
+	if (bytes)
+		HIP_TRY(hipMemcpyAsync(T->upd_values, values_host, bytes, hipMemcpyHostToDevice, nullptr));
+	return spmv_mi355x_trsv_update_values_device(T, T->upd_values, nullptr);
+}
+
+int
+spmv_mi355x_trsv_update_values_staged(spmv_mi355x_trsv * T, const double ** values_dev_out)
+{
+	if (values_dev_out)
+		*values_dev_out = nullptr;
+	if (!T || !values_dev_out || !T->upd_values)
+	{
+		set_error("trsv_update_values_staged: %s", !T ? "NULL handle" : !values_dev_out ? "NULL argument ( values_dev_out )"
+				: "the handle has taken no host values yet (spmv_mi355x_trsv_update_values)");
+		return 1;
+	}
+	*values_dev_out = T->upd_values;
+	return 0;
+}
+
+int
+spmv_mi355x_trsv_stored_values(spmv_mi355x_trsv * T, void * val_host, long * slots_out, void * diag_host)
+{
+	if (!T)
+	{
+		set_error("trsv_stored_values: NULL handle");
+		return 1;
+	}
+	if (slots_out)
+		*slots_out = T->slots;
+	if (!val_host)
+		return 0;
+	HIP_TRY(hipSetDevice(T->device));
+	HIP_TRY(hipDeviceSynchronize());          // an update in flight on any stream is in the bytes returned
+	const size_t size = T->f32 ? 4 : 8;
+	if (T->slots)
+		HIP_TRY(hipMemcpy(val_host, T->arr.val, (size_t) T->slots * size, hipMemcpyDeviceToHost));
+	if (diag_host && T->diag == SPMV_MI355X_DIAG_STORED && T->n)
+		HIP_TRY(hipMemcpy(diag_host, T->arr.diag, (size_t) T->n * size, hipMemcpyDeviceToHost));
 	return 0;
 }
 

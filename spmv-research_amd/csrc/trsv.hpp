@@ -32,6 +32,9 @@ constexpr int TRSV_CHAIN_ROWS_MAX = 65536;
 constexpr int TRSV_BLOCK_ROWS_DEFAULT = 4096;     // NOT from a sweep yet: profiles/r18_trsv_blocked.txt says what was measured
 constexpr int TRSV_BLOCK_ROWS_MAX = 16384;        // 16384 fp64 values = 128 KiB of the 160 KiB of LDS a workgroup may declare
 constexpr int TRSV_BLOCKED_THREADS_MAX = 1024;
+constexpr int TRSV_UPDATE_BLOCK = 256;            // threads per workgroup of the two update_values kernels
+constexpr long TRSV_UPDATE_MAX_GRID = 2048;       // their workgroups per launch, ILU0_MAX_GRID's rule: 8 x 256 threads on each of 256 CUs
+constexpr unsigned TRSV_UPDATE_FINE = 0xffffffffu;        // the status word when no diagonal was refused; else the lowest bad row
 
 struct TrsvArrays {
 	const void * val;                 // values in the handle's precision, slice by slice
@@ -77,6 +80,14 @@ int launch_trsv_chain_multi(bool f32, bool unit, const TrsvArrays & a, const Trs
 int launch_trsv_blocked_multi(bool f32, bool unit, const TrsvArrays & a, long blocks, int threads, long block_rows, long n,
 		const TrsvCols & c, hipStream_t st);
 
+// UPDATE_VALUES (kernels_trsv_update.hip). values = the caller's fp64 entries in the order of the CSR given to prepare; slot_src has
+// `slots` entries (-1 = padding), diag_src n (nullptr under DIAG_UNIT). check does atomicMin(status, row) for every diagonal that is
+// zero or not finite in the handle's precision; write returns at once when status names a row.
+int launch_trsv_update_check(bool f32, const int * diag_src, const int * perm, const double * values, unsigned * status, long n,
+		hipStream_t st);
+int launch_trsv_update_write(bool f32, const int * slot_src, const int * diag_src, const double * values, void * val, void * diag,
+		const unsigned * status, long slots, long n, hipStream_t st);
+
 // the widest chunk of a blocked handle: the largest KC in {8, 4, 2, 1} whose part of X fits in LDS
 inline int
 trsv_blocked_kmax(long block_rows, long n, bool f32)
@@ -105,6 +116,20 @@ struct spmv_mi355x_trsv {
 	void * d_bk = nullptr, * d_xk = nullptr;   // the n x block_k blocks of the host-buffer k-column solve, regrown for a larger k
 	int block_k = 0;
 	double mem_footprint = 0;
+	long slices = 0, slots = 0;           // of the stored layout: slots = slice_ptr[slices] entries of val and col
+	long nnz_csr = 0;                     // row_ptr[n] of the CSR given to create, then of the one given to update_values_prepare
+	// update_values (trsv.hip): nothing below is allocated before update_values_prepare, none of it counts in mem_footprint
+	int upd_state = 1;                    // 1 = prepare is missing, 2 = ready, 3 = the last update was refused
+	int * upd_slot_src = nullptr, * upd_diag_src = nullptr;       // device: slots and n entries
+	unsigned * upd_status = nullptr;      // device: 16 bytes, the first word is the status word
+	std::vector<int32_t> upd_diag_entry;  // host, STORED: the entry of row i's diagonal, for the refusal's message
+	double * upd_values = nullptr;        // device staging of the host form, allocated at its first call and kept
+	hipEvent_t upd_done = nullptr;        // recorded behind the last async update
+	const double * upd_last = nullptr;    // the values of the last async update (device), until its result was taken
+	bool upd_pending = false;
+	long upd_bad_row = -1;                // what the last result found: the refused row and its diagonal as given (-1: none)
+	double upd_bad_value = 0;
+	double upd_bytes = 0;
 };
 
 namespace spmv {

@@ -84,6 +84,10 @@ SYMBOLS = [
     "spmv_mi355x_time_trsv_multi_device", "spmv_mi355x_pcg_trsm_multi",
     "spmv_mi355x_ilu0_create", "spmv_mi355x_ilu0_factor", "spmv_mi355x_ilu0_factor_device_async", "spmv_mi355x_ilu0_values",
     "spmv_mi355x_ilu0_values_device", "spmv_mi355x_ilu0_get_info", "spmv_mi355x_ilu0_mem_footprint", "spmv_mi355x_ilu0_destroy",
+    "spmv_mi355x_trsv_update_map", "spmv_mi355x_trsv_update_values_prepare", "spmv_mi355x_trsv_update_values_bytes",
+    "spmv_mi355x_trsv_update_values_state", "spmv_mi355x_trsv_update_values_device_async", "spmv_mi355x_trsv_update_values_result",
+    "spmv_mi355x_trsv_update_values_device", "spmv_mi355x_trsv_update_values", "spmv_mi355x_trsv_stored_values",
+    "spmv_mi355x_trsv_update_values_staged",
 ]
 
 _lib = None
@@ -182,6 +186,26 @@ def lib():
         L.spmv_mi355x_ilu0_mem_footprint.argtypes = [C.c_void_p]
         L.spmv_mi355x_ilu0_destroy.restype = C.c_int
         L.spmv_mi355x_ilu0_destroy.argtypes = [C.c_void_p]
+        L.spmv_mi355x_trsv_update_map.restype = C.c_int
+        L.spmv_mi355x_trsv_update_map.argtypes = [C.c_int, C.c_int, C.c_long, C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_void_p,
+                                                  C.POINTER(C.c_long), C.c_void_p]
+        L.spmv_mi355x_trsv_update_values_prepare.restype = C.c_int
+        L.spmv_mi355x_trsv_update_values_prepare.argtypes = [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p]
+        L.spmv_mi355x_trsv_update_values_bytes.restype = C.c_double
+        L.spmv_mi355x_trsv_update_values_bytes.argtypes = [C.c_void_p]
+        L.spmv_mi355x_trsv_update_values_state.restype = C.c_int
+        L.spmv_mi355x_trsv_update_values_state.argtypes = [C.c_void_p]
+        for f in ("spmv_mi355x_trsv_update_values_device_async", "spmv_mi355x_trsv_update_values_device"):
+            getattr(L, f).restype = C.c_int
+            getattr(L, f).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.spmv_mi355x_trsv_update_values_result.restype = C.c_int
+        L.spmv_mi355x_trsv_update_values_result.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
+        L.spmv_mi355x_trsv_update_values.restype = C.c_int
+        L.spmv_mi355x_trsv_update_values.argtypes = [C.c_void_p, C.c_void_p]
+        L.spmv_mi355x_trsv_update_values_staged.restype = C.c_int
+        L.spmv_mi355x_trsv_update_values_staged.argtypes = [C.c_void_p, C.c_void_p]
+        L.spmv_mi355x_trsv_stored_values.restype = C.c_int
+        L.spmv_mi355x_trsv_stored_values.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_long), C.c_void_p]
         _lib = L
     return _lib
 
@@ -348,6 +372,25 @@ def trsv_analyze_blocked(row_ptr, col_idx, n, uplo, block_rows=0):
                 nnz_dropped=dropped.value, block_rows=used.value)
 
 
+def trsv_update_map(row_ptr, col_idx, n, uplo, diag="stored", chain_rows=0, block_rows=None):
+    """Where TriangularSolve.update_values takes every stored value from, derived on the host from the pattern alone
+    (spmv_mi355x_trsv_update_map): dict(slot_src, slots, diag_src). slot_src[e] is the entry of the given CSR in slot e of the stored
+    value array (-1: padding); diag_src[p] the first stored diagonal of the row at position p (None under diag="unit"). block_rows =
+    None gives the global form, 0 or a size the blocked one."""
+    row_ptr = np.ascontiguousarray(row_ptr, np.int32)
+    col_idx = np.ascontiguousarray(col_idx, np.int32)
+    ss, ds, slots = C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)(), C.c_long()
+    _check(lib().spmv_mi355x_trsv_update_map(_UPLO[uplo], _DIAG[diag], n, _p(row_ptr), _p(col_idx), chain_rows,
+                                             -1 if block_rows is None else block_rows, C.byref(ss), C.byref(slots), C.byref(ds)))
+    slot_src = np.ctypeslib.as_array(ss, shape=(max(slots.value, 1),))[:slots.value].copy()
+    lib().spmv_mi355x_free(ss)
+    diag_src = None
+    if ds:
+        diag_src = np.ctypeslib.as_array(ds, shape=(max(n, 1),))[:n].copy()
+        lib().spmv_mi355x_free(ds)
+    return dict(slot_src=slot_src, slots=slots.value, diag_src=diag_src)
+
+
 class TriangularSolve:
     """T x = b for one triangle of a square CSR matrix (include/spmv_mi355x.h "sparse triangular solve"): uplo "lower" keeps the
     entries with column <= row, "upper" those with column >= row; diag "stored" divides by the stored diagonal, "unit" takes 1 and
@@ -364,6 +407,7 @@ class TriangularSolve:
         values = np.ascontiguousarray(values, np.float64)
         self.dtype = np.dtype(dtype)
         self.n = int(n)
+        self.diag = _DIAG[diag]
         self.h = C.c_void_p()
         if block_rows is None:
             _check(lib().spmv_mi355x_trsv_create(C.byref(self.h), C.c_int(_UPLO[uplo]), C.c_int(_DIAG[diag]),
@@ -440,6 +484,64 @@ class TriangularSolve:
                                                         C.c_void_p(stream or 0), C.byref(ms)))
         return ms.value
 
+    def update_values_prepare(self, row_ptr, col_idx):
+        """Once per handle: derive and upload the entry map from the CSR the handle was created with, which also fixes the entry
+        order of every later values array (spmv_mi355x_trsv_update_values_prepare). A second call does nothing."""
+        row_ptr = np.ascontiguousarray(row_ptr, np.int32)
+        col_idx = np.ascontiguousarray(col_idx, np.int32)
+        _check(lib().spmv_mi355x_trsv_update_values_prepare(self.h, self.n, _p(row_ptr), _p(col_idx)))
+        self._update_nnz = int(row_ptr[self.n])
+        return self
+
+    def update_values(self, values):
+        """New host values in the entry order of prepare's CSR; the handle becomes byte for byte what the constructor builds from
+        them (spmv_mi355x_trsv_update_values; blocking). A zero or non-finite new diagonal raises, names the row and leaves the
+        previous values in place."""
+        values = np.ascontiguousarray(values, np.float64)
+        nnz = getattr(self, "_update_nnz", None)
+        if nnz is not None and values.shape != (nnz,):
+            raise ValueError(f"values must have {nnz} entries, got {values.shape}")
+        _check(lib().spmv_mi355x_trsv_update_values(self.h, _p(values)))
+        return self
+
+    def update_values_device(self, ptr, stream=None, wait=True):
+        """The same from a device pointer to fp64 values, enqueued on `stream`. wait=True (spmv_mi355x_trsv_update_values_device)
+        blocks and raises on a refusal; wait=False (spmv_mi355x_trsv_update_values_device_async) returns at once: the refusal is then
+        decided on the device alone and update_values_result() reports it. Solves of this handle must be ordered behind the update
+        through the stream."""
+        fn = lib().spmv_mi355x_trsv_update_values_device if wait else lib().spmv_mi355x_trsv_update_values_device_async
+        _check(fn(self.h, C.c_void_p(ptr), C.c_void_p(stream or 0)))
+        return self
+
+    def update_values_result(self):
+        """Waits for the last async update: -1 when it was accepted, else the lowest refused row, the handle holding the values from
+        before it (spmv_mi355x_trsv_update_values_result; the message is in spmv_mi355x_last_error)"""
+        bad = C.c_long(-1)
+        rc = lib().spmv_mi355x_trsv_update_values_result(self.h, C.byref(bad))
+        if rc != 0 and bad.value < 0:
+            _check(rc)
+        return bad.value
+
+    @property
+    def update_values_state(self):
+        """1 = update_values_prepare is missing, 2 = ready, 3 = the last update was refused (spmv_mi355x_trsv_update_values_state)"""
+        return lib().spmv_mi355x_trsv_update_values_state(self.h)
+
+    @property
+    def update_values_bytes(self):
+        """device bytes of the entry maps and the status block, which mem_footprint does not count; 0 before prepare"""
+        return lib().spmv_mi355x_trsv_update_values_bytes(self.h)
+
+    def stored_values(self):
+        """(val, diag): the stored value array, padding included, and the diagonal by position, both in the handle's precision; diag
+        is None under diag="unit" (spmv_mi355x_trsv_stored_values; blocking)"""
+        slots = C.c_long()
+        _check(lib().spmv_mi355x_trsv_stored_values(self.h, None, C.byref(slots), None))
+        val = np.zeros(max(slots.value, 1), self.dtype)
+        diag = np.zeros(max(self.n, 1), self.dtype) if self.diag == DIAG_STORED else None
+        _check(lib().spmv_mi355x_trsv_stored_values(self.h, _p(val), C.byref(slots), None if diag is None else _p(diag)))
+        return val[:slots.value], None if diag is None else diag[:self.n]
+
     def close(self):
         if getattr(self, "h", None) is not None and self.h:
             lib().spmv_mi355x_trsv_destroy(self.h)
@@ -469,6 +571,29 @@ def sgs_precond(row_ptr, col_idx, values, n, dtype=np.float64, block_rows=None, 
     first = TriangularSolve(row_ptr, col_idx, values, n, uplo="lower", dtype=dtype, block_rows=block_rows, **trsv_opts)
     second = TriangularSolve(row_ptr, col_idx, values, n, uplo="upper", dtype=dtype, block_rows=block_rows, **trsv_opts)
     return first, values[at].astype(dtype), second
+
+
+def sgs_precond_update(precond, row_ptr, col_idx, values):
+    """New values of A, same pattern, for the triple sgs_precond returned: both handles are prepared on first use and updated from
+    ONE upload of `values` (TriangularSolve.update_values_device), the scale array is rewritten in place with the new first-stored
+    diagonals. Returns the triple. A zero or non-finite new diagonal raises before anything is written: both handles check the same
+    diagonals and each keeps its previous values."""
+    first, scale, second = precond
+    row_ptr = np.ascontiguousarray(row_ptr, np.int32)
+    col_idx = np.ascontiguousarray(col_idx, np.int32)
+    values = np.ascontiguousarray(values, np.float64)
+    n = first.n
+    rows = np.repeat(np.arange(n), np.diff(row_ptr))
+    at = np.nonzero(col_idx == rows)[0]
+    at = at[np.unique(rows[at], return_index=True)[1]]               # the first of every row
+    first.update_values_prepare(row_ptr, col_idx)
+    second.update_values_prepare(row_ptr, col_idx)
+    first.update_values(values)                                      # the one upload: the handle's staging buffer
+    staged = C.c_void_p()
+    _check(lib().spmv_mi355x_trsv_update_values_staged(first.h, C.byref(staged)))
+    second.update_values_device(staged.value or 0, wait=True)
+    scale[:] = values[at].astype(scale.dtype)
+    return first, scale, second
 
 
 class Ilu0Info(C.Structure):
@@ -546,6 +671,23 @@ class Ilu0:
             first.close()
             raise
         return first, None, second
+
+    def update_precond(self, precond, stream=None, wait=True):
+        """Refresh the triple precond() returned with the factor this handle holds NOW (after a later factor / factor_device): both
+        TriangularSolve handles are prepared on first use with the factor's own pattern and updated from values_device(), enqueued
+        on `stream`; no host copy of f is made and nothing is analysed or laid out again. Returns the triple.
+        A breakdown surfaces as the UPPER handle's refusal, which names the row: `second` is therefore updated first, and when it
+        refused, `first` (LOWER / UNIT, which cannot refuse) is skipped, so both handles keep solving with the previous factor.
+        wait=False enqueues both updates and returns at once: the guard is then the device-side one alone (`second` keeps its values
+        when a pivot is bad, `first` is updated regardless) and the caller must ask second.update_values_result() before trusting
+        the pair. Solves must be ordered behind the updates through the stream."""
+        first, _, second = precond
+        for T in (first, second):
+            T.update_values_prepare(self.row_ptr, self.col_idx)
+        f = self.values_device()
+        second.update_values_device(f, stream, wait)
+        first.update_values_device(f, stream, wait)
+        return precond
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h:

@@ -20,6 +20,14 @@ a diagonal in few of its rows, --add-diagonal factorizes A + diag(1 + row sums o
     python tools/ilu0_bench.py                                       # stencil160, grid2d2000, cant, convdiff1000; global and B = 4096
     python tools/ilu0_bench.py --runs grid2d2000 --block-rows 1024,4096,16384
     python tools/ilu0_bench.py --runs stencil160 --no-solve          # factorization only
+With --refresh nothing above is solved. Per workload and variant the tool factorizes V1, builds the triple with precond() and then
+times, in one process and in --windows alternating windows after a warm-up, a refactorization on new values V2 two ways:
+  rebuild:  factor(V2) + precond(): host values in, f copied back, two trsv_create calls; the only path before trsv handles could
+            take new values, and still callable;
+  refresh:  factor_device(V2 resident) + update_precond(triple) and a synchronise: no host copy of f, no analysis, no layout;
+and, apart from the factorization, precond() alone against update_precond() alone. Medians with min .. max, the bytes the two
+updates move by the layout's own count, and whether the refreshed handles have the rebuilt handles' bytes. No ratio is asserted.
+    python tools/ilu0_bench.py --refresh --runs stencil160,grid2d2000 --block-rows 4096 --windows 7
 One JSON line per variant."""
 import argparse
 import json
@@ -94,6 +102,53 @@ def factor_legs(E, torch, ic, workload, rp, ci, va, n, B, args):
     return F, rec
 
 
+def refresh_legs(E, torch, workload, rp, ci, va, n, B, args):
+    """--refresh: factor + precond() against factor_device + update_precond on the same new values"""
+    rows = np.repeat(np.arange(n), np.diff(rp))
+    v2 = np.where(rows == ci, 1.3, 0.9) * va                  # same pattern, still symmetric and dominant
+    del rows
+    dev = torch.from_numpy(v2).cuda()
+    torch.cuda.synchronize()
+    F = E.Ilu0(rp, ci, n, block_rows=B)
+    M = F.factor(va).precond()
+    t0 = time.perf_counter()
+    F.update_precond(M)                                       # prepares both handles: once
+    prepare = time.perf_counter() - t0
+    rebuild, refresh, handles_new, handles_upd = [], [], [], []
+    W = None
+    for w in range(args.windows + 1):                         # window 0 warms up and is dropped
+        close(W)
+        t0 = time.perf_counter()
+        F.factor(v2)
+        t1 = time.perf_counter()
+        W = F.precond()
+        t2 = time.perf_counter()
+        F.factor_device(dev.data_ptr())
+        torch.cuda.synchronize()                              # only to time the two halves apart: a caller enqueues straight on
+        t3 = time.perf_counter()
+        F.update_precond(M)
+        torch.cuda.synchronize()
+        t4 = time.perf_counter()
+        if w:
+            rebuild.append(t2 - t0)
+            handles_new.append(t2 - t1)
+            refresh.append(t4 - t2)
+            handles_upd.append(t4 - t3)
+    same = all(np.array_equal(x.view(np.uint8), y.view(np.uint8)) for k in (0, 2)
+               for x, y in zip(M[k].stored_values(), W[k].stored_values()) if x is not None)
+    slots = [len(M[k].stored_values()[0]) for k in (0, 2)]
+    info = F.info
+    rec = dict(workload=workload, n=int(n), nnz=int(len(ci)), variant="global" if B is None else f"B={info['block_rows']}",
+               prepare_and_first_update_seconds=round(prepare, 4), rebuild_seconds=spread(rebuild), refresh_seconds=spread(refresh),
+               precond_seconds=spread(handles_new), update_precond_seconds=spread(handles_upd),
+               update_bytes=int((slots[0] + slots[1] + n) * 20), f_bytes=int(8 * len(ci)), trsv_launches=M[0].info["launches"] + M[2].info["launches"],
+               ilu0_launches=info["launches"], windows=args.windows, same_bytes=bool(same))
+    close(M)
+    close(W)
+    F.close()
+    return rec
+
+
 def pcg_legs(E, A, b, M, args):
     r = A.pcg_tri(b, precond=M, tol=args.tol, max_iterations=args.max_iterations, history=False)
     fixed = A.pcg_tri(b, precond=M, tol=0.0, max_iterations=0, history=False)["seconds"]
@@ -111,6 +166,11 @@ def close(M):
 def run(E, torch, ic, workload, args):
     rp, ci, va, n, kind = load(workload, args)
     rp = np.asarray(rp, np.int32)
+    if args.refresh:
+        for B in [None] + list(args.block_rows):
+            print(json.dumps(refresh_legs(E, torch, workload, rp, np.asarray(ci, np.int32), np.asarray(va, np.float64), n, B, args)),
+                  flush=True)
+        return
     A = None if kind == "factor only" or args.no_solve else E.Matrix(rp, ci, va, n, n, "sell_c_sigma", np.float64)
     b = np.random.default_rng(7).uniform(-1, 1, n)
     variants = ([None] if kind != "nonsymmetric" else []) + list(args.block_rows)
@@ -164,6 +224,8 @@ def main():
     ap.add_argument("--add-diagonal", action="store_true",
                     help="generated twins: factorize A + diag(1 + row sums of |a|) (the cant twin stores a diagonal in few of its rows)")
     ap.add_argument("--no-solve", action="store_true", help="factorization only")
+    ap.add_argument("--refresh", action="store_true",
+                    help="time factor + precond() against factor_device + update_precond on new values of the same pattern")
     ap.add_argument("--no-reference", action="store_true", help="skip the sequential loop on the host")
     args = ap.parse_args()
     args.block_rows = [int(v) for v in args.block_rows.split(",") if v != ""]

@@ -23,6 +23,17 @@ the plan, ms per solve, and ms per column over the single solve's ms (1 / k when
     python tools/trsv_bench.py --runs nlpkkt240:f64 --scale 0.25
     python tools/trsv_bench.py --runs cant:f64,cant:f32,stencil160:f64,nlpkkt240:f64 --chain-rows 256 --block-rows 1024,2048,4096,8192,16384
     python tools/trsv_bench.py --runs stencil160:f64 --chain-rows 256 --block-rows 1024,2048,4096 --rhs 1,2,4,8
+With --update nothing above is timed. Instead, per run and per variant (the global handle of the first --chain-rows value and the
+blocked handle of every --block-rows value), the tool times in one process and in alternating windows
+  create:  TriangularSolve(...) on new values V2: host analysis, layout and nine uploads, which is what a handle cost before it
+           could take new values;
+  update:  update_values_device on V2 resident on the device, with a synchronise behind it (spmv_mi355x_trsv_update_values_device),
+           and the same call once more at once ("again": the same work without the host-bound create in front of it);
+  host:    update_values on V2 in host memory (the upload of row_ptr[n] doubles included);
+and reports the medians with min .. max, update_values_prepare's seconds (once), the bytes an update moves by the layout's own count,
+slots * (4 + 8 + sizeof T) + n * (4 + 8 + sizeof T) under DIAG_STORED, and whether the updated handle has the fresh handle's bytes.
+grid2d<N> (the 5-point operator of tools/amg_bench.py) is a workload of this mode too. No ratio is asserted.
+    python tools/trsv_bench.py --update --runs stencil160:f64,grid2d2000:f64 --chain-rows 256 --block-rows 4096
 One JSON line per run and a table at the end.
 """
 import argparse
@@ -159,6 +170,61 @@ def run(E, torch, name, rp, ci, va, n, dts, data, args):
     return rec
 
 
+def spread(ts):
+    return dict(median=round(float(np.median(ts)), 6), min=round(min(ts), 6), max=round(max(ts), 6))
+
+
+def run_update(E, torch, name, rp, ci, va, n, dts, args):
+    """--update: a fresh handle on V2 against update_values of a handle that exists; one JSON line per variant"""
+    np_dtype = np.float32 if dts == "f32" else np.float64
+    rp, ci, va = lower_triangle(rp, ci, va, n)
+    va, stored = safe_diagonal(rp, ci, va, n)
+    diag = "stored" if stored else "unit"
+    v2 = va * np.random.default_rng(2).uniform(1.0, 1.5, len(va))
+    dev = torch.from_numpy(v2).cuda()
+    torch.cuda.synchronize()
+    out = []
+    for key in [("chain_rows", args.chain_rows[0])] + [("block_rows", B) for B in args.block_rows]:
+        make = lambda v: E.TriangularSolve(rp, ci, v, n, "lower", diag, np_dtype, **{key[0]: key[1]})
+        T = make(va)
+        t0 = time.perf_counter()
+        T.update_values_prepare(rp, ci)
+        prepare = time.perf_counter() - t0
+        create, update, again, host = [], [], [], []
+        for w in range(args.windows + 1):                 # window 0 warms every leg up and is dropped
+            t0 = time.perf_counter()
+            fresh = make(v2)
+            t1 = time.perf_counter()
+            T.update_values_device(dev.data_ptr())
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            T.update_values_device(dev.data_ptr())        # again at once: the same work without the host-bound pause before it
+            torch.cuda.synchronize()
+            t2b = time.perf_counter()
+            T.update_values(v2)
+            t3 = time.perf_counter()
+            if w:
+                create.append(t1 - t0)
+                update.append(t2 - t1)
+                again.append(t2b - t2)
+                host.append(t3 - t2b)
+            if w < args.windows:
+                fresh.close()
+        a, b = T.stored_values(), fresh.stored_values()
+        same = all((x is None and y is None) or np.array_equal(x.view(np.uint8), y.view(np.uint8)) for x, y in zip(a, b))
+        slots, size = len(a[0]), np.dtype(np_dtype).itemsize
+        rec = dict(workload=name, dtype=dts, n=int(n), nnz=int(len(ci)), variant=f"{key[0]}={key[1]}", diag=diag, slots=slots,
+                   levels=T.info["levels"], launches=T.info["launches"], prepare_seconds=round(prepare, 4), create_seconds=spread(create),
+                   update_device_seconds=spread(update), update_device_again_seconds=spread(again), update_host_seconds=spread(host),
+                   update_bytes=int((slots + (n if stored else 0)) * (4 + 8 + size)), map_mib=round(T.update_values_bytes / 2 ** 20, 1),
+                   handle_mib=round(T.mem_footprint / 2 ** 20, 1), windows=args.windows, same_bytes=bool(same))
+        print(json.dumps(rec), flush=True)
+        out.append(rec)
+        T.close()
+        fresh.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", default="cant:f64,nlpkkt240:f64,stencil160:f64", help="workload|stencil<N>:f64|f32,...")
@@ -169,6 +235,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20, help="SpMV launches per timed floor leg")
     ap.add_argument("--leg-ms", type=float, default=40.0, help="solves per timed leg: as many as last about this long (3 .. 200)")
     ap.add_argument("--scale", type=float, default=1.0, help="shrink the workload twins")
+    ap.add_argument("--update", action="store_true", help="time a fresh handle on new values against update_values of an existing one")
     args = ap.parse_args()
     if args.windows < 5:
         ap.error("--windows: at least 5")
@@ -191,14 +258,29 @@ def main():
         if w.startswith("stencil"):
             rp, ci, va, n = stencil27(int(w[len("stencil"):]))
             data = "generated"
+        elif w.startswith("grid2d") and args.update:
+            from amg_bench import grid2d
+            rp, ci, va, n = grid2d(int(w[len("grid2d"):]), 0.001)
+            data = "generated"
         else:
             A, data = bench.load_workload(H, w, args.scale)
             if A["m"] != A["n"]:
                 raise SystemExit(f"{w}: {A['m']} x {A['n']} is not square")
             rp, ci, va, n = A["row_ptr"], A["col_idx"], np.ascontiguousarray(A["values"], np.float64), A["n"]
             del A
+        if args.update:
+            rows += run_update(E, torch, w, np.asarray(rp, np.int32), ci, np.ascontiguousarray(va, np.float64), n, dts, args)
+            continue
         rows.append(run(E, torch, w, rp, ci, va, n, dts, data, args))
         del rp, ci, va
+    if args.update:
+        print(f"{'workload':11s} {'dtype':5s} {'variant':>16s} {'slots':>10s} {'create s':>9s} {'update s':>9s} {'host form s':>11s} "
+              f"{'create / update':>15s} {'update GB/s':>11s}")
+        for r in rows:
+            c, u = r["create_seconds"]["median"], r["update_device_seconds"]["median"]
+            print(f"{r['workload']:11s} {r['dtype']:5s} {r['variant']:>16s} {r['slots']:10d} {c:9.4f} {u:9.6f} "
+                  f"{r['update_host_seconds']['median']:11.4f} {c / max(u, 1e-9):15.1f} {r['update_bytes'] / max(u, 1e-9) / 1e9:11.1f}")
+        return
     print(f"{'workload':11s} {'dtype':5s} {'n':>9s} {'kept nnz':>10s} {'levels':>7s} {'widest':>8s} {'spmv ms':>9s} | "
           f"{'chain_rows':>10s} {'launches':>8s} {'trsv ms':>9s} {'spread':>19s} {'/ floor':>8s}")
     for r in rows:

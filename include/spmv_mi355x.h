@@ -730,6 +730,59 @@ int  spmv_mi355x_trsv_solve_multi_plan(const spmv_mi355x_trsv * T, int k, long *
 int  spmv_mi355x_time_trsv_multi_device(spmv_mi355x_trsv * T, int k, const void * b_dev, long ldb, void * x_dev, long ldx, int iters,
 		void * hip_stream, double * ms_per_iter_out);
 
+/* JACOBI SWEEPS: T^-1 b approximated by a fixed number of sweeps, each ONE full-width launch (csrc/trsv.hip,
+ * csrc/kernels_trsv_sweeps.hip). With T = D + N (D the diagonal, 1 under DIAG_UNIT):
+ *     x(1) = D^-1 b,    x(m + 1) = D^-1 (b - N x(m)),    x = x(sweeps)
+ * Every sweep is one launch over all n rows, one lane per row, over the arrays the handle already stores: no levels, no chains, no
+ * ordering inside the launch, no new copy of the values, no new analysis. Any handle serves, global or blocked (a blocked handle
+ * drops the entries that couple two blocks, as in its exact solve). A fixed sweep count is a fixed linear operator, so CG and GMRES
+ * may be given it as a preconditioner.
+ * PINNED TO THE BIT (tests/trsv_sweeps_reference.c): per row and sweep, s = b[i]; from the second sweep on, for each kept
+ * off-diagonal entry (i, j, a) in stored order s = fma(-a, x(m)[j], s); x(m + 1)[i] = s / d_i (s under DIAG_UNIT), in the handle's
+ * precision with an IEEE division. The first sweep reads no entry at all. This is the row expression of the exact solve, so a row
+ * of level l holds the exact solve's bits from sweep l + 1 on, and sweeps >= levels returns THE BITS OF trsv_solve.
+ * EFFECTIVE SWEEPS. Because of that the library runs min(sweeps, levels) sweeps, `levels` being the figure of trsv_info
+ * (max_block_levels for a blocked handle; 0 at n = 0, where nothing is launched): a large sweep count is an exact solve in `levels`
+ * full-width launches, and the work is bounded.
+ *   - trsv_solve_sweeps_device_async(T, sweeps, b, x, stream): enqueued on hip_stream; b_dev == x_dev (in place) is legal. Only
+ *     x[0 .. n) is written in the caller's memory, but x ALSO HOLDS INTERMEDIATE SWEEPS until the solve has finished; b is never
+ *     modified (in place it is x). trsv_solve_sweeps is the blocking host form (the vectors of trsv_solve).
+ *   - trsv_solve_sweeps_multi_device_async / trsv_solve_sweeps_multi: k columns of row-major blocks, the arguments and the rules of
+ *     trsv_solve_multi (ld >= k, in place needs ldb == ldx, the ld - k padding columns are neither read nor written). Chunks of
+ *     8, 4, 2, 1 columns (k = 11: 8 + 2 + 1) for EVERY handle, a blocked one included: no LDS bounds the chunk here. A chunk is
+ *     `effective sweeps` launches; column j returns the bits of the single sweep solve on column j.
+ *   - THE HANDLE OWNS ITS SCRATCH: a map of slices + 1 ints (the first position of every slice), built on the GPU at the handle's
+ *     first sweep solve (that one call synchronises the stream), and, from the first solve of more than one sweep on, two n x KC
+ *     blocks (KC = the widest chunk so far; replaced when a wider one arrives, which synchronises the device). None of it is
+ *     allocated by create, none of it counts in trsv_mem_footprint(): trsv_sweeps_info reports it, the rule of the update_values
+ *     maps. CONSEQUENCE: the sweep solves of ONE handle must not run on two streams at the same time.
+ *   - trsv_set_sweeps(T, s), s > 0: from now on trsv_solve_device_async, trsv_solve, trsv_solve_multi_device_async,
+ *     trsv_solve_multi, time_trsv_device and time_trsv_multi_device of THIS handle run s sweeps in the place of the exact plan
+ *     (their refusals and prefixes stay theirs). That is how every solver that takes a spmv_mi355x_tri_precond (pcg_tri,
+ *     pcg_trsm_multi, gmres_tri) uses sweeps with no change to the struct. s = 0 (the default) restores the exact plan. trsv_info,
+ *     trsv_solve_multi_plan and trsv_mem_footprint keep describing the EXACT plan whatever the setting; a handle on which
+ *     set_sweeps was never called behaves bit for bit and launch for launch as before. update_values needs nothing new.
+ *   - SYMMETRY. The swept operator is p_s(T) = sum_{j < s} (-D^-1 N)^j D^-1 and p_s(T^t) = p_s(T)^t, so an SGS or IC(0) triple
+ *     whose two handles run the SAME sweep count is a symmetric positive definite M^-1 for a positive diagonal. Unequal counts make
+ *     M nonsymmetric and CG must not be given it; the library cannot check this. Jacobi sweeps on a factor that is far from
+ *     diagonally dominant can GROW before the nilpotency bound ends them; this is not checked either.
+ *   - trsv_sweeps_info(T, k, ...) (host only): the setting of set_sweeps, effective = min(setting, levels) (0 while the setting is 0),
+ *     launches = effective * the number of chunks of k columns, bytes = the map and scratch allocated so far (0 before any sweep solve).
+ *   - rc 1 on the host before any device is touched, prefix "trsv_solve_sweeps:", in this order: 1. a NULL handle; 2. sweeps
+ *     outside 1 .. 1048576; then the checks of trsv_solve_multi: 3. k < 1; 4. ldb < k or ldx < k; 5. b == x with ldb != ldx; 6. for
+ *     n > 0 a NULL vector (the single forms make 1, 2 and 6). "trsv_set_sweeps:": a NULL handle, sweeps outside 0 .. 1048576.
+ *     "trsv_sweeps_info:": a NULL handle, k < 1. n = 0 is rc 0 with nothing launched and nothing written.
+ *   - NOT BUILT: damped or weighted sweeps, a residual-based stop, asynchronous (chaotic) sweeps, fusing sweeps 1 and 2, skipping
+ *     the rows that are already final, sweeps inside the AMG smoother. */
+int  spmv_mi355x_trsv_solve_sweeps_device_async(spmv_mi355x_trsv * T, int sweeps, const void * b_dev, void * x_dev, void * hip_stream);
+int  spmv_mi355x_trsv_solve_sweeps(spmv_mi355x_trsv * T, int sweeps, const void * b_host, void * x_host);       /* blocking */
+int  spmv_mi355x_trsv_solve_sweeps_multi_device_async(spmv_mi355x_trsv * T, int sweeps, int k, const void * b_dev, long ldb,
+		void * x_dev, long ldx, void * hip_stream);
+int  spmv_mi355x_trsv_solve_sweeps_multi(spmv_mi355x_trsv * T, int sweeps, int k, const void * B_host, void * X_host);  /* blocking, ld = k */
+int  spmv_mi355x_trsv_set_sweeps(spmv_mi355x_trsv * T, int sweeps /* 0 = exact (the default) */);
+int  spmv_mi355x_trsv_sweeps_info(const spmv_mi355x_trsv * T, int k, int * sweeps_out, long * effective_out, long * launches_out,
+		double * bytes_out);                                                                   /* any out pointer may be NULL */
+
 /* UPDATE_VALUES: new numbers for the pattern a trsv handle was created with, scattered on the GPU. The rule of
  * spmv_mi355x_update_values: same pattern, new numbers, no rebuild, and the handle comes out BYTE FOR BYTE what trsv_create /
  * trsv_create_blocked builds from the new values: every stored value, the padding (never written: it keeps create's zeros) and the

@@ -19,33 +19,12 @@
 
 #include "solvers_common.hpp"
 #include "trsv.hpp"
+#include "trsv_rows.hpp"          // TrsvTyped, typed(), TRSV_UNROLL and the k-column row helpers, shared with the sweep kernels
 
 namespace spmv {
 
-template <typename T>
-struct TrsvTyped {
-	const T * val;
-	const int * col;
-	const int64_t * slice_ptr;
-	const int * len;
-	const int * perm;
-	const T * diag;
-	const int * level_ptr;
-	const int * level_slice;
-	const int * block_level;
-};
-
-template <typename T>
-static TrsvTyped<T>
-typed(const TrsvArrays & a)
-{
-	return TrsvTyped<T>{(const T *) a.val, a.col, a.slice_ptr, a.len, a.perm, (const T *) a.diag, a.level_ptr, a.level_slice, a.block_level};
-}
-
 // What a row needs that does not depend on x: where it is, b[i], the diagonal and its first TRSV_UNROLL entries. The chain kernel
 // loads it for the NEXT level before the barrier that ends the current one, so that behind the barrier only the gathers of x remain.
-constexpr int TRSV_UNROLL = 4;
-
 template <typename T>
 struct TrsvHead {
 	int cnt, i, lanes;
@@ -339,13 +318,6 @@ launch_trsv_blocked(bool f32, bool unit, const TrsvArrays & a, long blocks, int 
 // Registers: the gathers of one trip are U * KC values, so U shrinks as KC * sizeof(T) grows (trsv_unroll_multi); the order of the
 // fmas does not depend on U. profiles/r28_trsv_multi.txt has the compiler's resource table: no instantiation uses scratch.
 
-template <typename T, int KC>
-constexpr int
-trsv_unroll_multi()
-{
-	return KC * sizeof(T) > 32 ? 2 : TRSV_UNROLL;      // at most 64 bytes (16 VGPRs) of gathered x per entry slot
-}
-
 template <typename T>
 struct TrsvBlock {
 	const T * b;
@@ -364,39 +336,6 @@ struct TrsvHeadMulti {
 	T a[U];
 	int c[U];
 };
-
-template <typename T, int U>
-__device__ __forceinline__ void
-trsv_entries_n(const TrsvTyped<T> & a, int64_t base, int lanes, int cnt, int k, T (&av)[U], int (&cv)[U])
-{
-	#pragma unroll
-	for (int j = 0; j < U; j++)
-	{
-		const int64_t e = base + (int64_t) (k + j < cnt ? k + j : k) * lanes;
-		av[j] = a.val[e];
-		cv[j] = a.col[e];
-	}
-}
-
-// xg + col * ldg is the row of x that a stored column names: the block itself (ldg = ldx), or the workgroup's part of it in LDS
-// (ldg = KC)
-template <typename T, int KC, int U>
-__device__ __forceinline__ void
-trsv_apply_multi(const T * xg, long ldg, bool vg, int cnt, int k, const T (&av)[U], const int (&cv)[U], T (&s)[KC])
-{
-	T xv[U][KC];
-	#pragma unroll
-	for (int j = 0; j < U; j++)
-		load_row(xv[j], xg + (long) cv[j] * ldg, vg);
-	#pragma unroll
-	for (int j = 0; j < U; j++)
-		if (k + j < cnt)
-		{
-			#pragma unroll
-			for (int c = 0; c < KC; c++)
-				s[c] = fma_t<T>(-av[j], xv[j][c], s[c]);
-		}
-}
 
 template <typename T, bool UNIT, int KC>
 __device__ __forceinline__ void
@@ -566,25 +505,6 @@ trsv_block(const TrsvCols & c)
 		return KC > 1 && ld % KC == 0 && c.c0 % KC == 0 && (uintptr_t) base % (KC * sizeof(T)) == 0;
 	};
 	return TrsvBlock<T>{(const T *) c.b + c.c0, (T *) c.x + c.c0, c.ldb, c.ldx, vec(c.b, c.ldb), vec(c.x, c.ldx)};
-}
-
-// f(T(), bool_constant<UNIT>, integral_constant<int, KC>) for the handle's precision and diagonal and the chunk's width
-template <typename F>
-static int
-trsv_multi_dispatch(bool f32, bool unit, int kc, F && f)
-{
-	auto by_kc = [&](auto t, auto u) {
-		switch (kc)
-		{
-		case 8: return f(t, u, std::integral_constant<int, 8>());
-		case 4: return f(t, u, std::integral_constant<int, 4>());
-		case 2: return f(t, u, std::integral_constant<int, 2>());
-		default: return f(t, u, std::integral_constant<int, 1>());
-		}
-	};
-	if (f32)
-		return unit ? by_kc(float(), std::true_type()) : by_kc(float(), std::false_type());
-	return unit ? by_kc(double(), std::true_type()) : by_kc(double(), std::false_type());
 }
 
 int

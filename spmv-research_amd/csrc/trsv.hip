@@ -421,7 +421,8 @@ trsv_free(spmv_mi355x_trsv * H)
 		(void) hipFree(H->d_bk);
 	if (H->d_xk)
 		(void) hipFree(H->d_xk);
-	for (void * p : {(void *) H->upd_slot_src, (void *) H->upd_diag_src, (void *) H->upd_status, (void *) H->upd_values})
+	for (void * p : {(void *) H->upd_slot_src, (void *) H->upd_diag_src, (void *) H->upd_status, (void *) H->upd_values,
+			(void *) H->swp_slice_pos, H->swp_keep, H->swp_buf})
 		if (p)
 			(void) hipFree(p);
 	if (H->upd_done)
@@ -516,6 +517,7 @@ trsv_create(const char * what, bool blocked, spmv_mi355x_trsv ** out, int uplo, 
 	H->device = device;
 	H->n = n;
 	H->levels = blocked ? an.max_block_levels : an.levels;
+	H->levels_total = an.levels;
 	H->max_level_rows = an.max_level_rows;
 	H->chain_rows = an.chain_rows;
 	H->plan = an.plan;
@@ -532,6 +534,9 @@ trsv_create(const char * what, bool blocked, spmv_mi355x_trsv ** out, int uplo, 
 	*out = H;
 	return 0;
 }
+
+// Jacobi sweeps (below): what the solve entries run in the place of the exact plan after trsv_set_sweeps
+static int trsv_sweeps_run(spmv_mi355x_trsv * T, int sweeps, int k, const void * b, long ldb, void * x, long ldx, hipStream_t st);
 
 }  // namespace spmv
 
@@ -630,6 +635,8 @@ spmv_mi355x_trsv_solve_device_async(spmv_mi355x_trsv * T, const void * b_dev, vo
 	}
 	if (T->block_rows ? T->n == 0 : T->plan.empty())
 		return 0;
+	if (T->sweeps > 0)        // trsv_set_sweeps: the Jacobi-sweep approximation in the place of the exact plan
+		return trsv_sweeps_run(T, T->sweeps, 1, b_dev, 1, x_dev, 1, (hipStream_t) hip_stream);
 	int cur = -1;
 	HIP_TRY(hipGetDevice(&cur));
 	if (cur != T->device)
@@ -781,6 +788,8 @@ spmv_mi355x_trsv_solve_multi_device_async(spmv_mi355x_trsv * T, int k, const voi
 		return 1;
 	if (T->n == 0)
 		return 0;
+	if (T->sweeps > 0)
+		return trsv_sweeps_run(T, T->sweeps, k, b_dev, ldb, x_dev, ldx, (hipStream_t) hip_stream);
 	// One contiguous column is a vector: the single solve with its kernels, so k = 1 costs what the single call costs. The KC = 1
 	// kernels serve a column of a wider block (ld > 1), such as the last one of k = 9; profiles/r28_trsv_multi.txt has their cost.
 	if (k == 1 && ldb == 1 && ldx == 1)
@@ -807,13 +816,15 @@ spmv_mi355x_trsv_solve_multi_device_async(spmv_mi355x_trsv * T, int k, const voi
 	return 0;
 }
 
-int
-spmv_mi355x_trsv_solve_multi(spmv_mi355x_trsv * T, int k, const void * B_host, void * X_host)
+}  // extern "C"
+
+namespace spmv {
+
+// The blocking host form of a k-column solve, arguments checked, n > 0: the two device blocks (ld = k), the copies, and between them
+// the solve under the handle's setting (sweeps = 0) or `sweeps` Jacobi sweeps whatever the setting is.
+static int
+trsv_solve_multi_staged(spmv_mi355x_trsv * T, int sweeps, int k, const void * B_host, void * X_host)
 {
-	if (!trsv_multi_arguments_ok("trsv_solve_multi", T, k, B_host, k, X_host, k))
-		return 1;
-	if (T->n == 0)
-		return 0;
 	HIP_TRY(hipSetDevice(T->device));
 	if (k > T->block_k)
 	{
@@ -833,11 +844,26 @@ spmv_mi355x_trsv_solve_multi(spmv_mi355x_trsv * T, int k, const void * B_host, v
 	}
 	const size_t bytes = (size_t) T->n * (size_t) k * (T->f32 ? 4 : 8);
 	HIP_TRY(hipMemcpyAsync(T->d_bk, B_host, bytes, hipMemcpyHostToDevice, nullptr));
-	if (spmv_mi355x_trsv_solve_multi_device_async(T, k, T->d_bk, k, T->d_xk, k, nullptr))
+	if (sweeps > 0 ? trsv_sweeps_run(T, sweeps, k, T->d_bk, k, T->d_xk, k, nullptr)
+	               : spmv_mi355x_trsv_solve_multi_device_async(T, k, T->d_bk, k, T->d_xk, k, nullptr))
 		return 1;
 	HIP_TRY(hipMemcpyAsync(X_host, T->d_xk, bytes, hipMemcpyDeviceToHost, nullptr));
 	HIP_TRY(hipStreamSynchronize(nullptr));
 	return 0;
+}
+
+}  // namespace spmv
+
+extern "C" {
+
+int
+spmv_mi355x_trsv_solve_multi(spmv_mi355x_trsv * T, int k, const void * B_host, void * X_host)
+{
+	if (!trsv_multi_arguments_ok("trsv_solve_multi", T, k, B_host, k, X_host, k))
+		return 1;
+	if (T->n == 0)
+		return 0;
+	return trsv_solve_multi_staged(T, 0, k, B_host, X_host);
 }
 
 int
@@ -897,6 +923,206 @@ spmv_mi355x_time_trsv_multi_device(spmv_mi355x_trsv * T, int k, const void * b_d
 	(void) hipEventDestroy(e0);
 	(void) hipEventDestroy(e1);
 	*ms_out = iters > 0 ? (double) ms / iters : 0;
+	return 0;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ Jacobi sweeps
+
+namespace spmv {
+
+// min(sweeps, levels): from `levels` sweeps on no bit changes, so more are never run. 0 at n = 0.
+static long
+trsv_sweeps_effective(const spmv_mi355x_trsv * T, long sweeps)
+{
+	return std::min<long>(sweeps, T->levels);
+}
+
+static bool
+trsv_sweeps_in_range(const char * what, int sweeps, int lowest)
+{
+	if (sweeps >= lowest && sweeps <= TRSV_SWEEPS_MAX)
+		return true;
+	set_error("%s: sweeps = %d: must be in %d .. %d", what, sweeps, lowest, TRSV_SWEEPS_MAX);
+	return false;
+}
+
+// The slice -> position map (at the first sweep solve) and the scratch of a chunk of kc columns (at the first solve of more than
+// one sweep, regrown for a wider chunk): two n x kc blocks with ld = kc, `keep` for the b of an in-place solve and `buf` for the
+// sweeps that do not write x.
+static int
+trsv_sweeps_prepare(spmv_mi355x_trsv * T, int kc, bool scratch, hipStream_t st)
+{
+	if (!T->swp_slice_pos)
+	{
+		const size_t bytes = (size_t) (T->slices + 1) * sizeof(int);
+		void * p = nullptr;
+		if (dev_alloc_bytes(&p, bytes))
+			return 1;
+		if (launch_trsv_sweep_map(T->arr, T->levels_total, T->slices, T->n, (int *) p, st))
+		{
+			(void) hipFree(p);
+			return 1;
+		}
+		// once per handle: a later solve may come on another stream
+		const hipError_t built = hipStreamSynchronize(st);
+		if (built != hipSuccess)
+		{
+			(void) hipFree(p);
+			set_error("trsv_solve_sweeps: the slice map could not be built: %s", hipGetErrorString(built));
+			return 1;
+		}
+		T->swp_slice_pos = (int *) p;
+		T->swp_bytes += (double) bytes;
+	}
+	if (scratch && kc > T->swp_k)
+	{
+		const size_t esz = T->f32 ? 4 : 8;
+		// the blocks of an earlier, narrower chunk may still be read by a solve in flight
+		HIP_TRY(hipDeviceSynchronize());
+		for (void ** p : {&T->swp_keep, &T->swp_buf})
+		{
+			if (*p)
+				(void) hipFree(*p);
+			*p = nullptr;
+		}
+		T->swp_bytes -= 2.0 * (double) T->n * T->swp_k * esz;
+		T->swp_k = 0;
+		const size_t grown = (size_t) T->n * (size_t) kc * esz;
+		if (dev_alloc_bytes(&T->swp_keep, grown) || dev_alloc_bytes(&T->swp_buf, grown))
+			return 1;
+		T->swp_k = kc;
+		T->swp_bytes += 2.0 * (double) grown;
+	}
+	return 0;
+}
+
+// The sweep solve of k columns, arguments checked, n > 0. THE BUFFERS: sweep m of S writes x when S - m is even and buf otherwise,
+// and reads what sweep m - 1 wrote, so no sweep reads the block it writes and the last one writes x; x doubles as the second
+// ping-pong buffer, and only the k columns of x are ever written in the caller's memory. b is read by every sweep: in place
+// (b == x) the first sweep copies it to keep in the pass that reads it, and the later sweeps read keep.
+static int
+trsv_sweeps_run(spmv_mi355x_trsv * T, int sweeps, int k, const void * b, long ldb, void * x, long ldx, hipStream_t st)
+{
+	int cur = -1;
+	HIP_TRY(hipGetDevice(&cur));
+	if (cur != T->device)
+		HIP_TRY(hipSetDevice(T->device));
+	const long S = trsv_sweeps_effective(T, sweeps);
+	const std::vector<Chunk> chunks = column_chunks(k);
+	if (trsv_sweeps_prepare(T, chunks[0].kc, S > 1, st))
+		return 1;
+	const bool unit = T->diag == SPMV_MI355X_DIAG_UNIT, in_place = b == x;
+	const size_t esz = T->f32 ? 4 : 8;
+	for (const Chunk & ch : chunks)
+	{
+		const void * bc = (const char *) b + (size_t) ch.c0 * esz;
+		void * xc = (char *) x + (size_t) ch.c0 * esz;
+		TrsvSweep s = {};
+		s.kc = ch.kc;
+		for (long m = 1; m <= S; m++)
+		{
+			const bool to_x = (S - m) % 2 == 0;
+			s.first = m == 1;
+			s.src = s.dst;
+			s.lds = s.ldd;
+			s.dst = to_x ? xc : T->swp_buf;
+			s.ldd = to_x ? ldx : ch.kc;
+			s.keep = s.first && in_place && S > 1 ? T->swp_keep : nullptr;
+			s.b = !s.first && in_place ? T->swp_keep : bc;
+			s.ldb = !s.first && in_place ? ch.kc : ldb;
+			if (launch_trsv_sweep(T->f32, unit, T->arr, T->swp_slice_pos, T->slices, T->block_rows, s, st))
+				return 1;
+		}
+	}
+	return 0;
+}
+
+}  // namespace spmv
+
+extern "C" {
+
+int
+spmv_mi355x_trsv_solve_sweeps_multi_device_async(spmv_mi355x_trsv * T, int sweeps, int k, const void * b_dev, long ldb, void * x_dev,
+		long ldx, void * hip_stream)
+{
+	if (!T)
+	{
+		set_error("trsv_solve_sweeps: NULL argument ( T )");
+		return 1;
+	}
+	if (!trsv_sweeps_in_range("trsv_solve_sweeps", sweeps, 1) || !trsv_multi_arguments_ok("trsv_solve_sweeps", T, k, b_dev, ldb, x_dev, ldx))
+		return 1;
+	if (T->n == 0)
+		return 0;
+	return trsv_sweeps_run(T, sweeps, k, b_dev, ldb, x_dev, ldx, (hipStream_t) hip_stream);
+}
+
+int
+spmv_mi355x_trsv_solve_sweeps_device_async(spmv_mi355x_trsv * T, int sweeps, const void * b_dev, void * x_dev, void * hip_stream)
+{
+	return spmv_mi355x_trsv_solve_sweeps_multi_device_async(T, sweeps, 1, b_dev, 1, x_dev, 1, hip_stream);
+}
+
+int
+spmv_mi355x_trsv_solve_sweeps_multi(spmv_mi355x_trsv * T, int sweeps, int k, const void * B_host, void * X_host)
+{
+	if (!T)
+	{
+		set_error("trsv_solve_sweeps: NULL argument ( T )");
+		return 1;
+	}
+	if (!trsv_sweeps_in_range("trsv_solve_sweeps", sweeps, 1) || !trsv_multi_arguments_ok("trsv_solve_sweeps", T, k, B_host, k, X_host, k))
+		return 1;
+	if (T->n == 0)
+		return 0;
+	return trsv_solve_multi_staged(T, sweeps, k, B_host, X_host);       // the staging of trsv_solve_multi; the setting is not touched
+}
+
+int
+spmv_mi355x_trsv_solve_sweeps(spmv_mi355x_trsv * T, int sweeps, const void * b_host, void * x_host)
+{
+	return spmv_mi355x_trsv_solve_sweeps_multi(T, sweeps, 1, b_host, x_host);
+}
+
+int
+spmv_mi355x_trsv_set_sweeps(spmv_mi355x_trsv * T, int sweeps)
+{
+	if (!T)
+	{
+		set_error("trsv_set_sweeps: NULL argument ( T )");
+		return 1;
+	}
+	if (!trsv_sweeps_in_range("trsv_set_sweeps", sweeps, 0))
+		return 1;
+	T->sweeps = sweeps;
+	return 0;
+}
+
+int
+spmv_mi355x_trsv_sweeps_info(const spmv_mi355x_trsv * T, int k, int * sweeps_out, long * effective_out, long * launches_out,
+		double * bytes_out)
+{
+	if (!T)
+	{
+		set_error("trsv_sweeps_info: NULL argument ( T )");
+		return 1;
+	}
+	if (k < 1)
+	{
+		set_error("trsv_sweeps_info: k = %d: at least one column is needed", k);
+		return 1;
+	}
+	const long S = trsv_sweeps_effective(T, T->sweeps);
+	if (sweeps_out)
+		*sweeps_out = T->sweeps;
+	if (effective_out)
+		*effective_out = S;
+	if (launches_out)
+		*launches_out = S * (long) column_chunks(k).size();
+	if (bytes_out)
+		*bytes_out = T->swp_bytes;
 	return 0;
 }
 

@@ -88,6 +88,31 @@ int launch_trsv_update_check(bool f32, const int * diag_src, const int * perm, c
 int launch_trsv_update_write(bool f32, const int * slot_src, const int * diag_src, const double * values, void * val, void * diag,
 		const unsigned * status, long slots, long n, hipStream_t st);
 
+// JACOBI SWEEPS (kernels_trsv_sweeps.hip): T^-1 b approximated by a fixed number of sweeps x <- D^-1 (b - N x), T = D + N, over the
+// same arrays. slice_pos (slices + 1 ints, slice_pos[slices] = n) is the first position of every slice; launch_trsv_sweep_map derives
+// it on the device from level_ptr / level_slice (`levels` = the number of entries of those two arrays less one).
+constexpr int TRSV_SWEEP_BLOCK = 256;             // threads per workgroup of the sweep kernel: four slices
+constexpr int TRSV_SWEEPS_MAX = 1 << 20;
+
+// One sweep over kc in {8, 4, 2, 1} columns (one launch). Row i of b is at b + i * ldb, of src at src + i * lds, of dst at
+// dst + i * ldd, all three already at the chunk's first column. first: x = b / d (b under UNIT), neither src, val nor col is read,
+// and when keep is not NULL row i of b is also copied to keep + i * kc (b may then be dst: the in-place solve saves its b here).
+// Later sweeps: no lane writes what any lane of the launch gathers, so src must be neither dst nor b's alias of dst.
+struct TrsvSweep {
+	const void * b;
+	const void * src;
+	void * dst;
+	void * keep;
+	long ldb, lds, ldd;
+	int kc;
+	bool first;
+};
+
+int launch_trsv_sweep_map(const TrsvArrays & a, long levels, long slices, long n, int * slice_pos, hipStream_t st);
+// block_rows = 0 for a global handle; else a stored column is block-local and the kernel adds the block's first row
+int launch_trsv_sweep(bool f32, bool unit, const TrsvArrays & a, const int * slice_pos, long slices, long block_rows,
+		const TrsvSweep & s, hipStream_t st);
+
 // the widest chunk of a blocked handle: the largest KC in {8, 4, 2, 1} whose part of X fits in LDS
 inline int
 trsv_blocked_kmax(long block_rows, long n, bool f32)
@@ -130,6 +155,13 @@ struct spmv_mi355x_trsv {
 	long upd_bad_row = -1;                // what the last result found: the refused row and its diagonal as given (-1: none)
 	double upd_bad_value = 0;
 	double upd_bytes = 0;
+	// Jacobi sweeps (trsv.hip): nothing below is allocated before the first sweep solve, none of it counts in mem_footprint
+	long levels_total = 0;                // entries of level_ptr less one: `levels` of a global handle, the sum over the blocks of a blocked one
+	int sweeps = 0;                       // trsv_set_sweeps: 0 = the solve entries run the exact plan
+	int * swp_slice_pos = nullptr;        // device: slices + 1
+	void * swp_keep = nullptr, * swp_buf = nullptr;       // device: n x swp_k values each, regrown for a wider chunk
+	int swp_k = 0;
+	double swp_bytes = 0;
 };
 
 namespace spmv {

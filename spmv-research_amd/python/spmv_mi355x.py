@@ -88,6 +88,8 @@ SYMBOLS = [
     "spmv_mi355x_trsv_update_values_state", "spmv_mi355x_trsv_update_values_device_async", "spmv_mi355x_trsv_update_values_result",
     "spmv_mi355x_trsv_update_values_device", "spmv_mi355x_trsv_update_values", "spmv_mi355x_trsv_stored_values",
     "spmv_mi355x_trsv_update_values_staged",
+    "spmv_mi355x_trsv_solve_sweeps_device_async", "spmv_mi355x_trsv_solve_sweeps", "spmv_mi355x_trsv_solve_sweeps_multi_device_async",
+    "spmv_mi355x_trsv_solve_sweeps_multi", "spmv_mi355x_trsv_set_sweeps", "spmv_mi355x_trsv_sweeps_info",
 ]
 
 _lib = None
@@ -166,6 +168,20 @@ def lib():
         L.spmv_mi355x_trsv_solve_multi_device_async.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_void_p]
         L.spmv_mi355x_trsv_solve_multi.restype = C.c_int
         L.spmv_mi355x_trsv_solve_multi.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.spmv_mi355x_trsv_solve_sweeps_device_async.restype = C.c_int
+        L.spmv_mi355x_trsv_solve_sweeps_device_async.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.spmv_mi355x_trsv_solve_sweeps.restype = C.c_int
+        L.spmv_mi355x_trsv_solve_sweeps.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.spmv_mi355x_trsv_solve_sweeps_multi_device_async.restype = C.c_int
+        L.spmv_mi355x_trsv_solve_sweeps_multi_device_async.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_void_p,
+                                                                       C.c_long, C.c_void_p]
+        L.spmv_mi355x_trsv_solve_sweeps_multi.restype = C.c_int
+        L.spmv_mi355x_trsv_solve_sweeps_multi.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.spmv_mi355x_trsv_set_sweeps.restype = C.c_int
+        L.spmv_mi355x_trsv_set_sweeps.argtypes = [C.c_void_p, C.c_int]
+        L.spmv_mi355x_trsv_sweeps_info.restype = C.c_int
+        L.spmv_mi355x_trsv_sweeps_info.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_long), C.POINTER(C.c_long),
+                                                   C.POINTER(C.c_double)]
         L.spmv_mi355x_trsv_solve_multi_plan.restype = C.c_int
         L.spmv_mi355x_trsv_solve_multi_plan.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_int)]
         L.spmv_mi355x_time_trsv_multi_device.restype = C.c_int
@@ -399,7 +415,7 @@ class TriangularSolve:
     rows and solves what is left in one launch (spmv_mi355x_trsv_create_blocked)."""
 
     def __init__(self, row_ptr, col_idx, values, n, uplo="lower", diag="stored", dtype=np.float64, chain_rows=0, device=-1,
-                 block_rows=None):
+                 block_rows=None, sweeps=0):
         if block_rows is not None and chain_rows != 0:
             raise ValueError("chain_rows belongs to the global plan: it cannot be combined with block_rows")
         row_ptr = np.ascontiguousarray(row_ptr, np.int32)
@@ -418,6 +434,60 @@ class TriangularSolve:
                                                          F64 if self.dtype == np.float64 else F32, C.c_long(n), _p(row_ptr),
                                                          _p(col_idx), _p(values), C.c_long(block_rows), C.c_int(device)))
         self.mem_footprint = lib().spmv_mi355x_trsv_mem_footprint(self.h)
+        if sweeps:
+            self.set_sweeps(sweeps)
+
+    def set_sweeps(self, sweeps):
+        """sweeps > 0: solve, solve_device, solve_multi*, time_device and time_multi_device of this handle, and with them every
+        solver that is given it in a precond triple, run that many Jacobi sweeps in the place of the exact plan; 0 restores the
+        exact plan (spmv_mi355x_trsv_set_sweeps). The two handles of an SGS / IC(0) triple need the SAME count under CG."""
+        _check(lib().spmv_mi355x_trsv_set_sweeps(self.h, int(sweeps)))
+
+    @property
+    def sweeps(self):
+        """the setting of set_sweeps (0 = exact)"""
+        return self.sweeps_info()["sweeps"]
+
+    def sweeps_info(self, k=1):
+        """dict(sweeps, effective, launches, bytes) of spmv_mi355x_trsv_sweeps_info for k columns: the setting, min(setting, levels),
+        the launches of one solve under the setting and the map and scratch bytes allocated so far (host only)"""
+        setting, effective, launches, nbytes = C.c_int(), C.c_long(), C.c_long(), C.c_double()
+        _check(lib().spmv_mi355x_trsv_sweeps_info(self.h, int(k), C.byref(setting), C.byref(effective), C.byref(launches),
+                                                  C.byref(nbytes)))
+        return dict(sweeps=setting.value, effective=effective.value, launches=launches.value, bytes=nbytes.value)
+
+    def solve_sweeps(self, b, sweeps):
+        """x(sweeps) of the Jacobi sweeps x(1) = D^-1 b, x(m + 1) = D^-1 (b - N x(m)) for a host vector b, whatever set_sweeps says;
+        from `levels` sweeps on the bits of solve(b) (spmv_mi355x_trsv_solve_sweeps; blocking)"""
+        b = np.ascontiguousarray(b, self.dtype)
+        if b.shape != (self.n,):
+            raise ValueError(f"b must have {self.n} values, got {b.shape}")
+        x = np.full(max(self.n, 1), np.nan, self.dtype)
+        _check(lib().spmv_mi355x_trsv_solve_sweeps(self.h, int(sweeps), _p(b), _p(x)))
+        return x[:self.n]
+
+    def solve_sweeps_device(self, b_ptr, x_ptr, sweeps, stream=None):
+        """The same on device pointers (b_ptr == x_ptr: in place), enqueued on `stream`; x holds intermediate sweeps until the solve
+        has finished (spmv_mi355x_trsv_solve_sweeps_device_async)"""
+        _check(lib().spmv_mi355x_trsv_solve_sweeps_device_async(self.h, int(sweeps), C.c_void_p(b_ptr), C.c_void_p(x_ptr),
+                                                                C.c_void_p(stream or 0)))
+
+    def solve_sweeps_multi(self, B, sweeps):
+        """The sweeps on a host block B of shape (n, k), column j bit-identical to solve_sweeps(B[:, j], sweeps)
+        (spmv_mi355x_trsv_solve_sweeps_multi; blocking)"""
+        B = np.ascontiguousarray(B, self.dtype)
+        if B.ndim != 2 or B.shape[0] != self.n or B.shape[1] < 1:
+            raise ValueError(f"B must have shape ({self.n}, k) with k >= 1, got {B.shape}")
+        k = B.shape[1]
+        X = np.full((max(self.n, 1), k), np.nan, self.dtype)
+        _check(lib().spmv_mi355x_trsv_solve_sweeps_multi(self.h, int(sweeps), k, _p(B), _p(X)))
+        return X[:self.n]
+
+    def solve_sweeps_multi_device(self, k, b_ptr, ldb, x_ptr, ldx, sweeps, stream=None):
+        """The same on device pointers of row-major blocks (row i at ptr + i * ld values; b_ptr == x_ptr with ldb == ldx: in place),
+        enqueued on `stream` (spmv_mi355x_trsv_solve_sweeps_multi_device_async)"""
+        _check(lib().spmv_mi355x_trsv_solve_sweeps_multi_device_async(self.h, int(sweeps), k, C.c_void_p(b_ptr), ldb, C.c_void_p(x_ptr),
+                                                                      ldx, C.c_void_p(stream or 0)))
 
     @property
     def info(self):

@@ -28,6 +28,14 @@ times, in one process and in --windows alternating windows after a warm-up, a re
 and, apart from the factorization, precond() alone against update_precond() alone. Medians with min .. max, the bytes the two
 updates move by the layout's own count, and whether the refreshed handles have the rebuilt handles' bytes. No ratio is asserted.
     python tools/ilu0_bench.py --refresh --runs stencil160,grid2d2000 --block-rows 4096 --windows 7
+With --sweeps 2,3,4,8 nothing above is timed either. On every symmetric positive definite workload the tool solves A x = b with
+spmv_mi355x_pcg_tri to --tol under the GLOBAL ILU(0) and the GLOBAL SGS of A with their triangular solves replaced by that many Jacobi
+sweeps (spmv_mi355x_trsv_set_sweeps, the same count on both handles), and beside them under the exact global forms, the blocked forms
+at every --block-rows value and no preconditioner. One pair of global handles per preconditioner serves every sweep count. All legs run
+in one process in --windows alternating windows after a warm-up window: per leg the iterations, the stop code, the median seconds of
+the whole call with min .. max, the launches of the two triangular solves per iteration, and the ratio to the fastest leg. No ratio is
+asserted; a sweep count that loses is reported as it comes out.
+    python tools/ilu0_bench.py --sweeps 2,3,4,8 --runs stencil160,grid2d2000 --block-rows 4096 --windows 5
 One JSON line per variant."""
 import argparse
 import json
@@ -163,9 +171,50 @@ def close(M):
             h.close()
 
 
+def sweep_legs(E, workload, rp, ci, va, n, args):
+    """--sweeps: whole pcg_tri solves under swept, exact and blocked ILU(0) / SGS and under nothing, in alternating windows"""
+    A = E.Matrix(rp, ci, va, n, n, "sell_c_sigma", np.float64)
+    b = np.random.default_rng(7).uniform(-1, 1, n)
+    triples = {"ilu0 global": E.ilu0_precond(rp, ci, va, n), "sgs global": E.sgs_precond(rp, ci, va, n)}
+    for B in args.block_rows:
+        triples[f"ilu0 B={B}"] = E.ilu0_precond(rp, ci, va, n, block_rows=B)
+        triples[f"sgs B={B}"] = E.sgs_precond(rp, ci, va, n, block_rows=B)
+    legs = [("none", None, 0)]
+    for name in triples:
+        legs.append((name, name, 0))
+        if name.endswith("global"):
+            legs += [(f"{name} sweeps={s}", name, s) for s in args.sweeps]
+    times, last = {leg[0]: [] for leg in legs}, {}
+    for w in range(args.windows + 1):                         # window 0 warms every leg up (code objects, scratch) and is dropped
+        for leg, name, s in legs:
+            M = triples.get(name)
+            for T in (M[0], M[2]) if M else ():
+                T.set_sweeps(s)
+            r = A.pcg_tri(b, precond=M, tol=args.tol, max_iterations=args.max_iterations, history=False)
+            last[leg] = (r, sum(T.sweeps_info()["launches"] if s else T.info["launches"] for T in (M[0], M[2])) if M else 0)
+            if w:
+                times[leg].append(r["seconds"])
+        print(f"# {workload}: window {w} done", flush=True)
+    best = min(float(np.median(t)) for t in times.values())
+    for leg, name, s in legs:
+        r, launches = last[leg]
+        t = spread(times[leg])
+        print(json.dumps(dict(workload=workload, n=int(n), nnz=int(len(ci)), variant=leg, sweeps=s, tol=args.tol, iterations=int(r["iterations"]),
+                              stop=int(r["stop"]), rnorm_over_b=float(r["rnorm"] / r["rnorm0"]), seconds=t, trsv_launches_per_iteration=launches,
+                              over_fastest=round(t["median"] / best, 2), windows=args.windows)), flush=True)
+    for M in triples.values():
+        close(M)
+    A.close()
+
+
 def run(E, torch, ic, workload, args):
     rp, ci, va, n, kind = load(workload, args)
     rp = np.asarray(rp, np.int32)
+    if args.sweeps:
+        if kind != "spd":
+            raise SystemExit(f"--sweeps compares whole CG solves: {workload} is not one of the SPD workloads")
+        sweep_legs(E, workload, rp, np.asarray(ci, np.int32), np.asarray(va, np.float64), n, args)
+        return
     if args.refresh:
         for B in [None] + list(args.block_rows):
             print(json.dumps(refresh_legs(E, torch, workload, rp, np.asarray(ci, np.int32), np.asarray(va, np.float64), n, B, args)),
@@ -227,8 +276,13 @@ def main():
     ap.add_argument("--refresh", action="store_true",
                     help="time factor + precond() against factor_device + update_precond on new values of the same pattern")
     ap.add_argument("--no-reference", action="store_true", help="skip the sequential loop on the host")
+    ap.add_argument("--sweeps", default="", help="Jacobi-sweep counts: whole CG solves under swept global ILU(0) / SGS beside the exact, "
+                    "the blocked and the unpreconditioned ones, e.g. 2,3,4,8")
     args = ap.parse_args()
     args.block_rows = [int(v) for v in args.block_rows.split(",") if v != ""]
+    args.sweeps = [int(v) for v in args.sweeps.split(",") if v != ""]
+    if any(v < 1 for v in args.sweeps):
+        ap.error("--sweeps: sweep counts are at least 1")
     os.environ.setdefault("OMP_NUM_THREADS", "16")
     import torch
     if not torch.cuda.is_available():

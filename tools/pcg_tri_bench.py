@@ -14,7 +14,12 @@ times in one process, alternating window by window (window 0 warms every leg up 
 The medians over the windows are reported with their min .. max spreads. No threshold is set and no speed is promised: the table is
 what tells a user whether block SGS beats Jacobi in seconds and not only in iterations.
 
+With --sweeps 2,3,4,8 the global SGS also runs with its two triangular solves replaced by that many Jacobi sweeps
+(spmv_mi355x_trsv_set_sweeps, the same count on both handles; one pair of global handles serves every count and the exact leg), as
+further variants in the same windows. grid2d<N> (the 5-point operator of tools/amg_bench.py, shift 0.001) is a workload too.
+
     python tools/pcg_tri_bench.py                                    # stencil160 fp64, B = 1024, 4096, 16384
+    python tools/pcg_tri_bench.py --runs stencil160:f64,grid2d2000:f64 --block-rows 0,4096 --sweeps 2,3,4,8
     python tools/pcg_tri_bench.py --runs stencil96:f32 --block-rows 0,4096
 One JSON line per variant, and a table at the end."""
 import argparse
@@ -31,10 +36,14 @@ for p in (ROOT, os.path.join(ROOT, "spmv-research_amd", "python"), os.path.join(
 
 
 def run(E, torch, workload, dts, args):
-    if not workload.startswith("stencil"):
-        raise SystemExit(f"pcg_tri_bench.py runs on stencil<N>, not on {workload}")
-    from solver_bench import stencil27
-    rp, ci, va, n = stencil27(int(workload[len("stencil"):]), args.stencil_diag)
+    if workload.startswith("grid2d"):
+        from amg_bench import grid2d
+        rp, ci, va, n = grid2d(int(workload[len("grid2d"):]), 0.001)
+    elif workload.startswith("stencil"):
+        from solver_bench import stencil27
+        rp, ci, va, n = stencil27(int(workload[len("stencil"):]), args.stencil_diag)
+    else:
+        raise SystemExit(f"pcg_tri_bench.py runs on stencil<N> and grid2d<N>, not on {workload}")
     rp = np.asarray(rp, np.int32)
     np_dtype = np.float32 if dts == "f32" else np.float64
     tdt = torch.float32 if dts == "f32" else torch.float64
@@ -56,11 +65,21 @@ def run(E, torch, workload, dts, args):
                          dict(dropped_share=round(dropped, 4), trsv_launches=L.info["launches"] + U.info["launches"],
                               block_levels=max(L.info["levels"], U.info["levels"]))))
         print(f"# built {variants[-1][0]}: {variants[-1][2]}", flush=True)
+    if args.sweeps:
+        # the swept variants share ONE global pair (that of --block-rows 0 when it is there); `sweeps` is set before a variant's legs
+        pair = next((M for name, M, _ in variants if name == "sgs global"), None)
+        if pair is None:
+            pair = E.sgs_precond(rp, ci, va, n, np_dtype)
+            handles += [pair[0], pair[2]]
+        for s in args.sweeps:
+            variants.append((f"sgs sweeps={s}", pair, dict(sweeps=s, trsv_launches=2 * min(s, pair[0].info["levels"]))))
     solve = lambda M, tol, steps: MA.pcg_tri(b, precond=M, tol=tol, max_iterations=steps, history=False)
     legs = {name: {k: [] for k in ("spmv", "seconds", "iter_ms", "ratio", "trsv_lower", "trsv_upper")} for name, _, _ in variants}
     last = {}
     for w in range(args.windows + 1):                         # window 0 warms every leg up and is dropped
-        for name, M, _ in variants:
+        for name, M, extra in variants:
+            for T in (M[0], M[2]) if M is not None and M[0] is not None else ():
+                T.set_sweeps(extra.get("sweeps", 0))
             t_a = MA.time_device(xa.data_ptr(), ya.data_ptr(), args.reps, stream.cuda_stream)
             torch.cuda.synchronize()
             t_l = t_u = float("nan")
@@ -103,6 +122,7 @@ def main():
     ap.add_argument("--runs", default="stencil160:f64", help="stencil<N>:f64|f32,...")
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--block-rows", default="1024,4096,16384", help="block sizes of the blocked SGS, 0 = global handles")
+    ap.add_argument("--sweeps", default="", help="Jacobi-sweep counts of the global SGS to run beside the exact forms, e.g. 2,3,4,8")
     ap.add_argument("--tol", type=float, default=1e-8, help="the tolerance of the solve leg")
     ap.add_argument("--max-iterations", type=int, default=3000, help="the cap of the solve leg")
     ap.add_argument("--steps", type=int, default=200, help="iterations of the tol = 0 leg")
@@ -112,6 +132,9 @@ def main():
     if args.windows < 5:
         ap.error("--windows: at least 5")
     args.block_rows = [int(v) for v in args.block_rows.split(",") if v != ""]
+    args.sweeps = [int(v) for v in args.sweeps.split(",") if v != ""]
+    if any(v < 1 for v in args.sweeps):
+        ap.error("--sweeps: sweep counts are at least 1")
     os.environ.setdefault("OMP_NUM_THREADS", "16")
     import torch
     if not torch.cuda.is_available():

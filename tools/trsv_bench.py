@@ -23,6 +23,12 @@ the plan, ms per solve, and ms per column over the single solve's ms (1 / k when
     python tools/trsv_bench.py --runs nlpkkt240:f64 --scale 0.25
     python tools/trsv_bench.py --runs cant:f64,cant:f32,stencil160:f64,nlpkkt240:f64 --chain-rows 256 --block-rows 1024,2048,4096,8192,16384
     python tools/trsv_bench.py --runs stencil160:f64 --chain-rows 256 --block-rows 1024,2048,4096 --rhs 1,2,4,8
+With --sweeps the Jacobi-sweep solve (spmv_mi355x_trsv_set_sweeps) of the first --chain-rows handle is timed for each sweep count in
+the same windows, through the same time_device call: per count the effective sweeps and launches, ms per solve, ms per sweep, and the
+ratios to the exact solve of that handle and to the floor SpMV. With --rhs as well, each k-column sweep solve is timed too and
+reported per column. The sweep solve approximates the system the exact solve solves: what that costs a solver is
+tools/pcg_tri_bench.py's question.
+    python tools/trsv_bench.py --runs stencil160:f64 --chain-rows 256 --sweeps 1,2,3,4,8
 With --update nothing above is timed. Instead, per run and per variant (the global handle of the first --chain-rows value and the
 blocked handle of every --block-rows value), the tool times in one process and in alternating windows
   create:  TriangularSolve(...) on new values V2: host analysis, layout and nine uploads, which is what a handle cost before it
@@ -32,7 +38,7 @@ blocked handle of every --block-rows value), the tool times in one process and i
   host:    update_values on V2 in host memory (the upload of row_ptr[n] doubles included);
 and reports the medians with min .. max, update_values_prepare's seconds (once), the bytes an update moves by the layout's own count,
 slots * (4 + 8 + sizeof T) + n * (4 + 8 + sizeof T) under DIAG_STORED, and whether the updated handle has the fresh handle's bytes.
-grid2d<N> (the 5-point operator of tools/amg_bench.py) is a workload of this mode too. No ratio is asserted.
+grid2d<N> (the 5-point operator of tools/amg_bench.py) is a workload of every mode. No ratio is asserted.
     python tools/trsv_bench.py --update --runs stencil160:f64,grid2d2000:f64 --chain-rows 256 --block-rows 4096
 One JSON line per run and a table at the end.
 """
@@ -120,12 +126,31 @@ def run(E, torch, name, rp, ci, va, n, dts, data, args):
             for k in args.rhs:
                 T.time_multi_device(k, bk.data_ptr(), k, xk.data_ptr(), k, 1, stream)          # warm-up: code objects, the LDS grant
                 legs[(c, k)] = []
+    # --sweeps: the first handle under set_sweeps(s), through the same timing entries; the setting is back at 0 (exact) after each leg
+    swept = handles[args.chain_rows[0]]
+    sweep_reps = {}
+    for s in args.sweeps:
+        swept.set_sweeps(s)
+        swept.time_device(b.data_ptr(), out.data_ptr(), 1, stream)                                # warm-up: the map, the scratch
+        one = swept.time_device(b.data_ptr(), out.data_ptr(), 2, stream)
+        sweep_reps[s] = int(min(200, max(3, np.ceil(args.leg_ms / max(one, 1e-3)))))
+        legs[("s", s)] = []
+        for k in args.rhs:
+            swept.time_multi_device(k, bk.data_ptr(), k, xk.data_ptr(), k, 1, stream)
+            legs[("s", s, k)] = []
+        swept.set_sweeps(0)
     for w in range(args.windows + 1):                     # window 0 warms every leg up and is dropped
         t = {"spmv": M.time_device(x.data_ptr(), y.data_ptr(), args.reps, stream)}
         for c, T in handles.items():
             t[c] = T.time_device(b.data_ptr(), out.data_ptr(), reps[c], stream)
             for k in args.rhs if c in multi else ():
                 t[(c, k)] = T.time_multi_device(k, bk.data_ptr(), k, xk.data_ptr(), k, max(3, reps[c] // k), stream)
+        for s in args.sweeps:
+            swept.set_sweeps(s)
+            t[("s", s)] = swept.time_device(b.data_ptr(), out.data_ptr(), sweep_reps[s], stream)
+            for k in args.rhs:
+                t[("s", s, k)] = swept.time_multi_device(k, bk.data_ptr(), k, xk.data_ptr(), k, max(3, sweep_reps[s] // k), stream)
+            swept.set_sweeps(0)
         torch.cuda.synchronize()
         if w:
             for k, v in t.items():
@@ -147,6 +172,18 @@ def run(E, torch, name, rp, ci, va, n, dts, data, args):
                                    ms=round(float(np.median(ts)), 5), spread=[round(min(ts), 5), round(max(ts), 5)],
                                    single_ms=round(float(np.median(single)), 5), single_spread=[round(min(single), 5), round(max(single), 5)],
                                    per_column_over_single=round(float(np.median(ts)) / k / float(np.median(single)), 4)))
+    rec["sweeps"] = []
+    for s in args.sweeps:
+        swept.set_sweeps(s)
+        for k in [0] + args.rhs:                          # 0: the single solve
+            ts, info = legs[("s", s, k) if k else ("s", s)], swept.sweeps_info(max(k, 1))
+            ms = float(np.median(ts))
+            rec["sweeps"].append(dict(sweeps=s, k=k, effective=info["effective"], launches=info["launches"],
+                                      reps=max(3, sweep_reps[s] // k) if k else sweep_reps[s], ms=round(ms, 5),
+                                      spread=[round(min(ts), 5), round(max(ts), 5)], ms_per_sweep=round(ms / max(info["effective"], 1), 5),
+                                      per_column_ms=round(ms / max(k, 1), 5), per_column_over_exact=round(ms / max(k, 1) / global_ms, 4),
+                                      per_column_over_floor=round(ms / max(k, 1) / rec["spmv_ms"], 2), scratch_bytes=int(info["bytes"])))
+        swept.set_sweeps(0)
     for c, T in handles.items():
         ts = legs[c]
         if isinstance(c, tuple):
@@ -232,6 +269,7 @@ def main():
     ap.add_argument("--chain-rows", default="64,256,1024,4096", help="the thresholds to sweep, first = the one the header line reports")
     ap.add_argument("--block-rows", default="", help="block sizes of the blocked form to time beside the plans, e.g. 1024,2048,4096,8192,16384")
     ap.add_argument("--rhs", default="", help="column counts of the k-column solve to time beside the single solve, e.g. 1,2,4,8")
+    ap.add_argument("--sweeps", default="", help="Jacobi-sweep counts to time beside the exact solve of the first --chain-rows handle, e.g. 1,2,3,4,8")
     ap.add_argument("--reps", type=int, default=20, help="SpMV launches per timed floor leg")
     ap.add_argument("--leg-ms", type=float, default=40.0, help="solves per timed leg: as many as last about this long (3 .. 200)")
     ap.add_argument("--scale", type=float, default=1.0, help="shrink the workload twins")
@@ -242,6 +280,9 @@ def main():
     args.chain_rows = [int(c) for c in args.chain_rows.split(",")]
     args.block_rows = [int(c) for c in args.block_rows.split(",") if c]
     args.rhs = [int(c) for c in args.rhs.split(",") if c]
+    args.sweeps = [int(c) for c in args.sweeps.split(",") if c]
+    if any(k < 1 for k in args.sweeps):
+        ap.error("--sweeps: sweep counts are at least 1")
     if any(k < 1 for k in args.rhs):
         ap.error("--rhs: column counts are at least 1")
     os.environ.setdefault("OMP_NUM_THREADS", "16")
@@ -258,7 +299,7 @@ def main():
         if w.startswith("stencil"):
             rp, ci, va, n = stencil27(int(w[len("stencil"):]))
             data = "generated"
-        elif w.startswith("grid2d") and args.update:
+        elif w.startswith("grid2d"):
             from amg_bench import grid2d
             rp, ci, va, n = grid2d(int(w[len("grid2d"):]), 0.001)
             data = "generated"
@@ -297,6 +338,14 @@ def main():
                 print(f"{r['workload']:11s} {r['dtype']:5s} | {s['block_rows']:10d} {s['blocks']:7d} {s['max_block_levels']:7d} "
                       f"{s['max_level_rows']:7d} {100 * s['dropped_share']:7.2f}% {s['ms']:9.4f} {s['spread'][0]:9.4f} ..{s['spread'][1]:8.4f} "
                       f"{s['over_floor']:8.2f} {s['over_global']:9.4f}")
+    if args.sweeps:
+        print(f"{'workload':11s} {'dtype':5s} | {'sweeps':>6s} {'k':>6s} {'run':>4s} {'launches':>8s} {'solve ms':>9s} {'spread':>19s} "
+              f"{'ms / sweep':>10s} {'exact ms':>9s} {'column / exact':>14s} {'column / spmv':>13s}")
+        for r in rows:
+            for s in r["sweeps"]:
+                print(f"{r['workload']:11s} {r['dtype']:5s} | {s['sweeps']:6d} {s['k'] or 'single':>6} {s['effective']:4d} {s['launches']:8d} "
+                      f"{s['ms']:9.4f} {s['spread'][0]:9.4f} ..{s['spread'][1]:8.4f} {s['ms_per_sweep']:10.4f} {r['sweep'][0]['ms']:9.4f} "
+                      f"{s['per_column_over_exact']:14.4f} {s['per_column_over_floor']:13.2f}")
     if args.rhs:
         print(f"{'workload':11s} {'dtype':5s} | {'block_rows':>10s} {'k':>3s} {'passes':>6s} {'launches':>8s} {'solve ms':>9s} {'spread':>19s} "
               f"{'single ms':>9s} {'spread':>19s} {'per column / single':>19s}")

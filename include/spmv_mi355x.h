@@ -925,6 +925,90 @@ int  spmv_mi355x_ilu0_get_info(spmv_mi355x_ilu0 * F, spmv_mi355x_ilu0_info * inf
 double spmv_mi355x_ilu0_mem_footprint(const spmv_mi355x_ilu0 * F);
 int  spmv_mi355x_ilu0_destroy(spmv_mi355x_ilu0 * F);
 
+/* ---- multicolour ordering: colour, permute, SGS / ILU(0) in as many launches as colours -------------------------------------------- */
+/* An exact global triangular solve, and the ILU(0) factorization, cost one launch per LEVEL of the triangle, and the natural ordering
+ * of a grid or a stencil has hundreds to thousands of levels. Under a multicolouring every row of colour c depends only on rows of
+ * lower colours, so the matrix B = P A P^t, whose rows are sorted by colour, has as many levels as colours: a handful, whatever n is.
+ * This handle colours the graph of a square CSR pattern on the GPU, derives the permutation, forms B with an entry map, and moves
+ * vectors and value arrays between the two orderings (csrc/color.hip, csrc/kernels_color.hip, csrc/color.hpp).
+ * Everything downstream is the existing API applied to B: trsv_create, ilu0_create, the preconditioner triples of pcg_tri,
+ * pcg_trsm_multi and gmres_tri, update_values. No solver changes. The solve of A x = b becomes B (P x) = P b.
+ * THE GRAPH. The vertices are the rows; i and j (i != j) are adjacent when a_ij OR a_ji is stored (a Gauss-Seidel or ILU ordering
+ * needs both directions: the pattern of A^t comes from the device transposition of "transposed handles"). Stored zeros count;
+ * duplicates and a missing diagonal are harmless; the columns of a row need not be sorted.
+ * THE COLOURING, PINNED. key(i) = ((uint64) (h >> 1) << 31) | i with h = (uint32) (i * 0x9E3779B1u), the keys of the AMG's
+ * independent set. Rounds are synchronous (each reads one colour array and writes another): an uncoloured vertex whose key exceeds
+ * the key of every UNCOLOURED neighbour takes the smallest colour >= 0 that none of its coloured neighbours holds. A neighbour of
+ * lower key is never coloured first, so the result EQUALS first-fit greedy colouring in descending key order
+ * (tests/color_reference.c), run after run, and every vertex of colour c > 0 has a neighbour of every colour below c. The rounds
+ * needed are the longest chain of ascending keys + 1: 6 on a 5-point grid, about 20 on a 27-point stencil, m ON A CLIQUE OF m ROWS.
+ * The host reads one counter per round; 4096 rounds are refused with a message. Nothing spins and nothing is ordered between
+ * workgroups except by the launch boundary. One lane per row; the smallest free colour is searched in windows of 64 colours (a
+ * 64-bit mask), so no row is refused for its width or its colour count.
+ * THE PERMUTATION. perm[p] = the old row at new position p, sorted by (colour, old row) (a stable radix sort on the device);
+ * rank = its inverse; color_ptr[c] .. color_ptr[c + 1] are the positions of colour c (num_colors + 1 entries).
+ * THE PERMUTED MATRIX. B(p, q) = A(perm[p], perm[q]): row p of B holds the entries of row perm[p] of A with columns rank[j], in
+ * ASCENDING NEW COLUMN order, equal columns in their stored order (so a sorted A with a diagonal gives a B that ilu0_create takes).
+ * entry_map[e_B] = e_A, int32, nnz entries; values_B = values_A[entry_map] is one gather.
+ *   - create is pattern only and blocking; it deep-copies the pattern to the device. The colours, perm, rank and color_ptr are kept on
+ *     the host for the getters and perm / rank on the device for the vector kernels.
+ *   - permute_csr (host outputs, blocking; values_host may be NULL, then values_out is not written) and permute_csr_device (device
+ *     pointers the handle owns, valid until destroy) form B's pattern and the map at their first call, on the device, by two stable
+ *     transpositions of the relabelled pattern; A's own pattern is dropped then. Later calls copy.
+ *   - permute_values_device_async is the gather alone, enqueued on hip_stream (after a first call that formed B; the first call
+ *     synchronises). Its output is what spmv_mi355x_update_values_device of a handle of B, spmv_mi355x_ilu0_factor_device_async and
+ *     spmv_mi355x_trsv_update_values_device_async take: a Newton loop refreshes the whole permuted preconditioner on one stream
+ *     without the host. permute_values is its blocking host form.
+ *   - permute_vectors_device_async: direction SPMV_MI355X_COLOR_FORWARD out[p] = in[perm[p]], SPMV_MI355X_COLOR_BACKWARD out[i] =
+ *     in[rank[i]] (the inverse), for the k columns of row-major n x k blocks (row i at ptr + i * ld), one launch per chunk of 8 / 4 /
+ *     2 / 1 columns; precision 0 = fp64, 1 = fp32 (the handle has none of its own). permute_vectors is the blocking host form; what
+ *     lies between k and ld in out stays as it was.
+ *   - info->struct_size in: sizeof; out: the bytes written. symmetric = 1 when row_ptr and col_idx of A^t equal A's array for array
+ *     (then one walk per row serves; a symmetric pattern with unsorted rows or duplicates may report 0 and is walked twice, with the
+ *     same result); max_class / min_class = the most and fewest rows of one colour; the seconds of the transposition (with the
+ *     comparison), of the rounds, of the sort (with the downloads) and of forming B (0 before the first permute call).
+ *   - mem_footprint: the pattern (4 (n + 1) + 4 nnz) and perm and rank (8 n); 4 nnz more once B and the map are formed.
+ *   - rc 1 with the prefix "color_create:" / "color_info:" / "color_permute_csr:" / "color_permute_values:" /
+ *     "color_permute_vectors:", in this order, 1 to 3 on the host before any device is touched:
+ *     1. scalars: n < 0 (or beyond the int32 range); for permute_vectors direction, precision, then k < 1 or ld < k; for info an
+ *        unset struct_size;
+ *     2. NULL pointers: out, row_ptr; col_idx when row_ptr[n] > 0; the handle; the arrays of a call when n (nnz) > 0;
+ *     3. the pattern, as spmv_mi355x_trsv_create checks it and with its messages: row_ptr from 0 and monotone, columns in [0, n);
+ *        then n + nnz beyond the int32 range (the transposition's limit);
+ *     4. in == out of permute_vectors and of permute_values (neither can run in place);
+ *     5. the device: without a usable one the library's "no HIP device available" message; `device` out of range;
+ *     6. more than 4096 rounds.
+ *     n = 0 is rc 0 with nothing launched (0 colours, color_ptr = {0}); color_destroy(NULL) is rc 0; color_mem_footprint(NULL) is 0.
+ *   - NOT CHECKABLE: that device pointers hold what the call says on the handle's device; that in and out of a device call do not
+ *     overlap in part; that the values are those of the pattern given to create.
+ *   - NOT BUILT: distance-2 colouring; balancing the colour classes; fewer colours than greedy gives (greedy finds 5 on the 5-point
+ *     grid, where 2 exist); a multicolour smoother inside the AMG cycle; applying P^t M^-1 P around an unpermuted A (the caller
+ *     permutes b and x once per solve instead); the blocked and the row-partitioned forms. */
+typedef struct spmv_mi355x_color spmv_mi355x_color;   /* opaque */
+enum { SPMV_MI355X_COLOR_FORWARD = 0, SPMV_MI355X_COLOR_BACKWARD = 1 };
+typedef struct {
+	size_t struct_size;           /* in: sizeof(spmv_mi355x_color_stats); out: the bytes written */
+	long n, nnz, symmetric, num_colors, rounds, max_class, min_class;
+	double transpose_seconds, round_seconds, sort_seconds, permute_seconds;
+} spmv_mi355x_color_stats;
+int  spmv_mi355x_color_create(spmv_mi355x_color ** out, long n, const int32_t * row_ptr, const int32_t * col_idx, int device /* -1 = current */);
+int  spmv_mi355x_color_destroy(spmv_mi355x_color * C);
+int  spmv_mi355x_color_info(const spmv_mi355x_color * C, spmv_mi355x_color_stats * stats);
+int  spmv_mi355x_color_colors(const spmv_mi355x_color * C, int32_t * colors_host /* n */);
+int  spmv_mi355x_color_perm(const spmv_mi355x_color * C, int32_t * perm_host /* n, may be NULL */, int32_t * rank_host /* n, may be NULL */);
+int  spmv_mi355x_color_color_ptr(const spmv_mi355x_color * C, int32_t * color_ptr_host /* num_colors + 1 */);
+double spmv_mi355x_color_mem_footprint(const spmv_mi355x_color * C);
+int  spmv_mi355x_color_permute_csr(spmv_mi355x_color * C, const double * values_host /* nnz, may be NULL */, int32_t * row_ptr_out /* n + 1 */,
+		int32_t * col_idx_out /* nnz */, double * values_out /* nnz, with values_host */, int32_t * entry_map_out /* nnz */);   /* blocking */
+int  spmv_mi355x_color_permute_csr_device(spmv_mi355x_color * C, const int32_t ** row_ptr_dev_out, const int32_t ** col_idx_dev_out,
+		const int32_t ** entry_map_dev_out);
+int  spmv_mi355x_color_permute_values(spmv_mi355x_color * C, const double * values_host, double * values_out_host);      /* blocking */
+int  spmv_mi355x_color_permute_values_device_async(spmv_mi355x_color * C, const double * values_dev, double * values_out_dev, void * hip_stream);
+int  spmv_mi355x_color_permute_vectors(spmv_mi355x_color * C, int direction, int precision, int k, const void * in_host, long ldin,
+		void * out_host, long ldout);                                                                                 /* blocking */
+int  spmv_mi355x_color_permute_vectors_device_async(spmv_mi355x_color * C, int direction, int precision, int k, const void * in_dev, long ldin,
+		void * out_dev, long ldout, void * hip_stream);
+
 /* ---- GMRES(m) right-preconditioned by triangular solves ------------------------------------------------------------------------ */
 /* spmv_mi355x_gmres with M^-1 v = second^-1 ( scale o ( first^-1 v ) ) for "M v" (csrc/solver_gmres.hip): each of
  * the three parts may be NULL, the two solves are spmv_mi355x_trsv handles of any kind, blocked or global, and scale is a vector.

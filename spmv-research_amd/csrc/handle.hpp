@@ -150,6 +150,8 @@ void transpose_csr_host(long m, long n, long nnz, const int * rp, const int * ci
 int transpose_entry_map(bool on_device, long m, long n, long nnz, const int * rp, const int * ci, long r0, long r1, int ** d_lrp_out,
 		unsigned ** d_src_out, long * lnnz_out);
 int transpose_gather_values(const unsigned * d_src, const double * d_va, long nnz, double * d_va_t, hipStream_t st);
+// the same order for a device-resident pattern alone: the pattern of A^t and, per entry of it, its number in the CSR of A
+int transpose_pattern_device(long m, long n, long nnz, const int * d_rp, const int * d_ci, int ** d_rp_t_out, int ** d_ci_t_out, unsigned ** d_ids_out);
 int ensure_x(spmv_mi355x_matrix * A);                                    // spmv_mi355x.hip: stream + the handle's own (zeroed) x
 int tune_placement(spmv_mi355x_matrix * A);                              // placement.hip: allocates the handle's y (and re-homes its x) in the device's vector pools
 int place_vector(spmv_mi355x_matrix * A, void ** out, size_t bytes, bool is_output);   // placement.hip: a zero-filled vector A's SpMV writes / reads

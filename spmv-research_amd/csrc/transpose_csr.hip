@@ -154,6 +154,18 @@ values_gather_kernel(const unsigned * __restrict__ src, const double * __restric
 	}
 }
 
+// step 4 for the pattern alone: ci_t[e] = row[ids[e]], and the ids copied out of the sort's scratch
+__global__ __launch_bounds__(TB) void
+transpose_rows_kernel(const unsigned * __restrict__ ids, const int * __restrict__ row, long nnz, int * __restrict__ ci_t, unsigned * __restrict__ ids_out)
+{
+	for (long e = (long) blockIdx.x * TB + threadIdx.x; e < nnz; e += (long) gridDim.x * TB)
+	{
+		const unsigned id = ids[e];
+		ci_t[e] = row[id];
+		ids_out[e] = id;
+	}
+}
+
 // lrp[i] = rp_t[r0 + i] - rp_t[r0], i = 0 .. rows: the row pointer of the row block [r0, r0 + rows) of A^t, from 0
 __global__ __launch_bounds__(TB) void
 transpose_block_kernel(const int * __restrict__ rp_t, long r0, long rows, int * __restrict__ lrp)
@@ -249,6 +261,42 @@ transpose_csr_device(long m, long n, long nnz, const int * rp, const int * ci, c
 	*rp_t_out = rp_t;
 	*ci_t_out = ci_t;
 	*va_t_out = va_t;
+	return 0;
+}
+
+// The pattern alone, for a device-resident pattern (color.hip: the graph of A + A^t, and the two transpositions behind P A P^t):
+// steps 1 to 3 and the row gather of step 4. *ids_out = the sorted entry numbers, the entry map of the transposition. Outputs: device
+// allocations of n + 1, max(nnz, 1) and max(nnz, 1) words, the caller's to hipFree. 0 = done, 1 = error set.
+int
+transpose_pattern_device(long m, long n, long nnz, const int * rp, const int * ci, int ** rp_t_out, int ** ci_t_out, unsigned ** ids_out)
+{
+	*rp_t_out = nullptr;
+	*ci_t_out = nullptr;
+	*ids_out = nullptr;
+	if (transpose_sizes_bad(m, n, nnz))
+		return 1;
+	Scratch out, tmp;
+	int * rp_t, * ci_t;
+	unsigned * ids;
+	if (out.get(&rp_t, (size_t) (n + 1) * 4) || out.get(&ci_t, (size_t) nnz * 4) || out.get(&ids, (size_t) nnz * 4))
+		return 1;
+	if (nnz == 0)
+		HIP_TRY(hipMemset(rp_t, 0, (size_t) (n + 1) * 4));
+	else
+	{
+		int * row;
+		unsigned * ids_sorted;
+		if (transpose_order(m, n, nnz, rp, ci, tmp, rp_t, &row, &ids_sorted))
+			return 1;
+		hipLaunchKernelGGL(transpose_rows_kernel, dim3(bandwidth_grid(nnz)), dim3(TB), 0, 0, ids_sorted, row, nnz, ci_t, ids);
+		HIP_TRY(hipGetLastError());
+	}
+	HIP_TRY(hipDeviceSynchronize());
+	tmp.release();
+	out.ptrs.clear();
+	*rp_t_out = rp_t;
+	*ci_t_out = ci_t;
+	*ids_out = ids;
 	return 0;
 }
 

@@ -90,6 +90,10 @@ SYMBOLS = [
     "spmv_mi355x_trsv_update_values_staged",
     "spmv_mi355x_trsv_solve_sweeps_device_async", "spmv_mi355x_trsv_solve_sweeps", "spmv_mi355x_trsv_solve_sweeps_multi_device_async",
     "spmv_mi355x_trsv_solve_sweeps_multi", "spmv_mi355x_trsv_set_sweeps", "spmv_mi355x_trsv_sweeps_info",
+    "spmv_mi355x_color_create", "spmv_mi355x_color_destroy", "spmv_mi355x_color_info", "spmv_mi355x_color_colors", "spmv_mi355x_color_perm",
+    "spmv_mi355x_color_color_ptr", "spmv_mi355x_color_mem_footprint", "spmv_mi355x_color_permute_csr", "spmv_mi355x_color_permute_csr_device",
+    "spmv_mi355x_color_permute_values", "spmv_mi355x_color_permute_values_device_async", "spmv_mi355x_color_permute_vectors",
+    "spmv_mi355x_color_permute_vectors_device_async",
 ]
 
 _lib = None
@@ -222,6 +226,28 @@ def lib():
         L.spmv_mi355x_trsv_update_values_staged.argtypes = [C.c_void_p, C.c_void_p]
         L.spmv_mi355x_trsv_stored_values.restype = C.c_int
         L.spmv_mi355x_trsv_stored_values.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_long), C.c_void_p]
+        L.spmv_mi355x_color_create.restype = C.c_int
+        L.spmv_mi355x_color_create.argtypes = [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_int]
+        for f in ("spmv_mi355x_color_info", "spmv_mi355x_color_colors", "spmv_mi355x_color_color_ptr"):
+            getattr(L, f).restype = C.c_int
+            getattr(L, f).argtypes = [C.c_void_p, C.c_void_p]
+        for f in ("spmv_mi355x_color_perm", "spmv_mi355x_color_permute_values"):
+            getattr(L, f).restype = C.c_int
+            getattr(L, f).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.spmv_mi355x_color_mem_footprint.restype = C.c_double
+        L.spmv_mi355x_color_mem_footprint.argtypes = [C.c_void_p]
+        L.spmv_mi355x_color_destroy.restype = C.c_int
+        L.spmv_mi355x_color_destroy.argtypes = [C.c_void_p]
+        L.spmv_mi355x_color_permute_csr.restype = C.c_int
+        L.spmv_mi355x_color_permute_csr.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        for f in ("spmv_mi355x_color_permute_csr_device", "spmv_mi355x_color_permute_values_device_async"):
+            getattr(L, f).restype = C.c_int
+            getattr(L, f).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.spmv_mi355x_color_permute_vectors.restype = C.c_int
+        L.spmv_mi355x_color_permute_vectors.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_void_p, C.c_long]
+        L.spmv_mi355x_color_permute_vectors_device_async.restype = C.c_int
+        L.spmv_mi355x_color_permute_vectors_device_async.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_void_p,
+                                                                     C.c_long, C.c_void_p]
         _lib = L
     return _lib
 
@@ -780,6 +806,149 @@ def ilu0_precond(row_ptr, col_idx, values, n, dtype=np.float64, block_rows=None,
         return F.factor(values).precond(dtype, **trsv_opts)
     finally:
         F.close()
+
+
+COLOR_FORWARD, COLOR_BACKWARD = 0, 1
+
+
+class ColorStats(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("n", C.c_long), ("nnz", C.c_long), ("symmetric", C.c_long), ("num_colors", C.c_long),
+                ("rounds", C.c_long), ("max_class", C.c_long), ("min_class", C.c_long), ("transpose_seconds", C.c_double),
+                ("round_seconds", C.c_double), ("sort_seconds", C.c_double), ("permute_seconds", C.c_double)]
+
+
+class Coloring:
+    """A multicolouring of the graph of a square CSR pattern (a_ij or a_ji stored), computed on the GPU, and the permutation that sorts
+    the rows by colour (include/spmv_mi355x.h "multicolour ordering"). colors[i] is the colour of row i, equal to first-fit greedy
+    colouring in descending key order; perm[p] is the old row at new position p, rank its inverse, color_ptr the first position of
+    every colour. permute_csr gives B = P A P^t, whose triangles have as many levels as there are colours: TriangularSolve, Ilu0,
+    sgs_precond, ilu0_precond and Matrix are then used on B as on any matrix, with permute(b) going in and unpermute(x) coming out."""
+
+    def __init__(self, row_ptr, col_idx, n, device=-1):
+        row_ptr = np.ascontiguousarray(row_ptr, np.int32)
+        col_idx = np.ascontiguousarray(col_idx, np.int32)
+        self.n = int(n)
+        self.h = C.c_void_p()
+        _check(lib().spmv_mi355x_color_create(C.byref(self.h), C.c_long(n), _p(row_ptr), _p(col_idx), C.c_int(device)))
+        self.nnz = int(row_ptr[n]) if len(row_ptr) else 0
+        st = self.info()
+        self.num_colors = st["num_colors"]
+        self.colors = np.full(max(self.n, 1), -1, np.int32)
+        self.perm = np.full(max(self.n, 1), -1, np.int32)
+        self.rank = np.full(max(self.n, 1), -1, np.int32)
+        self.color_ptr = np.full(self.num_colors + 1, -1, np.int32)
+        _check(lib().spmv_mi355x_color_colors(self.h, _p(self.colors)))
+        _check(lib().spmv_mi355x_color_perm(self.h, _p(self.perm), _p(self.rank)))
+        _check(lib().spmv_mi355x_color_color_ptr(self.h, _p(self.color_ptr)))
+        self.colors, self.perm, self.rank = self.colors[:self.n], self.perm[:self.n], self.rank[:self.n]
+
+    @property
+    def mem_footprint(self):
+        return lib().spmv_mi355x_color_mem_footprint(self.h)
+
+    def info(self):
+        """dict(n, nnz, symmetric, num_colors, rounds, max_class, min_class, transpose_seconds, round_seconds, sort_seconds,
+        permute_seconds) of spmv_mi355x_color_info"""
+        r = ColorStats()
+        r.struct_size = C.sizeof(ColorStats)
+        _check(lib().spmv_mi355x_color_info(self.h, C.byref(r)))
+        return {k: getattr(r, k) for k, _ in ColorStats._fields_ if k != "struct_size"}
+
+    def permute_csr(self, values=None):
+        """(row_ptr, col_idx, values, entry_map) of B = P A P^t on the host: row p holds row perm[p] of A with columns rank[j] in
+        ascending new column order, equal columns in stored order; values_B = values_A[entry_map] (None without values)
+        (spmv_mi355x_color_permute_csr; blocking)"""
+        rp = np.zeros(self.n + 1, np.int32)
+        ci = np.zeros(max(self.nnz, 1), np.int32)
+        em = np.zeros(max(self.nnz, 1), np.int32)
+        va = out = None
+        if values is not None:
+            va = np.ascontiguousarray(values, np.float64)
+            if va.shape != (self.nnz,):
+                raise ValueError(f"values must have {self.nnz} entries, got {va.shape}")
+            out = np.full(max(self.nnz, 1), np.nan)
+        _check(lib().spmv_mi355x_color_permute_csr(self.h, None if va is None else _p(va), _p(rp), _p(ci), None if out is None else _p(out),
+                                                   _p(em)))
+        return rp, ci[:self.nnz], None if out is None else out[:self.nnz], em[:self.nnz]
+
+    def permute_csr_device(self):
+        """(row_ptr, col_idx, entry_map) of B as device pointers the handle owns, valid until close()
+        (spmv_mi355x_color_permute_csr_device)"""
+        rp, ci, em = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(lib().spmv_mi355x_color_permute_csr_device(self.h, C.byref(rp), C.byref(ci), C.byref(em)))
+        return rp.value or 0, ci.value or 0, em.value or 0
+
+    def permute_values(self, values):
+        """values_A[entry_map] for host values (spmv_mi355x_color_permute_values; blocking)"""
+        values = np.ascontiguousarray(values, np.float64)
+        if values.shape != (self.nnz,):
+            raise ValueError(f"values must have {self.nnz} entries, got {values.shape}")
+        out = np.full(max(self.nnz, 1), np.nan)
+        _check(lib().spmv_mi355x_color_permute_values(self.h, _p(values), _p(out)))
+        return out[:self.nnz]
+
+    def permute_values_device(self, in_ptr, out_ptr, stream=None):
+        """The same gather on device pointers to nnz doubles each, enqueued on `stream`
+        (spmv_mi355x_color_permute_values_device_async): out is what update_values_device of a handle of B, Ilu0.factor_device and
+        TriangularSolve.update_values_device take"""
+        _check(lib().spmv_mi355x_color_permute_values_device_async(self.h, C.c_void_p(in_ptr), C.c_void_p(out_ptr), C.c_void_p(stream or 0)))
+
+    def _vectors(self, direction, V):
+        V = np.asarray(V)
+        if V.dtype not in (np.float32, np.float64):
+            V = V.astype(np.float64)
+        V = np.ascontiguousarray(V)
+        if V.ndim not in (1, 2) or V.shape[0] != self.n:
+            raise ValueError(f"expected {self.n} rows, got {V.shape}")
+        k = 1 if V.ndim == 1 else V.shape[1]
+        out = np.full_like(V, np.nan) if V.size else V.copy()
+        if V.size:
+            _check(lib().spmv_mi355x_color_permute_vectors(self.h, C.c_int(direction), C.c_int(F32 if V.dtype == np.float32 else F64),
+                                                           C.c_int(k), _p(V), C.c_long(k), _p(out), C.c_long(k)))
+        return out
+
+    def permute(self, V):
+        """V[perm] for a host vector of n values or an n x k block, fp32 or fp64: into the colour ordering
+        (spmv_mi355x_color_permute_vectors, forward; blocking)"""
+        return self._vectors(COLOR_FORWARD, V)
+
+    def unpermute(self, V):
+        """the inverse of permute: out[perm[p]] = V[p], back into the caller's ordering"""
+        return self._vectors(COLOR_BACKWARD, V)
+
+    def permute_device(self, in_ptr, out_ptr, k=1, dtype=np.float64, ldin=None, ldout=None, stream=None, direction=COLOR_FORWARD):
+        """The same on device pointers to row-major n x k blocks with leading dimensions ldin / ldout (default k), enqueued on
+        `stream` (spmv_mi355x_color_permute_vectors_device_async); in_ptr == out_ptr is refused"""
+        _check(lib().spmv_mi355x_color_permute_vectors_device_async(
+            self.h, C.c_int(direction), C.c_int(F32 if np.dtype(dtype) == np.float32 else F64), C.c_int(k), C.c_void_p(in_ptr),
+            C.c_long(k if ldin is None else ldin), C.c_void_p(out_ptr), C.c_long(k if ldout is None else ldout), C.c_void_p(stream or 0)))
+
+    def unpermute_device(self, in_ptr, out_ptr, k=1, dtype=np.float64, ldin=None, ldout=None, stream=None):
+        self.permute_device(in_ptr, out_ptr, k, dtype, ldin, ldout, stream, COLOR_BACKWARD)
+
+    def close(self):
+        if getattr(self, "h", None) is not None and self.h:
+            lib().spmv_mi355x_color_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def multicolor_system(row_ptr, col_idx, values, n, device=-1):
+    """(coloring, row_ptr_B, col_idx_B, values_B) of B = P A P^t under the multicolouring of A's graph: sgs_precond, ilu0_precond, Ilu0,
+    TriangularSolve and Matrix are called on B exactly as on A; A x = b becomes B (P x) = P b, i.e. x = coloring.unpermute(the
+    solution for coloring.permute(b)). The caller closes the coloring."""
+    col = Coloring(row_ptr, col_idx, n, device=device)
+    try:
+        rp, ci, va, _ = col.permute_csr(values)
+    except Exception:
+        col.close()
+        raise
+    return col, rp, ci, va
 
 
 FSAI_MAX_ROW = 128

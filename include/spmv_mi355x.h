@@ -1289,7 +1289,7 @@ int  spmv_mi355x_spgemm_info(const spmv_mi355x_spgemm * P, spmv_mi355x_spgemm_st
  *     passes: "new values for a hierarchy" below), W- and K-cycles, more than one near-null vector (block coarse unknowns,
  *     elasticity), filtering with a threshold of its own, gmres / minres / multi-RHS wiring other than CG's (k right-hand sides
  *     through the cycle and through CG: spmv_mi355x_amg_apply_multi and spmv_mi355x_pcg_amg_multi below), the row-partitioned
- *     form, folding the small levels into one launch. The setup routes patterns
+ *     form. (The small levels as one launch are built, opt-in: "AMG: the small levels as one launch" below.) The setup routes patterns
  *     through the host (spgemm_create and create take host arrays); the split in amg_info shows what that costs.
  * spmv_mi355x_pcg_amg is spmv_mi355x_pcg_tri with z = M^-1 r = amg_apply_device_async: the same recurrences, kernels, stop codes,
  * history, spmv_mi355x_pcg_tri_info and freeze (the SpMVs and vector kernels of a cycle write only the hierarchy's own vectors and
@@ -1497,6 +1497,66 @@ int  spmv_mi355x_pcg_fsai_multi(spmv_mi355x_matrix * A, int k, const void * B_ho
 		long max_iterations, double * history_out, spmv_mi355x_pcg_tri_info * infos);
 int  spmv_mi355x_pcg_amg_multi(spmv_mi355x_matrix * A, int k, const void * B_host, void * X_out_host, spmv_mi355x_amg * M, double tol,
 		long max_iterations, double * history_out, spmv_mi355x_pcg_tri_info * infos);
+
+/* ---- AMG: the small levels as one launch (opt-in fold) ---------------------------------------------------------------------------- */
+/* The cycle of a large hierarchy is bound by its launches, and most of them belong to levels that hold almost none of its entries.
+ * spmv_mi355x_amg_set_fold(M, fold_rows) is a setter on a built hierarchy (as trsv_set_sweeps is): fold_rows = 0, the state after
+ * create, is off; the range is 0..65536. With fold_rows > 0 let f be the first level, level 0 included, with rows[f] <= fold_rows.
+ * Levels 0 .. f-1 run exactly as before: same handles, same launches. The whole rest of the V cycle from level f down to the last
+ * level and back up to level f (smoothing, residual, restriction, the coarse solve or the coarse sweeps, prolongation, smoothing) is
+ * ONE launch of ONE workgroup of 1024 lanes (csrc/kernels_amg_fold.hip). If no level qualifies nothing folds and
+ * apply is the unfolded apply bit for bit. f depends on fold_rows and rows[] alone: never on k, the precision or LDS capacity. With
+ * the fold off every entry point does what it did, bit for bit and launch for launch.
+ * THE DATA. The fold owns plain int32 CSR copies of A_l, P_l and R_l of the folded levels, values narrowed to the handle's
+ * precision as the handles' are, uploaded at set_fold from the host copies the hierarchy keeps. R_l is the stable transposition of
+ * P_l's CSR (rows ascending within a column: the device transposition's order). w_l is the level's own w, the dense factor the
+ * hierarchy's own. The vectors are the hierarchy's level vectors in global memory, ordered by workgroup barriers; LDS holds the
+ * packed factor and the pivots of the dense solve alone. No atomics, no flags, no grid barrier, nothing spins; every barrier sits
+ * outside the row loops, whose trip counts are uniform. The copies are counted in amg_mem_footprint and freed at destroy.
+ * THE ARITHMETIC OF THE TAIL, pinned (tests/amg_fold_reference.c states it as sequential loops), in the handle's precision T, every
+ * product and sum rounded on its own, the only fused operations the fma() written here:
+ *      a row's product: s = +0, then s = fma(a_e, x_col(e), s) for the row's entries e in stored order;
+ *      x = w o b;   t = A x, x = x + w o (b - t);   t = b - A x;   b_{l+1} = R t;   x = x + P x_{l+1}
+ * in the cycle's order ("THE CYCLE" of "AMG" above). LANES PER ROW: the rows of A_l are split over G_l lanes, G_l = the largest
+ * power of two that is <= min(64, nnz(A_l) / n_l, 1024 / n_l) in integer division, and 1 where that minimum is 0. Lane g of a row
+ * takes the entries g, g + G, g + 2 G, ... of the row as its own fma chain from +0, and the G partial sums are combined by the
+ * halving tree s_g = s_g + s_{g + h} for h = G / 2, G / 4, ..., 1; the product is s_0. G_l depends on the CSR of A_l alone, never
+ * on k, T or the launch; amg_fold_info reports it. The rows of P_l and R_l are walked by one lane. A dense last level is solved
+ * inside the tail with the bits of the dense solve of "AMG" above: fp64, the same column order. The tail sums a row in another order
+ * than a handle's SpMV does: a folded apply differs from the unfolded one by rounding, and stays within the cycle's bound of it.
+ * K COLUMNS: amg_apply_multi launches the tail once per chunk of 8, 4, 2 or 1 columns; a lane loads a (value, column) pair once
+ * and keeps one partial sum per column; column j of amg_apply_multi has the bits of amg_apply on column j, fold on or off.
+ *   - amg_set_fold: blocking (it synchronises the device); not to be called while an apply is in flight. rc 1 with "amg_set_fold:":
+ *     a NULL handle; fold_rows outside 0..65536; a hierarchy whose last update failed. n == 0 is legal: no level, nothing folds.
+ *   - amg_fold_info: struct_size is set by the caller. fold_rows; first_level (= levels when nothing folds); folded_levels;
+ *     launches_per_apply and spmvs_per_apply (the handle SpMVs left) of one apply; tail_products, the matrix products inside the tail
+ *     and tail_entries, their entry visits per apply; lanes_per_row[l] = G_l of the folded levels (0 above them); bytes of the copies.
+ *     amg_info's spmvs_per_apply and launches_per_apply and amg_apply_multi_plan(k) follow the fold (one tail launch per chunk).
+ *   - amg_apply_level_device_async: out = cycle(level, in) for one column of rows[level] values under the current fold setting,
+ *     in == out legal. rc 1 with "amg_apply_level:": a NULL handle; a hierarchy whose last update failed; a level outside
+ *     0..levels-1; NULL in or out.
+ *   - amg_apply*, amg_apply_multi*, pcg_amg and pcg_amg_multi pick the fold up through apply.
+ *   - new values: amg_update_values* on a folded hierarchy refreshes the fold's value arrays on the device (narrowed from the
+ *     update's arrays, which are in the same entry order); w and the factor are the hierarchy's own; a last level that flips between
+ *     dense and sweeps is followed. The result is what set_fold gives on a hierarchy created from the new values (contract 1 of
+ *     "new values for a hierarchy"). set_fold before or after amg_update_values_prepare both work.
+ *   - NOT BUILT: a multi-workgroup tail (one CU bounds what is worth folding), folding by entries instead of rows, a fold for FSAI,
+ *     W-cycles inside the tail.
+ * MEASURED (one MI355X, fp64, every leg beside fold_rows = 0 on the same hierarchy; profiles/r33_amg_fold.txt): the fold LOSES unless
+ * the tail is tiny. Unfolded, the small levels cost 3.5 us per launch; one workgroup walks the tail at 1.1 ns per entry visit. On
+ * the 2000 x 2000 grid (theta 0.08, last levels of 37, 164, 301 entries per row) fold_rows = 1024 takes the apply from 0.553 to
+ * 1.603 ms, 8192 to 2.18 ms, 65536 to 5.65 ms; with filtered smoothing (tails of 9 222 to 27 453 entry visits) 1024 is level or 2 %
+ * ahead. The default stays 0 and no value is recommended as one. */
+typedef struct {
+	unsigned struct_size;   /* set by the caller */
+	int    fold_rows, first_level, folded_levels;
+	long   launches_per_apply, spmvs_per_apply, tail_products, tail_entries;
+	int    lanes_per_row[SPMV_MI355X_AMG_MAX_LEVELS];
+	double bytes;
+} spmv_mi355x_amg_fold_stats;
+int  spmv_mi355x_amg_set_fold(spmv_mi355x_amg * M, int fold_rows);                                           /* blocking */
+int  spmv_mi355x_amg_fold_info(const spmv_mi355x_amg * M, spmv_mi355x_amg_fold_stats * info /* struct_size first */);
+int  spmv_mi355x_amg_apply_level_device_async(spmv_mi355x_amg * M, int level, const void * in_dev, void * out_dev, void * hip_stream);
 
 /* Row-partitioned (multi-GPU) form of the same two solvers: one process per GPU owns the row block [row_offset,
  * row_offset + m_local) of A, b and x. The solver keeps every vector device-resident and local; the two things that cross

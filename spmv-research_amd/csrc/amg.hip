@@ -126,10 +126,45 @@ amg_update_free(AmgUpdate * u)
 }
 
 static void
+amg_fold_free(spmv_mi355x_amg * M)
+{
+	if (!M->fold)
+		return;
+	for (void * p : M->fold->owned)
+		(void) hipFree(p);
+	delete M->fold;
+	M->fold = nullptr;
+}
+
+// the first folded level; `levels` when nothing folds
+static int
+amg_fold_first(const spmv_mi355x_amg * M)
+{
+	return M->fold ? M->fold->first : M->levels;
+}
+
+// SpMVs and launches of one apply: the levels above the first folded one as ever, then one launch for the tail
+static void
+amg_count_launches(spmv_mi355x_amg * M)
+{
+	const int nu = M->opts.sweeps, cs = M->opts.coarse_sweeps, f = amg_fold_first(M);
+	const bool dense = M->coarse_kind == SPMV_MI355X_AMG_COARSE_DENSE;
+	if (f < M->levels)
+	{
+		M->spmvs = (long) f * (2 * nu + 2);
+		M->launches = M->spmvs + (long) f * (2 * nu + 1) + 1;
+		return;
+	}
+	M->spmvs = (long) (M->levels - 1) * (2 * nu + 2) + (dense ? 0 : cs - 1);
+	M->launches = M->spmvs + (long) (M->levels - 1) * (2 * nu + 1) + (dense ? 1 : cs);
+}
+
+static void
 amg_free(spmv_mi355x_amg * M)
 {
 	amg_update_free(M->upd);
 	M->upd = nullptr;
+	amg_fold_free(M);
 	for (AmgLevel & L : M->lev)
 	{
 		for (spmv_mi355x_matrix * h : {L.A, L.P, L.R})
@@ -546,7 +581,6 @@ amg_build(spmv_mi355x_amg * M, const spmv_mi355x_opts & o)
 	}
 	M->levels = (int) M->lev.size();
 	const AmgLevel & Z = M->lev.back();
-	const int nu = M->opts.sweeps, cs = M->opts.coarse_sweeps;
 	M->coarse_kind = SPMV_MI355X_AMG_COARSE_SWEEPS;
 	if (Z.n <= AMG_DENSE_MAX)
 	{
@@ -561,8 +595,7 @@ amg_build(spmv_mi355x_amg * M, const spmv_mi355x_opts & o)
 		else
 			M->coarse_kind = SPMV_MI355X_AMG_COARSE_SWEEPS_AFTER_PIVOT;
 	}
-	M->spmvs = (long) (M->levels - 1) * (2 * nu + 2) + (M->coarse_kind == SPMV_MI355X_AMG_COARSE_DENSE ? 0 : cs - 1);
-	M->launches = M->spmvs + (long) (M->levels - 1) * (2 * nu + 1) + (M->coarse_kind == SPMV_MI355X_AMG_COARSE_DENSE ? 1 : cs);
+	amg_count_launches(M);
 	return 0;
 }
 
@@ -849,6 +882,10 @@ amg_update_levels(spmv_mi355x_amg * M, double rho0, hipStream_t st)
 		auto t0 = std::chrono::steady_clock::now();
 		ABI_TRY(spmv_mi355x_update_values_device(L.A, U.d_va, st));
 		u->handle_seconds += amg_since(t0);
+		// a folded level: the tail's copy of A_l's values, narrowed as the handle's are (w is the level's own array)
+		const bool folded = M->fold && l >= M->fold->first;
+		if (folded)
+			ABI_TRY(launch_amg_fold_values(f32, U.d_va, M->fold->va[(size_t) l], L.nnz, st));
 		if (!L.P)
 			continue;
 		AmgUpdateLevel & C = u->lev[(size_t) l + 1];
@@ -885,6 +922,11 @@ amg_update_levels(spmv_mi355x_amg * M, double rho0, hipStream_t st)
 		else
 			ABI_TRY(launch_amg_prolong(n, U.at->d_c_rp, U.at->d_c_ci, U.d_at, U.d_agg, U.d_d, L.omega, U.d_p, st));
 		ABI_TRY(transpose_gather_values(U.d_src, U.d_p, L.nnz_p, U.d_r, st));
+		if (folded)
+		{
+			ABI_TRY(launch_amg_fold_values(f32, U.d_p, M->fold->p_va[(size_t) l], L.nnz_p, st));
+			ABI_TRY(launch_amg_fold_values(f32, U.d_r, M->fold->r_va[(size_t) l], L.nnz_p, st));
+		}
 		HIP_TRY(hipStreamSynchronize(st));
 		t0 = std::chrono::steady_clock::now();
 		ABI_TRY(spmv_mi355x_spgemm_multiply_device_async(U.ap, U.d_va, U.d_p, U.d_ap, st));
@@ -931,10 +973,185 @@ amg_update_levels(spmv_mi355x_amg * M, double rho0, hipStream_t st)
 			M->coarse_kind = SPMV_MI355X_AMG_COARSE_DENSE;
 		}
 	}
-	const int nu = M->opts.sweeps, cs = M->opts.coarse_sweeps;
-	M->spmvs = (long) (M->levels - 1) * (2 * nu + 2) + (M->coarse_kind == SPMV_MI355X_AMG_COARSE_DENSE ? 0 : cs - 1);
-	M->launches = M->spmvs + (long) (M->levels - 1) * (2 * nu + 1) + (M->coarse_kind == SPMV_MI355X_AMG_COARSE_DENSE ? 1 : cs);
+	amg_count_launches(M);                                // the tail reads coarse_kind and d_factor at every launch: it follows a flip
 	return 0;
+}
+
+// out = cycle(start, in) for one column of rows[start] values: the levels above the first folded one through their handles, the rest
+// as one launch. start = 0 is amg_apply; with no fold this enqueues what it has always enqueued.
+static int
+amg_cycle(spmv_mi355x_amg * M, int start, const void * in_dev, void * out_dev, hipStream_t st)
+{
+	const bool f32 = M->f32;
+	const int nl = M->levels, nu = M->opts.sweeps, cs = M->opts.coarse_sweeps, f = amg_fold_first(M);
+	const bool dense = M->coarse_kind == SPMV_MI355X_AMG_COARSE_DENSE;
+	if (in_dev == out_dev)
+	{
+		// the level reads b after it has written x: an apply in place works on a copy of `in`
+		HIP_TRY(hipMemcpyAsync(M->lev[(size_t) start].b, in_dev, (size_t) M->lev[(size_t) start].n * (f32 ? 4 : 8), hipMemcpyDeviceToDevice, st));
+		in_dev = M->lev[(size_t) start].b;
+	}
+	auto rhs = [&](int l) { return l == start ? in_dev : (const void *) M->lev[(size_t) l].b; };
+	auto sol = [&](int l) { return l == start ? out_dev : M->lev[(size_t) l].x; };
+	auto tail = [&](int l) {
+		return launch_amg_fold_tail(f32, 1, M->fold->d_single, l, nl - 1, rhs(l), 1, sol(l), 1, 1, nu, cs, dense ? M->d_factor : nullptr, st);
+	};
+	if (start >= f)
+		return tail(start);
+	auto sweep = [&](int l) {
+		AmgLevel & L = M->lev[(size_t) l];
+		ABI_TRY(spmv_mi355x_spmv_device_async(L.A, sol(l), L.t, 0, st));
+		return launch_amg_sweep(f32, L.w, rhs(l), L.t, sol(l), L.n, st);
+	};
+	const int bottom = std::min(f, nl - 1);                   // the level the handles stop above
+	for (int l = start; l < bottom; l++)
+	{
+		AmgLevel & L = M->lev[(size_t) l];
+		ABI_TRY(launch_amg_first(f32, L.w, rhs(l), sol(l), L.n, st));
+		for (int s = 1; s < nu; s++)
+			ABI_TRY(sweep(l));
+		ABI_TRY(spmv_mi355x_spmv_device_async(L.A, sol(l), L.t, 0, st));
+		ABI_TRY(launch_amg_residual(f32, rhs(l), L.t, L.n, st));
+		ABI_TRY(spmv_mi355x_spmv_device_async(L.R, L.t, M->lev[(size_t) l + 1].b, 0, st));
+	}
+	if (f < nl)
+		ABI_TRY(tail(f));
+	else
+	{
+		const int l = nl - 1;
+		AmgLevel & L = M->lev[(size_t) l];
+		if (dense)
+			ABI_TRY(launch_amg_dense_solve(f32, M->d_factor, rhs(l), sol(l), (int) L.n, st));
+		else
+		{
+			ABI_TRY(launch_amg_first(f32, L.w, rhs(l), sol(l), L.n, st));
+			for (int s = 1; s < cs; s++)
+				ABI_TRY(sweep(l));
+		}
+	}
+	for (int l = bottom - 1; l >= start; l--)
+	{
+		AmgLevel & L = M->lev[(size_t) l];
+		ABI_TRY(spmv_mi355x_spmv_device_async(L.P, M->lev[(size_t) l + 1].x, sol(l), 1, st));
+		for (int s = 0; s < nu; s++)
+			ABI_TRY(sweep(l));
+	}
+	return 0;
+}
+
+// the k-column descriptors of the tail: the single ones with the blocks mb, mx, mt for vectors (after amg_multi_reserve, which has
+// synchronised the device when it replaced them)
+static int
+amg_fold_multi_descriptors(spmv_mi355x_amg * M)
+{
+	AmgFold * F = M->fold;
+	if (!F || M->multi_k == 0)
+		return 0;
+	std::vector<AmgFoldLevel> d = F->host;
+	for (int l = F->first; l < M->levels; l++)
+	{
+		d[(size_t) l].b = M->mb[(size_t) l];
+		d[(size_t) l].x = M->mx[(size_t) l];
+		d[(size_t) l].t = M->mt[(size_t) l];
+	}
+	HIP_TRY(hipMemcpy(F->d_multi, d.data(), d.size() * sizeof(AmgFoldLevel), hipMemcpyHostToDevice));
+	return 0;
+}
+
+template <typename T>
+static int
+amg_fold_keep(AmgFold * F, T ** out, size_t count, const T * host)
+{
+	void * p = nullptr;
+	const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
+	ABI_TRY(dev_alloc_bytes(&p, bytes));
+	F->owned.push_back(p);
+	F->bytes += (double) bytes;
+	*out = (T *) p;
+	if (host && count)
+		HIP_TRY(hipMemcpy(p, host, count * sizeof(T), hipMemcpyHostToDevice));
+	return 0;
+}
+
+// `count` fp64 values narrowed to the handle's precision, as create narrows them, on the device
+static int
+amg_fold_keep_values(AmgFold * F, bool f32, void ** out, const double * host, size_t count)
+{
+	if (!f32)
+		return amg_fold_keep(F, (double **) out, count, host);
+	std::vector<float> v(count);
+	for (size_t e = 0; e < count; e++)
+		v[e] = (float) host[e];
+	return amg_fold_keep(F, (float **) out, count, v.data());
+}
+
+// The fold's data for the levels first .. levels - 1: the CSR copies of A_l and P_l from the host copies the hierarchy keeps, R_l as
+// the stable transposition of P_l (rows ascending within a column: the device transposition's order), the descriptors.
+static int
+amg_fold_build(spmv_mi355x_amg * M, int first)
+{
+	AmgFold * F = new AmgFold();
+	M->fold = F;
+	F->first = first;
+	const size_t nl = (size_t) M->levels;
+	F->host.assign(nl, AmgFoldLevel{});
+	F->va.assign(nl, nullptr);
+	F->p_va.assign(nl, nullptr);
+	F->r_va.assign(nl, nullptr);
+	for (size_t l = (size_t) first; l < nl; l++)
+	{
+		const AmgLevel & L = M->lev[l];
+		AmgFoldLevel & D = F->host[l];
+		int * rp, * ci;
+		ABI_TRY(amg_fold_keep(F, &rp, (size_t) L.n + 1, (const int *) L.rp.data()));
+		ABI_TRY(amg_fold_keep(F, &ci, (size_t) L.nnz, (const int *) L.ci.data()));
+		ABI_TRY(amg_fold_keep_values(F, M->f32, &F->va[l], L.va.data(), (size_t) L.nnz));
+		D.a_rp = rp;
+		D.a_ci = ci;
+		D.a_va = F->va[l];
+		D.w = L.w;
+		D.b = L.b;
+		D.x = L.x;
+		D.t = L.t;
+		D.n = (int) L.n;
+		const int g = amg_fold_lanes(L.n, L.nnz);
+		for (D.lg = 0; (1 << D.lg) < g; D.lg++)
+			;
+		if (!L.P)
+			continue;
+		const long nc = L.aggregates, nnz_p = L.nnz_p;
+		ABI_TRY(amg_fold_keep(F, &rp, (size_t) L.n + 1, (const int *) L.p_rp.data()));
+		ABI_TRY(amg_fold_keep(F, &ci, (size_t) nnz_p, (const int *) L.p_ci.data()));
+		ABI_TRY(amg_fold_keep_values(F, M->f32, &F->p_va[l], L.p_va.data(), (size_t) nnz_p));
+		D.p_rp = rp;
+		D.p_ci = ci;
+		D.p_va = F->p_va[l];
+		std::vector<int> r_rp((size_t) nc + 1, 0), r_ci((size_t) std::max<long>(nnz_p, 1)), at((size_t) std::max<long>(nc, 1));
+		std::vector<double> r_va((size_t) std::max<long>(nnz_p, 1));
+		for (long e = 0; e < nnz_p; e++)
+			r_rp[(size_t) L.p_ci[(size_t) e] + 1]++;
+		for (long j = 0; j < nc; j++)
+		{
+			r_rp[(size_t) j + 1] += r_rp[(size_t) j];
+			at[(size_t) j] = r_rp[(size_t) j];
+		}
+		for (long i = 0; i < L.n; i++)
+			for (long e = L.p_rp[(size_t) i]; e < L.p_rp[(size_t) i + 1]; e++)
+			{
+				const int to = at[(size_t) L.p_ci[(size_t) e]]++;
+				r_ci[(size_t) to] = (int) i;
+				r_va[(size_t) to] = L.p_va[(size_t) e];
+			}
+		ABI_TRY(amg_fold_keep(F, &rp, (size_t) nc + 1, (const int *) r_rp.data()));
+		ABI_TRY(amg_fold_keep(F, &ci, (size_t) nnz_p, (const int *) r_ci.data()));
+		ABI_TRY(amg_fold_keep_values(F, M->f32, &F->r_va[l], r_va.data(), (size_t) nnz_p));
+		D.r_rp = rp;
+		D.r_ci = ci;
+		D.r_va = F->r_va[l];
+	}
+	ABI_TRY(amg_fold_keep(F, &F->d_single, nl, F->host.data()));
+	ABI_TRY(amg_fold_keep(F, &F->d_multi, nl, F->host.data()));
+	return amg_fold_multi_descriptors(M);
 }
 
 }  // namespace spmv
@@ -1158,52 +1375,35 @@ spmv_mi355x_amg_apply_device_async(spmv_mi355x_amg * M, const void * in_dev, voi
 				"with values it accepts first");
 		return 1;
 	}
-	hipStream_t st = (hipStream_t) hip_stream;
-	const bool f32 = M->f32;
-	const int nl = M->levels, nu = M->opts.sweeps;
-	if (in_dev == out_dev)
+	return amg_cycle(M, 0, in_dev, out_dev, (hipStream_t) hip_stream);
+}
+
+int
+spmv_mi355x_amg_apply_level_device_async(spmv_mi355x_amg * M, int level, const void * in_dev, void * out_dev, void * hip_stream)
+{
+	const char * what = "amg_apply_level";
+	if (!M)
 	{
-		// level 0 reads b after it has written x: an apply in place works on a copy of `in`
-		HIP_TRY(hipMemcpyAsync(M->lev[0].b, in_dev, (size_t) M->n * (f32 ? 4 : 8), hipMemcpyDeviceToDevice, st));
-		in_dev = M->lev[0].b;
+		set_error("%s: NULL handle", what);
+		return 1;
 	}
-	auto rhs = [&](int l) { return l == 0 ? in_dev : (const void *) M->lev[(size_t) l].b; };
-	auto sol = [&](int l) { return l == 0 ? out_dev : M->lev[(size_t) l].x; };
-	auto sweep = [&](int l) {
-		AmgLevel & L = M->lev[(size_t) l];
-		ABI_TRY(spmv_mi355x_spmv_device_async(L.A, sol(l), L.t, 0, st));
-		return launch_amg_sweep(f32, L.w, rhs(l), L.t, sol(l), L.n, st);
-	};
-	for (int l = 0; l < nl - 1; l++)
+	if (M->update_failed)
 	{
-		AmgLevel & L = M->lev[(size_t) l];
-		ABI_TRY(launch_amg_first(f32, L.w, rhs(l), sol(l), L.n, st));
-		for (int s = 1; s < nu; s++)
-			ABI_TRY(sweep(l));
-		ABI_TRY(spmv_mi355x_spmv_device_async(L.A, sol(l), L.t, 0, st));
-		ABI_TRY(launch_amg_residual(f32, rhs(l), L.t, L.n, st));
-		ABI_TRY(spmv_mi355x_spmv_device_async(L.R, L.t, M->lev[(size_t) l + 1].b, 0, st));
+		set_error("%s: the last amg_update_values of this hierarchy failed below level 0 and left it half rewritten: update it with "
+				"values it accepts first", what);
+		return 1;
 	}
+	if (level < 0 || level >= M->levels)
 	{
-		const int l = nl - 1;
-		AmgLevel & L = M->lev[(size_t) l];
-		if (M->coarse_kind == SPMV_MI355X_AMG_COARSE_DENSE)
-			ABI_TRY(launch_amg_dense_solve(f32, M->d_factor, rhs(l), sol(l), (int) L.n, st));
-		else
-		{
-			ABI_TRY(launch_amg_first(f32, L.w, rhs(l), sol(l), L.n, st));
-			for (int s = 1; s < M->opts.coarse_sweeps; s++)
-				ABI_TRY(sweep(l));
-		}
+		set_error("%s: level %d out of range: the hierarchy has %d", what, level, M->levels);
+		return 1;
 	}
-	for (int l = nl - 2; l >= 0; l--)
+	if (!in_dev || !out_dev)
 	{
-		AmgLevel & L = M->lev[(size_t) l];
-		ABI_TRY(spmv_mi355x_spmv_device_async(L.P, M->lev[(size_t) l + 1].x, sol(l), 1, st));
-		for (int s = 0; s < nu; s++)
-			ABI_TRY(sweep(l));
+		set_error("%s: NULL argument (%s%s )", what, !in_dev ? " in" : "", !out_dev ? " out" : "");
+		return 1;
 	}
-	return 0;
+	return amg_cycle(M, level, in_dev, out_dev, (hipStream_t) hip_stream);
 }
 
 int
@@ -1292,7 +1492,7 @@ amg_multi_reserve(spmv_mi355x_amg * M, int k)
 	}
 	M->vector_bytes += M->multi_bytes;
 	M->multi_k = k;
-	return 0;
+	return amg_fold_multi_descriptors(M);
 }
 
 int
@@ -1332,7 +1532,8 @@ spmv_mi355x_amg_apply_multi_device_async(spmv_mi355x_amg * M, int k, const void 
 		ABI_TRY(spmv_mi355x_spmm_device_async(L.A, k, sol(l), ldx(l), M->mt[(size_t) l], ld, 0, st));
 		return launch_amg_sweep_multi(f32, k, L.w, rhs(l), ldb(l), M->mt[(size_t) l], ld, sol(l), ldx(l), L.n, st);
 	};
-	for (int l = 0; l < nl - 1; l++)
+	const int f = amg_fold_first(M), bottom = std::min(f, nl - 1);
+	for (int l = 0; l < bottom; l++)
 	{
 		AmgLevel & L = M->lev[(size_t) l];
 		ABI_TRY(launch_amg_first_multi(f32, k, L.w, rhs(l), ldb(l), sol(l), ldx(l), L.n, st));
@@ -1342,6 +1543,11 @@ spmv_mi355x_amg_apply_multi_device_async(spmv_mi355x_amg * M, int k, const void 
 		ABI_TRY(launch_amg_residual_multi(f32, k, rhs(l), ldb(l), M->mt[(size_t) l], ld, L.n, st));
 		ABI_TRY(spmv_mi355x_spmm_device_async(L.R, k, M->mt[(size_t) l], ld, M->mb[(size_t) l + 1], ld, 0, st));
 	}
+	if (f < nl)
+		// the rest of the cycle: one launch per chunk of columns
+		ABI_TRY(launch_amg_fold_tail(f32, k, M->fold->d_multi, f, nl - 1, rhs(f), ldb(f), sol(f), ldx(f), ld, nu, M->opts.coarse_sweeps,
+				M->coarse_kind == SPMV_MI355X_AMG_COARSE_DENSE ? M->d_factor : nullptr, st));
+	else
 	{
 		const int l = nl - 1;
 		AmgLevel & L = M->lev[(size_t) l];
@@ -1354,7 +1560,7 @@ spmv_mi355x_amg_apply_multi_device_async(spmv_mi355x_amg * M, int k, const void 
 				ABI_TRY(sweep(l));
 		}
 	}
-	for (int l = nl - 2; l >= 0; l--)
+	for (int l = bottom - 1; l >= 0; l--)
 	{
 		AmgLevel & L = M->lev[(size_t) l];
 		ABI_TRY(spmv_mi355x_spmm_device_async(L.P, k, M->mx[(size_t) l + 1], ld, sol(l), ldx(l), 1, st));
@@ -1415,7 +1621,8 @@ spmv_mi355x_amg_apply_multi_plan(const spmv_mi355x_amg * M, int k, long * matrix
 	long passes = 0;
 	const int nu = M->opts.sweeps, cs = M->opts.coarse_sweeps;
 	const bool dense = M->coarse_kind == SPMV_MI355X_AMG_COARSE_DENSE;
-	for (int l = 0; l < M->levels; l++)
+	// a folded tail has no product of a handle: its one launch per chunk is among the vector launches below
+	for (int l = 0; l < std::min(M->levels, amg_fold_first(M)); l++)
 	{
 		const AmgLevel & L = M->lev[(size_t) l];
 		const bool last = l == M->levels - 1;
@@ -1478,6 +1685,87 @@ spmv_mi355x_amg_info(const spmv_mi355x_amg * M, spmv_mi355x_amg_stats * info)
 	s.transpose_seconds = M->transpose_seconds;
 	s.create_seconds = M->create_seconds;
 	s.download_seconds = M->download_seconds;
+	put_info(info, info->struct_size, s);
+	return 0;
+}
+
+int
+spmv_mi355x_amg_set_fold(spmv_mi355x_amg * M, int fold_rows)
+{
+	const char * what = "amg_set_fold";
+	if (!M)
+	{
+		set_error("%s: NULL handle", what);
+		return 1;
+	}
+	if (fold_rows < 0 || fold_rows > AMG_FOLD_MAX_ROWS)
+	{
+		set_error("%s: fold_rows = %d out of range 0..%d", what, fold_rows, AMG_FOLD_MAX_ROWS);
+		return 1;
+	}
+	if (M->update_failed)
+	{
+		set_error("%s: the last amg_update_values of this hierarchy failed below level 0 and left it half rewritten: update it with "
+				"values it accepts first", what);
+		return 1;
+	}
+	if (M->levels == 0)
+	{
+		M->fold_rows = fold_rows;
+		return 0;
+	}
+	HIP_TRY(hipSetDevice(M->device));
+	HIP_TRY(hipDeviceSynchronize());
+	amg_fold_free(M);
+	M->fold_rows = fold_rows;
+	int first = M->levels;
+	for (int l = M->levels - 1; l >= 0; l--)
+		if (M->lev[(size_t) l].n <= fold_rows)
+			first = l;
+	int rc = 0;
+	if (first < M->levels)
+	{
+		// the host copies of the values are what an update left on the device
+		rc = amg_refresh_host(M) || amg_fold_build(M, first);
+		if (rc)
+		{
+			const std::string msg = spmv_mi355x_last_error();
+			amg_fold_free(M);
+			M->fold_rows = 0;
+			set_error("%s: %s", what, msg.c_str());
+		}
+	}
+	amg_count_launches(M);
+	return rc;
+}
+
+int
+spmv_mi355x_amg_fold_info(const spmv_mi355x_amg * M, spmv_mi355x_amg_fold_stats * info)
+{
+	if (!M || !info)
+	{
+		set_error("amg_fold_info: NULL %s", !M ? "handle" : "info");
+		return 1;
+	}
+	if (!info_size_ok("amg_fold_info", info))
+		return 1;
+	spmv_mi355x_amg_fold_stats s;
+	memset(&s, 0, sizeof(s));
+	const int nu = M->opts.sweeps, cs = M->opts.coarse_sweeps;
+	s.fold_rows = M->fold_rows;
+	s.first_level = amg_fold_first(M);
+	s.folded_levels = M->levels - s.first_level;
+	s.launches_per_apply = M->launches;
+	s.spmvs_per_apply = M->spmvs;
+	for (int l = s.first_level; l < M->levels; l++)
+	{
+		const AmgLevel & L = M->lev[(size_t) l];
+		const long with_a = L.P ? 2 * nu : M->coarse_kind == SPMV_MI355X_AMG_COARSE_DENSE ? 0 : cs - 1;
+		s.tail_products += with_a + (L.P ? 2 : 0);
+		s.tail_entries += with_a * L.nnz + (L.P ? 2 * L.nnz_p : 0);
+		s.lanes_per_row[l] = 1 << M->fold->host[(size_t) l].lg;
+	}
+	s.bytes = M->fold ? M->fold->bytes : 0;
 	put_info(info, info->struct_size, s);
 	return 0;
 }
@@ -1765,7 +2053,7 @@ spmv_mi355x_amg_mem_footprint(const spmv_mi355x_amg * M)
 {
 	if (!M)
 		return 0;
-	double bytes = M->vector_bytes;
+	double bytes = M->vector_bytes + (M->fold ? M->fold->bytes : 0);
 	for (const AmgLevel & L : M->lev)
 		for (const spmv_mi355x_matrix * h : {L.A, L.P, L.R})
 			if (h)

@@ -37,8 +37,18 @@
 //                          62 / 38 / 26 / 26     0         0
 //     amg_dense_solve_multi_kernel <KC = 8 / 4 / 2 / 1>
 //                          40 / 30 / 26 / 20   74 240 / 70 144 / 68 096 / 67 072 B   0
-// (-Rpass-analysis=kernel-resource-usage, gfx950; profiles/r23_amg.txt, profiles/r24_amg_update.txt and
-// profiles/r25_amg_prolongator.txt have the compiler's own table.)
+//     amg_fold_tail_kernel <KC = 8 / 4 / 2 / 1>, fp32 / fp64, 1024 lanes (at most 128 VGPRs)
+//            55 / 44 / 38 / 31 and 80 / 56 / 45 / 36     74 240 / 70 144 / 68 096 / 67 072 B   0
+//     amg_fold_narrow_kernel        8        0         0
+// (-Rpass-analysis=kernel-resource-usage, gfx950; profiles/r23_amg.txt, profiles/r24_amg_update.txt,
+// profiles/r25_amg_prolongator.txt and profiles/r33_amg_fold.txt have the compiler's own table.)
+// THE FOLDED TAIL (amg_set_fold; kernels_amg_fold.hip; the header's "AMG: the small levels as one launch"). ONE workgroup of
+// AMG_FOLD_TB = 1024 lanes runs the cycle from the first folded level down and back up, once per chunk of KC columns. A row of A_l is
+// walked by G_l = amg_fold_lanes(n_l, nnz_l) adjacent lanes of one wave (lane g takes the entries g, g + G, ..., a shuffle tree adds the
+// partials), a row of P_l or R_l by one lane; rows are dealt to the lanes in trips of 1024 / G rows, and every lane runs the same
+// number of trips. The elementwise steps are one lane per row with a stride of 1024. The dense solve is amg_dense_solve_multi_kernel's
+// with lanes 128.. idle: lane a owns y_a, one barrier per column in each direction, n trips in every lane. The vectors stay in global
+// memory (the hierarchy's b, x, t or mb, mx, mt), ordered by __syncthreads(); LDS holds the packed factor and piv alone.
 // STEPS 5a TO 5c (amg_create_with; the header's "AMG: a caller's near-null vector and filtered prolongator smoothing"). Filtered: a
 // count pass (kept entries, the lump and the fall-back per row), hipcub's exclusive scan over n + 1 counts, a fill pass (A_F's columns,
 // values, the int32 map into A_l, the partials of rho_p). Near-null: the device transposition of T's pattern with b as its values
@@ -66,6 +76,9 @@ constexpr int AMG_MAX_GRID = 1024;                        // workgroups per setu
 constexpr int AMG_DENSE_MAX = 128;                        // rows of a dense coarsest level: 128 * 129 / 2 doubles = 66 048 B of LDS
 constexpr int AMG_MIS_ROUND_CAP = 1024;                   // every round decides a node, real counts are below 20: a bug becomes a message
 constexpr unsigned AMG_HASH_MUL = 0x9E3779B1u;            // SPGEMM_HASH_MUL
+constexpr int AMG_FOLD_TB = 1024;                         // lanes of the one workgroup that runs the folded tail
+constexpr int AMG_FOLD_MAX_ROWS = 65536;                  // the largest fold_rows
+constexpr int AMG_FOLD_MAX_LANES = 64;                    // lanes per row of A_l inside the tail: at most a wave
 
 // A_l on the device
 struct AmgCsr {
@@ -135,6 +148,50 @@ int launch_amg_weights(bool f32, long n, const double * d, double omega, void * 
 // the packed factor of a.n <= AMG_DENSE_MAX rows into F; *failed = 1 at a pivot that is <= 0 or not finite (zeroed by the caller)
 int launch_amg_dense_factor(const AmgCsr & a, double * F, int * failed, hipStream_t st);
 
+// ---- the folded tail (amg_set_fold; kernels_amg_fold.hip) -----------------------------------------------------------------------------
+// One level as the tail kernel reads it, an array of `levels` of them on the device (entries above the first folded level are zero):
+// the fold's own int32 CSR copies of A_l, P_l and R_l with values of the handle's precision (P and R NULL on the last level), the
+// level's w, and the level's vectors: b, x, t of the single apply or mb, mx, mt of the k-column apply (x is NULL on level 0).
+struct AmgFoldLevel {
+	const int * a_rp, * a_ci;
+	const void * a_va;
+	const int * p_rp, * p_ci;
+	const void * p_va;
+	const int * r_rp, * r_ci;
+	const void * r_va;
+	const void * w;
+	void * b, * x, * t;
+	int n, lg;                                            // rows; log2 of the lanes per row of A_l
+};
+
+// THE RULE of the lanes per row (the header's): the largest power of two that is <= min(64, nnz / n, 1024 / n) in integer division,
+// and 1 where that minimum is 0. It depends on the CSR of A_l alone.
+inline int
+amg_fold_lanes(long n, long nnz)
+{
+	const long cap = n > 0 ? std::min<long>(AMG_FOLD_MAX_LANES, std::min(nnz / n, (long) AMG_FOLD_TB / n)) : 1;
+	int g = 1;
+	while (2L * g <= cap)
+		g *= 2;
+	return g;
+}
+
+struct AmgFold {
+	int first = 0;                                        // the first folded level
+	std::vector<AmgFoldLevel> host;                       // the descriptors with the single apply's vectors
+	std::vector<void *> va, p_va, r_va;                   // per level the fold's value arrays: what an update rewrites
+	AmgFoldLevel * d_single = nullptr, * d_multi = nullptr;
+	std::vector<void *> owned;
+	double bytes = 0;
+};
+
+// the tail from level `first` to `last` and back for k columns (one launch per chunk of 8, 4, 2 or 1): rhs `in` and solution `out` of
+// level `first` with their own ld, the other vectors the descriptors' with ld; factor NULL = the last level takes cs - 1 sweeps
+int launch_amg_fold_tail(bool f32, int k, const AmgFoldLevel * lv, int first, int last, const void * in, long ldin, void * out, long ldout, long ld,
+		int nu, int cs, const double * factor, hipStream_t st);
+// dst = src narrowed to the handle's precision (a copy in fp64)
+int launch_amg_fold_values(bool f32, const double * src, void * dst, long count, hipStream_t st);
+
 // what amg_update_values_prepare keeps of level l, all on the device
 struct AmgUpdateLevel {
 	spmv_mi355x_spgemm * at = nullptr, * ap = nullptr, * ac = nullptr;   // A T, A P, R (A P); NULL on the last level
@@ -199,4 +256,6 @@ struct spmv_mi355x_amg {
 	void * d_in_multi = nullptr, * d_out_multi = nullptr; // the blocks of the host-buffer apply_multi, n x multi_host_k
 	spmv::AmgUpdate * upd = nullptr;                      // amg_update_values_prepare's; NULL before it
 	bool update_failed = false;                           // the last update stopped below level 0: apply refuses
+	int fold_rows = 0;                                    // amg_set_fold's; 0 = off
+	spmv::AmgFold * fold = nullptr;                       // NULL while no level has rows <= fold_rows
 };

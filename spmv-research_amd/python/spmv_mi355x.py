@@ -78,6 +78,7 @@ SYMBOLS = [
     "spmv_mi355x_amg_update_values_state", "spmv_mi355x_amg_update_info",
     "spmv_mi355x_amg_create_with", "spmv_mi355x_amg_prolongator_info", "spmv_mi355x_amg_near_null",
     "spmv_mi355x_amg_apply_multi_device_async", "spmv_mi355x_amg_apply_multi", "spmv_mi355x_amg_apply_multi_plan",
+    "spmv_mi355x_amg_set_fold", "spmv_mi355x_amg_fold_info", "spmv_mi355x_amg_apply_level_device_async",
     "spmv_mi355x_fsai_apply_multi_device_async", "spmv_mi355x_fsai_apply_multi",
     "spmv_mi355x_pcg_tri_multi", "spmv_mi355x_pcg_fsai_multi", "spmv_mi355x_pcg_amg_multi",
     "spmv_mi355x_trsv_solve_multi_device_async", "spmv_mi355x_trsv_solve_multi", "spmv_mi355x_trsv_solve_multi_plan",
@@ -164,6 +165,12 @@ def lib():
             getattr(L, f).argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.spmv_mi355x_amg_apply_multi_plan.restype = C.c_int
         L.spmv_mi355x_amg_apply_multi_plan.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_long), C.POINTER(C.c_long)]
+        L.spmv_mi355x_amg_set_fold.restype = C.c_int
+        L.spmv_mi355x_amg_set_fold.argtypes = [C.c_void_p, C.c_int]
+        L.spmv_mi355x_amg_fold_info.restype = C.c_int
+        L.spmv_mi355x_amg_fold_info.argtypes = [C.c_void_p, C.c_void_p]
+        L.spmv_mi355x_amg_apply_level_device_async.restype = C.c_int
+        L.spmv_mi355x_amg_apply_level_device_async.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         for f in ("spmv_mi355x_pcg_tri_multi", "spmv_mi355x_pcg_trsm_multi"):
             getattr(L, f).restype = C.c_int
             getattr(L, f).argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(TriPrecond), C.c_double, C.c_long,
@@ -1100,6 +1107,13 @@ class AmgUpdateStats(C.Structure):
                 ("update_seconds", C.c_double), ("spgemm_seconds", C.c_double), ("handle_seconds", C.c_double)]
 
 
+class AmgFoldStats(C.Structure):
+    """spmv_mi355x_amg_fold_stats (include/spmv_mi355x.h "AMG: the small levels as one launch")"""
+    _fields_ = [("struct_size", C.c_uint), ("fold_rows", C.c_int), ("first_level", C.c_int), ("folded_levels", C.c_int),
+                ("launches_per_apply", C.c_long), ("spmvs_per_apply", C.c_long), ("tail_products", C.c_long), ("tail_entries", C.c_long),
+                ("lanes_per_row", C.c_int * AMG_MAX_LEVELS), ("bytes", C.c_double)]
+
+
 class Amg:
     """The smoothed-aggregation multilevel preconditioner of a symmetric positive definite matrix (include/spmv_mi355x.h "AMG"),
     built on the GPU: apply(v) is one V(sweeps, sweeps) cycle over handles built in `fmt` with `opts`. `.A` is the borrowed handle of
@@ -1245,6 +1259,45 @@ class Amg:
         passes, launches = C.c_long(0), C.c_long(0)
         _check(lib().spmv_mi355x_amg_apply_multi_plan(self.h, k, C.byref(passes), C.byref(launches)))
         return passes.value, launches.value
+
+    def set_fold(self, rows):
+        """rows > 0: the levels from the first one with at most `rows` rows on run as one launch of one workgroup per apply
+        (spmv_mi355x_amg_set_fold; blocking); 0, the state after creation, turns the fold off"""
+        _check(lib().spmv_mi355x_amg_set_fold(self.h, int(rows)))
+        self.mem_footprint = lib().spmv_mi355x_amg_mem_footprint(self.h)
+
+    @property
+    def fold_rows(self):
+        return self.fold_info()["fold_rows"]
+
+    def fold_info(self):
+        """dict of spmv_mi355x_amg_fold_stats, lanes_per_row cut to `levels` entries; first_level == levels: nothing folds"""
+        s = AmgFoldStats()
+        s.struct_size = C.sizeof(AmgFoldStats)
+        _check(lib().spmv_mi355x_amg_fold_info(self.h, C.byref(s)))
+        out = {k: getattr(s, k) for k, _ in AmgFoldStats._fields_ if k != "struct_size"}
+        out["lanes_per_row"] = list(s.lanes_per_row)[:self.levels]
+        return out
+
+    def apply_level(self, level, v):
+        """cycle(level, v) for a host vector of rows[level] values under the current fold setting (blocking)"""
+        import torch
+        rows = self.info()["rows"]
+        if not 0 <= level < len(rows):
+            raise IndexError(f"level {level} of {len(rows)}")
+        v = np.ascontiguousarray(v, self.dtype)
+        if v.shape != (rows[level],):
+            raise ValueError(f"v must have {rows[level]} values, got {v.shape}")
+        t = torch.from_numpy(v).cuda()
+        u = torch.empty_like(t)
+        self.apply_level_device(level, t.data_ptr(), u.data_ptr())
+        torch.cuda.synchronize()
+        return u.cpu().numpy()
+
+    def apply_level_device(self, level, in_ptr, out_ptr, stream=None):
+        """The same on device pointers (in_ptr == out_ptr: in place), enqueued on `stream` (spmv_mi355x_amg_apply_level_device_async)"""
+        _check(lib().spmv_mi355x_amg_apply_level_device_async(self.h, C.c_int(level), C.c_void_p(in_ptr), C.c_void_p(out_ptr),
+                                                              C.c_void_p(stream or 0)))
 
     def update_values_prepare(self):
         """once, before the first update_values: keeps the SpGEMM plans, the aggregates and the value arrays of every level on the

@@ -31,7 +31,12 @@ beside the unscaled legs. Their spmv, solve and iteration legs run on the scaled
 --update times the other thing a caller with changing values can do: per theta, amg_create on every window (its setup_seconds: the
 yardstick) against amg_update_values_prepare once and amg_update_values_device per window with the values already resident,
 alternating between two value sets; the update's seconds are split into the SpGEMM numeric passes, the handles' blocking
-update_values_device and the rest (amg_update_info). Medians over the windows with their spreads."""
+update_values_device and the rest (amg_update_info). Medians over the windows with their spreads.
+
+--fold-rows 0,1024,8192,65536 times the opt-in fold of the small levels (spmv_mi355x_amg_set_fold): per theta (and per --filtered
+hierarchy) ONE hierarchy, and in every window every fold_rows of the list beside fold_rows = 0, the baseline of the same run: the
+apply (HIP events over --reps applies), the tail alone (apply_level(f) with the fold against apply_level(f) without it, f the leg's
+first folded level) and the whole solve to --tol with its iteration count. set_fold is called outside the timed stretches."""
 import argparse
 import json
 import os
@@ -212,6 +217,81 @@ def run_update(E, torch, workload, dts, args):
     return rows
 
 
+def run_fold(E, torch, workload, dts, args):
+    """--fold-rows: every fold_rows beside fold_rows = 0 on the same hierarchy, window by window (window 0 is dropped)"""
+    if workload.startswith("stencil"):
+        from solver_bench import stencil27
+        rp, ci, va, n = stencil27(int(workload[len("stencil"):]), args.stencil_diag)
+    elif workload.startswith("grid2d"):
+        rp, ci, va, n = grid2d(int(workload[len("grid2d"):]), args.shift)
+    else:
+        raise SystemExit(f"amg_bench.py runs on stencil<N> and grid2d<N>, not on {workload}")
+    rp = np.asarray(rp, np.int32)
+    np_dtype = np.float32 if dts == "f32" else np.float64
+    tdt = torch.float32 if dts == "f32" else torch.float64
+    stream = torch.cuda.current_stream()
+    b = np.random.default_rng(7).uniform(-1, 1, n).astype(np_dtype)
+    xa = (torch.rand(n, device="cuda", dtype=torch.float64) * 2 - 1).to(tdt)
+    ya = torch.empty(n + 64, dtype=tdt, device="cuda")
+    folds = [0] + [f for f in args.fold_rows if f != 0]
+
+    def timed(call):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for _ in range(args.reps):
+            call()
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1) / args.reps
+
+    rows = []
+    for theta in args.theta:
+        for filtered in ((False, True) if args.filtered else (False,)):
+            if filtered:
+                M = E.Amg.build(rp, ci, va, n, None, True, "sell_c_sigma", np_dtype, theta=theta, sweeps=args.sweeps)
+            else:
+                M = E.Amg(rp, ci, va, n, "sell_c_sigma", np_dtype, theta=theta, sweeps=args.sweeps)
+            info = M.info()
+            print(f"# built amg t={theta:g}{' F' if filtered else ''}: levels {info['levels']}, rows {info['rows']}, nnz {info['nnz']}, coarse "
+                  f"{info['coarse']}, launches {info['launches_per_apply']}", flush=True)
+            legs = {f: {k: [] for k in ("apply", "tail", "tail_unfolded", "seconds")} for f in folds}
+            last, fold_info = {}, {}
+            for w in range(args.windows + 1):
+                for f in folds:
+                    M.set_fold(f)
+                    fi = fold_info[f] = M.fold_info()
+                    t_apply = timed(lambda: M.apply_device(xa.data_ptr(), ya.data_ptr(), stream.cuda_stream))
+                    t_tail = t_plain = float("nan")
+                    level = fi["first_level"]
+                    if level < info["levels"]:
+                        t_tail = timed(lambda: M.apply_level_device(level, xa.data_ptr(), ya.data_ptr(), stream.cuda_stream))
+                        M.set_fold(0)
+                        t_plain = timed(lambda: M.apply_level_device(level, xa.data_ptr(), ya.data_ptr(), stream.cuda_stream))
+                        M.set_fold(f)
+                    r = M.A.pcg_tri(b, precond=M, tol=args.tol, max_iterations=args.max_iterations, history=False)
+                    last[f] = r
+                    if w:
+                        for key, t in zip(legs[f], (t_apply, t_tail, t_plain, r["seconds"])):
+                            legs[f][key].append(t)
+                print(f"# fold window {w} done", flush=True)
+            for f in folds:
+                fi, r = fold_info[f], last[f]
+                rec = dict(workload=workload, dtype=dts, leg="fold", theta=theta, filtered=int(filtered), sweeps=args.sweeps, n=int(n),
+                           levels=info["levels"], rows=info["rows"], coarse=info["coarse"], fold_rows=f, first_level=fi["first_level"],
+                           folded_levels=fi["folded_levels"], launches=fi["launches_per_apply"], spmvs=fi["spmvs_per_apply"],
+                           tail_products=fi["tail_products"], tail_entries=fi["tail_entries"], lanes_per_row=fi["lanes_per_row"],
+                           fold_bytes=fi["bytes"], iterations=int(r["iterations"]), stop=int(r["stop"]), windows=args.windows, reps=args.reps)
+                for key, ts in legs[f].items():
+                    if np.isnan(ts).all():
+                        continue
+                    rec[key] = round(float(np.nanmedian(ts)), 5)
+                    rec[key + "_spread"] = [round(float(np.nanmin(ts)), 5), round(float(np.nanmax(ts)), 5)]
+                print(json.dumps(rec), flush=True)
+                rows.append(rec)
+            M.close()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", default=None, help="stencil<N>:f64|f32 or grid2d<N>:f64|f32, comma separated (default stencil160:f64; "
@@ -222,6 +302,8 @@ def main():
     ap.add_argument("--filtered", action="store_true", help="per theta also the hierarchy with filtered prolongator smoothing")
     ap.add_argument("--near-null", action="store_true", help="also S A S of the workload (s = 1 +- 0.5, a fixed seed): per theta the "
                     "default hierarchy on it and the one given near_null = 1 / s")
+    ap.add_argument("--fold-rows", default=None, help="time the opt-in fold instead of the solves: the fold_rows values, comma separated "
+                    "(0, the baseline, always runs beside them)")
     ap.add_argument("--sweeps", type=int, default=1, help="nu of the V(nu, nu) cycle")
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--tol", type=float, default=1e-8, help="the tolerance of the solve leg")
@@ -241,9 +323,21 @@ def main():
         raise SystemExit("amg_bench.py needs a GPU: the engine has no CPU path")
     import spmv_mi355x as E
     rows = []
+    if args.fold_rows is not None:
+        args.fold_rows = [int(v) for v in args.fold_rows.split(",") if v != ""]
     for item in args.runs.split(","):
         w, dts = item.split(":")[:2]
-        rows += (run_update if args.update else run)(E, torch, w, dts, args)
+        rows += (run_fold if args.fold_rows is not None else run_update if args.update else run)(E, torch, w, dts, args)
+    if args.fold_rows is not None:
+        nan = float("nan")
+        print(f"{'workload':11s} {'theta':>6s} {'F':>1s} {'fold_rows':>9s} {'first':>5s} {'launches':>8s} {'apply ms':>9s} {'spread':>19s} "
+              f"{'tail ms':>8s} {'unfolded':>8s} {'tail entries':>12s} {'iters':>6s} {'solve s':>8s} {'spread':>19s}")
+        for r in rows:
+            print(f"{r['workload']:11s} {r['theta']:6g} {r['filtered']:1d} {r['fold_rows']:9d} {r['first_level']:5d} {r['launches']:8d} "
+                  f"{r['apply']:9.4f} {r['apply_spread'][0]:9.4f} ..{r['apply_spread'][1]:8.4f} {r.get('tail', nan):8.4f} "
+                  f"{r.get('tail_unfolded', nan):8.4f} {r['tail_entries']:12d} {r['iterations']:6d} {r['seconds']:8.4f} "
+                  f"{r['seconds_spread'][0]:9.4f} ..{r['seconds_spread'][1]:8.4f}")
+        return
     if args.update:
         print(f"{'workload':11s} {'dtype':5s} {'theta':>6s} {'levels':>6s} {'create s':>9s} {'spread':>19s} {'prepare s':>9s} {'update s':>9s} "
               f"{'spread':>19s} {'spgemm':>8s} {'handles':>8s} {'rest':>8s} {'create / update':>15s} {'kept / footprint':>16s}")

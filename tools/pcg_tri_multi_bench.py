@@ -2,6 +2,7 @@
 (Matrix.pcg_tri) on the same handles in the same run, and the same for the AMG cycle alone (Amg.apply_multi_device against k calls of
 Amg.apply_device). Follows tools/amg_bench.py: one sell_c_sigma handle of A, and for every preconditioner
     none | jacobi = (None, 1 / diag(A), None) | fsai = Fsai on tril(A) | amg t=<theta> = Amg with every theta of --theta
+(--fold-rows adds, per theta, a hierarchy per value whose small levels run as one launch: "amg t=<theta> fold=<rows>")
 (--precond picks among them; sgs, not in the default list, adds the global SGS of A, sgs_precond, and with --block-rows a blocked
 SGS per size: their k-column solves go through Matrix.pcg_trsm_multi and the k-column triangular solve)
 and every k of --rhs, in one process, alternating window by window (window 0 warms every leg up and is dropped):
@@ -66,11 +67,14 @@ def run(E, torch, workload, dts, args):
                   flush=True)
     if "fsai" in args.precond:
         variants.append(("fsai", E.Fsai(rp, ci, va, n, None, "sell_c_sigma", np_dtype)))
-    for theta in args.theta if "amg" in args.precond else ():
-        variants.append((f"amg t={theta:g}", E.Amg(rp, ci, va, n, "sell_c_sigma", np_dtype, theta=theta, sweeps=args.sweeps)))
+    # per theta the hierarchy as it is created (fold off), then one of its own per --fold-rows value with the small levels folded
+    for theta, fold in [(t, f) for t in args.theta for f in [0] + args.fold_rows] if "amg" in args.precond else ():
+        variants.append((f"amg t={theta:g}" + (f" fold={fold}" if fold else ""),
+                         E.Amg(rp, ci, va, n, "sell_c_sigma", np_dtype, theta=theta, sweeps=args.sweeps)))
+        variants[-1][1].set_fold(fold)
         info = variants[-1][1].info()
-        print(f"# built {variants[-1][0]}: rows {info['rows']}, coarse {info['coarse']}, spmvs {info['spmvs_per_apply']}, "
-              f"launches {info['launches_per_apply']}", flush=True)
+        print(f"# built {variants[-1][0]}: rows {info['rows']}, coarse {info['coarse']}, first folded level "
+              f"{variants[-1][1].fold_info()['first_level']}, spmvs {info['spmvs_per_apply']}, launches {info['launches_per_apply']}", flush=True)
     stream = torch.cuda.current_stream()
     xs = [(torch.rand(n, device="cuda", dtype=torch.float64) * 2 - 1).to(tdt) for _ in range(kmax)]
     ys = [torch.empty(n, dtype=tdt, device="cuda") for _ in range(kmax)]
@@ -150,6 +154,8 @@ def main():
                     "SGS of A through Matrix.pcg_trsm_multi")
     ap.add_argument("--block-rows", default="", help="with --precond sgs: a blocked SGS per size beside the global one, e.g. 4096")
     ap.add_argument("--theta", default="0.08,0.03", help="the strength thresholds of the AMG variants")
+    ap.add_argument("--fold-rows", default="", help="per theta also a hierarchy with the small levels folded into one launch "
+                    "(Amg.set_fold) per value, e.g. 1024,8192, beside the unfolded one")
     ap.add_argument("--sweeps", type=int, default=1, help="nu of the V(nu, nu) cycle")
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--tol", type=float, default=1e-8, help="the tolerance of the solves")
@@ -166,6 +172,7 @@ def main():
     if set(args.precond) - {"none", "jacobi", "sgs", "fsai", "amg"}:
         ap.error("--precond: a comma separated list of none, jacobi, sgs, fsai, amg")
     args.block_rows = [int(v) for v in args.block_rows.split(",") if v != ""]
+    args.fold_rows = [int(v) for v in args.fold_rows.split(",") if v not in ("", "0")]
     os.environ.setdefault("OMP_NUM_THREADS", "16")
     import torch
     if not torch.cuda.is_available():
